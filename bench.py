@@ -5,19 +5,27 @@ A "step" is one pass of the hot path — INTEGRATE_t(0, 10 s) (tot.f:2812) — o
 100 000 cells per GPU (BASELINE.json configs[2]; mistra_amd/workload.py builds it from captured reference states,
 directly in HBM).  `value` = cells integrated by all ranks / wall time, inputs resident before the clock starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--cells-per-gpu C] [--mech tot]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--cells-per-gpu C] [--mech tot] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started plainly with --gpus N > 1 (no WORLD_SIZE in the environment), this process starts that torch.distributed.run
 command itself as a child — before it has touched the GPU — relays rank 0's JSON line and exits with the child's code.
 
 Cells are independent, so ranks share nothing on the data path (no collective inside the timed region; weak scaling).
-The data path BASELINE.json's north_star names for a single-process caller — base states broadcast from rank 0, every rank
-integrating its shard, results gathered to rank 0 — is timed as a second leg at N > 1 and reported beside the headline
-value (`config.root_io_path`), never as `value`.
-Rank 0 at N=1 also times the CPU path on the host cores on a bounded sample of the same workload (`cpu_baseline`):
-the compiled reference itself (oracle/_ref/libmistra_ref.so, kind "reference") when it was built, else the plain-C
-restatement (oracle/kpp_ros3.c, kind "port").  The oracle is only ever the thing compared against / timed beside.
+
+A plain run sets up, warms up, times K steps and prints the result line (`ms_per_step` = wall milliseconds of one timed step;
+`roofline` comes from the same timed steps).  Everything that needs runs of its own is behind --full (off by default):
+  * the data path BASELINE.json's north_star names for a single-process caller — base states broadcast from rank 0, every rank
+    integrating its shard, results gathered to rank 0 — timed as a second leg at N > 1 (`config.root_io_path`), never as `value`;
+  * at N = 1, the CPU path on the host cores on a bounded sample of the same workload (`cpu_baseline`): the compiled reference
+    itself (oracle/_ref/libmistra_ref.so, kind "reference") when it was built, else the plain-C restatement (oracle/kpp_ros3.c,
+    kind "port"), and the parity sample of the timed batch against that CPU checker (`parity`);
+  * at N = 1 with tot, the aer and gas mechanisms on the same GPU (`extra`).
+The oracle is only ever the thing compared against / timed beside.  Without --full the line has no `cpu_baseline` and the others are null.
+
+--dump-outputs DIR writes what the last timed step returned to its caller — VAR_out, IERR and /Statistics/ — for a fixed,
+seeded sample of cells as DIR/<name>.npy (float64; at most 48 MiB), so two builds can be compared output for output: the
+inputs depend only on the arguments.  Rank r > 0 of a multi-GPU run writes its own shard's sample as <name>_rank<r>.npy.
 """
 import argparse
 import json
@@ -262,16 +270,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cells-per-gpu", type=int, default=100000)
     ap.add_argument("--mech", default="tot", choices=["gas", "aer", "tot"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what needs runs of its own: CPU baseline, parity sample, aer / gas legs (N = 1), root-I/O leg (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write a fixed, seeded sample of the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N>1 (nccl = RCCL; gloo only for rehearsing the rank logic)")
     ap.add_argument("--dump-root-io", default=None,
-                    help="tests only: rank 0 writes what the root-I/O leg gathered (VAR_out, ierr, stats of all shards) to this .npz")
-    ap.add_argument("--no-parity", action="store_true", help="skip the post-run parity sample against the CPU checker")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary aer / gas legs of the default (tot, one GPU) run")
+                    help="tests only, with --full: rank 0 writes what the root-I/O leg gathered (VAR_out, ierr, stats of all shards) to this .npz")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the post-run parity sample against the CPU checker")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary aer / gas legs of the (tot, one GPU) run")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank uses cuda:0 (requires --backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))          # nothing in this process has touched the GPU yet
@@ -281,9 +297,9 @@ def main():
     args.gpus = world
 
     cpu, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.mech)          # before any GPU initialisation in this process (forks workers)
-    if rank == 0 and world == 1 and not args.no_parity:
+    if rank == 0 and world == 1 and args.full and not args.no_parity:
         parity = ParityChecker(args.mech)      # idle worker processes, forked before any GPU initialisation
 
     import torch
@@ -339,8 +355,9 @@ class GpuEngine:
 
 def rank_body(args, rank, world, dev, engine, parity=None):
     """What one rank does (the process group, if any, is up): build its shard in place, warm up, time `steps` passes between
-    barrier + synchronize on both sides, reduce (max of the time, sums of the counters), run the root-I/O leg; returns the
-    JSON line on rank 0.  `engine` is the product (GpuEngine); tests/test_partition_gloo.py drives this same function on two
+    barrier + synchronize on both sides, reduce (max of the time, sums of the counters), write the outputs' sample if
+    --dump-outputs asks, and with --full run the root-I/O leg, the parity check and the secondary legs; returns the JSON
+    line on rank 0.  `engine` is the product (GpuEngine); tests/test_partition_gloo.py drives this same function on two
     CPU ranks with a stand-in engine."""
     import torch
     import torch.distributed as dist
@@ -381,13 +398,16 @@ def rank_body(args, rank, world, dev, engine, parity=None):
         dist.all_reduce(agg, op=dist.ReduceOp.SUM)
     elapsed = float(t_el.item())
     nstp_total, nfail, cells_done = (float(x) for x in agg.tolist())
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, "" if world == 1 else "_rank%d" % rank, start, out, ierr, stats)
 
-    root_io = root_io_leg(args, dist, dev, world, rank, engine, make_batch, shard)
+    full = getattr(args, "full", False)
+    root_io = root_io_leg(args, dist, dev, world, rank, engine, make_batch, shard) if full else None
     if rank != 0:
         return None
     parity_line = parity.check(var, fix, rconst, out, stats) if parity is not None else None      # outside the timed region
     extra = None
-    if world == 1 and args.mech == "tot" and not getattr(args, "no_extra", False):
+    if full and world == 1 and args.mech == "tot" and not getattr(args, "no_extra", False):
         del var, fix, rconst, out
         extra = {m: secondary_leg(m, args.cells_per_gpu, dev, engine, make_batch) for m in ("aer", "gas")}
     value = total_cells * args.steps / elapsed
@@ -422,6 +442,29 @@ def rank_body(args, rank, world, dev, engine, parity=None):
                      "fp64_tflops": flops / 1e12, "fp64_frac_of_vector_peak": flops / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
                      "flop_per_internal_step": flop_per_step(args.mech)},
     }
+
+
+DUMP_BYTES = 48 << 20          # --dump-outputs: at most this many bytes of samples (headers aside)
+DUMP_SEED = 20260102
+
+
+def dump_outputs(outdir, suffix, start, out, ierr, stats):
+    """What the last timed step returned to its caller, for a fixed, seeded sample of this rank's cells (sorted, without
+    repetition; every cell when they fit): var_out [k, NVAR], ierr [k], stats [k, 8] as float64, and `cells` [k], the cells'
+    global indices in the synthetic workload."""
+    import numpy as np
+    import torch
+    ncell, nvar = out.shape
+    k = min(ncell, DUMP_BYTES // (8 * (nvar + 1 + stats.shape[1] + 1)))
+    if k == ncell:
+        idx = np.arange(ncell, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(ncell, size=k, replace=False))
+    sel = torch.as_tensor(idx, device=out.device)
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"var_out": out[sel], "ierr": ierr[sel], "stats": stats[sel], "cells": sel + start}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + suffix + ".npy"), a.cpu().numpy().astype(np.float64))
 
 
 def secondary_leg(mech, ncell, dev, engine, make_batch, passes=2):

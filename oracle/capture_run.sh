@@ -15,6 +15,7 @@ rm -rf "$RUN/out"; mkdir -p "$RUN/out"
 sed -e 's/^\( *netcdf *= *\)T/\1F/' -e 's/^\( *chem *= *\)F/\1T/' -e "s/^\( *lstmax *= *\)[0-9]*/\1$HOURS/" \
     -e "${MISTRA_NAMELIST_SED:-s/^$//}" "$REFROOT/namelists/namelist.$CASE" > "$RUN/namelist"
 cd "$RUN"
-env INPDIR="$REFROOT/input/" MECHDIR="$REFROOT/src/mech/" OUTDIR="$RUN/out/" NAMELIST="$RUN/namelist" \
+# OUTDIR and NAMELIST relative to the run dir: the model keeps them in CHARACTER(len=100) (config.f90) and cuts longer values
+env INPDIR="$REFROOT/input/" MECHDIR="$REFROOT/src/mech/" OUTDIR="out/" NAMELIST="namelist" \
     MISTRA_CAPTURE_FILE="$HERE/_ref/capture_${CASE}${MISTRA_RUN_TAG:-}.bin" "$@" "${MISTRA_MODEL_BIN:-$HERE/_ref/mistra_capture}" > "$RUN/stdout.log" 2> "$RUN/stderr.log"
 tail -4 "$RUN/stderr.log"

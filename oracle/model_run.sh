@@ -12,7 +12,11 @@ IN="${MISTRA_MODEL_INPUTS:-$HERE/_ref/model_inputs}"
 [ -f "$IN/namelists/namelist.$CASE" ] || { echo "no staged namelist for $CASE under $IN (oracle/build_gpu_model.sh stages them)" >&2; exit 1; }
 rm -rf "$RUN"; mkdir -p "$RUN/out"
 sed -e 's/^\( *netcdf *= *\)T/\1F/' -e 's/^\( *chem *= *\)F/\1T/' "$IN/namelists/namelist.$CASE" > "$RUN/namelist"
+# The model keeps INPDIR, OUTDIR, MECHDIR and NAMELIST in CHARACTER(len=100) (config.f90) and cuts longer values: it is handed paths
+# relative to the run dir (the inputs through a link), whatever the length of the run dir's or the inputs' absolute path.
+ln -s "$(cd "$IN" && pwd)" "$RUN/in"
 cd "$RUN"
-env INPDIR="$IN/input/" MECHDIR="$IN/mech/" OUTDIR="$RUN/out/" NAMELIST="$RUN/namelist" MISTRA_COLUMN_MINUTES="$MINUTES" "$@" "$BIN" > "$RUN/stdout.log" 2> "$RUN/stderr.log" \
+env INPDIR="in/input/" MECHDIR="in/mech/" OUTDIR="out/" NAMELIST="namelist" MISTRA_COLUMN_MINUTES="$MINUTES" "$@" "$BIN" > "$RUN/stdout.log" 2> "$RUN/stderr.log" \
   || { echo "model failed:"; tail -5 "$RUN/stderr.log"; exit 1; }
-grep -a "chemistry stem" "$RUN/stderr.log" | tail -1
+# a Fortran STOP (the model's abort) ends the process with status 0: the time loop's closing line is the proof it ran
+grep -a "chemistry stem" "$RUN/stderr.log" | tail -1 | grep . || { echo "model stopped before the end of its time loop:"; tail -5 "$RUN/stderr.log"; exit 1; }

@@ -77,7 +77,7 @@ def test_two_ranks_share_the_gpu_union_matches_single_rank(chem, tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device",
-           "--cells-per-gpu", str(cells), "--steps", "1", "--warmup", "0", "--mech", "tot", "--dump-root-io", str(dump)]
+           "--cells-per-gpu", str(cells), "--steps", "1", "--warmup", "0", "--mech", "tot", "--full", "--dump-root-io", str(dump)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

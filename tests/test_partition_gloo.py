@@ -94,7 +94,7 @@ def _bench_rank_main(rank, world, port, q):
     import argparse
     import bench
     args = argparse.Namespace(gpus=world, steps=2, warmup=1, cells_per_gpu=9, mech="gas", backend="gloo", share_device=False,
-                              no_cpu_baseline=True)
+                              no_cpu_baseline=True, full=True)
     line = bench.rank_body(args, rank, world, torch.device("cpu"), _OracleEngine())
     if rank == 0:
         q.put(line)
@@ -123,6 +123,49 @@ def test_bench_rank_logic_on_two_gloo_ranks():
     assert io["cells_ok_at_root"] == 18 and io["value"] > 0          # every shard's results arrived at rank 0
     for key in ("roofline",):
         assert key in line
+
+
+class _CountingEngine(_OracleEngine):
+    def __init__(self):
+        super().__init__()
+        self.calls = 0
+
+    def integrate_into(self, *a):
+        self.calls += 1
+        super().integrate_into(*a)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path, monkeypatch):
+    """A plain one-rank run (no --full): warm-up + exactly `steps` timed steps, nothing beside them, and --dump-outputs writes
+    what the last step returned for a fixed, seeded sample of cells, as float64."""
+    import argparse
+    import bench
+    from mistra_amd.workload import make_batch
+    from oracle.oracle import Oracle
+    ncell = 7
+    var, fix, rconst = make_batch("gas", 0, ncell, "cpu")
+    want, ierr, st = Oracle("gas").integrate_batch(var.numpy(), fix.numpy(), rconst.numpy())
+
+    def run(outdir):
+        engine = _CountingEngine()
+        args = argparse.Namespace(gpus=1, steps=3, warmup=2, cells_per_gpu=ncell, mech="gas", backend="gloo", share_device=False,
+                                  full=False, dump_outputs=str(outdir))
+        line = bench.rank_body(args, 0, 1, torch.device("cpu"), engine)
+        assert engine.calls == 5
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+        assert line["parity"] is None and line["extra"] is None and line["config"]["root_io_path"] is None
+        got = {n: np.load(os.path.join(outdir, n + ".npy")) for n in ("var_out", "ierr", "stats", "cells")}
+        assert all(a.dtype == np.float64 for a in got.values())
+        return got
+
+    got = run(tmp_path / "all")          # every cell fits
+    assert np.array_equal(got["cells"], np.arange(ncell)) and np.array_equal(got["var_out"], want)
+    assert np.array_equal(got["ierr"], ierr) and np.array_equal(got["stats"], st)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 8 * (102 + 1 + 8 + 1))      # room for 4 of the 7 cells
+    a, b = run(tmp_path / "a"), run(tmp_path / "b")
+    c = a["cells"].astype(np.int64)
+    assert len(c) == 4 and np.all(np.diff(c) > 0) and np.array_equal(a["cells"], b["cells"])
+    assert np.array_equal(a["var_out"], want[c]) and np.array_equal(a["stats"], st[c]) and np.array_equal(a["var_out"], b["var_out"])
 
 
 def test_bench_self_launch_command(monkeypatch):

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-echo "== bench (tot, with cpu baseline)"; timeout -k 10 400 python3 $R/bench.py > $OUT/${TAG}_bench_tot_1gpu.json 2> $OUT/bench_tot.err
+echo "== bench (tot, with cpu baseline)"; timeout -k 10 400 python3 $R/bench.py --full > $OUT/${TAG}_bench_tot_1gpu.json 2> $OUT/bench_tot.err
 for m in gas aer; do
   echo "== bench $m"; timeout -k 10 200 python3 $R/bench.py --mech $m --no-cpu-baseline --no-parity --no-extra > $OUT/${TAG}_bench_${m}_1gpu.json 2> $OUT/bench_$m.err
 done
