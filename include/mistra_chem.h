@@ -202,7 +202,10 @@ int mistra_chem_drive(int mech, int nlayer, const int32_t* layer, int n, double*
  * idle behind any one mechanism — a step then lasts as long as its slowest cell, not as the three mechanisms' slowest cells in a row (BTZ96: 14.4 -> 8.4 ms,
  * INTEGRATION.md §4d).  mistra_chem_drive_begin takes mistra_chem_drive's arguments, gathers the layers, and returns once the copies and kernels are
  * enqueued on the mechanism's private stream; mistra_chem_drive_end(mech) waits for them and scatters the results into the arrays given to begin.  Between
- * the two the caller must not touch those arrays' rows (nor ierr, stats, t_h, c_packed); one step per mechanism may be open at a time.
+ * the two the caller must not touch those arrays' rows (nor ierr, stats, t_h, c_packed).  One step per mechanism may be open at a time: while it is,
+ * the host-buffer calls of that mechanism fail — mistra_chem_drive(_begin), mistra_chem_integrate(_ex, _env_ex), mistra_chem_update_rconst,
+ * mistra_chem_integrate_common(_status), mistra_chem_set_species_maps, mistra_chem_singular_rows, mistra_chem_debug_first_step — until
+ * mistra_chem_drive_end has fetched it; the *_device calls, the liq_parm calls and the other mechanisms are not affected.
  * shim/mistra_kpp_drive.f90: KPP_DRIVE_RUN issues all mechanisms, then fetches them in mechanism order. */
 int mistra_chem_drive_begin(int mech, int nlayer, const int32_t* layer, int n, double* s1, double* s3, double* sl1, double* sion1, const double* scal,
                       const double* env, double tin, double dt, int32_t* ierr, int32_t* stats, double* t_h, double* bg, int nrxn,

@@ -36,9 +36,20 @@ int fail(const std::string& msg) {
     hipError_t e_ = (expr);                                                                              \
     if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));               \
   } while (0)
+#define LAUNCH_TRY(expr)                                                                                 \
+  do {                                                                                                   \
+    hipError_t e_ = (expr);                                                                              \
+    if (e_ != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e_));          \
+  } while (0)
 
 const char* kMechName[3] = {"gas", "aer", "tot"};
-const int kDims[3][4] = {{102, 3, 331, 1110}, {257, 5, 979, 6579}, {417, 7, 1627, 13503}};
+// the sizes of gas_Parameters.h | aer_Parameters.h | tot_Parameters.h, as the kernel is compiled for them (mistra_chem_dims needs no init)
+struct MechDims {
+  int nvar, nfix, nreact, lu_nonzero;
+};
+template <class MT>
+constexpr MechDims dims_of() { return MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}; }
+constexpr MechDims kDims[3] = {dims_of<GasTraits>(), dims_of<AerTraits>(), dims_of<TotTraits>()};
 
 template <class T>
 struct DevBuf {
@@ -258,108 +269,263 @@ struct GsBufs {
   void release() { wave_base.release(); recs.release(); rows.release(); }
 };
 
-struct MechState {
-  bool ready = false;
-  int nt = 0, n_temps = 0;
-  MechTables tab;
-  std::string text;
+// ---- the per-mechanism device tables, one group per kernel-argument block: upload, release, `ready`, and the one place its block is built
+
+struct KernelBufs {      // the integrator's (ros3_kernel.hip; make_args)
+  int n_temps = 0, lu_scale_slots = 0;
   DevBuf<double> consts;
   DevBuf<uint64_t> fun_fac, jac_fac;
-  DevBuf<uint16_t> jvs_pos, zero_pos, diag_pos;
+  DevBuf<uint16_t> jvs_pos, zero_pos, diag_pos, schur_cells;
   GsBufs vdot, jvs;
   VmBufs lu, solve_head_fwd, solve_head_bwd;
-  DevBuf<uint32_t> tail_fwd, tail_bwd, lu_scale;
-  DevBuf<uint32_t> dense_rows;
-  DevBuf<uint16_t> schur_cells;
-  // Update_RCONST_x on the device (rates.hip): present for the mechanisms whose table and rate-law functions exist
-  bool rates_ready = false;
-  int rates_nenv = 0;
-  DevBuf<double> rates_consts, s_env;
-  DevBuf<int32_t> rates_offs, rates_words, rates_fslot;
-  int lu_scale_slots = 0;
-  // the hand-over halves of x_drive on the device (pack.hip): tables of the mechanism + the model's species maps
-  bool pack_ready = false, maps_ready = false;
-  PackTable pack_tab;
-  DevBuf<int32_t> pk_pack, pk_fix, pk_unpack, pk_slot_id, pk_slot_first, pk_terms, pk_words, pk_acc, pk_envc, pk_aptr, pk_afac;
-  DevBuf<int32_t> map_gas_m2k, map_gas_k2m, map_rad_m2k, map_rad_k2m;
-  int map_j1 = 0, map_j5 = 0;
-  DevBuf<double> d_env, d_rct;      // scratch of mistra_chem_drive_device (grow-only)
-  // mistra_chem_drive (host buffers): ONE device block and ONE pinned host mirror hold everything that crosses PCIe for a batch of layers
-  // (model slabs, scal, env, budgets in; slabs, budgets, exit data out), a private stream carries the two copies and the kernel chain
-  double* drv_dev = nullptr;
-  double* drv_host = nullptr;
-  size_t drv_cap = 0;               // doubles
-  hipStream_t drv_stream = nullptr;
-  struct PendingDrive {             // a column step issued by mistra_chem_drive_begin and not yet fetched by mistra_chem_drive_end
-    bool active = false;
-    std::vector<int32_t> layer, level;
-    double *s1 = nullptr, *s3 = nullptr, *sl1 = nullptr, *sion1 = nullptr, *bg = nullptr, *bgs = nullptr, *t_h = nullptr, *c_packed = nullptr;
-    int32_t *ierr = nullptr, *stats = nullptr;
-    int nrxn = 0;
-    size_t o_s1 = 0, o_s3 = 0, o_sl1 = 0, o_si = 0, o_bg = 0, o_bgs = 0, o_th = 0, o_hl = 0, o_int = 0, o_cp = 0;
-  } pend;
-  // fast_k_mt_a / fast_k_mt_t (aer, tot): the exchanged species and the size-axis limits of the last call
-  bool kmt_ready = false;
-  KmtTable kmt_tab;
-  DevBuf<int32_t> kmt_lex;
-  // henry_x / equil_co_x (aer, tot)
-  bool liq_ready = false;
-  LiqTable liq_tab;
-  DevBuf<int32_t> lq_hkind, lq_eof, lq_foff, lq_boff, lq_fkind, lq_farg;
-  DevBuf<double> lq_ha0, lq_hb0, lq_fa, lq_fb;
-  // st_coeff_x (aer, tot): one table per setting of the two namelist switches
-  bool stc_ready = false;
-  StcoeffTable stc_tab;
-  DevBuf<double> stc_consts[4];
-  DevBuf<int32_t> stc_offs[4], stc_words[4];
-  // v_mean_x (aer, tot)
-  bool vmean_ready = false;
-  VmeanTable vmean_tab;
-  DevBuf<double> vm_mass;
-  // staging for the host-buffer entry point (grow-only)
-  DevBuf<double> s_var, s_fix, s_rct, s_out, s_th;
+  DevBuf<uint32_t> tail_fwd, tail_bwd, lu_scale, dense_rows;
+  int upload(const MechTables& t, const KernelSchedule& K) {
+    n_temps = K.n_temps;
+    lu_scale_slots = K.lu_scale.nslots;
+    HIP_TRY(consts.upload(t.consts));
+    HIP_TRY(fun_fac.upload(K.fun_fac));
+    HIP_TRY(jac_fac.upload(K.jac_fac));
+    HIP_TRY(jvs_pos.upload(K.jvs_pos));
+    HIP_TRY(zero_pos.upload(K.zero_pos));
+    HIP_TRY(diag_pos.upload(K.diag_pos));
+    HIP_TRY(vdot.upload(K.vdot));
+    HIP_TRY(jvs.upload(K.jvs));
+    HIP_TRY(lu.upload(K.lu));
+    HIP_TRY(solve_head_fwd.upload(K.solve_head_fwd));
+    HIP_TRY(solve_head_bwd.upload(K.solve_head_bwd));
+    HIP_TRY(tail_fwd.upload(K.tail.fwd));
+    HIP_TRY(tail_bwd.upload(K.tail.bwd));
+    HIP_TRY(lu_scale.upload(K.lu_scale.recs));
+    HIP_TRY(dense_rows.upload(K.dense.row_info));
+    HIP_TRY(schur_cells.upload(K.dense.schur_cells));
+    return 0;
+  }
+  void release() {
+    consts.release(); fun_fac.release(); jac_fac.release(); jvs_pos.release(); zero_pos.release(); diag_pos.release(); schur_cells.release();
+    vdot.release(); jvs.release(); lu.release(); solve_head_fwd.release(); solve_head_bwd.release();
+    tail_fwd.release(); tail_bwd.release(); lu_scale.release(); dense_rows.release();
+  }
+};
+
+struct RatesBufs {       // Update_RCONST_x on the device (rates.hip): the mechanisms whose table and rate-law functions exist
+  bool ready = false;
+  int nreact = 0, nenv = 0;
+  DevBuf<double> consts;
+  DevBuf<int32_t> offs, words, fslot;
+  int upload(const RatesTable& T) {
+    HIP_TRY(consts.upload(T.consts));
+    HIP_TRY(offs.upload(T.offs));
+    HIP_TRY(words.upload(T.words));
+    HIP_TRY(fslot.upload(T.fslot));
+    nreact = T.nreact; nenv = T.nenv;
+    ready = true;
+    return 0;
+  }
+  RatesDev dev() const { return RatesDev{consts.p, offs.p, words.p, fslot.p, nreact, nenv}; }
+  void release() { consts.release(); offs.release(); words.release(); fslot.release(); ready = false; }
+};
+
+struct PackBufs {        // the hand-over halves of x_drive (pack.hip): tables of the mechanism + the model's species maps
+  bool ready = false, maps_ready = false;
+  PackTable tab;
+  DevBuf<int32_t> pack, fix, unpack, slot_id, slot_first, terms, words, acc, envc, a_ptr, a_fac;
+  DevBuf<int32_t> gas_m2k, gas_k2m, rad_m2k, rad_k2m;
+  int j1 = 0, j5 = 0;
+  int upload(const MechTables& t) {      // (tab: loaded and checked by setup_mech)
+    HIP_TRY(pack.upload(tab.pack)); HIP_TRY(fix.upload(tab.fix)); HIP_TRY(unpack.upload(tab.unpack));
+    HIP_TRY(slot_id.upload(tab.slot_id)); HIP_TRY(slot_first.upload(tab.slot_first)); HIP_TRY(terms.upload(tab.terms));
+    HIP_TRY(words.upload(tab.term_words)); HIP_TRY(acc.upload(tab.acc)); HIP_TRY(envc.upload(tab.envc));
+    HIP_TRY(a_ptr.upload(t.a_ptr)); HIP_TRY(a_fac.upload(t.a_fac));
+    ready = true;
+    return 0;
+  }
+  int set_maps(int n1, const int32_t* g_m2k, const int32_t* g_k2m, int n5, const int32_t* r_m2k, const int32_t* r_k2m) {
+    HIP_TRY(gas_m2k.upload(std::vector<int32_t>(g_m2k, g_m2k + 2 * (size_t)n1)));
+    HIP_TRY(gas_k2m.upload(std::vector<int32_t>(g_k2m, g_k2m + (size_t)n1)));
+    HIP_TRY(rad_m2k.upload(std::vector<int32_t>(r_m2k, r_m2k + 2 * (size_t)n5)));
+    HIP_TRY(rad_k2m.upload(std::vector<int32_t>(r_k2m, r_k2m + (size_t)n5)));
+    j1 = n1; j5 = n5;
+    maps_ready = true;
+    return 0;
+  }
+  PackDev dev(int nreact, const double* consts) const {
+    const PackTable& T = tab;
+    return PackDev{pack.p, fix.p, unpack.p, slot_id.p, slot_first.p, terms.p, words.p, acc.p, envc.p,
+                   T.n_pack(), T.n_fix(), T.n_unpack(), T.n_slots(), (int)T.terms.size() / 3, (int)T.term_words.size(), (int)T.acc.size() / 2, T.n_envc(),
+                   T.nvar, T.nfix, nreact, T.j2, T.j6, T.nkc, T.preclamp, gas_m2k.p, gas_k2m.p, rad_m2k.p, rad_k2m.p, j1, j5, a_ptr.p, a_fac.p, consts};
+  }
+  void release() {
+    pack.release(); fix.release(); unpack.release(); slot_id.release(); slot_first.release(); terms.release(); words.release(); acc.release();
+    envc.release(); a_ptr.release(); a_fac.release(); gas_m2k.release(); gas_k2m.release(); rad_m2k.release(); rad_k2m.release();
+    ready = maps_ready = false;
+  }
+};
+
+struct KmtBufs {         // fast_k_mt_a / fast_k_mt_t (aer, tot): the exchanged species
+  bool ready = false;
+  KmtTable tab;
+  DevBuf<int32_t> lex;
+  int upload() {
+    HIP_TRY(lex.upload(tab.lex));
+    ready = true;
+    return 0;
+  }
+  KmtDev dev(int nspec, int ka, int ifeed, int nkc_l) const { return KmtDev{lex.p, {0}, tab.nx, tab.nka, tab.nkt, tab.nkc, nspec, ka, ifeed, nkc_l}; }
+  void release() { lex.release(); ready = false; }
+};
+
+struct LiqBufs {         // henry_x / equil_co_x (aer, tot)
+  bool ready = false;
+  LiqTable tab;
+  DevBuf<int32_t> h_kind, e_of, foff, boff, fkind, farg;
+  DevBuf<double> h_a0, h_b0, fa, fb;
+  int upload() {
+    HIP_TRY(h_kind.upload(tab.h_kind)); HIP_TRY(e_of.upload(tab.e_of)); HIP_TRY(foff.upload(tab.foff)); HIP_TRY(boff.upload(tab.boff));
+    HIP_TRY(fkind.upload(tab.fkind)); HIP_TRY(farg.upload(tab.farg)); HIP_TRY(h_a0.upload(tab.h_a0)); HIP_TRY(h_b0.upload(tab.h_b0));
+    HIP_TRY(fa.upload(tab.fa)); HIP_TRY(fb.upload(tab.fb));
+    ready = true;
+    return 0;
+  }
+  LiqDev dev() const {
+    return LiqDev{h_kind.p, e_of.p, foff.p, boff.p, fkind.p, farg.p, h_a0.p, h_b0.p, fa.p, fb.p, tab.nspec, tab.nkc_eq, tab.henry_tref, tab.henry_fct, tab.equil_tref};
+  }
+  void release() {
+    h_kind.release(); e_of.release(); foff.release(); boff.release(); fkind.release(); farg.release(); h_a0.release(); h_b0.release();
+    fa.release(); fb.release(); ready = false;
+  }
+};
+
+struct StcBufs {         // st_coeff_x (aer, tot): one table per setting of the two namelist switches
+  bool ready = false;
+  StcoeffTable tab;
+  DevBuf<double> consts[4];
+  DevBuf<int32_t> offs[4], words[4];
+  int upload() {
+    for (int i = 0; i < 4; i++) {
+      HIP_TRY(consts[i].upload(tab.v[i].consts)); HIP_TRY(offs[i].upload(tab.v[i].offs)); HIP_TRY(words[i].upload(tab.v[i].words));
+    }
+    ready = true;
+    return 0;
+  }
+  RatesDev dev(int v) const { return RatesDev{consts[v].p, offs[v].p, words[v].p, nullptr, tab.v[v].nreact, tab.v[v].nenv}; }
+  void release() {
+    for (int i = 0; i < 4; i++) { consts[i].release(); offs[i].release(); words[i].release(); }
+    ready = false;
+  }
+};
+
+struct VmeanBufs {       // v_mean_x (aer, tot)
+  bool ready = false;
+  VmeanTable tab;
+  DevBuf<double> mass;
+  int upload() {
+    HIP_TRY(mass.upload(tab.mass));
+    ready = true;
+    return 0;
+  }
+  void release() { mass.release(); ready = false; }
+};
+
+// the groups an entry needs (require)
+enum : unsigned { kNeedRates = 1, kNeedPackTable = 2, kNeedMaps = 4, kNeedPack = kNeedPackTable | kNeedMaps, kNeedKmt = 8, kNeedLiq = 16, kNeedStc = 32, kNeedVmean = 64 };
+
+// ---- staging of the host-buffer entries
+
+// A grow-only device block, a pinned host mirror of the same layout and a private non-blocking stream.  Freed by release() only: the
+// instances are globals, and a destructor would run after the HIP runtime may be gone.
+struct Staging {
+  char *dev = nullptr, *host = nullptr;
+  size_t cap = 0;      // bytes
+  hipStream_t st = nullptr;
+  hipError_t ensure(size_t bytes) {
+    if (!st)
+      if (hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) return e;
+    if (bytes <= cap) return hipSuccess;
+    free_blocks();
+    const size_t want = bytes + bytes / 2;
+    if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), want)) return e;
+    if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&host), want, hipHostMallocDefault)) return e;
+    cap = want;
+    return hipSuccess;
+  }
+  template <class T = double>
+  T* d(size_t off) const { return reinterpret_cast<T*>(dev + off); }
+  template <class T = double>
+  T* h(size_t off) const { return reinterpret_cast<T*>(host + off); }
+  void free_blocks() {
+    if (dev) (void)hipFree(dev);
+    if (host) (void)hipHostFree(host);
+    dev = host = nullptr; cap = 0;
+  }
+  void release() {
+    free_blocks();
+    if (st) (void)hipStreamDestroy(st);
+    st = nullptr;
+  }
+};
+
+// 256-byte aligned parts of a staging block: take() gives back a part's byte offset, the same in the device block and in the mirror
+struct Layout {
+  size_t end = 0;
+  size_t take(size_t bytes) {
+    const size_t at = end;
+    end += (bytes + 255) & ~(size_t)255;
+    return at;
+  }
+};
+
+// one column step in the drive arena of its mechanism.  In/out first — s1 | s3 | sl1 | sion1 | bg | bgs — then in-only — scal | env — then
+// out-only — th(2) | hlast | ierr | stats | c_packed — then device only — var | fix | rct.  Counts in doubles per layer, offsets in bytes.
+struct DriveLayout {
+  size_t nl = 0, j1 = 0, j5 = 0, nsl = 0, nsi = 0, nv = 0, nf = 0, nr = 0, ne = 0;
+  size_t s1 = 0, s3 = 0, sl1 = 0, si = 0, bg = 0, bgs = 0, io_end = 0, scal = 0, env = 0, in_end = 0;
+  size_t th = 0, hl = 0, ierr = 0, stats = 0, cp = 0, out_end = 0, var = 0, fix = 0, rct = 0, end = 0;
+};
+
+struct MechState {
+  bool ready = false;
+  int nt = 0;
+  MechTables tab;
+  std::string text;
+  KernelBufs k;
+  RatesBufs rates;
+  PackBufs pack;
+  KmtBufs kmt;
+  LiqBufs liq;
+  StcBufs stc;
+  VmeanBufs vmean;
+  DevBuf<double> d_rct;      // scratch of mistra_chem_drive_device (grow-only)
+  // staging of the batched host-buffer entries (grow-only)
+  DevBuf<double> s_var, s_fix, s_rct, s_th, s_env;
   DevBuf<int32_t> s_ierr, s_stats, s_sing;
   // where the zero-pivot rows of the LAST host-buffer call of this slot are (mistra_chem_singular_rows): cells [sing_start,
   // sing_start + sing_count) of the caller's batch in s_sing, or the one cell of the COMMON-block call in one_sing
   size_t sing_start = 0, sing_count = 0;
   bool sing_one = false;
   int32_t one_sing[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // one-cell calls (the Fortran shim): one contiguous device block in, one out, pinned host mirrors, a private stream
-  double* one_dev = nullptr;      // [C(NSPEC) | RCONST(NREACT)]  then  [VAR out | Texit Hexit | 8 stats + ierr as int32]
-  double* one_host = nullptr;
-  hipStream_t one_stream = nullptr;
+  Staging drive;      // mistra_chem_drive(_begin): everything that crosses PCIe for a batch of layers, one copy up and the chain on its stream
+  Staging one;        // one-cell calls (the Fortran shim): one copy in, one out
+  struct PendingDrive {      // a column step issued by mistra_chem_drive_begin and not yet fetched by mistra_chem_drive_end
+    bool active = false;
+    DriveLayout lay;
+    std::vector<int32_t> layer, level;
+    double *s1 = nullptr, *s3 = nullptr, *sl1 = nullptr, *sion1 = nullptr, *bg = nullptr, *bgs = nullptr, *t_h = nullptr, *c_packed = nullptr;
+    int32_t *ierr = nullptr, *stats = nullptr;
+    int nrxn = 0;
+  } pend;
   void release() {
-    consts.release(); fun_fac.release(); jac_fac.release(); jvs_pos.release(); zero_pos.release(); diag_pos.release();
-    vdot.release(); jvs.release(); lu.release(); solve_head_fwd.release(); solve_head_bwd.release();
-    tail_fwd.release(); tail_bwd.release(); lu_scale.release();
-    pk_pack.release(); pk_fix.release(); pk_unpack.release(); pk_slot_id.release(); pk_slot_first.release(); pk_terms.release(); pk_words.release();
-    pk_acc.release(); pk_envc.release(); pk_aptr.release(); pk_afac.release(); map_gas_m2k.release(); map_gas_k2m.release(); map_rad_m2k.release();
-    map_rad_k2m.release(); d_env.release(); d_rct.release(); pack_ready = maps_ready = false;
-    kmt_lex.release(); kmt_ready = false;
-    lq_hkind.release(); lq_eof.release(); lq_foff.release(); lq_boff.release(); lq_fkind.release(); lq_farg.release(); lq_ha0.release(); lq_hb0.release();
-    lq_fa.release(); lq_fb.release(); liq_ready = false;
-    vm_mass.release(); vmean_ready = false;
-    for (int i = 0; i < 4; i++) { stc_consts[i].release(); stc_offs[i].release(); stc_words[i].release(); }
-    stc_ready = false;
-    dense_rows.release(); schur_cells.release(); rates_consts.release(); rates_offs.release(); rates_words.release(); rates_fslot.release(); s_env.release(); rates_ready = false;
-    s_var.release(); s_fix.release(); s_rct.release(); s_out.release(); s_th.release(); s_ierr.release(); s_stats.release(); s_sing.release();
+    k.release(); rates.release(); pack.release(); kmt.release(); liq.release(); stc.release(); vmean.release();
+    d_rct.release();
+    s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
     sing_count = 0; sing_one = false;
-    if (drv_dev) (void)hipFree(drv_dev);
-    if (drv_host) (void)hipHostFree(drv_host);
-    if (drv_stream) (void)hipStreamDestroy(drv_stream);
-    drv_dev = drv_host = nullptr; drv_cap = 0; drv_stream = nullptr;
-    if (one_dev) (void)hipFree(one_dev);
-    if (one_host) (void)hipHostFree(one_host);
-    if (one_stream) (void)hipStreamDestroy(one_stream);
-    one_dev = one_host = nullptr;
-    one_stream = nullptr;
+    drive.release(); one.release();
     pend = PendingDrive{};      // (a step issued and never fetched dies with its buffers)
     ready = false;
   }
 };
 
 // One DeviceState per GPU the library was initialised on (mistra_chem_init: one; mistra_chem_init_devices: several).
-// Slot 0 is the primary device: the one-cell Fortran entry points and mistra_chem_describe use it.
+// Slot 0 is the primary device: the host-buffer entry points and mistra_chem_describe use it.
 struct DeviceState {
   int id = -1;
   MechState mech[3];
@@ -377,46 +543,30 @@ bool g_inited = false;
 int g_max_steps = 100000;      // Max_no_steps (gas.f:1042); only mistra_chem_debug_set_max_steps changes it
 std::vector<DeviceState> g_devs;
 
-// host-buffer entries of the liq_parm kernels: arenas on the primary device (see DevBlock below)
-struct LiqStage {
-  char *dev = nullptr, *host = nullptr;
-  size_t cap = 0;
-  hipStream_t st = nullptr;
-  std::vector<std::pair<const char*, size_t>> pinned;      // caller ranges registered by mistra_chem_pin_host
-  hipError_t ensure(size_t bytes) {
-    if (!st)
-      if (hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) return e;
-    if (bytes <= cap) return hipSuccess;
-    if (dev) (void)hipFree(dev);
-    if (host) (void)hipHostFree(host);
-    dev = host = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 4;
-    if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), want)) return e;
-    if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&host), want, hipHostMallocDefault)) return e;
-    cap = want;
-    return hipSuccess;
-  }
-  bool is_pinned(const void* p, size_t n) const {
+// the host-buffer entries of the liq_parm kernels: one arena on the primary device (DevBlock below), and the caller ranges that
+// mistra_chem_pin_host registered, which those entries copy to and from directly
+Staging g_liq;
+struct PinnedRanges {
+  std::vector<std::pair<const char*, size_t>> r;
+  bool contains(const void* p, size_t n) const {
     const char* c = static_cast<const char*>(p);
-    for (const auto& r : pinned)
-      if (c >= r.first && c + n <= r.first + r.second) return true;
+    for (const auto& x : r)
+      if (c >= x.first && c + n <= x.first + x.second) return true;
     return false;
   }
   void release() {
-    for (const auto& r : pinned) (void)hipHostUnregister(const_cast<char*>(r.first));
-    pinned.clear();
-    if (dev) (void)hipFree(dev);
-    if (host) (void)hipHostFree(host);
-    if (st) (void)hipStreamDestroy(st);
-    dev = host = nullptr; cap = 0; st = nullptr;
+    for (const auto& x : r) (void)hipHostUnregister(const_cast<char*>(x.first));
+    r.clear();
   }
-};
-LiqStage g_liq;
+} g_pinned;
 
-DeviceState* device_slot(int hip_device) {
-  for (auto& d : g_devs)
-    if (d.id == hip_device) return &d;
-  return nullptr;
+void release_all() {
+  if (!g_devs.empty() && g_devs[0].id >= 0) (void)hipSetDevice(g_devs[0].id);
+  g_pinned.release();
+  g_liq.release();
+  for (auto& d : g_devs) d.release();
+  g_devs.clear();
+  g_inited = false;
 }
 
 std::string mech_dir() {
@@ -441,8 +591,9 @@ bool traits_match(const MechTables& t, int n_jnz, int tail_regs, bool scale_pass
 
 int setup_mech(DeviceState& D, int mech) {
   MechState& S = D.mech[mech];
+  const std::string name = kMechName[mech], base = mech_dir() + "/" + name;
   std::string err;
-  if (!S.tab.load(mech_dir() + "/" + kMechName[mech] + ".mech", &err)) return fail(err);
+  if (!S.tab.load(base + ".mech", &err)) return fail(err);
   S.nt = default_nt(mech);
   const bool nt_ok = (mech == MISTRA_MECH_GAS && S.nt == kGasNT) || (mech == MISTRA_MECH_AER && S.nt == kAerNT) ||
                      (mech == MISTRA_MECH_TOT && S.nt == kTotNT);
@@ -465,95 +616,42 @@ int setup_mech(DeviceState& D, int mech) {
   bool ok = mech == MISTRA_MECH_GAS   ? traits_match<GasTraits>(S.tab, K.n_jnz, K.tail.regs, K.lu_scale.nslots > 0, K.dense)
             : mech == MISTRA_MECH_AER ? traits_match<AerTraits>(S.tab, K.n_jnz, K.tail.regs, K.lu_scale.nslots > 0, K.dense)
                                       : traits_match<TotTraits>(S.tab, K.n_jnz, K.tail.regs, K.lu_scale.nslots > 0, K.dense);
-  if (!ok) return fail(std::string(kMechName[mech]) + ": mechanism table does not match the compiled kernel sizes");
-  S.text = std::string(kMechName[mech]) + ": " + describe(K);
-  S.n_temps = K.n_temps;
-  HIP_TRY(S.consts.upload(S.tab.consts));
-  HIP_TRY(S.fun_fac.upload(K.fun_fac));
-  HIP_TRY(S.jac_fac.upload(K.jac_fac));
-  HIP_TRY(S.jvs_pos.upload(K.jvs_pos));
-  HIP_TRY(S.zero_pos.upload(K.zero_pos));
-  HIP_TRY(S.diag_pos.upload(K.diag_pos));
-  HIP_TRY(S.vdot.upload(K.vdot));
-  HIP_TRY(S.jvs.upload(K.jvs));
-  HIP_TRY(S.lu.upload(K.lu));
-  HIP_TRY(S.solve_head_fwd.upload(K.solve_head_fwd));
-  HIP_TRY(S.solve_head_bwd.upload(K.solve_head_bwd));
-  HIP_TRY(S.tail_fwd.upload(K.tail.fwd));
-  HIP_TRY(S.tail_bwd.upload(K.tail.bwd));
-  HIP_TRY(S.lu_scale.upload(K.lu_scale.recs));
-  HIP_TRY(S.dense_rows.upload(K.dense.row_info));
-  HIP_TRY(S.schur_cells.upload(K.dense.schur_cells));
-  {   // optional: the rate table (gas today)
-    RatesTable T;
-    std::string rerr;
-    if (T.load(mech_dir() + "/" + kMechName[mech] + ".rates", &rerr)) {
-      if (T.nreact != S.tab.nreact) return fail(std::string(kMechName[mech]) + ".rates does not belong to this mechanism");
-      HIP_TRY(S.rates_consts.upload(T.consts));
-      HIP_TRY(S.rates_offs.upload(T.offs));
-      HIP_TRY(S.rates_words.upload(T.words));
-      HIP_TRY(S.rates_fslot.upload(T.fslot));
-      S.rates_nenv = T.nenv;
-      S.rates_ready = true;
-    }
+  if (!ok) return fail(name + ": mechanism table does not match the compiled kernel sizes");
+  S.text = name + ": " + describe(K);
+  if (int rc = S.k.upload(S.tab, K)) return rc;
+  // the optional tables: a mechanism without the file has no such routine (the entries that need one say so)
+  const int nspec = S.tab.nvar + S.tab.nfix;
+  RatesTable R;
+  if (R.load(base + ".rates", &err)) {      // (gas today)
+    if (R.nreact != S.tab.nreact) return fail(name + ".rates does not belong to this mechanism");
+    if (int rc = S.rates.upload(R)) return rc;
   }
-  {   // the drivers' hand-over tables
-    std::string perr;
-    if (S.pack_tab.load(mech_dir() + "/" + kMechName[mech] + ".pack", &perr)) {
-      const PackTable& T = S.pack_tab;
-      if (T.nvar != S.tab.nvar || T.nfix != S.tab.nfix) return fail(std::string(kMechName[mech]) + ".pack does not belong to this mechanism");
-      for (size_t q = 0; q < T.terms.size() / 3; q++)
-        if (T.terms[3 * q + 1] >= S.tab.nreact) return fail(std::string(kMechName[mech]) + ".pack: a budget term names a reaction the mechanism does not have");
-      for (int i = 0; i < T.n_envc(); i++)
-        if (S.rates_ready && T.envc[(size_t)2 * i] >= S.rates_nenv) return fail(std::string(kMechName[mech]) + ".pack: a concentration slot lies outside the rate evaluator's input");
-      HIP_TRY(S.pk_pack.upload(T.pack)); HIP_TRY(S.pk_fix.upload(T.fix)); HIP_TRY(S.pk_unpack.upload(T.unpack));
-      HIP_TRY(S.pk_slot_id.upload(T.slot_id)); HIP_TRY(S.pk_slot_first.upload(T.slot_first)); HIP_TRY(S.pk_terms.upload(T.terms));
-      HIP_TRY(S.pk_words.upload(T.term_words)); HIP_TRY(S.pk_acc.upload(T.acc)); HIP_TRY(S.pk_envc.upload(T.envc));
-      HIP_TRY(S.pk_aptr.upload(S.tab.a_ptr)); HIP_TRY(S.pk_afac.upload(S.tab.a_fac));
-      S.pack_ready = true;
-    }
+  if (S.pack.tab.load(base + ".pack", &err)) {      // the drivers' hand-over tables
+    const PackTable& T = S.pack.tab;
+    if (T.nvar != S.tab.nvar || T.nfix != S.tab.nfix) return fail(name + ".pack does not belong to this mechanism");
+    for (size_t q = 0; q < T.terms.size() / 3; q++)
+      if (T.terms[3 * q + 1] >= S.tab.nreact) return fail(name + ".pack: a budget term names a reaction the mechanism does not have");
+    for (int i = 0; i < T.n_envc(); i++)
+      if (S.rates.ready && T.envc[(size_t)2 * i] >= S.rates.nenv) return fail(name + ".pack: a concentration slot lies outside the rate evaluator's input");
+    if (int rc = S.pack.upload(S.tab)) return rc;
   }
-  {   // species list of the mass-transfer routines (aer, tot)
-    std::string kerr;
-    if (S.kmt_tab.load(mech_dir() + "/" + kMechName[mech] + ".kmt", &kerr)) {
-      for (int32_t i : S.kmt_tab.lex)
-        if (i < 1 || i > S.tab.nvar + S.tab.nfix) return fail(std::string(kMechName[mech]) + ".kmt does not belong to this mechanism");
-      HIP_TRY(S.kmt_lex.upload(S.kmt_tab.lex));
-      S.kmt_ready = true;
-    }
+  if (S.kmt.tab.load(base + ".kmt", &err)) {      // species list of the mass-transfer routines (aer, tot)
+    for (int32_t i : S.kmt.tab.lex)
+      if (i < 1 || i > nspec) return fail(name + ".kmt does not belong to this mechanism");
+    if (int rc = S.kmt.upload()) return rc;
   }
-  {   // Henry and equilibrium constants (aer, tot)
-    std::string lerr;
-    LiqTable& T = S.liq_tab;
-    if (T.load(mech_dir() + "/" + kMechName[mech] + ".liq", &lerr)) {
-      if (T.nspec != S.tab.nvar + S.tab.nfix) return fail(std::string(kMechName[mech]) + ".liq does not belong to this mechanism");
-      HIP_TRY(S.lq_hkind.upload(T.h_kind)); HIP_TRY(S.lq_eof.upload(T.e_of)); HIP_TRY(S.lq_foff.upload(T.foff)); HIP_TRY(S.lq_boff.upload(T.boff));
-      HIP_TRY(S.lq_fkind.upload(T.fkind)); HIP_TRY(S.lq_farg.upload(T.farg)); HIP_TRY(S.lq_ha0.upload(T.h_a0)); HIP_TRY(S.lq_hb0.upload(T.h_b0));
-      HIP_TRY(S.lq_fa.upload(T.fa)); HIP_TRY(S.lq_fb.upload(T.fb));
-      S.liq_ready = true;
-    }
+  if (S.liq.tab.load(base + ".liq", &err)) {      // Henry and equilibrium constants (aer, tot)
+    if (S.liq.tab.nspec != nspec) return fail(name + ".liq does not belong to this mechanism");
+    if (int rc = S.liq.upload()) return rc;
   }
-  {   // accommodation coefficients (aer, tot)
-    std::string serr;
-    StcoeffTable& T = S.stc_tab;
-    if (T.load(mech_dir() + "/" + kMechName[mech] + ".stcoeff", &serr)) {
-      if (T.v[0].nreact != S.tab.nvar + S.tab.nfix) return fail(std::string(kMechName[mech]) + ".stcoeff does not belong to this mechanism");
-      for (int i = 0; i < 4; i++) {
-        HIP_TRY(S.stc_consts[i].upload(T.v[i].consts)); HIP_TRY(S.stc_offs[i].upload(T.v[i].offs)); HIP_TRY(S.stc_words[i].upload(T.v[i].words));
-      }
-      S.stc_ready = true;
-    }
+  if (S.stc.tab.load(base + ".stcoeff", &err)) {      // accommodation coefficients (aer, tot)
+    if (S.stc.tab.v[0].nreact != nspec) return fail(name + ".stcoeff does not belong to this mechanism");
+    if (int rc = S.stc.upload()) return rc;
   }
-  {   // mean molecular speeds (aer, tot)
-    std::string verr;
-    VmeanTable& T = S.vmean_tab;
-    if (T.load(mech_dir() + "/" + kMechName[mech] + ".vmean", &verr)) {
-      if (T.nspec != S.tab.nvar + S.tab.nfix) return fail(std::string(kMechName[mech]) + ".vmean does not belong to this mechanism");
-      HIP_TRY(S.vm_mass.upload(T.mass));
-      S.vmean_ready = true;
-    }
+  if (S.vmean.tab.load(base + ".vmean", &err)) {      // mean molecular speeds (aer, tot)
+    if (S.vmean.tab.nspec != nspec) return fail(name + ".vmean does not belong to this mechanism");
+    if (int rc = S.vmean.upload()) return rc;
   }
-  S.lu_scale_slots = K.lu_scale.nslots;
   S.ready = true;
   return 0;
 }
@@ -569,27 +667,79 @@ int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream) {
 
 KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                      double tout, double* var_out, int32_t* ierr, int32_t* stats, double* th) {
+  const KernelBufs& k = S.k;
   KernelArgs a;
   a.var_in = var_in; a.fix = fix; a.rconst = rconst; a.var_out = var_out; a.ierr = ierr; a.stats = stats;
-  a.texit_hexit = th; a.h_last = nullptr; a.hstart = nullptr; a.prof = nullptr; a.dump = nullptr; a.sing_rows = nullptr; a.n_temps = S.n_temps; a.max_steps = g_max_steps; a.tin = tin; a.tout = tout; a.ncell = ncell;
-  a.consts = S.consts.p; a.fun_fac = S.fun_fac.p; a.jac_fac = S.jac_fac.p; a.jvs_pos = S.jvs_pos.p;
-  a.zero_pos = S.zero_pos.p; a.diag_pos = S.diag_pos.p;
-  a.vdot = S.vdot.dev(); a.jvs = S.jvs.dev(); a.lu = S.lu.dev();
+  a.texit_hexit = th; a.h_last = nullptr; a.hstart = nullptr; a.prof = nullptr; a.dump = nullptr; a.sing_rows = nullptr; a.n_temps = k.n_temps; a.max_steps = g_max_steps; a.tin = tin; a.tout = tout; a.ncell = ncell;
+  a.consts = k.consts.p; a.fun_fac = k.fun_fac.p; a.jac_fac = k.jac_fac.p; a.jvs_pos = k.jvs_pos.p;
+  a.zero_pos = k.zero_pos.p; a.diag_pos = k.diag_pos.p;
+  a.vdot = k.vdot.dev(); a.jvs = k.jvs.dev(); a.lu = k.lu.dev();
 #ifdef MISTRA_DIAG_ENV      // diagnostic builds only (tools/diag_dense.sh env): never in the product library
   if (const char* cut = std::getenv("MISTRA_DIAG_LU_ROUNDS"))      // timing diagnostic (tools/profile_lu_rounds.py): results are garbage
     a.lu.nrounds = std::max(1, std::min(a.lu.nrounds, std::atoi(cut)));
 #endif
-  a.solve_head_fwd = S.solve_head_fwd.dev(); a.solve_head_bwd = S.solve_head_bwd.dev();
-  a.tail = TailDev{S.tail_fwd.p, S.tail_bwd.p};
-  a.lu_scale = ScaleDev{S.lu_scale.p, S.lu_scale_slots, S.lu_scale_slots + VM_LOOKAHEAD_ROWS};
-  a.dense = DenseDev{S.dense_rows.p, S.schur_cells.p};
+  a.solve_head_fwd = k.solve_head_fwd.dev(); a.solve_head_bwd = k.solve_head_bwd.dev();
+  a.tail = TailDev{k.tail_fwd.p, k.tail_bwd.p};
+  a.lu_scale = ScaleDev{k.lu_scale.p, k.lu_scale_slots, k.lu_scale_slots + VM_LOOKAHEAD_ROWS};
+  a.dense = DenseDev{k.dense_rows.p, k.schur_cells.p};
   return a;
 }
+
+PackDev pack_dev(const MechState& S) { return S.pack.dev(S.tab.nreact, S.k.consts.p); }
 
 int check_call(int mech, int ncell) {
   if (mech < 0 || mech > 2) return fail("unknown mechanism id");
   if (ncell < 0) return fail("negative cell count");
   if (!g_inited || g_devs.empty() || !g_devs[0].mech[mech].ready) return fail("mistra_chem_init has not been called (or failed)");
+  return 0;
+}
+
+// the groups of tables an entry needs are there
+int require(const MechState& S, int mech, unsigned need) {
+  const std::string m = kMechName[mech];
+  if ((need & kNeedPackTable) && !S.pack.ready) return fail("no hand-over table for the " + m + " mechanism");
+  if ((need & kNeedMaps) && !S.pack.maps_ready) return fail("mistra_chem_set_species_maps has not been called for the " + m + " mechanism");
+  if ((need & kNeedRates) && !S.rates.ready) return fail("no device rate table for the " + m + " mechanism");
+  if ((need & kNeedKmt) && !S.kmt.ready) return fail("the " + m + " mechanism has no mass-transfer routine (fast_k_mt_a: aer, fast_k_mt_t: tot)");
+  if ((need & kNeedLiq) && !S.liq.ready)
+    return fail("the " + m + " mechanism has no liquid-phase routines (henry_a / equil_co_a: aer, henry_t / equil_co_t: tot)");
+  if ((need & kNeedStc) && !S.stc.ready) return fail("the " + m + " mechanism has no st_coeff routine (st_coeff_a: aer, st_coeff_t: tot)");
+  if ((need & kNeedVmean) && !S.vmean.ready) return fail("the " + m + " mechanism has no v_mean routine (v_mean_a: aer, v_mean_t: tot)");
+  return 0;
+}
+
+struct Slot {
+  DeviceState* D = nullptr;
+  MechState* S = nullptr;
+};
+
+// The preamble of a device-pointer entry: the buffers decide the device.  The call runs on the slot `p` lives on — the first slot set up
+// on that device — with the tables `need` names; the calling thread is switched to that device.
+int on_device(int mech, int ncell, const void* p, const char* what, unsigned need, Slot* t) {
+  if (int rc = check_call(mech, ncell)) return rc;
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) return fail(std::string(what) + " is not a device pointer");
+  DeviceState* D = nullptr;
+  for (auto& d : g_devs)
+    if (d.id == attr.device) { D = &d; break; }
+  if (!D) return fail("the buffers live on device " + std::to_string(attr.device) + ", which mistra_chem_init(_devices) did not set up");
+  if (int rc = require(D->mech[mech], mech, need)) return rc;
+  HIP_TRY(hipSetDevice(D->id));
+  *t = Slot{D, &D->mech[mech]};
+  return 0;
+}
+
+// The primary slot for a host-buffer entry (the caller holds g_mu), with the tables `need` names.  `mutates`: the entry changes the
+// mechanism's staging, species maps or singular-row record, which a column step issued by mistra_chem_drive_begin may still be using —
+// refused while such a step is open.
+int on_primary(int mech, unsigned need, bool mutates, Slot* t) {
+  DeviceState& D = g_devs[0];
+  MechState& S = D.mech[mech];
+  if (mutates && S.pend.active)
+    return fail(std::string("a column step of the ") + kMechName[mech] + " mechanism is open (mistra_chem_drive_begin): fetch it with mistra_chem_drive_end first");
+  if (int rc = require(S, mech, need)) return rc;
+  HIP_TRY(hipSetDevice(D.id));
+  *t = Slot{&D, &S};
   return 0;
 }
 
@@ -611,12 +761,8 @@ int init_locked(int n, const int* ids) {
     HIP_TRY(hipSetDevice(g_devs[0].id));
     return 0;
   }
-  if (!g_devs.empty() && g_devs[0].id >= 0) (void)hipSetDevice(g_devs[0].id);
-  g_liq.release();
-  for (auto& d : g_devs) d.release();
-  g_devs.clear();
+  release_all();
   g_devs.resize(want.size());
-  g_inited = false;
   for (size_t i = 0; i < want.size(); i++) {
     HIP_TRY(hipSetDevice(want[i]));
     g_devs[i].id = want[i];
@@ -636,7 +782,7 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
                       const double* env = nullptr) {
   HIP_TRY(hipSetDevice(D.id));
   MechState& S = D.mech[mech];
-  const size_t nv = (size_t)kDims[mech][0], nf = (size_t)kDims[mech][1], nr = (size_t)kDims[mech][2], nc = (size_t)ncell;
+  const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact, nc = (size_t)ncell;
   HIP_TRY(S.s_var.reserve(nc * nv));
   HIP_TRY(S.s_fix.reserve(nc * nf));
   HIP_TRY(S.s_rct.reserve(nc * nr));
@@ -646,14 +792,11 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
   if (t_h) HIP_TRY(S.s_th.reserve(nc * 3));
   HIP_TRY(hipMemcpy(S.s_var.p, var_in, nc * nv * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(S.s_fix.p, fix, nc * nf * sizeof(double), hipMemcpyHostToDevice));
-  if (env) {
-    if (!S.rates_ready) return fail(std::string("no device rate table for the ") + kMechName[mech] + " mechanism");
-    const size_t ne = (size_t)S.rates_nenv;
+  if (env) {      // (the caller has checked that the mechanism has a rate table)
+    const size_t ne = (size_t)S.rates.nenv;
     HIP_TRY(S.s_env.reserve(nc * ne));
     HIP_TRY(hipMemcpy(S.s_env.p, env, nc * ne * sizeof(double), hipMemcpyHostToDevice));
-    const RatesDev R{S.rates_consts.p, S.rates_offs.p, S.rates_words.p, S.rates_fslot.p, S.tab.nreact, S.rates_nenv};
-    hipError_t e = launch_update_rconst(R, S.s_env.p, S.s_rct.p, ncell, nullptr);
-    if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+    LAUNCH_TRY(launch_update_rconst(S.rates.dev(), S.s_env.p, S.s_rct.p, ncell, nullptr));
   } else {
     HIP_TRY(hipMemcpy(S.s_rct.p, rconst, nc * nr * sizeof(double), hipMemcpyHostToDevice));
   }
@@ -698,6 +841,141 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
   return 0;
 }
 
+// ---- one column step on the device: x_drive for a batch of layers
+
+// where the step's arrays live: caller buffers (mistra_chem_drive_device) or parts of the drive arena (mistra_chem_drive_begin)
+struct ColumnDev {
+  double *s1, *s3, *sl1, *sion1;
+  const double* scal;
+  double *env, *var, *fix, *rct;
+  int32_t *ierr, *stats;
+  double* th;
+  double *bg, *bgs;             // budgets, each may be nullptr
+  double *c_packed, *h_last;    // nullptr unless wanted
+  int32_t* sing_rows;           // nullptr unless wanted
+};
+
+// pack -> (C as packed) -> env from C -> Update_RCONST_x -> INTEGRATE_x -> budgets -> unpack, in order on `st`
+int column_step(DeviceState& D, int mech, int ncell, const ColumnDev& c, double tin, double dt, hipStream_t st) {
+  const MechState& S = D.mech[mech];
+  const PackDev P = pack_dev(S);
+  LAUNCH_TRY(launch_pack(P, ncell, c.s1, c.s3, c.sl1, c.sion1, c.scal, c.var, c.fix, st));
+  if (c.c_packed) {      // [ncell][NVAR + NFIX]
+    const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nl = (size_t)ncell;
+    HIP_TRY(hipMemcpy2DAsync(c.c_packed, (nv + nf) * sizeof(double), c.var, nv * sizeof(double), nv * sizeof(double), nl, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(c.c_packed + nv, (nv + nf) * sizeof(double), c.fix, nf * sizeof(double), nf * sizeof(double), nl, hipMemcpyDeviceToDevice, st));
+  }
+  LAUNCH_TRY(launch_env_from_c(P, ncell, S.rates.nenv, c.var, c.fix, c.env, st));
+  LAUNCH_TRY(launch_update_rconst(S.rates.dev(), c.env, c.rct, ncell, st));
+  KernelArgs a = make_args(S, ncell, c.var, c.fix, c.rct, tin, tin + dt, c.var, c.ierr, c.stats, c.th);
+  a.h_last = c.h_last;
+  a.sing_rows = c.sing_rows;
+  if (int rc = launch(D, mech, a, st)) return rc;
+  if (c.bg || c.bgs) LAUNCH_TRY(launch_budgets(P, ncell, c.var, c.fix, c.rct, dt, c.bg, c.bgs, st));
+  LAUNCH_TRY(launch_unpack(P, ncell, c.var, c.s1, c.s3, c.sl1, c.sion1, st));
+  return 0;
+}
+
+DriveLayout drive_layout(const MechState& S, int mech, size_t nl, bool bg, bool bgs, bool c_packed) {
+  const PackTable& T = S.pack.tab;
+  DriveLayout L;
+  L.nl = nl; L.j1 = (size_t)S.pack.j1; L.j5 = (size_t)S.pack.j5; L.nsl = (size_t)T.j2 * T.nkc; L.nsi = (size_t)T.j6 * T.nkc;
+  L.nv = (size_t)kDims[mech].nvar; L.nf = (size_t)kDims[mech].nfix; L.nr = (size_t)kDims[mech].nreact; L.ne = (size_t)S.rates.nenv;
+  const size_t d8 = sizeof(double), nb = 2 * (size_t)kBudSlots;
+  Layout B;
+  L.s1 = B.take(nl * L.j1 * d8); L.s3 = B.take(nl * L.j5 * d8); L.sl1 = B.take(nl * L.nsl * d8); L.si = B.take(nl * L.nsi * d8);
+  L.bg = B.take(bg ? nl * 2 * L.nr * d8 : 0); L.bgs = B.take(bgs ? nl * nb * d8 : 0);
+  L.io_end = B.end;
+  L.scal = B.take(nl * 6 * d8); L.env = B.take(nl * L.ne * d8);
+  L.in_end = B.end;
+  L.th = B.take(nl * 2 * d8); L.hl = B.take(nl * d8); L.ierr = B.take(nl * sizeof(int32_t)); L.stats = B.take(nl * 8 * sizeof(int32_t));
+  L.cp = B.take(c_packed ? nl * (L.nv + L.nf) * d8 : 0);
+  L.out_end = B.end;
+  L.var = B.take(nl * L.nv * d8); L.fix = B.take(nl * L.nf * d8); L.rct = B.take(nl * L.nr * d8);
+  L.end = B.end;
+  return L;
+}
+
+// ---- the host-buffer forms of the liq_parm kernels: what a Fortran caller reaches (shim/mistra_kpp_liq.f90).  A call gathers its inputs into the
+//      pinned mirror of g_liq (or, for caller memory that mistra_chem_pin_host registered, leaves them where they are), sends them up, runs the
+//      kernel on the arena's stream and fetches its outputs; one stream synchronisation per call, no allocation once the arena has grown to the
+//      column's size.
+struct DevBlock {      // the arrays of one call as parts of g_liq
+  struct Part {
+    size_t off, bytes;
+    const void* src;      // where its input comes from (nullptr: not an input)
+    void* dst;            // where its output goes (nullptr: not an output)
+  };
+  Layout L;
+  std::vector<Part> parts;
+  size_t add(size_t bytes) {
+    parts.push_back(Part{L.take(bytes), bytes, nullptr, nullptr});
+    return parts.size() - 1;
+  }
+  hipError_t alloc() { return g_liq.ensure(L.end ? L.end : 256); }
+  double* dptr(size_t i) const { return g_liq.d(parts[i].off); }
+  void up(size_t i, const void* from) { parts[i].src = from; }
+  void down(size_t i, void* to) { parts[i].dst = to; }
+  hipStream_t stream() const { return g_liq.st; }
+  // every transfer costs ~15 us of latency in the stream whatever its size: neighbouring staged parts travel as ONE copy (the padding between them with
+  // them), parts inside a registered caller range go straight from / to the caller's memory
+  hipError_t transfer(bool upward) {
+    auto end = [&](size_t i) { return upward ? parts[i].src : static_cast<const void*>(parts[i].dst); };
+    size_t i = 0;
+    while (i < parts.size()) {
+      const void* p = end(i);
+      if (!p) { i++; continue; }
+      if (g_pinned.contains(p, parts[i].bytes)) {
+        hipError_t e = upward ? hipMemcpyAsync(g_liq.dev + parts[i].off, p, parts[i].bytes, hipMemcpyHostToDevice, g_liq.st)
+                              : hipMemcpyAsync(parts[i].dst, g_liq.dev + parts[i].off, parts[i].bytes, hipMemcpyDeviceToHost, g_liq.st);
+        if (e != hipSuccess) return e;
+        i++;
+        continue;
+      }
+      size_t j = i;      // the run of staged parts i..j-1
+      while (j < parts.size() && end(j) && !g_pinned.contains(end(j), parts[j].bytes)) {
+        if (upward) std::memcpy(g_liq.host + parts[j].off, parts[j].src, parts[j].bytes);
+        j++;
+      }
+      const size_t lo = parts[i].off, hi = parts[j - 1].off + parts[j - 1].bytes;
+      hipError_t e = upward ? hipMemcpyAsync(g_liq.dev + lo, g_liq.host + lo, hi - lo, hipMemcpyHostToDevice, g_liq.st)
+                            : hipMemcpyAsync(g_liq.host + lo, g_liq.dev + lo, hi - lo, hipMemcpyDeviceToHost, g_liq.st);
+      if (e != hipSuccess) return e;
+      i = j;
+    }
+    return hipSuccess;
+  }
+  hipError_t send() { return transfer(true); }      // after the last up(), before the kernel
+  hipError_t finish() {       // after the last down(): fetch, wait, hand the staged outputs to the caller
+    if (hipError_t e = transfer(false)) return e;
+    if (hipError_t e = hipStreamSynchronize(g_liq.st)) return e;
+    for (const Part& q : parts)
+      if (q.dst && !g_pinned.contains(q.dst, q.bytes)) std::memcpy(q.dst, g_liq.host + q.off, q.bytes);
+    return hipSuccess;
+  }
+};
+
+// the arguments of fast_k_mt against the mechanism's table (the kernel's loop limits: checked here, on the host)
+int kmt_args(const MechState& S, const int32_t* kw, int nkw, int ka, int ifeed, int nkc_l, KmtDev* K) {
+  const KmtTable& T = S.kmt.tab;
+  if (nkw != T.nka || T.nka > kKmtMaxNka) return fail("kw does not have nka entries");
+  if (ka < 0 || ka > T.nka || nkc_l < 1 || nkc_l > T.nkc) return fail("ka / nkc_l out of range");
+  *K = S.kmt.dev(S.tab.nvar + S.tab.nfix, ka, ifeed, nkc_l);
+  for (int i = 0; i < T.nka; i++) {
+    if (kw[i] < 0 || kw[i] > T.nkt) return fail("kw out of range");
+    K->kw[i] = kw[i];
+  }
+  return 0;
+}
+
+int equil_co_check(const MechState& S, int nkc, int j6) {
+  const LiqTable& T = S.liq.tab;
+  if (nkc < T.nkc_eq) return fail("nkc is smaller than the number of bins the routine sets");
+  for (size_t i = 0; i < T.fkind.size(); i++)
+    if (T.fkind[i] == 3 && T.farg[i] > j6) return fail("j6 is smaller than an activity-coefficient index the routine reads");
+  return 0;
+}
+
 }  // namespace
 
 static int lazy_init();
@@ -708,10 +986,10 @@ const char* mistra_chem_last_error(void) { return g_err.c_str(); }
 
 int mistra_chem_dims(int mech, int* nvar, int* nfix, int* nreact, int* lu_nonzero) {
   if (mech < 0 || mech > 2) return fail("unknown mechanism id");
-  if (nvar) *nvar = kDims[mech][0];
-  if (nfix) *nfix = kDims[mech][1];
-  if (nreact) *nreact = kDims[mech][2];
-  if (lu_nonzero) *lu_nonzero = kDims[mech][3];
+  if (nvar) *nvar = kDims[mech].nvar;
+  if (nfix) *nfix = kDims[mech].nfix;
+  if (nreact) *nreact = kDims[mech].nreact;
+  if (lu_nonzero) *lu_nonzero = kDims[mech].lu_nonzero;
   return 0;
 }
 
@@ -731,11 +1009,7 @@ int mistra_chem_device_count(void) { return g_inited ? (int)g_devs.size() : 0; }
 
 void mistra_chem_finalize(void) {
   std::lock_guard<std::mutex> lock(g_mu);
-  if (!g_devs.empty() && g_devs[0].id >= 0) (void)hipSetDevice(g_devs[0].id);
-  g_liq.release();
-  for (auto& d : g_devs) d.release();
-  g_devs.clear();
-  g_inited = false;
+  release_all();
 }
 
 const char* mistra_chem_describe(int mech) {
@@ -753,39 +1027,26 @@ int mistra_chem_integrate_device(int mech, int ncell, const double* d_var_in, co
 int mistra_chem_integrate_device_hstart(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
                                         double tin, double tout, double* d_var_out, int32_t* d_ierr, int32_t* d_stats,
                                         double* d_texit_hexit, const double* d_hstart, void* hip_stream) {
-  if (int rc = check_call(mech, ncell)) return rc;
-  if (ncell == 0) return 0;
+  if (ncell == 0) return check_call(mech, 0);      // (nothing to do, but an uninitialised library says so)
   if (!d_var_in || !d_fix || !d_rconst || !d_var_out || !d_ierr || !d_stats) return fail("null device pointer");
-  // the buffers decide the device: the call runs where d_var_in lives, which must be one of the initialised devices
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, d_var_in) != hipSuccess) return fail("d_var_in is not a device pointer");
-  DeviceState* D = device_slot(attr.device);
-  if (!D) return fail("the buffers live on device " + std::to_string(attr.device) + ", which mistra_chem_init(_devices) did not set up");
-  HIP_TRY(hipSetDevice(D->id));
-  KernelArgs a = make_args(D->mech[mech], ncell, d_var_in, d_fix, d_rconst, tin, tout, d_var_out, d_ierr, d_stats, d_texit_hexit);
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
+  KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, tin, tout, d_var_out, d_ierr, d_stats, d_texit_hexit);
   a.hstart = d_hstart;
-  return launch(*D, mech, a, static_cast<hipStream_t>(hip_stream));
+  return launch(*t.D, mech, a, static_cast<hipStream_t>(hip_stream));
 }
 
 int mistra_chem_rates_env_size(int mech) {
-  if (mech < 0 || mech > 2 || !g_inited || g_devs.empty() || !g_devs[0].mech[mech].rates_ready) return 0;
-  return g_devs[0].mech[mech].rates_nenv;
+  if (mech < 0 || mech > 2 || !g_inited || g_devs.empty() || !g_devs[0].mech[mech].rates.ready) return 0;
+  return g_devs[0].mech[mech].rates.nenv;
 }
 
 int mistra_chem_update_rconst_device(int mech, int ncell, const double* d_env, double* d_rconst, void* hip_stream) {
-  if (int rc = check_call(mech, ncell)) return rc;
-  if (ncell == 0) return 0;
+  if (ncell == 0) return check_call(mech, 0);
   if (!d_env || !d_rconst) return fail("null device pointer");
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, d_env) != hipSuccess) return fail("d_env is not a device pointer");
-  DeviceState* D = device_slot(attr.device);
-  if (!D) return fail("the buffers live on a device mistra_chem_init(_devices) did not set up");
-  MechState& S = D->mech[mech];
-  if (!S.rates_ready) return fail(std::string("no device rate table for the ") + kMechName[mech] + " mechanism");
-  HIP_TRY(hipSetDevice(D->id));
-  const RatesDev R{S.rates_consts.p, S.rates_offs.p, S.rates_words.p, S.rates_fslot.p, S.tab.nreact, S.rates_nenv};
-  hipError_t e = launch_update_rconst(R, d_env, d_rconst, ncell, static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_env, "d_env", kNeedRates, &t)) return rc;
+  LAUNCH_TRY(launch_update_rconst(t.S->rates.dev(), d_env, d_rconst, ncell, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
@@ -795,52 +1056,28 @@ int mistra_chem_update_rconst(int mech, int ncell, const double* env, double* rc
   if (ncell == 0) return 0;
   if (!env || !rconst) return fail("null host pointer");
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  MechState& S = D.mech[mech];
-  if (!S.rates_ready) return fail(std::string("no device rate table for the ") + kMechName[mech] + " mechanism");
-  HIP_TRY(hipSetDevice(D.id));
-  const size_t nc = (size_t)ncell, ne = (size_t)S.rates_nenv, nr = (size_t)S.tab.nreact;
+  Slot t;
+  if (int rc = on_primary(mech, kNeedRates, true, &t)) return rc;
+  MechState& S = *t.S;
+  const size_t nc = (size_t)ncell, ne = (size_t)S.rates.nenv, nr = (size_t)S.tab.nreact;
   HIP_TRY(S.s_env.reserve(nc * ne));
   HIP_TRY(S.s_rct.reserve(nc * nr));
   HIP_TRY(hipMemcpy(S.s_env.p, env, nc * ne * sizeof(double), hipMemcpyHostToDevice));
-  if (int rc = mistra_chem_update_rconst_device(mech, ncell, S.s_env.p, S.s_rct.p, nullptr)) return rc;
+  LAUNCH_TRY(launch_update_rconst(S.rates.dev(), S.s_env.p, S.s_rct.p, ncell, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(rconst, S.s_rct.p, nc * nr * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
 // ---- the hand-over halves of x_drive (pack.hip)
-static int pack_dev(int mech, const void* any_device_ptr, DeviceState** Dout, PackDev* P) {
-  if (int rc = check_call(mech, 1)) return rc;
-  hipPointerAttribute_t attr;
-  if (!any_device_ptr || hipPointerGetAttributes(&attr, any_device_ptr) != hipSuccess) return fail("not a device pointer");
-  DeviceState* D = device_slot(attr.device);
-  if (!D) return fail("the buffers live on a device mistra_chem_init(_devices) did not set up");
-  MechState& S = D->mech[mech];
-  if (!S.pack_ready) return fail(std::string("no hand-over table for the ") + kMechName[mech] + " mechanism");
-  if (!S.maps_ready) return fail("mistra_chem_set_species_maps has not been called for this mechanism");
-  HIP_TRY(hipSetDevice(D->id));
-  const PackTable& T = S.pack_tab;
-  *P = PackDev{S.pk_pack.p, S.pk_fix.p, S.pk_unpack.p, S.pk_slot_id.p, S.pk_slot_first.p, S.pk_terms.p, S.pk_words.p, S.pk_acc.p, S.pk_envc.p,
-               T.n_pack(), T.n_fix(), T.n_unpack(), T.n_slots(), (int)T.terms.size() / 3, (int)T.term_words.size(), (int)T.acc.size() / 2, T.n_envc(),
-               T.nvar, T.nfix, S.tab.nreact, T.j2, T.j6, T.nkc, T.preclamp,
-               S.map_gas_m2k.p, S.map_gas_k2m.p, S.map_rad_m2k.p, S.map_rad_k2m.p, S.map_j1, S.map_j5, S.pk_aptr.p, S.pk_afac.p, S.consts.p};
-  *Dout = D;
-  return 0;
-}
-#define LAUNCH_TRY(expr)                                                                                 \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e_));          \
-  } while (0)
 
 int mistra_chem_drive_dims(int mech, int* j2, int* j6, int* nkc, int* nbgs) {
   if (int rc = check_call(mech, 1)) return rc;
   const MechState& S = g_devs[0].mech[mech];
-  if (!S.pack_ready) return fail(std::string("no hand-over table for the ") + kMechName[mech] + " mechanism");
-  if (j2) *j2 = S.pack_tab.j2;
-  if (j6) *j6 = S.pack_tab.j6;
-  if (nkc) *nkc = S.pack_tab.nkc;
+  if (int rc = require(S, mech, kNeedPackTable)) return rc;
+  if (j2) *j2 = S.pack.tab.j2;
+  if (j6) *j6 = S.pack.tab.j6;
+  if (nkc) *nkc = S.pack.tab.nkc;
   if (nbgs) *nbgs = kBudSlots;
   return 0;
 }
@@ -850,8 +1087,10 @@ int mistra_chem_set_species_maps(int mech, int j1, const int32_t* gas_m2k, const
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, 1)) return rc;
   if (j1 < 0 || j5 < 0 || (j1 > 0 && (!gas_m2k || !gas_k2m)) || (j5 > 0 && (!rad_m2k || !rad_k2m))) return fail("bad species maps");
-  const int nvar = kDims[mech][0];
+  const int nvar = kDims[mech].nvar;
   std::lock_guard<std::mutex> lock(g_mu);
+  Slot t;
+  if (int rc = on_primary(mech, kNeedPackTable, true, &t)) return rc;      // (the maps are the same on every slot)
   // what the kernels rely on: every map entry names a VARIABLE species, and no species is written twice by the pack (neither by two
   // map entries nor by a map entry and one of the driver's explicit liquid-phase assignments): the reference assigns in sequence
   // and the later one wins, the kernel assigns in parallel
@@ -865,19 +1104,13 @@ int mistra_chem_set_species_maps(int mech, int j1, const int32_t* gas_m2k, const
     if (back != c) return fail("gas_m2k / gas_k2m (rad_m2k / rad_k2m) are not inverse to each other");
   }
   for (auto& D : g_devs) {
-    MechState& S = D.mech[mech];
-    if (!S.pack_ready) return fail(std::string("no hand-over table for the ") + kMechName[mech] + " mechanism");
-    for (int i = 0; i < S.pack_tab.n_pack(); i++) {
-      const int c0 = S.pack_tab.pack[(size_t)4 * i];
+    PackBufs& K = D.mech[mech].pack;
+    for (int i = 0; i < K.tab.n_pack(); i++) {
+      const int c0 = K.tab.pack[(size_t)4 * i];
       if (c0 < nvar && seen[(size_t)c0]) return fail("a species of the gas maps is also packed from sl1 / sion1");
     }
     HIP_TRY(hipSetDevice(D.id));
-    HIP_TRY(S.map_gas_m2k.upload(std::vector<int32_t>(gas_m2k, gas_m2k + 2 * (size_t)j1)));
-    HIP_TRY(S.map_gas_k2m.upload(std::vector<int32_t>(gas_k2m, gas_k2m + (size_t)j1)));
-    HIP_TRY(S.map_rad_m2k.upload(std::vector<int32_t>(rad_m2k, rad_m2k + 2 * (size_t)j5)));
-    HIP_TRY(S.map_rad_k2m.upload(std::vector<int32_t>(rad_k2m, rad_k2m + (size_t)j5)));
-    S.map_j1 = j1; S.map_j5 = j5;
-    S.maps_ready = true;
+    if (int rc = K.set_maps(j1, gas_m2k, gas_k2m, j5, rad_m2k, rad_k2m)) return rc;
   }
   (void)hipSetDevice(g_devs[0].id);
   return 0;
@@ -887,18 +1120,18 @@ int mistra_chem_pack_device(int mech, int ncell, const double* d_s1, const doubl
                             double* d_var, double* d_fix, void* hip_stream) {
   if (ncell == 0) return 0;
   if (!d_s1 || !d_s3 || !d_sl1 || !d_sion1 || !d_scal || !d_var || !d_fix) return fail("null device pointer");
-  DeviceState* D; PackDev P;
-  if (int rc = pack_dev(mech, d_var, &D, &P)) return rc;
-  LAUNCH_TRY(launch_pack(P, ncell, d_s1, d_s3, d_sl1, d_sion1, d_scal, d_var, d_fix, static_cast<hipStream_t>(hip_stream)));
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var, "d_var", kNeedPack, &t)) return rc;
+  LAUNCH_TRY(launch_pack(pack_dev(*t.S), ncell, d_s1, d_s3, d_sl1, d_sion1, d_scal, d_var, d_fix, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
 int mistra_chem_unpack_device(int mech, int ncell, const double* d_var, double* d_s1, double* d_s3, double* d_sl1, double* d_sion1, void* hip_stream) {
   if (ncell == 0) return 0;
   if (!d_var || !d_s1 || !d_s3 || !d_sl1 || !d_sion1) return fail("null device pointer");
-  DeviceState* D; PackDev P;
-  if (int rc = pack_dev(mech, d_var, &D, &P)) return rc;
-  LAUNCH_TRY(launch_unpack(P, ncell, d_var, d_s1, d_s3, d_sl1, d_sion1, static_cast<hipStream_t>(hip_stream)));
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var, "d_var", kNeedPack, &t)) return rc;
+  LAUNCH_TRY(launch_unpack(pack_dev(*t.S), ncell, d_var, d_s1, d_s3, d_sl1, d_sion1, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
@@ -906,19 +1139,18 @@ int mistra_chem_budgets_device(int mech, int ncell, const double* d_var, const d
                                double* d_bgs, void* hip_stream) {
   if (ncell == 0) return 0;
   if (!d_var || !d_fix || !d_rconst) return fail("null device pointer");
-  DeviceState* D; PackDev P;
-  if (int rc = pack_dev(mech, d_var, &D, &P)) return rc;
-  LAUNCH_TRY(launch_budgets(P, ncell, d_var, d_fix, d_rconst, dt, d_bg, d_bgs, static_cast<hipStream_t>(hip_stream)));
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var, "d_var", kNeedPack, &t)) return rc;
+  LAUNCH_TRY(launch_budgets(pack_dev(*t.S), ncell, d_var, d_fix, d_rconst, dt, d_bg, d_bgs, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
 int mistra_chem_rates_env_from_c_device(int mech, int ncell, const double* d_var, const double* d_fix, double* d_env, void* hip_stream) {
   if (ncell == 0) return 0;
   if (!d_var || !d_fix || !d_env) return fail("null device pointer");
-  DeviceState* D; PackDev P;
-  if (int rc = pack_dev(mech, d_var, &D, &P)) return rc;
-  if (!D->mech[mech].rates_ready) return fail("no device rate table for this mechanism");
-  LAUNCH_TRY(launch_env_from_c(P, ncell, D->mech[mech].rates_nenv, d_var, d_fix, d_env, static_cast<hipStream_t>(hip_stream)));
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var, "d_var", kNeedPack | kNeedRates, &t)) return rc;
+  LAUNCH_TRY(launch_env_from_c(pack_dev(*t.S), ncell, t.S->rates.nenv, d_var, d_fix, d_env, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
@@ -927,24 +1159,18 @@ int mistra_chem_drive_device(int mech, int ncell, double* d_s1, double* d_s3, do
                              double* d_bg, double* d_bgs, void* hip_stream) {
   if (ncell == 0) return 0;
   if (!d_s1 || !d_s3 || !d_sl1 || !d_sion1 || !d_scal || !d_env || !d_var || !d_fix || !d_ierr || !d_stats) return fail("null device pointer");
-  DeviceState* D; PackDev P;
-  if (int rc = pack_dev(mech, d_var, &D, &P)) return rc;
-  MechState& S = D->mech[mech];
-  if (!S.rates_ready) return fail("no device rate table for this mechanism");
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var, "d_var", kNeedPack | kNeedRates, &t)) return rc;
+  MechState& S = *t.S;
   HIP_TRY(S.d_rct.reserve((size_t)ncell * (size_t)S.tab.nreact));      // (grow-only: the first call of a size allocates, i.e. synchronises)
-  LAUNCH_TRY(launch_pack(P, ncell, d_s1, d_s3, d_sl1, d_sion1, d_scal, d_var, d_fix, st));
-  LAUNCH_TRY(launch_env_from_c(P, ncell, S.rates_nenv, d_var, d_fix, d_env, st));
-  if (int rc = mistra_chem_update_rconst_device(mech, ncell, d_env, S.d_rct.p, hip_stream)) return rc;
-  if (int rc = mistra_chem_integrate_device(mech, ncell, d_var, d_fix, S.d_rct.p, tin, tin + dt, d_var, d_ierr, d_stats, d_texit_hexit, hip_stream)) return rc;
-  if (d_bg || d_bgs) LAUNCH_TRY(launch_budgets(P, ncell, d_var, d_fix, S.d_rct.p, dt, d_bg, d_bgs, st));
-  LAUNCH_TRY(launch_unpack(P, ncell, d_var, d_s1, d_s3, d_sl1, d_sion1, st));
-  return 0;
+  const ColumnDev c{d_s1, d_s3, d_sl1, d_sion1, d_scal, d_env, d_var, d_fix, S.d_rct.p, d_ierr, d_stats, d_texit_hexit, d_bg, d_bgs, nullptr, nullptr, nullptr};
+  return column_step(*t.D, mech, ncell, c, tin, dt, static_cast<hipStream_t>(hip_stream));
 }
 
-// x_drive for a batch of layers from the model's own arrays in HOST memory (include/mistra_chem.h).  The layers' slabs are gathered into one
-// pinned block, go up in one copy, the device chain of mistra_chem_drive_device runs on a private stream, everything the model gets back
-// comes down in one copy and is scattered into the model arrays.  Primary device only: a column step is 148 layers.
+// x_drive for a batch of layers from the model's own arrays in HOST memory (include/mistra_chem.h).  The layers' slabs are gathered into the
+// mechanism's pinned drive arena, go up in one copy, the column step runs on the arena's stream, everything the model gets back comes down
+// in two copies (in/out and out-only: the in-only part between them stays up) and mistra_chem_drive_end scatters it into the model arrays.
+// Primary device only: a column step is 148 layers.
 int mistra_chem_drive_begin(int mech, int nlayer, const int32_t* layer, int n, double* s1, double* s3, double* sl1, double* sion1, const double* scal,
                             const double* env, double tin, double dt, int32_t* ierr, int32_t* stats, double* t_h, double* bg, int nrxn,
                             const int32_t* bg_level, double* bgs, double* c_packed) {
@@ -952,97 +1178,51 @@ int mistra_chem_drive_begin(int mech, int nlayer, const int32_t* layer, int n, d
   if (int rc = check_call(mech, nlayer)) return rc;
   if (nlayer == 0) return 0;
   if (!layer || !s1 || !s3 || !sl1 || !sion1 || !scal || !env) return fail("null host pointer");
-  if (bg && (!bg_level || nrxn < kDims[mech][2])) return fail("bg needs bg_level and nrxn >= NREACT");
+  if (bg && (!bg_level || nrxn < kDims[mech].nreact)) return fail("bg needs bg_level and nrxn >= NREACT");
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  MechState& S = D.mech[mech];
-  if (!S.pack_ready) return fail(std::string("no hand-over table for the ") + kMechName[mech] + " mechanism");
-  if (!S.maps_ready) return fail("mistra_chem_set_species_maps has not been called for this mechanism");
-  if (!S.rates_ready) return fail("no device rate table for this mechanism");
-  if (S.pend.active) return fail("mistra_chem_drive_begin: the mechanism's previous step has not been fetched (mistra_chem_drive_end)");
+  Slot t;
+  if (int rc = on_primary(mech, kNeedPack | kNeedRates, true, &t)) return rc;
+  MechState& S = *t.S;
   for (int i = 0; i < nlayer; i++) {
     if (layer[i] < 1 || layer[i] > n) return fail("layer index out of range");
     if (bg && (bg_level[i] < 0)) return fail("bg_level out of range");
   }
-  HIP_TRY(hipSetDevice(D.id));
-  const PackTable& T = S.pack_tab;
-  const size_t nl = (size_t)nlayer, j1 = (size_t)S.map_j1, j5 = (size_t)S.map_j5, nsl = (size_t)T.j2 * T.nkc, nsi = (size_t)T.j6 * T.nkc;
-  const size_t nv = (size_t)kDims[mech][0], nf = (size_t)kDims[mech][1], nr = (size_t)kDims[mech][2], ne = (size_t)S.rates_nenv, nb = 2 * (size_t)kBudSlots;
-  // block layout (doubles): in/out part first — s1 | s3 | sl1 | sion1 | bg | bgs — then in-only — scal | env — then out-only — th(2) | hlast | int32 ierr, stats
-  size_t off = 0;
-  auto take = [&](size_t count) { const size_t at = off; off += (count + 31) & ~(size_t)31; return at; };      // 256-byte aligned sub-blocks
-  const size_t o_s1 = take(nl * j1), o_s3 = take(nl * j5), o_sl1 = take(nl * nsl), o_si = take(nl * nsi), o_bg = take(bg ? nl * 2 * nr : 0), o_bgs = take(bgs ? nl * nb : 0);
-  const size_t io_end = off;
-  const size_t o_scal = take(nl * 6), o_env = take(nl * ne);
-  const size_t in_end = off;
-  const size_t o_th = take(nl * 2), o_hl = take(nl), o_int = take((nl * 9 + 1) / 2), o_cp = take(c_packed ? nl * (nv + nf) : 0);
-  const size_t out_end = off;
-  const size_t o_var = take(nl * nv), o_fix = take(nl * nf), o_rct = take(nl * nr);      // device only
-  if (off > S.drv_cap) {
-    if (S.drv_dev) (void)hipFree(S.drv_dev);
-    if (S.drv_host) (void)hipHostFree(S.drv_host);
-    S.drv_dev = S.drv_host = nullptr; S.drv_cap = 0;
-    const size_t cap = off + off / 2;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&S.drv_dev), cap * sizeof(double)));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.drv_host), cap * sizeof(double), hipHostMallocDefault));
-    S.drv_cap = cap;
-  }
-  if (!S.drv_stream) HIP_TRY(hipStreamCreateWithFlags(&S.drv_stream, hipStreamNonBlocking));
-  double* H = S.drv_host;
-  double* Dv = S.drv_dev;
+  const DriveLayout L = drive_layout(S, mech, (size_t)nlayer, bg != nullptr, bgs != nullptr, c_packed != nullptr);
+  const size_t nl = L.nl, nb = 2 * (size_t)kBudSlots;
+  HIP_TRY(S.drive.ensure(L.end));
+  HIP_TRY(S.s_sing.reserve(nl * 8));
+  const Staging& A = S.drive;
   // ---- gather the layers (the model arrays hold layer k at stride j1 / j5 / j2*nkc / j6*nkc; bg at stride 2*nrxn per level; bgs at 2*122 per layer)
   for (size_t i = 0; i < nl; i++) {
     const size_t k = (size_t)layer[i] - 1;
-    std::memcpy(H + o_s1 + i * j1, s1 + k * j1, j1 * sizeof(double));
-    std::memcpy(H + o_s3 + i * j5, s3 + k * j5, j5 * sizeof(double));
-    std::memcpy(H + o_sl1 + i * nsl, sl1 + k * nsl, nsl * sizeof(double));
-    std::memcpy(H + o_si + i * nsi, sion1 + k * nsi, nsi * sizeof(double));
+    std::memcpy(A.h(L.s1) + i * L.j1, s1 + k * L.j1, L.j1 * sizeof(double));
+    std::memcpy(A.h(L.s3) + i * L.j5, s3 + k * L.j5, L.j5 * sizeof(double));
+    std::memcpy(A.h(L.sl1) + i * L.nsl, sl1 + k * L.nsl, L.nsl * sizeof(double));
+    std::memcpy(A.h(L.si) + i * L.nsi, sion1 + k * L.nsi, L.nsi * sizeof(double));
     if (bg) {
-      if (bg_level[i] > 0) std::memcpy(H + o_bg + i * 2 * nr, bg + ((size_t)bg_level[i] - 1) * 2 * (size_t)nrxn, 2 * nr * sizeof(double));
-      else std::memset(H + o_bg + i * 2 * nr, 0, 2 * nr * sizeof(double));
+      if (bg_level[i] > 0) std::memcpy(A.h(L.bg) + i * 2 * L.nr, bg + ((size_t)bg_level[i] - 1) * 2 * (size_t)nrxn, 2 * L.nr * sizeof(double));
+      else std::memset(A.h(L.bg) + i * 2 * L.nr, 0, 2 * L.nr * sizeof(double));
     }
-    if (bgs) std::memcpy(H + o_bgs + i * nb, bgs + k * nb, nb * sizeof(double));
+    if (bgs) std::memcpy(A.h(L.bgs) + i * nb, bgs + k * nb, nb * sizeof(double));
   }
-  std::memcpy(H + o_scal, scal, nl * 6 * sizeof(double));
-  std::memcpy(H + o_env, env, nl * ne * sizeof(double));
-  hipStream_t st = S.drv_stream;
-  HIP_TRY(hipMemcpyAsync(Dv, H, in_end * sizeof(double), hipMemcpyHostToDevice, st));
+  std::memcpy(A.h(L.scal), scal, nl * 6 * sizeof(double));
+  std::memcpy(A.h(L.env), env, nl * L.ne * sizeof(double));
+  HIP_TRY(hipMemcpyAsync(A.dev, A.host, L.in_end, hipMemcpyHostToDevice, A.st));
   // KPP's dummy product species are not set by the drivers; the reference carries over what the previous LAYER left in COMMON /GDATA_x/
   // (INTEGRATION.md §4): a batch gives every layer zeros
-  HIP_TRY(hipMemsetAsync(Dv + o_var, 0, nl * nv * sizeof(double), st));
-  int32_t* d_int = reinterpret_cast<int32_t*>(Dv + o_int);      // [nl] ierr, then [nl][8] stats
-  PackDev P{S.pk_pack.p, S.pk_fix.p, S.pk_unpack.p, S.pk_slot_id.p, S.pk_slot_first.p, S.pk_terms.p, S.pk_words.p, S.pk_acc.p, S.pk_envc.p,
-            T.n_pack(), T.n_fix(), T.n_unpack(), T.n_slots(), (int)T.terms.size() / 3, (int)T.term_words.size(), (int)T.acc.size() / 2, T.n_envc(),
-            T.nvar, T.nfix, S.tab.nreact, T.j2, T.j6, T.nkc, T.preclamp,
-            S.map_gas_m2k.p, S.map_gas_k2m.p, S.map_rad_m2k.p, S.map_rad_k2m.p, S.map_j1, S.map_j5, S.pk_aptr.p, S.pk_afac.p, S.consts.p};
-  LAUNCH_TRY(launch_pack(P, nlayer, Dv + o_s1, Dv + o_s3, Dv + o_sl1, Dv + o_si, Dv + o_scal, Dv + o_var, Dv + o_fix, st));
-  if (c_packed) {
-    HIP_TRY(hipMemcpy2DAsync(Dv + o_cp, (nv + nf) * sizeof(double), Dv + o_var, nv * sizeof(double), nv * sizeof(double), nl, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpy2DAsync(Dv + o_cp + nv, (nv + nf) * sizeof(double), Dv + o_fix, nf * sizeof(double), nf * sizeof(double), nl, hipMemcpyDeviceToDevice, st));
-  }
-  LAUNCH_TRY(launch_env_from_c(P, nlayer, S.rates_nenv, Dv + o_var, Dv + o_fix, Dv + o_env, st));
-  {
-    const RatesDev R{S.rates_consts.p, S.rates_offs.p, S.rates_words.p, S.rates_fslot.p, S.tab.nreact, S.rates_nenv};
-    LAUNCH_TRY(launch_update_rconst(R, Dv + o_env, Dv + o_rct, nlayer, st));
-  }
-  {
-    HIP_TRY(S.s_sing.reserve(nl * 8));
-    KernelArgs a = make_args(S, nlayer, Dv + o_var, Dv + o_fix, Dv + o_rct, tin, tin + dt, Dv + o_var, d_int, d_int + nl, Dv + o_th);
-    a.h_last = Dv + o_hl;
-    a.sing_rows = S.s_sing.p;
-    S.sing_start = 0; S.sing_count = nl; S.sing_one = false;
-    if (int rc = launch(D, mech, a, st)) return rc;
-  }
-  if (bg || bgs) LAUNCH_TRY(launch_budgets(P, nlayer, Dv + o_var, Dv + o_fix, Dv + o_rct, dt, bg ? Dv + o_bg : nullptr, bgs ? Dv + o_bgs : nullptr, st));
-  LAUNCH_TRY(launch_unpack(P, nlayer, Dv + o_var, Dv + o_s1, Dv + o_s3, Dv + o_sl1, Dv + o_si, st));
-  // what comes back: the in/out part and the out-only part (two copies: the in-only part between them stays up)
-  HIP_TRY(hipMemcpyAsync(H, Dv, io_end * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(H + in_end, Dv + in_end, (out_end - in_end) * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemsetAsync(A.d(L.var), 0, nl * L.nv * sizeof(double), A.st));
+  const ColumnDev c{A.d(L.s1), A.d(L.s3), A.d(L.sl1), A.d(L.si), A.d(L.scal), A.d(L.env), A.d(L.var), A.d(L.fix), A.d(L.rct),
+                    A.d<int32_t>(L.ierr), A.d<int32_t>(L.stats), A.d(L.th), bg ? A.d(L.bg) : nullptr, bgs ? A.d(L.bgs) : nullptr,
+                    c_packed ? A.d(L.cp) : nullptr, A.d(L.hl), S.s_sing.p};
+  S.sing_start = 0; S.sing_count = nl; S.sing_one = false;
+  if (int rc = column_step(*t.D, mech, nlayer, c, tin, dt, A.st)) return rc;
+  HIP_TRY(hipMemcpyAsync(A.host, A.dev, L.io_end, hipMemcpyDeviceToHost, A.st));
+  HIP_TRY(hipMemcpyAsync(A.host + L.in_end, A.dev + L.in_end, L.out_end - L.in_end, hipMemcpyDeviceToHost, A.st));
   MechState::PendingDrive& Q = S.pend;
+  Q.lay = L;
   Q.layer.assign(layer, layer + nl);
   if (bg) Q.level.assign(bg_level, bg_level + nl); else Q.level.clear();
   Q.s1 = s1; Q.s3 = s3; Q.sl1 = sl1; Q.sion1 = sion1; Q.bg = bg; Q.bgs = bgs; Q.t_h = t_h; Q.c_packed = c_packed; Q.ierr = ierr; Q.stats = stats; Q.nrxn = nrxn;
-  Q.o_s1 = o_s1; Q.o_s3 = o_s3; Q.o_sl1 = o_sl1; Q.o_si = o_si; Q.o_bg = o_bg; Q.o_bgs = o_bgs; Q.o_th = o_th; Q.o_hl = o_hl; Q.o_int = o_int; Q.o_cp = o_cp;
   Q.active = true;
   return 0;
 }
@@ -1056,31 +1236,25 @@ int mistra_chem_drive_end(int mech) {
   if (!Q.active) return fail("mistra_chem_drive_end: nothing issued for this mechanism");
   Q.active = false;
   HIP_TRY(hipSetDevice(D.id));
-  HIP_TRY(hipStreamSynchronize(S.drv_stream));
-  const PackTable& T = S.pack_tab;
-  const size_t nl = Q.layer.size(), j1 = (size_t)S.map_j1, j5 = (size_t)S.map_j5, nsl = (size_t)T.j2 * T.nkc, nsi = (size_t)T.j6 * T.nkc;
-  const size_t nv = (size_t)kDims[mech][0], nf = (size_t)kDims[mech][1], nr = (size_t)kDims[mech][2], nb = 2 * (size_t)kBudSlots;
-  const double* H = S.drv_host;
-  double *s1 = Q.s1, *s3 = Q.s3, *sl1 = Q.sl1, *sion1 = Q.sion1, *bg = Q.bg, *bgs = Q.bgs, *t_h = Q.t_h, *c_packed = Q.c_packed;
-  int32_t *ierr = Q.ierr, *stats = Q.stats;
-  const int nrxn = Q.nrxn;
-  const int32_t *layer = Q.layer.data(), *bg_level = Q.level.data();
-  const size_t o_s1 = Q.o_s1, o_s3 = Q.o_s3, o_sl1 = Q.o_sl1, o_si = Q.o_si, o_bg = Q.o_bg, o_bgs = Q.o_bgs, o_th = Q.o_th, o_hl = Q.o_hl, o_int = Q.o_int, o_cp = Q.o_cp;
+  HIP_TRY(hipStreamSynchronize(S.drive.st));
+  const DriveLayout& L = Q.lay;
+  const Staging& A = S.drive;
+  const size_t nl = L.nl, nb = 2 * (size_t)kBudSlots;
   // ---- scatter
-  const int32_t* h_int = reinterpret_cast<const int32_t*>(H + o_int);
+  const int32_t *h_ierr = A.h<int32_t>(L.ierr), *h_stats = A.h<int32_t>(L.stats);
   for (size_t i = 0; i < nl; i++) {
-    const size_t k = (size_t)layer[i] - 1;
-    std::memcpy(s1 + k * j1, H + o_s1 + i * j1, j1 * sizeof(double));
-    std::memcpy(s3 + k * j5, H + o_s3 + i * j5, j5 * sizeof(double));
-    std::memcpy(sl1 + k * nsl, H + o_sl1 + i * nsl, nsl * sizeof(double));
-    std::memcpy(sion1 + k * nsi, H + o_si + i * nsi, nsi * sizeof(double));
-    if (bg && bg_level[i] > 0) std::memcpy(bg + ((size_t)bg_level[i] - 1) * 2 * (size_t)nrxn, H + o_bg + i * 2 * nr, 2 * nr * sizeof(double));
-    if (bgs) std::memcpy(bgs + k * nb, H + o_bgs + i * nb, nb * sizeof(double));
-    if (ierr) ierr[i] = h_int[i];
-    if (stats) std::memcpy(stats + i * 8, h_int + nl + i * 8, 8 * sizeof(int32_t));
-    if (t_h) { t_h[3 * i] = H[o_th + 2 * i]; t_h[3 * i + 1] = H[o_th + 2 * i + 1]; t_h[3 * i + 2] = H[o_hl + i]; }
+    const size_t k = (size_t)Q.layer[i] - 1;
+    std::memcpy(Q.s1 + k * L.j1, A.h(L.s1) + i * L.j1, L.j1 * sizeof(double));
+    std::memcpy(Q.s3 + k * L.j5, A.h(L.s3) + i * L.j5, L.j5 * sizeof(double));
+    std::memcpy(Q.sl1 + k * L.nsl, A.h(L.sl1) + i * L.nsl, L.nsl * sizeof(double));
+    std::memcpy(Q.sion1 + k * L.nsi, A.h(L.si) + i * L.nsi, L.nsi * sizeof(double));
+    if (Q.bg && Q.level[i] > 0) std::memcpy(Q.bg + ((size_t)Q.level[i] - 1) * 2 * (size_t)Q.nrxn, A.h(L.bg) + i * 2 * L.nr, 2 * L.nr * sizeof(double));
+    if (Q.bgs) std::memcpy(Q.bgs + k * nb, A.h(L.bgs) + i * nb, nb * sizeof(double));
+    if (Q.ierr) Q.ierr[i] = h_ierr[i];
+    if (Q.stats) std::memcpy(Q.stats + i * 8, h_stats + i * 8, 8 * sizeof(int32_t));
+    if (Q.t_h) { Q.t_h[3 * i] = A.h(L.th)[2 * i]; Q.t_h[3 * i + 1] = A.h(L.th)[2 * i + 1]; Q.t_h[3 * i + 2] = A.h(L.hl)[i]; }
   }
-  if (c_packed) std::memcpy(c_packed, H + o_cp, nl * (nv + nf) * sizeof(double));
+  if (Q.c_packed) std::memcpy(Q.c_packed, A.h(L.cp), nl * (L.nv + L.nf) * sizeof(double));
   return 0;
 }
 
@@ -1092,194 +1266,82 @@ int mistra_chem_drive(int mech, int nlayer, const int32_t* layer, int n, double*
   return mistra_chem_drive_end(mech);
 }
 
+// ---- liq_parm: the device-pointer entries, then the host-buffer forms (DevBlock)
+
 int mistra_chem_fast_k_mt_device(int mech, int nlayer, const double* d_ff, const double* d_rq, const int32_t* kw, int nkw, int ka, int ifeed,
                                  int nkc_l, const double* d_cw, const double* d_cm, const double* d_freep, const double* d_alpha,
                                  const double* d_vmean, double* d_xkmt, const double* d_t, const double* d_p, double* d_vt, void* hip_stream) {
-  if (int rc = check_call(mech, 1)) return rc;
-  if (nlayer == 0) return 0;
+  if (nlayer == 0) return check_call(mech, 0);
   if (!d_ff || !d_rq || !kw || !d_cw || !d_cm || !d_freep || !d_alpha || !d_vmean || !d_xkmt) return fail("null pointer");
   if (d_vt && (!d_t || !d_p)) return fail("the sedimentation velocity needs the layers' temperature and pressure (d_t, d_p)");
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, d_xkmt) != hipSuccess) return fail("d_xkmt is not a device pointer");
-  DeviceState* D = device_slot(attr.device);
-  if (!D) return fail("the buffers live on a device mistra_chem_init(_devices) did not set up");
-  MechState& S = D->mech[mech];
-  if (!S.kmt_ready) return fail(std::string("the ") + kMechName[mech] + " mechanism has no mass-transfer routine (fast_k_mt_a: aer, fast_k_mt_t: tot)");
-  const KmtTable& T = S.kmt_tab;
-  if (nkw != T.nka || T.nka > kKmtMaxNka) return fail("kw does not have nka entries");
-  if (ka < 0 || ka > T.nka || nkc_l < 1 || nkc_l > T.nkc) return fail("ka / nkc_l out of range");
-  KmtDev K{S.kmt_lex.p, {0}, T.nx, T.nka, T.nkt, T.nkc, S.tab.nvar + S.tab.nfix, ka, ifeed, nkc_l};
-  for (int i = 0; i < T.nka; i++) {
-    if (kw[i] < 0 || kw[i] > T.nkt) return fail("kw out of range");      // the kernel's loop limits: checked here, on the host
-    K.kw[i] = kw[i];
-  }
-  HIP_TRY(hipSetDevice(D->id));
+  Slot t;
+  if (int rc = on_device(mech, nlayer, d_xkmt, "d_xkmt", kNeedKmt, &t)) return rc;
+  KmtDev K;
+  if (int rc = kmt_args(*t.S, kw, nkw, ka, ifeed, nkc_l, &K)) return rc;
   LAUNCH_TRY(launch_fast_k_mt(K, nlayer, d_ff, d_rq, d_cw, d_cm, d_freep, d_alpha, d_vmean, d_xkmt, d_t, d_p, d_vt, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
-namespace {
-// the device slot the buffer lives on and its table of Henry / equilibrium constants
-int liq_state(int mech, const void* d_out, DeviceState** D, MechState** S) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, d_out) != hipSuccess) return fail("the output is not a device pointer");
-  *D = device_slot(attr.device);
-  if (!*D) return fail("the buffers live on a device mistra_chem_init(_devices) did not set up");
-  *S = &(*D)->mech[mech];
-  if (!(*S)->liq_ready) return fail(std::string("the ") + kMechName[mech] + " mechanism has no liquid-phase routines (henry_a / equil_co_a: aer, henry_t / equil_co_t: tot)");
-  return 0;
-}
-LiqDev liq_dev(const MechState& S) {
-  const LiqTable& T = S.liq_tab;
-  return LiqDev{S.lq_hkind.p, S.lq_eof.p, S.lq_foff.p, S.lq_boff.p, S.lq_fkind.p, S.lq_farg.p, S.lq_ha0.p, S.lq_hb0.p, S.lq_fa.p, S.lq_fb.p,
-                T.nspec, T.nkc_eq, T.henry_tref, T.henry_fct, T.equil_tref};
-}
-}  // namespace
-
 int mistra_chem_henry_device(int mech, int nlayer, const double* d_tt, double* d_henry, void* hip_stream) {
-  if (int rc = check_call(mech, 1)) return rc;
-  if (nlayer == 0) return 0;
-  if (nlayer < 0) return fail("nlayer < 0");
+  if (nlayer == 0) return check_call(mech, 0);
   if (!d_tt || !d_henry) return fail("null pointer");
-  DeviceState* D;
-  MechState* S;
-  if (int rc = liq_state(mech, d_henry, &D, &S)) return rc;
-  HIP_TRY(hipSetDevice(D->id));
-  LAUNCH_TRY(launch_henry(liq_dev(*S), nlayer, d_tt, d_henry, static_cast<hipStream_t>(hip_stream)));
+  Slot t;
+  if (int rc = on_device(mech, nlayer, d_henry, "d_henry", kNeedLiq, &t)) return rc;
+  LAUNCH_TRY(launch_henry(t.S->liq.dev(), nlayer, d_tt, d_henry, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
 int mistra_chem_st_coeff_device(int mech, int nlayer, int lp_joyce14bc, int lp_buxmann15alph, const double* d_env, double* d_alpha, void* hip_stream) {
-  if (int rc = check_call(mech, 1)) return rc;
-  if (nlayer == 0) return 0;
-  if (nlayer < 0) return fail("nlayer < 0");
+  if (nlayer == 0) return check_call(mech, 0);
   if (!d_env || !d_alpha) return fail("null pointer");
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, d_alpha) != hipSuccess) return fail("the output is not a device pointer");
-  DeviceState* D = device_slot(attr.device);
-  if (!D) return fail("the buffers live on a device mistra_chem_init(_devices) did not set up");
-  const MechState& S = D->mech[mech];
-  if (!S.stc_ready) return fail(std::string("the ") + kMechName[mech] + " mechanism has no st_coeff routine (st_coeff_a: aer, st_coeff_t: tot)");
-  HIP_TRY(hipSetDevice(D->id));
+  Slot t;
+  if (int rc = on_device(mech, nlayer, d_alpha, "d_alpha", kNeedStc, &t)) return rc;
   const int v = (lp_joyce14bc ? 1 : 0) + (lp_buxmann15alph ? 2 : 0);
-  const RatesDev R{S.stc_consts[v].p, S.stc_offs[v].p, S.stc_words[v].p, nullptr, S.stc_tab.v[v].nreact, S.stc_tab.v[v].nenv};
-  LAUNCH_TRY(launch_update_rconst(R, d_env, d_alpha, nlayer, static_cast<hipStream_t>(hip_stream)));
+  LAUNCH_TRY(launch_update_rconst(t.S->stc.dev(v), d_env, d_alpha, nlayer, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
 int mistra_chem_v_mean_device(int mech, int nlayer, const double* d_tt, double* d_vmean, void* hip_stream) {
-  if (int rc = check_call(mech, 1)) return rc;
-  if (nlayer == 0) return 0;
-  if (nlayer < 0) return fail("nlayer < 0");
+  if (nlayer == 0) return check_call(mech, 0);
   if (!d_tt || !d_vmean) return fail("null pointer");
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, d_vmean) != hipSuccess) return fail("the output is not a device pointer");
-  DeviceState* D = device_slot(attr.device);
-  if (!D) return fail("the buffers live on a device mistra_chem_init(_devices) did not set up");
-  const MechState& S = D->mech[mech];
-  if (!S.vmean_ready) return fail(std::string("the ") + kMechName[mech] + " mechanism has no v_mean routine (v_mean_a: aer, v_mean_t: tot)");
-  HIP_TRY(hipSetDevice(D->id));
-  LAUNCH_TRY(launch_v_mean(S.vm_mass.p, S.vmean_tab.nspec, S.vmean_tab.coef, nlayer, d_tt, d_vmean, static_cast<hipStream_t>(hip_stream)));
+  Slot t;
+  if (int rc = on_device(mech, nlayer, d_vmean, "d_vmean", kNeedVmean, &t)) return rc;
+  const VmeanBufs& V = t.S->vmean;
+  LAUNCH_TRY(launch_v_mean(V.mass.p, V.tab.nspec, V.tab.coef, nlayer, d_tt, d_vmean, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
 
 int mistra_chem_equil_co_device(int mech, int nlayer, int nkc, int j6, const double* d_tt, const double* d_conv2, const double* d_xgamma,
                                 double* d_xkef, double* d_xkeb, void* hip_stream) {
-  if (int rc = check_call(mech, 1)) return rc;
-  if (nlayer == 0) return 0;
-  if (nlayer < 0) return fail("nlayer < 0");
+  if (nlayer == 0) return check_call(mech, 0);
   if (!d_tt || !d_conv2 || !d_xgamma || !d_xkef || !d_xkeb) return fail("null pointer");
-  DeviceState* D;
-  MechState* S;
-  if (int rc = liq_state(mech, d_xkef, &D, &S)) return rc;
-  const LiqTable& T = S->liq_tab;
-  if (nkc < T.nkc_eq) return fail("nkc is smaller than the number of bins the routine sets");
-  for (size_t i = 0; i < T.fkind.size(); i++)
-    if (T.fkind[i] == 3 && T.farg[i] > j6) return fail("j6 is smaller than an activity-coefficient index the routine reads");
-  HIP_TRY(hipSetDevice(D->id));
-  LAUNCH_TRY(launch_equil_co(liq_dev(*S), nlayer, nkc, j6, d_tt, d_conv2, d_xgamma, d_xkef, d_xkeb, static_cast<hipStream_t>(hip_stream)));
+  Slot t;
+  if (int rc = on_device(mech, nlayer, d_xkef, "d_xkef", kNeedLiq, &t)) return rc;
+  if (int rc = equil_co_check(*t.S, nkc, j6)) return rc;
+  LAUNCH_TRY(launch_equil_co(t.S->liq.dev(), nlayer, nkc, j6, d_tt, d_conv2, d_xgamma, d_xkef, d_xkeb, static_cast<hipStream_t>(hip_stream)));
   return 0;
 }
-
-// ---- host-buffer forms of the liq_parm kernels: what a Fortran caller reaches (shim/mistra_kpp_liq.f90).  One grow-only device arena and a pinned host
-//      arena of the same layout on the primary device, a private stream: a call gathers its inputs into the pinned arena (or, for caller memory that
-//      mistra_chem_pin_host registered, leaves them where they are), sends them up, runs the kernel on the same stream and fetches its outputs; one
-//      stream synchronisation per call, no allocation once the arenas have grown to the column's size.
-namespace {
-struct DevBlock {      // the arrays of one call as 256-byte aligned sub-blocks of the arenas
-  std::vector<std::pair<size_t, size_t>> parts;      // (offset, bytes)
-  std::vector<const void*> src;                      // per part: where its input comes from (nullptr: not an input)
-  std::vector<void*> dst;                            // per part: where its output goes (nullptr: not an output)
-  size_t cap = 0;
-  size_t add(size_t bytes) {
-    const size_t at = cap;
-    parts.emplace_back(at, bytes); src.push_back(nullptr); dst.push_back(nullptr);
-    cap += (bytes + 255) & ~(size_t)255;
-    return parts.size() - 1;
-  }
-  hipError_t alloc() { return g_liq.ensure(cap ? cap : 256); }
-  double* dptr(size_t i) const { return reinterpret_cast<double*>(g_liq.dev + parts[i].first); }
-  hipError_t up(size_t i, const void* from) { src[i] = from; return hipSuccess; }
-  // every transfer costs ~15 us of latency in the stream whatever its size: neighbouring staged parts travel as ONE copy (the padding between them with
-  // them), parts inside a registered caller range go straight from / to the caller's memory
-  hipError_t transfer(bool upward) {
-    size_t i = 0;
-    while (i < parts.size()) {
-      const void* p = upward ? src[i] : dst[i];
-      if (!p) { i++; continue; }
-      if (g_liq.is_pinned(p, parts[i].second)) {
-        hipError_t e = upward ? hipMemcpyAsync(g_liq.dev + parts[i].first, p, parts[i].second, hipMemcpyHostToDevice, g_liq.st)
-                              : hipMemcpyAsync(const_cast<void*>(p), g_liq.dev + parts[i].first, parts[i].second, hipMemcpyDeviceToHost, g_liq.st);
-        if (e != hipSuccess) return e;
-        i++;
-        continue;
-      }
-      size_t j = i;      // the run of staged parts i..j-1
-      while (j < parts.size() && (upward ? src[j] : dst[j]) && !g_liq.is_pinned(upward ? src[j] : dst[j], parts[j].second)) {
-        if (upward) std::memcpy(g_liq.host + parts[j].first, src[j], parts[j].second);
-        j++;
-      }
-      const size_t lo = parts[i].first, hi = parts[j - 1].first + parts[j - 1].second;
-      hipError_t e = upward ? hipMemcpyAsync(g_liq.dev + lo, g_liq.host + lo, hi - lo, hipMemcpyHostToDevice, g_liq.st)
-                            : hipMemcpyAsync(g_liq.host + lo, g_liq.dev + lo, hi - lo, hipMemcpyDeviceToHost, g_liq.st);
-      if (e != hipSuccess) return e;
-      i = j;
-    }
-    return hipSuccess;
-  }
-  hipError_t send() { return transfer(true); }      // after the last up(), before the kernel
-  hipStream_t stream() const { return g_liq.st; }
-  hipError_t down(size_t i, void* to) { dst[i] = to; return hipSuccess; }
-  hipError_t finish() {       // after the last down(): fetch, wait, hand the staged outputs to the caller
-    if (hipError_t e = transfer(false)) return e;
-    if (hipError_t e = hipStreamSynchronize(g_liq.st)) return e;
-    for (size_t i = 0; i < parts.size(); i++)
-      if (dst[i] && !g_liq.is_pinned(dst[i], parts[i].second)) std::memcpy(dst[i], g_liq.host + parts[i].first, parts[i].second);
-    return hipSuccess;
-  }
-};
-}  // namespace
 
 int mistra_chem_pin_host(void* p, size_t bytes) {
   if (int rc = lazy_init()) return rc;
   if (!p || !bytes) return fail("mistra_chem_pin_host: null range");
   std::lock_guard<std::mutex> lock(g_mu);
-  if (g_liq.is_pinned(p, bytes)) return 0;
+  if (g_pinned.contains(p, bytes)) return 0;
   const char* c = static_cast<const char*>(p);
-  for (const auto& r : g_liq.pinned)
+  for (const auto& r : g_pinned.r)
     if (c < r.first + r.second && r.first < c + bytes) return fail("mistra_chem_pin_host: the range overlaps one registered before");
   HIP_TRY(hipSetDevice(g_devs[0].id));
   HIP_TRY(hipHostRegister(p, bytes, hipHostRegisterDefault));
-  g_liq.pinned.emplace_back(c, bytes);
+  g_pinned.r.emplace_back(c, bytes);
   return 0;
 }
 
 int mistra_chem_unpin_host(void* p) {
   std::lock_guard<std::mutex> lock(g_mu);
-  for (size_t i = 0; i < g_liq.pinned.size(); i++)
-    if (g_liq.pinned[i].first == static_cast<const char*>(p)) {
+  for (size_t i = 0; i < g_pinned.r.size(); i++)
+    if (g_pinned.r[i].first == static_cast<const char*>(p)) {
       HIP_TRY(hipHostUnregister(p));
-      g_liq.pinned.erase(g_liq.pinned.begin() + (long)i);
+      g_pinned.r.erase(g_pinned.r.begin() + (long)i);
       return 0;
     }
   return fail("mistra_chem_unpin_host: not a registered range");
@@ -1294,27 +1356,24 @@ int mistra_chem_fast_k_mt(int mech, int nlayer, const double* ff, const double* 
   if (!ff || !rq || !kw || !cw || !cm || !freep || !alpha || !vmean || !xkmt) return fail("null pointer");
   if (vt && (!t || !p)) return fail("the sedimentation velocity needs the layers' temperature and pressure (t, p)");
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  const MechState& S = D.mech[mech];
-  if (!S.kmt_ready) return fail(std::string("the ") + kMechName[mech] + " mechanism has no mass-transfer routine (fast_k_mt_a: aer, fast_k_mt_t: tot)");
-  const KmtTable& T = S.kmt_tab;
-  HIP_TRY(hipSetDevice(D.id));
-  const size_t nl = (size_t)nlayer, grid = (size_t)T.nka * T.nkt, nspec = (size_t)(S.tab.nvar + S.tab.nfix), nkc = (size_t)T.nkc, d8 = sizeof(double);
+  Slot s;
+  if (int rc = on_primary(mech, kNeedKmt, false, &s)) return rc;
+  KmtDev K;
+  if (int rc = kmt_args(*s.S, kw, nkw, ka, ifeed, nkc_l, &K)) return rc;
+  const KmtTable& T = s.S->kmt.tab;
+  const size_t nl = (size_t)nlayer, grid = (size_t)T.nka * T.nkt, nspec = (size_t)(s.S->tab.nvar + s.S->tab.nfix), nkc = (size_t)T.nkc, d8 = sizeof(double);
   DevBlock B;
   const size_t i_ff = B.add(nl * grid * d8), i_rq = B.add(grid * d8), i_cw = B.add(nl * nkc * d8), i_cm = B.add(nl * nkc * d8), i_fp = B.add(nl * d8),
                i_al = B.add(nl * nspec * d8), i_vm = B.add(nl * nspec * d8), i_xk = B.add(nl * nkc * nspec * d8), i_t = B.add(nl * d8), i_p = B.add(nl * d8),
                i_vt = B.add(nl * nkc * d8);
   HIP_TRY(B.alloc());
-  HIP_TRY(B.up(i_ff, ff)); HIP_TRY(B.up(i_rq, rq)); HIP_TRY(B.up(i_cw, cw)); HIP_TRY(B.up(i_cm, cm)); HIP_TRY(B.up(i_fp, freep)); HIP_TRY(B.up(i_al, alpha));
-  HIP_TRY(B.up(i_vm, vmean)); HIP_TRY(B.up(i_xk, xkmt));
-  if (vt) { HIP_TRY(B.up(i_t, t)); HIP_TRY(B.up(i_p, p)); HIP_TRY(B.up(i_vt, vt)); }
+  B.up(i_ff, ff); B.up(i_rq, rq); B.up(i_cw, cw); B.up(i_cm, cm); B.up(i_fp, freep); B.up(i_al, alpha); B.up(i_vm, vmean); B.up(i_xk, xkmt);
+  if (vt) { B.up(i_t, t); B.up(i_p, p); B.up(i_vt, vt); }
   HIP_TRY(B.send());
-  if (int rc = mistra_chem_fast_k_mt_device(mech, nlayer, B.dptr(i_ff), B.dptr(i_rq), kw, nkw, ka, ifeed, nkc_l, B.dptr(i_cw), B.dptr(i_cm),
-                                            B.dptr(i_fp), B.dptr(i_al), B.dptr(i_vm), B.dptr(i_xk), vt ? B.dptr(i_t) : nullptr,
-                                            vt ? B.dptr(i_p) : nullptr, vt ? B.dptr(i_vt) : nullptr, B.stream()))
-    return rc;
-  HIP_TRY(B.down(i_xk, xkmt));
-  if (vt) HIP_TRY(B.down(i_vt, vt));
+  LAUNCH_TRY(launch_fast_k_mt(K, nlayer, B.dptr(i_ff), B.dptr(i_rq), B.dptr(i_cw), B.dptr(i_cm), B.dptr(i_fp), B.dptr(i_al), B.dptr(i_vm), B.dptr(i_xk),
+                              vt ? B.dptr(i_t) : nullptr, vt ? B.dptr(i_p) : nullptr, vt ? B.dptr(i_vt) : nullptr, B.stream()));
+  B.down(i_xk, xkmt);
+  if (vt) B.down(i_vt, vt);
   HIP_TRY(B.finish());
   return 0;
 }
@@ -1325,18 +1384,16 @@ int mistra_chem_henry(int mech, int nlayer, const double* tt, double* henry) {
   if (nlayer == 0) return 0;
   if (!tt || !henry) return fail("null pointer");
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  const MechState& S = D.mech[mech];
-  if (!S.liq_ready) return fail(std::string("the ") + kMechName[mech] + " mechanism has no liquid-phase routines (henry_a: aer, henry_t: tot)");
-  HIP_TRY(hipSetDevice(D.id));
-  const size_t nl = (size_t)nlayer, nspec = (size_t)S.liq_tab.nspec;
+  Slot s;
+  if (int rc = on_primary(mech, kNeedLiq, false, &s)) return rc;
+  const size_t nl = (size_t)nlayer, nspec = (size_t)s.S->liq.tab.nspec;
   DevBlock B;
   const size_t i_t = B.add(nl * sizeof(double)), i_h = B.add(nl * nspec * sizeof(double));
   HIP_TRY(B.alloc());
-  HIP_TRY(B.up(i_t, tt));
+  B.up(i_t, tt);
   HIP_TRY(B.send());
-  if (int rc = mistra_chem_henry_device(mech, nlayer, B.dptr(i_t), B.dptr(i_h), B.stream())) return rc;
-  HIP_TRY(B.down(i_h, henry));
+  LAUNCH_TRY(launch_henry(s.S->liq.dev(), nlayer, B.dptr(i_t), B.dptr(i_h), B.stream()));
+  B.down(i_h, henry);
   HIP_TRY(B.finish());
   return 0;
 }
@@ -1348,20 +1405,19 @@ int mistra_chem_dry_rates(int gas, int nlayer, const double* tt, const double* f
   if (nlayer < 0) return fail("nlayer < 0");
   if (!tt || !freep || !rcd || !xkmtd || !xeq || (gas ? !henry4 : !vmean4)) return fail("null pointer");
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  HIP_TRY(hipSetDevice(D.id));
+  HIP_TRY(hipSetDevice(g_devs[0].id));
   const size_t nl = (size_t)nlayer, d8 = sizeof(double);
   DevBlock B;
   const size_t i_t = B.add(nl * d8), i_f = B.add(nl * d8), i_r = B.add(nl * 2 * d8), i_v = B.add(nl * 4 * d8), i_x = B.add(nl * 8 * d8), i_q = B.add(nl * d8),
                i_h = B.add(nl * 4 * d8);
   HIP_TRY(B.alloc());
-  HIP_TRY(B.up(i_t, tt)); HIP_TRY(B.up(i_f, freep)); HIP_TRY(B.up(i_r, rcd));
-  if (gas) HIP_TRY(B.up(i_h, henry4)); else HIP_TRY(B.up(i_v, vmean4));
+  B.up(i_t, tt); B.up(i_f, freep); B.up(i_r, rcd);
+  if (gas) B.up(i_h, henry4); else B.up(i_v, vmean4);
   const DryRatesArgs A{nlayer, gas ? 1 : 0, B.dptr(i_t), B.dptr(i_f), B.dptr(i_r), B.dptr(i_v), B.dptr(i_x), B.dptr(i_q), B.dptr(i_h)};
   HIP_TRY(B.send());
   LAUNCH_TRY(launch_dry_rates(A, B.stream()));
-  HIP_TRY(B.down(i_x, xkmtd)); HIP_TRY(B.down(i_q, xeq));
-  if (gas) HIP_TRY(B.down(i_h, henry4));
+  B.down(i_x, xkmtd); B.down(i_q, xeq);
+  if (gas) B.down(i_h, henry4);
   HIP_TRY(B.finish());
   return 0;
 }
@@ -1375,16 +1431,15 @@ int mistra_chem_cw_rc(int nlayer, int nkt, int nka, int dry, const double* ff, c
   for (int i = 0; i < nka; i++)
     if (kw[i] < 0 || kw[i] > nkt) return fail("kw out of range");      // the kernel's loop limits: checked here, on the host
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  HIP_TRY(hipSetDevice(D.id));
+  HIP_TRY(hipSetDevice(g_devs[0].id));
   const size_t nl = (size_t)nlayer, grid = (size_t)nka * nkt, nb = dry ? 2 : 4, d8 = sizeof(double);
   DevBlock B;
   const size_t i_ff = B.add(nl * grid * d8), i_rq = B.add(grid * d8), i_e = B.add((size_t)nkt * d8), i_kw = B.add((size_t)nka * 4), i_feu = B.add(nl * d8),
                i_cl = B.add(nl * 4 * 4), i_rc = B.add(nl * nb * d8), i_cw = B.add(nl * nb * d8), i_cm = B.add(nl * nb * d8), i_cv = B.add(nl * nb * d8),
                i_bl = B.add(nl * 4);
   HIP_TRY(B.alloc());
-  HIP_TRY(B.up(i_ff, ff)); HIP_TRY(B.up(i_rq, rq)); HIP_TRY(B.up(i_kw, kw));
-  if (!dry) { HIP_TRY(B.up(i_e, e)); HIP_TRY(B.up(i_feu, feu)); HIP_TRY(B.up(i_cl, cloud)); }
+  B.up(i_ff, ff); B.up(i_rq, rq); B.up(i_kw, kw);
+  if (!dry) { B.up(i_e, e); B.up(i_feu, feu); B.up(i_cl, cloud); }
   CwRcArgs A{};
   A.nlayer = nlayer; A.nkt = nkt; A.nka = nka; A.ka = ka; A.ial = ifeed == 2 ? 2 : 1; A.dry = dry ? 1 : 0;
   if (!dry) { A.xcryssulf = crys4[0]; A.xcrysss = crys4[1]; A.xdelisulf = crys4[2]; A.xdeliss = crys4[3]; }
@@ -1393,8 +1448,8 @@ int mistra_chem_cw_rc(int nlayer, int nkt, int nka, int dry, const double* ff, c
   A.below = reinterpret_cast<int32_t*>(B.dptr(i_bl));
   HIP_TRY(B.send());
   LAUNCH_TRY(launch_cw_rc(A, B.stream()));
-  HIP_TRY(B.down(i_rc, rc)); HIP_TRY(B.down(i_cw, cw));
-  if (!dry) { HIP_TRY(B.down(i_cm, cm)); HIP_TRY(B.down(i_cv, conv2)); if (below) HIP_TRY(B.down(i_bl, below)); }
+  B.down(i_rc, rc); B.down(i_cw, cw);
+  if (!dry) { B.down(i_cm, cm); B.down(i_cv, conv2); if (below) B.down(i_bl, below); }
   HIP_TRY(B.finish());
   return 0;
 }
@@ -1405,18 +1460,17 @@ int mistra_chem_st_coeff(int mech, int nlayer, int lp_joyce14bc, int lp_buxmann1
   if (nlayer == 0) return 0;
   if (!env || !alpha) return fail("null pointer");
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  const MechState& S = D.mech[mech];
-  if (!S.stc_ready) return fail(std::string("the ") + kMechName[mech] + " mechanism has no st_coeff routine (st_coeff_a: aer, st_coeff_t: tot)");
-  HIP_TRY(hipSetDevice(D.id));
-  const size_t nl = (size_t)nlayer, nspec = (size_t)S.stc_tab.v[0].nreact, nenv = (size_t)S.stc_tab.v[0].nenv;
+  Slot s;
+  if (int rc = on_primary(mech, kNeedStc, false, &s)) return rc;
+  const int v = (lp_joyce14bc ? 1 : 0) + (lp_buxmann15alph ? 2 : 0);
+  const size_t nl = (size_t)nlayer, nspec = (size_t)s.S->stc.tab.v[0].nreact, nenv = (size_t)s.S->stc.tab.v[0].nenv;
   DevBlock B;
   const size_t i_e = B.add(nl * nenv * sizeof(double)), i_a = B.add(nl * nspec * sizeof(double));
   HIP_TRY(B.alloc());
-  HIP_TRY(B.up(i_e, env));
+  B.up(i_e, env);
   HIP_TRY(B.send());
-  if (int rc = mistra_chem_st_coeff_device(mech, nlayer, lp_joyce14bc, lp_buxmann15alph, B.dptr(i_e), B.dptr(i_a), B.stream())) return rc;
-  HIP_TRY(B.down(i_a, alpha));
+  LAUNCH_TRY(launch_update_rconst(s.S->stc.dev(v), B.dptr(i_e), B.dptr(i_a), nlayer, B.stream()));
+  B.down(i_a, alpha);
   HIP_TRY(B.finish());
   return 0;
 }
@@ -1427,18 +1481,17 @@ int mistra_chem_v_mean(int mech, int nlayer, const double* tt, double* vmean) {
   if (nlayer == 0) return 0;
   if (!tt || !vmean) return fail("null pointer");
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  const MechState& S = D.mech[mech];
-  if (!S.vmean_ready) return fail(std::string("the ") + kMechName[mech] + " mechanism has no v_mean routine (v_mean_a: aer, v_mean_t: tot)");
-  HIP_TRY(hipSetDevice(D.id));
-  const size_t nl = (size_t)nlayer, nspec = (size_t)S.vmean_tab.nspec;
+  Slot s;
+  if (int rc = on_primary(mech, kNeedVmean, false, &s)) return rc;
+  const VmeanBufs& V = s.S->vmean;
+  const size_t nl = (size_t)nlayer, nspec = (size_t)V.tab.nspec;
   DevBlock B;
   const size_t i_t = B.add(nl * sizeof(double)), i_v = B.add(nl * nspec * sizeof(double));
   HIP_TRY(B.alloc());
-  HIP_TRY(B.up(i_t, tt));
+  B.up(i_t, tt);
   HIP_TRY(B.send());
-  if (int rc = mistra_chem_v_mean_device(mech, nlayer, B.dptr(i_t), B.dptr(i_v), B.stream())) return rc;
-  HIP_TRY(B.down(i_v, vmean));
+  LAUNCH_TRY(launch_v_mean(V.mass.p, V.tab.nspec, V.tab.coef, nlayer, B.dptr(i_t), B.dptr(i_v), B.stream()));
+  B.down(i_v, vmean);
   HIP_TRY(B.finish());
   return 0;
 }
@@ -1449,19 +1502,17 @@ int mistra_chem_equil_co(int mech, int nlayer, int nkc, int j6, const double* tt
   if (nlayer == 0) return 0;
   if (!tt || !conv2 || !xgamma || !xkef || !xkeb || nkc < 1 || j6 < 1) return fail("null pointer or bad dimensions");
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  const MechState& S = D.mech[mech];
-  if (!S.liq_ready) return fail(std::string("the ") + kMechName[mech] + " mechanism has no liquid-phase routines (equil_co_a: aer, equil_co_t: tot)");
-  HIP_TRY(hipSetDevice(D.id));
-  const size_t nl = (size_t)nlayer, nspec = (size_t)S.liq_tab.nspec, d8 = sizeof(double);
+  Slot s;
+  if (int rc = on_primary(mech, kNeedLiq, false, &s)) return rc;
+  if (int rc = equil_co_check(*s.S, nkc, j6)) return rc;
+  const size_t nl = (size_t)nlayer, nspec = (size_t)s.S->liq.tab.nspec, d8 = sizeof(double);
   DevBlock B;
   const size_t i_t = B.add(nl * d8), i_c = B.add(nl * nkc * d8), i_g = B.add(nl * nkc * j6 * d8), i_f = B.add(nl * nkc * nspec * d8), i_b = B.add(nl * nkc * nspec * d8);
   HIP_TRY(B.alloc());
-  HIP_TRY(B.up(i_t, tt)); HIP_TRY(B.up(i_c, conv2)); HIP_TRY(B.up(i_g, xgamma)); HIP_TRY(B.up(i_f, xkef)); HIP_TRY(B.up(i_b, xkeb));
+  B.up(i_t, tt); B.up(i_c, conv2); B.up(i_g, xgamma); B.up(i_f, xkef); B.up(i_b, xkeb);
   HIP_TRY(B.send());
-  if (int rc = mistra_chem_equil_co_device(mech, nlayer, nkc, j6, B.dptr(i_t), B.dptr(i_c), B.dptr(i_g), B.dptr(i_f), B.dptr(i_b), B.stream()))
-    return rc;
-  HIP_TRY(B.down(i_f, xkef)); HIP_TRY(B.down(i_b, xkeb));
+  LAUNCH_TRY(launch_equil_co(s.S->liq.dev(), nlayer, nkc, j6, B.dptr(i_t), B.dptr(i_c), B.dptr(i_g), B.dptr(i_f), B.dptr(i_b), B.stream()));
+  B.down(i_f, xkef); B.down(i_b, xkeb);
   HIP_TRY(B.finish());
   return 0;
 }
@@ -1478,11 +1529,11 @@ int mistra_chem_debug_first_step(int mech, int ncell, const double* var_in, cons
   if (ncell == 0) return 0;
   if (!var_in || !fix || !rconst || !dump) return fail("null host pointer");
   std::lock_guard<std::mutex> lock(g_mu);
-  DeviceState& D = g_devs[0];
-  HIP_TRY(hipSetDevice(D.id));
-  MechState& S = D.mech[mech];
-  const size_t nv = (size_t)kDims[mech][0], nf = (size_t)kDims[mech][1], nr = (size_t)kDims[mech][2], nc = (size_t)ncell;
-  const size_t per = 5 * nv + 2 * (size_t)kDims[mech][3] + 2;
+  Slot t;
+  if (int rc = on_primary(mech, 0, true, &t)) return rc;
+  MechState& S = *t.S;
+  const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact, nc = (size_t)ncell;
+  const size_t per = 5 * nv + 2 * (size_t)kDims[mech].lu_nonzero + 2;
   DevBuf<double> d_dump;
   HIP_TRY(S.s_var.reserve(nc * nv));
   HIP_TRY(S.s_fix.reserve(nc * nf));
@@ -1496,7 +1547,7 @@ int mistra_chem_debug_first_step(int mech, int ncell, const double* var_in, cons
   HIP_TRY(hipMemcpy(S.s_rct.p, rconst, nc * nr * sizeof(double), hipMemcpyHostToDevice));
   KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, tin, tout, S.s_var.p, S.s_ierr.p, S.s_stats.p, nullptr);
   a.dump = d_dump.p;
-  if (int rc = launch(D, mech, a, nullptr)) return rc;
+  if (int rc = launch(*t.D, mech, a, nullptr)) return rc;
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(dump, d_dump.p, nc * per * sizeof(double), hipMemcpyDeviceToHost));
   d_dump.release();
@@ -1537,8 +1588,10 @@ static int integrate_host(int mech, int ncell, const double* var_in, const doubl
   if (ncell == 0) return 0;
   if (!var_in || !fix || !var_out || (!rconst && !env)) return fail("null host pointer");
   std::lock_guard<std::mutex> lock(g_mu);
-  const size_t nv = (size_t)kDims[mech][0], nf = (size_t)kDims[mech][1], nr = (size_t)kDims[mech][2];
-  const size_t ne = env ? (size_t)g_devs[0].mech[mech].rates_nenv : 0;
+  Slot t;
+  if (int rc = on_primary(mech, env ? kNeedRates : 0, true, &t)) return rc;
+  const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact;
+  const size_t ne = env ? (size_t)t.S->rates.nenv : 0;
   const int ndev = (int)g_devs.size();
   for (auto& d : g_devs) d.mech[mech].sing_count = 0;
   if (ndev == 1 || ncell < 2 * ndev) {
@@ -1589,52 +1642,44 @@ int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, doub
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, 1)) return rc;
   if (!gdata || !tin || !tout) return fail("null pointer");
-  const int nv = kDims[mech][0], nf = kDims[mech][1], nr = kDims[mech][2];
+  const int nv = kDims[mech].nvar, nf = kDims[mech].nfix, nr = kDims[mech].nreact;
   double* c = static_cast<double*>(gdata);          // C(NSPEC) = VAR | FIX
-  double* rconst = c + nv + nf;                     // RCONST(NREACT)
-  double* atol = rconst + nr + 2;                   // after TIME, DT
+  double* atol = c + nv + nf + nr + 2;              // after RCONST(NREACT), TIME, DT
   double* rtol = atol + nv;
   double* stepmin = rtol + nv;
   for (int i = 0; i < nv; i++) { rtol[i] = 1.0e-3; atol[i] = 1.0e-25; }   // INTEGRATE_x, gas.f:745-746
-  int32_t ierr = 0;
-  DeviceState& D = g_devs[0];
-  MechState& S = D.mech[mech];
-  {
-    // One call = one cell: what costs here is synchronisation, not bytes.  /GDATA_x/ holds C and RCONST back to back, so
-    // the inputs go up in ONE copy from a pinned mirror and everything the kernel writes comes back in ONE, on a private
-    // stream with a single wait (seven blocking calls before: 340 us per gas call, of which the kernel is a fraction).
-    std::lock_guard<std::mutex> lock(g_mu);
-    HIP_TRY(hipSetDevice(D.id));
-    const size_t n_in = (size_t)(nv + nf + nr), n_out = (size_t)nv + 2 + 1 + 5 + 4;   // VAR | Texit Hexit | H at exit | 9 int32 in 5 doubles | 8 zero-pivot rows in 4
-    if (!S.one_dev) {
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&S.one_dev), (n_in + n_out) * sizeof(double)));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.one_host), (n_in + n_out) * sizeof(double), hipHostMallocDefault));
-      HIP_TRY(hipStreamCreateWithFlags(&S.one_stream, hipStreamNonBlocking));
-    }
-    std::memcpy(S.one_host, c, n_in * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(S.one_dev, S.one_host, n_in * sizeof(double), hipMemcpyHostToDevice, S.one_stream));
-    double* d_out = S.one_dev + n_in;
-    int32_t* d_stats = reinterpret_cast<int32_t*>(d_out + nv + 3);
-    KernelArgs a = make_args(S, 1, S.one_dev, S.one_dev + nv, S.one_dev + nv + nf, *tin, *tout, d_out, d_stats + 8, d_stats, d_out + nv);
-    a.h_last = d_out + nv + 2;
-    a.sing_rows = d_stats + 10;
-    if (int rc = launch(D, mech, a, S.one_stream)) return rc;
-    double* h_out = S.one_host + n_in;
-    HIP_TRY(hipMemcpyAsync(h_out, d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, S.one_stream));
-    HIP_TRY(hipStreamSynchronize(S.one_stream));
-    std::memcpy(c, h_out, (size_t)nv * sizeof(double));
-    const int32_t* st = reinterpret_cast<const int32_t*>(h_out + nv + 3);
-    std::memcpy(&ierr, st + 8, sizeof ierr);
-    if (ierr_out) *ierr_out = ierr;
-    if (nsng) *nsng = st[7];
-    for (auto& d : g_devs) d.mech[mech].sing_count = 0;
-    std::memcpy(S.one_sing, st + 10, sizeof S.one_sing);
-    S.sing_one = true;
-    if (t_err) *t_err = h_out[nv];         // T when the integrator returned
-    if (h_err) *h_err = h_out[nv + 2];     // H when the integrator returned (what ros_ErrorMsg_x prints)
-    *tin = h_out[nv];          // TIN = RPAR(11), exit time
-    *stepmin = h_out[nv + 1];  // STEPMIN = RPAR(12), last step
-  }
+  // One call = one cell: what costs here is synchronisation, not bytes.  /GDATA_x/ holds C and RCONST back to back, so the inputs go
+  // up in ONE copy from the pinned mirror of the mechanism's one-cell arena and everything the kernel writes comes back in ONE, on the
+  // arena's stream with a single wait (seven blocking calls before: 340 us per gas call, of which the kernel is a fraction).
+  std::lock_guard<std::mutex> lock(g_mu);
+  Slot t;
+  if (int rc = on_primary(mech, 0, true, &t)) return rc;
+  MechState& S = *t.S;
+  const size_t d8 = sizeof(double), n_in = (size_t)(nv + nf + nr) * d8;
+  Layout B;
+  const size_t o_in = B.take(n_in);      // C | RCONST
+  const size_t o_var = B.take(nv * d8), o_th = B.take(2 * d8), o_hl = B.take(d8), o_ierr = B.take(4), o_stats = B.take(8 * 4), o_sing = B.take(8 * 4);
+  HIP_TRY(S.one.ensure(B.end));
+  const Staging& A = S.one;
+  std::memcpy(A.h(o_in), c, n_in);
+  HIP_TRY(hipMemcpyAsync(A.d(o_in), A.h(o_in), n_in, hipMemcpyHostToDevice, A.st));
+  KernelArgs a = make_args(S, 1, A.d(o_in), A.d(o_in) + nv, A.d(o_in) + nv + nf, *tin, *tout, A.d(o_var), A.d<int32_t>(o_ierr), A.d<int32_t>(o_stats), A.d(o_th));
+  a.h_last = A.d(o_hl);
+  a.sing_rows = A.d<int32_t>(o_sing);
+  if (int rc = launch(*t.D, mech, a, A.st)) return rc;
+  HIP_TRY(hipMemcpyAsync(A.h(o_var), A.d(o_var), B.end - o_var, hipMemcpyDeviceToHost, A.st));
+  HIP_TRY(hipStreamSynchronize(A.st));
+  std::memcpy(c, A.h(o_var), (size_t)nv * d8);
+  const int32_t ierr = *A.h<int32_t>(o_ierr);
+  if (ierr_out) *ierr_out = ierr;
+  if (nsng) *nsng = A.h<int32_t>(o_stats)[7];
+  for (auto& d : g_devs) d.mech[mech].sing_count = 0;
+  std::memcpy(S.one_sing, A.h<int32_t>(o_sing), sizeof S.one_sing);
+  S.sing_one = true;
+  if (t_err) *t_err = A.h(o_th)[0];       // T when the integrator returned
+  if (h_err) *h_err = A.h(o_hl)[0];       // H when the integrator returned (what ros_ErrorMsg_x prints)
+  *tin = A.h(o_th)[0];                    // TIN = RPAR(11), exit time
+  *stepmin = A.h(o_th)[1];                // STEPMIN = RPAR(12), last step
   return 0;
 }
 
@@ -1642,6 +1687,8 @@ int mistra_chem_singular_rows(int mech, int cell, int32_t* rows8) {
   if (int rc = check_call(mech, 1)) return rc;
   if (!rows8 || cell < 0) return fail("bad argument");
   std::lock_guard<std::mutex> lock(g_mu);
+  Slot t;
+  if (int rc = on_primary(mech, 0, true, &t)) return rc;      // (the rows of an open column step are not written yet)
   for (auto& D : g_devs) {
     MechState& S = D.mech[mech];
     if (S.sing_one && cell == 0 && &D == &g_devs[0]) {

@@ -202,6 +202,51 @@ def test_mechanisms_of_a_step_side_by_side(chem, case):
     assert min(t[True]) < 1.05 * min(t[False])
 
 
+def test_an_open_step_refuses_the_calls_that_would_touch_its_buffers(chem):
+    """While a gas step issued by mistra_chem_drive_begin is open, the gas mechanism's host-buffer calls that reuse its staging, species maps or
+    singular-row record are refused (include/mistra_chem.h); the aer mechanism's calls go on; the step's results are those of a plain call.  The
+    calls that would free memory the queued kernels read come last, so that a broken guard fails the test before they run."""
+    g = _load("base1")
+    idx = np.nonzero(g["mech"] == 0)[0]
+    maps = [g["gas_" + key] for key in ("gas_m2k", "gas_k2m", "rad_m2k", "rad_k2m")]
+    chem.set_species_maps("gas", *maps)
+    env = g["env"][idx, :NENV["gas"]].copy()
+    gas = dict(np.load(os.path.join(REPO, "tests", "golden", "integrate_gas.npz")))
+    aer = dict(np.load(os.path.join(REPO, "tests", "golden", "integrate_aer.npz")))
+
+    def step(a, begin_only=False):
+        return chem.drive_host("gas", g["k"][idx], a["s1"], a["s3"], a["sl1"], a["sion1"], g["scal"][idx], env, 0.0, 10.0, bg=a["bg"],
+                               bg_level=g["level"][idx], bgs=a["bgs"], begin_only=begin_only)
+
+    def aer_cell():
+        res, th = chem.integrate_ex("aer", aer["var_in"][:1], aer["fix"][:1], aer["rconst"][:1], aer["tin"][0], aer["tout"][0])
+        assert res.ierr[0] == 1
+        return res.var, th
+
+    a1 = _model_arrays(g)
+    o1 = step(a1)
+    a2 = _model_arrays(g)
+    r = step(a2, begin_only=True)
+    try:
+        with pytest.raises(chem.MistraChemError):
+            chem.singular_rows("gas", 0)
+        with pytest.raises(chem.MistraChemError):
+            chem.integrate_ex("gas", gas["var_in"][:1], gas["fix"][:1], gas["rconst"][:1])
+        with pytest.raises(chem.MistraChemError):
+            chem.set_species_maps("gas", *maps)
+        with pytest.raises(chem.MistraChemError):
+            step(_model_arrays(g))
+        aer_open = aer_cell()
+    finally:
+        chem.drive_host_end("gas")
+    for key in a1:
+        assert np.array_equal(a1[key], a2[key]), "%s differs from a plain call of the same step" % key
+    for x, y in zip(o1, r[:3]):
+        assert np.array_equal(x, y)
+    for x, y in zip(aer_open, aer_cell()):
+        assert np.array_equal(x, y)
+
+
 needs_flang = pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/flang"), reason="no Fortran compiler here")
 
 
