@@ -69,8 +69,8 @@ def build_lib(force=False, verbose=False):
 
 def ring_register_report(isa_path=None):
     """Checks the one assumption the table look-ahead ring of ros3_kernel.hip rests on (see the comment there): in the
-    non-inlined device functions, every register the COMPILER allocates stays below the ring's blocks (v192.. or, in the
-    low placement, v64..), so a
+    non-inlined device functions, every register the COMPILER allocates — named outside inline asm, or chosen by it for an asm
+    statement's result — stays below the ring's blocks (v192.. or, in the low placement, v64..), so a
     table load landing in the ring can never hit a compiler value.  Compiles the kernel source to gfx950 assembly and
     scans it.  Returns {function: highest VGPR named outside inline asm}; raises if a ring-using function reaches its ring."""
     import re
@@ -101,6 +101,15 @@ def ring_register_report(isa_path=None):
             elif not in_asm and not l.strip().startswith((";", ".")):
                 for m in re.finditer(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]", l):
                     hi = max(hi, int(m.group(1) or m.group(3)))
+            elif in_asm and not l.strip().startswith((";", ".")):
+                # inside asm: the destination the compiler chose for an asm result (an LDS gather, a multiply-add...) — every value
+                # of the compiler's is written either outside asm or here; the ring loads' own destinations and the ring registers
+                # read as sources (gather addresses, table words) are the ring itself
+                t = l.split(";")[0].strip().split(None, 1)
+                if len(t) == 2 and t[0].startswith("v_") or len(t) == 2 and t[0].startswith("ds_read"):
+                    m = re.match(r"\s*(?:v(\d+)\b|v\[(\d+):(\d+)\])", t[1])
+                    if m:
+                        hi = max(hi, int(m.group(1) or m.group(3)))
         report[name] = hi
         low = re.search(r"(gsum_run|tail_solve|tail_solve_columns|scale_run)I.*Lb([01])E+[A-Z]", name)       # last template argument: ring placement LOW
         if low:
@@ -121,8 +130,11 @@ def ring_register_report(isa_path=None):
 #         states later (round 3: a table base moved to scalar registers in front of a global_load -> memory access fault);
 #   (ii)  a DPP instruction whose DPP-read source (src0) was written by a VALU instruction less than 2 wait states earlier (the hardware
 #         does not interlock the read: tools/ubench/dpp.hip returns wrong sums with none);
-#   (iii) an `s_waitcnt vmcnt(N)` inside an asm block with N not below the number of distinct registers-in-flight slots the function's own
-#         asm loads fill (such a wait can never guarantee that the oldest slot has landed).
+#   (iii) an `s_waitcnt vmcnt(N)` inside an asm block with N not below the number of distinct registers-in-flight slots of its ring (such
+#         a wait can never guarantee that the oldest slot has landed): the slots the block's own loads fill where it issues loads (an
+#         executor that streams its ring inside one statement: vm_exec_asm.inc, gsum_exec_asm.inc), else the slots all asm loads of the
+#         function fill (a ring loaded and waited for by separate statements: the ring helpers, the tail chain).  Per block, not per
+#         function: an integrating kernel inlines rings of several depths, whose union would pass a wait too deep for the smaller one.
 # An instruction is one wait state, `s_nop N` is N + 1.  The scan is linear per function (labels are ignored: conservative for the
 # straight-line blocks these sequences are).
 def isa_hazard_report(isa_text, sgpr_vmem_wait=5, dpp_wait=2, seen=None):
@@ -149,7 +161,11 @@ def isa_hazard_report(isa_text, sgpr_vmem_wait=5, dpp_wait=2, seen=None):
         if func is None:
             return
         seen["functions"] += 1
-        depth = len({i["ops"][0] for i in insts if i["asm"] and i["op"].startswith(("global_load", "buffer_load")) and i["ops"]})
+        loads = [i for i in insts if i["asm"] and i["op"].startswith(("global_load", "buffer_load")) and i["ops"]]
+        depth = len({i["ops"][0] for i in loads})
+        block_depth = {}
+        for i in loads:
+            block_depth.setdefault(i["block"], set()).add(i["ops"][0])
         for n, it in enumerate(insts):
             if not it["asm"]:
                 continue
@@ -185,18 +201,20 @@ def isa_hazard_report(isa_text, sgpr_vmem_wait=5, dpp_wait=2, seen=None):
             if op == "s_waitcnt" and depth:
                 m = re.search(r"vmcnt\((\d+)\)", it["text"])
                 seen["vmcnt"] += 1 if m else 0
-                if m and int(m.group(1)) >= depth:
-                    hits.append("%s: line %d `%s` waits for at most %s loads in flight, the function's asm loads fill only %d slots" %
-                                (func, it["line"], it["text"], m.group(1), depth))
+                own = len(block_depth.get(it["block"], ()))
+                if m and int(m.group(1)) >= (own or depth):
+                    hits.append("%s: line %d `%s` waits for at most %s loads in flight, %s fill only %d slots" %
+                                (func, it["line"], it["text"], m.group(1), "its asm block's loads" if own else "the function's asm loads",
+                                 own or depth))
 
-    in_asm = False
+    in_asm, block = False, 0
     for ln, raw in enumerate(isa_text.split("\n"), 1):
         if re.match(r"^[A-Za-z_.$][\w.$]*:", raw) and not raw.startswith(".L"):
             flush()
             func, insts, in_asm = raw.split(":")[0], [], False
             continue
         if "ASMSTART" in raw:
-            in_asm = True
+            in_asm, block = True, block + 1
             continue
         if "ASMEND" in raw:
             in_asm = False
@@ -212,7 +230,7 @@ def isa_hazard_report(isa_text, sgpr_vmem_wait=5, dpp_wait=2, seen=None):
         wait = 1
         if op == "s_nop" and ops:
             wait = int(ops[0], 0) + 1
-        insts.append({"op": op, "ops": ops, "asm": in_asm, "line": ln, "text": t, "wait": wait})
+        insts.append({"op": op, "ops": ops, "asm": in_asm, "block": block if in_asm else 0, "line": ln, "text": t, "wait": wait})
     flush()
     return hits
 

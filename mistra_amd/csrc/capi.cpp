@@ -278,7 +278,7 @@ struct KernelBufs {      // the integrator's (ros3_kernel.hip; make_args)
   DevBuf<uint16_t> jvs_pos, zero_pos, diag_pos, schur_cells;
   GsBufs vdot, jvs;
   VmBufs lu, solve_head_fwd, solve_head_bwd;
-  DevBuf<uint32_t> tail_fwd, tail_bwd, lu_scale, dense_rows;
+  DevBuf<uint32_t> tail_fwd, tail_bwd, tail_fwd_addr[2], tail_bwd_addr[2], lu_scale, dense_rows;
   int upload(const MechTables& t, const KernelSchedule& K) {
     n_temps = K.n_temps;
     lu_scale_slots = K.lu_scale.nslots;
@@ -295,6 +295,10 @@ struct KernelBufs {      // the integrator's (ros3_kernel.hip; make_args)
     HIP_TRY(solve_head_bwd.upload(K.solve_head_bwd));
     HIP_TRY(tail_fwd.upload(K.tail.fwd));
     HIP_TRY(tail_bwd.upload(K.tail.bwd));
+    for (int r = 0; r < 2; r++) {
+      HIP_TRY(tail_fwd_addr[r].upload(K.tail.fwd_addr[r]));
+      HIP_TRY(tail_bwd_addr[r].upload(K.tail.bwd_addr[r]));
+    }
     HIP_TRY(lu_scale.upload(K.lu_scale.recs));
     HIP_TRY(dense_rows.upload(K.dense.row_info));
     HIP_TRY(schur_cells.upload(K.dense.schur_cells));
@@ -304,6 +308,7 @@ struct KernelBufs {      // the integrator's (ros3_kernel.hip; make_args)
     consts.release(); fun_fac.release(); jac_fac.release(); jvs_pos.release(); zero_pos.release(); diag_pos.release(); schur_cells.release();
     vdot.release(); jvs.release(); lu.release(); solve_head_fwd.release(); solve_head_bwd.release();
     tail_fwd.release(); tail_bwd.release(); lu_scale.release(); dense_rows.release();
+    for (int r = 0; r < 2; r++) { tail_fwd_addr[r].release(); tail_bwd_addr[r].release(); }
   }
 };
 
@@ -679,7 +684,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
     a.lu.nrounds = std::max(1, std::min(a.lu.nrounds, std::atoi(cut)));
 #endif
   a.solve_head_fwd = k.solve_head_fwd.dev(); a.solve_head_bwd = k.solve_head_bwd.dev();
-  a.tail = TailDev{k.tail_fwd.p, k.tail_bwd.p};
+  a.tail = TailDev{k.tail_fwd.p, k.tail_bwd.p, {k.tail_fwd_addr[0].p, k.tail_fwd_addr[1].p}, {k.tail_bwd_addr[0].p, k.tail_bwd_addr[1].p}};
   a.lu_scale = ScaleDev{k.lu_scale.p, k.lu_scale_slots, k.lu_scale_slots + VM_LOOKAHEAD_ROWS};
   a.dense = DenseDev{k.dense_rows.p, k.schur_cells.p};
   return a;

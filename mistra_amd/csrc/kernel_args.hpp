@@ -27,8 +27,10 @@ struct ScaleDev {              // final scaling of the factorisation (schedule.h
 };
 
 struct TailDev {               // tail chain of the triangular solves (schedule.hpp: TailSolve)
-  const uint32_t* fwd;         // u32x4 per lane and group of 4 columns, columns ascending
+  const uint32_t* fwd;         // u32x4 per lane and group of 4 columns, columns ascending (two 16-bit cells per word: tail_solve_columns)
   const uint32_t* bwd;         // same, columns descending
+  const uint32_t* fwd_addr[2]; // per register: the same layout, one LDS byte address per word (tail_solve); null past the tail's registers
+  const uint32_t* bwd_addr[2];
 };
 
 struct DenseDev {              // dense tail block (schedule.hpp: DenseTail); null where the mechanism has none

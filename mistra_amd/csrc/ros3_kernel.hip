@@ -277,7 +277,7 @@ __device__ __forceinline__ u32x4 vm_ring_take() {
 #undef MISTRA_RING_TAKE
   return u32x4{x, y, z, w};
 }
-// The table rows of the tail chain hold two 16-bit Ghimj cell numbers per word (low half: the rows of register 0, high half: of
+// The 16-bit table rows of the tail chain (tail_solve_columns; the block form reads address tables) hold two Ghimj cell numbers per word (low half: the rows of register 0, high half: of
 // register 1).  This takes slot K out of the ring and turns the halves that are wanted straight into LDS byte addresses, one
 // v_lshlrev_b32_sdwa per cell reading the ring register itself: copied out first and decoded by the compiler it was 4 moves, 4 ands and
 // 8 shifts per slot, a fifth of the instructions of a chain that is bound by instruction issue (a lone wave: one instruction per
@@ -464,6 +464,120 @@ __device__ __forceinline__ void tail_update(double& x, const double xb, const do
   else static_assert(MASK == 15, "row mask not instantiated");
 #undef MISTRA_UPD_CASE
 }
+// The same phases with the gathers of one ring group (the 16 operand addresses of one register's rows in one block, table column
+// order, in four ring slots) issued inside them: straight from the ring registers, whose words are LDS byte addresses
+// (schedule.hpp: TailSolve::fwd_addr / bwd_addr), into g.  The compiler does not know the ring, nor that the loads are in flight:
+// each statement waits for its group's table loads first (vmcnt(4): the group after it is the only one issued since, see
+// tail_solve) and for its own gathers last (lgkmcnt(0); cdna_hip_programming.md §5.7), and g are early-clobber outputs.  In the
+// diagonal steps the gathers take the wait slots, two per slot (an instruction is a wait state); in the 16-step update of the other
+// register two precede each of the first eight steps, the last eight cover the LDS round trip.  (The diagonal steps are the 15 of
+// tail_diag: the block's last column has no rows below it in the block, forward, nor its first above, backward; the closing
+// s_waitcnt is the wait state tail_diag's trailing s_nop 0 gives.)
+#define MISTRA_TAIL_GOPS                                                                                                          \
+  [g0] "=&v"(g[0]), [g1] "=&v"(g[1]), [g2] "=&v"(g[2]), [g3] "=&v"(g[3]), [g4] "=&v"(g[4]), [g5] "=&v"(g[5]), [g6] "=&v"(g[6]),           \
+      [g7] "=&v"(g[7]), [g8] "=&v"(g[8]), [g9] "=&v"(g[9]), [g10] "=&v"(g[10]), [g11] "=&v"(g[11]), [g12] "=&v"(g[12]),                   \
+      [g13] "=&v"(g[13]), [g14] "=&v"(g[14]), [g15] "=&v"(g[15])
+// the ring registers of group half H (slots 4H .. 4H + 3, see vm_ring_load) in table column order
+#define MISTRA_RING_HALF_HI0 192, 193, 194, 195, 196, 197, 198, 199, 208, 209, 210, 211, 212, 213, 214, 215
+#define MISTRA_RING_HALF_HI1 224, 225, 226, 227, 228, 229, 230, 231, 240, 241, 242, 243, 244, 245, 246, 247
+#define MISTRA_RING_HALF_LO0 64, 65, 66, 67, 68, 69, 70, 71, 80, 81, 82, 83, 84, 85, 86, 87
+#define MISTRA_RING_HALF_LO1 96, 97, 98, 99, 100, 101, 102, 103, 112, 113, 114, 115, 116, 117, 118, 119
+#define MISTRA_APPLY(M, ...) M(__VA_ARGS__)
+#define MISTRA_ON_RING_HALF(M, ...)                                                                                            \
+  if constexpr (LOW && H == 0) MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HALF_LO0);                                            \
+  else if constexpr (LOW) MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HALF_LO1);                                                 \
+  else if constexpr (H == 0) MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HALF_HI0);                                              \
+  else MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HALF_HI1);
+#define MISTRA_G2(A, RA, B, RB) "ds_read_b64 %[g" #A "], v" #RA "\n\tds_read_b64 %[g" #B "], v" #RB "\n\t"
+#define MISTRA_G16(r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15)                                        \
+  MISTRA_G2(0, r0, 1, r1) MISTRA_G2(2, r2, 3, r3) MISTRA_G2(4, r4, 5, r5) MISTRA_G2(6, r6, 7, r7) MISTRA_G2(8, r8, 9, r9)       \
+      MISTRA_G2(10, r10, 11, r11) MISTRA_G2(12, r12, 13, r13) MISTRA_G2(14, r14, 15, r15)
+#define MISTRA_DSTEP(J, RM) "v_fmac_f64_dpp %[x], -%[x], %[c" #J "] row_newbcast:" #J " row_mask:" RM " bank_mask:0xf\n\t"
+#define MISTRA_NSTEP(J, RM) "s_nop 1\n\t" MISTRA_DSTEP(J, RM)
+#define MISTRA_DIAG_G_FWD(RM, r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15)                               \
+  asm volatile("s_waitcnt vmcnt(4)\n\t"                                                                                       \
+               MISTRA_G2(0, r0, 1, r1) MISTRA_DSTEP(0, RM) MISTRA_G2(2, r2, 3, r3) MISTRA_DSTEP(1, RM)                        \
+               MISTRA_G2(4, r4, 5, r5) MISTRA_DSTEP(2, RM) MISTRA_G2(6, r6, 7, r7) MISTRA_DSTEP(3, RM)                        \
+               MISTRA_G2(8, r8, 9, r9) MISTRA_DSTEP(4, RM) MISTRA_G2(10, r10, 11, r11) MISTRA_DSTEP(5, RM)                    \
+               MISTRA_G2(12, r12, 13, r13) MISTRA_DSTEP(6, RM) MISTRA_G2(14, r14, 15, r15) MISTRA_DSTEP(7, RM)                \
+               MISTRA_NSTEP(8, RM) MISTRA_NSTEP(9, RM) MISTRA_NSTEP(10, RM) MISTRA_NSTEP(11, RM) MISTRA_NSTEP(12, RM)         \
+               MISTRA_NSTEP(13, RM) MISTRA_NSTEP(14, RM) "s_waitcnt lgkmcnt(0)"              \
+               : [x] "+v"(x), MISTRA_TAIL_GOPS : MISTRA_TAIL_COPS : "memory")
+#define MISTRA_DIAG_G_BWD(RM, r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15)                               \
+  asm volatile("s_waitcnt vmcnt(4)\n\t"                                                                                       \
+               MISTRA_G2(0, r0, 1, r1) MISTRA_DSTEP(15, RM) MISTRA_G2(2, r2, 3, r3) MISTRA_DSTEP(14, RM)                      \
+               MISTRA_G2(4, r4, 5, r5) MISTRA_DSTEP(13, RM) MISTRA_G2(6, r6, 7, r7) MISTRA_DSTEP(12, RM)                      \
+               MISTRA_G2(8, r8, 9, r9) MISTRA_DSTEP(11, RM) MISTRA_G2(10, r10, 11, r11) MISTRA_DSTEP(10, RM)                  \
+               MISTRA_G2(12, r12, 13, r13) MISTRA_DSTEP(9, RM) MISTRA_G2(14, r14, 15, r15) MISTRA_DSTEP(8, RM)                \
+               MISTRA_NSTEP(7, RM) MISTRA_NSTEP(6, RM) MISTRA_NSTEP(5, RM) MISTRA_NSTEP(4, RM) MISTRA_NSTEP(3, RM)            \
+               MISTRA_NSTEP(2, RM) MISTRA_NSTEP(1, RM) "s_waitcnt lgkmcnt(0)"                 \
+               : [x] "+v"(x), MISTRA_TAIL_GOPS : MISTRA_TAIL_COPS : "memory")
+#define MISTRA_USTEP(J) "v_fmac_f64_dpp %[x], -%[xb], %[c" #J "] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+#define MISTRA_UPDATE_G_FWD(UNUSED, r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15)                                 \
+  asm volatile("s_waitcnt vmcnt(4)\n\t"                                                                                       \
+               MISTRA_G2(0, r0, 1, r1) MISTRA_USTEP(0) MISTRA_G2(2, r2, 3, r3) MISTRA_USTEP(1)                                \
+               MISTRA_G2(4, r4, 5, r5) MISTRA_USTEP(2) MISTRA_G2(6, r6, 7, r7) MISTRA_USTEP(3)                                \
+               MISTRA_G2(8, r8, 9, r9) MISTRA_USTEP(4) MISTRA_G2(10, r10, 11, r11) MISTRA_USTEP(5)                            \
+               MISTRA_G2(12, r12, 13, r13) MISTRA_USTEP(6) MISTRA_G2(14, r14, 15, r15) MISTRA_USTEP(7)                        \
+               MISTRA_USTEP(8) MISTRA_USTEP(9) MISTRA_USTEP(10) MISTRA_USTEP(11) MISTRA_USTEP(12) MISTRA_USTEP(13)            \
+               MISTRA_USTEP(14) MISTRA_USTEP(15) "s_waitcnt lgkmcnt(0)"                                                       \
+               : [x] "+v"(x), MISTRA_TAIL_GOPS : [xb] "v"(xb), MISTRA_TAIL_COPS : "memory")
+#define MISTRA_UPDATE_G_BWD(UNUSED, r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15)                                 \
+  asm volatile("s_waitcnt vmcnt(4)\n\t"                                                                                       \
+               MISTRA_G2(0, r0, 1, r1) MISTRA_USTEP(15) MISTRA_G2(2, r2, 3, r3) MISTRA_USTEP(14)                              \
+               MISTRA_G2(4, r4, 5, r5) MISTRA_USTEP(13) MISTRA_G2(6, r6, 7, r7) MISTRA_USTEP(12)                              \
+               MISTRA_G2(8, r8, 9, r9) MISTRA_USTEP(11) MISTRA_G2(10, r10, 11, r11) MISTRA_USTEP(10)                          \
+               MISTRA_G2(12, r12, 13, r13) MISTRA_USTEP(9) MISTRA_G2(14, r14, 15, r15) MISTRA_USTEP(8)                        \
+               MISTRA_USTEP(7) MISTRA_USTEP(6) MISTRA_USTEP(5) MISTRA_USTEP(4) MISTRA_USTEP(3) MISTRA_USTEP(2)                \
+               MISTRA_USTEP(1) MISTRA_USTEP(0) "s_waitcnt lgkmcnt(0)"                                                         \
+               : [x] "+v"(x), MISTRA_TAIL_GOPS : [xb] "v"(xb), MISTRA_TAIL_COPS : "memory")
+#define MISTRA_GATHER_ONLY(UNUSED, r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15)                                  \
+  asm volatile("s_waitcnt vmcnt(4)\n\t" MISTRA_G16(r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15)       \
+               "s_waitcnt lgkmcnt(0)" : MISTRA_TAIL_GOPS : : "memory")
+
+// step 1 with the gathers of ring half H
+template <bool LOW, int H, int ROW, bool BACKWARD>
+__device__ __forceinline__ void tail_diag_gather(double& x, const double (&c)[16], double (&g)[16]) {
+  if constexpr (!BACKWARD) {
+    if constexpr (ROW == 0) { MISTRA_ON_RING_HALF(MISTRA_DIAG_G_FWD, "0x1") }
+    else if constexpr (ROW == 1) { MISTRA_ON_RING_HALF(MISTRA_DIAG_G_FWD, "0x2") }
+    else if constexpr (ROW == 2) { MISTRA_ON_RING_HALF(MISTRA_DIAG_G_FWD, "0x4") }
+    else { MISTRA_ON_RING_HALF(MISTRA_DIAG_G_FWD, "0x8") }
+  } else {
+    if constexpr (ROW == 0) { MISTRA_ON_RING_HALF(MISTRA_DIAG_G_BWD, "0x1") }
+    else if constexpr (ROW == 1) { MISTRA_ON_RING_HALF(MISTRA_DIAG_G_BWD, "0x2") }
+    else if constexpr (ROW == 2) { MISTRA_ON_RING_HALF(MISTRA_DIAG_G_BWD, "0x4") }
+    else { MISTRA_ON_RING_HALF(MISTRA_DIAG_G_BWD, "0x8") }
+  }
+}
+// step 3 for all four lane rows of the other register, with the gathers of ring half H
+template <bool LOW, int H, bool BACKWARD>
+__device__ __forceinline__ void tail_update_gather(double& x, const double xb, const double (&c)[16], double (&g)[16]) {
+  if constexpr (BACKWARD) { MISTRA_ON_RING_HALF(MISTRA_UPDATE_G_BWD, 0) }
+  else { MISTRA_ON_RING_HALF(MISTRA_UPDATE_G_FWD, 0) }
+}
+// the gathers of ring half H alone (a block with nothing left to host them)
+template <bool LOW, int H>
+__device__ __forceinline__ void tail_gather(double (&g)[16]) {
+  MISTRA_ON_RING_HALF(MISTRA_GATHER_ONLY, 0)
+}
+#undef MISTRA_TAIL_GOPS
+#undef MISTRA_RING_HALF_HI0
+#undef MISTRA_RING_HALF_HI1
+#undef MISTRA_RING_HALF_LO0
+#undef MISTRA_RING_HALF_LO1
+#undef MISTRA_APPLY
+#undef MISTRA_ON_RING_HALF
+#undef MISTRA_G2
+#undef MISTRA_G16
+#undef MISTRA_DSTEP
+#undef MISTRA_NSTEP
+#undef MISTRA_DIAG_G_FWD
+#undef MISTRA_DIAG_G_BWD
+#undef MISTRA_USTEP
+#undef MISTRA_UPDATE_G_FWD
+#undef MISTRA_UPDATE_G_BWD
+#undef MISTRA_GATHER_ONLY
 #undef MISTRA_DIAG_STEP
 #undef MISTRA_DIAG_FWD
 #undef MISTRA_DIAG_BWD
@@ -472,44 +586,86 @@ __device__ __forceinline__ void tail_update(double& x, const double xb, const do
 #undef MISTRA_UPDATE_BWD
 #undef MISTRA_TAIL_COPS
 
-// One block column, in two halves so that the operand gathers of block b + 1 are in flight while block b computes (a lone wave
-// would otherwise sit out the table wait and an LDS round trip in front of every block: measured, the chain then took as long
-// as the column-by-column one).  w[0..3]: the block's four table slots (16 columns in chain order: ascending forward,
-// descending backward); a word holds the Ghimj cell of (row h + lane, column) in its low half and of (row h + 64 + lane,
-// column) in its high half.  (vm_ring_take_cells turns them into LDS addresses as they come out of the ring; a[i]: column i of the
-// block in TABLE order, the chain's step j is table column j forward and 15 - j backward.)
-// NEXT: takes the next block's table slots and issues the gathers of its operands (into c and w, free by then) — placed between
-// the block's last use of c and the other register's update, whose 16 dependent steps cover the gathers' LDS round trip.
-// ad: LDS addresses of the other register's operands of this block, in table order (taken from the ring with the block's own).
-template <int R, int J, bool BACKWARD, bool LAST, class NEXT>
-__device__ __forceinline__ void tail_block(double (&xr)[R], double (&c)[16], const uint32_t (&ad)[16], NEXT&& next) {
-  constexpr int REG = J / 4, ROW = J % 4;
-  constexpr int OTHER = BACKWARD ? 0 : R - 1;                    // the other register's rows lie wholly below (forward) / above (backward) the block
-  constexpr bool HAS_OTHER = !LAST && R == 2 && REG != OTHER;
-  double d[16];      // ... their operands: gathered here, used three phases further down
-  if constexpr (HAS_OTHER) {
-#pragma unroll
-    for (int j = 0; j < 16; j++) d[j] = lds_ld(ad[BACKWARD ? 15 - j : j]);
+// The block stream of one solve (forward blocks from FWD_BLOCK0 on, then every block backward) and the groups it reads from the
+// look-ahead ring: per block its own register's 16 operand addresses and, where the other register takes part, that register's
+// 16 — one group of four ring slots each, in the order the chain gathers them (own(0); other(0), own(1); ...).  Group g lands in
+// ring half g & 1; once it is gathered its half is refilled with group g + 2, so every gathering statement waits for vmcnt(4).
+template <int R, int FWD_BLOCK0>
+struct TailStream {
+  static constexpr int NB = 4 * R;               // 16-column blocks of the tail triangle
+  static constexpr int NF = NB - FWD_BLOCK0;     // ... of them in the forward chain
+  static constexpr int NS = NF + NB;             // blocks of the whole solve, forward then backward
+  static constexpr bool bw(int s) { return s >= NF; }
+  static constexpr int col_block(int s) { return bw(s) ? NB - 1 - (s - NF) : FWD_BLOCK0 + s; }
+  static constexpr bool last(int s) { return bw(s) ? s == NS - 1 : FWD_BLOCK0 + s == NB - 1; }
+  static constexpr int reg(int s) { return col_block(s) / 4; }
+  static constexpr int other(int s) { return bw(s) ? 0 : R - 1; }     // the other register's rows lie wholly below (forward) / above (backward) the block
+  static constexpr bool has_other(int s) { return !last(s) && R == 2 && reg(s) != other(s); }
+  static constexpr int own_group(int s) {
+    int g = 0;
+    for (int i = 0; i < s && i < NS; i++) g += has_other(i) ? 2 : 1;
+    return g;
   }
+  static constexpr int NG = own_group(NS);
+  static constexpr int group_block(int g) {
+    int s = 0;
+    while (s + 1 < NS && own_group(s + 1) <= g) s++;
+    return s;
+  }
+  static constexpr int group_reg(int g) { return g == own_group(group_block(g)) ? reg(group_block(g)) : other(group_block(g)); }
+};
+
+// One block column, in two halves so that the operand gathers of block b + 1 are in flight while block b computes (a lone wave
+// would otherwise sit out an LDS round trip in front of every block: measured, the chain then took as long as the column-by-column
+// one).  c: the block's own operands in chain order (step j: table column j forward, 15 - j backward), gathered by the previous
+// block.  Where the other register takes part, its operands are gathered in the wait slots of the diagonal steps, and the next
+// block's own ones inside the other register's 16-step update.  Elsewhere the next block's own operands take the diagonal steps'
+// wait slots — except in the low ring placement, whose functions stay below v64 and cannot hold two operand sets at once: there
+// they are gathered on their own once the block's last use of c is issued (an exposed LDS round trip per block).
+// load(g): refills the ring half of group g - 2, just gathered, with group g.
+template <class TS, int S, bool LOW, int R, class LOAD>
+__device__ __forceinline__ void tail_block(double (&xr)[R], double (&c)[16], LOAD&& load) {
+  constexpr int J = TS::col_block(S), REG = J / 4, ROW = J % 4, OTHER = TS::other(S);
+  constexpr bool BACKWARD = TS::bw(S), LAST = TS::last(S), HAS_OTHER = TS::has_other(S), NEXT = S + 1 < TS::NS;
+  constexpr int GO = TS::own_group(S) + 1, GN = TS::own_group(S + 1);     // groups: the other register's operands, the next block's own
+  constexpr bool DIAG_NEXT = !HAS_OTHER && NEXT && !LOW;                   // the next block's own operands gathered in the diagonal steps
   double x = xr[REG];
-  tail_diag<ROW, BACKWARD>(x, c);                                  // 1.
+  double g[16], d[16];
+  if constexpr (HAS_OTHER) {
+    tail_diag_gather<LOW, GO & 1, ROW, BACKWARD>(x, c, g);               // 1. (and the other register's operands)
+    load(std::integral_constant<int, GO + 2>());
+#pragma unroll
+    for (int j = 0; j < 16; j++) d[j] = g[BACKWARD ? 15 - j : j];
+  } else if constexpr (DIAG_NEXT) {
+    tail_diag_gather<LOW, GN & 1, ROW, BACKWARD>(x, c, g);               // 1. (and the next block's operands)
+    load(std::integral_constant<int, GN + 2>());
+  } else {
+    tail_diag<ROW, BACKWARD>(x, c);                                      // 1.
+  }
   if constexpr (!LAST) {
-    const double xb = lane_row_to_all<ROW>(x);                     // 2.
+    const double xb = lane_row_to_all<ROW>(x);                           // 2.
     constexpr int same = BACKWARD ? (1 << ROW) - 1 : (0xF << (ROW + 1)) & 0xF;      // 3. lane rows above / below in the same register
     if constexpr (same != 0) tail_update<same, BACKWARD>(x, xb, c);
     xr[REG] = x;
     if constexpr (HAS_OTHER) {
       double y = xr[OTHER];
-      asm volatile("" : "+v"(y), "+v"(d[0]), "+v"(d[15]));      // (d and y are in registers before the next block's table words overwrite w)
-      next();
-      tail_update<15, BACKWARD>(y, xb, d);
+      tail_update_gather<LOW, GN & 1, BACKWARD>(y, xb, d, g);          // 3. for the other register (and the next block's operands)
       xr[OTHER] = y;
-    } else {
-      next();
+      load(std::integral_constant<int, GN + 2>());
+    } else if constexpr (!DIAG_NEXT) {
+      tail_gather<LOW, GN & 1>(g);
+      load(std::integral_constant<int, GN + 2>());
     }
   } else {
     xr[REG] = x;
-    next();
+    if constexpr (NEXT && !DIAG_NEXT) {
+      tail_gather<LOW, GN & 1>(g);
+      load(std::integral_constant<int, GN + 2>());
+    }
+  }
+  if constexpr (NEXT) {
+#pragma unroll
+    for (int j = 0; j < 16; j++) c[j] = g[TS::bw(S + 1) ? 15 - j : j];
   }
 }
 
@@ -518,70 +674,59 @@ __device__ __forceinline__ void tail_block(double (&xr)[R], double (&c)[16], con
 // whose rows the LU program leaves without exactly those terms (schedule.cpp: lu_entries, dense_h)
 template <int R, int FWD_BLOCK0, bool LOW>
 __device__ __attribute__((noinline)) void tail_solve(const TailDev T, uint32_t xb, uint32_t rb, int lane) {
-  constexpr int NB = 4 * R;                      // 16-column blocks of the tail triangle
-  constexpr int NF = NB - FWD_BLOCK0;            // ... of them in the forward chain
-  constexpr int NS = NF + NB;                    // blocks of the whole solve, forward then backward
-  static_assert(FWD_BLOCK0 >= 0 && FWD_BLOCK0 <= NB && NS <= 16, "first forward block");
+  using TS = TailStream<R, FWD_BLOCK0>;
+  static_assert(FWD_BLOCK0 >= 0 && FWD_BLOCK0 <= TS::NB && TS::NS <= 16, "first forward block");
   double x[R], rd[R];
 #pragma unroll
   for (int r = 0; r < R; r++) {
     x[r] = lds_ld(xb + 8 * (r * 64 + lane));
     rd[r] = lds_ld(rb + 8 * (r * 64 + lane));          // R(k) = 1/U(k,k), published by the LU program
   }
-  // table rows: one u32x4 per lane and group of 4 columns, 1 KiB per row; the forward tables from block FWD_BLOCK0 on, then the
-  // backward ones; past the last block: the tables' slack rows.  Row bases in scalar registers, the lane's offset in one vector register.
-  const uint64_t tf = ring_base(T.fwd + FWD_BLOCK0 * 4 * 64 * 4).b0, tb = ring_base(T.bwd).b0;
+  // table rows: one u32x4 per lane and group of 4 columns, 1 KiB per row, 4 rows per block; past the stream's last group: the
+  // backward tables' slack rows.  Table bases in scalar registers, the lane's offset in one vector register.
+  uint64_t tf[R], tb[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    tf[r] = ring_base(T.fwd_addr[r]).b0;
+    tb[r] = ring_base(T.bwd_addr[r]).b0;
+  }
   const uint32_t voff = 16u * (uint32_t)lane;
-  uint32_t three = 3;
-  asm volatile("" : "+v"(three));      // (held in one register for the whole solve)
-#define MISTRA_TAIL_LOADS(S, K0)                                                                                          \
-  {                                                                                                                      \
-    const uint64_t base = (S) < NF ? tf + (uint64_t)(S) * 4096u : tb + (uint64_t)((S) - NF) * 4096u;                     \
-    vm_ring_load_at<LOW, K0, 0>(base, voff); vm_ring_load_at<LOW, K0 + 1, 1024>(base, voff);                             \
-    vm_ring_load_at<LOW, K0 + 2, 2048>(base, voff); vm_ring_load_at<LOW, K0 + 3, 3072>(base, voff);                      \
-  }
+  auto load = [&](auto group) {
+    constexpr int G = decltype(group)::value, K0 = 4 * (G & 1);
+    uint64_t base;
+    if constexpr (G < TS::NG) {
+      constexpr int s = TS::group_block(G), r = TS::group_reg(G);
+      base = TS::bw(s) ? tb[r] + (uint64_t)(s - TS::NF) * 4096u : tf[r] + (uint64_t)TS::col_block(s) * 4096u;
+    } else {
+      base = tb[0] + (uint64_t)(TS::NB + G - TS::NG) * 4096u;
+    }
+    vm_ring_load_at<LOW, K0, 0>(base, voff); vm_ring_load_at<LOW, K0 + 1, 1024>(base, voff);
+    vm_ring_load_at<LOW, K0 + 2, 2048>(base, voff); vm_ring_load_at<LOW, K0 + 3, 3072>(base, voff);
+  };
   asm volatile("s_waitcnt vmcnt(0)" : : : "memory");     // nothing of the caller's may sit between the counted loads
-  MISTRA_TAIL_LOADS(0, 0) MISTRA_TAIL_LOADS(1, 4)
-  // block S of the stream (S < NF: forward block FWD_BLOCK0 + S; else backward block NB - 1 - (S - NF)): its four slots (blocks
-  // alternate between the ring's halves, refilled with block S + 2's) come out of the ring as LDS addresses — of the block's own
-  // register's operands (gathered at once, into c) and, where the other register takes part, of its operands (ad, gathered by tail_block)
+  load(std::integral_constant<int, 0>());
+  load(std::integral_constant<int, 1>());
   double c[16];
-  uint32_t ad[16];
-#define MISTRA_TAIL_GATHER(S)                                                                                             \
-  if constexpr ((S) < NS) {                                                                                              \
-    constexpr int K0 = ((S) & 1) * 4;                                                                                    \
-    constexpr bool BW = (S) >= NF;                                                                                       \
-    constexpr int J = BW ? (NB - 1 - ((S) - NF) + NB) % NB : (FWD_BLOCK0 + (S)) % NB;                                    \
-    constexpr int REG = J / 4, OTHER = BW ? 0 : R - 1;                                                                   \
-    constexpr bool LAST = BW ? (S) == NS - 1 : FWD_BLOCK0 + (S) == NB - 1;                                               \
-    constexpr bool HAS_OTHER = !LAST && R == 2 && REG != OTHER;                                                          \
-    constexpr bool LO = REG == 0 || (HAS_OTHER && OTHER == 0), HI = REG == 1 || (HAS_OTHER && OTHER == 1);               \
-    uint32_t ac[16];                                                                                                     \
-    uint32_t* const alo = REG == 0 ? ac : ad;                                                                            \
-    uint32_t* const ahi = REG == 1 ? ac : ad;                                                                            \
-    vm_ring_take_cells<LOW, K0, 7, LO, HI>(alo, ahi, three);         vm_ring_take_cells<LOW, K0 + 1, 6, LO, HI>(alo + 4, ahi + 4, three);   \
-    vm_ring_take_cells<LOW, K0 + 2, 5, LO, HI>(alo + 8, ahi + 8, three); vm_ring_take_cells<LOW, K0 + 3, 4, LO, HI>(alo + 12, ahi + 12, three); \
-    MISTRA_TAIL_LOADS((S) + 2, K0)                                                                                       \
-    _Pragma("unroll") for (int j = 0; j < 16; j++) c[j] = lds_ld(ac[BW ? 15 - j : j]);                                   \
+  {
+    double g[16];
+    tail_gather<LOW, 0>(g);
+    load(std::integral_constant<int, 2>());
+#pragma unroll
+    for (int j = 0; j < 16; j++) c[j] = g[TS::bw(0) ? 15 - j : j];
   }
-  // ... and its arithmetic; between the forward and the backward half: x = R .* x (the backward half runs on the row-scaled
-  // triangle U' = D^-1 U that the factorisation leaves in the tail block — schedule.cpp: lu_entries; dense_lu — so there is
-  // no quotient on the serial chain)
+  // the blocks; between the forward and the backward half: x = R .* x (the backward half runs on the row-scaled triangle
+  // U' = D^-1 U that the factorisation leaves in the tail block — schedule.cpp: lu_entries; dense_lu — so there is no quotient
+  // on the serial chain)
 #define MISTRA_TAIL_STEP(S)                                                                                               \
-  if constexpr ((S) < NS) {                                                                                              \
-    if constexpr ((S) == NF) {                                                                                           \
+  if constexpr ((S) < TS::NS) {                                                                                          \
+    if constexpr ((S) == TS::NF) {                                                                                       \
       _Pragma("unroll") for (int r = 0; r < R; r++) x[r] = x[r] * rd[r];                                                 \
     }                                                                                                                    \
-    auto next = [&]() { MISTRA_TAIL_GATHER((S) + 1) };                                                                   \
-    if constexpr ((S) < NF) tail_block<R, (FWD_BLOCK0 + (S)) % NB, false, FWD_BLOCK0 + (S) == NB - 1>(x, c, ad, next);   \
-    else tail_block<R, (NB - 1 - ((S) - NF) + NB) % NB, true, (S) == NS - 1>(x, c, ad, next);                            \
+    tail_block<TS, (S), LOW>(x, c, load);                                                                                \
   }
-  MISTRA_TAIL_GATHER(0)
   MISTRA_TAIL_STEP(0) MISTRA_TAIL_STEP(1) MISTRA_TAIL_STEP(2) MISTRA_TAIL_STEP(3) MISTRA_TAIL_STEP(4) MISTRA_TAIL_STEP(5) MISTRA_TAIL_STEP(6) MISTRA_TAIL_STEP(7)
   MISTRA_TAIL_STEP(8) MISTRA_TAIL_STEP(9) MISTRA_TAIL_STEP(10) MISTRA_TAIL_STEP(11) MISTRA_TAIL_STEP(12) MISTRA_TAIL_STEP(13) MISTRA_TAIL_STEP(14) MISTRA_TAIL_STEP(15)
 #undef MISTRA_TAIL_STEP
-#undef MISTRA_TAIL_GATHER
-#undef MISTRA_TAIL_LOADS
   asm volatile("s_waitcnt vmcnt(0)" : : : "memory");     // the look-ahead loads past the stream's end have landed
 #pragma unroll
   for (int r = 0; r < R; r++) lds_st(xb + 8 * (r * 64 + lane), x[r]);

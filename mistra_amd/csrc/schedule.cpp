@@ -835,6 +835,15 @@ TailSolve build_tail_solve(const MechTables& m, const VmLayout& lay, int regs) {
       else put(T.bwd, T.m - 1 - q, lane, r, p);             // U(i, c): used when the backward chain reaches column q
     }
   }
+  auto addresses = [](const std::vector<uint32_t>& tab, int r) {      // slack and absent operands stay on the 0.0 cell
+    std::vector<uint32_t> a(tab.size());
+    for (size_t k = 0; k < tab.size(); k++) a[k] = 8u * ((tab[k] >> (16 * r)) & 0xFFFFu);
+    return a;
+  };
+  for (int r = 0; r < T.regs; r++) {
+    T.fwd_addr[r] = addresses(T.fwd, r);
+    T.bwd_addr[r] = addresses(T.bwd, r);
+  }
   return T;
 }
 

@@ -146,6 +146,9 @@ struct TailSolve {
   int m = 0, h = 0, regs = 0;                   // tail rows [h, h+m), m = 64*regs, regs in {1,2}
   std::vector<uint32_t> fwd;                    // [((q/4)*64 + lane)*4 + q%4]  lo16: r=0, hi16: r=1; columns ascending
   std::vector<uint32_t> bwd;                    // same, columns DEscending: group g, word c  <->  q = m-1-(4g+c)
+  // the same words per register r < regs as LDS byte addresses (8 * cell: M starts at LDS address 0), one operand per word:
+  // the block-form chain (ros3_kernel.hip: tail_solve) gathers through them straight from its look-ahead ring, with no decode
+  std::vector<uint32_t> fwd_addr[2], bwd_addr[2];
 };
 
 // The factorisation's last act, M[tgt] *= M[aux] for ~11 000 independent cells of the tot mechanism (L(k,j) *= R(j), and
