@@ -321,6 +321,13 @@ int mistra_chem_equil_co(int mech, int nlayer, int nkc, int j6, const double* tt
  * 1/U(k,k) | K(1) | K(2) | K(3) (KppSolve_x results of the three stages) | Err (ros_ErrorNorm_x) | H. */
 int mistra_chem_debug_first_step(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
                                  double tin, double tout, double* dump);
+/* The same at a first step size of the caller's choosing, handing back what that kernel variant finished with.  hstart [ncell] (host,
+ * may be null): first step size per cell as in mistra_chem_integrate_device_hstart (entries <= 0: the reference's 1e-3); the dumped
+ * attempt then runs at H = min(hstart, |tout - tin|).  var_out [ncell][NVAR], ierr [ncell], stats [ncell][8] (host, each may be null):
+ * results of the integration the dump variant carried to its end, to be compared with the product kernel's on the same inputs. */
+int mistra_chem_debug_first_step_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                    double tin, double tout, const double* hstart, double* dump, double* var_out, int32_t* ierr,
+                                    int32_t* stats);
 
 /* Test hook for the one exit of RosenbrockIntegrator_x that INTEGRATE_x's fixed options put out of a test's reach: IERR = -6, "No of steps
  * exceeds maximum bound" (gas.f:1199-1202), taken when Nstp > Max_no_steps = IPAR(3), which INTEGRATE_x leaves at its default of 100000

@@ -265,6 +265,36 @@ def debug_set_max_steps(n=0):
     _check(lib().mistra_chem_debug_set_max_steps(int(n)))
 
 
+FirstStep = namedtuple("FirstStep", "fcn0 ghimj lu r k1 k2 k3 err h var ierr stats")
+
+
+def debug_first_step(mech, var, fix, rconst, tin=0.0, tout=10.0, hstart=None):
+    """Test hook (include/mistra_chem.h: mistra_chem_debug_first_step_ex): the kernel's dump variant on host arrays -> FirstStep, per cell the
+    intermediate results of the first attempt of the first step (Fcn0, Ghimj as prepared, the factors in the kernel's form, 1/U(k,k), K1..K3,
+    the error norm, H) and var, ierr, stats of the integration that variant carried to its end.  hstart [ncell]: first step size per cell."""
+    mid, name = _mech_id(mech)
+    nvar, nfix, nreact, nnz = DIMS[name]
+    if _inited_device is None:
+        init(0)
+    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+    ncell = v.shape[0]
+    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
+    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
+    h = None if hstart is None else np.ascontiguousarray(hstart, np.float64).reshape(ncell)
+    dump = np.zeros((ncell, 5 * nvar + 2 * nnz + 2))
+    out, ierr, stats = np.empty_like(v), np.zeros(ncell, np.int32), np.zeros((ncell, 8), np.int32)
+    L = lib()
+    L.mistra_chem_debug_first_step_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _ip, _ip]
+    _check(L.mistra_chem_debug_first_step_ex(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tin), float(tout),
+                                             None if h is None else h.ctypes.data_as(_dp), dump.ctypes.data_as(_dp), out.ctypes.data_as(_dp),
+                                             ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip)))
+    parts, o = [], 0
+    for ln in (nvar, nnz, nnz, nvar, nvar, nvar, nvar, 1, 1):
+        parts.append(dump[:, o:o + ln])
+        o += ln
+    return FirstStep(*parts, out, ierr, stats)
+
+
 def integrate_into(mech, var, fix, rconst, out, ierr, stats, tin=0.0, tout=10.0, texit_hexit=None, hstart=None):
     """Device path with caller-owned output tensors (no allocation inside the timed region of bench.py).  texit_hexit
     [ncell, 2]: exit time and last step size per cell (what INTEGRATE_x leaves in TIN and STEPMIN).  hstart [ncell]: OPT-IN

@@ -1530,6 +1530,11 @@ int mistra_chem_debug_set_max_steps(int max_steps) {
 
 int mistra_chem_debug_first_step(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                                  double tout, double* dump) {
+  return mistra_chem_debug_first_step_ex(mech, ncell, var_in, fix, rconst, tin, tout, nullptr, dump, nullptr, nullptr, nullptr);
+}
+
+int mistra_chem_debug_first_step_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
+                                    double tout, const double* hstart, double* dump, double* var_out, int32_t* ierr, int32_t* stats) {
   if (int rc = check_call(mech, ncell)) return rc;
   if (ncell == 0) return 0;
   if (!var_in || !fix || !rconst || !dump) return fail("null host pointer");
@@ -1539,7 +1544,7 @@ int mistra_chem_debug_first_step(int mech, int ncell, const double* var_in, cons
   MechState& S = *t.S;
   const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact, nc = (size_t)ncell;
   const size_t per = 5 * nv + 2 * (size_t)kDims[mech].lu_nonzero + 2;
-  DevBuf<double> d_dump;
+  DevBuf<double> d_dump, d_hstart;
   HIP_TRY(S.s_var.reserve(nc * nv));
   HIP_TRY(S.s_fix.reserve(nc * nf));
   HIP_TRY(S.s_rct.reserve(nc * nr));
@@ -1552,10 +1557,20 @@ int mistra_chem_debug_first_step(int mech, int ncell, const double* var_in, cons
   HIP_TRY(hipMemcpy(S.s_rct.p, rconst, nc * nr * sizeof(double), hipMemcpyHostToDevice));
   KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, tin, tout, S.s_var.p, S.s_ierr.p, S.s_stats.p, nullptr);
   a.dump = d_dump.p;
+  if (hstart) {
+    HIP_TRY(d_hstart.reserve(nc));
+    HIP_TRY(hipMemcpy(d_hstart.p, hstart, nc * sizeof(double), hipMemcpyHostToDevice));
+    a.hstart = d_hstart.p;
+  }
   if (int rc = launch(*t.D, mech, a, nullptr)) return rc;
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(dump, d_dump.p, nc * per * sizeof(double), hipMemcpyDeviceToHost));
+  // what the dump instantiation carried to the end of the integration (the same staging buffers the host-buffer entries use)
+  if (var_out) HIP_TRY(hipMemcpy(var_out, S.s_var.p, nc * nv * sizeof(double), hipMemcpyDeviceToHost));
+  if (ierr) HIP_TRY(hipMemcpy(ierr, S.s_ierr.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (stats) HIP_TRY(hipMemcpy(stats, S.s_stats.p, nc * 8 * sizeof(int32_t), hipMemcpyDeviceToHost));
   d_dump.release();
+  d_hstart.release();
   return 0;
 }
 

@@ -10,27 +10,30 @@ chemistry, not of the kernel: the REFERENCE ALGORITHM ITSELF, re-associated the 
 (a*b+c contracted to fma, or the backward sweep summed in the other direction — oracle.set_variant, measured in
 test_reference_sensitivity below and on the CPU in tests/test_oracle.py), moves by up to 1.9e-6 (aer), 2.4e-7 (tot),
 1e-16 (gas) in the worst species, which are trace species ~1e-9 of the largest concentration.
-Stated bound, every species of every cell:   |dc| / (|c| + 1e-12 * max|c| of the cell)  <=  2e-5   (10x that spread),
-species above 1e-4 of the cell maximum <= 1e-12 (their spread under re-association is 1e-15), and identical step
-bookkeeping (COMMON /Statistics/).
+Stated bound, every species of every cell:   |dc| / (|c| + 1e-12 * max|c| of the cell)  <=  10x that spread PER MECHANISM
+(tests/parity_bounds.py: PARITY_RTOL — gas 1e-13, the floor; tot 3.5e-6; aer 2e-5, the bound all three had before, because its
+cloud-free set base1 moves by 7.3e-6; tests/test_oracle.py re-measures the spreads over every captured set and holds the constants
+to [10x, 100x] of them), species above 1e-4 of the cell maximum <= 1e-12 (their spread under re-association is 1e-15), and
+identical step bookkeeping (COMMON /Statistics/).
 """
 import numpy as np
 import pytest
 
 from conftest import EXTRA_SETS, MECHS, load_golden, rel_diff
+from parity_bounds import PARITY_RTOL
 
 pytestmark = pytest.mark.gpu
-RTOL = 2e-5          # all species, floor 1e-12 of the cell maximum
+RTOL = PARITY_RTOL   # all species, floor 1e-12 of the cell maximum: per mechanism
 RTOL_MAJOR = 1e-12   # species above 1e-4 of the cell maximum
 
 
-def check(got, want, tag=""):
+def check(mech, got, want, tag=""):
     d = rel_diff(got, want)
     major = np.abs(want) >= 1e-4 * np.abs(want).max(axis=1, keepdims=True)
     dm = np.where(major, d, 0.0)
     print("%s max rel diff %.3e (all species), %.3e (major species), median of per-cell max %.3e"
           % (tag, d.max() if d.size else 0.0, dm.max() if d.size else 0.0, np.median(d.max(axis=1)) if d.size else 0.0))
-    assert d.size == 0 or (d.max() <= RTOL and dm.max() <= RTOL_MAJOR)
+    assert d.size == 0 or (d.max() <= RTOL[mech] and dm.max() <= RTOL_MAJOR)
 
 
 @pytest.fixture(scope="module")
@@ -47,7 +50,7 @@ def test_golden_reference_calls_host_buffers(chem, mech, golden):
     g = golden[mech]
     res = chem.integrate(mech, g["var_in"], g["fix"], g["rconst"], 0.0, 10.0)
     assert np.all(res.ierr == 1)
-    check(res.var, g["var_out"], "%s: %d reference calls," % (mech, len(res.var)))
+    check(mech, res.var, g["var_out"], "%s: %d reference calls," % (mech, len(res.var)))
     assert np.array_equal(res.stats, g["stats"]), "COMMON /Statistics/ differs from the reference"
 
 
@@ -56,7 +59,7 @@ def test_golden_further_reference_captures(chem, which, mech):
     g = load_golden(mech, "_" + which)
     res = chem.integrate(mech, g["var_in"], g["fix"], g["rconst"], 0.0, 10.0)
     assert np.all(res.ierr == 1)
-    check(res.var, g["var_out"], "%s: %d reference calls of set '%s'," % (mech, len(res.var), which))
+    check(mech, res.var, g["var_out"], "%s: %d reference calls of set '%s'," % (mech, len(res.var), which))
     assert np.array_equal(res.stats, g["stats"]), "COMMON /Statistics/ differs from the reference"
 
 
@@ -68,7 +71,7 @@ def test_golden_reference_calls_device_buffers(chem, mech, golden):
     res = chem.integrate(mech, torch.tensor(g["var_in"], device=dev), torch.tensor(g["fix"], device=dev),
                          torch.tensor(g["rconst"], device=dev))
     torch.cuda.synchronize()
-    check(res.var.cpu().numpy(), g["var_out"], mech + " device buffers:")
+    check(mech, res.var.cpu().numpy(), g["var_out"], mech + " device buffers:")
     assert np.array_equal(res.stats.cpu().numpy()[:, 2:5], g["stats"][:, 2:5])
 
 
@@ -82,7 +85,7 @@ def test_synthetic_batch_against_oracle(chem, mech, ncell, oracles):
     torch.cuda.synchronize()
     want, ierr, st = oracles[mech].integrate_batch(var.cpu().numpy(), fix.cpu().numpy(), rconst.cpu().numpy())
     assert np.all(ierr == 1) and np.all(res.ierr.cpu().numpy() == 1)
-    check(res.var.cpu().numpy(), want, "%s: %d synthetic cells, steps/cell %.1f," % (mech, ncell, st[:, 2].mean()))
+    check(mech, res.var.cpu().numpy(), want, "%s: %d synthetic cells, steps/cell %.1f," % (mech, ncell, st[:, 2].mean()))
     assert np.array_equal(res.stats.cpu().numpy(), st)
 
 
@@ -94,7 +97,7 @@ def test_replicated_cells_are_identical(chem, golden):
     rconst = np.repeat(g["rconst"][:1], 1000, axis=0)
     res = chem.integrate("gas", var, fix, rconst)
     assert np.all(res.var == res.var[0]) and np.all(res.stats[:, 2] == 7)
-    assert rel_diff(res.var[:1], g["var_out"][:1]).max() <= RTOL
+    assert rel_diff(res.var[:1], g["var_out"][:1]).max() <= RTOL["gas"]
 
 
 def test_edge_cases(chem, golden, oracles):
@@ -104,7 +107,7 @@ def test_edge_cases(chem, golden, oracles):
     assert res.var.shape == (0, 102)
     # single cell, in-place (var_out aliases var_in inside the library's staging buffer)
     res = chem.integrate("gas", g["var_in"][:1], g["fix"][:1], g["rconst"][:1])
-    assert rel_diff(res.var, g["var_out"][:1]).max() <= RTOL
+    assert rel_diff(res.var, g["var_out"][:1]).max() <= RTOL["gas"]
     # zero-length interval: untouched state, IERR = 1, no steps
     res = chem.integrate("gas", g["var_in"][:3], g["fix"][:3], g["rconst"][:3], 5.0, 5.0)
     assert np.array_equal(res.var, g["var_in"][:3]) and np.all(res.ierr == 1) and np.all(res.stats[:, 2] == 0)
@@ -112,7 +115,7 @@ def test_edge_cases(chem, golden, oracles):
     for tout in (1.0, 60.0):
         res = chem.integrate("gas", g["var_in"][:4], g["fix"][:4], g["rconst"][:4], 0.0, tout)
         want, ierr, st = oracles["gas"].integrate_batch(g["var_in"][:4], g["fix"][:4], g["rconst"][:4], 0.0, tout)
-        assert rel_diff(res.var, want).max() <= RTOL and np.array_equal(res.stats, st)
+        assert rel_diff(res.var, want).max() <= RTOL["gas"] and np.array_equal(res.stats, st)
     # failure code: NaN state -> IERR = -7 ("step size too small"), same bookkeeping as the oracle, and the call returns
     bad = g["var_in"][:2].copy()
     bad[1, :] = np.nan
@@ -120,7 +123,7 @@ def test_edge_cases(chem, golden, oracles):
     want, ierr, st = oracles["gas"].integrate_batch(bad, g["fix"][:2], g["rconst"][:2])
     assert list(res.ierr) == [1, -7] and list(ierr) == [1, -7]
     assert np.array_equal(res.stats, st)
-    assert rel_diff(res.var[:1], want[:1]).max() <= RTOL
+    assert rel_diff(res.var[:1], want[:1]).max() <= RTOL["gas"]
 
 
 def test_full_size_properties(chem):
@@ -144,7 +147,7 @@ def test_full_size_properties(chem):
     torch.cuda.synchronize()
     assert torch.equal(again.var, res.var[sel]) and torch.equal(again.stats, res.stats[sel])
     want, ierr, st = Oracle("tot").integrate_batch(var[sel].cpu().numpy(), fix[sel].cpu().numpy(), rconst[sel].cpu().numpy())
-    check(res.var[sel].cpu().numpy(), want, "tot 1e5 sample:")
+    check("tot", res.var[sel].cpu().numpy(), want, "tot 1e5 sample:")
     assert np.array_equal(res.stats[sel].cpu().numpy(), st)
 
 
@@ -182,14 +185,14 @@ def test_opt_in_hstart_reuse(chem, golden, oracles):
     want, ierr, st = oracles["tot"].integrate_batch(o1.cpu().numpy(), g["fix"][:16], g["rconst"][:16], 0.0, 10.0, hstart=hstart.cpu().numpy())
     assert np.all(ierr == 1)
     assert np.array_equal(s2.cpu().numpy(), st), "/Statistics/ of the Hstart-reuse path differ from the oracle started at the same H"
-    check(o2.cpu().numpy(), want, "tot, Hstart reuse vs the oracle at the same first steps:")
+    check("tot", o2.cpu().numpy(), want, "tot, Hstart reuse vs the oracle at the same first steps:")
     # mixed: some cells reuse, some (entry 0) start at 1e-3 — per-cell, as the header says
     mixed = hstart.clone()
     mixed[::2] = 0.0
     o3, s3, _ = call(o1, mixed)
     want3, _, st3 = oracles["tot"].integrate_batch(o1.cpu().numpy(), g["fix"][:16], g["rconst"][:16], 0.0, 10.0, hstart=mixed.cpu().numpy())
     assert np.array_equal(s3.cpu().numpy(), st3)
-    check(o3.cpu().numpy(), want3, "tot, Hstart reuse on every other cell:")
+    check("tot", o3.cpu().numpy(), want3, "tot, Hstart reuse on every other cell:")
     d = rel_diff(o2.cpu().numpy(), o2_ref.cpu().numpy())
     print("Hstart reuse, second call: %d steps instead of %d; max rel diff to the reference path %.2e"
           % (int(s2[:, 2].sum()), int(s2_ref[:, 2].sum()), d.max()))

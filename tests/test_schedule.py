@@ -29,6 +29,7 @@ def emu():
     lib.emu_dense_nd.argtypes = [C.c_void_p]
     lib.emu_lu.argtypes = [C.c_void_p, dp, dp, dp]
     lib.emu_solve_backward.argtypes = [C.c_void_p, dp, dp]
+    lib.emu_solve_kernel_form.argtypes = [C.c_void_p, dp, dp]
     lib.emu_solve.argtypes = [C.c_void_p, dp, dp]
     lib.emu_solve_split.argtypes = [C.c_void_p, dp, dp]
     lib.emu_fun.argtypes = [C.c_void_p, dp, dp, dp, dp]
@@ -97,6 +98,62 @@ def test_programs_match_oracle(emu, mech, nt, golden, oracles):
         x2 = b.copy()
         assert emu.emu_solve_split(h, P(lu_ref), P(x2)) == 0, "hazard inside a head round"
         assert np.abs(x2 - x_ref).max() <= 1e-11 * np.abs(x_ref).max()
+
+
+@pytest.mark.parametrize("mech,nt", [("gas", 128), ("gas", 64), ("aer", 512), ("aer", 320), ("tot", 512), ("tot", 1024)])
+def test_programs_match_oracle_variant4_at_running_step_sizes(emu, mech, nt, golden, oracles):
+    """The CPU mirror of tests/test_gpu_phases.py::test_phases_at_running_step_sizes.  test_programs_match_oracle above factorises Ghimj = 2294*I - J,
+    the matrix of the first attempt at H = 1e-3; the integrator spends its life at H of 0.1 to 10 s, where the factors of the pinned oracle and of
+    the kernel's programs drift apart by up to 2.6e-5 of the row maximum (aer, H = 10) — because the kernel forms its multipliers as W*R instead
+    of W/U(j,j), which is oracle.set_variant(4).  Against THAT re-association of the oracle the programs agree to round-off at every H: cells
+    {0, 7, last} in two states (var_in and the captured var_out) at H in {1e-3, 0.1, Hexit, 10}:
+      head rows (below emu_tail_h)   bit for bit
+      tail rows, gas and aer         <= 4 units of round-off of each entry (R = 1/U, W*R, U*R and the un-scaling product: one rounding each);
+                                     measured 2.2 (gas), 2.3 (aer)
+      tail rows, tot                 the dense block's fused multiply-add chains: measured 7.4e-14 of the row maximum, bound 10x that
+                                     (parity_bounds.TOT_TAIL_BOUND, held to [10x, 100x] of the measurement here); variant 4 against variant 6, the
+                                     oracle's own contracted factorisation, moves the same entries by 9.5e-10
+      K1..K3 by the solve programs   against the oracle's reciprocal-pivot solve on variant-4 factors, <= 10x the spread of the oracle's eight solve
+                                     variants at that step size (parity_bounds.check_k_vectors); measured error / spread, worst of both states:
+                                     gas 5e-17 / 1.7e-16, aer 2.8e-12 / 6.9e-13 (Hexit), tot 1.1e-9 / 4.0e-10 (Hexit)."""
+    import parity_bounds as pb
+    from mistra_amd.mechtab import load
+    o, g, t = oracles[mech], golden[mech], load(mech)
+    h = emu.emu_create(os.path.join(REPO, "mistra_amd", "mech", mech + ".mech").encode(), nt)
+    assert h, "schedule compiler failed"
+    tail_h = emu.emu_tail_h(h)
+    C21, C31, C32 = -0.10156171083877702091975600115545e+01, 0.40759956452537699824805835358067e+01, 0.92076794298330791242156818474003e+01
+    worst_ulps = worst_row = 0.0
+    for state in pb.PHASE_STATES:
+        V, F, K, H = pb.phase_cases(g, o, state)
+        found = []
+        for i in range(len(H)):
+            v, f, k = V[i], F[i], K[i]
+            fcn0 = o.fun(v, f, k)
+            G = -o.jac_sp(v, f, k)
+            G[t.diag] += 1.0 / (H[i] * GAMMA1)
+            lu_v4 = pb.variant4_factors(o, G)
+            lu, R, k1 = G.copy(), np.empty(o.nvar), fcn0.copy()
+            assert emu.emu_lu(h, P(lu), P(R), P(k1)) == 0
+            ulps, of_row = pb.check_lu_against_variant4(mech, t, tail_h, lu, lu_v4)
+            worst_ulps, worst_row = max(worst_ulps, ulps), max(worst_row, of_row)
+            # the three stages as the kernel runs them (gas.f:1236-1262), each on the previous stages' vectors
+            assert emu.emu_solve_backward(h, P(lu), P(k1)) == 0
+            fcn = o.fun(v + k1, f, k)
+            r2 = np.ascontiguousarray(fcn + (C21 / H[i]) * k1)
+            k2 = r2.copy()
+            assert emu.emu_solve_kernel_form(h, P(lu), P(k2)) == 0
+            r3 = np.ascontiguousarray((fcn + (C31 / H[i]) * k1) + (C32 / H[i]) * k2)
+            k3 = r3.copy()
+            assert emu.emu_solve_kernel_form(h, P(lu), P(k3)) == 0
+            for got, rhs in ((k1, fcn0), (k2, r2), (k3, r3)):
+                want, spread = pb.solve_reference_and_spread(o, lu_v4, rhs)
+                found.append((i % len(pb.PHASE_H), np.abs(got - want).max() / np.abs(want).max(), spread))
+        per_h = pb.check_k_vectors(mech, found)
+        print(mech, nt, state, "K vectors, error / spread per H:", "  ".join("%.1e / %.1e" % per_h[i] for i in sorted(per_h)))
+    print(mech, nt, "LU tail rows vs variant 4: %.2f units of round-off of the entry, %.2e of the row maximum" % (worst_ulps, worst_row))
+    if mech == "tot":
+        pb.check_constant("TOT_TAIL_BOUND", pb.TOT_TAIL_BOUND, worst_row)
 
 
 def test_round_structure_tot(emu):
