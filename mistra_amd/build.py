@@ -111,7 +111,7 @@ def ring_register_report(isa_path=None):
                     if m:
                         hi = max(hi, int(m.group(1) or m.group(3)))
         report[name] = hi
-        low = re.search(r"(gsum_run|tail_solve|tail_solve_columns|scale_run)I.*Lb([01])E+[A-Z]", name)       # last template argument: ring placement LOW
+        low = re.search(r"(gsum_run|tail_solve|scale_run)I.*Lb([01])E+[A-Z]", name)       # last template argument: ring placement LOW
         if low:
             limit = 64 if low.group(2) == "1" else 192
             if hi >= limit:

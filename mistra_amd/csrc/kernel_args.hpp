@@ -9,7 +9,7 @@ constexpr int kVmSweepUpdPerRec = 3;   // updates per record of the sweep progra
 
 struct VmDev {                 // LDS VM program in device memory (see schedule.hpp)
   const uint32_t* wave_base;   // [NW]         first record row of each wave's stream
-  const uint16_t* blk_n;       // [nrounds*NW] record rows per (round, wave)
+  const uint16_t* blk_n;       // [nrounds*NW] record rows per (round, wave): uploaded, but no kernel reads it (the host-side copy serves the emulator)
   const uint32_t* recs;        // uint4 per lane and row, 16-byte aligned
   int nrounds;
 };
@@ -27,10 +27,10 @@ struct ScaleDev {              // final scaling of the factorisation (schedule.h
 };
 
 struct TailDev {               // tail chain of the triangular solves (schedule.hpp: TailSolve)
-  const uint32_t* fwd;         // u32x4 per lane and group of 4 columns, columns ascending (two 16-bit cells per word: tail_solve_columns)
-  const uint32_t* bwd;         // same, columns descending
-  const uint32_t* fwd_addr[2]; // per register: the same layout, one LDS byte address per word (tail_solve); null past the tail's registers
-  const uint32_t* bwd_addr[2];
+  const uint32_t* fwd;         // the host-side 16-bit tables (TailSolve::fwd / bwd): uploaded, but no kernel reads them — the device
+  const uint32_t* bwd;         //   gathers through the address tables below
+  const uint32_t* fwd_addr[2]; // per register: u32x4 per lane and group of 4 columns, columns ascending, one LDS byte address per word
+  const uint32_t* bwd_addr[2]; //   (tail_solve); bwd: columns descending; null past the tail's registers
 };
 
 struct DenseDev {              // dense tail block (schedule.hpp: DenseTail); null where the mechanism has none

@@ -134,117 +134,98 @@ __device__ __forceinline__ double fmax_f(double a, double b) { return (a > b || 
 // hipcc's own s_waitcnt placement falls back to vmcnt(0) around branches and barriers, which would serialise every
 // table row behind a full memory round trip, so the loads are issued from asm and counted by hand.  A compiler-visible
 // VGPR destination would be unsafe (the compiler may copy an asm output before the data lands, cdna_hip_programming.md
-// §5.7 item 1).  The ring therefore lives in fixed registers named only by the two statements below; the consume
-// statement waits and copies out in ONE asm (§5.7 form i).  Loads are in flight only inside the two non-inlined functions
-// that use the ring (each drains it before returning), and those functions' own values sit below the ring (they need
+// §5.7 item 1).  The ring therefore lives in fixed registers named only by the statements built from the table below; a consume
+// statement waits and copies out (or gathers through the words) in ONE asm (§5.7 form i).  Loads are in flight only inside the
+// non-inlined functions that use the ring (gsum_run, tail_solve, scale_run: each drains it before returning), and those functions' own values sit below the ring (they need
 // < 64 registers; mistra_amd/build.py checks the generated ISA before it links), so nothing of the compiler's can be hit by a landing
 // load; the callers see the blocks as ordinary call-clobbered registers.  Two placements (LOW):
 //   false  v192-199, v208-215, v224-231, v240-247: four caller-saved blocks at the top of the file, nothing to save — for
 //          kernels that run two waves per SIMD and have 256 registers (tot: one cell fills a CU's LDS anyway);
-//   true   v64-71, v80-87, v96-103, v112-119: four caller-saved blocks again, for the kernels held to 128 registers (FOUR waves
-//          per SIMD — aer: two cells per CU instead of one, +39 %; gas: eight cells per CU); the functions' own values stay below v64
-//          (the build checks it).  (Until round 2 this ring was v96-127: two of those blocks are callee-saved, every call
+//   true   v64-71, v80-87, v96-103, v112-119: four caller-saved blocks again, for the kernel that runs more than two waves per
+//          SIMD (gas; aer too while it was held to 128 registers); the functions' own values stay below v64 (the build checks it).  (Until round 2 this ring was v96-127: two of those blocks are callee-saved, every call
 //          of gsum_run / tail_solve stored and reloaded 16 registers per lane — most of the aer kernel's HBM-side traffic.)
 // Loads return in issue order, hence "at most PENDING outstanding" means the oldest one — the slot about to be
 // consumed — has landed.  (An earlier version kept the ring in AGPRs: any AGPR use halves the compiler's VGPR budget
 // on gfx950, which cost the kernel ~100 spilled registers.)
+//
+// The ring's sixteen slots of four registers, stated ONCE: slot K of the low (v64..) and of the high (v192..) placement.  (The
+// generated streams name the same blocks: tools/gen_gsum_asm.py: SLOTS; tests/test_capi.py holds the two together.)
+#define MISTRA_RING_LO0 64, 65, 66, 67
+#define MISTRA_RING_LO1 68, 69, 70, 71
+#define MISTRA_RING_LO2 80, 81, 82, 83
+#define MISTRA_RING_LO3 84, 85, 86, 87
+#define MISTRA_RING_LO4 96, 97, 98, 99
+#define MISTRA_RING_LO5 100, 101, 102, 103
+#define MISTRA_RING_LO6 112, 113, 114, 115
+#define MISTRA_RING_LO7 116, 117, 118, 119
+#define MISTRA_RING_HI0 192, 193, 194, 195
+#define MISTRA_RING_HI1 196, 197, 198, 199
+#define MISTRA_RING_HI2 208, 209, 210, 211
+#define MISTRA_RING_HI3 212, 213, 214, 215
+#define MISTRA_RING_HI4 224, 225, 226, 227
+#define MISTRA_RING_HI5 228, 229, 230, 231
+#define MISTRA_RING_HI6 240, 241, 242, 243
+#define MISTRA_RING_HI7 244, 245, 246, 247
+#define MISTRA_APPLY(M, ...) M(__VA_ARGS__)
+// M(the four registers of slot K in placement LOW): K and LOW are the template parameters of the function it stands in
+#define MISTRA_ON_RING_SLOT(M)                                                                                                 \
+  static_assert(K >= 0 && K < kRingSlots, "ring slot");                                                                        \
+  if constexpr (LOW) {                                                                                                         \
+    if constexpr (K == 0) MISTRA_APPLY(M, MISTRA_RING_LO0);                                                                    \
+    else if constexpr (K == 1) MISTRA_APPLY(M, MISTRA_RING_LO1);                                                               \
+    else if constexpr (K == 2) MISTRA_APPLY(M, MISTRA_RING_LO2);                                                               \
+    else if constexpr (K == 3) MISTRA_APPLY(M, MISTRA_RING_LO3);                                                               \
+    else if constexpr (K == 4) MISTRA_APPLY(M, MISTRA_RING_LO4);                                                               \
+    else if constexpr (K == 5) MISTRA_APPLY(M, MISTRA_RING_LO5);                                                               \
+    else if constexpr (K == 6) MISTRA_APPLY(M, MISTRA_RING_LO6);                                                               \
+    else MISTRA_APPLY(M, MISTRA_RING_LO7);                                                                                     \
+  } else {                                                                                                                     \
+    if constexpr (K == 0) MISTRA_APPLY(M, MISTRA_RING_HI0);                                                                    \
+    else if constexpr (K == 1) MISTRA_APPLY(M, MISTRA_RING_HI1);                                                               \
+    else if constexpr (K == 2) MISTRA_APPLY(M, MISTRA_RING_HI2);                                                               \
+    else if constexpr (K == 3) MISTRA_APPLY(M, MISTRA_RING_HI3);                                                               \
+    else if constexpr (K == 4) MISTRA_APPLY(M, MISTRA_RING_HI4);                                                               \
+    else if constexpr (K == 5) MISTRA_APPLY(M, MISTRA_RING_HI5);                                                               \
+    else if constexpr (K == 6) MISTRA_APPLY(M, MISTRA_RING_HI6);                                                               \
+    else MISTRA_APPLY(M, MISTRA_RING_HI7);                                                                                     \
+  }
+// M(args, the sixteen registers of ring half H — slots 4H .. 4H + 3 — in table column order)
+#define MISTRA_ON_RING_HALF(M, ...)                                                                                            \
+  if constexpr (LOW && H == 0) MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_LO0, MISTRA_RING_LO1, MISTRA_RING_LO2, MISTRA_RING_LO3); \
+  else if constexpr (LOW) MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_LO4, MISTRA_RING_LO5, MISTRA_RING_LO6, MISTRA_RING_LO7);    \
+  else if constexpr (H == 0) MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HI0, MISTRA_RING_HI1, MISTRA_RING_HI2, MISTRA_RING_HI3); \
+  else MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HI4, MISTRA_RING_HI5, MISTRA_RING_HI6, MISTRA_RING_HI7);
+
 template <bool LOW, int K, int BYTE_OFFSET = 0>
 __device__ __forceinline__ void vm_ring_load(gptr<u32x4> p) {
 #define MISTRA_RING_LOAD(R0, R1, R2, R3)                                                                              \
   asm volatile("global_load_dwordx4 v[" #R0 ":" #R3 "], %0, off offset:%1" : : "v"(p), "n"(BYTE_OFFSET)             \
                : "memory", "v" #R0, "v" #R1, "v" #R2, "v" #R3)
-  if constexpr (LOW) {
-    if constexpr (K == 0) MISTRA_RING_LOAD(64, 65, 66, 67);
-    else if constexpr (K == 1) MISTRA_RING_LOAD(68, 69, 70, 71);
-    else if constexpr (K == 2) MISTRA_RING_LOAD(80, 81, 82, 83);
-    else if constexpr (K == 3) MISTRA_RING_LOAD(84, 85, 86, 87);
-    else if constexpr (K == 4) MISTRA_RING_LOAD(96, 97, 98, 99);
-    else if constexpr (K == 5) MISTRA_RING_LOAD(100, 101, 102, 103);
-    else if constexpr (K == 6) MISTRA_RING_LOAD(112, 113, 114, 115);
-    else MISTRA_RING_LOAD(116, 117, 118, 119);
-  } else {
-    if constexpr (K == 0) MISTRA_RING_LOAD(192, 193, 194, 195);
-    else if constexpr (K == 1) MISTRA_RING_LOAD(196, 197, 198, 199);
-    else if constexpr (K == 2) MISTRA_RING_LOAD(208, 209, 210, 211);
-    else if constexpr (K == 3) MISTRA_RING_LOAD(212, 213, 214, 215);
-    else if constexpr (K == 4) MISTRA_RING_LOAD(224, 225, 226, 227);
-    else if constexpr (K == 5) MISTRA_RING_LOAD(228, 229, 230, 231);
-    else if constexpr (K == 6) MISTRA_RING_LOAD(240, 241, 242, 243);
-    else MISTRA_RING_LOAD(244, 245, 246, 247);
-  }
+  MISTRA_ON_RING_SLOT(MISTRA_RING_LOAD)
 #undef MISTRA_RING_LOAD
 }
 
-// The same load with the table's base in scalar registers and the lane's 32-bit byte offset in ONE vector register: the row a load
-// fetches is base + ROW KiB.  Rows 0..3 go into the instruction's immediate offset (13 bits signed on gfx950), rows 4..8 take the
-// second base, 4 KiB further on.  (With per-lane 64-bit pointers the compiler kept one 64-bit row offset per load in scalar
-// registers — enough of them to reach the callee-saved ones, whose save area cost tail_solve_columns a scratch store and reload
-// per call: aer's last per-step HBM traffic.)
-struct RingBase { uint64_t b0, b1; };      // b1 = b0 + 4096
-__device__ __forceinline__ RingBase ring_base(const void* p) {
+// A table's base in scalar registers: the tail chain loads its rows through a scalar base and the lane's 32-bit byte offset in ONE
+// vector register (vm_ring_load_at).  (With per-lane 64-bit pointers the compiler kept one 64-bit row offset per load in scalar
+// registers — enough of them to reach the callee-saved ones, whose save area cost the tail chain a scratch store and reload per
+// call: aer's last per-step HBM traffic.)
+__device__ __forceinline__ uint64_t ring_base(const void* p) {
   const uint64_t u = (uint64_t)(uintptr_t)p;
   uint32_t lo, hi;
   // (a scalar register written by a vector instruction may not feed a memory instruction's address for 5 wait states, and the
   // compiler's hazard pass does not look inside the asm statements that issue the loads: the wait is spelled out here)
   asm volatile("v_readfirstlane_b32 %0, %2\n\tv_readfirstlane_b32 %1, %3\n\ts_nop 4" : "=s"(lo), "=s"(hi) : "v"((uint32_t)u), "v"((uint32_t)(u >> 32)));
-  const uint64_t b = (uint64_t)lo | ((uint64_t)hi << 32);
-  return RingBase{b, b + 4096};
+  return (uint64_t)lo | ((uint64_t)hi << 32);
 }
-__device__ __forceinline__ void ring_advance(RingBase& r, uint32_t bytes) { r.b0 += bytes; r.b1 += bytes; }
-template <bool LOW, int K, int ROW>
-__device__ __forceinline__ void vm_ring_load_s(const RingBase& r, uint32_t voff) {
-  static_assert(ROW >= 0 && ROW <= 7, "row within the two 4-KiB windows");
-#define MISTRA_RING_LOAD_S(R0, R1, R2, R3)                                                                                    \
-  asm volatile("global_load_dwordx4 v[" #R0 ":" #R3 "], %0, %1 offset:%2" : : "v"(voff), "s"(ROW < 4 ? r.b0 : r.b1), "n"((ROW % 4) * 1024) \
-               : "memory", "v" #R0, "v" #R1, "v" #R2, "v" #R3)
-  if constexpr (LOW) {
-    if constexpr (K == 0) MISTRA_RING_LOAD_S(64, 65, 66, 67);
-    else if constexpr (K == 1) MISTRA_RING_LOAD_S(68, 69, 70, 71);
-    else if constexpr (K == 2) MISTRA_RING_LOAD_S(80, 81, 82, 83);
-    else if constexpr (K == 3) MISTRA_RING_LOAD_S(84, 85, 86, 87);
-    else if constexpr (K == 4) MISTRA_RING_LOAD_S(96, 97, 98, 99);
-    else if constexpr (K == 5) MISTRA_RING_LOAD_S(100, 101, 102, 103);
-    else if constexpr (K == 6) MISTRA_RING_LOAD_S(112, 113, 114, 115);
-    else MISTRA_RING_LOAD_S(116, 117, 118, 119);
-  } else {
-    if constexpr (K == 0) MISTRA_RING_LOAD_S(192, 193, 194, 195);
-    else if constexpr (K == 1) MISTRA_RING_LOAD_S(196, 197, 198, 199);
-    else if constexpr (K == 2) MISTRA_RING_LOAD_S(208, 209, 210, 211);
-    else if constexpr (K == 3) MISTRA_RING_LOAD_S(212, 213, 214, 215);
-    else if constexpr (K == 4) MISTRA_RING_LOAD_S(224, 225, 226, 227);
-    else if constexpr (K == 5) MISTRA_RING_LOAD_S(228, 229, 230, 231);
-    else if constexpr (K == 6) MISTRA_RING_LOAD_S(240, 241, 242, 243);
-    else MISTRA_RING_LOAD_S(244, 245, 246, 247);
-  }
-#undef MISTRA_RING_LOAD_S
-}
-
-// ... and with the row's base handed over as it stands (a compile-time offset from a table's start: two scalar additions)
+// The same load from such a base: the row's base handed over as it stands (a compile-time offset from a table's start: two scalar
+// additions), IMM in the instruction's immediate offset (13 bits signed on gfx950)
 template <bool LOW, int K, int IMM>
 __device__ __forceinline__ void vm_ring_load_at(uint64_t sbase, uint32_t voff) {
   static_assert(IMM >= 0 && IMM < 4096, "13-bit signed immediate offset");
 #define MISTRA_RING_LOAD_AT(R0, R1, R2, R3)                                                                                   \
   asm volatile("global_load_dwordx4 v[" #R0 ":" #R3 "], %0, %1 offset:%2" : : "v"(voff), "s"(sbase), "n"(IMM)                \
                : "memory", "v" #R0, "v" #R1, "v" #R2, "v" #R3)
-  if constexpr (LOW) {
-    if constexpr (K == 0) MISTRA_RING_LOAD_AT(64, 65, 66, 67);
-    else if constexpr (K == 1) MISTRA_RING_LOAD_AT(68, 69, 70, 71);
-    else if constexpr (K == 2) MISTRA_RING_LOAD_AT(80, 81, 82, 83);
-    else if constexpr (K == 3) MISTRA_RING_LOAD_AT(84, 85, 86, 87);
-    else if constexpr (K == 4) MISTRA_RING_LOAD_AT(96, 97, 98, 99);
-    else if constexpr (K == 5) MISTRA_RING_LOAD_AT(100, 101, 102, 103);
-    else if constexpr (K == 6) MISTRA_RING_LOAD_AT(112, 113, 114, 115);
-    else MISTRA_RING_LOAD_AT(116, 117, 118, 119);
-  } else {
-    if constexpr (K == 0) MISTRA_RING_LOAD_AT(192, 193, 194, 195);
-    else if constexpr (K == 1) MISTRA_RING_LOAD_AT(196, 197, 198, 199);
-    else if constexpr (K == 2) MISTRA_RING_LOAD_AT(208, 209, 210, 211);
-    else if constexpr (K == 3) MISTRA_RING_LOAD_AT(212, 213, 214, 215);
-    else if constexpr (K == 4) MISTRA_RING_LOAD_AT(224, 225, 226, 227);
-    else if constexpr (K == 5) MISTRA_RING_LOAD_AT(228, 229, 230, 231);
-    else if constexpr (K == 6) MISTRA_RING_LOAD_AT(240, 241, 242, 243);
-    else MISTRA_RING_LOAD_AT(244, 245, 246, 247);
-  }
+  MISTRA_ON_RING_SLOT(MISTRA_RING_LOAD_AT)
 #undef MISTRA_RING_LOAD_AT
 }
 
@@ -255,77 +236,17 @@ __device__ __forceinline__ u32x4 vm_ring_take() {
   asm volatile("s_waitcnt vmcnt(%4)\n\tv_mov_b32 %0, v" #R0 "\n\tv_mov_b32 %1, v" #R1                                   \
                "\n\tv_mov_b32 %2, v" #R2 "\n\tv_mov_b32 %3, v" #R3                                                    \
                : "=v"(x), "=v"(y), "=v"(z), "=v"(w) : "n"(PENDING) : "memory")
-  if constexpr (LOW) {
-    if constexpr (K == 0) MISTRA_RING_TAKE(64, 65, 66, 67);
-    else if constexpr (K == 1) MISTRA_RING_TAKE(68, 69, 70, 71);
-    else if constexpr (K == 2) MISTRA_RING_TAKE(80, 81, 82, 83);
-    else if constexpr (K == 3) MISTRA_RING_TAKE(84, 85, 86, 87);
-    else if constexpr (K == 4) MISTRA_RING_TAKE(96, 97, 98, 99);
-    else if constexpr (K == 5) MISTRA_RING_TAKE(100, 101, 102, 103);
-    else if constexpr (K == 6) MISTRA_RING_TAKE(112, 113, 114, 115);
-    else MISTRA_RING_TAKE(116, 117, 118, 119);
-  } else {
-    if constexpr (K == 0) MISTRA_RING_TAKE(192, 193, 194, 195);
-    else if constexpr (K == 1) MISTRA_RING_TAKE(196, 197, 198, 199);
-    else if constexpr (K == 2) MISTRA_RING_TAKE(208, 209, 210, 211);
-    else if constexpr (K == 3) MISTRA_RING_TAKE(212, 213, 214, 215);
-    else if constexpr (K == 4) MISTRA_RING_TAKE(224, 225, 226, 227);
-    else if constexpr (K == 5) MISTRA_RING_TAKE(228, 229, 230, 231);
-    else if constexpr (K == 6) MISTRA_RING_TAKE(240, 241, 242, 243);
-    else MISTRA_RING_TAKE(244, 245, 246, 247);
-  }
+  MISTRA_ON_RING_SLOT(MISTRA_RING_TAKE)
 #undef MISTRA_RING_TAKE
   return u32x4{x, y, z, w};
 }
-// The 16-bit table rows of the tail chain (tail_solve_columns; the block form reads address tables) hold two Ghimj cell numbers per word (low half: the rows of register 0, high half: of
-// register 1).  This takes slot K out of the ring and turns the halves that are wanted straight into LDS byte addresses, one
-// v_lshlrev_b32_sdwa per cell reading the ring register itself: copied out first and decoded by the compiler it was 4 moves, 4 ands and
-// 8 shifts per slot, a fifth of the instructions of a chain that is bound by instruction issue (a lone wave: one instruction per
-// 4-7 cycles whatever it is).  three: a register holding 3 (the shift count; SDWA takes no literal).
-template <bool LOW, int K, int PENDING, bool LO, bool HI>
-__device__ __forceinline__ void vm_ring_take_cells(uint32_t* lo, uint32_t* hi, uint32_t three) {
-  static_assert(LO || HI, "nothing to take");
-#define MISTRA_SDWA(D, R, W) "\n\tv_lshlrev_b32_sdwa %" #D ", %[three], v" #R " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_" #W
-#define MISTRA_TAKE_CELLS(R0, R1, R2, R3)                                                                                              \
-  if constexpr (LO && HI)                                                                                                              \
-    asm volatile("s_waitcnt vmcnt(%[pend])" MISTRA_SDWA(0, R0, 0) MISTRA_SDWA(1, R1, 0) MISTRA_SDWA(2, R2, 0) MISTRA_SDWA(3, R3, 0)    \
-                 MISTRA_SDWA(4, R0, 1) MISTRA_SDWA(5, R1, 1) MISTRA_SDWA(6, R2, 1) MISTRA_SDWA(7, R3, 1)                              \
-                 : "=&v"(lo[0]), "=&v"(lo[1]), "=&v"(lo[2]), "=&v"(lo[3]), "=&v"(hi[0]), "=&v"(hi[1]), "=&v"(hi[2]), "=&v"(hi[3])      \
-                 : [three] "v"(three), [pend] "n"(PENDING) : "memory");                                                              \
-  else if constexpr (LO)                                                                                                               \
-    asm volatile("s_waitcnt vmcnt(%[pend])" MISTRA_SDWA(0, R0, 0) MISTRA_SDWA(1, R1, 0) MISTRA_SDWA(2, R2, 0) MISTRA_SDWA(3, R3, 0)    \
-                 : "=&v"(lo[0]), "=&v"(lo[1]), "=&v"(lo[2]), "=&v"(lo[3]) : [three] "v"(three), [pend] "n"(PENDING) : "memory");      \
-  else                                                                                                                                 \
-    asm volatile("s_waitcnt vmcnt(%[pend])" MISTRA_SDWA(0, R0, 1) MISTRA_SDWA(1, R1, 1) MISTRA_SDWA(2, R2, 1) MISTRA_SDWA(3, R3, 1)    \
-                 : "=&v"(hi[0]), "=&v"(hi[1]), "=&v"(hi[2]), "=&v"(hi[3]) : [three] "v"(three), [pend] "n"(PENDING) : "memory");
-  if constexpr (LOW) {
-    if constexpr (K == 0) { MISTRA_TAKE_CELLS(64, 65, 66, 67) }
-    else if constexpr (K == 1) { MISTRA_TAKE_CELLS(68, 69, 70, 71) }
-    else if constexpr (K == 2) { MISTRA_TAKE_CELLS(80, 81, 82, 83) }
-    else if constexpr (K == 3) { MISTRA_TAKE_CELLS(84, 85, 86, 87) }
-    else if constexpr (K == 4) { MISTRA_TAKE_CELLS(96, 97, 98, 99) }
-    else if constexpr (K == 5) { MISTRA_TAKE_CELLS(100, 101, 102, 103) }
-    else if constexpr (K == 6) { MISTRA_TAKE_CELLS(112, 113, 114, 115) }
-    else { MISTRA_TAKE_CELLS(116, 117, 118, 119) }
-  } else {
-    if constexpr (K == 0) { MISTRA_TAKE_CELLS(192, 193, 194, 195) }
-    else if constexpr (K == 1) { MISTRA_TAKE_CELLS(196, 197, 198, 199) }
-    else if constexpr (K == 2) { MISTRA_TAKE_CELLS(208, 209, 210, 211) }
-    else if constexpr (K == 3) { MISTRA_TAKE_CELLS(212, 213, 214, 215) }
-    else if constexpr (K == 4) { MISTRA_TAKE_CELLS(224, 225, 226, 227) }
-    else if constexpr (K == 5) { MISTRA_TAKE_CELLS(228, 229, 230, 231) }
-    else if constexpr (K == 6) { MISTRA_TAKE_CELLS(240, 241, 242, 243) }
-    else { MISTRA_TAKE_CELLS(244, 245, 246, 247) }
-  }
-#undef MISTRA_TAKE_CELLS
-#undef MISTRA_SDWA
-}
-static_assert(kRingSlots == 8, "the ring helpers above are written for 8 slots");
+#undef MISTRA_ON_RING_SLOT
+static_assert(kRingSlots == 8, "the ring table above has 8 slots per placement");
 
 // ---- the LDS VM executor (schedule.hpp), hand-scheduled: one asm statement holds the whole program loop; its instruction
 // stream is generated (tools/gen_vm_asm.py -> vm_exec_asm.inc, where the pipeline and the wait counts are explained).
-//   * records land straight in VGPRs: a ring of N 8-register slots in caller-saved blocks (v48-55, v64-71, ...: N = MT::VM_SLOTS), named only inside this statement, so no compiler copy can get between a load
-//     and its counted wait (cdna_hip_programming.md §5.7); a slot is refilled (row + N) behind its record's store;
+//   * records land straight in VGPRs: a ring of four 8-register slots in caller-saved blocks (v48-55, v64-71, v80-87, v96-103), named only inside this statement, so no compiler copy can get between a load
+//     and its counted wait (cdna_hip_programming.md §5.7); a slot is refilled (row + 4) behind its record's store;
 //   * d0, d2..d7 of a record are LDS byte addresses as they stand (M starts at LDS address 0, checked at kernel entry);
 //     every mark sits on d1: one v_readfirstlane per record, one scalar test for "any mark" on the main line;
 //   * round 3: the six operand gathers of record S+1 are issued at the head of record S (two operand register sets), so a
@@ -339,8 +260,7 @@ static_assert(kRingSlots == 8, "the ring helpers above are written for 8 slots")
 // UPR: updates per record — 2: (a, r, u) triples, the LU program; 3: (a, u) pairs, the triangular sweeps (schedule.hpp)
 template <int NT, int SLOTS, int UPR = 2>
 __device__ __attribute__((noinline)) void vm_run(const VmDev P, uint32_t row0, int lane) {
-  static_assert(SLOTS == 4 || SLOTS == 6 || SLOTS == 8, "ring depths vm_exec_asm.inc is generated for");
-  static_assert(UPR == 2 || (UPR == 3 && SLOTS == 4), "executor variants vm_exec_asm.inc is generated for");
+  static_assert(SLOTS == 4 && (UPR == 2 || UPR == 3), "ring depth and executor variants vm_exec_asm.inc is generated for");
   const uint64_t recs = reinterpret_cast<uint64_t>(P.recs);      // the same in every lane: move it to SGPRs
   const uint64_t base = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)recs) |
                         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(recs >> 32)) << 32);
@@ -359,12 +279,6 @@ __device__ __attribute__((noinline)) void vm_run(const VmDev P, uint32_t row0, i
       [vb] "+v"(vb)
   if constexpr (UPR == 3) {
     asm volatile(MISTRA_VM_ASM_N4_SWEEP : MISTRA_VM_OPERANDS : [base] "s"(base) : "memory", "vcc", "scc", MISTRA_VM_CLOBBER_N4);
-  } else if constexpr (SLOTS == 8) {
-    uint32_t vc = va + 8192u, vd = va + 12288u;                                      // rows +4, +5 and +6, +7
-    asm volatile(MISTRA_VM_ASM_N8 : MISTRA_VM_OPERANDS, [vc] "+v"(vc), [vd] "+v"(vd) : [base] "s"(base) : "memory", "vcc", "scc", MISTRA_VM_CLOBBER_N8);
-  } else if constexpr (SLOTS == 6) {
-    uint32_t vc = va + 8192u;
-    asm volatile(MISTRA_VM_ASM_N6 : MISTRA_VM_OPERANDS, [vc] "+v"(vc) : [base] "s"(base) : "memory", "vcc", "scc", MISTRA_VM_CLOBBER_N6);
   } else {
     asm volatile(MISTRA_VM_ASM_N4 : MISTRA_VM_OPERANDS : [base] "s"(base) : "memory", "vcc", "scc", MISTRA_VM_CLOBBER_N4);
   }
@@ -477,17 +391,6 @@ __device__ __forceinline__ void tail_update(double& x, const double xb, const do
   [g0] "=&v"(g[0]), [g1] "=&v"(g[1]), [g2] "=&v"(g[2]), [g3] "=&v"(g[3]), [g4] "=&v"(g[4]), [g5] "=&v"(g[5]), [g6] "=&v"(g[6]),           \
       [g7] "=&v"(g[7]), [g8] "=&v"(g[8]), [g9] "=&v"(g[9]), [g10] "=&v"(g[10]), [g11] "=&v"(g[11]), [g12] "=&v"(g[12]),                   \
       [g13] "=&v"(g[13]), [g14] "=&v"(g[14]), [g15] "=&v"(g[15])
-// the ring registers of group half H (slots 4H .. 4H + 3, see vm_ring_load) in table column order
-#define MISTRA_RING_HALF_HI0 192, 193, 194, 195, 196, 197, 198, 199, 208, 209, 210, 211, 212, 213, 214, 215
-#define MISTRA_RING_HALF_HI1 224, 225, 226, 227, 228, 229, 230, 231, 240, 241, 242, 243, 244, 245, 246, 247
-#define MISTRA_RING_HALF_LO0 64, 65, 66, 67, 68, 69, 70, 71, 80, 81, 82, 83, 84, 85, 86, 87
-#define MISTRA_RING_HALF_LO1 96, 97, 98, 99, 100, 101, 102, 103, 112, 113, 114, 115, 116, 117, 118, 119
-#define MISTRA_APPLY(M, ...) M(__VA_ARGS__)
-#define MISTRA_ON_RING_HALF(M, ...)                                                                                            \
-  if constexpr (LOW && H == 0) MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HALF_LO0);                                            \
-  else if constexpr (LOW) MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HALF_LO1);                                                 \
-  else if constexpr (H == 0) MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HALF_HI0);                                              \
-  else MISTRA_APPLY(M, __VA_ARGS__, MISTRA_RING_HALF_HI1);
 #define MISTRA_G2(A, RA, B, RB) "ds_read_b64 %[g" #A "], v" #RA "\n\tds_read_b64 %[g" #B "], v" #RB "\n\t"
 #define MISTRA_G16(r0, r1, r2, r3, r4, r5, r6, r7, r8, r9, r10, r11, r12, r13, r14, r15)                                        \
   MISTRA_G2(0, r0, 1, r1) MISTRA_G2(2, r2, 3, r3) MISTRA_G2(4, r4, 5, r5) MISTRA_G2(6, r6, 7, r7) MISTRA_G2(8, r8, 9, r9)       \
@@ -562,12 +465,8 @@ __device__ __forceinline__ void tail_gather(double (&g)[16]) {
   MISTRA_ON_RING_HALF(MISTRA_GATHER_ONLY, 0)
 }
 #undef MISTRA_TAIL_GOPS
-#undef MISTRA_RING_HALF_HI0
-#undef MISTRA_RING_HALF_HI1
-#undef MISTRA_RING_HALF_LO0
-#undef MISTRA_RING_HALF_LO1
-#undef MISTRA_APPLY
 #undef MISTRA_ON_RING_HALF
+#undef MISTRA_APPLY
 #undef MISTRA_G2
 #undef MISTRA_G16
 #undef MISTRA_DSTEP
@@ -687,8 +586,8 @@ __device__ __attribute__((noinline)) void tail_solve(const TailDev T, uint32_t x
   uint64_t tf[R], tb[R];
 #pragma unroll
   for (int r = 0; r < R; r++) {
-    tf[r] = ring_base(T.fwd_addr[r]).b0;
-    tb[r] = ring_base(T.bwd_addr[r]).b0;
+    tf[r] = ring_base(T.fwd_addr[r]);
+    tb[r] = ring_base(T.bwd_addr[r]);
   }
   const uint32_t voff = 16u * (uint32_t)lane;
   auto load = [&](auto group) {
@@ -728,120 +627,6 @@ __device__ __attribute__((noinline)) void tail_solve(const TailDev T, uint32_t x
   MISTRA_TAIL_STEP(8) MISTRA_TAIL_STEP(9) MISTRA_TAIL_STEP(10) MISTRA_TAIL_STEP(11) MISTRA_TAIL_STEP(12) MISTRA_TAIL_STEP(13) MISTRA_TAIL_STEP(14) MISTRA_TAIL_STEP(15)
 #undef MISTRA_TAIL_STEP
   asm volatile("s_waitcnt vmcnt(0)" : : : "memory");     // the look-ahead loads past the stream's end have landed
-#pragma unroll
-  for (int r = 0; r < R; r++) lds_st(xb + 8 * (r * 64 + lane), x[r]);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, l);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), l);
-  return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
-}
-
-// FWD_FROM: first 64-row block of the forward chain.  0: the whole forward chain; R: none (the vector has been forward-swept
-// already — stage 1, inside the LU program).
-// The column-by-column form of the chain, kept for the kernels held to 128 registers (aer, gas): the pivot value travels by
-// v_readlane (~57 cycles per column); the block form above needs 16 operands per lane in registers at once, more than those
-// kernels' functions have below their look-ahead ring.
-template <int R, int FWD_FROM, bool LOW>
-__device__ __attribute__((noinline)) void tail_solve_columns(const TailDev T, uint32_t xb, uint32_t rb, int lane) {
-  constexpr int FWD_END = R;
-  constexpr bool FORWARD = FWD_FROM < FWD_END;
-  constexpr uint32_t mb = 0;      // M starts at LDS address 0 (checked at kernel entry); xb, rb: LDS addresses of the tail of XS and R
-  double x[R], rd[R];
-  const uint32_t voff = 16u * (uint32_t)lane;      // the lane's u32x4 within a table row
-  static_assert(R == 1 || R == 2, "one or two 64-row registers");
-  uint32_t three = 3;
-  asm volatile("" : "+v"(three));
-#pragma unroll
-  for (int r = 0; r < R; r++) x[r] = lds_ld(xb + 8 * (r * 64 + lane));
-  // Matrix entries of a 4-column group are read from LDS one group AHEAD of the chain that uses them (two register
-  // buffers, alternating): a lone wave would otherwise expose the LDS latency once per group.  Every row slot is read
-  // for every group (rows that take no part point at the 0.0 cell); the arithmetic loops keep their exact row ranges.
-  // (the group's table words come out of the ring as LDS addresses, vm_ring_take_cells: low halves = register 0's rows, high = register 1's)
-#define MISTRA_TAIL_OPERANDS(BUF, K, PENDING)                                           \
-  {                                                                                     \
-    uint32_t alo[4], ahi[4];                                                            \
-    vm_ring_take_cells<LOW, K, PENDING, true, R == 2>(alo, ahi, three);                 \
-    _Pragma("unroll") for (int c = 0; c < 4; c++) {                                     \
-      BUF[c][0] = lds_ld(mb + alo[c]);                                                  \
-      if constexpr (R == 2) BUF[c][1] = lds_ld(mb + ahi[c]);                            \
-    }                                                                                   \
-  }
-  // The compiler would otherwise park the off-chain row updates (and their operands) until the row is next read, sixty
-  // columns later: pin every group's results to the end of its group.
-#define MISTRA_TAIL_PIN _Pragma("unroll") for (int r = 0; r < R; r++) asm volatile("" : "+v"(x[r]));
-  double opa[4][R], opb[4][R];
-  // ---- forward: for every tail column q ascending:  x(i) -= L(i,q) * x(q)  for the tail rows i > q
-  if constexpr (FORWARD) {
-    RingBase tp = ring_base(T.fwd + FWD_FROM * 16 * 64 * 4);      // 16 groups of 4 columns per block, one u32x4 per lane and group
-    asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-    vm_ring_load_s<LOW, 0, 0>(tp, voff); vm_ring_load_s<LOW, 1, 1>(tp, voff); vm_ring_load_s<LOW, 2, 2>(tp, voff); vm_ring_load_s<LOW, 3, 3>(tp, voff);
-    vm_ring_load_s<LOW, 4, 4>(tp, voff); vm_ring_load_s<LOW, 5, 5>(tp, voff); vm_ring_load_s<LOW, 6, 6>(tp, voff); vm_ring_load_s<LOW, 7, 7>(tp, voff);
-    ring_advance(tp, kRingSlots * 1024);
-    MISTRA_TAIL_OPERANDS(opa, 0, 7)
-    vm_ring_load_s<LOW, 0, 0>(tp, voff);
-#pragma unroll
-    for (int rq = FWD_FROM; rq < FWD_END; rq++) {
-      for (int gb = 0; gb < 16; gb += kRingSlots) {
-#define MISTRA_TAIL_FWD(K, CUR, NXT)                                                    \
-        {                                                                               \
-          MISTRA_TAIL_OPERANDS(NXT, (K + 1) % kRingSlots, 7)                                 \
-          if constexpr (K + 1 == kRingSlots) ring_advance(tp, kRingSlots * 1024);            \
-          vm_ring_load_s<LOW, (K + 1) % kRingSlots, (K + 1) % kRingSlots>(tp, voff);         \
-          _Pragma("unroll") for (int c = 0; c < 4; c++) {                               \
-            const double xq = readlane_f64(x[rq], 4 * (gb + K) + c);                    \
-            _Pragma("unroll") for (int r = rq; r < R; r++) x[r] = __builtin_fma(-CUR[c][r], xq, x[r]); \
-          }                                                                             \
-          MISTRA_TAIL_PIN                                                               \
-        }
-        MISTRA_TAIL_FWD(0, opa, opb) MISTRA_TAIL_FWD(1, opb, opa) MISTRA_TAIL_FWD(2, opa, opb) MISTRA_TAIL_FWD(3, opb, opa)
-        MISTRA_TAIL_FWD(4, opa, opb) MISTRA_TAIL_FWD(5, opb, opa) MISTRA_TAIL_FWD(6, opa, opb) MISTRA_TAIL_FWD(7, opb, opa)
-#undef MISTRA_TAIL_FWD
-      }
-    }
-  }
-  // ---- backward, on the row-scaled triangle U' = D^-1 U that the LU program's last phase leaves in the tail block
-  //      (schedule.cpp: lu_entries): x = R .* x, then for every tail column q descending  x(i) -= U'(i,q) * x(q)  for the
-  //      tail rows i < q.  No quotient on the serial chain: per column it is readlane -> multiply -> subtract.
-  {
-    RingBase tp = ring_base(T.bwd);
-    asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-    vm_ring_load_s<LOW, 0, 0>(tp, voff); vm_ring_load_s<LOW, 1, 1>(tp, voff); vm_ring_load_s<LOW, 2, 2>(tp, voff); vm_ring_load_s<LOW, 3, 3>(tp, voff);
-    vm_ring_load_s<LOW, 4, 4>(tp, voff); vm_ring_load_s<LOW, 5, 5>(tp, voff); vm_ring_load_s<LOW, 6, 6>(tp, voff); vm_ring_load_s<LOW, 7, 7>(tp, voff);
-    ring_advance(tp, kRingSlots * 1024);
-    // R(k) = 1/U(k,k), published by the LU program: fetched here, under the table's first round trip (held through the forward
-    // chain it was the register that pushed this function into a callee-saved one, stored to scratch and reloaded on every call)
-#pragma unroll
-    for (int r = 0; r < R; r++) rd[r] = lds_ld(rb + 8 * (r * 64 + lane));
-#pragma unroll
-    for (int r = 0; r < R; r++) x[r] = x[r] * rd[r];
-    MISTRA_TAIL_OPERANDS(opa, 0, 7)
-    vm_ring_load_s<LOW, 0, 0>(tp, voff);
-#pragma unroll
-    for (int rq = R - 1; rq >= 0; rq--) {
-      for (int gb = 0; gb < 16; gb += kRingSlots) {
-#define MISTRA_TAIL_BWD(K, CUR, NXT)                                                    \
-        {                                                                               \
-          MISTRA_TAIL_OPERANDS(NXT, (K + 1) % kRingSlots, 7)                                 \
-          if constexpr (K + 1 == kRingSlots) ring_advance(tp, kRingSlots * 1024);            \
-          vm_ring_load_s<LOW, (K + 1) % kRingSlots, (K + 1) % kRingSlots>(tp, voff);         \
-          _Pragma("unroll") for (int c = 0; c < 4; c++) {                               \
-            const double xq = readlane_f64(x[rq], 63 - (4 * (gb + K) + c));             \
-            _Pragma("unroll") for (int r = 0; r <= rq; r++) x[r] = __builtin_fma(-CUR[c][r], xq, x[r]); \
-          }                                                                             \
-          MISTRA_TAIL_PIN                                                               \
-        }
-        MISTRA_TAIL_BWD(0, opa, opb) MISTRA_TAIL_BWD(1, opb, opa) MISTRA_TAIL_BWD(2, opa, opb) MISTRA_TAIL_BWD(3, opb, opa)
-        MISTRA_TAIL_BWD(4, opa, opb) MISTRA_TAIL_BWD(5, opb, opa) MISTRA_TAIL_BWD(6, opa, opb) MISTRA_TAIL_BWD(7, opb, opa)
-#undef MISTRA_TAIL_BWD
-      }
-    }
-  }
-#undef MISTRA_TAIL_OPERANDS
-#undef MISTRA_TAIL_PIN
-  asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
 #pragma unroll
   for (int r = 0; r < R; r++) lds_st(xb + 8 * (r * 64 + lane), x[r]);
 }
@@ -1238,21 +1023,15 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     const int s = q * NT + t;
     y[q] = s < NVAR ? G_(a.var_in)[(size_t)cell * NVAR + s] : 0.0;
   }
-  // (the register-starved kernels fetch them per use, like their factor words; MISTRA_RCT_RESIDENT_SLOTS of the RPT values per thread stay in
-  //  registers all the same: every value kept is one global re-read per Fun / Jac_SP less — the re-reads that miss the L2 are what is left
-  //  of aer's HBM-side excess)
-#ifndef MISTRA_RCT_RESIDENT_SLOTS
-#define MISTRA_RCT_RESIDENT_SLOTS 0
-#endif
-  constexpr bool RCT_PER_USE = MT::WAVES_PER_SIMD > MISTRA_RESIDENT_MAX_WPS || L::RCT_IN_LDS;
-  constexpr int RCT_KEEP = !RCT_PER_USE ? RPT : (MISTRA_RCT_RESIDENT_SLOTS < RPT ? MISTRA_RCT_RESIDENT_SLOTS : RPT);
-  auto load_rct = [&](bool opaque) {      // this thread's rate constants; opaque: the per-use fetch of the values that are not kept
+  // (the register-starved kernels fetch them per use, like their factor words)
+  constexpr bool RCT_PER_USE = MT::WAVES_PER_SIMD > kResidentMaxWps || L::RCT_IN_LDS;
+  auto load_rct = [&](bool opaque) {      // this thread's rate constants; opaque: the per-use fetch (RCT_PER_USE)
     const double* rc = a.rconst;
     if (opaque) asm volatile("" : "+s"(rc));
     int tt = t;
     if (opaque) asm volatile("" : "+v"(tt));      // (addresses derived where they are used: hoisted out of the step loop they are registers that spill)
 #pragma unroll
-    for (int q = opaque ? RCT_KEEP : 0; q < RPT; q++) {
+    for (int q = 0; q < RPT; q++) {
       const int r = q * NT + tt;
       if constexpr (L::RCT_IN_LDS) {      // (per use: out of the cell's copy in LDS, put there once, below)
         if (opaque) { rct[q] = r < NREACT ? lds_ld(8u * (uint32_t)(L::RCT + r)) : 0.0; continue; }
@@ -1274,7 +1053,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   // (two 16-bit positions per register)
   // RESIDENT: the kernel with 256 registers (tot) keeps these words for the whole call; the 128-register ones (aer, gas: four
   // waves per SIMD) fetch them where they are used — there they were spilled to scratch and came back from it one at a time.
-  constexpr bool RESIDENT = MT::WAVES_PER_SIMD <= MISTRA_RESIDENT_MAX_WPS;
+  constexpr bool RESIDENT = MT::WAVES_PER_SIMD <= kResidentMaxWps;
   uint32_t jpos[(JPT + 1) / 2], zpos[(ZPT + 1) / 2];
   auto load_pos = [&]() {
     const uint16_t* jp = a.jvs_pos;
@@ -1289,27 +1068,21 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       zpos[q] = (uint32_t)G_(zp)[(2 * q) * NT + t] | ((2 * q + 1 < ZPT ? (uint32_t)G_(zp)[(2 * q + 1) * NT + t] : (uint32_t)kPosNone) << 16);
   };
   if constexpr (RESIDENT) load_pos();
-  // factor words of the products this thread forms in Fun (one per owned reaction): static per mechanism, kept in registers
-  // for the whole integration.  The (up to three per reaction) words of Jac_SP's products are NOT: values that live across
-  // the calls of the step loop need callee-saved registers, there are not enough of those, and the compiler's answer was to
-  // spill nine of the twelve and reload them one at a time, each load's latency exposed.  jac() fetches them in one batch of
-  // coalesced loads instead (48 KB table, L2-resident; measured: the batch lands in ~380 cycles, Jac_SP's products went from
-  // 11 000 to 7 400 cycles per call, the kernel's scratch from 104 to 8 bytes per lane).
-  // (tot, round 4: with the four words resident the kernel was 3 registers over what it can keep across its calls — one of these words and an
-  //  LDS address went through scratch, reloaded right behind a barrier in every Fun, a memory round trip each; fetched per use they ride in
-  //  the batch of Jac_SP's words that fun_jac issues anyway, and the kernel has no scratch)
-#ifndef MISTRA_FFAC_RESIDENT
-#define MISTRA_FFAC_RESIDENT 0
-#endif
-  constexpr bool FFAC_RESIDENT = RESIDENT && MISTRA_FFAC_RESIDENT;
+  // factor words of the products this thread forms in Fun (one per owned reaction) and in Jac_SP (up to three per reaction): static
+  // per mechanism, and fetched PER USE, in one batch of coalesced loads.  Values that live across the calls of the step loop need
+  // callee-saved registers, there are not enough of those, and the compiler's answer was to spill nine of Jac_SP's twelve words and
+  // reload them one at a time, each load's latency exposed (48 KB table, L2-resident; measured: the batch lands in ~380 cycles,
+  // Jac_SP's products went from 11 000 to 7 400 cycles per call, the kernel's scratch from 104 to 8 bytes per lane).  Fun's words
+  // likewise: resident, even the 256-register kernel was 3 registers over what it can keep across its calls — one word and an LDS
+  // address went through scratch, reloaded right behind a barrier in every Fun, a memory round trip each; fetched per use they ride
+  // in the batch of Jac_SP's words that fun_jac issues anyway, and the kernel has no scratch.
   uint64_t ffac[RPT];
   auto load_ffac = [&]() {
     const uint64_t* ff = a.fun_fac;
-    if constexpr (!FFAC_RESIDENT) asm volatile("" : "+s"(ff));
+    asm volatile("" : "+s"(ff));      // opaque: loads through it are not hoisted out of the step loop (and spilled there)
 #pragma unroll
     for (int q = 0; q < RPT; q++) ffac[q] = G_(ff)[q * NT + t];
   };
-  if constexpr (FFAC_RESIDENT) load_ffac();
   if (t < NFIX) X[NVAR + t] = G_(a.fix)[(size_t)cell * NFIX + t];
   if (t < NCONST) X[NVAR + NFIX + t] = G_(a.consts)[t];
   if constexpr (MT::DENSE_ND > 0) {      // the dense tail block's row table stays in LDS for the whole call
@@ -1358,78 +1131,47 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   };
 
   // ---- Fun_x (gas.f:2043): X <- v; A(r) = RCT(r)*X*X*X; Vdot = signed sums of A
+  //      Jac_SP_x (gas.f:2656) on the V already in X: B products under their reaction, JVS sums into registers
+  //      The pieces first; the three evaluators below (fun, jac, fun_jac) are sequences of them, with the barriers between.
   static_assert(SPT <= 2 && JPT * NT <= NNZ, "output cells of the gather-sum machine: at most two species per thread, JVS sums inside Ghimj");
-  // Fun_x's sums land in the thread's own cells of XS: species t and, where a thread owns two (one wavefront per cell: NT = 64 < NVAR), t + NT.
-  // A thread whose second species does not exist parks that (empty) sum in the trash cell: the stride between a lane's outputs is per lane.
-  auto vdot_out = [&](int tt, uint32_t& addr, uint32_t& stride) {
-    constexpr uint32_t trash = 8u * (uint32_t)(NNZ + NVAR + 2);
-    addr = tt < NVAR ? 8u * (uint32_t)(NNZ + tt) : trash;
-    if constexpr (SPT == 1) stride = tt < NVAR ? 8u * (uint32_t)NT : 0u;
-    else stride = tt + NT < NVAR ? 8u * (uint32_t)NT : trash - addr;
-  };
-  auto fun = [&](const double (&v)[SPT], double (&out)[SPT]) {
-    if constexpr (!FFAC_RESIDENT) load_ffac();
-    if constexpr (RCT_PER_USE) load_rct(true);
+  auto store_x = [&](const double (&v)[SPT]) {
 #pragma unroll
     for (int q = 0; q < SPT; q++) {
       const int s = q * NT + t;
       if (s < NVAR) X[s] = v[q];
     }
-    lds_barrier();
-    {
-      // every factor read is issued before the first product is stored: X and the product array are one LDS object to the
-      // compiler, so a read behind a store stays behind it, and product by product each one waited out its own LDS round trip
-      double f0[RPT], f1[RPT], f2[RPT];
-      uint32_t slot[RPT];
+  };
+  auto a_products = [&]() {
+    // every factor read is issued before the first product is stored: X and the product array are one LDS object to the
+    // compiler, so a read behind a store stays behind it, and product by product each one waited out its own LDS round trip
+    double f0[RPT], f1[RPT], f2[RPT];
+    uint32_t slot[RPT];
 #pragma unroll
-      for (int q = 0; q < RPT; q++) {
-        uint64_t w = ffac[q];
-        asm volatile("" : "+v"(w));   // decode here: hoisted out of the step loop, the derived addresses only spill
-        f0[q] = X[w & 0xFFFFu];
-        f1[q] = X[(w >> 16) & 0xFFFFu];
-        f2[q] = X[(w >> 32) & 0xFFFFu];
-        slot[q] = (uint32_t)(w >> 48);
-      }
-#pragma unroll
-      for (int q = 0; q < RPT; q++) {
-        double p = rct[q] * f0[q];
-        p = p * f1[q];
-        p = p * f2[q];
-        AB[slot[q]] = p;            // a slot without a reaction (rct = 0) writes a spare cell: no branch
-      }
-    }
-    lds_barrier();
-    lap(15);
-    // sums land in this thread's own cells of XS (free here: the solves copy their result out before Fun runs again);
-    // a thread without a species parks its (empty) sum in the trash cell
-    {
-      int tt = t;
-      if constexpr (!RESIDENT) asm volatile("" : "+v"(tt));      // (derived here: kept across the step loop, the stride was one more register stored to scratch per step)
-      uint32_t oa, os;
-      vdot_out(tt, oa, os);
-      gsum_run<NT, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, lane, oa, os);
+    for (int q = 0; q < RPT; q++) {
+      uint64_t w = ffac[q];
+      asm volatile("" : "+v"(w));   // decode here: hoisted out of the step loop, the derived addresses only spill
+      f0[q] = X[w & 0xFFFFu];
+      f1[q] = X[(w >> 16) & 0xFFFFu];
+      f2[q] = X[(w >> 32) & 0xFFFFu];
+      slot[q] = (uint32_t)(w >> 48);
     }
 #pragma unroll
-    for (int q = 0; q < SPT; q++) {
-      const int s = q * NT + t;
-      out[q] = s < NVAR ? XS[s] : 0.0;
+    for (int q = 0; q < RPT; q++) {
+      double p = rct[q] * f0[q];
+      p = p * f1[q];
+      p = p * f2[q];
+      AB[slot[q]] = p;            // a slot without a reaction (rct = 0) writes a spare cell: no branch
     }
   };
-
-  // ---- Jac_SP_x (gas.f:2656) on the V already in X: B products under their reaction, JVS sums into registers
-  double jac0[JPT];
-  auto jac = [&]() {
-    uint64_t jfac[3 * RPT];
-    {
-      const uint64_t* jf = a.jac_fac;
-      asm volatile("" : "+s"(jf));      // opaque: loads through it are not hoisted out of the step loop (and spilled there)
+  auto load_jfac = [&](uint64_t (&jfac)[3 * RPT]) {
+    const uint64_t* jf = a.jac_fac;
+    asm volatile("" : "+s"(jf));      // opaque: loads through it are not hoisted out of the step loop (and spilled there)
 #pragma unroll
-      for (int q = 0; q < 3 * RPT; q++) jfac[q] = G_(jf)[q * NT + t];
-      if constexpr (RCT_PER_USE) load_rct(true);
-    }
-    lds_barrier();   // every lane is done reading AB as A
+    for (int q = 0; q < 3 * RPT; q++) jfac[q] = G_(jf)[q * NT + t];
+  };
+  auto b_products = [&](const uint64_t (&jfac)[3 * RPT]) {
 #pragma unroll
-    for (int q = 0; q < RPT; q++) {      // the three products under one reaction: nine factor reads in flight, then the stores (see fun)
+    for (int q = 0; q < RPT; q++) {      // the three products under one reaction: nine factor reads in flight, then the stores (see a_products)
       double f0[3], f1[3], f2[3];
 #pragma unroll
       for (int b = 0; b < 3; b++) {
@@ -1446,91 +1188,78 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         JBp[(uint32_t)(jfac[q * 3 + b] >> 48)] = p;         // unused product slots write a spare cell: no branch
       }
     }
-    lds_barrier();
-    lap(13);
-    // sums land in this thread's own cells of the Ghimj area (free here: ros_PrepareMatrix rebuilds it from jac0)
-    gsum_run<NT, MT::RING_LOW>(a.jvs, hdr.jvs_row0, hdr.jvs_rows, lane, 8u * (uint32_t)t, 8u * (uint32_t)NT);
-    lap(14);
-#pragma unroll
-    for (int q = 0; q < JPT; q++) jac0[q] = M[q * NT + t];
   };
-
-  // ---- the step's first Fun_x and its Jac_SP_x in one go (both read the same V): the A and the B products are formed in ONE phase — the
-  //      B products have an array of their own inside the Ghimj area — and the two gather-sum programs run back to back.  Two
-  //      barrier phases and one table-stream start-up fewer per step than fun() followed by jac(); operation order inside every
-  //      product and sum unchanged.
-  auto fun_jac = [&](const double (&v)[SPT], double (&out)[SPT]) {
-    uint64_t jfac[3 * RPT];
-    {
-      const uint64_t* jf = a.jac_fac;
-      asm volatile("" : "+s"(jf));      // opaque: loads through it are not hoisted out of the step loop (and spilled there)
-#pragma unroll
-      for (int q = 0; q < 3 * RPT; q++) jfac[q] = G_(jf)[q * NT + t];
-    }
-    if constexpr (!FFAC_RESIDENT) load_ffac();
-    if constexpr (RCT_PER_USE) load_rct(true);
-#pragma unroll
-    for (int q = 0; q < SPT; q++) {
-      const int s = q * NT + t;
-      if (s < NVAR) X[s] = v[q];
-    }
-    lds_barrier();   // X is complete; nobody reads the Ghimj area any more (the last solve's sweeps are behind the error norm's barriers)
-    {
-      double f0[RPT], f1[RPT], f2[RPT];
-      uint32_t slot[RPT];
-#pragma unroll
-      for (int q = 0; q < RPT; q++) {
-        uint64_t w = ffac[q];
-        asm volatile("" : "+v"(w));
-        f0[q] = X[w & 0xFFFFu];
-        f1[q] = X[(w >> 16) & 0xFFFFu];
-        f2[q] = X[(w >> 32) & 0xFFFFu];
-        slot[q] = (uint32_t)(w >> 48);
-      }
-#pragma unroll
-      for (int q = 0; q < RPT; q++) {
-        double p = rct[q] * f0[q];
-        p = p * f1[q];
-        p = p * f2[q];
-        AB[slot[q]] = p;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < RPT; q++) {
-      double f0[3], f1[3], f2[3];
-#pragma unroll
-      for (int b = 0; b < 3; b++) {
-        const uint64_t w = jfac[q * 3 + b];
-        f0[b] = X[w & 0xFFFFu];
-        f1[b] = X[(w >> 16) & 0xFFFFu];
-        f2[b] = X[(w >> 32) & 0xFFFFu];
-      }
-#pragma unroll
-      for (int b = 0; b < 3; b++) {
-        double p = rct[q] * f0[b];
-        p = p * f1[b];
-        p = p * f2[b];
-        JBp[(uint32_t)(jfac[q * 3 + b] >> 48)] = p;
-      }
-    }
-    lds_barrier();
-    lap(13);
-    {
-      int tt = t;
-      if constexpr (!RESIDENT) asm volatile("" : "+v"(tt));
-      uint32_t oa, os;
-      vdot_out(tt, oa, os);
-      gsum_run<NT, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, lane, oa, os);
-    }
-    gsum_run<NT, MT::RING_LOW>(a.jvs, hdr.jvs_row0, hdr.jvs_rows, lane, 8u * (uint32_t)t, 8u * (uint32_t)NT);      // (other cells, another source array: no barrier between)
-    lap(14);
+  // Fun_x's sums land in the thread's own cells of XS (free here: the solves copy their result out before Fun runs again): species t
+  // and, where a thread owns two (one wavefront per cell: NT = 64 < NVAR), t + NT.  A thread without a species, or whose second one
+  // does not exist, parks that (empty) sum in the trash cell: the stride between a lane's outputs is per lane.
+  auto vdot_sums = [&]() {
+    int tt = t;
+    if constexpr (!RESIDENT) asm volatile("" : "+v"(tt));      // (derived here: kept across the step loop, the stride was one more register stored to scratch per step)
+    constexpr uint32_t trash = 8u * (uint32_t)(NNZ + NVAR + 2);
+    const uint32_t addr = tt < NVAR ? 8u * (uint32_t)(NNZ + tt) : trash;
+    uint32_t stride;
+    if constexpr (SPT == 1) stride = tt < NVAR ? 8u * (uint32_t)NT : 0u;
+    else stride = tt + NT < NVAR ? 8u * (uint32_t)NT : trash - addr;
+    gsum_run<NT, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, lane, addr, stride);
+  };
+  auto read_vdot = [&](double (&out)[SPT]) {
 #pragma unroll
     for (int q = 0; q < SPT; q++) {
       const int s = q * NT + t;
       out[q] = s < NVAR ? XS[s] : 0.0;
     }
+  };
+  // Jac_SP_x's sums land in this thread's own cells of the Ghimj area (free here: ros_PrepareMatrix rebuilds it from jac0)
+  double jac0[JPT];
+  auto jvs_sums = [&]() { gsum_run<NT, MT::RING_LOW>(a.jvs, hdr.jvs_row0, hdr.jvs_rows, lane, 8u * (uint32_t)t, 8u * (uint32_t)NT); };
+  auto read_jvs = [&]() {
 #pragma unroll
     for (int q = 0; q < JPT; q++) jac0[q] = M[q * NT + t];
+  };
+
+  auto fun = [&](const double (&v)[SPT], double (&out)[SPT]) {
+    load_ffac();
+    if constexpr (RCT_PER_USE) load_rct(true);
+    store_x(v);
+    lds_barrier();
+    a_products();
+    lds_barrier();
+    lap(15);
+    vdot_sums();
+    read_vdot(out);
+  };
+  auto jac = [&]() {
+    uint64_t jfac[3 * RPT];
+    load_jfac(jfac);
+    if constexpr (RCT_PER_USE) load_rct(true);
+    lds_barrier();   // every lane is done reading AB as A
+    b_products(jfac);
+    lds_barrier();
+    lap(13);
+    jvs_sums();
+    lap(14);
+    read_jvs();
+  };
+  // The step's first Fun_x and its Jac_SP_x in one go (both read the same V): the A and the B products are formed in ONE phase — the
+  // B products have an array of their own inside the Ghimj area — and the two gather-sum programs run back to back.  Two
+  // barrier phases and one table-stream start-up fewer per step than fun() followed by jac(); operation order inside every
+  // product and sum unchanged.
+  auto fun_jac = [&](const double (&v)[SPT], double (&out)[SPT]) {
+    uint64_t jfac[3 * RPT];
+    load_jfac(jfac);
+    load_ffac();
+    if constexpr (RCT_PER_USE) load_rct(true);
+    store_x(v);
+    lds_barrier();   // X is complete; nobody reads the Ghimj area any more (the last solve's sweeps are behind the error norm's barriers)
+    a_products();
+    b_products(jfac);
+    lds_barrier();
+    lap(13);
+    vdot_sums();
+    jvs_sums();      // (other cells, another source array: no barrier between)
+    lap(14);
+    read_vdot(out);
+    read_jvs();
   };
 
   // ---- ros_PrepareMatrix_x (gas.f:1404), first half: Ghimj = -Jac0, diagonal += 1/(H*gamma).
@@ -1579,13 +1308,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   auto tail = [&](auto swept_tag) {
     constexpr bool SWEPT = decltype(swept_tag)::value;
     constexpr uint32_t xs_tail = 8u * (NNZ + NVAR - 64 * MT::TAIL_REGS), r_tail = 8u * (NNZ + NVAR + 4 + NVAR - 64 * MT::TAIL_REGS);
-#ifndef MISTRA_LOW_BLOCK_TAIL      // 1: the kernels with the low ring placement whose tail is ONE register (gas) run the block form too
-#define MISTRA_LOW_BLOCK_TAIL 1
-#endif
-    if constexpr (MT::RING_LOW && !(MISTRA_LOW_BLOCK_TAIL && MT::TAIL_REGS <= MISTRA_LOW_BLOCK_TAIL)) {
-      static_assert(MT::DENSE_ND == 0, "the column form has no dense-block variant");
-      tail_solve_columns<MT::TAIL_REGS, SWEPT ? MT::TAIL_REGS : 0, true>(a.tail, xs_tail, r_tail, lane);
-    } else if constexpr (MT::RING_LOW) {
+    static_assert(!MT::RING_LOW || (MT::TAIL_REGS == 1 && MT::DENSE_ND == 0),
+                  "the low ring placement runs the block form with one tail register only (tail_block: no room below v64 for two operand sets)");
+    if constexpr (MT::RING_LOW) {
       tail_solve<MT::TAIL_REGS, SWEPT ? 4 * MT::TAIL_REGS : 0, true>(a.tail, xs_tail, r_tail, lane);
     } else {
       tail_solve<MT::TAIL_REGS, !SWEPT ? 0 : MT::DENSE_ND ? 4 * (MT::TAIL_REGS - 1) : 4 * MT::TAIL_REGS, false>(a.tail, xs_tail, r_tail, lane);
@@ -1748,7 +1473,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
             if (nconsecutive <= 5) Hset(Hget() * 0.5);
             else { ierr = -8; break; }
           } else {
-            vm_run<NT, MT::VM_SLOTS>(a.lu, hdr.lu_row0, lane);
+            vm_run<NT, 4>(a.lu, hdr.lu_row0, lane);
             if constexpr (MT::SCALE_PASS) {      // else the scaling is the LU program's last round
               lap(3);
               scale_run<NT, MT::RING_LOW>(a.lu_scale, wave, lane);      // L(k,j) *= R(j); tail block: U(i,c) *= R(i)

@@ -29,9 +29,6 @@ namespace mistra {
 #ifndef MISTRA_AER_WPS
 #define MISTRA_AER_WPS 2
 #endif
-#ifndef MISTRA_AER_RING_LOW          // 1: look-ahead ring in v64.. (kernels held to 128 registers), 0: in v192.. (256 registers: the block-form tail chain)
-#define MISTRA_AER_RING_LOW 0
-#endif
 #ifndef MISTRA_AER_SCALE_PASS        // whether the schedule compiler gives the factorisation's scaling its own pass at this workgroup size (schedule.cpp: >= 16 cells per thread)
 #define MISTRA_AER_SCALE_PASS 1
 #endif
@@ -41,17 +38,15 @@ namespace mistra {
 #ifndef MISTRA_TOT_WPS
 #define MISTRA_TOT_WPS 2
 #endif
-#ifndef MISTRA_TOT_VM_SLOTS          // ring depth of the LDS VM executor (table rows in flight per lane): 4, 6 or 8 slots of 8 registers from v48 up
-#define MISTRA_TOT_VM_SLOTS 4        // (the kernels held to 128 registers have room for 4)
-#endif
-#ifndef MISTRA_RESIDENT_MAX_WPS      // kernels with more waves per SIMD than this fetch their static per-thread words where they are used (ros3_kernel.hip)
-#define MISTRA_RESIDENT_MAX_WPS 2
-#endif
 constexpr int kGasNT = MISTRA_GAS_NT, kAerNT = MISTRA_AER_NT, kTotNT = MISTRA_TOT_NT;
 
-struct GasTraits { static constexpr int NVAR = 102, NFIX = 3, NREACT = 331, NNZ = 1110, NB = 568, NCONST = 2, NJNZ = 945, TAIL_REGS = 1, MAX_TEMPS = 10, WAVES_PER_SIMD = MISTRA_GAS_WPS, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = true, SCALE_PASS = false, RCT_LDS = false; static constexpr int VM_SLOTS = 4; };
-struct AerTraits { static constexpr int NVAR = 257, NFIX = 5, NREACT = 979, NNZ = 6579, NB = 1598, NCONST = 2, NJNZ = 2831, TAIL_REGS = 2, MAX_TEMPS = 192, WAVES_PER_SIMD = MISTRA_AER_WPS, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = MISTRA_AER_RING_LOW, SCALE_PASS = MISTRA_AER_SCALE_PASS, RCT_LDS = true; static constexpr int VM_SLOTS = 4; };
-struct TotTraits { static constexpr int NVAR = 417, NFIX = 7, NREACT = 1627, NNZ = 13503, NB = 2628, NCONST = 2, NJNZ = 4709, TAIL_REGS = 2, MAX_TEMPS = 768, WAVES_PER_SIMD = MISTRA_TOT_WPS, DENSE_ND = MISTRA_TOT_DENSE ? 64 : 0, DENSE_KB = MISTRA_TOT_DENSE ? 14 : 0; static constexpr bool RING_LOW = false, SCALE_PASS = true, RCT_LDS = false; static constexpr int VM_SLOTS = MISTRA_TOT_VM_SLOTS; };
+struct GasTraits { static constexpr int NVAR = 102, NFIX = 3, NREACT = 331, NNZ = 1110, NB = 568, NCONST = 2, NJNZ = 945, TAIL_REGS = 1, MAX_TEMPS = 10, WAVES_PER_SIMD = MISTRA_GAS_WPS, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = true, SCALE_PASS = false, RCT_LDS = false; };
+struct AerTraits { static constexpr int NVAR = 257, NFIX = 5, NREACT = 979, NNZ = 6579, NB = 1598, NCONST = 2, NJNZ = 2831, TAIL_REGS = 2, MAX_TEMPS = 192, WAVES_PER_SIMD = MISTRA_AER_WPS, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = false, SCALE_PASS = MISTRA_AER_SCALE_PASS, RCT_LDS = true; };
+struct TotTraits { static constexpr int NVAR = 417, NFIX = 7, NREACT = 1627, NNZ = 13503, NB = 2628, NCONST = 2, NJNZ = 4709, TAIL_REGS = 2, MAX_TEMPS = 768, WAVES_PER_SIMD = MISTRA_TOT_WPS, DENSE_ND = MISTRA_TOT_DENSE ? 64 : 0, DENSE_KB = MISTRA_TOT_DENSE ? 14 : 0; static constexpr bool RING_LOW = false, SCALE_PASS = true, RCT_LDS = false; };
+// RING_LOW: placement of the table look-ahead ring (ros3_kernel.hip): v64.. in the kernel that runs more than two waves per SIMD
+// (gas; its tail chain is one register), v192.. in the 256-register ones.
+// Kernels with more waves per SIMD than this fetch their static per-thread words where they are used (ros3_kernel.hip)
+constexpr int kResidentMaxWps = 2;
 
 constexpr int round_up2(int x) { return (x + 1) & ~1; }
 // spare cells behind a product array (slots no reaction owns write there, one cell per lane of a wave — two lanes per cell in the one-wave

@@ -135,19 +135,20 @@ struct GsumProgram {
 
 // Triangular solves, tail part.  The last m rows of the LU pattern (the gas-phase block every other species couples
 // to) form a nearly dense triangle whose substitution is an inherently serial chain; it is run by ONE wave with the
-// tail of the solution vector in registers (lane l holds rows h+l, h+64+l), the pivot value passed lane-to-lane by
-// v_readlane, and only the matrix entries gathered from LDS through these per-column index tables:
-//   word (16 bit) for column q, lane l, register r  =  Ghimj slot of entry (row h+64r+l, column h+q), or the 0.0 cell
+// tail of the solution vector in registers (lane l holds rows h+l, h+64+l), the pivot value passed lane-to-lane in
+// 16-column blocks (ros3_kernel.hip: tail_solve), and only the matrix entries gathered from LDS through per-column tables:
+//   entry for column q, lane l, register r  =  Ghimj slot of entry (row h+64r+l, column h+q), or the 0.0 cell
 // Forward: x(i) -= L(i,q)*x(q), columns ascending, as the reference's sweep orders the terms of a row.  Backward: the
 // LU program leaves the tail block's upper triangle ROW-SCALED, U'(i,c) = U(i,c)*R(i), so that with x := R .* x the
 // chain is  x(i) -= U'(i,q)*x(q)  (columns descending) with no quotient between consecutive columns; the reference
 // computes (x(i) - sum U(i,c) x(c)) / U(i,i) — same terms, each carrying one more rounding.
 struct TailSolve {
   int m = 0, h = 0, regs = 0;                   // tail rows [h, h+m), m = 64*regs, regs in {1,2}
+  // host side (the emulator, tests/probe/tail_tables.cpp, and the source of the address tables below): 16-bit slots, two per word
   std::vector<uint32_t> fwd;                    // [((q/4)*64 + lane)*4 + q%4]  lo16: r=0, hi16: r=1; columns ascending
   std::vector<uint32_t> bwd;                    // same, columns DEscending: group g, word c  <->  q = m-1-(4g+c)
-  // the same words per register r < regs as LDS byte addresses (8 * cell: M starts at LDS address 0), one operand per word:
-  // the block-form chain (ros3_kernel.hip: tail_solve) gathers through them straight from its look-ahead ring, with no decode
+  // what the kernel reads: the same entries per register r < regs as LDS byte addresses (8 * cell: M starts at LDS address 0), one
+  // operand per word: the chain (ros3_kernel.hip: tail_solve) gathers through them straight from its look-ahead ring, with no decode
   std::vector<uint32_t> fwd_addr[2], bwd_addr[2];
 };
 

@@ -72,10 +72,29 @@ def test_lookahead_ring_registers_are_out_of_the_compilers_reach():
     generated gfx950 assembly).  Cross-compiles, no GPU needed."""
     from mistra_amd.build import ring_register_report
     rep = ring_register_report()          # raises if a function's own registers reach its ring
-    dev = {k: v for k, v in rep.items() if "gsum_run" in k or "tail_solve" in k or "scale_run" in k}      # (tail_solve and tail_solve_columns)
+    dev = {k: v for k, v in rep.items() if "gsum_run" in k or "tail_solve" in k or "scale_run" in k}      # (three gsum_run, five tail_solve, two scale_run)
     assert len(dev) >= 9, rep
     low = {k: v for k, v in dev.items() if "Lb1E" in k}
     assert low and max(low.values()) < 64, low      # (ring_register_report has raised already if not)
+
+
+def test_ring_register_table_matches_the_generated_gather_sum_stream():
+    """The look-ahead ring's sixteen slots are stated once in ros3_kernel.hip (MISTRA_RING_LO<K> / MISTRA_RING_HI<K>) and once in
+    tools/gen_gsum_asm.py (SLOTS), whose generated stream loads and clobbers the same registers: the two tables agree."""
+    import re
+    import sys
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    try:
+        import gen_gsum_asm
+    finally:
+        sys.path.pop(0)
+    text = open(os.path.join(REPO, "mistra_amd", "csrc", "ros3_kernel.hip")).read()
+    table = {(m.group(1), int(m.group(2))): [int(r) for r in m.group(3).split(",")]
+             for m in re.finditer(r"^#define MISTRA_RING_(LO|HI)(\d) ([\d, ]+)$", text, re.M)}
+    assert len(table) == 16, sorted(table)
+    for half, name in (("LO", "LOW"), ("HI", "HIGH")):
+        for k, first in enumerate(gen_gsum_asm.SLOTS[name]):
+            assert table[(half, k)] == [first, first + 1, first + 2, first + 3], (half, k)
 
 
 @pytest.mark.parametrize("tool", ["gen_vm_asm.py", "gen_gsum_asm.py", "gen_rates_shim.py"])

@@ -1,7 +1,7 @@
 """The tail chain's address tables (mistra_amd/csrc/schedule.hpp: TailSolve::fwd_addr / bwd_addr): one table per register and
-direction, the words of the 16-bit tables (two Ghimj cells per word, the form the emulator and tail_solve_columns read) as LDS
-byte addresses, 8 * cell, in the same group / lane / column layout — slack and absent operands on the 0.0 cell.  The block-form
-chain of ros3_kernel.hip gathers through them straight from its look-ahead ring."""
+direction, the words of the host-side 16-bit tables (two Ghimj cells per word, the form the emulator reads) as LDS
+byte addresses, 8 * cell, in the same group / lane / column layout — slack and absent operands on the 0.0 cell.  The tail
+chain of ros3_kernel.hip (tail_solve) gathers through them straight from its look-ahead ring."""
 import ctypes as C
 import os
 import shutil

@@ -15,8 +15,6 @@ for V in "$@"; do
   case $V in
     p*) DEF="-DMISTRA_DIAG_DENSE_PANELS=${V#p}";;
     stamps) DEF="-DMISTRA_DIAG_STAMPS";;
-    callervm) DEF="-DMISTRA_DIAG_CALLER_RUNS_VM -DMISTRA_DIAG_LATE_LOADS";;
-    stampslate) DEF="-DMISTRA_DIAG_STAMPS -DMISTRA_DIAG_LATE_LOADS";;
   esac
   hipcc --offload-arch=gfx950 $FLAGS $DEF -c mistra_amd/csrc/ros3_kernel.hip -o /tmp/ros3_diag_$V.o &&
   hipcc --offload-arch=gfx950 -shared -fPIC -o tools/diaglib/libdiag_$V.so /tmp/ros3_diag_$V.o mistra_amd/build/capi.o mistra_amd/build/schedule.o mistra_amd/build/mech_tables.o mistra_amd/build/rates.o mistra_amd/build/pack.o -ldl

@@ -27,6 +27,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "..", "mistra_amd", "csrc", "gsum_exec_asm.inc")
 
+# the kernel's copy of these blocks: the MISTRA_RING_LO<K> / MISTRA_RING_HI<K> table of ros3_kernel.hip (tests/test_capi.py compares them)
 SLOTS = {"LOW": [64, 68, 80, 84, 96, 100, 112, 116], "HIGH": [192, 196, 208, 212, 224, 228, 240, 244]}
 
 

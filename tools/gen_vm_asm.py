@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes mistra_amd/csrc/vm_exec_asm.inc: the gfx950 instruction stream of the LDS VM executor (ros3_kernel.hip: vm_run),
-one variant per ring depth, as C string literals.  The stream is regular but long (N ring slots x {main line, marked rows,
+one variant per record form, as C string literals.  The stream is regular but long (N = 4 ring slots x {main line, marked rows,
 end of round}); generating it keeps the slot arithmetic (register blocks, table offsets, wait counts) in ONE place.
 
     python tools/gen_vm_asm.py          (the output is committed; tests/test_capi.py checks that it is up to date)
@@ -27,10 +27,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "..", "mistra_amd", "csrc", "vm_exec_asm.inc")
 
 # ring slots: 8-register blocks that are CALLER-saved in the AMDGPU calling convention (v0-39, then every other block of
-# 8: 48-55, 64-71, ...), so the non-inlined executor has nothing to save; the kernels held to 128 registers stop at v103
-BLOCKS = {4: [48, 64, 80, 96], 6: [48, 64, 80, 96, 112, 128], 8: [48, 64, 80, 96, 112, 128, 144, 160]}
+# 8: 48-55, 64-71, ...), so the non-inlined executor has nothing to save; the kernels held to 128 registers stop at v103.
+# The kernel's copy of these blocks is MISTRA_VM_CLOBBER_N4, generated below: ros3_kernel.hip names them nowhere else.
+N = 4
+BLOCKS = [48, 64, 80, 96]
 # table address registers: one per pair of slots (13-bit signed immediate offsets reach 2 rows of 2048 bytes)
-BASES = ["%[va]", "%[vb]", "%[vc]", "%[vd]"]
+BASES = ["%[va]", "%[vb]"]
 
 RCP = """v_div_scale_f64 %[a1{P}], vcc, %[acc], %[acc], 1.0
 v_rcp_f64 %[r1{P}], %[a1{P}]
@@ -46,8 +48,8 @@ v_div_fmas_f64 %[a1{P}], %[a1{P}], %[r1{P}], %[a2{P}]
 v_div_fixup_f64 %[a1{P}], %[a1{P}], %[acc], 1.0"""      # the sequence hipcc emits for 1.0/x (IEEE)
 
 
-def variant(n, upr=2):
-    blk = BLOCKS[n]
+def variant(upr=2):
+    n, blk = N, BLOCKS
     L = []
     emit = L.append
 
@@ -198,9 +200,9 @@ def variant(n, upr=2):
 
 def render():
     out = ["// GENERATED by tools/gen_vm_asm.py — do not edit.  Instruction stream of the LDS VM executor (ros3_kernel.hip: vm_run).", ""]
-    for n, upr in ((4, 2), (6, 2), (8, 2), (4, 3)):
-        lines, clob = variant(n, upr)
-        tag = "N%d" % n if upr == 2 else "N%d_SWEEP" % n      # _SWEEP: records of three two-operand updates (schedule.hpp: VM_SWEEP_UPD_PER_REC)
+    for upr in (2, 3):
+        lines, clob = variant(upr)
+        tag = "N%d" % N if upr == 2 else "N%d_SWEEP" % N      # _SWEEP: records of three two-operand updates (schedule.hpp: VM_SWEEP_UPD_PER_REC)
         out.append("#define MISTRA_VM_ASM_%s \\" % tag)
         for i, ln in enumerate(lines):
             sep = "\\n" if ln.endswith(":") else "\\n\\t"
@@ -208,7 +210,7 @@ def render():
             out.append('  "%s%s"%s' % (ln, "" if last else sep, "" if last else " \\"))
         out.append("")
         if upr == 2:
-            out.append("#define MISTRA_VM_CLOBBER_N%d %s" % (n, clob))
+            out.append("#define MISTRA_VM_CLOBBER_N%d %s" % (N, clob))
         out.append("")
     return "\n".join(out)
 
