@@ -3,7 +3,8 @@
 !
 ! Linked with -Wl,--wrap=fast_k_mt_a_ / fast_k_mt_t_: liq_parm's calls (kpp.f90:617,637) land here.  For the calls selected by
 ! MISTRA_CAPTURE_KMT_SKIP_x / _EVERY_x / _MAX_x (x = a | t) and, inside them, up to MISTRA_CAPTURE_KMT_LAYERS layers with an active
-! bin (cm > 0), it records what the routine READS for that layer — the particle spectrum ff(:,:,k), cw(:,k), cm(:,k), freep(k),
+! bin (cm > 0) — or, with MISTRA_CAPTURE_KMT_DROPLET=1 | 2, up to that many layers whose droplet bin 3 is active (cm(3,k) > 0 | cm(3,k) > 0 and
+! cm(4,k) > 0: cloud layers, of which the default selection below the cloud takes none; a call without such a layer does not count) — it records what the routine READS for that layer — the particle spectrum ff(:,:,k), cw(:,k), cm(:,k), freep(k),
 ! alpha(:,k), vmean(:,k), t(k), p(k) (the terminal velocity's arguments), plus once per record rq, kw, ka, ifeed, nkc_l — and xkmt(:,:,k)
 ! and the LWC-weighted sedimentation velocity vt(:,k) of /kpp_vt/ before and after the real call, into MISTRA_CAPTURE_KMT_FILE.  No
 ! reference source is modified.
@@ -12,7 +13,7 @@
 !         t(k), p(k), vt_before(nkc), vt_after(nkc)
 module capture_kmt_state
   implicit none
-  integer :: unit_out = 0, nlayers = 4
+  integer :: unit_out = 0, nlayers = 4, droplet = 0
   logical :: inited = .false., opened = .false.
   integer :: ncall(2) = 0, nrec(2) = 0, nskip(2) = 0, nevery(2) = 1, nmax(2) = 4
 contains
@@ -28,6 +29,8 @@ contains
     end if
     call get_environment_variable('MISTRA_CAPTURE_KMT_LAYERS', buf, status=stat)
     if (stat == 0) read (buf, *) nlayers
+    call get_environment_variable('MISTRA_CAPTURE_KMT_DROPLET', buf, status=stat)
+    if (stat == 0) read (buf, *) droplet
     do m = 1, 2
        call get_environment_variable('MISTRA_CAPTURE_KMT_SKIP_'//sfx(m), buf, status=stat)
        if (stat == 0) read (buf, *) nskip(m)
@@ -47,6 +50,29 @@ contains
     want = opened .and. nrec(m) < nmax(m) .and. n >= nskip(m)
     if (want) want = mod(n - nskip(m), nevery(m)) == 0
   end function want
+  subroutine pick_layers(cm, nkc, n, nf, nsel, klist, taken)
+    ! the layers of one call that are recorded: with an active bin among 1:nsel, the first and every 13th spread over the column — or (droplet
+    ! mode) every layer whose bin 3 is active (droplet = 2: bins 3 and 4), from the lowest up
+    integer, intent(in) :: nkc, n, nf, nsel
+    double precision, intent(in) :: cm(nkc, n)
+    integer, intent(out) :: klist(64), taken
+    integer :: k
+    taken = 0
+    do k = 2, nf
+       if (taken >= min(nlayers, 64)) exit
+       if (droplet /= 0) then
+          if (nsel >= 2 + droplet .and. all(cm(3:min(2 + droplet, nkc), k) > 0.d0)) then
+             taken = taken + 1
+             klist(taken) = k
+          end if
+       else if (any(cm(1:nsel, k) > 0.d0)) then
+          if (taken == 0 .or. mod(k, 13) == 0) then
+             taken = taken + 1
+             klist(taken) = k
+          end if
+       end if
+    end do
+  end subroutine pick_layers
 end module capture_kmt_state
 
 subroutine wrap_fast_k_mt_a(freep, box, n_bl) bind(C, name="__wrap_fast_k_mt_a_")
@@ -81,14 +107,7 @@ subroutine wrap_fast_k_mt_a(freep, box, n_bl) bind(C, name="__wrap_fast_k_mt_a_"
   keep = want(1)
   taken = 0
   if (keep) then
-     do k = 2, nf      ! layers with an active bin, spread over the column
-        if (any(cm(1:nkc_l, k) > 0.d0) .and. taken < min(nlayers, 64)) then
-           if (taken == 0 .or. mod(k, 13) == 0) then
-              taken = taken + 1
-              klist(taken) = k
-           end if
-        end if
-     end do
+     call pick_layers(cm, nkc, n, nf, nkc_l, klist, taken)
      allocate (before(NSPEC, nkc, taken), vt_before(nkc, taken))
      do i = 1, taken
         before(:, :, i) = xkmt(:, :, klist(i))
@@ -140,14 +159,7 @@ subroutine wrap_fast_k_mt_t(freep, box, n_bl) bind(C, name="__wrap_fast_k_mt_t_"
   keep = want(2)
   taken = 0
   if (keep) then
-     do k = 2, nf
-        if (any(cm(1:nkc, k) > 0.d0) .and. taken < min(nlayers, 64)) then
-           if (taken == 0 .or. mod(k, 13) == 0) then
-              taken = taken + 1
-              klist(taken) = k
-           end if
-        end if
-     end do
+     call pick_layers(cm, nkc, n, nf, nkc, klist, taken)
      allocate (before(NSPEC, nkc, taken), vt_before(nkc, taken))
      do i = 1, taken
         before(:, :, i) = xkmt(:, :, klist(i))

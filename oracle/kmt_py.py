@@ -3,6 +3,7 @@
 (mistra_amd/mech/<mech>.kmt.json) and the formula on the CPU against layers captured from the running reference model
 (tests/golden/kmt_<mech>.npz, tests/test_pack.py); the device kernel is then checked against the same fixtures."""
 import json
+import math
 import os
 
 import numpy as np
@@ -17,7 +18,6 @@ def load(mech):
 
 def vterm(a, t, p):
     """str.f90:2793-2863, one rounding per operation, the PARAMETER constants folded left to right as the compiler does; a**3 = (a*a)*a"""
-    import math
     g, r0, rhow = 9.80665, 8.3144743 / 28.96546e-3, 1000.0
     b = (-.318657e+1, .992696e+0, -.153193e-2, -.987059e-3, -.578878e-3, +.855176e-4, -.327815e-5)
     c1, c3, c4 = 2.0 * g / 9.0, 1.26 * 6.6e-8 * 101325.0 / 293.15, 32.0 * g / 3.0

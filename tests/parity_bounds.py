@@ -163,3 +163,14 @@ def reject_case_inputs(name):
     g = load_golden(mech, suffix)
     c = list(cells)
     return mech, g["var_in"][c], g["fix"][c], g["rconst"][c], tin, tout
+
+
+# ---- F. the liq_parm kernels on the seeded cases of tests/liq_cases.py (tests/test_gpu_liq_synth.py), where a result passes through exp or log.
+# Spread: the worst relative movement of the restatement itself (oracle/liq_py.py, oracle/kmt_py.py, oracle/rates_py.py) over those cases when exp, log,
+# log10, pow and sqrt return the next double up, or down (liq_cases.MathShim), measured by
+# tests/test_liq_cases.py::test_bounds_of_the_synthetic_comparisons_follow_the_restatements_own_movement.  Bound = max(LIQ_SYNTH_FLOOR, 10 x spread).
+#   measured (CPU):  henry 5.94e-16  equil_co 5.89e-16  dry_rates (xeq, the gas routine's henry4) 4.30e-16  st_coeff 5.21e-16  vt 1.30e-15
+# (200-320 K, against the 281-288 K of the captured layers: the temperature laws' exponents grow to ~16 and with them the last place of exp's argument,
+# which this measure does not move — argument roundings are the same operations on both sides.)  vt: Beard's polynomial sits between a log and an exp.
+LIQ_SYNTH_FLOOR = 1e-14            # what tests/test_gpu_liq.py, tests/test_gpu_kmt.py (vt) and tests/test_gpu_rates.py (st_coeff) hold on the captured layers
+LIQ_SYNTH_RTOL = {"henry": LIQ_SYNTH_FLOOR, "equil_co": LIQ_SYNTH_FLOOR, "dry_rates": LIQ_SYNTH_FLOOR, "st_coeff": LIQ_SYNTH_FLOOR, "vt": 1.3e-14}

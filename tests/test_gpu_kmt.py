@@ -45,6 +45,13 @@ def test_mass_transfer_coefficients_on_the_device(mech):
     changed = int((g["xkmt_after"] != g["xkmt_before"]).sum())
     assert changed >= 100
     assert np.array_equal(got, g["xkmt_after"]), "xkmt differs from the reference's (max rel %.2e)" % np.nanmax(np.abs(got - g["xkmt_after"]) / (np.abs(g["xkmt_after"]) + 1e-300))
+    # the droplet bins (jt > kw(ia)): at least one captured cloud layer has both active, the reference rewrote their rows, and the device's are the same bits
+    cloud = (g["cm"][:, 2] > 0) & (g["cm"][:, 3] > 0) & (g["cw"][:, 2] > 0) & (g["cw"][:, 3] > 0)
+    assert cloud.any(), "no layer with both droplet bins active in the fixture"
+    import json
+    lex = np.array(json.load(open(os.path.join(REPO, "mistra_amd", "mech", mech + ".kmt.json")))["lex"]) - 1
+    assert (g["xkmt_after"][cloud][:, 2:4][:, :, lex] != g["xkmt_before"][cloud][:, 2:4][:, :, lex]).all()
+    assert np.array_equal(got[cloud][:, 2:4], g["xkmt_after"][cloud][:, 2:4])
     print("%s: xkmt of %d captured layers bit-identical (%d coefficients rewritten, bins active: %s)" % (mech, got.shape[0], changed, (g["cm"] > 0).sum(axis=0).tolist()))
     # gas has no such routine: the call fails loudly
     with pytest.raises(chem.MistraChemError):

@@ -61,12 +61,19 @@ def test_mass_transfer_coefficients_of_captured_layers(mech):
     tab = kmt_py.load(mech)
     g = np.load(os.path.join(REPO, "tests", "golden", "kmt_%s.npz" % mech))
     assert g["ff"].shape[0] >= 4
+    cloud = [i for i in range(g["ff"].shape[0]) if g["cm"][i, 2] > 0 and g["cm"][i, 3] > 0 and g["cw"][i, 2] > 0 and g["cw"][i, 3] > 0]
+    assert len(cloud) >= 1, "no layer with both droplet bins (jt > kw(ia)) active in the fixture"
+    lex = np.array(tab["lex"]) - 1
     rewritten = 0
-    for i in (0, g["ff"].shape[0] // 2, g["ff"].shape[0] - 1):      # (pure-Python loops: a few layers; the last one has a droplet bin active)
+    below = [i for i in range(g["ff"].shape[0]) if i not in cloud]
+    for i in [below[0], below[len(below) // 2], below[-1]] + cloud:      # (pure-Python loops: three layers below the cloud, where no droplet bin carries chemistry, and the cloud layers)
         got = kmt_py.fast_k_mt_layer(tab, g["ff"][i], g["rq"], g["kw"], int(g["ka"]), int(g["ifeed"]), int(g["nkc_l"]), g["cw"][i], g["cm"][i], float(g["freep"][i]),
                                      g["alpha"][i], g["vmean"][i], g["xkmt_before"][i])
         assert np.array_equal(got, g["xkmt_after"][i]), "xkmt of layer k=%d differs" % int(g["k"][i])
         rewritten += int((got != g["xkmt_before"][i]).sum())
+        if i in cloud:      # the droplet bins' rows: rewritten by the reference, and the restatement's are the same bits
+            for b in (2, 3):
+                assert (g["xkmt_after"][i, b, lex] != g["xkmt_before"][i, b, lex]).all() and np.array_equal(got[b], g["xkmt_after"][i, b])
     assert rewritten > 0
     # the LWC-weighted sedimentation velocity vt(kc,k) the same routine leaves in /kpp_vt/ for SR sedl ("whatever LWC": bins without
     # chemistry too), every captured layer, from a poisoned start: bit for bit (Stokes and Beard regimes; the host libm is the reference's)
