@@ -7,7 +7,7 @@
  * Semantics shared by the integrate calls (what the reference does for one cell, gas.f:710-773):
  *   input   VAR(NVAR), FIX(NFIX), RCONST(NREACT)   = COMMON /GDATA_x/  C(1:NVAR), C(NVAR+1:NSPEC), RCONST
  *                                                    (gas_Global.h:29-41 | aer_Global.h | tot_Global.h)
- *   options fixed as INTEGRATE_x fixes them: Ros3, RTOL 1e-3, ATOL 1e-25 (scalar), Hstart 1e-3 s, Hmin 0,
+ *   options as INTEGRATE_x fixes them unless mistra_chem_set_options has put others in force: Ros3, RTOL 1e-3, ATOL 1e-25 (scalar), Hstart 1e-3 s, Hmin 0,
  *           Hmax |TOUT-TIN|, FacMin 0.2, FacMax 6, FacRej 0.1, FacSafe 0.9, at most 100000 steps (gas.f:739-746, 950-1043)
  *   output  VAR after integrating from TIN to TOUT; ierr = 1 on success or the negative code of
  *           ros_ErrorMsg_x (gas.f:1474-1509: -6 too many steps, -7 step too small, -8 matrix repeatedly singular);
@@ -94,7 +94,7 @@ int mistra_chem_integrate_device_hstart(int mech, int ncell, const double* d_var
 /* Fortran-callable per-cell entry points with the reference's own signature, `SUBROUTINE INTEGRATE_x(TIN,TOUT)`
  * (REAL*8 by reference; data through COMMON /GDATA_x/).  `gdata` is the address of that COMMON block, laid out
  * C(NSPEC), RCONST(NREACT), TIME, DT, ATOL(NVAR), RTOL(NVAR), STEPMIN, STEPMAX (gas_Global.h:29-58).  On return VAR
- * is updated in place, *tin = exit time, STEPMIN = last step size, ATOL/RTOL are set as INTEGRATE_x sets them, and an
+ * is updated in place, *tin = exit time, STEPMIN = last step size, ATOL/RTOL are set as INTEGRATE_x sets them (or to the options in force), and an
  * unsuccessful integration prints the reference's message.  The ISO_C_BINDING shim in shim/ passes the COMMON block. */
 int mistra_chem_integrate_common(int mech, void* gdata, double* tin, double* tout);
 
@@ -105,6 +105,44 @@ int mistra_chem_integrate_common(int mech, void* gdata, double* tin, double* tou
  * may be NULL. */
 int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, double* tout, int32_t* ierr, double* t_err,
                                         double* h_err, int32_t* nsng);
+
+/* Rosenbrock_x's options (gas.f:777-1108 | aer.f | tot.f), one layer below INTEGRATE_x, which hard-codes seven of them (gas.f:739-746).  A
+ * model whose gas.f / aer.f / tot.f carry other values there calls mistra_chem_set_options once after init; every
+ * integrate path of that mechanism then uses them — mistra_chem_integrate(_ex, _env_ex, _device, _device_hstart),
+ * mistra_chem_integrate_common(_status), mistra_chem_drive(_begin, _device).  The arguments are Rosenbrock_x's own and are decoded
+ * as it decodes them (gas.f:936-1053):
+ *   ipar[20] = IPAR   [0] /= 0: autonomous, ros_FunTimeDerivative_x is not evaluated (one Fun count and the HG*dFdT terms less per step,
+ *                     gas.f:1221, 1268); [1] = 0: vector tolerances atol[NVAR], rtol[NVAR], anything else: atol[0], rtol[0] alone are read
+ *                     (and alone checked); [2] Max_no_steps, 0 = 100000, < 0: IERR -1; [3] the method, 0 = Ros4 (sic), outside 0..5:
+ *                     IERR -2; [10..17] are ignored (INTEGRATE_x zeroes them: the statistics start at 0).
+ *   rpar[20] = RPAR   [0] Hmin, 0 = 0; [1] Hmax = min(rpar[1], |Tend-Tstart|), 0 = |Tend-Tstart|; [2] Hstart = min(rpar[2],
+ *                     |Tend-Tstart|), 0 = max(Hmin, 1e-5) — each < 0: IERR -3; [3..6] FacMin, FacMax, FacRej, FacSafe, 0 = 0.2, 6, 0.1,
+ *                     0.9, < 0: IERR -4.
+ *   atol, rtol        AbsTol <= 0, RelTol <= 10 eps or RelTol >= 1 in an entry that is read: IERR -5.
+ * Only Ros3 (ipar[3] = 2) is built: the four other valid methods are refused by the library (non-zero return), which is not a code
+ * of Rosenbrock_x's.  One vector pair per call, shared by all cells, as in KPP.  A per-cell first step size of
+ * mistra_chem_integrate_device_hstart still goes before rpar[2]; ipar[2] /= 0 goes before mistra_chem_debug_set_max_steps.
+ *
+ * mistra_chem_check_options: the decode alone, pure host arithmetic, works before init.  *ierr = 1, or the IERR Rosenbrock_x would return
+ * (-1 .. -5; the call itself then still returns 0); a valid method that is not built: non-zero return, *ierr = 0.  For *ierr = 1,
+ * resolved_r[7] (may be NULL) = Hmin, Hmax, Hstart, FacMin, FacMax, FacRej, FacSafe as RosenbrockIntegrator_x receives them for a call over
+ * interval = |Tend-Tstart|, resolved_i[3] (may be NULL) = Max_no_steps, autonomous (0/1), vector tolerances (0/1). */
+int mistra_chem_check_options(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, double interval,
+                              int32_t* ierr, double* resolved_r, int32_t* resolved_i);
+
+/* Puts the options in force for `mech`, process-wide, on every device the library runs on, until they are replaced or cleared (ipar = NULL:
+ * back to INTEGRATE_x's values; the other pointers are then ignored), or mistra_chem_finalize is called; they outlive a re-initialisation.
+ * Options Rosenbrock_x would refuse (*ierr = its code, may be NULL) or whose method is not built (*ierr = 0) make the call fail and leave the
+ * previous ones in force.  While options are set the integrator runs in a kernel instantiation of its own — also where the values equal
+ * INTEGRATE_x's, with bit-identical results — and the diagnostic kernels, which keep INTEGRATE_x's values, fail (mistra_chem_debug_first_step).
+ * Fails while a column step of the mechanism is open (mistra_chem_drive_begin), like the other host-buffer calls.  Initialises the library like
+ * the Fortran entry points if nothing has. */
+int mistra_chem_set_options(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, int32_t* ierr);
+
+/* The options in force: *is_set = 0 (INTEGRATE_x's values, nothing else is written) or 1, then ipar[20], rpar[20] as they were given and
+ * atol[NVAR], rtol[NVAR] as the integrator uses them (scalar tolerances: entry 1 repeated); each of the four may be NULL.  These are also what
+ * mistra_chem_integrate_common(_status) leaves in ATOL / RTOL of COMMON /GDATA_x/ while options are set. */
+int mistra_chem_get_options(int mech, int32_t* is_set, int32_t* ipar, double* rpar, double* atol, double* rtol);
 
 /* The rows of the zero pivots a cell met: what KppDecomp_x returns in IER — the first row k whose diagonal is exactly zero when the
  * elimination reaches it (gas.f:6157) — and ros_PrepareMatrix_x prints once per failed decomposition ("Warning: LU Decomposition

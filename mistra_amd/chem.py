@@ -92,6 +92,10 @@ def lib():
         if hasattr(L, "mistra_chem_drive_begin"):
             L.mistra_chem_drive_begin.argtypes = L.mistra_chem_drive.argtypes
             L.mistra_chem_drive_end.argtypes = [C.c_int]
+        if hasattr(L, "mistra_chem_set_options"):
+            L.mistra_chem_check_options.argtypes = [C.c_int, _ip, _dp, _dp, _dp, C.c_double, _ip, _dp, _ip]
+            L.mistra_chem_set_options.argtypes = [C.c_int, _ip, _dp, _dp, _dp, _ip]
+            L.mistra_chem_get_options.argtypes = [C.c_int, _ip, _ip, _dp, _dp, _dp]
         L.mistra_chem_last_error.restype = C.c_char_p
         L.mistra_chem_describe.restype = C.c_char_p
         L.mistra_chem_describe.argtypes = [C.c_int]
@@ -258,6 +262,82 @@ def update_rconst(mech, env):
     out = np.empty((e.shape[0], nreact))
     _check(lib().mistra_chem_update_rconst(mid, e.shape[0], e.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
     return out
+
+
+# ---- Rosenbrock_x's options (include/mistra_chem.h: mistra_chem_set_options).  INTEGRATE_x's own: gas.f:739-746
+BASE_IPAR = (0, 1, 0, 2)           # IPAR(1:4): time dependent, scalar tolerances, 100000 steps, Ros3
+BASE_RPAR = (0.0, 0.0, 1.0e-3)     # RPAR(1:3): Hmin 0, Hmax the interval, Hstart 1e-3
+BASE_RTOL, BASE_ATOL = 1.0e-3, 1.0e-25
+Options = namedtuple("Options", "ipar rpar atol rtol")
+ResolvedOptions = namedtuple("ResolvedOptions", "ierr hmin hmax hstart facmin facmax facrej facsafe max_steps autonomous vector")
+
+
+def _option_args(name, ipar, rpar, atol, rtol):
+    """IPAR(20), RPAR(20), AbsTol(NVAR), RelTol(NVAR) from what the caller gave: None = INTEGRATE_x's value, a shorter ipar / rpar is padded
+    with zeros, a scalar tolerance fills the vector."""
+    nvar = DIMS[name][0]
+    ip, rp = np.zeros(20, np.int32), np.zeros(20, np.float64)
+    for out, given, base, what in ((ip, ipar, BASE_IPAR, "ipar"), (rp, rpar, BASE_RPAR, "rpar")):
+        v = np.atleast_1d(np.asarray(base if given is None else given))
+        if v.ndim != 1 or v.size > 20:
+            raise MistraChemError("%s: at most 20 entries, as Rosenbrock_x takes them" % what)
+        if what == "ipar" and not np.all(np.equal(np.mod(v, 1), 0)):
+            raise MistraChemError("ipar: integers expected")
+        out[:v.size] = v
+    tol = []
+    for given, base, what in ((atol, BASE_ATOL, "atol"), (rtol, BASE_RTOL, "rtol")):
+        v = np.asarray(base if given is None else given, np.float64)
+        if v.ndim == 0:
+            v = np.full(nvar, float(v))
+        if v.shape != (nvar,):
+            raise MistraChemError("%s: a scalar or %d entries (NVAR of %s) expected" % (what, nvar, name))
+        tol.append(np.ascontiguousarray(v))
+    return ip, rp, tol[0], tol[1]
+
+
+def check_options(mech, ipar=None, rpar=None, atol=None, rtol=None, interval=10.0):
+    """Rosenbrock_x's decode of its options (gas.f:936-1053) without a GPU -> ResolvedOptions: ierr = 1 or the IERR it would return (-1 .. -5, the
+    other fields are then None), else Hmin, Hmax, Hstart for a call over `interval`, the four factors, Max_no_steps, autonomous, vector.  A valid
+    method that is not built (anything but Ros3) raises."""
+    mid, name = _mech_id(mech)
+    ip, rp, at, rt = _option_args(name, ipar, rpar, atol, rtol)
+    ierr, r, i = C.c_int32(0), np.zeros(7), np.zeros(3, np.int32)
+    _check(lib().mistra_chem_check_options(mid, ip.ctypes.data_as(_ip), rp.ctypes.data_as(_dp), at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp),
+                                           float(interval), C.byref(ierr), r.ctypes.data_as(_dp), i.ctypes.data_as(_ip)))
+    if ierr.value != 1:
+        return ResolvedOptions(ierr.value, *([None] * 10))
+    return ResolvedOptions(1, *[float(x) for x in r], int(i[0]), bool(i[1]), bool(i[2]))
+
+
+def set_options(mech, ipar=None, rpar=None, atol=None, rtol=None):
+    """Rosenbrock_x's IPAR, RPAR, AbsTol, RelTol for every later integrate call of `mech` (mistra_chem_set_options), instead of the values
+    INTEGRATE_x hard-codes; None = INTEGRATE_x's value for that argument.  Options Rosenbrock_x would refuse, or a method that is not built, raise
+    and leave the previous ones in force."""
+    mid, name = _mech_id(mech)
+    ip, rp, at, rt = _option_args(name, ipar, rpar, atol, rtol)
+    if _inited_device is None:
+        init(0)
+    ierr = C.c_int32(0)
+    _check(lib().mistra_chem_set_options(mid, ip.ctypes.data_as(_ip), rp.ctypes.data_as(_dp), at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp),
+                                         C.byref(ierr)))
+
+
+def clear_options(mech):
+    """Back to INTEGRATE_x's values for `mech`."""
+    mid, _ = _mech_id(mech)
+    if _inited_device is None:
+        return
+    _check(lib().mistra_chem_set_options(mid, None, None, None, None, None))
+
+
+def get_options(mech):
+    """-> Options(ipar[20], rpar[20], atol[NVAR], rtol[NVAR]) in force for `mech` (the tolerances as the integrator uses them), or None."""
+    mid, name = _mech_id(mech)
+    nvar = DIMS[name][0]
+    is_set, ip, rp, at, rt = C.c_int32(0), np.zeros(20, np.int32), np.zeros(20), np.zeros(nvar), np.zeros(nvar)
+    _check(lib().mistra_chem_get_options(mid, C.byref(is_set), ip.ctypes.data_as(_ip), rp.ctypes.data_as(_dp), at.ctypes.data_as(_dp),
+                                         rt.ctypes.data_as(_dp)))
+    return Options(ip, rp, at, rt) if is_set.value else None
 
 
 def debug_set_max_steps(n=0):

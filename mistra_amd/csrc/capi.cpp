@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -500,6 +501,10 @@ struct MechState {
   StcBufs stc;
   VmeanBufs vmean;
   DevBuf<double> d_rct;      // scratch of mistra_chem_drive_device (grow-only)
+  // Rosenbrock_x's options on this slot (mistra_chem_set_options): the block the options kernel reads (kernel_args.hpp: RosOptSlot), null while
+  // none are set, and IPAR(3) (0: the library's Max_no_steps)
+  DevBuf<double> opt;
+  int opt_max_steps = 0;
   // staging of the batched host-buffer entries (grow-only)
   DevBuf<double> s_var, s_fix, s_rct, s_th, s_env;
   DevBuf<int32_t> s_ierr, s_stats, s_sing;
@@ -521,6 +526,7 @@ struct MechState {
   void release() {
     k.release(); rates.release(); pack.release(); kmt.release(); liq.release(); stc.release(); vmean.release();
     d_rct.release();
+    opt.release(); opt_max_steps = 0;
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
     sing_count = 0; sing_one = false;
     drive.release(); one.release();
@@ -547,6 +553,20 @@ std::mutex g_mu;
 bool g_inited = false;
 int g_max_steps = 100000;      // Max_no_steps (gas.f:1042); only mistra_chem_debug_set_max_steps changes it
 std::vector<DeviceState> g_devs;
+
+// ---- Rosenbrock_x's options (gas.f:777-1108 | aer.f | tot.f), which INTEGRATE_x fixes and mistra_chem_set_options opens: per mechanism,
+// process-wide.  They outlive a re-initialisation on other devices (setup_mech uploads them again); mistra_chem_finalize drops them.
+struct RosResolved {      // what Rosenbrock_x's decode (gas.f:936-1053) hands to RosenbrockIntegrator_x
+  double hmin = 0.0, hmax = 0.0, hstart = 0.0, facmin = 0.0, facmax = 0.0, facrej = 0.0, facsafe = 0.0;      // hmax: RPAR(2), +inf where it is 0
+  int max_steps = 0, autonomous = 0, vector = 0;
+};
+struct RosOptions {
+  bool set = false;
+  int32_t ipar[20] = {0};
+  double rpar[20] = {0.0};
+  RosResolved r;
+  std::vector<double> block;      // the device block: RosOptSlot scalars, then AbsTol(1:NVAR), RelTol(1:NVAR) as the integrator uses them
+} g_opts[3];
 
 // the host-buffer entries of the liq_parm kernels: one arena on the primary device (DevBlock below), and the caller ranges that
 // mistra_chem_pin_host registered, which those entries copy to and from directly
@@ -657,8 +677,69 @@ int setup_mech(DeviceState& D, int mech) {
     if (S.vmean.tab.nspec != nspec) return fail(name + ".vmean does not belong to this mechanism");
     if (int rc = S.vmean.upload()) return rc;
   }
+  if (g_opts[mech].set) {      // options set before this (re-)initialisation stay in force
+    HIP_TRY(S.opt.upload(g_opts[mech].block));
+    S.opt_max_steps = g_opts[mech].ipar[2];
+  }
   S.ready = true;
   return 0;
+}
+
+// text of ros_ErrorMsg_x (gas.f:1474-1509) for an error code
+const char* ros_error_text(int code) {
+  switch (code) {
+    case -1: return "--> Improper value for maximal no of steps";
+    case -2: return "--> Selected Rosenbrock method not implemented";
+    case -3: return "--> Hmin/Hmax/Hstart must be positive";
+    case -4: return "--> FacMin/FacMax/FacRej must be positive";
+    case -5: return "--> Improper tolerance values";
+    case -6: return "--> No of steps exceeds maximum bound";
+    case -7: return "--> Step size too small: T + 10*H = T or H < Roundoff";
+    case -8: return "--> Matrix is repeatedly singular";
+  }
+  return nullptr;
+}
+
+// Rosenbrock_x's decode of IPAR, RPAR and the tolerances, test by test in its order (gas.f:936-1053) -> 1, or the IERR it returns through
+// ros_ErrorMsg_x; *r is complete only for 1.  Pure host arithmetic.  atol / rtol: entry 1 alone is read unless IPAR(2) = 0.
+int resolve_options(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, RosResolved* r) {
+  r->autonomous = ipar[0] != 0;                                   // gas.f:937
+  r->vector = ipar[1] == 0;                                       // gas.f:941
+  if (ipar[2] == 0) r->max_steps = 100000;                        // gas.f:950
+  else if (ipar[2] > 0) r->max_steps = ipar[2];
+  else return -1;
+  if (ipar[3] < 0 || ipar[3] > 5) return -2;                      // gas.f:961 (0 selects Ros4)
+  if (rpar[0] == 0.0) r->hmin = 0.0;                              // gas.f:976
+  else if (rpar[0] > 0.0) r->hmin = rpar[0];
+  else return -3;
+  if (rpar[1] == 0.0) r->hmax = HUGE_VAL;                         // gas.f:986: ABS(Tend-Tstart), the call's
+  else if (rpar[1] > 0.0) r->hmax = rpar[1];
+  else return -3;
+  if (rpar[2] == 0.0) r->hstart = r->hmin > 1.0e-5 ? r->hmin : 1.0e-5;      // gas.f:996: MAX(Hmin, DeltaMin)
+  else if (rpar[2] > 0.0) r->hstart = rpar[2];
+  else return -3;
+  double* fac[4] = {&r->facmin, &r->facmax, &r->facrej, &r->facsafe};
+  const double fac_default[4] = {0.2, 6.0, 0.1, 0.9};
+  for (int i = 0; i < 4; i++) {                                   // gas.f:1006-1043
+    if (rpar[3 + i] == 0.0) *fac[i] = fac_default[i];
+    else if (rpar[3 + i] > 0.0) *fac[i] = rpar[3 + i];
+    else return -4;
+  }
+  const double roundoff = 2.220446049250313e-16;                  // epsilon(ONE), gas.f:973
+  const int uplim = r->vector ? kDims[mech].nvar : 1;
+  for (int i = 0; i < uplim; i++)                                 // gas.f:1045 (written so that a NaN passes, as it does there)
+    if (atol[i] <= 0.0 || rtol[i] <= 10.0 * roundoff || rtol[i] >= 1.0) return -5;
+  return 1;
+}
+
+std::string options_refusal(int mech, int ierr) {
+  return std::string("Rosenbrock_") + "gat"[mech] + " would refuse these options, IERR = " + std::to_string(ierr) + " " + ros_error_text(ierr);
+}
+int method_built(int mech, const int32_t* ipar) {
+  static const char* names[6] = {"Ros4 (IPAR(4) = 0 selects it)", "Ros2", "Ros3", "Ros4", "Rodas3", "Rodas4"};
+  if (ipar[3] == 2) return 0;
+  return fail(std::string("the ") + kMechName[mech] + " kernel is built for Ros3 (IPAR(4) = 2) only: " + names[ipar[3]] + " is a valid method of Rosenbrock_" +
+              "gat"[mech] + " that this library does not have");
 }
 
 int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream) {
@@ -675,7 +756,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   const KernelBufs& k = S.k;
   KernelArgs a;
   a.var_in = var_in; a.fix = fix; a.rconst = rconst; a.var_out = var_out; a.ierr = ierr; a.stats = stats;
-  a.texit_hexit = th; a.h_last = nullptr; a.hstart = nullptr; a.prof = nullptr; a.dump = nullptr; a.sing_rows = nullptr; a.n_temps = k.n_temps; a.max_steps = g_max_steps; a.tin = tin; a.tout = tout; a.ncell = ncell;
+  a.texit_hexit = th; a.h_last = nullptr; a.hstart = nullptr; a.prof = nullptr; a.dump = nullptr; a.sing_rows = nullptr; a.n_temps = k.n_temps; a.max_steps = S.opt_max_steps ? S.opt_max_steps : g_max_steps; a.tin = tin; a.tout = tout; a.ncell = ncell;
   a.consts = k.consts.p; a.fun_fac = k.fun_fac.p; a.jac_fac = k.jac_fac.p; a.jvs_pos = k.jvs_pos.p;
   a.zero_pos = k.zero_pos.p; a.diag_pos = k.diag_pos.p;
   a.vdot = k.vdot.dev(); a.jvs = k.jvs.dev(); a.lu = k.lu.dev();
@@ -687,6 +768,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.tail = TailDev{k.tail_fwd.p, k.tail_bwd.p, {k.tail_fwd_addr[0].p, k.tail_fwd_addr[1].p}, {k.tail_bwd_addr[0].p, k.tail_bwd_addr[1].p}};
   a.lu_scale = ScaleDev{k.lu_scale.p, k.lu_scale_slots, k.lu_scale_slots + VM_LOOKAHEAD_ROWS};
   a.dense = DenseDev{k.dense_rows.p, k.schur_cells.p};
+  a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
 
@@ -818,6 +900,7 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
   const bool profile = false;
 #endif
   if (profile) {
+    if (a.opt) return fail("the profiling kernel keeps INTEGRATE_x's values: clear the options (mistra_chem_set_options) first");
     HIP_TRY(prof.reserve(nc * kProfSlots));
     a.prof = prof.p;
   }
@@ -1014,6 +1097,7 @@ int mistra_chem_device_count(void) { return g_inited ? (int)g_devs.size() : 0; }
 
 void mistra_chem_finalize(void) {
   std::lock_guard<std::mutex> lock(g_mu);
+  for (auto& o : g_opts) o = RosOptions{};
   release_all();
 }
 
@@ -1528,6 +1612,96 @@ int mistra_chem_debug_set_max_steps(int max_steps) {
   return 0;
 }
 
+int mistra_chem_check_options(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, double interval,
+                              int32_t* ierr, double* resolved_r, int32_t* resolved_i) {
+  if (mech < 0 || mech > 2) return fail("unknown mechanism id");
+  if (!ipar || !rpar || !atol || !rtol || !ierr) return fail("null pointer");
+  *ierr = 0;
+  RosResolved r;
+  const int code = resolve_options(mech, ipar, rpar, atol, rtol, &r);
+  if (code == 1)
+    if (int rc = method_built(mech, ipar)) return rc;      // (*ierr stays 0: not a code of Rosenbrock_x's)
+  *ierr = code;
+  if (code != 1) return 0;
+  const double span = std::fabs(interval);
+  if (resolved_r) {
+    const double hmax = std::min(r.hmax, span);                             // gas.f:987-989
+    const double hstart = rpar[2] == 0.0 ? r.hstart : std::min(r.hstart, span);      // gas.f:997-999
+    const double v[7] = {r.hmin, hmax, hstart, r.facmin, r.facmax, r.facrej, r.facsafe};
+    std::memcpy(resolved_r, v, sizeof v);
+  }
+  if (resolved_i) { resolved_i[0] = r.max_steps; resolved_i[1] = r.autonomous; resolved_i[2] = r.vector; }
+  return 0;
+}
+
+int mistra_chem_set_options(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, int32_t* ierr) {
+  if (int rc = lazy_init()) return rc;
+  if (int rc = check_call(mech, 0)) return rc;
+  if (ierr) *ierr = 0;
+  if (ipar && (!rpar || !atol || !rtol)) return fail("null pointer");
+  std::lock_guard<std::mutex> lock(g_mu);
+  Slot t;
+  if (int rc = on_primary(mech, 0, true, &t)) return rc;      // (a column step in flight reads the block that would be freed here)
+  RosOptions next;
+  if (ipar) {
+    const int code = resolve_options(mech, ipar, rpar, atol, rtol, &next.r);
+    if (code != 1) {
+      if (ierr) *ierr = code;
+      return fail(options_refusal(mech, code));
+    }
+    if (int rc = method_built(mech, ipar)) return rc;
+    if (ierr) *ierr = 1;
+    next.set = true;
+    std::memcpy(next.ipar, ipar, sizeof next.ipar);
+    std::memcpy(next.rpar, rpar, sizeof next.rpar);
+    const size_t nv = (size_t)kDims[mech].nvar;
+    next.block.assign((size_t)kOptTol + 2 * nv, 0.0);
+    const RosResolved& r = next.r;
+    next.block[kOptHmin] = r.hmin; next.block[kOptHmax] = r.hmax; next.block[kOptHstart] = r.hstart;
+    next.block[kOptFacMin] = r.facmin; next.block[kOptFacMax] = r.facmax; next.block[kOptFacRej] = r.facrej; next.block[kOptFacSafe] = r.facsafe;
+    next.block[kOptAutonomous] = r.autonomous ? 1.0 : 0.0;
+    for (size_t i = 0; i < nv; i++) {      // scalar tolerances: AbsTol(1), RelTol(1) for every species (gas.f:1363); the other entries are not read
+      next.block[(size_t)kOptTol + i] = atol[r.vector ? i : 0];
+      next.block[(size_t)kOptTol + nv + i] = rtol[r.vector ? i : 0];
+    }
+  }
+  int rc = 0;
+  for (auto& D : g_devs) {      // every slot: the device-buffer entries run where their buffers live
+    MechState& S = D.mech[mech];
+    if (hipSetDevice(D.id) != hipSuccess) { rc = fail("hipSetDevice failed"); break; }
+    if (hipDeviceSynchronize() != hipSuccess) { rc = fail("hipDeviceSynchronize failed"); break; }      // (launches of the device-buffer entries that still read the old block)
+    S.opt.release();
+    S.opt_max_steps = 0;
+    if (next.set) {
+      if (hipError_t e = S.opt.upload(next.block)) { rc = fail(std::string("uploading the options: ") + hipGetErrorString(e)); break; }
+      S.opt_max_steps = next.ipar[2];
+    }
+  }
+  (void)hipSetDevice(g_devs[0].id);
+  if (rc) {      // a failed upload leaves no slot with options the others do not have
+    for (auto& D : g_devs) { D.mech[mech].opt.release(); D.mech[mech].opt_max_steps = 0; }
+    g_opts[mech] = RosOptions{};
+    return rc;
+  }
+  g_opts[mech] = next;
+  return 0;
+}
+
+int mistra_chem_get_options(int mech, int32_t* is_set, int32_t* ipar, double* rpar, double* atol, double* rtol) {
+  if (mech < 0 || mech > 2) return fail("unknown mechanism id");
+  if (!is_set) return fail("null pointer");
+  std::lock_guard<std::mutex> lock(g_mu);
+  const RosOptions& o = g_opts[mech];
+  *is_set = o.set ? 1 : 0;
+  if (!o.set) return 0;
+  const size_t nv = (size_t)kDims[mech].nvar;
+  if (ipar) std::memcpy(ipar, o.ipar, sizeof o.ipar);
+  if (rpar) std::memcpy(rpar, o.rpar, sizeof o.rpar);
+  if (atol) std::memcpy(atol, o.block.data() + kOptTol, nv * sizeof(double));
+  if (rtol) std::memcpy(rtol, o.block.data() + kOptTol + nv, nv * sizeof(double));
+  return 0;
+}
+
 int mistra_chem_debug_first_step(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                                  double tout, double* dump) {
   return mistra_chem_debug_first_step_ex(mech, ncell, var_in, fix, rconst, tin, tout, nullptr, dump, nullptr, nullptr, nullptr);
@@ -1542,6 +1716,7 @@ int mistra_chem_debug_first_step_ex(int mech, int ncell, const double* var_in, c
   Slot t;
   if (int rc = on_primary(mech, 0, true, &t)) return rc;
   MechState& S = *t.S;
+  if (S.opt.p) return fail("the first-step dump keeps INTEGRATE_x's values: clear the options (mistra_chem_set_options) first");
   const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact, nc = (size_t)ncell;
   const size_t per = 5 * nv + 2 * (size_t)kDims[mech].lu_nonzero + 2;
   DevBuf<double> d_dump, d_hstart;
@@ -1642,21 +1817,6 @@ static int integrate_host(int mech, int ncell, const double* var_in, const doubl
   return 0;
 }
 
-// text of ros_ErrorMsg_x (gas.f:1474-1509) for an error code
-static const char* ros_error_text(int code) {
-  switch (code) {
-    case -1: return "--> Improper value for maximal no of steps";
-    case -2: return "--> Selected Rosenbrock method not implemented";
-    case -3: return "--> Hmin/Hmax/Hstart must be positive";
-    case -4: return "--> FacMin/FacMax/FacRej must be positive";
-    case -5: return "--> Improper tolerance values";
-    case -6: return "--> No of steps exceeds maximum bound";
-    case -7: return "--> Step size too small: T + 10*H = T or H < Roundoff";
-    case -8: return "--> Matrix is repeatedly singular";
-  }
-  return nullptr;
-}
-
 int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, double* tout, int32_t* ierr_out, double* t_err,
                                         double* h_err, int32_t* nsng) {
   if (int rc = lazy_init()) return rc;
@@ -1675,6 +1835,10 @@ int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, doub
   Slot t;
   if (int rc = on_primary(mech, 0, true, &t)) return rc;
   MechState& S = *t.S;
+  if (g_opts[mech].set) {      // what the options in force make the integrator use instead
+    std::memcpy(atol, g_opts[mech].block.data() + kOptTol, (size_t)nv * sizeof(double));
+    std::memcpy(rtol, g_opts[mech].block.data() + kOptTol + nv, (size_t)nv * sizeof(double));
+  }
   const size_t d8 = sizeof(double), n_in = (size_t)(nv + nf + nr) * d8;
   Layout B;
   const size_t o_in = B.take(n_in);      // C | RCONST

@@ -38,6 +38,18 @@ struct DenseDev {              // dense tail block (schedule.hpp: DenseTail); nu
   const uint16_t* schur_cells; // [8 * DENSE_KB * 64]: operand cells of the Schur steps in MFMA lane order (schedule.hpp: DenseTail)
 };
 
+// Rosenbrock_x's options as the kernel's options instantiation (VARIANT 3) reads them: one block of doubles in device memory per
+// mechanism and device slot, resolved by the host (capi.cpp: resolve_options, after gas.f:936-1053).  What depends on the call's
+// interval is left to the kernel: Hmax = min(HMAX, |Tend-Tstart|), H = min(min(HSTART, |Tend-Tstart|), Hmax).
+enum RosOptSlot : int {
+  kOptHmin = 0,        // RPAR(1)
+  kOptHmax,            // RPAR(2); +inf where RPAR(2) = 0
+  kOptHstart,          // RPAR(3); max(Hmin, 1e-5) where RPAR(3) = 0
+  kOptFacMin, kOptFacMax, kOptFacRej, kOptFacSafe,      // RPAR(4:7), defaults filled in
+  kOptAutonomous,      // 1.0: IPAR(1) /= 0 (no ros_FunTimeDerivative_x: one Fun count and the HG*dFdT terms less per step); 0.0: time dependent
+  kOptTol              // AbsTol(1:NVAR) then RelTol(1:NVAR); scalar tolerances (IPAR(2) /= 0) arrive as entry 1 repeated
+};
+
 struct KernelArgs {
   // per-cell data, cell-major (one cell's VAR / FIX / RCONST contiguous, as COMMON /GDATA_x/ holds them)
   const double* var_in;        // [ncell][NVAR]
@@ -70,6 +82,7 @@ struct KernelArgs {
   ScaleDev lu_scale;
   TailDev tail;
   DenseDev dense;
+  const double* opt;           // [kOptTol + 2*NVAR] or null: Rosenbrock_x's options (RosOptSlot); set = the options instantiation runs (VARIANT 3)
 };
 
 }  // namespace mistra

@@ -975,10 +975,12 @@ __device__ __attribute__((noinline)) void dense_lu(int lane) {
 
 // VARIANT: 0 = the product kernel; 1 = phase timing (MISTRA_CHEM_PROFILE, capi.cpp); 2 = first-step dump: the intermediate
 // results of the FIRST attempt of the first step of every cell go to a.dump (layout: kernel_args.hpp), for the phase-level
-// parity tests (tests/test_gpu_parity.py); the integration itself is untouched.
+// parity tests (tests/test_gpu_parity.py); the integration itself is untouched.  3 = Rosenbrock_x's options (gas.f:936-1053) out of
+// a.opt instead of the values INTEGRATE_x fixes (kernel_args.hpp: RosOptSlot; capi.cpp: mistra_chem_set_options): every difference
+// from variant 0 sits behind `if constexpr (OPT)`, the other three compile from the statements they always had.
 template <class MT, int NT, int VARIANT>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
-  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2;
+  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, OPT = VARIANT == 3;
   constexpr int NVAR = MT::NVAR, NFIX = MT::NFIX, NREACT = MT::NREACT, NNZ = MT::NNZ, NCONST = MT::NCONST;
   constexpr int NW = NT / 64;
   constexpr int SPT = (NVAR + NT - 1) / NT, RPT = (NREACT + NT - 1) / NT;
@@ -1022,6 +1024,25 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   for (int q = 0; q < SPT; q++) {
     const int s = q * NT + t;
     y[q] = s < NVAR ? G_(a.var_in)[(size_t)cell * NVAR + s] : 0.0;
+  }
+  // VARIANT 3: AbsTol / RelTol of this thread's species, one vector pair per call shared by all cells as in KPP.  Fetched once, here:
+  // a global load in the middle of a step would wait behind the table streams.  The scalars of the block are fetched where the step
+  // control uses them (opt), not kept across the step loop.
+  [[maybe_unused]] double atol_r[SPT], rtol_r[SPT];
+  [[maybe_unused]] bool autonomous = false;
+  [[maybe_unused]] auto opt = [&](int slot) -> double {
+    const double* ob = a.opt;
+    asm volatile("" : "+s"(ob));      // opaque: the load stays where the value is used
+    return G_(ob)[slot];
+  };
+  if constexpr (OPT) {
+#pragma unroll
+    for (int q = 0; q < SPT; q++) {
+      const int s = q * NT + t;
+      atol_r[q] = s < NVAR ? G_(a.opt)[kOptTol + s] : 1.0;
+      rtol_r[q] = s < NVAR ? G_(a.opt)[kOptTol + NVAR + s] : 0.0;
+    }
+    autonomous = opt(kOptAutonomous) != 0.0;
   }
   // (the register-starved kernels fetch them per use, like their factor words)
   constexpr bool RCT_PER_USE = MT::WAVES_PER_SIMD > kResidentMaxWps || L::RCT_IN_LDS;
@@ -1354,7 +1375,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       const int s = q * NT + t;
       if (s < NVAR) {
         const double ymax = fmax_f(fabs(y0[q]), fabs(y1[q]));
-        const double scale = 1.0e-25 + 1.0e-3 * ymax;
+        double scale;
+        if constexpr (OPT) scale = atol_r[q] + rtol_r[q] * ymax;      // AbsTol(i) + RelTol(i)*Ymax (gas.f:1361)
+        else scale = 1.0e-25 + 1.0e-3 * ymax;
         const double e = ye[q] / scale;
         part = part + e * e;
       }
@@ -1377,11 +1400,21 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   const double Tstart = a.tin, Tend = a.tout;
   const double Roundoff = 2.220446049250313e-16, Hmin = 0.0, Hmax = wave_uniform(fabs(Tend - Tstart));
   const double FacMin = 0.2, FacMax = 6.0, FacRej = 0.1, FacSafe = 0.9;
+  // VARIANT 3: the same seven out of the options block, fetched where they are used
+  auto hmin = [&]() -> double { if constexpr (OPT) return opt(kOptHmin); else return Hmin; };
+  auto hmax = [&]() -> double { if constexpr (OPT) return fmin_f(opt(kOptHmax), Hmax); else return Hmax; };      // MIN(RPAR(2), ABS(Tend-Tstart)) (gas.f:989)
+  auto facmin = [&]() -> double { if constexpr (OPT) return opt(kOptFacMin); else return FacMin; };
+  auto facmax = [&]() -> double { if constexpr (OPT) return opt(kOptFacMax); else return FacMax; };
+  auto facrej = [&]() -> double { if constexpr (OPT) return opt(kOptFacRej); else return scalar_const(FacRej); };
+  auto facsafe = [&]() -> double { if constexpr (OPT) return opt(kOptFacSafe); else return FacSafe; };
   const double Direction = (Tend >= Tstart) ? 1.0 : -1.0;
   double T = Tstart;
   // Hstart: INTEGRATE_x fixes RPAR(3) = 1e-3 (gas.f:743).  Opt-in departure from the reference: a caller that keeps
   // each cell's last step size from one chemistry timestep to the next passes it in a.hstart; <= 0 means the reference's value.
-  const double hstart0 = (a.hstart && G_(a.hstart)[cell] > 0.0) ? G_(a.hstart)[cell] : 1.0e-3;
+  // VARIANT 3: RPAR(3) as resolved by the host (gas.f:996-999) in its place; a per-cell a.hstart > 0 still goes first.
+  double hstart_call = 1.0e-3;
+  if constexpr (OPT) hstart_call = opt(kOptHstart);
+  const double hstart0 = (a.hstart && G_(a.hstart)[cell] > 0.0) ? G_(a.hstart)[cell] : hstart_call;
   // The step size H lives across the whole step loop, and the compiler carried a vector-register copy of it (and of Hexit) around
   // the loop through scratch: 8-16 bytes per lane and step, stored through to HBM — most of aer's memory traffic in rounds 2 and 3.
   // So it lives in LDS: one cell per wave behind the error norm's partial sums, written by the wave's lane 0 and read back by the
@@ -1400,7 +1433,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   static_assert(NW <= L::RED_H && L::RED_H + NW <= L::RED_HEXIT, "red[]: partial sums | H per wave | Hexit");
   if (t == 0) *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT)) = 0.0;
   {
-    double H0 = fmin_f(fmin_f(hstart0, fabs(Tend - Tstart)), Hmax);
+    double H0 = fmin_f(fmin_f(hstart0, fabs(Tend - Tstart)), hmax());
     if (fabs(H0) <= 10.0 * Roundoff) H0 = 1.0e-5;
     Hset(H0);
   }
@@ -1435,7 +1468,8 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     }
     // ros_FunTimeDerivative_x (gas.f:1375): Fun_x does not depend on T and RCONST is frozen, so
     // dFdT = (1/Delta)*(Fun - Fcn0) is an exact +0.0; the evaluation is skipped, its count and its "+ HG*0.0" are kept.
-    nfun += 2;
+    if constexpr (OPT) nfun += autonomous ? 1 : 2;      // Autonomous: no ros_FunTimeDerivative_x, no Fun call of its own (gas.f:1221)
+    else nfun += 2;
     njac += 1;
     lap(1);
 
@@ -1444,7 +1478,10 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       {
         // K1's right-hand side, Fcn0 + HG*dFdT with dFdT = +0.0 (see above); independent of H
 #pragma unroll
-        for (int q = 0; q < SPT; q++) k1[q] = fcn0[q] + 0.0;
+        for (int q = 0; q < SPT; q++) {
+          if constexpr (OPT) k1[q] = autonomous ? fcn0[q] : fcn0[q] + 0.0;      // Autonomous: the HG*dFdT terms are not added at all (gas.f:1268)
+          else k1[q] = fcn0[q] + 0.0;
+        }
         int nconsecutive = 0;
         bool singular = true;
         while (singular) {
@@ -1514,7 +1551,10 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       {
         const double hc = wave_uniform(kRosC1 / dh);
 #pragma unroll
-        for (int q = 0; q < SPT; q++) k2[q] = (fcn[q] + hc * k1[q]) + dh * 0.0;      // + HG*dFdT with dFdT = +0.0: (dh*gamma2)*0.0, a zero of dh's sign (gamma2 > 0)
+        for (int q = 0; q < SPT; q++) {
+          if constexpr (OPT) k2[q] = autonomous ? fcn[q] + hc * k1[q] : (fcn[q] + hc * k1[q]) + dh * 0.0;
+          else k2[q] = (fcn[q] + hc * k1[q]) + dh * 0.0;      // + HG*dFdT with dFdT = +0.0: (dh*gamma2)*0.0, a zero of dh's sign (gamma2 > 0)
+        }
       }
       lap(6);
       solve(k2, false);
@@ -1524,7 +1564,10 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       {
         const double hc1 = wave_uniform(kRosC2 / dh), hc2 = wave_uniform(kRosC3 / dh);
 #pragma unroll
-        for (int q = 0; q < SPT; q++) k3[q] = ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;      // (dh*gamma3)*0.0 likewise (gamma3 > 0)
+        for (int q = 0; q < SPT; q++) {
+          if constexpr (OPT) k3[q] = autonomous ? (fcn[q] + hc1 * k1[q]) + hc2 * k2[q] : ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;
+          else k3[q] = ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;      // (dh*gamma3)*0.0 likewise (gamma3 > 0)
+        }
       }
       lap(6);
       solve(k3, false);
@@ -1546,23 +1589,23 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       double root;
       if constexpr (MT::WAVES_PER_SIMD > 2) root = err_root(Err);      // register-starved kernels: see err_root
       else root = pow(Err, 1.0 / kRosElo);
-      const double Fac = fmin_f(FacMax, fmax_f(FacMin, FacSafe / root));
+      const double Fac = fmin_f(facmax(), fmax_f(facmin(), facsafe() / root));
       const double H = Hget();
       double Hnew = H * Fac;
       nstp += 1;
-      if ((Err <= 1.0) || (H <= Hmin)) {
+      if ((Err <= 1.0) || (H <= hmin())) {
         nacc += 1;
 #pragma unroll
         for (int q = 0; q < SPT; q++) y[q] = ynew[q];
         T = wave_uniform(T + dh);
-        Hnew = fmax_f(Hmin, fmin_f(Hnew, Hmax));
+        Hnew = fmax_f(hmin(), fmin_f(Hnew, hmax()));
         if (RejectLastH) Hnew = fmin_f(Hnew, H);
         RejectLastH = false;
         RejectMoreH = false;
         Hset(Hnew);
         accepted = true;
       } else {
-        if (RejectMoreH) Hnew = H * scalar_const(FacRej);
+        if (RejectMoreH) Hnew = H * facrej();
         RejectMoreH = RejectLastH;
         RejectLastH = true;
         Hset(Hnew);
@@ -1607,8 +1650,10 @@ hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_config
   auto kern = ros3_integrate_kernel<MT, NT, 0>;
   auto kern_prof = ros3_integrate_kernel<MT, NT, 1>;      // MISTRA_CHEM_PROFILE diagnostics (capi.cpp)
   auto kern_dump = ros3_integrate_kernel<MT, NT, 2>;      // first-step dump (mistra_chem_debug_first_step)
+  auto kern_opt = ros3_integrate_kernel<MT, NT, 3>;       // Rosenbrock_x's options (mistra_chem_set_options); capi.cpp keeps a.dump and a.prof off while they are set
   if (!configured) {
-    for (const void* k : {reinterpret_cast<const void*>(kern), reinterpret_cast<const void*>(kern_prof), reinterpret_cast<const void*>(kern_dump)}) {
+    for (const void* k : {reinterpret_cast<const void*>(kern), reinterpret_cast<const void*>(kern_prof), reinterpret_cast<const void*>(kern_dump),
+                          reinterpret_cast<const void*>(kern_opt)}) {
       hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
       if (e != hipSuccess) return e;
     }
@@ -1617,6 +1662,7 @@ hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_config
   if (a.ncell <= 0) return hipSuccess;
   if (a.dump) hipLaunchKernelGGL(kern_dump, dim3((unsigned)a.ncell), dim3(NT), lds_bytes, stream, a);
   else if (a.prof) hipLaunchKernelGGL(kern_prof, dim3((unsigned)a.ncell), dim3(NT), lds_bytes, stream, a);
+  else if (a.opt) hipLaunchKernelGGL(kern_opt, dim3((unsigned)a.ncell), dim3(NT), lds_bytes, stream, a);
   else hipLaunchKernelGGL(kern, dim3((unsigned)a.ncell), dim3(NT), lds_bytes, stream, a);
   return hipGetLastError();
 }

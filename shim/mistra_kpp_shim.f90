@@ -14,6 +14,12 @@
 ! integration writes the lines of ros_ErrorMsg_x (gas.f:1474-1509) and of INTEGRATE_x (gas.f:764-767) to unit 6 and the
 ! model carries on; so does ros_PrepareMatrix_x's 'Warning: LU Decomposition returned ising =' line with the row of the zero
 ! pivot (gas.f:1456; the kernel records the rows, mistra_chem_singular_rows hands them out), once per failed decomposition.
+!
+! A model whose INTEGRATE_x carries other options than the generated ones (gas.f:739-746 edited: tolerances, step bounds, factors) hands them
+! over once, after which every call above uses them (include/mistra_chem.h: mistra_chem_set_options):
+!     SUBROUTINE MISTRA_SET_OPTIONS_g / _a / _t (IPAR, RPAR, ATOL, RTOL, IERR)      Rosenbrock_x's own IPAR(20), RPAR(20), AbsTol(NVAR), RelTol(NVAR)
+!     SUBROUTINE MISTRA_CLEAR_OPTIONS_g / _a / _t ()                                 back to INTEGRATE_x's values
+! IERR = 1, or the code Rosenbrock_x would return for them (gas.f:936-1053): its ros_ErrorMsg_x lines go to unit 6 and the previous options stay.
 module mistra_chem_c_api
   use iso_c_binding
   implicit none
@@ -57,6 +63,12 @@ module mistra_chem_c_api
        integer(c_int32_t) :: rows8(8)
        integer(c_int) :: rc
      end function mistra_chem_singular_rows
+     function mistra_chem_set_options(mech, ipar, rpar, atol, rtol, ierr) bind(C, name="mistra_chem_set_options") result(rc)
+       import :: c_int, c_ptr
+       integer(c_int), value :: mech
+       type(c_ptr), value :: ipar, rpar, atol, rtol, ierr      ! ipar = c_null_ptr clears
+       integer(c_int) :: rc
+     end function mistra_chem_set_options
      function mistra_chem_last_error() bind(C, name="mistra_chem_last_error") result(msg)
        import :: c_ptr
        type(c_ptr) :: msg
@@ -101,6 +113,15 @@ contains
        end do
     end if
     if (code >= 0) return
+    call mistra_chem_error_lines(sfx, code, t, h)
+    print *, 'Rosenbrock: Unsucessful step at T=', tin, ' (IERR=', code, ')'
+  end subroutine mistra_chem_report
+
+  ! ros_ErrorMsg_x (gas.f:1474-1509)
+  subroutine mistra_chem_error_lines(sfx, code, t, h)
+    character(len=1), intent(in) :: sfx
+    integer, intent(in) :: code
+    double precision, intent(in) :: t, h
     write (6, *) 'Forced exit from Rosenbrock_'//sfx//' due to the following error:'
     if (code == -1) then
        write (6, *) '--> Improper value for maximal no of steps'
@@ -124,8 +145,32 @@ contains
 102 format('       ', A, I4)
     write (6, 103) t, h
 103 format('        T=', E15.7, ' and H=', E15.7)
-    print *, 'Rosenbrock: Unsucessful step at T=', tin, ' (IERR=', code, ')'
-  end subroutine mistra_chem_report
+  end subroutine mistra_chem_error_lines
+
+  ! Rosenbrock_x's options for every later call of the mechanism.  A refusal of Rosenbrock_x's own (IERR -1 .. -5) writes the lines it would
+  ! write (ros_ErrorMsg_x is called with H = 0 there; T is the call's Tstart, which no call has given yet: 0) and leaves the previous options
+  ! in force; anything else the library refuses (a method other than Ros3) stops the program like every other failure.
+  subroutine set_options(mech, sfx, nvar, IPAR, RPAR, ATOL, RTOL, IERR)
+    integer, intent(in) :: mech, nvar
+    character(len=1), intent(in) :: sfx
+    integer(c_int32_t), target :: IPAR(20)
+    real(c_double), target :: RPAR(20), ATOL(nvar), RTOL(nvar)
+    integer :: IERR
+    integer(c_int32_t), target :: code
+    code = 0
+    if (mistra_chem_set_options(int(mech, c_int), c_loc(IPAR), c_loc(RPAR), c_loc(ATOL), c_loc(RTOL), c_loc(code)) /= 0) then
+       if (code >= 0) call mistra_chem_fail('MISTRA_SET_OPTIONS_'//sfx)
+       call mistra_chem_error_lines(sfx, int(code), 0.d0, 0.d0)
+    end if
+    IERR = code
+  end subroutine set_options
+
+  subroutine clear_options(mech, sfx)
+    integer, intent(in) :: mech
+    character(len=1), intent(in) :: sfx
+    if (mistra_chem_set_options(int(mech, c_int), c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr) /= 0) &
+         call mistra_chem_fail('MISTRA_CLEAR_OPTIONS_'//sfx)
+  end subroutine clear_options
 
   ! the three one-cell routines and the three batched ones differ in sizes only
   subroutine integrate_one(mech, sfx, gdata, TIN, TOUT)
@@ -304,3 +349,52 @@ subroutine INTEGRATE_BATCH_ENV_t(NCELL, VAR, FIX, ENV, TIN, TOUT, TEXIT, HEXIT, 
   integer(c_int32_t) :: IERR(*), ISTAT(8, *)
   call integrate_batch(2, 't', NCELL, VAR, FIX, ENV, TIN, TOUT, TEXIT, HEXIT, IERR, ISTAT, .true.)
 end subroutine INTEGRATE_BATCH_ENV_t
+
+! ---- Rosenbrock_x's options in place of the seven values INTEGRATE_x hard-codes (gas.f:739-746): call once after the edit, before the first step
+subroutine MISTRA_SET_OPTIONS_g(IPAR, RPAR, ATOL, RTOL, IERR)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer(c_int32_t) :: IPAR(20)
+  real(c_double) :: RPAR(20), ATOL(102), RTOL(102)
+  integer :: IERR
+  call set_options(0, 'g', 102, IPAR, RPAR, ATOL, RTOL, IERR)
+end subroutine MISTRA_SET_OPTIONS_g
+
+subroutine MISTRA_SET_OPTIONS_a(IPAR, RPAR, ATOL, RTOL, IERR)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer(c_int32_t) :: IPAR(20)
+  real(c_double) :: RPAR(20), ATOL(257), RTOL(257)
+  integer :: IERR
+  call set_options(1, 'a', 257, IPAR, RPAR, ATOL, RTOL, IERR)
+end subroutine MISTRA_SET_OPTIONS_a
+
+subroutine MISTRA_SET_OPTIONS_t(IPAR, RPAR, ATOL, RTOL, IERR)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer(c_int32_t) :: IPAR(20)
+  real(c_double) :: RPAR(20), ATOL(417), RTOL(417)
+  integer :: IERR
+  call set_options(2, 't', 417, IPAR, RPAR, ATOL, RTOL, IERR)
+end subroutine MISTRA_SET_OPTIONS_t
+
+subroutine MISTRA_CLEAR_OPTIONS_g()
+  use mistra_chem_c_api
+  implicit none
+  call clear_options(0, 'g')
+end subroutine MISTRA_CLEAR_OPTIONS_g
+
+subroutine MISTRA_CLEAR_OPTIONS_a()
+  use mistra_chem_c_api
+  implicit none
+  call clear_options(1, 'a')
+end subroutine MISTRA_CLEAR_OPTIONS_a
+
+subroutine MISTRA_CLEAR_OPTIONS_t()
+  use mistra_chem_c_api
+  implicit none
+  call clear_options(2, 't')
+end subroutine MISTRA_CLEAR_OPTIONS_t

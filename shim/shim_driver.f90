@@ -4,6 +4,9 @@
 !          shim_driver <G|A|T> <in.bin> <out.bin>      the same cells as ONE batched call, INTEGRATE_BATCH_x — the call a two-pass
 !                                                      kpp_driver makes per mechanism and 10-s step (INTEGRATION.md); out.bin then
 !                                                      ends with per cell IERR and the 8 statistics, and the call's wall time in ms
+!          shim_driver <OG|OA|OT> <in.bin> <out.bin>   the batched call under Rosenbrock_x's options: in.bin starts with IPAR(20), RPAR(20), ATOL(NVAR),
+!                                                      RTOL(NVAR) (float64), handed to MISTRA_SET_OPTIONS_x once, and goes on as for <G|A|T>; out.bin likewise,
+!                                                      with the IERR of MISTRA_SET_OPTIONS_x behind the wall time
 !          shim_driver <Eg|Ea|Et> <in.bin> <out.bin>   in.bin = ncell, then per cell VAR, FIX, ENV (the vector MISTRA_RATES_ENV_x packs,
 !                                                      mistra_kpp_rates.f90): UPDATE_RCONST_BATCH_x, then INTEGRATE_BATCH_ENV_x (rates and
 !                                                      integrator on the device, RCONST never crosses PCIe); out.bin = per cell VAR,
@@ -37,6 +40,13 @@ program shim_driver
   case ('A'); call run_batch(1, 257, 5, 979, trim(fin), trim(fout))
   case ('T'); call run_batch(2, 417, 7, 1627, trim(fin), trim(fout))
   case ('D'); call run_drive(trim(fin), trim(fout))
+  case ('O')
+     select case (a1(2:2))
+     case ('G'); call run_batch(0, 102, 3, 331, trim(fin), trim(fout), .true.)
+     case ('A'); call run_batch(1, 257, 5, 979, trim(fin), trim(fout), .true.)
+     case ('T'); call run_batch(2, 417, 7, 1627, trim(fin), trim(fout), .true.)
+     case default; stop 'mechanism must be G, A or T'
+     end select
   case ('K', 'H', 'Q', 'V', 'S', 'C', 'R')
      select case (a1(2:2))
      case ('g')
@@ -116,9 +126,13 @@ contains
     end do
     close (11); close (12)
   end subroutine run_t
-  subroutine run_batch(mech, NVAR, NFIX, NREACT, fin, fout)
+  subroutine run_batch(mech, NVAR, NFIX, NREACT, fin, fout, with_options)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT
     character(len=*), intent(in) :: fin, fout
+    logical, intent(in), optional :: with_options
+    double precision :: ropt(40)
+    double precision, allocatable :: ATOL(:), RTOL(:)
+    integer :: IPAR(20), ierr_opt
     double precision, allocatable :: VAR(:, :), VAR0(:, :), FIX(:, :), RCONST(:, :), TEXIT(:), HEXIT(:), rec(:)
     integer, allocatable :: IERR(:), ISTAT(:, :)
     double precision :: rn, tin, tout
@@ -126,6 +140,17 @@ contains
     integer(8) :: c0, c1, rate
     open (11, file=fin, access='stream', form='unformatted', status='old')
     open (12, file=fout, access='stream', form='unformatted', status='replace')
+    ierr_opt = 0
+    if (present(with_options)) then      ! what a model with an edited INTEGRATE_x does once after start-up
+       allocate (ATOL(NVAR), RTOL(NVAR))
+       read (11) ropt, ATOL, RTOL
+       IPAR = int(ropt(1:20))
+       select case (mech)
+       case (0); call MISTRA_SET_OPTIONS_g(IPAR, ropt(21:40), ATOL, RTOL, ierr_opt)
+       case (1); call MISTRA_SET_OPTIONS_a(IPAR, ropt(21:40), ATOL, RTOL, ierr_opt)
+       case (2); call MISTRA_SET_OPTIONS_t(IPAR, ropt(21:40), ATOL, RTOL, ierr_opt)
+       end select
+    end if
     read (11) rn
     n = int(rn)
     allocate (VAR(NVAR, n), VAR0(NVAR, n), FIX(NFIX, n), RCONST(NREACT, n), TEXIT(n), HEXIT(n), IERR(n), ISTAT(8, n), rec(NVAR + NFIX + NREACT))
@@ -154,6 +179,7 @@ contains
        write (12) dble(IERR(i)), dble(ISTAT(:, i))
     end do
     write (12) 1.d3 * dble(c1 - c0) / dble(rate)
+    if (present(with_options)) write (12) dble(ierr_opt)
     close (11); close (12)
   end subroutine run_batch
   subroutine run_env(mech, NVAR, NFIX, NREACT, NENV, fin, fout)
