@@ -714,6 +714,10 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) f64x4 lds_f64x4;
 __device__ __forceinline__ f64x4 lds_ld4(uint32_t addr) { return *(const lds_f64x4*)(uintptr_t)addr; }
 __device__ __forceinline__ void lds_st4(uint32_t addr, f64x4 v) { *(lds_f64x4*)(uintptr_t)addr = v; }
+// the same at an address that is a multiple of 16 only (two 16-byte accesses either way)
+typedef __attribute__((address_space(3))) __attribute__((aligned(16))) f64x4 lds_f64x4_a16;
+__device__ __forceinline__ f64x4 lds_ld4_a16(uint32_t addr) { return *(const lds_f64x4_a16*)(uintptr_t)addr; }
+__device__ __forceinline__ void lds_st4_a16(uint32_t addr, f64x4 v) { *(lds_f64x4_a16*)(uintptr_t)addr = v; }
 
 // Ghimj slot (LDS byte address) of column c of a row's column range, from the row's table entry {first, absent lo, absent hi}
 // (schedule.hpp: DenseTail); an absent entry reads as the 0.0 cell `zero`.
@@ -771,8 +775,9 @@ __device__ __forceinline__ void dense_store_panel(const int P, const int wave, c
 // During step 2 of the NEXT panel two otherwise idle waves store the finished L(i,j), U'(j,c) = U(j,c)*R(j), U(j,j), R(j)
 // to their Ghimj slots, for the solves (dense_store_panel)
 // The two panel buffers alternate, so that step 1 of the next panel can start while slower waves are still in step 3.
-// The sixteen panels run as a loop of two copies of eight (MISTRA_DENSE_UNROLL below; fully unrolled, the block's factorisation
-// was 39 KB of straight-line code executed once per decomposition, and instruction fetch, not arithmetic, set its pace); the tile
+// Panels 0 .. 11 run here (pivots 0 .. 47; the last sixteen pivots are dense_finish's), as a loop of copies of the body
+// (MISTRA_DENSE_UNROLL below; fully unrolled, sixteen panels were 39 KB of straight-line code executed once per decomposition, and
+// instruction fetch, not arithmetic, set its pace); the tile
 // registers a panel needs are picked with selects on wave-uniform conditions, which the compiler resolves where P's low bits are
 // compile-time constants of the copy.
 template <class MT, int NT>
@@ -849,7 +854,7 @@ __device__ __forceinline__ void dense_panel(f64x4& T0, f64x4& T1, const int P, c
   MISTRA_STAMP(tc)
   lds_barrier();
   MISTRA_STAMP(td)
-  if (I >= K2) {      // (nothing is left open after the last panels: K2 = 4)
+  if (I >= K2) {
     // rows and columns up to the panel's last pivot are finished: their operand is an exact zero, whatever the buffers hold there
     const double aop = (int)(16u * I + lcol) >= J0P + 4 ? -lds_ld(PL + 8u * ((16u * I + lcol) * 4u + lrow)) : 0.0;
     if (J0 >= K2) {
@@ -867,11 +872,124 @@ __device__ __forceinline__ void dense_panel(f64x4& T0, f64x4& T1, const int P, c
 #endif
 }
 
+// ---- the block's last 16 pivots, 48 .. 63: tile (3,3) factorised by its owner, wave 7, alone — no panel, no workgroup barrier.
+// As panels these four cost what any panel costs (~1.9 k cycles each: two barriers, two LDS hand-overs) for a matrix that
+// sits in one wave's registers.  Here: lane = row (lane & 15; the four 16-lane rows hold the same problem, so that
+// row_newbcast serves all of them and the stores can be shared out), the row's 16 columns in registers.  Per pivot j, ascending,
+// exactly dense_panel's operations per entry: R = 1/D(j,j); l(i) = D(i,j) * R; D(i,c) = fma(-l(i), D(j,c), D(i,c)) for i, c > j,
+// the pivot row's entry reaching its lane row inside the multiply-add (v_fmac_f64_dpp, as the tail chain's).
+// Which lanes take a pivot's update is EXEC's business, lanes >= j: a finished row must not take a "neutral" update with l = 0
+// (x + (+0.0) turns a stored -0.0 into +0.0), and DPP is not assumed to read a lane that EXEC has switched off — so the pivot's
+// own lane j stays on and multiplies with l = -0.0: its update is x + (-x)(-0.0), a zero of x's own sign added to x, which
+// leaves every finite x and both zeros bit for bit as they are.  Not an infinite x: inf + (-inf)(-0.0) is NaN, where the panels
+// left the pivot row's inf alone.  After such an overflow the stored U'(j,c) of that row differ from the panel form's (NaN for
+// inf); a factorisation holding either makes the solves' result non-finite, the error norm with it, and `Err <= 1` rejects the step.
+#define MISTRA_FIN_F(J, C) "v_fmac_f64_dpp %[x" #C "], -%[x" #C "], %[l] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+#define MISTRA_FIN_FROM_15(J) MISTRA_FIN_F(J, 15)
+#define MISTRA_FIN_FROM_14(J) MISTRA_FIN_F(J, 14) MISTRA_FIN_FROM_15(J)
+#define MISTRA_FIN_FROM_13(J) MISTRA_FIN_F(J, 13) MISTRA_FIN_FROM_14(J)
+#define MISTRA_FIN_FROM_12(J) MISTRA_FIN_F(J, 12) MISTRA_FIN_FROM_13(J)
+#define MISTRA_FIN_FROM_11(J) MISTRA_FIN_F(J, 11) MISTRA_FIN_FROM_12(J)
+#define MISTRA_FIN_FROM_10(J) MISTRA_FIN_F(J, 10) MISTRA_FIN_FROM_11(J)
+#define MISTRA_FIN_FROM_9(J) MISTRA_FIN_F(J, 9) MISTRA_FIN_FROM_10(J)
+#define MISTRA_FIN_FROM_8(J) MISTRA_FIN_F(J, 8) MISTRA_FIN_FROM_9(J)
+#define MISTRA_FIN_FROM_7(J) MISTRA_FIN_F(J, 7) MISTRA_FIN_FROM_8(J)
+#define MISTRA_FIN_FROM_6(J) MISTRA_FIN_F(J, 6) MISTRA_FIN_FROM_7(J)
+#define MISTRA_FIN_FROM_5(J) MISTRA_FIN_F(J, 5) MISTRA_FIN_FROM_6(J)
+#define MISTRA_FIN_FROM_4(J) MISTRA_FIN_F(J, 4) MISTRA_FIN_FROM_5(J)
+#define MISTRA_FIN_FROM_3(J) MISTRA_FIN_F(J, 3) MISTRA_FIN_FROM_4(J)
+#define MISTRA_FIN_FROM_2(J) MISTRA_FIN_F(J, 2) MISTRA_FIN_FROM_3(J)
+#define MISTRA_FIN_FROM_1(J) MISTRA_FIN_F(J, 1) MISTRA_FIN_FROM_2(J)
+#define MISTRA_FIN_XS [x0] "+v"(x0), [x1] "+v"(x1), [x2] "+v"(x2), [x3] "+v"(x3), [x4] "+v"(x4), [x5] "+v"(x5), [x6] "+v"(x6), [x7] "+v"(x7), \
+                      [x8] "+v"(x8), [x9] "+v"(x9), [x10] "+v"(x10), [x11] "+v"(x11), [x12] "+v"(x12), [x13] "+v"(x13), [x14] "+v"(x14), [x15] "+v"(x15)
+// pivot J (J1 = J + 1): the diagonal to every lane of its row (the wait states: the register was written two instructions back
+// at the latest); the IEEE division in C++, the same one dense_panel compiles to; then the multipliers for the lanes below J — into
+// the column's own register, which is where L(i, J) is stored from, and into l — and the update of the columns behind J.
+#define MISTRA_FIN_PIVOT(J, J1)                                                                                                       \
+  {                                                                                                                                   \
+    double dg, l;                                                                                                                     \
+    asm volatile("s_nop 1\n\tv_mov_b64_dpp %[dg], %[x] row_newbcast:" #J " row_mask:0xf bank_mask:0xf" : [dg] "=v"(dg) : [x] "v"(x##J));       \
+    const double R = 1.0 / dg;                                                                                                        \
+    constexpr uint32_t GE = ((0xffffu << J) & 0xffffu) * 0x10001u, GT = ((0xffffu << J1) & 0xffffu) * 0x10001u;                       \
+    asm volatile("v_mov_b64 %[l], %[nz]\n\t"                                                                                          \
+                 "s_mov_b32 exec_lo, %[gt]\n\ts_mov_b32 exec_hi, %[gt]\n\t"                                                           \
+                 "v_mul_f64 %[l], %[x" #J "], %[R]\n\t"                                                                               \
+                 "v_mul_f64 %[x" #J "], %[x" #J "], %[R]\n\t"                                                                         \
+                 "s_mov_b32 exec_lo, %[ge]\n\ts_mov_b32 exec_hi, %[ge]\n\t"                                                           \
+                 MISTRA_FIN_FROM_##J1(J)                                                                                              \
+                 "s_mov_b64 exec, -1"                                                                                                 \
+                 : [l] "=&v"(l), MISTRA_FIN_XS : [R] "v"(R), [nz] "v"(nz), [gt] "i"((int)GT), [ge] "i"((int)GE));                               \
+  }
+template <class MT, int NT>
+__device__ __attribute__((noinline)) void dense_finish(const f64x4 T, const int lane) {
+  constexpr uint32_t NNZ = MT::NNZ, NVAR = MT::NVAR, H = NVAR - 64, ZERO = 8u * (NNZ + NVAR);
+  constexpr uint32_t INFO = 8u * (uint32_t)LdsLayout<MT, NT>::DINFO, RDIAG = 8u * (NNZ + NVAR + 4u);
+  constexpr uint32_t BUF = 8u * (uint32_t)LdsLayout<MT, NT>::PANEL, STRIDE = 144u;      // the panel buffers' even half: panel 11 and its storers use the odd one; rows 16 bytes apart in the banks
+  const uint32_t lrow = (uint32_t)(lane >> 4), i = (uint32_t)(lane & 15);
+  MISTRA_STAMP(tf0)
+  // accumulator layout (lane l, element r = row (l>>4) + 4r, column l&15) -> lane = row: through LDS; one wave, in-order LDS
+#pragma unroll
+  for (int r = 0; r < 4; r++) lds_st(BUF + STRIDE * (lrow + 4u * r) + 8u * i, T[r]);
+  const f64x4 q0 = lds_ld4_a16(BUF + STRIDE * i), q1 = lds_ld4_a16(BUF + STRIDE * i + 32u), q2 = lds_ld4_a16(BUF + STRIDE * i + 64u), q3 = lds_ld4_a16(BUF + STRIDE * i + 96u);
+  double x0 = q0[0], x1 = q0[1], x2 = q0[2], x3 = q0[3], x4 = q1[0], x5 = q1[1], x6 = q1[2], x7 = q1[3];
+  double x8 = q2[0], x9 = q2[1], x10 = q2[2], x11 = q2[3], x12 = q3[0], x13 = q3[1], x14 = q3[2], x15 = q3[3];
+  // the lane's four slots: row 48 + i, columns 48 + 4 lrow .. + 3 (dense_slot for four columns in a row, all in the table's high word)
+  const u32x4 info = lds_ldu4(INFO + 16u * (48u + i));
+  const uint32_t cb = 16u + 4u * lrow;
+  uint32_t idx = info.x + 32u + cb - (uint32_t)__builtin_popcount(info.y) - (uint32_t)__builtin_popcount(info.z & ((1u << cb) - 1u));
+  uint32_t at[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t absent = (info.z >> (cb + (uint32_t)k)) & 1u;
+    at[k] = absent ? ZERO : 8u * idx;
+    idx += 1u - absent;
+  }
+  const double nz = -0.0;
+  MISTRA_FIN_PIVOT(0, 1) MISTRA_FIN_PIVOT(1, 2) MISTRA_FIN_PIVOT(2, 3) MISTRA_FIN_PIVOT(3, 4) MISTRA_FIN_PIVOT(4, 5)
+  MISTRA_FIN_PIVOT(5, 6) MISTRA_FIN_PIVOT(6, 7) MISTRA_FIN_PIVOT(7, 8) MISTRA_FIN_PIVOT(8, 9) MISTRA_FIN_PIVOT(9, 10)
+  MISTRA_FIN_PIVOT(10, 11) MISTRA_FIN_PIVOT(11, 12) MISTRA_FIN_PIVOT(12, 13) MISTRA_FIN_PIVOT(13, 14) MISTRA_FIN_PIVOT(14, 15)
+  MISTRA_STAMP(tf1)
+  // rows as they are finished — L(i,c) left of the diagonal, U(i,c) from it on — back through LDS, so that each of the four
+  // lanes of a row takes its four columns and the row's own diagonal without sixteen-way selects
+  lds_st4_a16(BUF + STRIDE * i, f64x4{x0, x1, x2, x3}); lds_st4_a16(BUF + STRIDE * i + 32u, f64x4{x4, x5, x6, x7});
+  lds_st4_a16(BUF + STRIDE * i + 64u, f64x4{x8, x9, x10, x11}); lds_st4_a16(BUF + STRIDE * i + 96u, f64x4{x12, x13, x14, x15});
+  const f64x4 v = lds_ld4_a16(BUF + STRIDE * i + 32u * lrow);
+  const double R = 1.0 / lds_ld(BUF + STRIDE * i + 8u * i);      // R(i) = 1/U(i,i): the pivot's own division again, in the row's lanes
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t c = 4u * lrow + (uint32_t)k;
+    if (at[k] != ZERO) lds_st(at[k], c > i ? v[k] * R : v[k]);      // U'(i,c) = U(i,c) * R(i); the diagonal and L(i,c) as they are
+  }
+  if (lrow == 0) lds_st(RDIAG + 8u * (H + 48u + i), R);
+  MISTRA_STAMP(tf2)
+#ifdef MISTRA_DIAG_STAMPS
+  if ((lane & 63) == 0) { atomicAdd(&g_dense_stamps[13], tf1 - tf0); atomicAdd(&g_dense_stamps[14], tf2 - tf1); }
+#endif
+}
+#undef MISTRA_FIN_PIVOT
+#undef MISTRA_FIN_XS
+#undef MISTRA_FIN_F
+#undef MISTRA_FIN_FROM_1
+#undef MISTRA_FIN_FROM_2
+#undef MISTRA_FIN_FROM_3
+#undef MISTRA_FIN_FROM_4
+#undef MISTRA_FIN_FROM_5
+#undef MISTRA_FIN_FROM_6
+#undef MISTRA_FIN_FROM_7
+#undef MISTRA_FIN_FROM_8
+#undef MISTRA_FIN_FROM_9
+#undef MISTRA_FIN_FROM_10
+#undef MISTRA_FIN_FROM_11
+#undef MISTRA_FIN_FROM_12
+#undef MISTRA_FIN_FROM_13
+#undef MISTRA_FIN_FROM_14
+#undef MISTRA_FIN_FROM_15
+
 // The dense tail block after the LU program and the scaling pass: Schur steps, then the block's own factorisation.  Every
 // Ghimj slot it touches is found by arithmetic on the row table in LDS: a global load issued here, in the middle of a cell's
 // step, waits behind the table streams of the whole chip (measured: 13 000 cycles in front of the first MFMA).
 template <class MT, int NT>
-__device__ __attribute__((noinline)) void dense_lu(int lane) {
+__device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
   static_assert(NT == 512 && MT::DENSE_ND == 64, "eight waves, two 16x16 tiles each");
   constexpr int KB = MT::DENSE_KB;
   constexpr uint32_t NNZ = MT::NNZ, NVAR = MT::NVAR, H = NVAR - 64, JM = H - 4 * KB, ZERO = 8u * (NNZ + NVAR);
@@ -946,12 +1064,15 @@ __device__ __attribute__((noinline)) void dense_lu(int lane) {
   MISTRA_STAMP(t2)
   MISTRA_STAMP_ADD(0, t1 - t0) MISTRA_STAMP_ADD(1, t2 - t1) MISTRA_STAMP_ADD(9, 1)
   // ---- the block's own factorisation
-#ifndef MISTRA_DENSE_UNROLL      // panels per copy of the loop body: with 8 the choices among tile registers (panel within its block column, odd / even
-#define MISTRA_DENSE_UNROLL 8      // block column) are made at compile time — 22 selects fewer per panel and wave; measured on one box: 1: 24 990, 2: 24 860, 4: 24 770,
-#endif                            // 8: 25 210 timesteps/s (16 = the whole loop unrolled was slower in round 2: instruction fetch)
-#ifndef MISTRA_DIAG_DENSE_PANELS      // timing diagnostics only (tools/diag_dense.sh): a library built with fewer panels computes garbage
-#define MISTRA_DIAG_DENSE_PANELS 16
+  // Twelve panels, pivots 0 .. 47; the last sixteen pivots are tile (3,3)'s alone and wave 7 finishes them by itself (dense_finish).
+#ifndef MISTRA_DENSE_UNROLL      // panels per copy of the loop body.  12 = all of them: every choice among tile registers (panel within its block column,
+#define MISTRA_DENSE_UNROLL 12     // odd / even block column) is made at compile time.  The same-box passes of 2, 3, 6, 8 (the compiler adds a copy of four
+#endif                            // for the remainder) and 12 are in profiles/r06_ab_dense_finish.txt; 4 makes the function save a register to scratch and
+                                  // was not measured.  (All 16 panels unrolled were slower than two copies of eight in round 2: instruction fetch.)
+#ifndef MISTRA_DIAG_DENSE_PANELS      // timing diagnostics only (tools/diag_dense.sh): a library built with fewer than 12 panels computes garbage
+#define MISTRA_DIAG_DENSE_PANELS 12
 #endif
+  static_assert(MISTRA_DIAG_DENSE_PANELS <= 12, "the panels end where the in-wave finish begins");
 #ifdef MISTRA_DIAG_STAMPS
   unsigned long long acc[5] = {0, 0, 0, 0, 0};
   MISTRA_STAMP(tp0)
@@ -963,12 +1084,16 @@ __device__ __attribute__((noinline)) void dense_lu(int lane) {
 #pragma unroll MISTRA_DENSE_UNROLL
   for (int P = 0; P < MISTRA_DIAG_DENSE_PANELS; P++) dense_panel<MT, NT>(T0, T1, P, wave, lane);
 #endif
-  if (dense_is_storer(wave)) dense_store_panel<MT, NT>(15, wave, lane);      // (behind the last panel's second barrier)
+  // behind panel 11's second barrier: its entries go to their Ghimj slots from the odd panel buffers, while wave 7 takes its tile
+  // to dense_finish (the caller's call: a call from here would make this function save registers of its own) and works in the even
+  // ones; everybody else goes on to the caller's barrier
+  if (dense_is_storer(wave)) dense_store_panel<MT, NT>(11, wave, lane);
 #ifdef MISTRA_DIAG_STAMPS
   lds_barrier();
   MISTRA_STAMP(tz)
   MISTRA_STAMP_ADD(11, tz - t0)
 #endif
+  return T1;
 }
 
 }  // namespace
@@ -1520,7 +1645,8 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
             if constexpr (MT::DENSE_ND > 0) {
               static_assert(MT::SCALE_PASS, "the Schur steps read what the scaling pass leaves");
               lap(3);
-              dense_lu<MT, NT>(lane);
+              const f64x4 tile = dense_lu<MT, NT>(lane);      // tile (3,3) of the block with pivots 0 .. 47 applied, in wave 7
+              if (wave == 7) dense_finish<MT, NT>(tile, lane);
               lds_barrier();
               lap(12);
             }

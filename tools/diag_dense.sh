@@ -1,7 +1,7 @@
 #!/bin/bash
 # Diagnostic builds of the library (results of a cut build are garbage; the timing is what is read):
-#   tools/diag_dense.sh pN      dense block's factorisation cut after N panels   -> tools/diaglib/libdiag_pN.so
-#   tools/diag_dense.sh stamps  cycle stamps inside dense_lu (tools/diag_dense_stamps.py reads them) -> libdiag_stamps.so
+#   tools/diag_dense.sh pN      dense block's panel loop cut after N <= 12 panels (the in-wave finish of the last 16 pivots still runs) -> tools/diaglib/libdiag_pN.so
+#   tools/diag_dense.sh stamps  cycle stamps inside dense_lu and dense_finish (tools/diag_dense_stamps.py reads them) -> libdiag_stamps.so
 cd "$(dirname "$0")/.."
 mkdir -p tools/diaglib
 FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math"
