@@ -67,12 +67,19 @@ def build_lib(force=False, verbose=False):
     return LIB
 
 
+# the non-inlined device functions of ros3_kernel.hip in which table loads are in flight in the look-ahead ring (their last template
+# argument is the ring's placement).  In gsum_run_pair a FILLED ring outlives compiler code: the statements between its two programs.
+RING_FUNCTIONS = ("gsum_run", "gsum_run_bar", "gsum_run_pair", "tail_solve", "scale_run")
+RING_HIGH_SLOTS = (192, 196, 208, 212, 224, 228, 240, 244)      # ros3_kernel.hip: MISTRA_RING_HI<K>
+
+
 def ring_register_report(isa_path=None):
     """Checks the one assumption the table look-ahead ring of ros3_kernel.hip rests on (see the comment there): in the
     non-inlined device functions, every register the COMPILER allocates — named outside inline asm, or chosen by it for an asm
     statement's result — stays below the ring's blocks (v192.. or, in the low placement, v64..), so a
     table load landing in the ring can never hit a compiler value.  Compiles the kernel source to gfx950 assembly and
-    scans it.  Returns {function: highest VGPR named outside inline asm}; raises if a ring-using function reaches its ring."""
+    scans it.  Returns {function: highest VGPR named outside inline asm}; raises if a ring-using function reaches its ring, and if
+    a function that is not one of RING_FUNCTIONS (nor an integrating kernel, which only calls them) loads into the ring at all."""
     import re
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
@@ -96,6 +103,9 @@ def ring_register_report(isa_path=None):
             elif in_asm and re.search(r"global_load_dwordx4 v\[(64|192):\d+\], v\[\d+:\d+\], off", l):
                 ring_users.add(name)         # the function issues ring loads (vm_ring_load) itself; (vm_run's own ring is
                                              # loaded and consumed inside ONE asm statement that lists it as clobbered)
+            elif in_asm and re.search(r"global_load_dwordx4 v\[(%s):\d+\]," % "|".join(map(str, RING_HIGH_SLOTS)), l):
+                ring_users.add(name)         # any load into the high placement, whatever its address form (the generated streams,
+                                             # the tail chain's scalar-base loads): nothing else lives up there
             elif "Folded Spill" in l or "Folded Reload" in l:
                 pass    # prologue / epilogue saves of callee-saved ring blocks: before the first ring load, after the drain
             elif not in_asm and not l.strip().startswith((";", ".")):
@@ -111,7 +121,7 @@ def ring_register_report(isa_path=None):
                     if m:
                         hi = max(hi, int(m.group(1) or m.group(3)))
         report[name] = hi
-        low = re.search(r"(gsum_run|tail_solve|scale_run)I.*Lb([01])E+[A-Z]", name)       # last template argument: ring placement LOW
+        low = re.search(r"\d(%s)I.*Lb([01])E+[A-Z]" % "|".join(RING_FUNCTIONS), name)       # last template argument: ring placement LOW
         if low:
             limit = 64 if low.group(2) == "1" else 192
             if hi >= limit:

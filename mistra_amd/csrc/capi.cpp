@@ -262,6 +262,10 @@ struct GsBufs {
   DevBuf<uint16_t> rows;
   hipError_t upload(const GsumProgram& P) {
     hipError_t e;
+    // whole ring turns per wave: gsum_run's loop counts in fours, and gsum_run_pair derives the next program's base from the count
+    static_assert(GS_ROW_ALIGN == 4, "ring turn of gsum_exec_asm.inc");
+    for (const auto r : P.rows)
+      if (r % GS_ROW_ALIGN != 0) return hipErrorInvalidValue;
     if ((e = wave_base.upload(P.wave_base)) != hipSuccess) return e;
     if ((e = rows.upload(P.rows)) != hipSuccess) return e;
     return recs.upload(P.recs);

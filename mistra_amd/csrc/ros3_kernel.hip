@@ -27,6 +27,24 @@ namespace {
 constexpr uint16_t kPosDiag = 0x8000, kPosNone = 0xFFFF;
 constexpr int kRingSlots = 8;  // 16-byte table loads in flight per lane (schedule.cpp appends 2x that many rows of slack)
 
+// ---- table-stream start-up: every table-driven executor call opened with a whole table round trip in which its
+// waves did nothing else.  The sites below move the ring fill in front of what the call waited for anyway, or take it over from
+// the stream in front; each has a compile-time switch (on in the product build; tools/build_variant.sh NAME -DMISTRA_STREAM_...=0
+// builds the library without one, for same-box A/B runs).  No table, record, operation or order of operations differs.
+// The low ring placement (gas) keeps the executors it had.  (Tried and taken out again: the tail chain's ring filled ahead)
+#ifndef MISTRA_STREAM_GSUM_BARRIER      // Fun / Jac sums: ring fill in front of the barrier behind the products (gsum_run_bar)
+#define MISTRA_STREAM_GSUM_BARRIER 1
+#endif
+#ifndef MISTRA_STREAM_GSUM_CHAIN        // fun_jac: the JVS program enters on rows the Vdot program fetched in its last ring turn (gsum_run_pair)
+#define MISTRA_STREAM_GSUM_CHAIN 1
+#endif
+#ifndef MISTRA_STREAM_SWEEP_BARRIER     // head sweeps of the solves: ring fill in front of the barrier they follow (vm_run<.., true>)
+#define MISTRA_STREAM_SWEEP_BARRIER 1
+#endif
+#ifndef MISTRA_STREAM_SCALE_TRIM        // scale_run: the last ring turn issues no refills (they fetched rows nobody reads, drained on the spot)
+#define MISTRA_STREAM_SCALE_TRIM 1
+#endif
+
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // plain vector types load from any address space
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -258,9 +276,12 @@ static_assert(kRingSlots == 8, "the ring table above has 8 slots per placement")
 #include "vm_exec_asm.inc"
 
 // UPR: updates per record — 2: (a, r, u) triples, the LU program; 3: (a, u) pairs, the triangular sweeps (schedule.hpp)
-template <int NT, int SLOTS, int UPR = 2>
+// BARRIER: the call stands in place of lds_barrier() + vm_run(): the barrier sits between the ring fill and the first counted wait
+// (table loads do not depend on LDS, the first record's gathers stay behind the barrier)
+template <int NT, int SLOTS, int UPR = 2, bool BARRIER = false>
 __device__ __attribute__((noinline)) void vm_run(const VmDev P, uint32_t row0, int lane) {
   static_assert(SLOTS == 4 && (UPR == 2 || UPR == 3), "ring depth and executor variants vm_exec_asm.inc is generated for");
+  static_assert(!BARRIER || UPR == 3, "the barrier form is generated for the sweep programs");
   const uint64_t recs = reinterpret_cast<uint64_t>(P.recs);      // the same in every lane: move it to SGPRs
   const uint64_t base = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)recs) |
                         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(recs >> 32)) << 32);
@@ -277,7 +298,9 @@ __device__ __attribute__((noinline)) void vm_run(const VmDev P, uint32_t row0, i
       [r1B] "=&v"(r1B), [u1B] "=&v"(u1B), [a2B] "=&v"(a2B), [r2B] "=&v"(r2B), [u2B] "=&v"(u2B), [sc] "=&v"(sc), [tg] "=&v"(tg), [ax] "=&v"(ax),          \
       [t] "=&v"(t), [flA] "=&s"(flA), [flB] "=&s"(flB), [tmp] "=&s"(tmp), [sv] "=&s"(sv), [sm] "=&s"(sm), [rounds] "+s"(rounds), [va] "+v"(va),         \
       [vb] "+v"(vb)
-  if constexpr (UPR == 3) {
+  if constexpr (BARRIER) {
+    asm volatile(MISTRA_VM_ASM_N4_SWEEP_BAR : MISTRA_VM_OPERANDS : [base] "s"(base) : "memory", "vcc", "scc", MISTRA_VM_CLOBBER_N4);
+  } else if constexpr (UPR == 3) {
     asm volatile(MISTRA_VM_ASM_N4_SWEEP : MISTRA_VM_OPERANDS : [base] "s"(base) : "memory", "vcc", "scc", MISTRA_VM_CLOBBER_N4);
   } else {
     asm volatile(MISTRA_VM_ASM_N4 : MISTRA_VM_OPERANDS : [base] "s"(base) : "memory", "vcc", "scc", MISTRA_VM_CLOBBER_N4);
@@ -638,6 +661,12 @@ __device__ __attribute__((noinline)) void tail_solve(const TailDev T, uint32_t x
 //      LDS (out_addr, then every out_stride bytes) — the caller reads its own cells back, no barrier needed.
 //      The instruction stream is generated (tools/gen_gsum_asm.py -> gsum_exec_asm.inc: why, and the pipeline, are described there).
 #include "gsum_exec_asm.inc"
+// the wave's first row of program P (2 KiB per row), in scalar registers
+__device__ __forceinline__ uint64_t gsum_base(const GsDev P, uint32_t row0) {
+  const uint64_t recs = reinterpret_cast<uint64_t>(P.recs) + (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)row0) * 2048u;
+  return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)recs) |
+         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(recs >> 32)) << 32);
+}
 template <int NT, bool LOW>
 __device__ __attribute__((noinline)) void gsum_run(const GsDev P, uint32_t row0, int rows, int lane, uint32_t out_addr, uint32_t out_stride) {
   // row0, rows: P.wave_base[wave] and P.rows[wave], fetched by the kernel when it started (see vm_run)
@@ -659,7 +688,59 @@ __device__ __attribute__((noinline)) void gsum_run(const GsDev P, uint32_t row0,
       : [b0] "s"(b0), [b1] "s"(b1), [stride] "v"(out_stride), [mzero] "v"(mzero)
   if constexpr (LOW) asm volatile(MISTRA_GSUM_ASM_LOW : MISTRA_GSUM_OPERANDS : "memory", "scc", MISTRA_GSUM_CLOBBER_LOW);
   else asm volatile(MISTRA_GSUM_ASM_HIGH : MISTRA_GSUM_OPERANDS : "memory", "scc", MISTRA_GSUM_CLOBBER_HIGH);
+}
+// The same behind a workgroup barrier that the stream runs itself, between its ring fill and its first counted wait: a call that
+// follows lds_barrier() directly waited out the barrier and THEN a whole table round trip with nothing to do; the table loads do
+// not depend on LDS, only the operand gathers do.  (The call stands in place of lds_barrier() + gsum_run().)
+template <int NT, bool LOW>
+__device__ __attribute__((noinline)) void gsum_run_bar(const GsDev P, uint32_t row0, int rows, int lane, uint32_t out_addr, uint32_t out_stride) {
+  int n = __builtin_amdgcn_readfirstlane(rows);
+  const uint64_t b0 = gsum_base(P, row0), b1 = b0 + 4096u;
+  uint32_t voff = (uint32_t)lane * 32u;
+  double acc = -0.0;
+  const double mzero = -0.0;
+  double xA0, xA1, xA2, xA3, xB0, xB1, xB2, xB3, cA0, cA1, cA2, cA3, cB0, cB1, cB2, cB3;
+  uint32_t ad, flA, flB;
+  static_assert(!LOW, "generated for the high placement of the ring only (gsum_exec_asm.inc)");
+  asm volatile(MISTRA_GSUM_ASM_HIGH_BAR : MISTRA_GSUM_OPERANDS : "memory", "scc", MISTRA_GSUM_CLOBBER_HIGH);
+}
 #undef MISTRA_GSUM_OPERANDS
+// Two programs back to back (fun_jac: the Vdot sums, then the JVS sums): in its last ring turn the first stream's refills fetch the
+// second one's first four rows where they fetched slack rows, it returns without draining them, and the second stream enters on
+// the ring as it stands — one table round trip where there were two.  The ring is full between the two statements: they sit in
+// ONE non-inlined function, whose own values the build holds below the ring like the other executors'.  BARRIER (0 | 1): as
+// gsum_run_bar.  (An int: the ring's placement is the one bool among these functions' template arguments, the build's register check and
+// tests/test_capi.py read it off the symbol.)
+template <int NT, int BARRIER, bool LOW>
+__device__ __attribute__((noinline)) void gsum_run_pair(const GsDev P, uint32_t row0, int rows, uint32_t out_addr, uint32_t out_stride,
+                                                        const GsDev Q, uint32_t qrow0, int qrows, uint32_t qout_addr, uint32_t qout_stride, int lane) {
+  static_assert(!LOW, "generated for the high placement of the ring only (gsum_exec_asm.inc)");
+  int n = __builtin_amdgcn_readfirstlane(rows), m = __builtin_amdgcn_readfirstlane(qrows);
+  const uint64_t q0 = gsum_base(Q, qrow0);
+  uint64_t b0 = gsum_base(P, row0), b1 = b0 + 4096u;
+  // the lane offset has moved on by 8 KiB per group of four rows when the last turn's refills are issued: 2 KiB per row
+  const uint64_t nb0 = q0 - (uint64_t)(uint32_t)n * 2048u, nb1 = nb0 + 4096u;
+  uint32_t voff = (uint32_t)lane * 32u;
+  double acc = -0.0;
+  const double mzero = -0.0;
+  double xA0, xA1, xA2, xA3, xB0, xB1, xB2, xB3, cA0, cA1, cA2, cA3, cB0, cB1, cB2, cB3;
+  uint32_t ad, flA, flB;
+#define MISTRA_GSUM_OUTPUTS(N, OUT)                                                                                                            \
+  [acc] "+&v"(acc), [ad] "=&v"(ad), [xA0] "=&v"(xA0), [xA1] "=&v"(xA1), [xA2] "=&v"(xA2), [xA3] "=&v"(xA3), [xB0] "=&v"(xB0), [xB1] "=&v"(xB1),    \
+      [xB2] "=&v"(xB2), [xB3] "=&v"(xB3), [cA0] "=&v"(cA0), [cA1] "=&v"(cA1), [cA2] "=&v"(cA2), [cA3] "=&v"(cA3), [cB0] "=&v"(cB0),               \
+      [cB1] "=&v"(cB1), [cB2] "=&v"(cB2), [cB3] "=&v"(cB3), [flA] "=&s"(flA), [flB] "=&s"(flB), [n] "+s"(N), [voff] "+&v"(voff), [out] "+&v"(OUT)
+#define MISTRA_GSUM_FIRST MISTRA_GSUM_OUTPUTS(n, out_addr), [b0] "+&s"(b0), [b1] "+&s"(b1) : [nb0] "s"(nb0), [nb1] "s"(nb1), [stride] "v"(out_stride), [mzero] "v"(mzero)
+  if constexpr (BARRIER) asm volatile(MISTRA_GSUM_ASM_HIGH_BAR_CHAIN : MISTRA_GSUM_FIRST : "memory", "scc", MISTRA_GSUM_CLOBBER_HIGH);
+  else asm volatile(MISTRA_GSUM_ASM_HIGH_CHAIN : MISTRA_GSUM_FIRST : "memory", "scc", MISTRA_GSUM_CLOBBER_HIGH);
+  // the second program, its first four rows in flight
+  const uint64_t q1 = q0 + 4096u;
+  voff = (uint32_t)lane * 32u;
+  acc = -0.0;
+#define MISTRA_GSUM_SECOND MISTRA_GSUM_OUTPUTS(m, qout_addr) : [b0] "s"(q0), [b1] "s"(q1), [stride] "v"(qout_stride), [mzero] "v"(mzero)
+  asm volatile(MISTRA_GSUM_ASM_HIGH_PRIMED : MISTRA_GSUM_SECOND : "memory", "scc", MISTRA_GSUM_CLOBBER_HIGH);
+#undef MISTRA_GSUM_OUTPUTS
+#undef MISTRA_GSUM_FIRST
+#undef MISTRA_GSUM_SECOND
 }
 
 // ---- the factorisation's last act (schedule.hpp: ScaleProgram): M[tgt] *= M[aux] for two cells per 16-byte slot,
@@ -672,15 +753,18 @@ __device__ __attribute__((noinline)) void scale_run(const ScaleDev P, int wave, 
   vm_ring_load<LOW, 0>(rp);       vm_ring_load<LOW, 1>(rp + 64);  vm_ring_load<LOW, 2>(rp + 128); vm_ring_load<LOW, 3>(rp + 192);
   vm_ring_load<LOW, 4>(rp + 256); vm_ring_load<LOW, 5>(rp + 320); vm_ring_load<LOW, 6>(rp + 384); vm_ring_load<LOW, 7>(rp + 448);
   rp += kRingSlots * 64;
-  for (int i = 0; i < n; i += kRingSlots) {
+  // TRIM: the last ring turn issues no refills — nobody reads those rows, and the drain below waited a whole table round trip for
+  // them, issued an iteration earlier.  Without refills behind it, slot K is the oldest of 8 - K loads in flight.
+  constexpr bool TRIM = MISTRA_STREAM_SCALE_TRIM && !LOW;
+  const int n_refilled = TRIM ? n - kRingSlots : n;
     // four slots at a time: sixteen gathers in flight, then the eight products (a lone gather-multiply-store chain per
     // slot would expose the LDS latency sixteen times over)
-#define MISTRA_SCALE_GROUP(K)                                                        \
+#define MISTRA_SCALE_GROUP(K, REFILL)                                                \
     {                                                                                \
-      const u32x4 a0 = vm_ring_take<LOW, K>();     vm_ring_load<LOW, K>(rp + K * 64);         \
-      const u32x4 a1 = vm_ring_take<LOW, K + 1>(); vm_ring_load<LOW, K + 1>(rp + (K + 1) * 64); \
-      const u32x4 a2 = vm_ring_take<LOW, K + 2>(); vm_ring_load<LOW, K + 2>(rp + (K + 2) * 64); \
-      const u32x4 a3 = vm_ring_take<LOW, K + 3>(); vm_ring_load<LOW, K + 3>(rp + (K + 3) * 64); \
+      const u32x4 a0 = vm_ring_take<LOW, K, REFILL ? 7 : 7 - K>();     if constexpr (REFILL) vm_ring_load<LOW, K>(rp + K * 64);         \
+      const u32x4 a1 = vm_ring_take<LOW, K + 1, REFILL ? 7 : 6 - K>(); if constexpr (REFILL) vm_ring_load<LOW, K + 1>(rp + (K + 1) * 64); \
+      const u32x4 a2 = vm_ring_take<LOW, K + 2, REFILL ? 7 : 5 - K>(); if constexpr (REFILL) vm_ring_load<LOW, K + 2>(rp + (K + 2) * 64); \
+      const u32x4 a3 = vm_ring_take<LOW, K + 3, REFILL ? 7 : 4 - K>(); if constexpr (REFILL) vm_ring_load<LOW, K + 3>(rp + (K + 3) * 64); \
       const double v0 = lds_ld(a0.x), f0 = lds_ld(a0.y), v1 = lds_ld(a0.z), f1 = lds_ld(a0.w); \
       const double v2 = lds_ld(a1.x), f2 = lds_ld(a1.y), v3 = lds_ld(a1.z), f3 = lds_ld(a1.w); \
       const double v4 = lds_ld(a2.x), f4 = lds_ld(a2.y), v5 = lds_ld(a2.z), f5 = lds_ld(a2.w); \
@@ -688,10 +772,14 @@ __device__ __attribute__((noinline)) void scale_run(const ScaleDev P, int wave, 
       lds_st(a0.x, v0 * f0); lds_st(a0.z, v1 * f1); lds_st(a1.x, v2 * f2); lds_st(a1.z, v3 * f3); \
       lds_st(a2.x, v4 * f4); lds_st(a2.z, v5 * f5); lds_st(a3.x, v6 * f6); lds_st(a3.z, v7 * f7); \
     }
-    MISTRA_SCALE_GROUP(0) MISTRA_SCALE_GROUP(4)
-#undef MISTRA_SCALE_GROUP
+  for (int i = 0; i < n_refilled; i += kRingSlots) {
+    MISTRA_SCALE_GROUP(0, true) MISTRA_SCALE_GROUP(4, true)
     rp += kRingSlots * 64;
   }
+  if constexpr (TRIM) {
+    if (n > 0) { MISTRA_SCALE_GROUP(0, false) MISTRA_SCALE_GROUP(4, false) }
+  }
+#undef MISTRA_SCALE_GROUP
   asm volatile("s_waitcnt vmcnt(0)" : : : "memory");     // drain the look-ahead loads before returning
 }
 
@@ -1338,15 +1426,22 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   // Fun_x's sums land in the thread's own cells of XS (free here: the solves copy their result out before Fun runs again): species t
   // and, where a thread owns two (one wavefront per cell: NT = 64 < NVAR), t + NT.  A thread without a species, or whose second one
   // does not exist, parks that (empty) sum in the trash cell: the stride between a lane's outputs is per lane.
-  auto vdot_sums = [&]() {
+  // (the stream start-up sites: tot's placement of the ring only, see MISTRA_STREAM_* above)
+  constexpr bool kGsumBarrier = MISTRA_STREAM_GSUM_BARRIER && !MT::RING_LOW, kGsumChain = MISTRA_STREAM_GSUM_CHAIN && !MT::RING_LOW;
+  constexpr bool kSweepBarrier = MISTRA_STREAM_SWEEP_BARRIER && !MT::RING_LOW;
+  auto vdot_out = [&](uint32_t& addr, uint32_t& stride) {
     int tt = t;
     if constexpr (!RESIDENT) asm volatile("" : "+v"(tt));      // (derived here: kept across the step loop, the stride was one more register stored to scratch per step)
     constexpr uint32_t trash = 8u * (uint32_t)(NNZ + NVAR + 2);
-    const uint32_t addr = tt < NVAR ? 8u * (uint32_t)(NNZ + tt) : trash;
-    uint32_t stride;
+    addr = tt < NVAR ? 8u * (uint32_t)(NNZ + tt) : trash;
     if constexpr (SPT == 1) stride = tt < NVAR ? 8u * (uint32_t)NT : 0u;
     else stride = tt + NT < NVAR ? 8u * (uint32_t)NT : trash - addr;
-    gsum_run<NT, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, lane, addr, stride);
+  };
+  auto vdot_sums = [&](auto barrier_tag) {      // barrier: in place of the lds_barrier() in front
+    uint32_t addr, stride;
+    vdot_out(addr, stride);
+    if constexpr (decltype(barrier_tag)::value) gsum_run_bar<NT, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, lane, addr, stride);
+    else gsum_run<NT, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, lane, addr, stride);
   };
   auto read_vdot = [&](double (&out)[SPT]) {
 #pragma unroll
@@ -1358,6 +1453,14 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   // Jac_SP_x's sums land in this thread's own cells of the Ghimj area (free here: ros_PrepareMatrix rebuilds it from jac0)
   double jac0[JPT];
   auto jvs_sums = [&]() { gsum_run<NT, MT::RING_LOW>(a.jvs, hdr.jvs_row0, hdr.jvs_rows, lane, 8u * (uint32_t)t, 8u * (uint32_t)NT); };
+  auto vdot_jvs_sums = [&]() {      // fun_jac's two programs as one call (gsum_run_pair)
+    if constexpr (kGsumChain) {
+      uint32_t addr, stride;
+      vdot_out(addr, stride);
+      gsum_run_pair<NT, kGsumBarrier ? 1 : 0, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, addr, stride,
+                                                    a.jvs, hdr.jvs_row0, hdr.jvs_rows, 8u * (uint32_t)t, 8u * (uint32_t)NT, lane);
+    }
+  };
   auto read_jvs = [&]() {
 #pragma unroll
     for (int q = 0; q < JPT; q++) jac0[q] = M[q * NT + t];
@@ -1369,9 +1472,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     store_x(v);
     lds_barrier();
     a_products();
-    lds_barrier();
+    if constexpr (!kGsumBarrier) lds_barrier();      // (else: inside the sums' executor, behind its ring fill)
     lap(15);
-    vdot_sums();
+    vdot_sums(std::bool_constant<kGsumBarrier>{});
     read_vdot(out);
   };
   auto jac = [&]() {
@@ -1399,10 +1502,14 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     lds_barrier();   // X is complete; nobody reads the Ghimj area any more (the last solve's sweeps are behind the error norm's barriers)
     a_products();
     b_products(jfac);
-    lds_barrier();
+    if constexpr (!kGsumBarrier) lds_barrier();      // (else: inside the sums' executor, behind its ring fill)
     lap(13);
-    vdot_sums();
-    jvs_sums();      // (other cells, another source array: no barrier between)
+    if constexpr (kGsumChain) {
+      vdot_jvs_sums();
+    } else {
+      vdot_sums(std::bool_constant<kGsumBarrier>{});
+      jvs_sums();      // (other cells, another source array: no barrier between)
+    }
     lap(14);
     read_vdot(out);
     read_jvs();
@@ -1470,9 +1577,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         const int s = q * NT + t;
         if (s < NVAR) XS[s] = k[q];
       }
-      lds_barrier();
+      if constexpr (!kSweepBarrier) lds_barrier();      // (else: inside the sweep's executor, behind its ring fill)
       lap(6);
-      vm_run<NT, 4, kVmSweepUpdPerRec>(a.solve_head_fwd, hdr.fwd_row0, lane);                                          // head rows, all waves
+      vm_run<NT, 4, kVmSweepUpdPerRec, kSweepBarrier>(a.solve_head_fwd, hdr.fwd_row0, lane);                           // head rows, all waves
       lap(8);
       if (wave == 0)                                                                         // tail chain, one wave
         tail(std::false_type{});
@@ -1481,9 +1588,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       if (wave == 0)      // with the dense tail block the forward chain still has the block's own columns to do
         tail(std::true_type{});
     }
-    lds_barrier();
+    if constexpr (!kSweepBarrier) lds_barrier();
     lap(9);
-    vm_run<NT, 4, kVmSweepUpdPerRec>(a.solve_head_bwd, hdr.bwd_row0, lane);
+    vm_run<NT, 4, kVmSweepUpdPerRec, kSweepBarrier>(a.solve_head_bwd, hdr.bwd_row0, lane);
     lap(10);
 #pragma unroll
     for (int q = 0; q < SPT; q++) {

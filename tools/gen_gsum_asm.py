@@ -31,7 +31,13 @@ OUT = os.path.join(HERE, "..", "mistra_amd", "csrc", "gsum_exec_asm.inc")
 SLOTS = {"LOW": [64, 68, 80, 84, 96, 100, 112, 116], "HIGH": [192, 196, 208, 212, 224, 228, 240, 244]}
 
 
-def variant(name):
+def variant(name, fill=True, barrier=False, chain=False):
+    """fill: the stream fills its own ring (else it enters on a ring that the stream in front of it filled: its first four rows
+    are in flight, issued in the order a fill issues them, so the counted waits below hold as they stand).
+    barrier: the workgroup barrier in front of the stream sits behind the fill — table loads do not depend on LDS, the gathers do.
+    chain: in the last ring turn the refills fetch the NEXT stream's first four rows (%[nb0], %[nb1]: its base less the distance
+    %[voff] has moved on by then, 8 KiB per group of four rows) where they would fetch slack rows, and the stream returns with
+    those loads in flight."""
     slot = SLOTS[name]
     L = []
     emit = L.append
@@ -66,13 +72,30 @@ def variant(name):
         emit("v_mov_b64 %[acc], %[mzero]")
         emit("Lgs_nf%s_%%=:" % tag)
 
-    emit("s_waitcnt vmcnt(0)")          # nothing of the caller's may sit between the counted loads
-    emit("s_nop 4")                     # (the bases may have been written by v_readfirstlane just before: 5 wait states before a memory instruction reads them)
-    for r in range(4):
-        load_row(r)
-    emit("v_add_u32 %[voff], 0x2000, %[voff]")      # the next group of four rows
-    emit("s_cmp_lt_i32 %[n], 1")
-    emit("s_cbranch_scc1 Lgs_exit_%=")
+    def to_next():              # from here on the refills fetch the next stream (scalar registers written by scalar instructions: no wait states)
+        emit("s_mov_b64 %[b0], %[nb0]")
+        emit("s_mov_b64 %[b1], %[nb1]")
+
+    if fill:
+        emit("s_waitcnt vmcnt(0)")          # nothing of the caller's may sit between the counted loads
+        emit("s_nop 4")                     # (the bases may have been written by v_readfirstlane just before: 5 wait states before a memory instruction reads them)
+        for r in range(4):
+            load_row(r)
+    if barrier:
+        emit("s_waitcnt lgkmcnt(0)")        # the caller's LDS stores are done (lds_barrier's release), then the barrier itself
+        emit("s_barrier")
+    if chain:
+        emit("s_cmp_lt_i32 %[n], 1")
+        emit("s_cbranch_scc1 Lgs_none_%=")
+        emit("v_add_u32 %[voff], 0x2000, %[voff]")
+        emit("s_cmp_lt_i32 %[n], 5")        # one group only: its refills are the last turn's
+        emit("s_cbranch_scc0 Lgs_go_%=")
+        to_next()
+        emit("Lgs_go_%=:")
+    else:
+        emit("v_add_u32 %[voff], 0x2000, %[voff]")      # the next group of four rows
+        emit("s_cmp_lt_i32 %[n], 1")
+        emit("s_cbranch_scc1 Lgs_exit_%=")
     fetch(0, "A")
     emit("Lgs_loop_%=:")
     fetch(1, "B"); summ("A", "0")
@@ -80,29 +103,61 @@ def variant(name):
     fetch(3, "B"); summ("A", "2")
     emit("v_add_u32 %[voff], 0x2000, %[voff]")
     emit("s_sub_i32 %[n], %[n], 4")
-    emit("s_cmp_lt_i32 %[n], 1")
-    emit("s_cbranch_scc1 Lgs_last_%=")
+    if chain:
+        emit("s_cmp_lt_i32 %[n], 5")        # (the main line carries the same three scalar instructions as without a next stream)
+        emit("s_cbranch_scc1 Lgs_few_%=")
+    else:
+        emit("s_cmp_lt_i32 %[n], 1")
+        emit("s_cbranch_scc1 Lgs_last_%=")
     fetch(0, "A"); summ("B", "3")
     emit("s_branch Lgs_loop_%=")
+    if chain:
+        emit("Lgs_few_%=:")
+        emit("s_cmp_lt_i32 %[n], 1")
+        emit("s_cbranch_scc1 Lgs_last_%=")
+        to_next()                           # one group left: the last ring turn begins with this refill
+        fetch(0, "A"); summ("B", "5")
+        emit("s_branch Lgs_loop_%=")
     emit("Lgs_last_%=:")
     emit("s_waitcnt lgkmcnt(0)")
     summ("B", "4")
-    emit("Lgs_exit_%=:")
-    emit("s_waitcnt vmcnt(0) lgkmcnt(0)")      # the look-ahead loads have landed before the ring registers are reused; stores done
+    if chain:
+        emit("s_branch Lgs_exit_%=")
+        emit("Lgs_none_%=:")                # a wave without rows: its own fill was for nothing, the next stream's takes its place
+        emit("s_waitcnt vmcnt(0)")
+        to_next()
+        for r in range(4):
+            load_row(r)
+        emit("Lgs_exit_%=:")
+        emit("s_waitcnt lgkmcnt(0)")        # stores done; the next stream's first four rows stay in flight
+    else:
+        emit("Lgs_exit_%=:")
+        emit("s_waitcnt vmcnt(0) lgkmcnt(0)")      # the look-ahead loads have landed before the ring registers are reused; stores done
     clob = ", ".join('"v%d"' % (b + k) for b in slot for k in range(4))
     return L, clob
+
+
+# the streams ros3_kernel.hip runs: suffix -> (fill, barrier, chain)
+FORMS = [("", (True, False, False)),                 # gsum_run: fill, run, drain
+         ("_BAR", (True, True, False)),              # gsum_run_bar: fill, workgroup barrier, run, drain
+         ("_CHAIN", (True, False, True)),            # gsum_run_pair, first program: fill, run, leave the second program's first rows in flight
+         ("_BAR_CHAIN", (True, True, True)),         #   ... with the workgroup barrier behind the fill
+         ("_PRIMED", (False, False, False))]         # gsum_run_pair, second program: run on the ring as filled, drain
 
 
 def render():
     out = ["// GENERATED by tools/gen_gsum_asm.py — do not edit.  Instruction stream of the gather-sum machine (ros3_kernel.hip: gsum_run).", ""]
     for name in ("LOW", "HIGH"):
-        lines, clob = variant(name)
-        out.append("#define MISTRA_GSUM_ASM_%s \\" % name)
-        for i, ln in enumerate(lines):
-            sep = "\\n" if ln.endswith(":") else "\\n\\t"
-            last = i == len(lines) - 1
-            out.append('  "%s%s"%s' % (ln, "" if last else sep, "" if last else " \\"))
-        out.append("")
+        for suffix, form in FORMS:
+            if name == "LOW" and suffix:      # the low placement (gas) runs the plain form only
+                continue
+            lines, clob = variant(name, *form)
+            out.append("#define MISTRA_GSUM_ASM_%s%s \\" % (name, suffix))
+            for i, ln in enumerate(lines):
+                sep = "\\n" if ln.endswith(":") else "\\n\\t"
+                last = i == len(lines) - 1
+                out.append('  "%s%s"%s' % (ln, "" if last else sep, "" if last else " \\"))
+            out.append("")
         out.append("#define MISTRA_GSUM_CLOBBER_%s %s" % (name, clob))
         out.append("")
     return "\n".join(out)

@@ -48,7 +48,9 @@ v_div_fmas_f64 %[a1{P}], %[a1{P}], %[r1{P}], %[a2{P}]
 v_div_fixup_f64 %[a1{P}], %[a1{P}], %[acc], 1.0"""      # the sequence hipcc emits for 1.0/x (IEEE)
 
 
-def variant(upr=2):
+def variant(upr=2, barrier=False):
+    """barrier: the workgroup barrier in front of the program sits between the ring fill and the first counted wait (table loads
+    do not depend on LDS; the first record's gathers stay behind the barrier)."""
     n, blk = N, BLOCKS
     L = []
     emit = L.append
@@ -117,6 +119,9 @@ def variant(upr=2):
         refill(s)
     for b in range(n // 2):
         emit("v_add_u32 %s, %d, %s" % (BASES[b], n * 2048, BASES[b]))
+    if barrier:
+        emit("s_waitcnt lgkmcnt(0)")     # the caller's LDS stores are done (lds_barrier's release), then the barrier itself
+        emit("s_barrier")
     emit("s_waitcnt vmcnt(%d)" % vm_after)
     prefetch(0, "A")
     # ---- main line
@@ -200,9 +205,10 @@ def variant(upr=2):
 
 def render():
     out = ["// GENERATED by tools/gen_vm_asm.py — do not edit.  Instruction stream of the LDS VM executor (ros3_kernel.hip: vm_run).", ""]
-    for upr in (2, 3):
-        lines, clob = variant(upr)
+    for upr, barrier in ((2, False), (3, False), (3, True)):
+        lines, clob = variant(upr, barrier)
         tag = "N%d" % N if upr == 2 else "N%d_SWEEP" % N      # _SWEEP: records of three two-operand updates (schedule.hpp: VM_SWEEP_UPD_PER_REC)
+        tag += "_BAR" if barrier else ""                        # _BAR: the head sweeps behind a barrier (ros3_kernel.hip: solve)
         out.append("#define MISTRA_VM_ASM_%s \\" % tag)
         for i, ln in enumerate(lines):
             sep = "\\n" if ln.endswith(":") else "\\n\\t"
