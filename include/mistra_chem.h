@@ -91,6 +91,14 @@ int mistra_chem_integrate_device_hstart(int mech, int ncell, const double* d_var
                                         int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                         const double* d_hstart, void* hip_stream);
 
+/* OPT-IN likewise, for a caller that is not a torch program: mistra_chem_integrate_ex (rconst given, env = NULL) or mistra_chem_integrate_env_ex (env given,
+ * rconst = NULL) — exactly one of the two — with a first step size per cell in HOST memory, hstart [ncell]; hstart = NULL, or an entry <= 0, gives the
+ * reference's value (1e-3, or RPAR(3) of the options in force).  The library cannot key a caller-ordered batch by layer, so here the caller keeps the step
+ * sizes: t_h[3c+1] of one call is hstart[c] of the next (shim/mistra_kpp_shim.f90: INTEGRATE_BATCH_H_x).  With several device slots every block of cells takes
+ * its own part of hstart.  The batched driver keeps them itself: mistra_chem_set_step_reuse below. */
+int mistra_chem_integrate_hstart_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, const double* env, double tin,
+                                    double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart);
+
 /* Fortran-callable per-cell entry points with the reference's own signature, `SUBROUTINE INTEGRATE_x(TIN,TOUT)`
  * (REAL*8 by reference; data through COMMON /GDATA_x/).  `gdata` is the address of that COMMON block, laid out
  * C(NSPEC), RCONST(NREACT), TIME, DT, ATOL(NVAR), RTOL(NVAR), STEPMIN, STEPMAX (gas_Global.h:29-58).  On return VAR
@@ -121,7 +129,7 @@ int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, doub
  *   atol, rtol        AbsTol <= 0, RelTol <= 10 eps or RelTol >= 1 in an entry that is read: IERR -5.
  * Only Ros3 (ipar[3] = 2) is built: the four other valid methods are refused by the library (non-zero return), which is not a code
  * of Rosenbrock_x's.  One vector pair per call, shared by all cells, as in KPP.  A per-cell first step size of
- * mistra_chem_integrate_device_hstart still goes before rpar[2]; ipar[2] /= 0 goes before mistra_chem_debug_set_max_steps.
+ * mistra_chem_integrate_device_hstart, of mistra_chem_integrate_hstart_ex or remembered under mistra_chem_set_step_reuse still goes before rpar[2]; ipar[2] /= 0 goes before mistra_chem_debug_set_max_steps.
  *
  * mistra_chem_check_options: the decode alone, pure host arithmetic, works before init.  *ierr = 1, or the IERR Rosenbrock_x would return
  * (-1 .. -5; the call itself then still returns 0); a valid method that is not built: non-zero return, *ierr = 0.  For *ierr = 1,
@@ -249,6 +257,29 @@ int mistra_chem_drive_begin(int mech, int nlayer, const int32_t* layer, int n, d
                       const double* env, double tin, double dt, int32_t* ierr, int32_t* stats, double* t_h, double* bg, int nrxn,
                       const int32_t* bg_level, double* bgs, double* c_packed);
 int mistra_chem_drive_end(int mech);
+
+/* OPT-IN, NOT the reference's behaviour: carry every layer's step size from one column step to the next.  INTEGRATE_x starts
+ * every call at Hstart = 1e-3 s (gas.f:743) and leaves the last accepted step in STEPMIN (gas.f:770) for a driver to feed back; the reference never does.  With
+ * reuse on for `mech`, mistra_chem_drive(_begin) keeps a step memory on the device — one double per model layer k = 1..n (n: the call's argument), 0 = none —
+ * and, on the mechanism's stream, in order with the rest of the chain: starts layer[i] at mem[layer[i] - 1] (mistra_chem_integrate_device_hstart's d_hstart;
+ * 0: the call's Hstart), and after the integrator clears the whole memory and stores Hexit of the layers that returned IERR = 1.  So a layer starts from the
+ * call's Hstart again if it was not in the mechanism's PREVIOUS column step (cloud formed or went: it ran another mechanism in between) or if it failed there.
+ * The three mechanisms' memories are independent.  A remembered step goes before RPAR(3) of the options in force, which serves (or 1e-3) where there is none.
+ * The memory is forgotten when reuse is switched, on mistra_chem_set_options (also when it clears them), on mistra_chem_finalize and every re-initialisation, and
+ * when n changes.  Off (the default) nothing of this runs: the reference's path, bit for bit.  mistra_chem_drive_device is not affected: a device-resident
+ * caller composes the public pieces with mistra_chem_integrate_device_hstart.
+ *
+ * mistra_chem_set_step_reuse / mistra_chem_get_step_reuse (-> 0 | 1): host state, per mechanism, process-wide; they work before init and without a device, and the
+ * flag outlives mistra_chem_finalize.  MISTRA_CHEM_HSTART_REUSE=1 in the environment turns reuse on for all three mechanisms when the library starts (read once,
+ * by the first initialisation or the first of these two calls; unset or 0: off) — for a model binary that is already linked.
+ * mistra_chem_get_step_memory / mistra_chem_set_step_memory: the memory of `mech` from / to a host double[n], for a restart file (a restarted run that puts it
+ * back after turning reuse on continues like an uninterrupted one) or to look at it.  get: zeros while nothing is remembered; n must else be the memory's.  set:
+ * entries finite and >= 0.  Primary device; they initialise the library like the Fortran entry points.
+ * set_step_reuse, get_step_memory and set_step_memory fail while a column step of the mechanism is open, like the other host-buffer calls. */
+int mistra_chem_set_step_reuse(int mech, int on);
+int mistra_chem_get_step_reuse(int mech);
+int mistra_chem_get_step_memory(int mech, int n, double* h);
+int mistra_chem_set_step_memory(int mech, int n, const double* h);
 
 /* ---- liq_parm, first slice: the gas <-> particle mass-transfer coefficients of fast_k_mt_a (mech = aer;
  * kpp.f90:2683-2947) and fast_k_mt_t (mech = tot; kpp.f90:2421-2676), called by liq_parm every 120 s (kpp.f90:617,637), for nlayer

@@ -96,6 +96,12 @@ def lib():
             L.mistra_chem_check_options.argtypes = [C.c_int, _ip, _dp, _dp, _dp, C.c_double, _ip, _dp, _ip]
             L.mistra_chem_set_options.argtypes = [C.c_int, _ip, _dp, _dp, _dp, _ip]
             L.mistra_chem_get_options.argtypes = [C.c_int, _ip, _ip, _dp, _dp, _dp]
+        if hasattr(L, "mistra_chem_set_step_reuse"):
+            L.mistra_chem_set_step_reuse.argtypes = [C.c_int, C.c_int]
+            L.mistra_chem_get_step_reuse.argtypes = [C.c_int]
+            L.mistra_chem_get_step_memory.argtypes = [C.c_int, C.c_int, _dp]
+            L.mistra_chem_set_step_memory.argtypes = [C.c_int, C.c_int, _dp]
+            L.mistra_chem_integrate_hstart_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp, _ip, _ip, _dp, _dp]
         L.mistra_chem_last_error.restype = C.c_char_p
         L.mistra_chem_describe.restype = C.c_char_p
         L.mistra_chem_describe.argtypes = [C.c_int]
@@ -172,17 +178,22 @@ def integrate(mech, var, fix, rconst, tin=0.0, tout=10.0, device=None):
     return IntegrateResult(out, ierr, stats)
 
 
-def integrate_ex(mech, var, fix, rconst, tin=0.0, tout=10.0, env=None):
+def integrate_ex(mech, var, fix, rconst, tin=0.0, tout=10.0, env=None, hstart=None):
     """mistra_chem_integrate_ex on host buffers: what `integrate` returns plus t_h [ncell, 3] — per cell the exit time (-> TIN,
     gas.f:769), the last accepted step (-> STEPMIN, gas.f:770) and H when the integrator returned.  This is the call the batched
     Fortran surface makes (shim/mistra_kpp_shim.f90: INTEGRATE_BATCH_x); with several devices initialised (init_devices) the
-    library cuts the batch into one block per device."""
+    library cuts the batch into one block per device.  hstart [ncell]: OPT-IN first step size per cell, e.g. t_h[:, 1] of the previous
+    call (mistra_chem_integrate_hstart_ex; entries <= 0: the reference's value)."""
     mid, name = _mech_id(mech)
     nvar, nfix, nreact, _ = DIMS[name]
-    if _inited_device is None:
-        init(0)
     v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
     ncell = v.shape[0]
+    if hstart is not None:
+        hs = np.ascontiguousarray(hstart, np.float64)
+        if hs.shape != (ncell,):
+            raise MistraChemError("hstart: %d entries expected, one per cell" % ncell)
+    if _inited_device is None:
+        init(0)
     f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
     if env is not None:      # mistra_chem_integrate_env_ex: the rate evaluator's inputs instead of the rate constants
         r = np.ascontiguousarray(env, np.float64).reshape(ncell, -1)
@@ -193,6 +204,12 @@ def integrate_ex(mech, var, fix, rconst, tin=0.0, tout=10.0, env=None):
     ierr = np.zeros(ncell, np.int32)
     stats = np.zeros((ncell, 8), np.int32)
     th = np.zeros((ncell, 3))
+    if hstart is not None:
+        rp, ep = (None, r.ctypes.data_as(_dp)) if env is not None else (r.ctypes.data_as(_dp), None)
+        _check(lib().mistra_chem_integrate_hstart_ex(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), rp, ep, float(tin), float(tout),
+                                                     out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip),
+                                                     th.ctypes.data_as(_dp), hs.ctypes.data_as(_dp)))
+        return IntegrateResult(out, ierr, stats), th
     _check((lib().mistra_chem_integrate_env_ex if env is not None else lib().mistra_chem_integrate_ex)(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp),
                                          float(tin), float(tout), out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip),
                                          stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp)))
@@ -338,6 +355,36 @@ def get_options(mech):
     _check(lib().mistra_chem_get_options(mid, C.byref(is_set), ip.ctypes.data_as(_ip), rp.ctypes.data_as(_dp), at.ctypes.data_as(_dp),
                                          rt.ctypes.data_as(_dp)))
     return Options(ip, rp, at, rt) if is_set.value else None
+
+
+# ---- OPT-IN: every layer's step size carried from one column step to the next (include/mistra_chem.h: mistra_chem_set_step_reuse)
+def set_step_reuse(mech, on=True):
+    """Step reuse of drive_host for `mech`: each layer starts at the last accepted step size of its previous column step of this mechanism instead
+    of INTEGRATE_x's 1e-3.  Host state: works before init and without a GPU.  Switching forgets the memory."""
+    _check(lib().mistra_chem_set_step_reuse(_mech_id(mech)[0], int(bool(on))))
+
+
+def get_step_reuse(mech):
+    return bool(lib().mistra_chem_get_step_reuse(_mech_id(mech)[0]))
+
+
+def get_step_memory(mech, n):
+    """-> the step memory of `mech`, float64 [n]: per model layer k = 1..n the step size its next column step starts at, 0 = none."""
+    if _inited_device is None:
+        init(0)
+    h = np.zeros(int(n))
+    _check(lib().mistra_chem_get_step_memory(_mech_id(mech)[0], int(n), h.ctypes.data_as(_dp)))
+    return h
+
+
+def set_step_memory(mech, h):
+    """Puts a saved step memory back (a restart): h [n], one entry per model layer, 0 = none.  Call it after set_step_reuse(mech, True)."""
+    if _inited_device is None:
+        init(0)
+    a = np.ascontiguousarray(h, np.float64)
+    if a.ndim != 1:
+        raise MistraChemError("the step memory is one entry per model layer")
+    _check(lib().mistra_chem_set_step_memory(_mech_id(mech)[0], a.size, a.ctypes.data_as(_dp)))
 
 
 def debug_set_max_steps(n=0):

@@ -486,10 +486,11 @@ struct Layout {
 
 // one column step in the drive arena of its mechanism.  In/out first — s1 | s3 | sl1 | sion1 | bg | bgs — then in-only — scal | env — then
 // out-only — th(2) | hlast | ierr | stats | c_packed — then device only — var | fix | rct.  Counts in doubles per layer, offsets in bytes.
+// With step reuse on (mistra_chem_set_step_reuse) the layer list rides behind env in the in-only part and the gathered first steps behind rct.
 struct DriveLayout {
   size_t nl = 0, j1 = 0, j5 = 0, nsl = 0, nsi = 0, nv = 0, nf = 0, nr = 0, ne = 0;
-  size_t s1 = 0, s3 = 0, sl1 = 0, si = 0, bg = 0, bgs = 0, io_end = 0, scal = 0, env = 0, in_end = 0;
-  size_t th = 0, hl = 0, ierr = 0, stats = 0, cp = 0, out_end = 0, var = 0, fix = 0, rct = 0, end = 0;
+  size_t s1 = 0, s3 = 0, sl1 = 0, si = 0, bg = 0, bgs = 0, io_end = 0, scal = 0, env = 0, lyr = 0, in_end = 0;
+  size_t th = 0, hl = 0, ierr = 0, stats = 0, cp = 0, out_end = 0, var = 0, fix = 0, rct = 0, hs = 0, end = 0;
 };
 
 struct MechState {
@@ -509,8 +510,12 @@ struct MechState {
   // none are set, and IPAR(3) (0: the library's Max_no_steps)
   DevBuf<double> opt;
   int opt_max_steps = 0;
+  // the step memory of the batched driver (mistra_chem_set_step_reuse): per model layer k = 1..step_n the last accepted step size of the layer's previous
+  // column step of this mechanism, 0 = none.  step_n = 0: forgotten — the next column step under reuse sizes it to its n and zeroes it on the drive stream
+  DevBuf<double> step_mem;
+  int step_n = 0;
   // staging of the batched host-buffer entries (grow-only)
-  DevBuf<double> s_var, s_fix, s_rct, s_th, s_env;
+  DevBuf<double> s_var, s_fix, s_rct, s_th, s_env, s_hst;
   DevBuf<int32_t> s_ierr, s_stats, s_sing;
   // where the zero-pivot rows of the LAST host-buffer call of this slot are (mistra_chem_singular_rows): cells [sing_start,
   // sing_start + sing_count) of the caller's batch in s_sing, or the one cell of the COMMON-block call in one_sing
@@ -531,6 +536,8 @@ struct MechState {
     k.release(); rates.release(); pack.release(); kmt.release(); liq.release(); stc.release(); vmean.release();
     d_rct.release();
     opt.release(); opt_max_steps = 0;
+    step_mem.release(); step_n = 0;
+    s_hst.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
     sing_count = 0; sing_one = false;
     drive.release(); one.release();
@@ -571,6 +578,18 @@ struct RosOptions {
   RosResolved r;
   std::vector<double> block;      // the device block: RosOptSlot scalars, then AbsTol(1:NVAR), RelTol(1:NVAR) as the integrator uses them
 } g_opts[3];
+
+// ---- OPT-IN step reuse of the batched driver (mistra_chem_set_step_reuse): per mechanism, process-wide host state; MISTRA_CHEM_HSTART_REUSE=1 in the
+// environment turns all three on, read once — by the first initialisation or the first look at the flags, whichever comes first (g_mu held)
+bool g_step_reuse[3] = {false, false, false};
+bool g_step_env_read = false;
+void read_step_env() {
+  if (g_step_env_read) return;
+  g_step_env_read = true;
+  const char* e = std::getenv("MISTRA_CHEM_HSTART_REUSE");
+  if (e && std::atoi(e) != 0)
+    for (bool& r : g_step_reuse) r = true;
+}
 
 // the host-buffer entries of the liq_parm kernels: one arena on the primary device (DevBlock below), and the caller ranges that
 // mistra_chem_pin_host registered, which those entries copy to and from directly
@@ -823,11 +842,13 @@ int on_device(int mech, int ncell, const void* p, const char* what, unsigned nee
 // The primary slot for a host-buffer entry (the caller holds g_mu), with the tables `need` names.  `mutates`: the entry changes the
 // mechanism's staging, species maps or singular-row record, which a column step issued by mistra_chem_drive_begin may still be using —
 // refused while such a step is open.
+int step_is_open(int mech) {
+  return fail(std::string("a column step of the ") + kMechName[mech] + " mechanism is open (mistra_chem_drive_begin): fetch it with mistra_chem_drive_end first");
+}
 int on_primary(int mech, unsigned need, bool mutates, Slot* t) {
   DeviceState& D = g_devs[0];
   MechState& S = D.mech[mech];
-  if (mutates && S.pend.active)
-    return fail(std::string("a column step of the ") + kMechName[mech] + " mechanism is open (mistra_chem_drive_begin): fetch it with mistra_chem_drive_end first");
+  if (mutates && S.pend.active) return step_is_open(mech);
   if (int rc = require(S, mech, need)) return rc;
   HIP_TRY(hipSetDevice(D.id));
   *t = Slot{&D, &S};
@@ -835,6 +856,7 @@ int on_primary(int mech, unsigned need, bool mutates, Slot* t) {
 }
 
 int init_locked(int n, const int* ids) {
+  read_step_env();
   int count = 0;
   hipError_t e = hipGetDeviceCount(&count);
   if (e != hipSuccess || count <= 0) return fail("no HIP device available (this library has no CPU path)");
@@ -870,7 +892,7 @@ int init_locked(int n, const int* ids) {
 // is made on the device and never crosses PCIe
 int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                       double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, size_t batch_start = 0,
-                      const double* env = nullptr) {
+                      const double* env = nullptr, const double* hstart = nullptr) {
   HIP_TRY(hipSetDevice(D.id));
   MechState& S = D.mech[mech];
   const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact, nc = (size_t)ncell;
@@ -893,6 +915,11 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
   }
   KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, tin, tout, S.s_var.p, S.s_ierr.p, S.s_stats.p, t_h ? S.s_th.p : nullptr);
   if (t_h) a.h_last = S.s_th.p + 2 * nc;
+  if (hstart) {      // OPT-IN: the caller's first step size per cell (mistra_chem_integrate_hstart_ex)
+    HIP_TRY(S.s_hst.reserve(nc));
+    HIP_TRY(hipMemcpy(S.s_hst.p, hstart, nc * sizeof(double), hipMemcpyHostToDevice));
+    a.hstart = S.s_hst.p;
+  }
   a.sing_rows = S.s_sing.p;      // stays on the device: fetched by mistra_chem_singular_rows, i.e. only when a cell reports Nsng > 0
   S.sing_start = batch_start; S.sing_count = nc; S.sing_one = false;
   // diagnostic builds only (-DMISTRA_DIAG_ENV, tools/diag_dense.sh env): MISTRA_CHEM_PROFILE=1 prints where wave 0 of the
@@ -945,9 +972,15 @@ struct ColumnDev {
   double *bg, *bgs;             // budgets, each may be nullptr
   double *c_packed, *h_last;    // nullptr unless wanted
   int32_t* sing_rows;           // nullptr unless wanted
+  // step reuse (mem != nullptr): the batch's layer numbers on the device, where their first steps are gathered to, the mechanism's step memory [mem_n]
+  const int32_t* layer;
+  double* hstart;
+  double* mem;
+  int mem_n;
 };
 
-// pack -> (C as packed) -> env from C -> Update_RCONST_x -> INTEGRATE_x -> budgets -> unpack, in order on `st`
+// pack -> (C as packed) -> env from C -> Update_RCONST_x -> INTEGRATE_x -> budgets -> unpack, in order on `st`; under step reuse the integrator starts every
+// layer at the step size the memory holds for it, and the memory is then rewritten from this step: cleared, and Hexit of the layers that succeeded stored
 int column_step(DeviceState& D, int mech, int ncell, const ColumnDev& c, double tin, double dt, hipStream_t st) {
   const MechState& S = D.mech[mech];
   const PackDev P = pack_dev(S);
@@ -962,13 +995,21 @@ int column_step(DeviceState& D, int mech, int ncell, const ColumnDev& c, double 
   KernelArgs a = make_args(S, ncell, c.var, c.fix, c.rct, tin, tin + dt, c.var, c.ierr, c.stats, c.th);
   a.h_last = c.h_last;
   a.sing_rows = c.sing_rows;
+  if (c.mem) {
+    LAUNCH_TRY(launch_step_gather(c.mem, c.mem_n, c.layer, ncell, c.hstart, st));
+    a.hstart = c.hstart;
+  }
   if (int rc = launch(D, mech, a, st)) return rc;
+  if (c.mem) {
+    HIP_TRY(hipMemsetAsync(c.mem, 0, (size_t)c.mem_n * sizeof(double), st));
+    LAUNCH_TRY(launch_step_store(c.mem, c.mem_n, c.layer, ncell, c.ierr, c.th, st));
+  }
   if (c.bg || c.bgs) LAUNCH_TRY(launch_budgets(P, ncell, c.var, c.fix, c.rct, dt, c.bg, c.bgs, st));
   LAUNCH_TRY(launch_unpack(P, ncell, c.var, c.s1, c.s3, c.sl1, c.sion1, st));
   return 0;
 }
 
-DriveLayout drive_layout(const MechState& S, int mech, size_t nl, bool bg, bool bgs, bool c_packed) {
+DriveLayout drive_layout(const MechState& S, int mech, size_t nl, bool bg, bool bgs, bool c_packed, bool reuse) {
   const PackTable& T = S.pack.tab;
   DriveLayout L;
   L.nl = nl; L.j1 = (size_t)S.pack.j1; L.j5 = (size_t)S.pack.j5; L.nsl = (size_t)T.j2 * T.nkc; L.nsi = (size_t)T.j6 * T.nkc;
@@ -978,12 +1019,12 @@ DriveLayout drive_layout(const MechState& S, int mech, size_t nl, bool bg, bool 
   L.s1 = B.take(nl * L.j1 * d8); L.s3 = B.take(nl * L.j5 * d8); L.sl1 = B.take(nl * L.nsl * d8); L.si = B.take(nl * L.nsi * d8);
   L.bg = B.take(bg ? nl * 2 * L.nr * d8 : 0); L.bgs = B.take(bgs ? nl * nb * d8 : 0);
   L.io_end = B.end;
-  L.scal = B.take(nl * 6 * d8); L.env = B.take(nl * L.ne * d8);
+  L.scal = B.take(nl * 6 * d8); L.env = B.take(nl * L.ne * d8); L.lyr = B.take(reuse ? nl * sizeof(int32_t) : 0);
   L.in_end = B.end;
   L.th = B.take(nl * 2 * d8); L.hl = B.take(nl * d8); L.ierr = B.take(nl * sizeof(int32_t)); L.stats = B.take(nl * 8 * sizeof(int32_t));
   L.cp = B.take(c_packed ? nl * (L.nv + L.nf) * d8 : 0);
   L.out_end = B.end;
-  L.var = B.take(nl * L.nv * d8); L.fix = B.take(nl * L.nf * d8); L.rct = B.take(nl * L.nr * d8);
+  L.var = B.take(nl * L.nv * d8); L.fix = B.take(nl * L.nf * d8); L.rct = B.take(nl * L.nr * d8); L.hs = B.take(reuse ? nl * d8 : 0);
   L.end = B.end;
   return L;
 }
@@ -1280,11 +1321,17 @@ int mistra_chem_drive_begin(int mech, int nlayer, const int32_t* layer, int n, d
     if (layer[i] < 1 || layer[i] > n) return fail("layer index out of range");
     if (bg && (bg_level[i] < 0)) return fail("bg_level out of range");
   }
-  const DriveLayout L = drive_layout(S, mech, (size_t)nlayer, bg != nullptr, bgs != nullptr, c_packed != nullptr);
+  const bool reuse = g_step_reuse[mech];
+  const DriveLayout L = drive_layout(S, mech, (size_t)nlayer, bg != nullptr, bgs != nullptr, c_packed != nullptr, reuse);
   const size_t nl = L.nl, nb = 2 * (size_t)kBudSlots;
   HIP_TRY(S.drive.ensure(L.end));
   HIP_TRY(S.s_sing.reserve(nl * 8));
   const Staging& A = S.drive;
+  if (reuse && S.step_n != n) {      // first step under reuse, a column of another height, or forgotten: nothing is remembered (the stream is idle: no step is open)
+    HIP_TRY(S.step_mem.reserve((size_t)n));
+    HIP_TRY(hipMemsetAsync(S.step_mem.p, 0, (size_t)n * sizeof(double), A.st));
+    S.step_n = n;
+  }
   // ---- gather the layers (the model arrays hold layer k at stride j1 / j5 / j2*nkc / j6*nkc; bg at stride 2*nrxn per level; bgs at 2*122 per layer)
   for (size_t i = 0; i < nl; i++) {
     const size_t k = (size_t)layer[i] - 1;
@@ -1300,13 +1347,15 @@ int mistra_chem_drive_begin(int mech, int nlayer, const int32_t* layer, int n, d
   }
   std::memcpy(A.h(L.scal), scal, nl * 6 * sizeof(double));
   std::memcpy(A.h(L.env), env, nl * L.ne * sizeof(double));
+  if (reuse) std::memcpy(A.h<int32_t>(L.lyr), layer, nl * sizeof(int32_t));      // (every entry checked above: 1..n)
   HIP_TRY(hipMemcpyAsync(A.dev, A.host, L.in_end, hipMemcpyHostToDevice, A.st));
   // KPP's dummy product species are not set by the drivers; the reference carries over what the previous LAYER left in COMMON /GDATA_x/
   // (INTEGRATION.md §4): a batch gives every layer zeros
   HIP_TRY(hipMemsetAsync(A.d(L.var), 0, nl * L.nv * sizeof(double), A.st));
   const ColumnDev c{A.d(L.s1), A.d(L.s3), A.d(L.sl1), A.d(L.si), A.d(L.scal), A.d(L.env), A.d(L.var), A.d(L.fix), A.d(L.rct),
                     A.d<int32_t>(L.ierr), A.d<int32_t>(L.stats), A.d(L.th), bg ? A.d(L.bg) : nullptr, bgs ? A.d(L.bgs) : nullptr,
-                    c_packed ? A.d(L.cp) : nullptr, A.d(L.hl), S.s_sing.p};
+                    c_packed ? A.d(L.cp) : nullptr, A.d(L.hl), S.s_sing.p,
+                    reuse ? A.d<int32_t>(L.lyr) : nullptr, reuse ? A.d(L.hs) : nullptr, reuse ? S.step_mem.p : nullptr, reuse ? n : 0};
   S.sing_start = 0; S.sing_count = nl; S.sing_one = false;
   if (int rc = column_step(*t.D, mech, nlayer, c, tin, dt, A.st)) return rc;
   HIP_TRY(hipMemcpyAsync(A.host, A.dev, L.io_end, hipMemcpyDeviceToHost, A.st));
@@ -1610,6 +1659,63 @@ int mistra_chem_equil_co(int mech, int nlayer, int nkc, int j6, const double* tt
   return 0;
 }
 
+// ---- OPT-IN step reuse of the batched driver
+
+int mistra_chem_set_step_reuse(int mech, int on) {
+  if (mech < 0 || mech > 2) return fail("unknown mechanism id");
+  std::lock_guard<std::mutex> lock(g_mu);
+  read_step_env();
+  if (g_inited && !g_devs.empty() && g_devs[0].mech[mech].pend.active) return step_is_open(mech);
+  const bool want = on != 0;
+  if (want == g_step_reuse[mech]) return 0;
+  g_step_reuse[mech] = want;
+  for (auto& D : g_devs) D.mech[mech].step_n = 0;      // switched: nothing is remembered
+  return 0;
+}
+
+int mistra_chem_get_step_reuse(int mech) {
+  if (mech < 0 || mech > 2) return 0;
+  std::lock_guard<std::mutex> lock(g_mu);
+  read_step_env();
+  return g_step_reuse[mech] ? 1 : 0;
+}
+
+int mistra_chem_get_step_memory(int mech, int n, double* h) {
+  if (int rc = lazy_init()) return rc;
+  if (int rc = check_call(mech, n)) return rc;
+  if (n == 0) return 0;
+  if (!h) return fail("null host pointer");
+  std::lock_guard<std::mutex> lock(g_mu);
+  Slot t;
+  if (int rc = on_primary(mech, 0, true, &t)) return rc;      // (an open step is still rewriting it)
+  const MechState& S = *t.S;
+  if (S.step_n == 0) {
+    std::memset(h, 0, (size_t)n * sizeof(double));
+    return 0;
+  }
+  if (S.step_n != n) return fail("the step memory of the " + std::string(kMechName[mech]) + " mechanism holds " + std::to_string(S.step_n) + " layers, not " + std::to_string(n));
+  HIP_TRY(hipMemcpy(h, S.step_mem.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mistra_chem_set_step_memory(int mech, int n, const double* h) {
+  if (int rc = lazy_init()) return rc;
+  if (int rc = check_call(mech, n)) return rc;
+  if (n == 0) return fail("mistra_chem_set_step_memory: n must be the model's layer count");
+  if (!h) return fail("null host pointer");
+  for (int i = 0; i < n; i++)
+    if (!(h[i] >= 0.0) || std::isinf(h[i])) return fail("mistra_chem_set_step_memory: step sizes are finite and >= 0 (0 = none)");
+  std::lock_guard<std::mutex> lock(g_mu);
+  Slot t;
+  if (int rc = on_primary(mech, 0, true, &t)) return rc;
+  MechState& S = *t.S;
+  S.step_n = 0;
+  HIP_TRY(S.step_mem.reserve((size_t)n));
+  HIP_TRY(hipMemcpy(S.step_mem.p, h, (size_t)n * sizeof(double), hipMemcpyHostToDevice));      // (no step is open: the drive stream is idle)
+  S.step_n = n;
+  return 0;
+}
+
 int mistra_chem_debug_set_max_steps(int max_steps) {
   std::lock_guard<std::mutex> lock(g_mu);
   g_max_steps = max_steps > 0 ? max_steps : 100000;
@@ -1676,6 +1782,7 @@ int mistra_chem_set_options(int mech, const int32_t* ipar, const double* rpar, c
     if (hipDeviceSynchronize() != hipSuccess) { rc = fail("hipDeviceSynchronize failed"); break; }      // (launches of the device-buffer entries that still read the old block)
     S.opt.release();
     S.opt_max_steps = 0;
+    S.step_n = 0;      // other tolerances or step bounds: the step sizes remembered under the old ones are forgotten
     if (next.set) {
       if (hipError_t e = S.opt.upload(next.block)) { rc = fail(std::string("uploading the options: ") + hipGetErrorString(e)); break; }
       S.opt_max_steps = next.ipar[2];
@@ -1768,7 +1875,7 @@ static int lazy_init() {
 }
 
 static int integrate_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, const double* env, double tin,
-                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h);
+                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart = nullptr);
 
 int mistra_chem_integrate_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                              double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h) {
@@ -1780,8 +1887,14 @@ int mistra_chem_integrate_env_ex(int mech, int ncell, const double* var_in, cons
   return integrate_host(mech, ncell, var_in, fix, nullptr, env, tin, tout, var_out, ierr, stats, t_h);
 }
 
+int mistra_chem_integrate_hstart_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, const double* env, double tin,
+                                    double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart) {
+  if ((rconst != nullptr) == (env != nullptr)) return fail("mistra_chem_integrate_hstart_ex: exactly one of rconst and env");
+  return integrate_host(mech, ncell, var_in, fix, rconst, env, tin, tout, var_out, ierr, stats, t_h, hstart);
+}
+
 static int integrate_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, const double* env, double tin,
-                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h) {
+                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart) {
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, ncell)) return rc;
   if (ncell == 0) return 0;
@@ -1794,7 +1907,7 @@ static int integrate_host(int mech, int ncell, const double* var_in, const doubl
   const int ndev = (int)g_devs.size();
   for (auto& d : g_devs) d.mech[mech].sing_count = 0;
   if (ndev == 1 || ncell < 2 * ndev) {
-    int rc = integrate_host_on(g_devs[0], mech, ncell, var_in, fix, rconst, tin, tout, var_out, ierr, stats, t_h, 0, env);
+    int rc = integrate_host_on(g_devs[0], mech, ncell, var_in, fix, rconst, tin, tout, var_out, ierr, stats, t_h, 0, env, hstart);
     (void)hipSetDevice(g_devs[0].id);
     return rc;
   }
@@ -1810,7 +1923,7 @@ static int integrate_host(int mech, int ncell, const double* var_in, const doubl
     workers.emplace_back([=, &rcs, &errs]() {
       rcs[(size_t)d] = integrate_host_on(g_devs[(size_t)d], mech, count, var_in + start * nv, fix + start * nf, rconst ? rconst + start * nr : nullptr, tin, tout,
                                          var_out + start * nv, ierr ? ierr + start : nullptr, stats ? stats + start * 8 : nullptr, t_h ? t_h + start * 3 : nullptr, start,
-                                         env ? env + start * ne : nullptr);
+                                         env ? env + start * ne : nullptr, hstart ? hstart + start : nullptr);
       if (rcs[(size_t)d]) errs[(size_t)d] = g_err;      // g_err is thread-local: carry the text to the caller's thread
     });
   }

@@ -486,4 +486,34 @@ hipError_t launch_env_from_c(const PackDev& P, int ncell, int nenv, const double
   return hipGetLastError();
 }
 
+// ---- the step memory of the batched driver (pack.hpp): index work on a few hundred doubles, one thread per layer of the batch, one wave per block;
+//      a column's 148 layers are three waves, the last one ragged (the guard below)
+namespace {
+constexpr int kStepNT = 64;
+__global__ __launch_bounds__(kStepNT) void step_gather_kernel(const double* __restrict__ mem, int n, const int32_t* __restrict__ layer, int nlayer,
+                                                              double* __restrict__ hstart) {
+  const int i = blockIdx.x * kStepNT + threadIdx.x;
+  if (i >= nlayer) return;
+  const int k = layer[i];
+  hstart[i] = (k >= 1 && k <= n) ? mem[k - 1] : 0.0;
+}
+__global__ __launch_bounds__(kStepNT) void step_store_kernel(double* __restrict__ mem, int n, const int32_t* __restrict__ layer, int nlayer,
+                                                             const int32_t* __restrict__ ierr, const double* __restrict__ texit_hexit) {
+  const int i = blockIdx.x * kStepNT + threadIdx.x;
+  if (i >= nlayer) return;
+  const int k = layer[i];
+  if (k >= 1 && k <= n && ierr[i] == 1) mem[k - 1] = texit_hexit[2 * (size_t)i + 1];
+}
+}  // namespace
+hipError_t launch_step_gather(const double* mem, int n, const int32_t* layer, int nlayer, double* hstart, hipStream_t stream) {
+  if (nlayer <= 0) return hipSuccess;
+  hipLaunchKernelGGL(step_gather_kernel, dim3((unsigned)((nlayer + kStepNT - 1) / kStepNT)), dim3(kStepNT), 0, stream, mem, n, layer, nlayer, hstart);
+  return hipGetLastError();
+}
+hipError_t launch_step_store(double* mem, int n, const int32_t* layer, int nlayer, const int32_t* ierr, const double* texit_hexit, hipStream_t stream) {
+  if (nlayer <= 0) return hipSuccess;
+  hipLaunchKernelGGL(step_store_kernel, dim3((unsigned)((nlayer + kStepNT - 1) / kStepNT)), dim3(kStepNT), 0, stream, mem, n, layer, nlayer, ierr, texit_hexit);
+  return hipGetLastError();
+}
+
 }  // namespace mistra

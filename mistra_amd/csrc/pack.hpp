@@ -42,6 +42,14 @@ hipError_t launch_budgets(const PackDev& P, int ncell, const double* var, const 
                           double* bgs, hipStream_t stream);
 hipError_t launch_env_from_c(const PackDev& P, int ncell, int nenv, const double* var, const double* fix, double* env, hipStream_t stream);
 
+// ---- the step memory of the batched driver (OPT-IN, include/mistra_chem.h: mistra_chem_set_step_reuse): mem [n] holds, per model layer k = 1..n, the
+//      last accepted step size of the layer's previous column step of this mechanism, 0 = none.  One thread per layer of the batch; layer [nlayer] is
+//      1-based and checked on the host, an entry outside 1..n is skipped all the same.
+// hstart[i] = mem[layer[i] - 1]: the first step sizes of the batch (a.hstart of the integrator: entries <= 0 mean the call's Hstart)
+hipError_t launch_step_gather(const double* mem, int n, const int32_t* layer, int nlayer, double* hstart, hipStream_t stream);
+// mem[layer[i] - 1] = texit_hexit[2 i + 1] where ierr[i] == 1, after the caller has cleared mem on the same stream
+hipError_t launch_step_store(double* mem, int n, const int32_t* layer, int nlayer, const int32_t* ierr, const double* texit_hexit, hipStream_t stream);
+
 }  // namespace mistra
 
 // ---- mass-transfer coefficients (kpp.f90: fast_k_mt_a 2683-2947, fast_k_mt_t 2421-2676; SURVEY.md §8 f3, first slice)

@@ -20,6 +20,12 @@
 !     SUBROUTINE MISTRA_SET_OPTIONS_g / _a / _t (IPAR, RPAR, ATOL, RTOL, IERR)      Rosenbrock_x's own IPAR(20), RPAR(20), AbsTol(NVAR), RelTol(NVAR)
 !     SUBROUTINE MISTRA_CLEAR_OPTIONS_g / _a / _t ()                                 back to INTEGRATE_x's values
 ! IERR = 1, or the code Rosenbrock_x would return for them (gas.f:936-1053): its ros_ErrorMsg_x lines go to unit 6 and the previous options stay.
+!
+! OPT-IN, not the reference's behaviour (include/mistra_chem.h: mistra_chem_set_step_reuse): every layer starts at the last accepted step size of its previous
+! column step of the mechanism instead of Hstart = 1e-3 (gas.f:743).  Call once after start-up, next to MISTRA_SET_OPTIONS_x if that is called:
+!     SUBROUTINE MISTRA_STEP_REUSE_g / _a / _t (ON)                                  ON logical; the single-pass batched driver (KPP_DRIVE_RUN) keeps the steps
+! and for a caller that orders its own batches, the batched form with a first step size per cell (<= 0: the reference's), HEXIT of one call being HSTART of the next:
+!     SUBROUTINE INTEGRATE_BATCH_H_g / _a / _t (NCELL, VAR, FIX, RCONST, TIN, TOUT, HSTART, TEXIT, HEXIT, IERR, ISTAT)
 module mistra_chem_c_api
   use iso_c_binding
   implicit none
@@ -69,6 +75,22 @@ module mistra_chem_c_api
        type(c_ptr), value :: ipar, rpar, atol, rtol, ierr      ! ipar = c_null_ptr clears
        integer(c_int) :: rc
      end function mistra_chem_set_options
+     function mistra_chem_integrate_hstart_ex(mech, ncell, var_in, fix, rconst, env, tin, tout, var_out, ierr, stats, t_h, hstart) &
+          bind(C, name="mistra_chem_integrate_hstart_ex") result(rc)
+       import :: c_int, c_double, c_int32_t, c_ptr
+       integer(c_int), value :: mech, ncell
+       real(c_double), value :: tin, tout
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_out(*), t_h(*)
+       type(c_ptr), value :: env      ! c_null_ptr: rate constants are given
+       real(c_double), intent(in) :: hstart(*)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_integrate_hstart_ex
+     function mistra_chem_set_step_reuse(mech, on) bind(C, name="mistra_chem_set_step_reuse") result(rc)
+       import :: c_int
+       integer(c_int), value :: mech, on
+       integer(c_int) :: rc
+     end function mistra_chem_set_step_reuse
      function mistra_chem_last_error() bind(C, name="mistra_chem_last_error") result(msg)
        import :: c_ptr
        type(c_ptr) :: msg
@@ -172,6 +194,13 @@ contains
          call mistra_chem_fail('MISTRA_CLEAR_OPTIONS_'//sfx)
   end subroutine clear_options
 
+  subroutine step_reuse(mech, sfx, ON)
+    integer, intent(in) :: mech
+    character(len=1), intent(in) :: sfx
+    logical, intent(in) :: ON
+    if (mistra_chem_set_step_reuse(int(mech, c_int), int(merge(1, 0, ON), c_int)) /= 0) call mistra_chem_fail('MISTRA_STEP_REUSE_'//sfx)
+  end subroutine step_reuse
+
   ! the three one-cell routines and the three batched ones differ in sizes only
   subroutine integrate_one(mech, sfx, gdata, TIN, TOUT)
     integer, intent(in) :: mech
@@ -187,10 +216,12 @@ contains
   end subroutine integrate_one
 
   ! use_env: RCONST holds the rate evaluator's inputs (MISTRA_RATES_ENV_x) instead of rate constants: Update_RCONST_x runs on the GPU too
-  subroutine integrate_batch(mech, sfx, NCELL, VAR, FIX, RCONST, TIN, TOUT, TEXIT, HEXIT, IERR, ISTAT, use_env)
+  ! HSTART: a first step size per cell (rate constants only)
+  subroutine integrate_batch(mech, sfx, NCELL, VAR, FIX, RCONST, TIN, TOUT, TEXIT, HEXIT, IERR, ISTAT, use_env, HSTART)
     integer, intent(in) :: mech, NCELL
     character(len=1), intent(in) :: sfx
     logical, intent(in), optional :: use_env
+    real(c_double), intent(in), optional :: HSTART(NCELL)
     logical :: env
     real(c_double) :: VAR(*), FIX(*), RCONST(*), TEXIT(NCELL), HEXIT(NCELL)
     real(c_double), intent(in) :: TIN, TOUT
@@ -201,7 +232,10 @@ contains
     env = .false.
     if (present(use_env)) env = use_env
     allocate (th(3, NCELL))
-    if (env) then
+    if (present(HSTART)) then
+       if (mistra_chem_integrate_hstart_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, c_null_ptr, TIN, TOUT, VAR, IERR, ISTAT, th, HSTART) /= 0) &
+            call mistra_chem_fail('INTEGRATE_BATCH_H_'//sfx)
+    else if (env) then
        if (mistra_chem_integrate_env_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TIN, TOUT, VAR, IERR, ISTAT, th) /= 0) &
             call mistra_chem_fail('INTEGRATE_BATCH_ENV_'//sfx)
     else
@@ -318,6 +352,38 @@ subroutine INTEGRATE_BATCH_t(NCELL, VAR, FIX, RCONST, TIN, TOUT, TEXIT, HEXIT, I
   call integrate_batch(2, 't', NCELL, VAR, FIX, RCONST, TIN, TOUT, TEXIT, HEXIT, IERR, ISTAT)
 end subroutine INTEGRATE_BATCH_t
 
+! ---- OPT-IN: the same with a first step size per cell, HSTART(NCELL) (<= 0: the reference's 1e-3, or RPAR(3) of the options in force); the caller keeps
+!      the steps, HEXIT of one call being HSTART of the next for the same cells
+subroutine INTEGRATE_BATCH_H_g(NCELL, VAR, FIX, RCONST, TIN, TOUT, HSTART, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TIN, TOUT, HSTART(NCELL), TEXIT(*), HEXIT(*)
+  integer(c_int32_t) :: IERR(*), ISTAT(8, *)
+  call integrate_batch(0, 'g', NCELL, VAR, FIX, RCONST, TIN, TOUT, TEXIT, HEXIT, IERR, ISTAT, HSTART=HSTART)
+end subroutine INTEGRATE_BATCH_H_g
+
+subroutine INTEGRATE_BATCH_H_a(NCELL, VAR, FIX, RCONST, TIN, TOUT, HSTART, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TIN, TOUT, HSTART(NCELL), TEXIT(*), HEXIT(*)
+  integer(c_int32_t) :: IERR(*), ISTAT(8, *)
+  call integrate_batch(1, 'a', NCELL, VAR, FIX, RCONST, TIN, TOUT, TEXIT, HEXIT, IERR, ISTAT, HSTART=HSTART)
+end subroutine INTEGRATE_BATCH_H_a
+
+subroutine INTEGRATE_BATCH_H_t(NCELL, VAR, FIX, RCONST, TIN, TOUT, HSTART, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TIN, TOUT, HSTART(NCELL), TEXIT(*), HEXIT(*)
+  integer(c_int32_t) :: IERR(*), ISTAT(8, *)
+  call integrate_batch(2, 't', NCELL, VAR, FIX, RCONST, TIN, TOUT, TEXIT, HEXIT, IERR, ISTAT, HSTART=HSTART)
+end subroutine INTEGRATE_BATCH_H_t
+
 ! ---- the same from the rate evaluator's inputs: Update_RCONST_x + INTEGRATE_x of NCELL layers in one call, RCONST never on the host.
 !   ENV(nenv_x,NCELL): per layer what MISTRA_RATES_ENV_x (mistra_kpp_rates.f90) packs from the COMMON blocks
 subroutine INTEGRATE_BATCH_ENV_g(NCELL, VAR, FIX, ENV, TIN, TOUT, TEXIT, HEXIT, IERR, ISTAT)
@@ -398,3 +464,25 @@ subroutine MISTRA_CLEAR_OPTIONS_t()
   implicit none
   call clear_options(2, 't')
 end subroutine MISTRA_CLEAR_OPTIONS_t
+
+! ---- OPT-IN step reuse of the single-pass batched driver (include/mistra_chem.h: mistra_chem_set_step_reuse): call once after start-up
+subroutine MISTRA_STEP_REUSE_g(ON)
+  use mistra_chem_c_api
+  implicit none
+  logical :: ON
+  call step_reuse(0, 'g', ON)
+end subroutine MISTRA_STEP_REUSE_g
+
+subroutine MISTRA_STEP_REUSE_a(ON)
+  use mistra_chem_c_api
+  implicit none
+  logical :: ON
+  call step_reuse(1, 'a', ON)
+end subroutine MISTRA_STEP_REUSE_a
+
+subroutine MISTRA_STEP_REUSE_t(ON)
+  use mistra_chem_c_api
+  implicit none
+  logical :: ON
+  call step_reuse(2, 't', ON)
+end subroutine MISTRA_STEP_REUSE_t

@@ -20,6 +20,9 @@
 !                                                      sl1(121,4,n) sion1(55,4,n) bg(2,nrxn,nlev) bgs(2,122,n) | per layer: mech, k, air, h2o, env(nenv).
 !                                                      out.bin: the arrays after the step | per layer ierr, 8 statistics, texit, hexit | per repetition
 !                                                      the wall times (ms) of the staging loop and of the device call(s)
+!          shim_driver D2 <in.bin> <out.bin>           the same column step TWICE in a row under step reuse: MISTRA_STEP_REUSE_g/_a/_t(.true.) first, the second
+!                                                      step on the arrays the first one left (tkpp = 10).  in.bin as for D (nrep is not used).  out.bin: the arrays
+!                                                      after the second step | per step and layer: mech, k, ierr, 8 statistics, texit, hexit, H
 !          shim_driver <Ka|Kt|Ha|Ht|Va|Vt|Sa|St|Qa|Qt|Ca|Rg|Ra|Rt> <in.bin> <out.bin>   liq_parm's kernels through shim/mistra_kpp_liq.f90 (SURVEY §8 f3): K = FAST_K_MT_BATCH
 !                                                      (in: nlayer, nka, nkt, nkc, nspec, ka, ifeed, nkc_l | kw | rq | ff cw cm freep alpha vmean xkmt t p vt;
 !                                                      out: xkmt, vt), H = HENRY_BATCH (in: nlayer, nspec | tt; out: henry), V = V_MEAN_BATCH (the same shapes; out: vmean), S = ST_COEFF_BATCH (in: nlayer, nspec, lpJoyce14bc, lpBuxmann15alph | env(5,nlayer); out: alpha), R = DRY_RATES_BATCH (in: nlayer | tt, freep, rcd(2,nlayer), vmean4 / henry4 (4,nlayer); out: xkmtd, xeq, henry4), C = CW_RC_BATCH (in: nlayer, nkt, nka, dry, ka, ifeed | kw, rq, e, crys4, ff, feu, cloud; out: rc, cw, cm, conv2, below), Q = EQUIL_CO_BATCH (in: nlayer,
@@ -39,7 +42,7 @@ program shim_driver
   case ('G'); call run_batch(0, 102, 3, 331, trim(fin), trim(fout))
   case ('A'); call run_batch(1, 257, 5, 979, trim(fin), trim(fout))
   case ('T'); call run_batch(2, 417, 7, 1627, trim(fin), trim(fout))
-  case ('D'); call run_drive(trim(fin), trim(fout))
+  case ('D'); call run_drive(trim(fin), trim(fout), a1(2:2) == '2')
   case ('O')
      select case (a1(2:2))
      case ('G'); call run_batch(0, 102, 3, 331, trim(fin), trim(fout), .true.)
@@ -315,9 +318,10 @@ contains
     call CW_RC_BATCH(nl, nkt, nka, dry, ff, rq, e, kw, ka, ifeed, feu, cloud, crys4, rc, cw, cm, conv2, below)
     write (12) rc, cw, cm, conv2, dble(below)
   end subroutine run_cw_rc
-  subroutine run_drive(fin, fout)
+  subroutine run_drive(fin, fout, twice)
     use mistra_kpp_drive
     character(len=*), intent(in) :: fin, fout
+    logical, intent(in) :: twice      ! two consecutive steps under step reuse instead of nrep repetitions of one
     integer, parameter :: j2 = 121, j6 = 55, nkc = 4, nbgs = 122      ! global_params.f90:96-103, bud_s_g.f:63
     integer, parameter :: nenv(3) = [nenv_g, nenv_a, nenv_t]
     double precision :: hdr(7)
@@ -325,8 +329,11 @@ contains
     integer, allocatable :: gm(:, :, :), gk(:, :), rm(:, :, :), rk(:, :), il(:), lmech(:), lk(:)
     double precision, allocatable :: tmp(:), s1(:, :), s3(:, :), sl1(:, :, :), sion1(:, :, :), bg(:, :, :), bgs(:, :, :), lscal(:, :), lenv(:, :)
     double precision, allocatable :: s1_0(:, :), s3_0(:, :), sl1_0(:, :, :), sion1_0(:, :, :), bg_0(:, :, :), bgs_0(:, :, :), times(:, :)
-    double precision :: texit, hexit
+    double precision :: texit, hexit, hlast, tkpp
+    double precision, allocatable :: steps(:, :, :)
+    integer :: j
     integer(8) :: c0, c1, c2, rate
+    external :: MISTRA_STEP_REUSE_g, MISTRA_STEP_REUSE_a, MISTRA_STEP_REUSE_t
     external :: MISTRA_RATES_ENV_SET_g, MISTRA_RATES_ENV_SET_a, MISTRA_RATES_ENV_SET_t, KPP_DRIVE_STAGE_g, KPP_DRIVE_STAGE_a, KPP_DRIVE_STAGE_t
     open (11, file=fin, access='stream', form='unformatted', status='old')
     open (12, file=fout, access='stream', form='unformatted', status='replace')
@@ -352,8 +359,16 @@ contains
     do m = 1, 3      ! once per run, as KPP_DRIVE_RUN does on its first call (here only for the mechanisms the recorded step has layers of: the
        if (any(lmech == m)) call kpp_drive_maps(m, j1, gm(:, :, m), gk(:, m), j5, rm(:, :, m), rk(:, m))      ! file holds real maps only for those)
     end do
+    if (twice) then
+       nrep = 2
+       deallocate (times); allocate (times(2, nrep), steps(14, nl, nrep))
+       call MISTRA_STEP_REUSE_g(.true.); call MISTRA_STEP_REUSE_a(.true.); call MISTRA_STEP_REUSE_t(.true.)
+    end if
     do rep = 1, nrep      ! (the first repetition pays the library's start-up and the first allocation of the staging blocks)
-       s1 = s1_0; s3 = s3_0; sl1 = sl1_0; sion1 = sion1_0; bg = bg_0; bgs = bgs_0
+       if (.not. twice .or. rep == 1) then
+          s1 = s1_0; s3 = s3_0; sl1 = sl1_0; sion1 = sion1_0; bg = bg_0; bgs = bgs_0
+       end if
+       tkpp = merge(10.d0 * dble(rep - 1), 0.d0, twice)
        call system_clock(c0, rate)
        call kpp_drive_begin
        do i = 1, nl       ! kpp_driver's layer loop: per-layer set-up and the x_drive prologue (here: the recorded values back into the COMMON blocks), then the hand-over
@@ -364,12 +379,27 @@ contains
           end select
        end do
        call system_clock(c1)
-       call kpp_drive_run_arrays(0.d0, 10.d0, n, s1, s3, sl1, sion1, nrxn, nlev, il, bg, bgs)
+       call kpp_drive_run_arrays(tkpp, 10.d0, n, s1, s3, sl1, sion1, nrxn, nlev, il, bg, bgs)
        call system_clock(c2)
        times(1, rep) = 1.d3 * dble(c1 - c0) / dble(rate)
        times(2, rep) = 1.d3 * dble(c2 - c1) / dble(rate)
+       if (twice) then      ! per mechanism in staging order, as below
+          j = 0
+          do m = 1, 3
+             do i = 1, kpp_drive_count(m)
+                j = j + 1
+                call kpp_drive_last(m, i, k, ierr, istat, texit, hexit, hlast)
+                steps(:, j, rep) = [dble(m), dble(k), dble(ierr), dble(istat), texit, hexit, hlast]
+             end do
+          end do
+       end if
     end do
     write (12) s1, s3, sl1, sion1, bg, bgs
+    if (twice) then
+       write (12) steps
+       close (11); close (12)
+       return
+    end if
     do m = 1, 3           ! per mechanism in staging order (= layer order within the mechanism)
        cnt = kpp_drive_count(m)
        do i = 1, cnt
