@@ -170,6 +170,10 @@ int mistra_chem_singular_rows(int mech, int cell, int32_t* rows8);
  * device buffers on a HIP stream.  The lazy initialisation of the Fortran-facing entry points applies to the host-buffer
  * form. */
 int mistra_chem_rates_env_size(int mech);
+/* The deepest operand stack any postfix program of a rate table (<mech>.rates; stcoeff = 0) or of a table of accommodation coefficients
+ * (<mech>.stcoeff; stcoeff = 1) needs, read by the loader the library itself uses; needs no device.  -1 where that loader refuses the file
+ * (mistra_chem_last_error() says why): the evaluator's stack holds 12 entries per thread, a table with a deeper program is not loaded. */
+int mistra_chem_table_stack_depth(const char* path, int stcoeff);
 int mistra_chem_update_rconst(int mech, int ncell, const double* env, double* rconst);
 int mistra_chem_update_rconst_device(int mech, int ncell, const double* d_env, double* d_rconst, void* hip_stream);
 

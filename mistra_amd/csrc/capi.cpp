@@ -79,11 +79,45 @@ struct DevBuf {
 
 }  // namespace
 
+int mistra::rates_stack_depth(const RatesTable& T) {
+  if (T.nreact < 0 || T.offs.size() != (size_t)T.nreact + 1) return -1;
+  int deepest = 0;
+  for (int r = 0; r < T.nreact; r++) {
+    const int32_t w0 = T.offs[(size_t)r], w1 = T.offs[(size_t)r + 1];
+    if (w0 < 0 || w1 < w0 || (size_t)w1 > T.words.size()) return -1;
+    int sp = 0;
+    for (int32_t w = w0; w < w1; w++) {
+      const int op = T.words[(size_t)w] & 0xFF, arg = T.words[(size_t)w] >> 8;
+      if (op <= 1) sp++;                                             // literal, input
+      else if (op <= 5) { if (sp < 2) return -1; sp--; }             // + - * /
+      else if (op == 6) { if (sp < 1) return -1; }                   // neg
+      else if (op == 7 && arg >= 0 && arg < (int)(sizeof kRatesCallArgs / sizeof kRatesCallArgs[0])) {
+        if (sp < kRatesCallArgs[arg]) return -1;
+        sp += 1 - kRatesCallArgs[arg];
+      } else return -1;
+      if (sp > deepest) deepest = sp;
+    }
+    if (sp != 1) return -1;
+  }
+  return deepest;
+}
+
+namespace {
+// the evaluator's operand stack is a fixed LDS column per thread: a deeper program would write past it
+bool stack_fits(mistra::RatesTable& T, const std::string& path, std::string* err) {
+  T.depth = mistra::rates_stack_depth(T);
+  if (T.depth > mistra::kRatesStackDepth && err)
+    *err = path + ": a program needs " + std::to_string(T.depth) + " operand-stack entries, the evaluator holds " + std::to_string(mistra::kRatesStackDepth);
+  return T.depth <= mistra::kRatesStackDepth;
+}
+}  // namespace
+
 bool mistra::RatesTable::load(const std::string& path, std::string* err) {
   FILE* f = std::fopen(path.c_str(), "rb");
   if (!f) { if (err) *err = "cannot open " + path; return false; }
   int32_t h[8];
   bool ok = std::fread(h, sizeof h, 1, f) == 1 && h[0] == 0x5441524B && h[1] == 2;
+  depth = 0;
   if (ok) {
     nreact = h[2]; nenv = h[3];
     consts.resize((size_t)h[4]); offs.resize((size_t)nreact + 1); words.resize((size_t)h[5]); fslot.resize((size_t)h[6]);
@@ -92,6 +126,10 @@ bool mistra::RatesTable::load(const std::string& path, std::string* err) {
   }
   std::fclose(f);
   if (!ok && err) *err = path + ": not a rate table";
+  if (ok) {
+    ok = stack_fits(*this, path, err);
+    if (ok && depth < 0) { ok = false; if (err) *err = path + ": not a rate table (a program does not leave exactly one result)"; }
+  }
   return ok;
 }
 
@@ -119,6 +157,11 @@ bool mistra::StcoeffTable::load(const std::string& path, std::string* err) {
   }
   std::fclose(f);
   if (!ok && err) *err = path + ": not a table of accommodation coefficients";
+  for (int i = 0; ok && i < 4; i++) {
+    ok = stack_fits(v[i], path, err);
+    if (ok && v[i].depth < 0) { ok = false; if (err) *err = path + ": not a table of accommodation coefficients (a program does not leave exactly one result)"; }
+    if (!ok) v[0].depth = v[i].depth;      // (setup_mech asks the first table why the file was refused)
+  }
   return ok;
 }
 
@@ -673,6 +716,8 @@ int setup_mech(DeviceState& D, int mech) {
   if (R.load(base + ".rates", &err)) {      // (gas today)
     if (R.nreact != S.tab.nreact) return fail(name + ".rates does not belong to this mechanism");
     if (int rc = S.rates.upload(R)) return rc;
+  } else if (R.depth > kRatesStackDepth) {
+    return fail(err);      // (a missing table is a mechanism without the routine; a table the evaluator cannot run is an error)
   }
   if (S.pack.tab.load(base + ".pack", &err)) {      // the drivers' hand-over tables
     const PackTable& T = S.pack.tab;
@@ -695,6 +740,8 @@ int setup_mech(DeviceState& D, int mech) {
   if (S.stc.tab.load(base + ".stcoeff", &err)) {      // accommodation coefficients (aer, tot)
     if (S.stc.tab.v[0].nreact != nspec) return fail(name + ".stcoeff does not belong to this mechanism");
     if (int rc = S.stc.upload()) return rc;
+  } else if (S.stc.tab.v[0].depth > kRatesStackDepth) {
+    return fail(err);
   }
   if (S.vmean.tab.load(base + ".vmean", &err)) {      // mean molecular speeds (aer, tot)
     if (S.vmean.tab.nspec != nspec) return fail(name + ".vmean does not belong to this mechanism");
@@ -1168,6 +1215,24 @@ int mistra_chem_integrate_device_hstart(int mech, int ncell, const double* d_var
   KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, tin, tout, d_var_out, d_ierr, d_stats, d_texit_hexit);
   a.hstart = d_hstart;
   return launch(*t.D, mech, a, static_cast<hipStream_t>(hip_stream));
+}
+
+int mistra_chem_table_stack_depth(const char* path, int stcoeff) {
+  if (!path) return fail("null path"), -1;
+  std::string err;
+  int depth = 0;
+  bool ok;
+  if (stcoeff) {
+    StcoeffTable T;
+    ok = T.load(path, &err);
+    for (int i = 0; ok && i < 4; i++) depth = T.v[i].depth > depth ? T.v[i].depth : depth;
+  } else {
+    RatesTable T;
+    ok = T.load(path, &err);
+    depth = T.depth;
+  }
+  if (!ok) return fail(err), -1;
+  return depth;
 }
 
 int mistra_chem_rates_env_size(int mech) {

@@ -29,7 +29,9 @@ constexpr double kTenPowM616 = 6.91831189669755986e-07; // 10**(-6.16): INTEGER 
 
 struct Cb1 { double aircc, te, h2oppm, pk; };           // COMMON /cb_1/ (kpp.f90:7140)
 
-__device__ __forceinline__ double fmax_fortran(double a, double b) { return (a > b || b != b) ? a : b; }
+// MAX(a, b) as the reference's compiler makes it: a select on a > b.  A NaN in b comes through (fdhet*'s max(0.d0, x1+x2) is NaN), a NaN in a
+// does not (uplim's max(c, 0.d0) is 0 for c = NaN): both are in tests/golden/rates_edges_<mech>.npz from the compiled reference
+__device__ __forceinline__ double fmax_fortran(double a, double b) { return a > b ? a : b; }
 
 // kpp.f90:7127  farr=a*exp(b/te), b INTEGER
 __device__ double farr(const Cb1& c, double a, double b) { return a * exp(b / c.te); }
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(256) void update_rconst_kernel(const RatesDev R, co
   constexpr double dclim = 1.0e10;      // the reaction-rate ceiling of dmin2 / uplim / uparm / uplip / uparp
   // operand stack of the postfix programs: one LDS column per thread (a private array indexed by the stack pointer would live in
   // scratch memory: a global round trip per push and pop)
-  __shared__ double stack_cells[12][256];
+  __shared__ double stack_cells[kRatesStackDepth][256];      // (the loaders hold every program to this depth: rates_stack_depth)
 #define st_at(i) stack_cells[(i)][threadIdx.x]
   for (int r = r_begin; r < r_end; r++) {
   int sp = 0;

@@ -16,8 +16,15 @@ struct RatesDev {              // device copy of one mechanism's table
   int nreact, nenv;            // reactions; doubles per cell in the input vector ("env", layout: tools/extract_rates.py ENV)
 };
 
+// Operand-stack entries per thread of the device evaluator (update_rconst_kernel: one LDS column of this many doubles per thread).  The deepest
+// program of the shipped tables needs 7 (rates) or 8 (st_coeff); the loaders refuse a table that needs more.
+constexpr int kRatesStackDepth = 12;
+// arguments each function id of a call word takes off the stack (the call switch of update_rconst_kernel)
+constexpr int kRatesCallArgs[29] = {2, 4, 5, 5, 6, 7, 6, 6, 2, 6, 1, 0, 2, 2, 3, 5, 4, 1, 1, 3, 3, 2, 4, 5, 3, 4, 1, 4, 2};
+
 struct RatesTable {
   int nreact = 0, nenv = 0;
+  int depth = 0;               // deepest operand stack of any program (rates_stack_depth), set by load
   std::vector<double> consts;
   std::vector<int32_t> offs, words, fslot;
   bool load(const std::string& path, std::string* err);
@@ -29,6 +36,10 @@ struct StcoeffTable {
   RatesTable v[4];
   bool load(const std::string& path, std::string* err);
 };
+
+// deepest operand stack any program of T needs; -1 where a program is not one (words outside the table, an unknown word, a pop from an empty
+// stack, not exactly one result left)
+int rates_stack_depth(const RatesTable& T);
 
 hipError_t launch_update_rconst(const RatesDev& R, const double* d_env, double* d_rconst, int ncell, hipStream_t stream);
 

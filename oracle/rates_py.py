@@ -40,7 +40,17 @@ class E(list):
 
 
 def _fmax(a, b):
-    return a if (a > b or b != b) else b
+    """MAX(a, b) as flang compiles it: a select on a > b, so a NaN in b comes through (MAX(0.d0, NaN) is NaN) and a NaN in a does not (MAX(NaN, 0.d0) is 0);
+    tests/golden/rates_edges_<mech>.npz holds both from the compiled reference"""
+    return a if a > b else b
+
+
+def _div(a, b):
+    """a / b as the hardware divides (Python raises where IEEE 754 returns an infinity or a NaN)"""
+    try:
+        return a / b
+    except ZeroDivisionError:
+        return math.nan if (a != a or a == 0.0) else math.copysign(math.inf, a) * math.copysign(1.0, b)
 
 
 def _fdhet(e, na, nb):      # fdhetg | fdheta | fdhett (kpp.f90:8198, 8269, 8311)
@@ -54,7 +64,7 @@ def _fdhet(e, na, nb):      # fdhetg | fdheta | fdhett (kpp.f90:8198, 8269, 8311
             if (e.at("YXEQ_HNO3") + 1.0e-2) != 0.0:
                 caq = ((e.at("C_HNO3L", na - 1) + e.at("C_NO3ML", na - 1)) * 1.0e-2) / (e.at("YXEQ_HNO3") + 1.0e-2)
         else:
-            caq = ((e.at("C_HNO3L", na - 1) * 1.5e3) * 1.0e-2) / (e.at("YXEQ_HNO3") + 1.0e-2)
+            caq = _div((e.at("C_HNO3L", na - 1) * 1.5e3) * 1.0e-2, e.at("YXEQ_HNO3") + 1.0e-2)      # (no guard in fdhetg: yxeq = -1e-2 divides by 0)
         x2 = 0.0
         if e.at("C_HNO3") != 0.0 and e.at("YHENRY_HNO3") != 0.0:
             x2 = ((-yx) / (e.at("C_HNO3") * e.at("YHENRY_HNO3"))) * caq
@@ -215,7 +225,7 @@ def evaluate(table, slot, env, fslot=None):
                 st.append(FUNCS[t[1]](env, *args))
             else:
                 b, a = st.pop(), st.pop()
-                st.append(a + b if k == "+" else a - b if k == "-" else a * b if k == "*" else a / b)
+                st.append(a + b if k == "+" else a - b if k == "-" else a * b if k == "*" else _div(a, b))
         assert len(st) == 1
         out[r] = st[0]
     return out

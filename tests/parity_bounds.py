@@ -174,3 +174,15 @@ def reject_case_inputs(name):
 # which this measure does not move — argument roundings are the same operations on both sides.)  vt: Beard's polynomial sits between a log and an exp.
 LIQ_SYNTH_FLOOR = 1e-14            # what tests/test_gpu_liq.py, tests/test_gpu_kmt.py (vt) and tests/test_gpu_rates.py (st_coeff) hold on the captured layers
 LIQ_SYNTH_RTOL = {"henry": LIQ_SYNTH_FLOOR, "equil_co": LIQ_SYNTH_FLOOR, "dry_rates": LIQ_SYNTH_FLOOR, "st_coeff": LIQ_SYNTH_FLOOR, "vt": 1.3e-14}
+
+
+# ---- G. the rate evaluator on the edge cases of tests/rates_cases.py (tests/test_gpu_rates_edges.py), in the programs that hold a call of a rate law
+# with exp, pow or log10 in it (rates_cases.LIBRARY_LAWS; every other program is compared bit for bit).  Spread: the worst relative movement of the
+# restatement itself (oracle/rates_py.py) over those cases when exp, pow and log10 return the next double up, or down (liq_cases.MathShim), NaN,
+# infinite and exactly-zero entries left out (the GPU test holds those patterns equal), measured by
+# tests/test_rates_cases.py::test_bound_of_the_device_comparison_follows_the_restatements_own_movement.  Bound = max(RATES_EDGES_FLOOR, 10 x spread).
+#   measured (CPU):  gas 5.93e-16 (1 987 entries)  aer 8.07e-16 (8 923)  tot 8.07e-16 (14 185)
+# (180-330 K against the 220-310 K of the seeded fixture; the Troe laws chain two pow, a log10 and a pow.)  No entry cancels: the comparison leaves
+# none to a looser bound.
+RATES_EDGES_FLOOR = 1e-13          # what tests/test_gpu_rates.py holds on the seeded and the captured vectors
+RATES_EDGES_RTOL = {"gas": RATES_EDGES_FLOOR, "aer": RATES_EDGES_FLOOR, "tot": RATES_EDGES_FLOOR}

@@ -105,3 +105,67 @@ def test_generated_sources_are_up_to_date(tool):
     import sys
     r = subprocess.run([sys.executable, os.path.join(REPO, "tools", tool), "--check"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+def _read_tables(path, count):
+    """`count` tables of the 'KRAT' v2 format back to back (a .rates file holds one, a .stcoeff file four) -> [(header, consts, offs, words, fslot)]"""
+    raw = open(path, "rb").read()
+    off, out = 0, []
+    for _ in range(count):
+        h = np.frombuffer(raw, np.int32, 8, off).copy()
+        off += 32
+        parts = []
+        for dt, n in ((np.float64, h[4]), (np.int32, h[2] + 1), (np.int32, h[5]), (np.int32, h[6])):
+            parts.append(np.frombuffer(raw, dt, int(n), off).copy())
+            off += int(n) * np.dtype(dt).itemsize
+        out.append((h, *parts))
+    assert off == len(raw)
+    return out
+
+
+def _write_tables(path, tables):
+    with open(path, "wb") as f:
+        for h, consts, offs, words, fslot in tables:
+            h = h.copy()
+            h[4], h[5] = len(consts), len(words)
+            for a, dt in ((h, np.int32), (consts, np.float64), (offs, np.int32), (words, np.int32), (fslot, np.int32)):
+                f.write(np.ascontiguousarray(a, dt).tobytes())
+
+
+def _with_first_program(table, pushes):
+    """the table with its first program replaced by `pushes` literals summed up: that program needs `pushes` operand-stack entries"""
+    h, consts, offs, words, fslot = table
+    prog = np.array([0] * pushes + [2] * (pushes - 1), np.int32)      # word = opcode | operand << 8: literal 0, pushes times; then +
+    old = offs[1] - offs[0]
+    return (h, consts, np.concatenate([offs[:1], offs[1:] + (len(prog) - old)]), np.concatenate([prog, words[old:]]), fslot)
+
+
+@pytest.mark.parametrize("kind", ["rates", "stcoeff"])
+def test_loader_refuses_a_table_deeper_than_the_evaluators_stack(lib, tmp_path, kind):
+    """The device evaluator keeps its operand stack in a fixed column of kRatesStackDepth = 12 doubles per thread (mistra_amd/csrc/rates.hpp); a program
+    that pushes a thirteenth would write into the next column.  The library's own loaders (RatesTable::load, StcoeffTable::load, reached without a
+    device through mistra_chem_table_stack_depth) take a crafted table whose first program needs 12 entries and refuse one that needs 13."""
+    lib.mistra_chem_table_stack_depth.argtypes = [C.c_char_p, C.c_int]
+    mech, count = ("gas", 1) if kind == "rates" else ("aer", 4)
+    shipped = os.path.join(REPO, "mistra_amd", "mech", "%s.%s" % (mech, kind))
+    tables = _read_tables(shipped, count)
+    assert lib.mistra_chem_table_stack_depth(shipped.encode(), count == 4) == (7 if kind == "rates" else 8)
+    for which in range(count):
+        for pushes, accepted in ((12, True), (13, False)):
+            path = str(tmp_path / ("%d_%d.%s" % (which, pushes, kind)))
+            _write_tables(path, [_with_first_program(t, pushes) if i == which else t for i, t in enumerate(tables)])
+            got = lib.mistra_chem_table_stack_depth(path.encode(), count == 4)
+            if accepted:
+                assert got == 12, lib.mistra_chem_last_error()
+            else:
+                assert got == -1
+                msg = lib.mistra_chem_last_error().decode()
+                assert "needs 13 operand-stack entries" in msg and "holds 12" in msg and path in msg
+    # a program that pops from an empty stack, or leaves two results, is no program
+    h, consts, offs, words, fslot = tables[0]
+    for bad in (np.array([2], np.int32), np.array([0, 0], np.int32)):
+        old = offs[1] - offs[0]
+        t = (h, consts, np.concatenate([offs[:1], offs[1:] + (len(bad) - old)]), np.concatenate([bad, words[old:]]), fslot)
+        path = str(tmp_path / ("bad." + kind))
+        _write_tables(path, [t] + tables[1:])
+        assert lib.mistra_chem_table_stack_depth(path.encode(), count == 4) == -1

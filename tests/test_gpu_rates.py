@@ -4,7 +4,8 @@ and the rate laws of kpp.f90 through oracle/_ref/libmistra_ref.so, recorded by t
 
 Tolerance: the table and the evaluation order are the reference's (tests/test_rates.py reproduces it bit for bit with the
 host libm); the device's exp / pow / log10 differ from the host's in the last place, and a rate law chains up to five of
-them, so: exact where no transcendental is involved (switches, literals, photolysis rates), 1e-13 relative elsewhere."""
+them, so: exact where no transcendental is involved (switches, literals, photolysis rates, and the rate laws that are comparisons and + - * / only:
+rates_cases.LIBRARY_LAWS lists the others), 1e-13 relative elsewhere."""
 import os
 
 import numpy as np
@@ -41,6 +42,10 @@ def test_device_rate_constants_match_the_reference(chem, mech):
     table = json.load(open(os.path.join(REPO, "mistra_amd", "mech", mech + ".rates.json")))
     plain = np.array([not any(t[0] == "call" for t in p) for p in table["programs"]])
     assert plain.sum() > 100 and np.array_equal(got[:, plain], want[:, plain])
+    # ... and so are the reactions whose calls are all library-free (the guards, clamps and switches of fdhet*, fhet_*, flsc4/5/6, dmin2/3, uplim, uplip, sp_17)
+    import rates_cases
+    exact = ~rates_cases.program_kinds(mech)[2]
+    assert exact.sum() > plain.sum() and np.array_equal(got[:, exact], want[:, exact])
 
 
 @pytest.mark.parametrize("mech", ["gas", "aer", "tot"])
@@ -55,6 +60,9 @@ def test_model_captured_calls_on_the_device(chem, mech):
     rel = np.abs(got[nz] - want[nz]) / np.abs(want[nz])
     print("%s RCONST of %d model layers on the device: %.1f %% bit-identical, max rel diff %.2e" % (mech, len(want), 100 * float((got[nz] == want[nz]).mean()), rel.max()))
     assert rel.max() <= 1e-13
+    import rates_cases
+    exact = ~rates_cases.program_kinds(mech)[2]      # no call, or library-free calls only: bit for bit
+    assert np.array_equal(got[:, exact], want[:, exact])
 
 
 @pytest.mark.parametrize("mech", ["gas", "aer", "tot"])
