@@ -237,6 +237,28 @@ class Reference:
         getattr(self.lib, "update_rconst_%s_" % sfx)()
         return np.ctypeslib.as_array(self.gdata.rconst).copy()
 
+    BUD = {"gas": ("bud_gas_", "bud_s_gas_"), "aer": ("bud_aer_", "bud_s_aer_"), "tot": ("bud_tot_", "bud_s_tot_")}
+    NRXN, NLEV, NBGS, N = 1627, 15, 122, 150      # global_params.f90: nrxn, nlev, n; bud_s_g.f:63
+
+    def budgets(self, C_, rconst, dt, bg_in, bgs_in):
+        """bud_x (bud_g.f | bud_a.f | bud_t.f) and bud_s_x (bud_s_g.f | bud_s_a.f | bud_s_t.f) of the compiled reference on one state: fills C and RCONST
+        of COMMON /GDATA_x/, level 1 of COMMON /budg/ bg(2,nrxn,nlev),il(nlev) and layer 1 of COMMON /budgs/ bgs(2,122,n) with what the caller holds, calls
+        both routines (dtg, kl | k by reference) -> (bg [NREACT][2], bgs [122][2]) as they left them."""
+        g = self.gdata
+        np.ctypeslib.as_array(g.c)[:] = np.asarray(C_, np.float64).reshape(self.nvar + self.nfix)
+        np.ctypeslib.as_array(g.rconst)[:] = np.asarray(rconst, np.float64).reshape(self.nreact)
+        bg = np.ctypeslib.as_array((C.c_double * (2 * self.NRXN * self.NLEV)).in_dll(self.lib, "budg_")).reshape(self.NLEV, self.NRXN, 2)
+        bgs = np.ctypeslib.as_array((C.c_double * (2 * self.NBGS * self.N)).in_dll(self.lib, "budgs_")).reshape(self.N, self.NBGS, 2)
+        bg[0] = 0.0
+        bg[0, :self.nreact] = np.asarray(bg_in, np.float64).reshape(self.nreact, 2)
+        bgs[0] = np.asarray(bgs_in, np.float64).reshape(self.NBGS, 2)
+        d, one = C.c_double(dt), C.c_int32(1)
+        bud, bud_s = self.BUD[self.mech]
+        getattr(self.lib, bud)(C.byref(d), C.byref(one))
+        getattr(self.lib, bud_s)(C.byref(d), C.byref(one))
+        assert d.value == dt and one.value == 1
+        return bg[0, :self.nreact].copy(), bgs[0].copy()
+
     def integrate(self, var, fix, rconst, tin=0.0, tout=10.0):
         g = self.gdata
         np.ctypeslib.as_array(g.c)[:self.nvar] = var

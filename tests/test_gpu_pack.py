@@ -119,11 +119,14 @@ def test_clamps_keep_minus_zero_and_nan_like_the_compiled_max(chem, mech):
         assert same(tl.cpu().numpy()[0], want_l) and same(ti.cpu().numpy()[0], want_i), "clamped model arrays"
     # hand-over of a state with -0.0 / NaN / negative liquid-phase species
     c_out = g["c_out"][0].copy()
-    lst = sorted({c for _, _, _, c, cl in tab["unpack"] if cl})
-    if lst:
-        c_out[np.array(lst[0::3]) - 1] = -0.0
-        c_out[np.array(lst[1::3]) - 1] = np.nan
-        c_out[np.array(lst[2::3]) - 1] = -2.0e-12
+    # which hand-over is clamped at all: gas_drive's, every entry of it; aer_drive / tot_drive clamp sl1 / sion1 on the way IN and hand over plain
+    # copies (tests/test_drive_cases.py holds the tables to this) — for them this half checks the copy; their edge hand-over is tests/test_gpu_drive_edges.py's
+    import drive_cases
+    lst = np.array(drive_cases.handover_clamped(mech), np.int64)
+    assert lst.size == (len(tab["unpack"]) if mech == "gas" else 0), "%s: %d clamped hand-over entries" % (mech, lst.size)
+    c_out[lst[0::3] - 1] = -0.0
+    c_out[lst[1::3] - 1] = np.nan
+    c_out[lst[2::3] - 1] = -2.0e-12
     ws1, ws3, wl, wi = pack_py.unpack(tab, c_out, g["s1_in"][0], g["s3_in"][0], want_l, want_i, g["gas_k2m"], g["rad_k2m"])
     s1, s3 = T(g["s1_in"][:1]), T(g["s3_in"][:1])
     chem.unpack(mech, T(c_out[None, :nv]), s1, s3, tl, ti)
