@@ -128,7 +128,8 @@ int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, doub
  *                     0.9, < 0: IERR -4.
  *   atol, rtol        AbsTol <= 0, RelTol <= 10 eps or RelTol >= 1 in an entry that is read: IERR -5.
  * Only Ros3 (ipar[3] = 2) is built: the four other valid methods are refused by the library (non-zero return), which is not a code
- * of Rosenbrock_x's.  One vector pair per call, shared by all cells, as in KPP.  A per-cell first step size of
+ * of Rosenbrock_x's; Ros2, Ros4, Rodas3 and Rodas4 run through mistra_chem_rosenbrock_ex / _device below, whose options travel with the
+ * call.  One vector pair per call, shared by all cells, as in KPP.  A per-cell first step size of
  * mistra_chem_integrate_device_hstart, of mistra_chem_integrate_hstart_ex or remembered under mistra_chem_set_step_reuse still goes before rpar[2]; ipar[2] /= 0 goes before mistra_chem_debug_set_max_steps.
  *
  * mistra_chem_check_options: the decode alone, pure host arithmetic, works before init.  *ierr = 1, or the IERR Rosenbrock_x would return
@@ -151,6 +152,41 @@ int mistra_chem_set_options(int mech, const int32_t* ipar, const double* rpar, c
  * atol[NVAR], rtol[NVAR] as the integrator uses them (scalar tolerances: entry 1 repeated); each of the four may be NULL.  These are also what
  * mistra_chem_integrate_common(_status) leaves in ATOL / RTOL of COMMON /GDATA_x/ while options are set. */
 int mistra_chem_get_options(int mech, int32_t* is_set, int32_t* ipar, double* rpar, double* atol, double* rtol);
+
+/* Rosenbrock_x(Y,Tstart,Tend,AbsTol,RelTol,RPAR,IPAR,IERR) (gas.f:777 | aer.f | tot.f) for ncell cells, with ALL FIVE methods: ipar[3] = 1 Ros2,
+ * 2 Ros3, 3 Ros4, 4 Rodas3, 5 Rodas4, 0 = Ros4 as in the reference (gas.f:1057-1077).  The options are the call's own: ipar[20], rpar[20],
+ * atol, rtol as described above (one vector pair shared by all cells; atol[0], rtol[0] alone unless ipar[1] = 0), decoded as Rosenbrock_x decodes
+ * them.  The options in force (mistra_chem_set_options) are neither read nor changed, step reuse is not involved; ipar[2] /= 0 goes before
+ * mistra_chem_debug_set_max_steps.  Ros3 runs the options kernel of mistra_chem_set_options (bit-identical results), each other method a kernel
+ * of its own per mechanism, compiled from the tables mistra_chem_method_table returns.
+ *
+ * A refusal by Rosenbrock_x is a RESULT, not a failure of the call: for IERR -1 .. -5 every cell's ierr is the code, var_out = var_in, stats
+ * and t_h are zero, the call returns 0 and no kernel is launched — Rosenbrock_x returns before it touches Y (gas.f:936-1053).
+ *
+ * mistra_chem_rosenbrock_ex: host buffers, laid out as mistra_chem_integrate_ex's (t_h[ncell][3] = Texit, Hexit, H; ierr, stats, t_h may be
+ * NULL); the batch is split over the device slots as there; fails while a column step of the mechanism is open; initialises the library like
+ * the Fortran entry points if nothing has.
+ * mistra_chem_rosenbrock_device: device buffers on the device they live on, asynchronous on hip_stream; atol, rtol, rpar, ipar are HOST arrays,
+ * read before the call returns.  d_texit_hexit[ncell][2] and d_hstart[ncell] may be NULL; d_hstart as in mistra_chem_integrate_device_hstart:
+ * an entry > 0 goes before rpar[2].  The call's options block is copied to the device on hip_stream in front of its kernel, so calls queued
+ * back to back on one stream each run with their own.  Each mechanism and device slot keeps MISTRA_ROSENBROCK_CALLS_IN_FLIGHT such blocks: a call
+ * that finds all of them still in use by unfinished kernels waits (on the host) for the oldest. */
+#define MISTRA_ROSENBROCK_CALLS_IN_FLIGHT 8
+int mistra_chem_rosenbrock_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                              double tstart, double tend, const double* atol, const double* rtol,
+                              const double* rpar, const int32_t* ipar,
+                              double* var_out, int32_t* ierr, int32_t* stats, double* t_h);
+int mistra_chem_rosenbrock_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                  double tstart, double tend, const double* atol, const double* rtol,   /* host arrays */
+                                  const double* rpar, const int32_t* ipar,                              /* host arrays */
+                                  double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                  const double* d_hstart, void* hip_stream);
+
+/* The method tables the kernels were compiled with (Ros2_x .. Rodas4_x, gas.f:1514-1895), pure host, works before init: method 1 .. 5, 0 = 3.
+ * *S = ros_S; A15 / C15 = ros_A / ros_C, row-wise lower triangle, S*(S-1)/2 entries; M6, E6, gamma6 = ros_M, ros_E, ros_Gamma; newf6 =
+ * ros_NewF (0/1); *elo = ros_ELO.  Entries past the method's own are zero; any pointer may be NULL.  (ros_Alpha is not kept: Fun_x ignores T.) */
+int mistra_chem_method_table(int method, int* S, double* A15, double* C15, double* M6, double* E6, double* gamma6,
+                             int32_t* newf6, double* elo);
 
 /* The rows of the zero pivots a cell met: what KppDecomp_x returns in IER — the first row k whose diagonal is exactly zero when the
  * elimination reaches it (gas.f:6157) — and ros_PrepareMatrix_x prints once per failed decomposition ("Warning: LU Decomposition

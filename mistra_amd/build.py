@@ -18,6 +18,19 @@ ARCH = "gfx950"
 # -ffp-contract=off: one rounding per multiply and per add, as in the reference built without FMA contraction
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 SOURCES = ["mech_tables.cpp", "schedule.cpp", "capi.cpp", "ros3_kernel.hip", "rates.hip", "pack.hip"]
+# the method kernels (Ros2, Ros4, Rodas3, Rodas4 of Rosenbrock_x on gas, aer, tot): ros_method_kernel.hip once per (mechanism, IPAR(4)), each a
+# translation unit of its own — the product kernels' unit compiles as it does without them — and side by side
+METHOD_SOURCE = "ros_method_kernel.hip"
+METHOD_UNITS = [(mech, method) for mech in (0, 1, 2) for method in (1, 3, 4, 5)]
+MAX_JOBS = 16
+
+
+def method_flags(mech, method):
+    return ["-DMISTRA_METHOD_MECH=%d" % mech, "-DMISTRA_METHOD=%d" % method]
+
+
+def _jobs():
+    return max(1, min(MAX_JOBS, os.cpu_count() or 1))
 
 
 def hipcc():
@@ -41,25 +54,37 @@ def build_lib(force=False, verbose=False):
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))]
     headers.append(os.path.join(PKG, "..", "include", "mistra_chem.h"))
     headers.append(os.path.abspath(__file__))
-    objs = []
-    for src in SOURCES:
+    from concurrent.futures import ThreadPoolExecutor
+    objs, cmds = [], []
+    kernel_src = os.path.join(CSRC, "ros3_kernel.hip")
+    units = [(src, os.path.splitext(src)[0] + ".o", [], []) for src in SOURCES]
+    units += [(METHOD_SOURCE, "ros_method_%d_%d.o" % u, method_flags(*u), [kernel_src]) for u in METHOD_UNITS]      # (the unit includes ros3_kernel.hip)
+    for src, name, flags, deps in units:
         path = os.path.join(CSRC, src)
-        obj = os.path.join(OBJDIR, os.path.splitext(src)[0] + ".o")
+        obj = os.path.join(OBJDIR, name)
         objs.append(obj)
-        if force or _stale(obj, [path] + headers):
-            cmd = [cc, "--offload-arch=" + ARCH] + COMMON + ["-c", path, "-o", obj]
+        if force or _stale(obj, [path] + deps + headers):
+            cmd = [cc, "--offload-arch=" + ARCH] + COMMON + flags + ["-c", path, "-o", obj]
             if src.endswith(".hip"):
                 cmd += ["-Rpass-analysis=kernel-resource-usage"] if verbose else []
+            cmds.append(cmd)
+    with ThreadPoolExecutor(_jobs()) as pool:
+        def compile_one(cmd):
             if verbose:
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
+        list(pool.map(compile_one, cmds))
     if force or _stale(LIB, objs):
         # the look-ahead rings of ros3_kernel.hip sit in registers the compiler does not know are busy: no library is linked
-        # from a kernel object in which a ring-using function's own registers reach its ring (raises)
-        isa = ring_register_report()
-        hits = isa_hazard_report(isa["__isa_text__"])
-        if hits:
-            raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly:\n  " + "\n  ".join(hits))
+        # from a kernel object in which a ring-using function's own registers reach its ring (raises).  Every code object that
+        # holds the ring functions is checked: the product unit and the twelve method units.
+        with ThreadPoolExecutor(_jobs()) as pool:
+            reports = list(pool.map(lambda u: ring_register_report(unit=u), [None] + METHOD_UNITS))
+        for u, isa in zip([None] + METHOD_UNITS, reports):
+            hits = isa_hazard_report(isa["__isa_text__"])
+            if hits:
+                raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly%s:\n  " % (" (method unit %s)" % (u,) if u else "")
+                                   + "\n  ".join(hits))
         cmd = [cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
         if verbose:
             print(" ".join(cmd))
@@ -73,20 +98,22 @@ RING_FUNCTIONS = ("gsum_run", "gsum_run_bar", "gsum_run_pair", "tail_solve", "sc
 RING_HIGH_SLOTS = (192, 196, 208, 212, 224, 228, 240, 244)      # ros3_kernel.hip: MISTRA_RING_HI<K>
 
 
-def ring_register_report(isa_path=None):
+def ring_register_report(isa_path=None, unit=None):
     """Checks the one assumption the table look-ahead ring of ros3_kernel.hip rests on (see the comment there): in the
     non-inlined device functions, every register the COMPILER allocates — named outside inline asm, or chosen by it for an asm
     statement's result — stays below the ring's blocks (v192.. or, in the low placement, v64..), so a
     table load landing in the ring can never hit a compiler value.  Compiles the kernel source to gfx950 assembly and
     scans it.  Returns {function: highest VGPR named outside inline asm}; raises if a ring-using function reaches its ring, and if
-    a function that is not one of RING_FUNCTIONS (nor an integrating kernel, which only calls them) loads into the ring at all."""
+    a function that is not one of RING_FUNCTIONS (nor an integrating kernel, which only calls them) loads into the ring at all.
+    unit: None = the product kernels' unit (ros3_kernel.hip), or one (mechanism, method) of METHOD_UNITS."""
     import re
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         if isa_path is None:
             isa_path = os.path.join(tmp, "ros3_kernel.s")
-            cmd = [hipcc(), "--offload-arch=" + ARCH] + [f for f in COMMON if f != "-fPIC"] + \
-                  ["-S", "--offload-device-only", os.path.join(CSRC, "ros3_kernel.hip"), "-o", isa_path]
+            src, flags = ("ros3_kernel.hip", []) if unit is None else (METHOD_SOURCE, method_flags(*unit))
+            cmd = [hipcc(), "--offload-arch=" + ARCH] + [f for f in COMMON if f != "-fPIC"] + flags + \
+                  ["-S", "--offload-device-only", os.path.join(CSRC, src), "-o", isa_path]
             subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
         lines = open(isa_path).read().split("\n")
     starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if re.match(r"^_ZN6mistra.*:", l)]

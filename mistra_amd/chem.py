@@ -102,6 +102,10 @@ def lib():
             L.mistra_chem_get_step_memory.argtypes = [C.c_int, C.c_int, _dp]
             L.mistra_chem_set_step_memory.argtypes = [C.c_int, C.c_int, _dp]
             L.mistra_chem_integrate_hstart_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp, _ip, _ip, _dp, _dp]
+        if hasattr(L, "mistra_chem_rosenbrock_ex"):
+            L.mistra_chem_rosenbrock_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _ip, _dp, _ip, _ip, _dp]
+            L.mistra_chem_rosenbrock_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, _dp, _dp, _dp, _ip, vp, vp, vp, vp, vp, vp]
+            L.mistra_chem_method_table.argtypes = [C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp, _dp, _dp, _ip, _dp]
         L.mistra_chem_last_error.restype = C.c_char_p
         L.mistra_chem_describe.restype = C.c_char_p
         L.mistra_chem_describe.argtypes = [C.c_int]
@@ -355,6 +359,75 @@ def get_options(mech):
     _check(lib().mistra_chem_get_options(mid, C.byref(is_set), ip.ctypes.data_as(_ip), rp.ctypes.data_as(_dp), at.ctypes.data_as(_dp),
                                          rt.ctypes.data_as(_dp)))
     return Options(ip, rp, at, rt) if is_set.value else None
+
+
+# ---- Rosenbrock_x itself, batched, with all five methods and the options travelling with the call (include/mistra_chem.h: mistra_chem_rosenbrock_ex)
+METHOD_NAMES = {1: "Ros2", 2: "Ros3", 3: "Ros4", 4: "Rodas3", 5: "Rodas4"}
+MethodTable = namedtuple("MethodTable", "S A C M E gamma newf elo")
+
+
+def method_table(method):
+    """The tables the kernels are compiled with for IPAR(4) = `method` (1 Ros2, 2 Ros3, 3 Ros4, 4 Rodas3, 5 Rodas4; 0 = 3 as in Rosenbrock_x) ->
+    MethodTable(S, A[S(S-1)/2], C[S(S-1)/2], M[S], E[S], gamma[S], newf[S] (bool), elo).  Needs no GPU."""
+    s, elo = C.c_int(0), C.c_double(0.0)
+    a, c, m, e, g, nf = np.zeros(15), np.zeros(15), np.zeros(6), np.zeros(6), np.zeros(6), np.zeros(6, np.int32)
+    _check(lib().mistra_chem_method_table(int(method), C.byref(s), a.ctypes.data_as(_dp), c.ctypes.data_as(_dp), m.ctypes.data_as(_dp),
+                                          e.ctypes.data_as(_dp), g.ctypes.data_as(_dp), nf.ctypes.data_as(_ip), C.byref(elo)))
+    n, low = s.value, s.value * (s.value - 1) // 2
+    return MethodTable(n, a[:low].copy(), c[:low].copy(), m[:n].copy(), e[:n].copy(), g[:n].copy(), nf[:n].astype(bool), elo.value)
+
+
+def rosenbrock(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None, atol=None, rtol=None, hstart=None):
+    """Rosenbrock_x(Y, Tstart, Tend, AbsTol, RelTol, RPAR, IPAR, IERR) over a batch of cells, any of its five methods (ipar[3]); the options are this
+    call's alone — None = INTEGRATE_x's value — and the ones in force (set_options) are neither read nor changed.  numpy arrays: the host entry,
+    -> (IntegrateResult, t_h [ncell, 3]) as integrate_ex; torch CUDA tensors: the device entry on torch's current stream, -> (IntegrateResult,
+    texit_hexit [ncell, 2]), hstart [ncell] (a tensor, device entry only): first step size per cell, entries <= 0 = rpar[2].  Options Rosenbrock_x
+    refuses do not raise: every cell's ierr is its code (-1 .. -5), var comes back unchanged, stats and t_h are zero."""
+    mid, name = _mech_id(mech)
+    nvar, nfix, nreact, _ = DIMS[name]
+    ip, rp, at, rt = _option_args(name, ipar, rpar, atol, rtol)
+    opts = (at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp), rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
+    try:
+        import torch
+        is_torch = isinstance(var, torch.Tensor)
+    except ImportError:      # pragma: no cover
+        is_torch = False
+    if is_torch:
+        if not var.is_cuda:
+            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
+        init(var.device.index or 0)
+        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
+                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
+        ncell = var.numel() // nvar
+        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
+            raise MistraChemError("cell counts of var / fix / rconst differ")
+        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
+            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
+        out = torch.empty_like(var)
+        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
+        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
+        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
+        stream = torch.cuda.current_stream(var.device).cuda_stream
+        _check(lib().mistra_chem_rosenbrock_device(mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), *opts,
+                                                   out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(),
+                                                   None if hstart is None else hstart.data_ptr(), C.c_void_p(stream)))
+        return IntegrateResult(out, ierr, stats), th
+    if hstart is not None:
+        raise MistraChemError("hstart goes with the device entry: pass torch CUDA tensors (host buffers: rpar[2] is the first step size of every cell)")
+    if _inited_device is None:
+        init(0)
+    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+    ncell = v.shape[0]
+    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
+    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
+    out = np.empty_like(v)
+    ierr = np.zeros(ncell, np.int32)
+    stats = np.zeros((ncell, 8), np.int32)
+    th = np.zeros((ncell, 3))
+    _check(lib().mistra_chem_rosenbrock_ex(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend),
+                                           *opts, out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp)))
+    return IntegrateResult(out, ierr, stats), th
 
 
 # ---- OPT-IN: every layer's step size carried from one column step to the next (include/mistra_chem.h: mistra_chem_set_step_reuse)

@@ -21,6 +21,7 @@
 #include "pack.hpp"
 #include "rates.hpp"
 #include "ros3_kernel.hpp"
+#include "ros_methods.hpp"
 #include "schedule.hpp"
 
 using namespace mistra;
@@ -536,6 +537,37 @@ struct DriveLayout {
   size_t th = 0, hl = 0, ierr = 0, stats = 0, cp = 0, out_end = 0, var = 0, fix = 0, rct = 0, hs = 0, end = 0;
 };
 
+// The options blocks of mistra_chem_rosenbrock_device: each call's own (kernel_args.hpp: RosOptSlot), copied to the device on the call's stream in front
+// of its kernel.  kRosCallsInFlight blocks per mechanism and device slot, used in turn, each with a pinned host mirror and an event recorded behind the
+// kernel that reads it: the call that comes round to a block whose kernel has not finished waits for that event.
+constexpr int kRosCallsInFlight = MISTRA_ROSENBROCK_CALLS_IN_FLIGHT;
+struct RosCallRing {
+  double *dev = nullptr, *host = nullptr;      // kRosCallsInFlight blocks of `words` doubles each
+  size_t words = 0;
+  hipEvent_t ev[kRosCallsInFlight] = {};
+  bool pending[kRosCallsInFlight] = {};
+  int next = 0;
+  hipError_t ensure(size_t w) {
+    if (dev) return hipSuccess;
+    words = (w + 31) & ~(size_t)31;
+    if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), kRosCallsInFlight * words * sizeof(double))) return e;
+    if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&host), kRosCallsInFlight * words * sizeof(double), hipHostMallocDefault)) return e;
+    for (auto& e : ev)
+      if (hipError_t rc = hipEventCreateWithFlags(&e, hipEventDisableTiming)) return rc;
+    return hipSuccess;
+  }
+  void release() {
+    for (int i = 0; i < kRosCallsInFlight; i++) {
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+      ev[i] = nullptr;
+      pending[i] = false;
+    }
+    if (dev) (void)hipFree(dev);
+    if (host) (void)hipHostFree(host);
+    dev = host = nullptr; words = 0; next = 0;
+  }
+};
+
 struct MechState {
   bool ready = false;
   int nt = 0;
@@ -553,6 +585,9 @@ struct MechState {
   // none are set, and IPAR(3) (0: the library's Max_no_steps)
   DevBuf<double> opt;
   int opt_max_steps = 0;
+  // the per-call options of mistra_chem_rosenbrock_ex (host buffers: one block, the call is synchronous) and mistra_chem_rosenbrock_device
+  DevBuf<double> call_opt;
+  RosCallRing call_ring;
   // the step memory of the batched driver (mistra_chem_set_step_reuse): per model layer k = 1..step_n the last accepted step size of the layer's previous
   // column step of this mechanism, 0 = none.  step_n = 0: forgotten — the next column step under reuse sizes it to its n and zeroes it on the drive stream
   DevBuf<double> step_mem;
@@ -579,6 +614,7 @@ struct MechState {
     k.release(); rates.release(); pack.release(); kmt.release(); liq.release(); stc.release(); vmean.release();
     d_rct.release();
     opt.release(); opt_max_steps = 0;
+    call_opt.release(); call_ring.release();
     step_mem.release(); step_n = 0;
     s_hst.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
@@ -595,10 +631,13 @@ struct DeviceState {
   int id = -1;
   MechState mech[3];
   bool lds_configured[3] = {false, false, false};     // hipFuncAttributeMaxDynamicSharedMemorySize is per device
+  bool lds_method[3][6] = {};                         // ... and per kernel: the method kernels' [mechanism][IPAR(4)] (launch_ros_method)
   void release() {
     if (id >= 0) (void)hipSetDevice(id);
     for (auto& m : mech) m.release();
     for (bool& c : lds_configured) c = false;
+    for (auto& m : lds_method)
+      for (bool& c : m) c = false;
     id = -1;
   }
 };
@@ -812,9 +851,60 @@ int method_built(int mech, const int32_t* ipar) {
               "gat"[mech] + " that this library does not have");
 }
 
-int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream) {
+// the options block the options kernels read, from a decode that returned 1
+std::vector<double> options_block(int mech, const RosResolved& r, const double* atol, const double* rtol) {
+  const size_t nv = (size_t)kDims[mech].nvar;
+  std::vector<double> b((size_t)kOptTol + 2 * nv, 0.0);
+  b[kOptHmin] = r.hmin; b[kOptHmax] = r.hmax; b[kOptHstart] = r.hstart;
+  b[kOptFacMin] = r.facmin; b[kOptFacMax] = r.facmax; b[kOptFacRej] = r.facrej; b[kOptFacSafe] = r.facsafe;
+  b[kOptAutonomous] = r.autonomous ? 1.0 : 0.0;
+  for (size_t i = 0; i < nv; i++) {      // scalar tolerances: AbsTol(1), RelTol(1) for every species (gas.f:1363); the other entries are not read
+    b[(size_t)kOptTol + i] = atol[r.vector ? i : 0];
+    b[(size_t)kOptTol + nv + i] = rtol[r.vector ? i : 0];
+  }
+  return b;
+}
+
+// One call of Rosenbrock_x with its own options (mistra_chem_rosenbrock_ex / _device): nothing of it is kept, nothing process-wide is read but
+// Max_no_steps' default (mistra_chem_debug_set_max_steps, which ipar[2] /= 0 goes before)
+struct RosCall {
+  int ierr = 0;                   // the decode's: 1, or the refusal -1 .. -5
+  int method = kRos3;             // IPAR(4), 0 resolved to Ros4 (gas.f:1057)
+  int max_steps = 0;
+  std::vector<double> block;
+};
+RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol) {
+  RosCall c;
+  RosResolved r;
+  c.ierr = resolve_options(mech, ipar, rpar, atol, rtol, &r);
+  if (c.ierr != 1) return c;
+  c.method = ipar[3] == 0 ? (int)kRos4 : (int)ipar[3];
+  c.max_steps = ipar[2] ? ipar[2] : g_max_steps;
+  c.block = options_block(mech, r, atol, rtol);
+  return c;
+}
+
+// method: IPAR(4) resolved (ros_methods.hpp); anything but Ros3 runs its method kernel, which reads a.opt
+template <class MT, int NT>
+hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bool* configured) {
+  switch (method) {
+    case kRos2: return launch_ros_method<MT, NT, kRos2>(a, stream, configured);
+    case kRos4: return launch_ros_method<MT, NT, kRos4>(a, stream, configured);
+    case kRodas3: return launch_ros_method<MT, NT, kRodas3>(a, stream, configured);
+    case kRodas4: return launch_ros_method<MT, NT, kRodas4>(a, stream, configured);
+  }
+  return hipErrorInvalidValue;
+}
+
+int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, int method = kRos3) {
   hipError_t e = hipErrorInvalidValue;
-  if (mech == MISTRA_MECH_GAS) e = launch_ros3<GasTraits, kGasNT>(a, stream, &D.lds_configured[mech]);
+  if (method != kRos3) {
+    if (method < kRos2 || method > kRodas4 || !a.opt || a.dump || a.prof) return fail("no kernel for this Rosenbrock method");      // (never a quiet Ros3)
+    bool* c = &D.lds_method[mech][method];
+    e = mech == MISTRA_MECH_GAS   ? launch_method<GasTraits, kGasNT>(method, a, stream, c)
+        : mech == MISTRA_MECH_AER ? launch_method<AerTraits, kAerNT>(method, a, stream, c)
+                                  : launch_method<TotTraits, kTotNT>(method, a, stream, c);
+  } else if (mech == MISTRA_MECH_GAS) e = launch_ros3<GasTraits, kGasNT>(a, stream, &D.lds_configured[mech]);
   else if (mech == MISTRA_MECH_AER) e = launch_ros3<AerTraits, kAerNT>(a, stream, &D.lds_configured[mech]);
   else e = launch_ros3<TotTraits, kTotNT>(a, stream, &D.lds_configured[mech]);
   if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
@@ -939,7 +1029,7 @@ int init_locked(int n, const int* ids) {
 // is made on the device and never crosses PCIe
 int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                       double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, size_t batch_start = 0,
-                      const double* env = nullptr, const double* hstart = nullptr) {
+                      const double* env = nullptr, const double* hstart = nullptr, const RosCall* call = nullptr) {
   HIP_TRY(hipSetDevice(D.id));
   MechState& S = D.mech[mech];
   const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact, nc = (size_t)ncell;
@@ -962,6 +1052,12 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
   }
   KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, tin, tout, S.s_var.p, S.s_ierr.p, S.s_stats.p, t_h ? S.s_th.p : nullptr);
   if (t_h) a.h_last = S.s_th.p + 2 * nc;
+  if (call) {      // the call's own options (mistra_chem_rosenbrock_ex) instead of the ones in force
+    HIP_TRY(S.call_opt.reserve(call->block.size()));
+    HIP_TRY(hipMemcpy(S.call_opt.p, call->block.data(), call->block.size() * sizeof(double), hipMemcpyHostToDevice));
+    a.opt = S.call_opt.p;
+    a.max_steps = call->max_steps;
+  }
   if (hstart) {      // OPT-IN: the caller's first step size per cell (mistra_chem_integrate_hstart_ex)
     HIP_TRY(S.s_hst.reserve(nc));
     HIP_TRY(hipMemcpy(S.s_hst.p, hstart, nc * sizeof(double), hipMemcpyHostToDevice));
@@ -982,7 +1078,7 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     HIP_TRY(prof.reserve(nc * kProfSlots));
     a.prof = prof.p;
   }
-  if (int rc = launch(D, mech, a, nullptr)) return rc;
+  if (int rc = launch(D, mech, a, nullptr, call ? call->method : (int)kRos3)) return rc;
   HIP_TRY(hipDeviceSynchronize());
   if (profile) {
     std::vector<unsigned long long> h(nc * kProfSlots);
@@ -1829,16 +1925,7 @@ int mistra_chem_set_options(int mech, const int32_t* ipar, const double* rpar, c
     next.set = true;
     std::memcpy(next.ipar, ipar, sizeof next.ipar);
     std::memcpy(next.rpar, rpar, sizeof next.rpar);
-    const size_t nv = (size_t)kDims[mech].nvar;
-    next.block.assign((size_t)kOptTol + 2 * nv, 0.0);
-    const RosResolved& r = next.r;
-    next.block[kOptHmin] = r.hmin; next.block[kOptHmax] = r.hmax; next.block[kOptHstart] = r.hstart;
-    next.block[kOptFacMin] = r.facmin; next.block[kOptFacMax] = r.facmax; next.block[kOptFacRej] = r.facrej; next.block[kOptFacSafe] = r.facsafe;
-    next.block[kOptAutonomous] = r.autonomous ? 1.0 : 0.0;
-    for (size_t i = 0; i < nv; i++) {      // scalar tolerances: AbsTol(1), RelTol(1) for every species (gas.f:1363); the other entries are not read
-      next.block[(size_t)kOptTol + i] = atol[r.vector ? i : 0];
-      next.block[(size_t)kOptTol + nv + i] = rtol[r.vector ? i : 0];
-    }
+    next.block = options_block(mech, next.r, atol, rtol);
   }
   int rc = 0;
   for (auto& D : g_devs) {      // every slot: the device-buffer entries run where their buffers live
@@ -1940,7 +2027,8 @@ static int lazy_init() {
 }
 
 static int integrate_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, const double* env, double tin,
-                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart = nullptr);
+                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart = nullptr,
+                          const RosCall* call = nullptr);
 
 int mistra_chem_integrate_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                              double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h) {
@@ -1959,7 +2047,7 @@ int mistra_chem_integrate_hstart_ex(int mech, int ncell, const double* var_in, c
 }
 
 static int integrate_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, const double* env, double tin,
-                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart) {
+                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart, const RosCall* call) {
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, ncell)) return rc;
   if (ncell == 0) return 0;
@@ -1972,7 +2060,7 @@ static int integrate_host(int mech, int ncell, const double* var_in, const doubl
   const int ndev = (int)g_devs.size();
   for (auto& d : g_devs) d.mech[mech].sing_count = 0;
   if (ndev == 1 || ncell < 2 * ndev) {
-    int rc = integrate_host_on(g_devs[0], mech, ncell, var_in, fix, rconst, tin, tout, var_out, ierr, stats, t_h, 0, env, hstart);
+    int rc = integrate_host_on(g_devs[0], mech, ncell, var_in, fix, rconst, tin, tout, var_out, ierr, stats, t_h, 0, env, hstart, call);
     (void)hipSetDevice(g_devs[0].id);
     return rc;
   }
@@ -1988,7 +2076,7 @@ static int integrate_host(int mech, int ncell, const double* var_in, const doubl
     workers.emplace_back([=, &rcs, &errs]() {
       rcs[(size_t)d] = integrate_host_on(g_devs[(size_t)d], mech, count, var_in + start * nv, fix + start * nf, rconst ? rconst + start * nr : nullptr, tin, tout,
                                          var_out + start * nv, ierr ? ierr + start : nullptr, stats ? stats + start * 8 : nullptr, t_h ? t_h + start * 3 : nullptr, start,
-                                         env ? env + start * ne : nullptr, hstart ? hstart + start : nullptr);
+                                         env ? env + start * ne : nullptr, hstart ? hstart + start : nullptr, call);
       if (rcs[(size_t)d]) errs[(size_t)d] = g_err;      // g_err is thread-local: carry the text to the caller's thread
     });
   }
@@ -1997,6 +2085,87 @@ static int integrate_host(int mech, int ncell, const double* var_in, const doubl
   for (int d = 0; d < ndev; d++)
     if (rcs[(size_t)d]) return fail("device " + std::to_string(g_devs[(size_t)d].id) + ": " + errs[(size_t)d]);
   return 0;
+}
+
+int mistra_chem_method_table(int method, int* S, double* A15, double* C15, double* M6, double* E6, double* gamma6, int32_t* newf6, double* elo) {
+  if (method < 0 || method > 5) return fail("Rosenbrock_x has methods 1 .. 5 (Ros2, Ros3, Ros4, Rodas3, Rodas4; 0 selects Ros4)");
+  const RosMethodTable t = ros_method_table(method == 0 ? (int)kRos4 : method);      // the tables the kernels are compiled with (ros_methods.hpp)
+  const int nlow = t.S * (t.S - 1) / 2;
+  if (S) *S = t.S;
+  for (int i = 0; i < 15; i++) {
+    if (A15) A15[i] = i < nlow ? t.A[i] : 0.0;
+    if (C15) C15[i] = i < nlow ? t.C[i] : 0.0;
+  }
+  for (int i = 0; i < 6; i++) {
+    if (M6) M6[i] = i < t.S ? t.M[i] : 0.0;
+    if (E6) E6[i] = i < t.S ? t.E[i] : 0.0;
+    if (gamma6) gamma6[i] = i < t.S ? t.Gamma[i] : 0.0;
+    if (newf6) newf6[i] = i < t.S && t.NewF[i] ? 1 : 0;
+  }
+  if (elo) *elo = t.ELO;
+  return 0;
+}
+
+int mistra_chem_rosenbrock_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                              const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
+                              int32_t* stats, double* t_h) {
+  if (int rc = lazy_init()) return rc;
+  if (int rc = check_call(mech, ncell)) return rc;
+  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
+  if (ncell == 0) return 0;
+  if (!var_in || !fix || !rconst || !var_out) return fail("null host pointer");
+  RosCall call;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps)
+    if (g_devs[0].mech[mech].pend.active) return step_is_open(mech);
+    call = decode_call(mech, ipar, rpar, atol, rtol);
+  }
+  if (call.ierr != 1) {      // Rosenbrock_x returns before it touches Y or the statistics (gas.f:936-1053): a result, nothing is launched
+    const size_t nv = (size_t)kDims[mech].nvar, nc = (size_t)ncell;
+    if (var_out != var_in) std::memmove(var_out, var_in, nc * nv * sizeof(double));
+    if (ierr) std::fill(ierr, ierr + nc, (int32_t)call.ierr);
+    if (stats) std::fill(stats, stats + nc * 8, 0);
+    if (t_h) std::fill(t_h, t_h + nc * 3, 0.0);
+    return 0;
+  }
+  return integrate_host(mech, ncell, var_in, fix, rconst, nullptr, tstart, tend, var_out, ierr, stats, t_h, nullptr, &call);
+}
+
+int mistra_chem_rosenbrock_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                  double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
+                                  int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream) {
+  if (ncell == 0) return check_call(mech, 0);
+  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
+  if (!d_var_in || !d_fix || !d_rconst || !d_var_out || !d_ierr || !d_stats) return fail("null device pointer");
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of options blocks)
+  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol);
+  const size_t nv = (size_t)kDims[mech].nvar, nc = (size_t)ncell;
+  if (call.ierr != 1) {      // the refusal as a result, in stream order; no kernel of the library runs
+    if (d_var_out != d_var_in) HIP_TRY(hipMemcpyAsync(d_var_out, d_var_in, nc * nv * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_ierr), call.ierr, nc, st));
+    HIP_TRY(hipMemsetAsync(d_stats, 0, nc * 8 * sizeof(int32_t), st));
+    if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nc * 2 * sizeof(double), st));
+    return 0;
+  }
+  RosCallRing& R = t.S->call_ring;
+  HIP_TRY(R.ensure(call.block.size()));
+  const int i = R.next;
+  R.next = (i + 1) % kRosCallsInFlight;
+  if (R.pending[i]) HIP_TRY(hipEventSynchronize(R.ev[i]));      // the kernel that read this block kRosCallsInFlight calls ago
+  R.pending[i] = false;
+  double *hb = R.host + (size_t)i * R.words, *db = R.dev + (size_t)i * R.words;
+  std::memcpy(hb, call.block.data(), call.block.size() * sizeof(double));
+  HIP_TRY(hipMemcpyAsync(db, hb, call.block.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_var_out, d_ierr, d_stats, d_texit_hexit);
+  a.hstart = d_hstart;
+  a.opt = db;
+  a.max_steps = call.max_steps;
+  const int rc = launch(*t.D, mech, a, st, call.method);
+  if (hipEventRecord(R.ev[i], st) == hipSuccess) R.pending[i] = true;      // (also behind a failed launch: the copy is queued)
+  return rc;
 }
 
 int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, double* tout, int32_t* ierr_out, double* t_err,

@@ -38,8 +38,9 @@ struct DenseDev {              // dense tail block (schedule.hpp: DenseTail); nu
   const uint16_t* schur_cells; // [8 * DENSE_KB * 64]: operand cells of the Schur steps in MFMA lane order (schedule.hpp: DenseTail)
 };
 
-// Rosenbrock_x's options as the kernel's options instantiation (VARIANT 3) reads them: one block of doubles in device memory per
-// mechanism and device slot, resolved by the host (capi.cpp: resolve_options, after gas.f:936-1053).  What depends on the call's
+// Rosenbrock_x's options as the kernel's options instantiations (VARIANT 3: Ros3 and the four method kernels) read them: one block of doubles
+// in device memory — per mechanism and device slot for the options in force (mistra_chem_set_options), per call for mistra_chem_rosenbrock_ex /
+// _device — resolved by the host (capi.cpp: resolve_options, after gas.f:936-1053).  The method is not in the block: it picks the kernel.  What depends on the call's
 // interval is left to the kernel: Hmax = min(HMAX, |Tend-Tstart|), H = min(min(HSTART, |Tend-Tstart|), Hmax).
 enum RosOptSlot : int {
   kOptHmin = 0,        // RPAR(1)

@@ -19,6 +19,7 @@
 
 #include "kernel_args.hpp"
 #include "ros3_kernel.hpp"
+#include "ros_methods.hpp"
 
 namespace mistra {
 
@@ -94,6 +95,8 @@ constexpr double kRosElo = 3.0;
 // coefficients were hoisted out of the step loop as live registers, and the 128-register kernel spilled them to scratch and
 // read them back every step (most of its HBM-side traffic).  The 256-register kernel keeps the inlined form (0.7 % faster there).
 __device__ __attribute__((noinline)) double err_root(double err) { return pow(err, 1.0 / kRosElo); }
+// the method kernels' (ros_ELO = 2 and 4: Ros2, Ros4, Rodas4), likewise
+[[maybe_unused]] __device__ __attribute__((noinline)) double err_root_elo(double err, double inv_elo) { return pow(err, inv_elo); }
 
 // A value every lane of the wave holds identically (time, step size: sums reduced in a fixed order, the same in all lanes),
 // moved to scalar registers: the register-starved kernels spilled these to scratch at the head of the step loop.
@@ -1191,9 +1194,14 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // parity tests (tests/test_gpu_parity.py); the integration itself is untouched.  3 = Rosenbrock_x's options (gas.f:936-1053) out of
 // a.opt instead of the values INTEGRATE_x fixes (kernel_args.hpp: RosOptSlot; capi.cpp: mistra_chem_set_options): every difference
 // from variant 0 sits behind `if constexpr (OPT)`, the other three compile from the statements they always had.
-template <class MT, int NT, int VARIANT>
+// METHOD (variant 3 only): the Rosenbrock method, IPAR(4) of Rosenbrock_x (ros_methods.hpp).  Ros3 is the kernel as it was; Ros2, Ros4, Rodas3
+// and Rodas4 (the method kernels, instantiated by ros_method_kernel.hip in translation units of their own) differ in the stage loop, in the
+// number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
+template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
   constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, OPT = VARIANT == 3;
+  static_assert(METHOD == kRos3 || (OPT && METHOD >= kRos2 && METHOD <= kRodas4), "the method kernels are options instantiations");
+  constexpr double kGamma1 = METHOD == kRos3 ? kRosGamma1 : kRosMethod<METHOD>.Gamma[0];
   constexpr int NVAR = MT::NVAR, NFIX = MT::NFIX, NREACT = MT::NREACT, NNZ = MT::NNZ, NCONST = MT::NCONST;
   constexpr int NW = NT / 64;
   constexpr int SPT = (NVAR + NT - 1) / NT, RPT = (NREACT + NT - 1) / NT;
@@ -1674,6 +1682,18 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   int ierr = 1;
 
   double ynew[SPT], fcn0[SPT], fcn[SPT], k1[SPT], k2[SPT], k3[SPT], yerr[SPT];
+  [[maybe_unused]] double k4[SPT], k5[SPT], k6[SPT];      // the method kernels' further stage vectors (Ros4, Rodas3: k4; Rodas4: k4..k6)
+  // stage vector J (0-based) by its compile-time number: named register arrays, never an array indexed at run time (that one would live in scratch)
+  [[maybe_unused]] auto stage_k = [&](auto J) -> double (&)[SPT] {
+    constexpr int j = decltype(J)::value;
+    static_assert(j >= 0 && j < 6, "stage vector");
+    if constexpr (j == 0) return k1;
+    else if constexpr (j == 1) return k2;
+    else if constexpr (j == 2) return k3;
+    else if constexpr (j == 3) return k4;
+    else if constexpr (j == 4) return k5;
+    else return k6;
+  };
 
   while (fabs(Tend - T) >= Roundoff) {
     if (nstp > a.max_steps) { ierr = -6; break; }      // Max_no_steps: 100000 (gas.f:1042, 1199)
@@ -1711,13 +1731,14 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         // K1's right-hand side, Fcn0 + HG*dFdT with dFdT = +0.0 (see above); independent of H
 #pragma unroll
         for (int q = 0; q < SPT; q++) {
-          if constexpr (OPT) k1[q] = autonomous ? fcn0[q] : fcn0[q] + 0.0;      // Autonomous: the HG*dFdT terms are not added at all (gas.f:1268)
+          if constexpr (METHOD != kRos3) k1[q] = autonomous ? fcn0[q] : fcn0[q] + Direction * 0.0;      // (Direction*H*Gamma(1))*dFdT: a zero of Direction's sign (Gamma(1) > 0 in all five)
+          else if constexpr (OPT) k1[q] = autonomous ? fcn0[q] : fcn0[q] + 0.0;      // Autonomous: the HG*dFdT terms are not added at all (gas.f:1268)
           else k1[q] = fcn0[q] + 0.0;
         }
         int nconsecutive = 0;
         bool singular = true;
         while (singular) {
-          const double ghinv = wave_uniform(1.0 / (Direction * Hget() * kRosGamma1));
+          const double ghinv = wave_uniform(1.0 / (Direction * Hget() * kGamma1));
           singular = prepare(ghinv, k1);
           dump_matrix(NVAR);      // Ghimj = 1/(H*gamma) - Jac0
           ndec += 1;
@@ -1774,43 +1795,115 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       solve(k1, true);
       dump_vec(2 * NVAR + 2 * NNZ, k1);
       lap(4);
-      // stage 2: new function value at Y + A21*K1
+      if constexpr (METHOD == kRos3) {
+        // stage 2: new function value at Y + A21*K1
 #pragma unroll
-      for (int q = 0; q < SPT; q++) ynew[q] = y[q] + kRosA1 * k1[q];
-      lap(6);
-      fun(ynew, fcn);
-      lap(0);
-      nfun += 1;
-      {
-        const double hc = wave_uniform(kRosC1 / dh);
+        for (int q = 0; q < SPT; q++) ynew[q] = y[q] + kRosA1 * k1[q];
+        lap(6);
+        fun(ynew, fcn);
+        lap(0);
+        nfun += 1;
+        {
+          const double hc = wave_uniform(kRosC1 / dh);
+#pragma unroll
+          for (int q = 0; q < SPT; q++) {
+            if constexpr (OPT) k2[q] = autonomous ? fcn[q] + hc * k1[q] : (fcn[q] + hc * k1[q]) + dh * 0.0;
+            else k2[q] = (fcn[q] + hc * k1[q]) + dh * 0.0;      // + HG*dFdT with dFdT = +0.0: (dh*gamma2)*0.0, a zero of dh's sign (gamma2 > 0)
+          }
+        }
+        lap(6);
+        solve(k2, false);
+        dump_vec(3 * NVAR + 2 * NNZ, k2);
+        lap(4);
+        // stage 3 reuses the stage-2 function value
+        {
+          const double hc1 = wave_uniform(kRosC2 / dh), hc2 = wave_uniform(kRosC3 / dh);
+#pragma unroll
+          for (int q = 0; q < SPT; q++) {
+            if constexpr (OPT) k3[q] = autonomous ? (fcn[q] + hc1 * k1[q]) + hc2 * k2[q] : ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;
+            else k3[q] = ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;      // (dh*gamma3)*0.0 likewise (gamma3 > 0)
+          }
+        }
+        lap(6);
+        solve(k3, false);
+        dump_vec(4 * NVAR + 2 * NNZ, k3);
+        lap(4);
+        nsol += 3;
 #pragma unroll
         for (int q = 0; q < SPT; q++) {
-          if constexpr (OPT) k2[q] = autonomous ? fcn[q] + hc * k1[q] : (fcn[q] + hc * k1[q]) + dh * 0.0;
-          else k2[q] = (fcn[q] + hc * k1[q]) + dh * 0.0;      // + HG*dFdT with dFdT = +0.0: (dh*gamma2)*0.0, a zero of dh's sign (gamma2 > 0)
+          ynew[q] = ((y[q] + kRosM1 * k1[q]) + kRosM2 * k2[q]) + kRosM3 * k3[q];
+          yerr[q] = ((0.0 + kRosE1 * k1[q]) + kRosE2 * k2[q]) + kRosE3 * k3[q];
         }
-      }
-      lap(6);
-      solve(k2, false);
-      dump_vec(3 * NVAR + 2 * NNZ, k2);
-      lap(4);
-      // stage 3 reuses the stage-2 function value
-      {
-        const double hc1 = wave_uniform(kRosC2 / dh), hc2 = wave_uniform(kRosC3 / dh);
+      } else {
+        // ---- the method kernels: stages 2 .. ros_S (gas.f:1241-1276), unrolled at compile time, in the reference's order of operations.
+        //      WAXPY_x returns at once for a zero coefficient (gas.f:6641): such a term is dropped, not multiplied out.
+        auto for_stages = [&](auto&& f, auto FROM, auto TO) {      // f(integral_constant<int, FROM>) ... f(integral_constant<int, TO - 1>)
+          auto go = [&](auto&& self, auto I) {
+            if constexpr (decltype(I)::value < decltype(TO)::value) {
+              f(I);
+              self(self, std::integral_constant<int, decltype(I)::value + 1>{});
+            }
+          };
+          go(go, FROM);
+        };
+        for_stages([&](auto I) {
+          constexpr int i = decltype(I)::value;      // stage i + 1
+          constexpr int row = i * (i - 1) / 2;       // A(i+1, j+1) = ros_A[row + j]
+          if constexpr (kRosMethod<METHOD>.NewF[i]) {
 #pragma unroll
-        for (int q = 0; q < SPT; q++) {
-          if constexpr (OPT) k3[q] = autonomous ? (fcn[q] + hc1 * k1[q]) + hc2 * k2[q] : ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;
-          else k3[q] = ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;      // (dh*gamma3)*0.0 likewise (gamma3 > 0)
-        }
-      }
-      lap(6);
-      solve(k3, false);
-      dump_vec(4 * NVAR + 2 * NNZ, k3);
-      lap(4);
-      nsol += 3;
+            for (int q = 0; q < SPT; q++) ynew[q] = y[q];
+            for_stages([&](auto J) {
+              constexpr double aij = kRosMethod<METHOD>.A[row + decltype(J)::value];
+              if constexpr (aij != 0.0) {
+                const double (&kj)[SPT] = stage_k(J);
 #pragma unroll
-      for (int q = 0; q < SPT; q++) {
-        ynew[q] = ((y[q] + kRosM1 * k1[q]) + kRosM2 * k2[q]) + kRosM3 * k3[q];
-        yerr[q] = ((0.0 + kRosE1 * k1[q]) + kRosE2 * k2[q]) + kRosE3 * k3[q];
+                for (int q = 0; q < SPT; q++) ynew[q] = ynew[q] + aij * kj[q];
+              }
+            }, std::integral_constant<int, 0>{}, I);
+            lap(6);
+            fun(ynew, fcn);
+            lap(0);
+            nfun += 1;
+          }
+          // Fcn: the last function value formed, Fcn0 while no stage of this step has formed one (Rodas3's stage 2)
+          constexpr bool fresh = ros_fresh_fcn(METHOD, i);
+          double (&ki)[SPT] = stage_k(I);
+#pragma unroll
+          for (int q = 0; q < SPT; q++) ki[q] = fresh ? fcn[q] : fcn0[q];
+          for_stages([&](auto J) {
+            constexpr double cij = kRosMethod<METHOD>.C[row + decltype(J)::value];
+            if constexpr (cij != 0.0) {
+              const double hc = wave_uniform(cij / dh);
+              const double (&kj)[SPT] = stage_k(J);
+#pragma unroll
+              for (int q = 0; q < SPT; q++) ki[q] = ki[q] + hc * kj[q];
+            }
+          }, std::integral_constant<int, 0>{}, I);
+          constexpr double gi = kRosMethod<METHOD>.Gamma[i];
+          if constexpr (gi != 0.0) {      // + HG*dFdT with dFdT = +0.0: a zero with the sign of Direction*H*Gamma(i); nothing where Gamma(i) = 0 or autonomous (gas.f:1268)
+            const double hg0 = wave_uniform((dh * gi) * 0.0);
+#pragma unroll
+            for (int q = 0; q < SPT; q++) ki[q] = autonomous ? ki[q] : ki[q] + hg0;
+          }
+          lap(6);
+          solve(ki, false);
+          lap(4);
+        }, std::integral_constant<int, 1>{}, std::integral_constant<int, kRosMethod<METHOD>.S>{});
+        { constexpr int S = kRosMethod<METHOD>.S; nsol += S; }
+#pragma unroll
+        for (int q = 0; q < SPT; q++) { ynew[q] = y[q]; yerr[q] = 0.0; }
+        for_stages([&](auto J) {
+          constexpr double mj = kRosMethod<METHOD>.M[decltype(J)::value], ej = kRosMethod<METHOD>.E[decltype(J)::value];
+          const double (&kj)[SPT] = stage_k(J);
+          if constexpr (mj != 0.0) {
+#pragma unroll
+            for (int q = 0; q < SPT; q++) ynew[q] = ynew[q] + mj * kj[q];
+          }
+          if constexpr (ej != 0.0) {
+#pragma unroll
+            for (int q = 0; q < SPT; q++) yerr[q] = yerr[q] + ej * kj[q];
+          }
+        }, std::integral_constant<int, 0>{}, std::integral_constant<int, kRosMethod<METHOD>.S>{});
       }
       lap(6);
       const double Err = error_norm(y, ynew, yerr);
@@ -1820,7 +1913,11 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       }
       lap(5);
       double root;
-      if constexpr (MT::WAVES_PER_SIMD > 2) root = err_root(Err);      // register-starved kernels: see err_root
+      if constexpr (METHOD != kRos3 && kRosMethod<METHOD>.ELO != kRosElo) {      // Err**(1/ros_ELO), ros_ELO = 2 or 4
+        constexpr double inv_elo = 1.0 / kRosMethod<METHOD>.ELO;
+        if constexpr (MT::WAVES_PER_SIMD > 2) root = err_root_elo(Err, inv_elo);
+        else root = pow(Err, inv_elo);
+      } else if constexpr (MT::WAVES_PER_SIMD > 2) root = err_root(Err);      // register-starved kernels: see err_root
       else root = pow(Err, 1.0 / kRosElo);
       const double Fac = fmin_f(facmax(), fmax_f(facmin(), facsafe() / root));
       const double H = Hget();
@@ -1875,6 +1972,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   }
 }
 
+#ifndef MISTRA_METHOD_TU      // (ros_method_kernel.hip includes this file for the kernel template alone)
 // ---- launchers (one explicit instantiation per supported <mechanism, workgroup size>)
 template <class MT, int NT>
 hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_configured) {
@@ -1916,5 +2014,6 @@ template hipError_t launch_ros3<AerTraits, kAerNT>(const KernelArgs&, hipStream_
 template hipError_t launch_ros3<TotTraits, kTotNT>(const KernelArgs&, hipStream_t, bool*);
 // (a 1024-thread tot variant was measured slower, and instantiating it caps the register budget of the shared
 //  non-inlined device functions at that of a 16-wave workgroup)
+#endif      // MISTRA_METHOD_TU
 
 }  // namespace mistra

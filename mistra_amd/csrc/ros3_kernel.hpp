@@ -95,4 +95,9 @@ struct LdsLayout {
 template <class MT, int NT>
 hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
 
+// The method kernels (Ros2, Ros4, Rodas3, Rodas4; METHOD = IPAR(4), ros_methods.hpp): a.opt must be set.  One explicit specialisation per
+// <mechanism, method>, each in a translation unit of its own (ros_method_kernel.hip).  lds_configured: per device AND kernel.
+template <class MT, int NT, int METHOD>
+hipError_t launch_ros_method(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
+
 }  // namespace mistra

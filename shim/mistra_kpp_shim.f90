@@ -26,6 +26,12 @@
 !     SUBROUTINE MISTRA_STEP_REUSE_g / _a / _t (ON)                                  ON logical; the single-pass batched driver (KPP_DRIVE_RUN) keeps the steps
 ! and for a caller that orders its own batches, the batched form with a first step size per cell (<= 0: the reference's), HEXIT of one call being HSTART of the next:
 !     SUBROUTINE INTEGRATE_BATCH_H_g / _a / _t (NCELL, VAR, FIX, RCONST, TIN, TOUT, HSTART, TEXIT, HEXIT, IERR, ISTAT)
+!
+! One layer below INTEGRATE_x: Rosenbrock_x itself for NCELL cells, with its own argument list and ALL FIVE methods (IPAR(4) = 1 Ros2, 2 Ros3, 3 Ros4,
+! 4 Rodas3, 5 Rodas4, 0 = Ros4; include/mistra_chem.h: mistra_chem_rosenbrock_ex).  The options are the call's alone: the ones MISTRA_SET_OPTIONS_x put
+! in force are neither read nor changed.
+!     SUBROUTINE ROSENBROCK_BATCH_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+! IERR(k) = 1 or Rosenbrock_x's code, also for options it refuses (-1 .. -5: VAR untouched); ros_ErrorMsg_x's lines go to unit 6 for every failed cell.
 module mistra_chem_c_api
   use iso_c_binding
   implicit none
@@ -86,6 +92,17 @@ module mistra_chem_c_api
        integer(c_int32_t) :: ierr(*), stats(*)
        integer(c_int) :: rc
      end function mistra_chem_integrate_hstart_ex
+     function mistra_chem_rosenbrock_ex(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h) &
+          bind(C, name="mistra_chem_rosenbrock_ex") result(rc)
+       import :: c_int, c_double, c_int32_t
+       integer(c_int), value :: mech, ncell
+       real(c_double), value :: tstart, tend
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_out(*), t_h(*)
+       real(c_double), intent(in) :: atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_ex
      function mistra_chem_set_step_reuse(mech, on) bind(C, name="mistra_chem_set_step_reuse") result(rc)
        import :: c_int
        integer(c_int), value :: mech, on
@@ -249,6 +266,41 @@ contains
     end do
     deallocate (th)
   end subroutine integrate_batch
+
+  ! Rosenbrock_x for NCELL cells with the call's own options; the messages in cell order, as a serial loop over Rosenbrock_x would have written them
+  ! (ros_PrepareMatrix_x's warnings, then ros_ErrorMsg_x's lines: a refusal is reported at T = Tstart, H = 0 as Rosenbrock_x does, gas.f:955)
+  subroutine rosenbrock_batch(mech, sfx, NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+    integer, intent(in) :: mech, NCELL
+    character(len=1), intent(in) :: sfx
+    real(c_double) :: VAR(*), FIX(*), RCONST(*), TEXIT(NCELL), HEXIT(NCELL)
+    real(c_double), intent(in) :: TSTART, TEND, ATOL(*), RTOL(*), RPAR(20)
+    integer(c_int32_t), intent(in) :: IPAR(20)
+    integer(c_int32_t) :: IERR(NCELL), ISTAT(8, NCELL)
+    real(c_double), allocatable :: th(:, :)
+    integer(c_int32_t) :: rows(8)
+    integer :: k, i
+    if (NCELL <= 0) return
+    allocate (th(3, NCELL))
+    if (mistra_chem_rosenbrock_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, VAR, IERR, ISTAT, th) /= 0) &
+         call mistra_chem_fail('ROSENBROCK_BATCH_'//sfx)
+    do k = 1, NCELL
+       TEXIT(k) = th(1, k)
+       HEXIT(k) = th(2, k)
+       if (ISTAT(8, k) > 0) then
+          rows = 0
+          if (mistra_chem_singular_rows(int(mech, c_int), int(k - 1, c_int), rows) /= 0) call mistra_chem_fail('mistra_chem_singular_rows')
+          do i = 1, ISTAT(8, k)
+             print *, 'Warning: LU Decomposition returned ising = ', int(rows(min(i, 8)))
+          end do
+       end if
+       if (IERR(k) < -5) then
+          call mistra_chem_error_lines(sfx, int(IERR(k)), th(1, k), th(3, k))
+       else if (IERR(k) < 0) then
+          call mistra_chem_error_lines(sfx, int(IERR(k)), TSTART, 0.d0)
+       end if
+    end do
+    deallocate (th)
+  end subroutine rosenbrock_batch
 end module mistra_chem_c_api
 
 subroutine INTEGRATE_g(TIN, TOUT)
@@ -486,3 +538,34 @@ subroutine MISTRA_STEP_REUSE_t(ON)
   logical :: ON
   call step_reuse(2, 't', ON)
 end subroutine MISTRA_STEP_REUSE_t
+
+! ---- Rosenbrock_x, batched: the reference's argument list (gas.f:777) in front of the per-cell results.  ATOL / RTOL: NVAR entries (IPAR(2) = 0) or one.
+subroutine ROSENBROCK_BATCH_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), TEXIT(*), HEXIT(*)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(0, 'g', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+end subroutine ROSENBROCK_BATCH_g
+
+subroutine ROSENBROCK_BATCH_a(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), TEXIT(*), HEXIT(*)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(1, 'a', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+end subroutine ROSENBROCK_BATCH_a
+
+subroutine ROSENBROCK_BATCH_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), TEXIT(*), HEXIT(*)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+end subroutine ROSENBROCK_BATCH_t

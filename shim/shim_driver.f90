@@ -7,6 +7,9 @@
 !          shim_driver <OG|OA|OT> <in.bin> <out.bin>   the batched call under Rosenbrock_x's options: in.bin starts with IPAR(20), RPAR(20), ATOL(NVAR),
 !                                                      RTOL(NVAR) (float64), handed to MISTRA_SET_OPTIONS_x once, and goes on as for <G|A|T>; out.bin likewise,
 !                                                      with the IERR of MISTRA_SET_OPTIONS_x behind the wall time
+!          shim_driver <XG|XA|XT> <in.bin> <out.bin>   Rosenbrock_x itself, batched, any of its five methods: in.bin = IPAR(20), RPAR(20), ATOL(NVAR), RTOL(NVAR),
+!                                                      TSTART, TEND, ncell, then the cells as for <G|A|T> (float64), all handed to ONE call of ROSENBROCK_BATCH_x;
+!                                                      out.bin = per cell VAR, TEXIT, HEXIT, then per cell IERR and the 8 statistics
 !          shim_driver <Eg|Ea|Et> <in.bin> <out.bin>   in.bin = ncell, then per cell VAR, FIX, ENV (the vector MISTRA_RATES_ENV_x packs,
 !                                                      mistra_kpp_rates.f90): UPDATE_RCONST_BATCH_x, then INTEGRATE_BATCH_ENV_x (rates and
 !                                                      integrator on the device, RCONST never crosses PCIe); out.bin = per cell VAR,
@@ -48,6 +51,13 @@ program shim_driver
      case ('G'); call run_batch(0, 102, 3, 331, trim(fin), trim(fout), .true.)
      case ('A'); call run_batch(1, 257, 5, 979, trim(fin), trim(fout), .true.)
      case ('T'); call run_batch(2, 417, 7, 1627, trim(fin), trim(fout), .true.)
+     case default; stop 'mechanism must be G, A or T'
+     end select
+  case ('X')
+     select case (a1(2:2))
+     case ('G'); call run_rosenbrock(0, 102, 3, 331, trim(fin), trim(fout))
+     case ('A'); call run_rosenbrock(1, 257, 5, 979, trim(fin), trim(fout))
+     case ('T'); call run_rosenbrock(2, 417, 7, 1627, trim(fin), trim(fout))
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('K', 'H', 'Q', 'V', 'S', 'C', 'R')
@@ -185,6 +195,39 @@ contains
     if (present(with_options)) write (12) dble(ierr_opt)
     close (11); close (12)
   end subroutine run_batch
+  subroutine run_rosenbrock(mech, NVAR, NFIX, NREACT, fin, fout)
+    integer, intent(in) :: mech, NVAR, NFIX, NREACT
+    character(len=*), intent(in) :: fin, fout
+    double precision :: ropt(40), tt(3)
+    double precision, allocatable :: ATOL(:), RTOL(:), VAR(:, :), FIX(:, :), RCONST(:, :), TEXIT(:), HEXIT(:), rec(:)
+    integer :: IPAR(20), n, i
+    integer, allocatable :: IERR(:), ISTAT(:, :)
+    open (11, file=fin, access='stream', form='unformatted', status='old')
+    open (12, file=fout, access='stream', form='unformatted', status='replace')
+    allocate (ATOL(NVAR), RTOL(NVAR))
+    read (11) ropt, ATOL, RTOL, tt      ! tt: TSTART, TEND, ncell
+    IPAR = int(ropt(1:20))
+    n = int(tt(3))
+    allocate (VAR(NVAR, n), FIX(NFIX, n), RCONST(NREACT, n), TEXIT(n), HEXIT(n), IERR(n), ISTAT(8, n), rec(NVAR + NFIX + NREACT))
+    do i = 1, n
+       read (11) rec
+       VAR(:, i) = rec(1:NVAR)
+       FIX(:, i) = rec(NVAR + 1:NVAR + NFIX)
+       RCONST(:, i) = rec(NVAR + NFIX + 1:)
+    end do
+    select case (mech)
+    case (0); call ROSENBROCK_BATCH_g(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT)
+    case (1); call ROSENBROCK_BATCH_a(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT)
+    case (2); call ROSENBROCK_BATCH_t(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT)
+    end select
+    do i = 1, n
+       write (12) VAR(:, i), TEXIT(i), HEXIT(i)
+    end do
+    do i = 1, n
+       write (12) dble(IERR(i)), dble(ISTAT(:, i))
+    end do
+    close (11); close (12)
+  end subroutine run_rosenbrock
   subroutine run_env(mech, NVAR, NFIX, NREACT, NENV, fin, fout)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT, NENV
     character(len=*), intent(in) :: fin, fout
