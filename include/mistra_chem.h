@@ -182,6 +182,30 @@ int mistra_chem_rosenbrock_device(int mech, int ncell, const double* d_var_in, c
                                   double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                   const double* d_hstart, void* hip_stream);
 
+/* ---- The step-control trace: the same calls (Ros3 only: ipar[3] = 2, anything else fails with a text) run by a kernel that also records every
+ * attempt that reaches ros_ErrorNorm_x (gas.f:1279).  var_out, ierr, stats and t_h are bit-identical to the untraced call's.  Per attempt r of cell c:
+ *   trace_d[c][r][0..3] = T at the start of the step | H as attempted, after any halving by ros_PrepareMatrix_x | Err | share
+ *   trace_i[c][r][0..1] = species | code
+ * species (1-based) is the one with the largest term (Yerr_i / (AbsTol_i + RelTol_i*Ymax_i))**2 of ros_ErrorNorm_x's sum: ties go to the lowest
+ * species number, a NaN term never wins, and where no term is positive species = 0 and share = 0.  share = that term / (NVAR * Err**2).
+ * code = 1 if the attempt was accepted, else 0, plus 2 x the decompositions that returned a zero pivot within the attempt.
+ * ntrace[c] is the TRUE number of attempts (= stats[c][2]); records past cap are not written, and rows past min(ntrace, cap) are not touched.
+ * cap = 0 is legal (trace_d and trace_i may then be NULL).  ctrl[c][NVAR], optional (NULL), counts per species the attempts it controlled — all of
+ * them, also those past cap.  A refusal by Rosenbrock_x (-1 .. -5) stays a result: ntrace = 0, the logs and ctrl are not written.
+ * cap < 0, a NULL ntrace and cap > 0 with a NULL log array fail with a text before a device is touched.
+ * _trace_ex: host arrays (the logs go up and come back, so untouched rows keep the caller's contents); _trace_device: device arrays, in stream order. */
+int mistra_chem_rosenbrock_trace_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                    double tstart, double tend, const double* atol, const double* rtol,
+                                    const double* rpar, const int32_t* ipar,
+                                    double* var_out, int32_t* ierr, int32_t* stats, double* t_h,
+                                    int cap, double* trace_d, int32_t* trace_i, int32_t* ntrace, int32_t* ctrl);
+int mistra_chem_rosenbrock_trace_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                        double tstart, double tend, const double* atol, const double* rtol,   /* host arrays */
+                                        const double* rpar, const int32_t* ipar,                              /* host arrays */
+                                        double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                        const double* d_hstart, void* hip_stream,
+                                        int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl);
+
 /* The method tables the kernels were compiled with (Ros2_x .. Rodas4_x, gas.f:1514-1895), pure host, works before init: method 1 .. 5, 0 = 3.
  * *S = ros_S; A15 / C15 = ros_A / ros_C, row-wise lower triangle, S*(S-1)/2 entries; M6, E6, gamma6 = ros_M, ros_E, ros_Gamma; newf6 =
  * ros_NewF (0/1); *elo = ros_ELO.  Entries past the method's own are zero; any pointer may be NULL.  (ros_Alpha is not kept: Fun_x ignores T.) */

@@ -22,11 +22,21 @@ SOURCES = ["mech_tables.cpp", "schedule.cpp", "capi.cpp", "ros3_kernel.hip", "ra
 # translation unit of its own — the product kernels' unit compiles as it does without them — and side by side
 METHOD_SOURCE = "ros_method_kernel.hip"
 METHOD_UNITS = [(mech, method) for mech in (0, 1, 2) for method in (1, 3, 4, 5)]
+# the step-control trace kernels (kernel VARIANT 4, Ros3): ros_trace_kernel.hip once per mechanism, units of their own for the same reason.  In the
+# unit lists below a trace unit is (mechanism, None).
+TRACE_SOURCE = "ros_trace_kernel.hip"
+TRACE_UNITS = [(mech, None) for mech in (0, 1, 2)]
 MAX_JOBS = 16
 
 
 def method_flags(mech, method):
+    if method is None:
+        return ["-DMISTRA_TRACE_MECH=%d" % mech]
     return ["-DMISTRA_METHOD_MECH=%d" % mech, "-DMISTRA_METHOD=%d" % method]
+
+
+def unit_source(unit):
+    return TRACE_SOURCE if unit[1] is None else METHOD_SOURCE
 
 
 def _jobs():
@@ -59,6 +69,7 @@ def build_lib(force=False, verbose=False):
     kernel_src = os.path.join(CSRC, "ros3_kernel.hip")
     units = [(src, os.path.splitext(src)[0] + ".o", [], []) for src in SOURCES]
     units += [(METHOD_SOURCE, "ros_method_%d_%d.o" % u, method_flags(*u), [kernel_src]) for u in METHOD_UNITS]      # (the unit includes ros3_kernel.hip)
+    units += [(TRACE_SOURCE, "ros_trace_%d.o" % u[0], method_flags(*u), [kernel_src]) for u in TRACE_UNITS]
     for src, name, flags, deps in units:
         path = os.path.join(CSRC, src)
         obj = os.path.join(OBJDIR, name)
@@ -77,13 +88,14 @@ def build_lib(force=False, verbose=False):
     if force or _stale(LIB, objs):
         # the look-ahead rings of ros3_kernel.hip sit in registers the compiler does not know are busy: no library is linked
         # from a kernel object in which a ring-using function's own registers reach its ring (raises).  Every code object that
-        # holds the ring functions is checked: the product unit and the twelve method units.
+        # holds the ring functions is checked: the product unit, the twelve method units and the three trace units.
+        checked = [None] + METHOD_UNITS + TRACE_UNITS
         with ThreadPoolExecutor(_jobs()) as pool:
-            reports = list(pool.map(lambda u: ring_register_report(unit=u), [None] + METHOD_UNITS))
-        for u, isa in zip([None] + METHOD_UNITS, reports):
+            reports = list(pool.map(lambda u: ring_register_report(unit=u), checked))
+        for u, isa in zip(checked, reports):
             hits = isa_hazard_report(isa["__isa_text__"])
             if hits:
-                raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly%s:\n  " % (" (method unit %s)" % (u,) if u else "")
+                raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly%s:\n  " % (" (method / trace unit %s)" % (u,) if u else "")
                                    + "\n  ".join(hits))
         cmd = [cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
         if verbose:
@@ -105,13 +117,13 @@ def ring_register_report(isa_path=None, unit=None):
     table load landing in the ring can never hit a compiler value.  Compiles the kernel source to gfx950 assembly and
     scans it.  Returns {function: highest VGPR named outside inline asm}; raises if a ring-using function reaches its ring, and if
     a function that is not one of RING_FUNCTIONS (nor an integrating kernel, which only calls them) loads into the ring at all.
-    unit: None = the product kernels' unit (ros3_kernel.hip), or one (mechanism, method) of METHOD_UNITS."""
+    unit: None = the product kernels' unit (ros3_kernel.hip), one (mechanism, method) of METHOD_UNITS or one (mechanism, None) of TRACE_UNITS."""
     import re
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         if isa_path is None:
             isa_path = os.path.join(tmp, "ros3_kernel.s")
-            src, flags = ("ros3_kernel.hip", []) if unit is None else (METHOD_SOURCE, method_flags(*unit))
+            src, flags = ("ros3_kernel.hip", []) if unit is None else (unit_source(unit), method_flags(*unit))
             cmd = [hipcc(), "--offload-arch=" + ARCH] + [f for f in COMMON if f != "-fPIC"] + flags + \
                   ["-S", "--offload-device-only", os.path.join(CSRC, src), "-o", isa_path]
             subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)

@@ -106,6 +106,8 @@ def lib():
             L.mistra_chem_rosenbrock_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _ip, _dp, _ip, _ip, _dp]
             L.mistra_chem_rosenbrock_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, _dp, _dp, _dp, _ip, vp, vp, vp, vp, vp, vp]
             L.mistra_chem_method_table.argtypes = [C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp, _dp, _dp, _ip, _dp]
+            L.mistra_chem_rosenbrock_trace_ex.argtypes = L.mistra_chem_rosenbrock_ex.argtypes + [C.c_int, _dp, _ip, _ip, _ip]
+            L.mistra_chem_rosenbrock_trace_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [C.c_int, vp, vp, vp, vp]
         L.mistra_chem_last_error.restype = C.c_char_p
         L.mistra_chem_describe.restype = C.c_char_p
         L.mistra_chem_describe.argtypes = [C.c_int]
@@ -428,6 +430,88 @@ def rosenbrock(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None, atol=
     _check(lib().mistra_chem_rosenbrock_ex(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend),
                                            *opts, out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp)))
     return IntegrateResult(out, ierr, stats), th
+
+
+# ---- the step-control trace (include/mistra_chem.h: mistra_chem_rosenbrock_trace_ex / _device)
+# t, h, err, share [ncell, cap]; species, code [ncell, cap] int32; n [ncell] int32: the TRUE number of attempts; ctrl [ncell, NVAR] int32 or None
+Trace = namedtuple("Trace", "t h err share species code n ctrl")
+
+
+def rosenbrock_trace(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None, atol=None, rtol=None, hstart=None, cap=256, ctrl=True,
+                     trace_d=None, trace_i=None):
+    """rosenbrock() (Ros3 only) run by the kernel that also records every attempt of the step control -> rosenbrock's tuple + a Trace.  Per
+    attempt: t (start of the step), h (as attempted), err, the species (1-based, 0 = none) with the largest term of the error norm's sum and its
+    share of NVAR*err**2, code = accepted + 2 * zero pivots of the attempt.  cap: records kept per cell; n counts all attempts, records past cap
+    are dropped, rows past min(n, cap) are as they were (zeros, or what the caller's trace_d [ncell, cap, 4] / trace_i [ncell, cap, 2] held).
+    ctrl: whether the per-species count of controlled attempts is wanted.  The Trace's arrays are views of the log arrays, of the inputs' kind."""
+    mid, name = _mech_id(mech)
+    nvar, nfix, nreact, _ = DIMS[name]
+    ip, rp, at, rt = _option_args(name, ipar, rpar, atol, rtol)
+    opts = (at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp), rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
+    cap = int(cap)
+    try:
+        import torch
+        is_torch = isinstance(var, torch.Tensor)
+    except ImportError:      # pragma: no cover
+        is_torch = False
+    if is_torch:
+        if not var.is_cuda:
+            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
+        init(var.device.index or 0)
+        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
+                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
+        ncell = var.numel() // nvar
+        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
+            raise MistraChemError("cell counts of var / fix / rconst differ")
+        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
+            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
+        rows = max(cap, 0)
+        td = torch.zeros((ncell, rows, 4), dtype=torch.float64, device=var.device) if trace_d is None else trace_d
+        ti = torch.zeros((ncell, rows, 2), dtype=torch.int32, device=var.device) if trace_i is None else trace_i
+        for x, dt, k in ((td, torch.float64, 4), (ti, torch.int32, 2)):
+            if x.dtype != dt or not x.is_contiguous() or x.numel() != ncell * rows * k or x.device != var.device:
+                raise MistraChemError("trace_d / trace_i: contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] tensors on the cells' device expected")
+        td, ti = td.view(ncell, rows, 4), ti.view(ncell, rows, 2)
+        nt = torch.empty(ncell, dtype=torch.int32, device=var.device)
+        ct = torch.zeros((ncell, nvar), dtype=torch.int32, device=var.device) if ctrl else None
+        out = torch.empty_like(var)
+        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
+        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
+        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
+        stream = torch.cuda.current_stream(var.device).cuda_stream
+        _check(lib().mistra_chem_rosenbrock_trace_device(mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), *opts,
+                                                         out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(),
+                                                         None if hstart is None else hstart.data_ptr(), C.c_void_p(stream), cap,
+                                                         td.data_ptr() if rows else None, ti.data_ptr() if rows else None, nt.data_ptr(),
+                                                         None if ct is None else ct.data_ptr()))
+        return IntegrateResult(out, ierr, stats), th, Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct)
+    if hstart is not None:
+        raise MistraChemError("hstart goes with the device entry: pass torch CUDA tensors (host buffers: rpar[2] is the first step size of every cell)")
+    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+    ncell = v.shape[0]
+    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
+    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
+    rows = max(cap, 0)
+    td = np.zeros((ncell, rows, 4)) if trace_d is None else trace_d
+    ti = np.zeros((ncell, rows, 2), np.int32) if trace_i is None else trace_i
+    for x, dt, k in ((td, np.float64, 4), (ti, np.int32, 2)):
+        if not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags.c_contiguous or x.size != ncell * rows * k:
+            raise MistraChemError("trace_d / trace_i: C-contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] arrays expected")
+    td, ti = td.reshape(ncell, rows, 4), ti.reshape(ncell, rows, 2)
+    nt = np.zeros(ncell, np.int32)
+    ct = np.zeros((ncell, nvar), np.int32) if ctrl else None
+    out = np.empty_like(v)
+    ierr = np.zeros(ncell, np.int32)
+    stats = np.zeros((ncell, 8), np.int32)
+    th = np.zeros((ncell, 3))
+    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
+    _check(lib().mistra_chem_rosenbrock_trace_ex(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart),
+                                                 float(tend), *opts, out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip),
+                                                 th.ctypes.data_as(_dp), cap, td.ctypes.data_as(_dp) if rows else None,
+                                                 ti.ctypes.data_as(_ip) if rows else None, nt.ctypes.data_as(_ip),
+                                                 None if ct is None else ct.ctypes.data_as(_ip)))
+    return IntegrateResult(out, ierr, stats), th, Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct)
 
 
 # ---- OPT-IN: every layer's step size carried from one column step to the next (include/mistra_chem.h: mistra_chem_set_step_reuse)

@@ -595,6 +595,8 @@ struct MechState {
   // staging of the batched host-buffer entries (grow-only)
   DevBuf<double> s_var, s_fix, s_rct, s_th, s_env, s_hst;
   DevBuf<int32_t> s_ierr, s_stats, s_sing;
+  DevBuf<double> s_trd;                    // ... and of mistra_chem_rosenbrock_trace_ex: the records, the attempt counts, the per-species counts
+  DevBuf<int32_t> s_tri, s_ntr, s_ctl;
   // where the zero-pivot rows of the LAST host-buffer call of this slot are (mistra_chem_singular_rows): cells [sing_start,
   // sing_start + sing_count) of the caller's batch in s_sing, or the one cell of the COMMON-block call in one_sing
   size_t sing_start = 0, sing_count = 0;
@@ -618,6 +620,7 @@ struct MechState {
     step_mem.release(); step_n = 0;
     s_hst.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
+    s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release();
     sing_count = 0; sing_one = false;
     drive.release(); one.release();
     pend = PendingDrive{};      // (a step issued and never fetched dies with its buffers)
@@ -632,12 +635,14 @@ struct DeviceState {
   MechState mech[3];
   bool lds_configured[3] = {false, false, false};     // hipFuncAttributeMaxDynamicSharedMemorySize is per device
   bool lds_method[3][6] = {};                         // ... and per kernel: the method kernels' [mechanism][IPAR(4)] (launch_ros_method)
+  bool lds_trace[3] = {false, false, false};          //     and the step-control trace kernels' (launch_ros_trace)
   void release() {
     if (id >= 0) (void)hipSetDevice(id);
     for (auto& m : mech) m.release();
     for (bool& c : lds_configured) c = false;
     for (auto& m : lds_method)
       for (bool& c : m) c = false;
+    for (bool& c : lds_trace) c = false;
     id = -1;
   }
 };
@@ -872,7 +877,20 @@ struct RosCall {
   int method = kRos3;             // IPAR(4), 0 resolved to Ros4 (gas.f:1057)
   int max_steps = 0;
   std::vector<double> block;
+  // mistra_chem_rosenbrock_trace_ex: the step-control trace of the call, the caller's HOST arrays for the whole batch
+  bool trace = false;
+  int cap = 0;
+  double* trace_d = nullptr;
+  int32_t *trace_i = nullptr, *ntrace = nullptr, *ctrl = nullptr;
 };
+// the arguments of the trace entries, checked before anything touches a device
+int check_trace_args(const int32_t* ipar, int cap, const double* trace_d, const int32_t* trace_i, const int32_t* ntrace) {
+  if (cap < 0) return fail("negative trace capacity");
+  if (!ntrace) return fail("null ntrace pointer");
+  if (cap > 0 && (!trace_d || !trace_i)) return fail("trace capacity > 0 with a null trace_d or trace_i pointer");
+  if (ipar[3] != 2) return fail("the step-control trace is built for Ros3 (ipar[3] = 2) only");
+  return 0;
+}
 RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol) {
   RosCall c;
   RosResolved r;
@@ -898,7 +916,13 @@ hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bo
 
 int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, int method = kRos3) {
   hipError_t e = hipErrorInvalidValue;
-  if (method != kRos3) {
+  if (a.ntrace) {      // the step-control trace kernel (Ros3 with options)
+    if (method != kRos3 || !a.opt || a.dump || a.prof) return fail("no trace kernel for this Rosenbrock method");
+    bool* c = &D.lds_trace[mech];
+    e = mech == MISTRA_MECH_GAS   ? launch_ros_trace<GasTraits, kGasNT>(a, stream, c)
+        : mech == MISTRA_MECH_AER ? launch_ros_trace<AerTraits, kAerNT>(a, stream, c)
+                                  : launch_ros_trace<TotTraits, kTotNT>(a, stream, c);
+  } else if (method != kRos3) {
     if (method < kRos2 || method > kRodas4 || !a.opt || a.dump || a.prof) return fail("no kernel for this Rosenbrock method");      // (never a quiet Ros3)
     bool* c = &D.lds_method[mech][method];
     e = mech == MISTRA_MECH_GAS   ? launch_method<GasTraits, kGasNT>(method, a, stream, c)
@@ -928,6 +952,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.tail = TailDev{k.tail_fwd.p, k.tail_bwd.p, {k.tail_fwd_addr[0].p, k.tail_fwd_addr[1].p}, {k.tail_bwd_addr[0].p, k.tail_bwd_addr[1].p}};
   a.lu_scale = ScaleDev{k.lu_scale.p, k.lu_scale_slots, k.lu_scale_slots + VM_LOOKAHEAD_ROWS};
   a.dense = DenseDev{k.dense_rows.p, k.schur_cells.p};
+  a.trace_d = nullptr; a.trace_i = nullptr; a.ntrace = nullptr; a.ctrl = nullptr; a.trace_cap = 0;      // (the trace entries set them)
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
@@ -1058,6 +1083,25 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     a.opt = S.call_opt.p;
     a.max_steps = call->max_steps;
   }
+  const bool trace = call && call->trace;
+  const size_t cap = trace ? (size_t)call->cap : 0;
+  if (trace) {      // the caller's log arrays go up first: rows the kernel does not write come back as they were
+    HIP_TRY(S.s_ntr.reserve(nc));
+    a.ntrace = S.s_ntr.p;
+    a.trace_cap = call->cap;
+    if (cap) {
+      HIP_TRY(S.s_trd.reserve(nc * cap * 4));
+      HIP_TRY(S.s_tri.reserve(nc * cap * 2));
+      HIP_TRY(hipMemcpy(S.s_trd.p, call->trace_d + batch_start * cap * 4, nc * cap * 4 * sizeof(double), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(S.s_tri.p, call->trace_i + batch_start * cap * 2, nc * cap * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
+      a.trace_d = S.s_trd.p;
+      a.trace_i = S.s_tri.p;
+    }
+    if (call->ctrl) {
+      HIP_TRY(S.s_ctl.reserve(nc * nv));
+      a.ctrl = S.s_ctl.p;
+    }
+  }
   if (hstart) {      // OPT-IN: the caller's first step size per cell (mistra_chem_integrate_hstart_ex)
     HIP_TRY(S.s_hst.reserve(nc));
     HIP_TRY(hipMemcpy(S.s_hst.p, hstart, nc * sizeof(double), hipMemcpyHostToDevice));
@@ -1095,6 +1139,14 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
   HIP_TRY(hipMemcpy(var_out, S.s_var.p, nc * nv * sizeof(double), hipMemcpyDeviceToHost));
   if (ierr) HIP_TRY(hipMemcpy(ierr, S.s_ierr.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (stats) HIP_TRY(hipMemcpy(stats, S.s_stats.p, nc * 8 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (trace) {
+    HIP_TRY(hipMemcpy(call->ntrace + batch_start, S.s_ntr.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (cap) {
+      HIP_TRY(hipMemcpy(call->trace_d + batch_start * cap * 4, S.s_trd.p, nc * cap * 4 * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(call->trace_i + batch_start * cap * 2, S.s_tri.p, nc * cap * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    if (call->ctrl) HIP_TRY(hipMemcpy(call->ctrl + batch_start * nv, S.s_ctl.p, nc * nv * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
   if (t_h) {      // device: [ncell][2] (T, Hexit) then [ncell] (H)  ->  caller: [ncell][3]
     std::vector<double> h(nc * 3);
     HIP_TRY(hipMemcpy(h.data(), S.s_th.p, nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
@@ -2106,9 +2158,10 @@ int mistra_chem_method_table(int method, int* S, double* A15, double* C15, doubl
   return 0;
 }
 
-int mistra_chem_rosenbrock_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
-                              const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
-                              int32_t* stats, double* t_h) {
+// mistra_chem_rosenbrock_ex and, with tr set (its trace members filled in), mistra_chem_rosenbrock_trace_ex
+static int rosenbrock_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                           const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
+                           int32_t* stats, double* t_h, const RosCall* tr) {
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, ncell)) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
@@ -2120,8 +2173,10 @@ int mistra_chem_rosenbrock_ex(int mech, int ncell, const double* var_in, const d
     if (g_devs[0].mech[mech].pend.active) return step_is_open(mech);
     call = decode_call(mech, ipar, rpar, atol, rtol);
   }
+  if (tr) { call.trace = true; call.cap = tr->cap; call.trace_d = tr->trace_d; call.trace_i = tr->trace_i; call.ntrace = tr->ntrace; call.ctrl = tr->ctrl; }
   if (call.ierr != 1) {      // Rosenbrock_x returns before it touches Y or the statistics (gas.f:936-1053): a result, nothing is launched
     const size_t nv = (size_t)kDims[mech].nvar, nc = (size_t)ncell;
+    if (tr) std::fill(tr->ntrace, tr->ntrace + nc, 0);      // no attempt was made: the logs and ctrl stay as they are
     if (var_out != var_in) std::memmove(var_out, var_in, nc * nv * sizeof(double));
     if (ierr) std::fill(ierr, ierr + nc, (int32_t)call.ierr);
     if (stats) std::fill(stats, stats + nc * 8, 0);
@@ -2131,9 +2186,26 @@ int mistra_chem_rosenbrock_ex(int mech, int ncell, const double* var_in, const d
   return integrate_host(mech, ncell, var_in, fix, rconst, nullptr, tstart, tend, var_out, ierr, stats, t_h, nullptr, &call);
 }
 
-int mistra_chem_rosenbrock_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
-                                  double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
-                                  int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream) {
+int mistra_chem_rosenbrock_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                              const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
+                              int32_t* stats, double* t_h) {
+  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr);
+}
+
+int mistra_chem_rosenbrock_trace_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                    const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
+                                    int32_t* stats, double* t_h, int cap, double* trace_d, int32_t* trace_i, int32_t* ntrace, int32_t* ctrl) {
+  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
+  if (int rc = check_trace_args(ipar, cap, trace_d, trace_i, ntrace)) return rc;
+  RosCall tr;
+  tr.cap = cap; tr.trace_d = trace_d; tr.trace_i = trace_i; tr.ntrace = ntrace; tr.ctrl = ctrl;
+  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, &tr);
+}
+
+// mistra_chem_rosenbrock_device and, with tr set (device arrays), mistra_chem_rosenbrock_trace_device
+static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
+                                int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream, const RosCall* tr) {
   if (ncell == 0) return check_call(mech, 0);
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
   if (!d_var_in || !d_fix || !d_rconst || !d_var_out || !d_ierr || !d_stats) return fail("null device pointer");
@@ -2148,6 +2220,7 @@ int mistra_chem_rosenbrock_device(int mech, int ncell, const double* d_var_in, c
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_ierr), call.ierr, nc, st));
     HIP_TRY(hipMemsetAsync(d_stats, 0, nc * 8 * sizeof(int32_t), st));
     if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nc * 2 * sizeof(double), st));
+    if (tr) HIP_TRY(hipMemsetAsync(tr->ntrace, 0, nc * sizeof(int32_t), st));      // no attempt was made: the logs and ctrl stay as they are
     return 0;
   }
   RosCallRing& R = t.S->call_ring;
@@ -2163,9 +2236,29 @@ int mistra_chem_rosenbrock_device(int mech, int ncell, const double* d_var_in, c
   a.hstart = d_hstart;
   a.opt = db;
   a.max_steps = call.max_steps;
+  if (tr) { a.trace_cap = tr->cap; a.trace_d = tr->trace_d; a.trace_i = tr->trace_i; a.ntrace = tr->ntrace; a.ctrl = tr->ctrl; }
   const int rc = launch(*t.D, mech, a, st, call.method);
   if (hipEventRecord(R.ev[i], st) == hipSuccess) R.pending[i] = true;      // (also behind a failed launch: the copy is queued)
   return rc;
+}
+
+int mistra_chem_rosenbrock_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                  double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
+                                  int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream) {
+  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                              d_hstart, hip_stream, nullptr);
+}
+
+int mistra_chem_rosenbrock_trace_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                        double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
+                                        double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
+                                        void* hip_stream, int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl) {
+  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
+  if (int rc = check_trace_args(ipar, cap, d_trace_d, d_trace_i, d_ntrace)) return rc;
+  RosCall tr;
+  tr.cap = cap; tr.trace_d = d_trace_d; tr.trace_i = d_trace_i; tr.ntrace = d_ntrace; tr.ctrl = d_ctrl;
+  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                              d_hstart, hip_stream, &tr);
 }
 
 int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, double* tout, int32_t* ierr_out, double* t_err,

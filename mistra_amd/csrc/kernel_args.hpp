@@ -84,6 +84,13 @@ struct KernelArgs {
   TailDev tail;
   DenseDev dense;
   const double* opt;           // [kOptTol + 2*NVAR] or null: Rosenbrock_x's options (RosOptSlot); set = the options instantiation runs (VARIANT 3)
+  // step-control trace (kernel VARIANT 4, ros_trace_kernel.hip; mistra_chem_rosenbrock_trace_ex / _device): one record per attempt that reaches
+  // ros_ErrorNorm_x.  Read by the trace kernels only; null / 0 everywhere else (capi.cpp: make_args).
+  double* trace_d;             // [ncell][trace_cap][4] or null: T at the step's start, H as attempted, Err, share of the largest term in NVAR*Err**2
+  int32_t* trace_i;            // [ncell][trace_cap][2] or null: species (1-based) of the largest term, 0 = none | code = accepted + 2 * zero pivots of the attempt
+  int32_t* ntrace;             // [ncell]: the TRUE number of attempts (records past trace_cap are not written)
+  int32_t* ctrl;               // [ncell][NVAR] or null: attempts each species controlled
+  int32_t trace_cap;
 };
 
 }  // namespace mistra

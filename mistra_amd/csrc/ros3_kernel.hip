@@ -1199,7 +1199,8 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
 template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
-  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, OPT = VARIANT == 3;
+  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, OPT = VARIANT == 3 || TRACE;
+  static_assert(!TRACE || METHOD == kRos3, "the step-control trace is a Ros3 instantiation (ros_trace_kernel.hip)");
   static_assert(METHOD == kRos3 || (OPT && METHOD >= kRos2 && METHOD <= kRodas4), "the method kernels are options instantiations");
   constexpr double kGamma1 = METHOD == kRos3 ? kRosGamma1 : kRosMethod<METHOD>.Gamma[0];
   constexpr int NVAR = MT::NVAR, NFIX = MT::NFIX, NREACT = MT::NREACT, NNZ = MT::NNZ, NCONST = MT::NCONST;
@@ -1222,6 +1223,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   if (cell >= a.ncell) return;
   if (lds_addr(lds) != 0u) {      // the VM and the tail chain address M by absolute LDS offsets
     if (t == 0) GM_(a.ierr)[cell] = -99;
+    if constexpr (TRACE) {
+      if (t == 0) GM_(a.ntrace)[cell] = 0;
+    }
     return;
   }
 
@@ -1607,9 +1611,24 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     }
   };
 
+  // VARIANT 4 (the step-control trace): the largest term of the error norm's sum and its species (1-based; 0: no term is positive), found
+  // inside the norm's own reduction — per thread, per wave as (value, index), across waves through 2*NW cells behind L::TOTAL (the trace
+  // launcher sizes them) written where the partial sums are written.  Ties go to the lowest species, a NaN term never wins (no comparison
+  // with it holds).  No barrier is added and nothing here feeds Err.
+  [[maybe_unused]] double tr_val = 0.0;
+  [[maybe_unused]] int tr_idx = 0;
+  [[maybe_unused]] int tr_halved = 0;    // decompositions of the current attempt that returned a zero pivot.  (Declared here, not in the attempt's
+                                         // own scope: a declaration there, unused, changed the product kernels' instructions.)
+  [[maybe_unused]] int ctrl_r[SPT];      // attempts this thread's species controlled: stored once, at exit
+  if constexpr (TRACE) {
+#pragma unroll
+    for (int q = 0; q < SPT; q++) ctrl_r[q] = 0;
+  }
   // ---- ros_ErrorNorm_x (gas.f:1341): wave shuffle reduction, then the NW partial sums in a fixed order
   auto error_norm = [&](const double (&y0)[SPT], const double (&y1)[SPT], const double (&ye)[SPT]) -> double {
     double part = 0.0;
+    [[maybe_unused]] double tv = 0.0;
+    [[maybe_unused]] int ti = 0;
 #pragma unroll
     for (int q = 0; q < SPT; q++) {
       const int s = q * NT + t;
@@ -1620,16 +1639,44 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         else scale = 1.0e-25 + 1.0e-3 * ymax;
         const double e = ye[q] / scale;
         part = part + e * e;
+        if constexpr (TRACE) {
+          const double term = e * e;
+          if (term > tv) { tv = term; ti = s + 1; }      // q ascending: the thread's lowest species keeps a tie
+        }
       }
     }
     part = wave_sum(part);
+    if constexpr (TRACE) {
+#pragma unroll
+      for (int m = 1; m < 64; m <<= 1) {      // both partners of a pair choose the same one: every lane ends with the wave's
+        const double ov = __shfl_xor(tv, m);
+        const int oi = __shfl_xor(ti, m);
+        if (ov > tv || (ov == tv && oi < ti)) { tv = ov; ti = oi; }
+      }
+    }
     lds_barrier();   // red[] may still be read from the previous step
     {
       int wv = wave;
       asm volatile("" : "+v"(wv));      // (the cell's address is formed here: kept across the step loop it was one more spilled register)
       if (lane == 0) red[wv] = part;
+      if constexpr (TRACE) {
+        if (lane == 0) {
+          lds[L::TOTAL + wv] = tv;
+          lds[L::TOTAL + NW + wv] = (double)ti;
+        }
+      }
     }
     lds_barrier();
+    if constexpr (TRACE) {
+      tr_val = 0.0;
+      tr_idx = 0;
+#pragma unroll
+      for (int w = 0; w < NW; w++) {
+        const double ov = lds[L::TOTAL + w];
+        const int oi = (int)lds[L::TOTAL + NW + w];
+        if (ov > tr_val || (ov == tr_val && oi < tr_idx)) { tr_val = ov; tr_idx = oi; }
+      }
+    }
     double sum = 0.0;
 #pragma unroll
     for (int w = 0; w < NW; w++) sum += red[w];
@@ -1727,6 +1774,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
 
     bool accepted = false;
     while (!accepted) {
+      if constexpr (TRACE) tr_halved = 0;
       {
         // K1's right-hand side, Fcn0 + HG*dFdT with dFdT = +0.0 (see above); independent of H
 #pragma unroll
@@ -1760,6 +1808,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
             lds_barrier();   // everyone has read flags[0] (and flags[1]) before the retry clears them
             nsng += 1;
             nconsecutive += 1;
+            if constexpr (TRACE) tr_halved += 1;
             if (nconsecutive <= 5) Hset(Hget() * 0.5);
             else { ierr = -8; break; }
           } else {
@@ -1923,6 +1972,20 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       const double H = Hget();
       double Hnew = H * Fac;
       nstp += 1;
+      if constexpr (TRACE) {      // the attempt's record: T is still the step's start, H the step as attempted (after ros_PrepareMatrix_x's halvings)
+        const bool acc = (Err <= 1.0) || (H <= hmin());
+        if (t == 0 && nstp <= a.trace_cap) {
+          const size_t r = (size_t)cell * (size_t)a.trace_cap + (size_t)(nstp - 1);
+          gptr_mut<double> td = GM_(a.trace_d) + r * 4;
+          td[0] = T; td[1] = H; td[2] = Err;
+          td[3] = tr_idx > 0 ? tr_val / (((double)NVAR * Err) * Err) : 0.0;
+          gptr_mut<int32_t> ti2 = GM_(a.trace_i) + r * 2;
+          ti2[0] = tr_idx; ti2[1] = (acc ? 1 : 0) + 2 * tr_halved;
+        }
+#pragma unroll
+        for (int q = 0; q < SPT; q++)
+          if (tr_idx == q * NT + t + 1) ctrl_r[q] += 1;
+      }
       if ((Err <= 1.0) || (H <= hmin())) {
         nacc += 1;
 #pragma unroll
@@ -1955,6 +2018,16 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       if (s < NVAR) GM_(a.var_out)[(size_t)cell * NVAR + s] = y[q];
     }
   }
+  if constexpr (TRACE) {
+    if (a.ctrl) {
+#pragma unroll
+      for (int q = 0; q < SPT; q++) {
+        const int s = q * NT + t;
+        if (s < NVAR) GM_(a.ctrl)[(size_t)cell * NVAR + s] = ctrl_r[q];
+      }
+    }
+    if (t == 0) GM_(a.ntrace)[cell] = nstp;
+  }
   if (t == 0) {
     GM_(a.ierr)[cell] = ierr;
     gptr_mut<int32_t> st = GM_(a.stats) + (size_t)cell * 8;
@@ -1972,7 +2045,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   }
 }
 
-#ifndef MISTRA_METHOD_TU      // (ros_method_kernel.hip includes this file for the kernel template alone)
+#ifndef MISTRA_METHOD_TU      // (ros_method_kernel.hip and ros_trace_kernel.hip include this file for the kernel template alone)
 // ---- launchers (one explicit instantiation per supported <mechanism, workgroup size>)
 template <class MT, int NT>
 hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_configured) {

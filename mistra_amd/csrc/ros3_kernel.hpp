@@ -100,4 +100,9 @@ hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_config
 template <class MT, int NT, int METHOD>
 hipError_t launch_ros_method(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
 
+// The step-control trace kernels (VARIANT 4: the options kernel, Ros3, plus a record per attempt; kernel_args.hpp: trace_*): a.opt and a.ntrace
+// must be set.  One explicit specialisation per mechanism, each in a translation unit of its own (ros_trace_kernel.hip).
+template <class MT, int NT>
+hipError_t launch_ros_trace(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
+
 }  // namespace mistra
