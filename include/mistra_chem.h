@@ -29,10 +29,32 @@ extern "C" {
 #define MISTRA_MECH_GAS 0 /* gas.f  : NVAR 102, NFIX 3, NREACT 331, LU_NONZERO 1110  */
 #define MISTRA_MECH_AER 1 /* aer.f  : NVAR 257, NFIX 5, NREACT 979, LU_NONZERO 6579  */
 #define MISTRA_MECH_TOT 2 /* tot.f  : NVAR 417, NFIX 7, NREACT 1627, LU_NONZERO 13503 */
+/* Two USER MECHANISM SLOTS, compiled from mechanism tables when the library is built (mistra_amd/build.py: MISTRA_USER_MECHS = at most two
+ * table paths separated by colons; unset: the demo tables demo_g and demo_a, cut from gas and aer by tools/derive_mech.py; empty: none).  The
+ * kernels of a slot are compiled for the SIZES of its table (NVAR 64 .. 512); at run time the slot loads <mech dir>/<name>.mech, <name> the
+ * stem of the build-time table: a table with the same sizes and other contents runs (the schedule is compiled at init), one with other
+ * sizes fails mistra_chem_init with "does not match the compiled kernel sizes", and so does one of the same sizes for which the schedule
+ * compiler needs more partial-sum cells than the build-time table did, plus two ("out of VM temp cells"); a directory without the table
+ * leaves the slot out and the rest of the library as it is.
+ * A user slot has: mistra_chem_dims, _mech_name, _describe, _integrate, _integrate_ex, _integrate_device, _integrate_device_hstart,
+ * _integrate_hstart_ex (rate constants, not env), _singular_rows, _debug_first_step(_ex), _check_options, _set_options, _get_options,
+ * _rosenbrock_ex and _rosenbrock_device with Ros3 (ipar[3] = 2), and the split of a host batch over the device slots.  Every other entry that
+ * takes a mechanism id (rates, hand-over, drive, liq_parm, the COMMON-block entry, step reuse, the step-control trace, the four other methods)
+ * fails for it with one text that names the slot, before it touches a device.  An id of a slot the library was not built with is an
+ * "unknown mechanism id", as 5 and up are. */
+#define MISTRA_MECH_USER0 3
+#define MISTRA_MECH_USER1 4
 
-/* Select the HIP device, load the three mechanism tables (directory: env MISTRA_MECH_DIR, else ../mech next to the
- * library) and upload their kernel schedules.  Replaces nothing in the reference (its tables are compiled in:
- * BLOCK DATA JACOBIAN_SPARSE_DATA_x, gas.f:6718 | aer.f:23480 | tot.f:44435); call once before anything else. */
+/* How many user mechanism slots this library was built with (0 .. 2).  Works before init. */
+int mistra_chem_user_mechs(void);
+
+/* "gas" | "aer" | "tot" | the stem of a user slot's table; NULL for an unknown id.  Works before init. */
+const char* mistra_chem_mech_name(int mech);
+
+/* Select the HIP device, load the mechanism tables — gas, aer, tot and those of the user slots the library was built with
+ * (directory: env MISTRA_MECH_DIR, else ../mech next to the library) — and upload their kernel schedules.  A user slot whose
+ * table is not in that directory is left out (its entries then fail with a text that says so); gas, aer and tot must be there.
+ * Replaces nothing in the reference (its tables are compiled in: BLOCK DATA JACOBIAN_SPARSE_DATA_x, gas.f:6718 | aer.f:23480 | tot.f:44435); call once before anything else. */
 int mistra_chem_init(int device);
 
 /* The same on several GPUs of the node, for a single-process caller such as the reference's Fortran program (the model is

@@ -13,6 +13,9 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(PKG, "build")
 LIB = os.path.join(LIBDIR, "libmistra_chem.so")
+# the same library WITHOUT user slots, linked beside it whenever the library has slots (capi.cpp compiled once more, every other object shared):
+# what tests/test_gpu_user_mech.py holds gas, aer and tot of the library with slots to, bit for bit.  Nothing loads it otherwise.
+LIB_NOSLOTS = os.path.join(LIBDIR, "libmistra_chem_noslots.so")
 
 ARCH = "gfx950"
 # -ffp-contract=off: one rounding per multiply and per add, as in the reference built without FMA contraction
@@ -26,16 +29,101 @@ METHOD_UNITS = [(mech, method) for mech in (0, 1, 2) for method in (1, 3, 4, 5)]
 # unit lists below a trace unit is (mechanism, None).
 TRACE_SOURCE = "ros_trace_kernel.hip"
 TRACE_UNITS = [(mech, None) for mech in (0, 1, 2)]
+# the user mechanism slots (mechanism ids 3 and 4): MISTRA_USER_MECHS = at most two table paths separated by colons, default the two demo tables
+# (tools/derive_mech.py cuts them from gas and aer), empty = a library without user slots.  Per slot user_traits_gen (a host program built from the
+# schedule compiler) writes the traits header into the build directory and ros_user_kernel.hip is compiled against it, a unit of its own for the same
+# reason.  In the unit lists below a user unit is ("user", slot).
+USER_SOURCE = "ros_user_kernel.hip"
+USER_GEN_SOURCES = ["user_traits_gen.cpp", "schedule.cpp", "mech_tables.cpp"]
+USER_DEFAULT = [os.path.join(PKG, "mech", "demo_g.mech"), os.path.join(PKG, "mech", "demo_a.mech")]
+MAX_USER_MECHS = 2
 MAX_JOBS = 16
 
 
+def user_mech_tables():
+    """The tables of the user slots, from MISTRA_USER_MECHS (unset: the demo tables; empty: none)."""
+    env = os.environ.get("MISTRA_USER_MECHS")
+    if env is None:      # the demo tables are derived from gas.mech and aer.mech, not committed (binary): written here where missing or stale
+        from . import mechderive
+        return mechderive.ensure_demo_tables()
+    tables = [os.path.abspath(p) for p in env.split(":") if p]
+    if len(tables) > MAX_USER_MECHS:
+        raise RuntimeError("MISTRA_USER_MECHS names %d tables, there are %d user mechanism slots" % (len(tables), MAX_USER_MECHS))
+    if len({os.path.splitext(os.path.basename(p))[0] for p in tables}) != len(tables):
+        raise RuntimeError("MISTRA_USER_MECHS: the tables' names are the mechanisms' names, they must differ")
+    return tables
+
+
+def build_traits_gen(force=False, verbose=False):
+    """-> path of the host program that writes a slot's traits header (user_traits_gen.cpp with the schedule compiler)"""
+    os.makedirs(OBJDIR, exist_ok=True)
+    exe = os.path.join(OBJDIR, "user_traits_gen")
+    srcs = [os.path.join(CSRC, f) for f in USER_GEN_SOURCES]
+    deps = srcs + [os.path.join(CSRC, f) for f in ("schedule.hpp", "mech_tables.hpp", "kernel_args.hpp")]
+    if force or _stale(exe, deps):
+        cmd = [hipcc(), "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-o", exe] + srcs
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
+    return exe
+
+
+def user_traits(table, slot, out, gen=None):
+    """Runs the schedule compiler on `table` and writes the traits header of user slot `slot` to `out` -> the traits as a dict (integers, booleans,
+    'NT', 'NAME', and 'WAVES_PER_SIMD' as the macro it names).  Raises RuntimeError with the generator's text where it refuses the table."""
+    import re
+    gen = gen or build_traits_gen()
+    r = subprocess.run([gen, table, str(slot), out], stderr=subprocess.PIPE, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("user mechanism slot %d: %s" % (slot, r.stderr.strip()))
+    text = open(out).read()
+    traits = {}
+    for k, v in re.findall(r"\b([A-Z_]+) = (\w+)", text):
+        traits[k] = {"true": True, "false": False}.get(v, int(v) if v.isdigit() else v)
+    for k, v in re.findall(r"kUser\d(NT|LdsTotal|LdsAB|LdsJB|Temps) = (\d+)", text):
+        traits[k] = int(v)
+    traits["NAME"] = re.search(r'kUser\dName\[\] = "(\w+)"', text).group(1)
+    return traits
+
+
+def prepare_user_mechs(force=False, verbose=False):
+    """Writes build/user_traits_<slot>.hpp for every slot and build/user_mechs.cfg (what the slots were built from); both only when their content
+    changes, so that the units that include them are rebuilt exactly then.  -> (number of slots, the files)"""
+    tables = user_mech_tables()
+    files = []
+    if tables:
+        gen = build_traits_gen(force, verbose)
+    for slot, table in enumerate(tables):
+        tmp = os.path.join(OBJDIR, "user_traits_%d.hpp.new" % slot)
+        final = os.path.join(OBJDIR, "user_traits_%d.hpp" % slot)
+        files.append(final)
+        if not force and not _stale(final, [table, gen]) and ('"%s"' % os.path.splitext(os.path.basename(table))[0]) in open(final).read():
+            continue      # (written from this table by this generator)
+        user_traits(table, slot, tmp, gen)
+        if not os.path.exists(final) or open(final).read() != open(tmp).read():
+            os.replace(tmp, final)
+        else:
+            os.remove(tmp)
+    cfg = os.path.join(OBJDIR, "user_mechs.cfg")
+    text = "".join("%d %s\n" % (i, os.path.splitext(os.path.basename(t))[0]) for i, t in enumerate(tables)) or "none\n"
+    if not os.path.exists(cfg) or open(cfg).read() != text:
+        with open(cfg, "w") as f:
+            f.write(text)
+    files.append(cfg)
+    return len(tables), files
+
+
 def method_flags(mech, method):
+    if mech == "user":
+        return ["-DMISTRA_USER_SLOT=%d" % method, "-DMISTRA_USER_MECHS=%d" % (method + 1), "-I" + OBJDIR]
     if method is None:
         return ["-DMISTRA_TRACE_MECH=%d" % mech]
     return ["-DMISTRA_METHOD_MECH=%d" % mech, "-DMISTRA_METHOD=%d" % method]
 
 
 def unit_source(unit):
+    if unit[0] == "user":
+        return USER_SOURCE
     return TRACE_SOURCE if unit[1] is None else METHOD_SOURCE
 
 
@@ -67,9 +155,15 @@ def build_lib(force=False, verbose=False):
     from concurrent.futures import ThreadPoolExecutor
     objs, cmds = [], []
     kernel_src = os.path.join(CSRC, "ros3_kernel.hip")
-    units = [(src, os.path.splitext(src)[0] + ".o", [], []) for src in SOURCES]
+    n_user, user_files = prepare_user_mechs(force, verbose)
+    user_units = [("user", slot) for slot in range(n_user)]
+    units = [(src, os.path.splitext(src)[0] + ".o", ["-DMISTRA_USER_MECHS=%d" % n_user, "-I" + OBJDIR] if src == "capi.cpp" else [],
+              user_files if src == "capi.cpp" else []) for src in SOURCES]
     units += [(METHOD_SOURCE, "ros_method_%d_%d.o" % u, method_flags(*u), [kernel_src]) for u in METHOD_UNITS]      # (the unit includes ros3_kernel.hip)
     units += [(TRACE_SOURCE, "ros_trace_%d.o" % u[0], method_flags(*u), [kernel_src]) for u in TRACE_UNITS]
+    units += [(USER_SOURCE, "ros_user_%d.o" % u[1], method_flags(*u), [kernel_src] + user_files) for u in user_units]
+    if n_user:
+        units.append(("capi.cpp", "capi_noslots.o", ["-DMISTRA_USER_MECHS=0", "-I" + OBJDIR], []))
     for src, name, flags, deps in units:
         path = os.path.join(CSRC, src)
         obj = os.path.join(OBJDIR, name)
@@ -85,22 +179,26 @@ def build_lib(force=False, verbose=False):
                 print(" ".join(cmd))
             subprocess.run(cmd, check=True)
         list(pool.map(compile_one, cmds))
-    if force or _stale(LIB, objs):
+    noslots_objs = [o for o in objs if not os.path.basename(o).startswith("ros_user_") and os.path.basename(o) != "capi.o"] if n_user else []
+    objs = [o for o in objs if os.path.basename(o) != "capi_noslots.o"]
+    if force or _stale(LIB, objs) or (n_user and _stale(LIB_NOSLOTS, noslots_objs)):
         # the look-ahead rings of ros3_kernel.hip sit in registers the compiler does not know are busy: no library is linked
         # from a kernel object in which a ring-using function's own registers reach its ring (raises).  Every code object that
-        # holds the ring functions is checked: the product unit, the twelve method units and the three trace units.
-        checked = [None] + METHOD_UNITS + TRACE_UNITS
+        # holds the ring functions is checked: the product unit, the twelve method units, the three trace units and the user slots' units.
+        checked = [None] + METHOD_UNITS + TRACE_UNITS + user_units
         with ThreadPoolExecutor(_jobs()) as pool:
             reports = list(pool.map(lambda u: ring_register_report(unit=u), checked))
         for u, isa in zip(checked, reports):
             hits = isa_hazard_report(isa["__isa_text__"])
             if hits:
-                raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly%s:\n  " % (" (method / trace unit %s)" % (u,) if u else "")
+                raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly%s:\n  " % (" (method / trace / user unit %s)" % (u,) if u else "")
                                    + "\n  ".join(hits))
         cmd = [cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
+        if n_user:
+            subprocess.run([cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB_NOSLOTS] + noslots_objs + ["-ldl"], check=True)
     return LIB
 
 
@@ -117,7 +215,8 @@ def ring_register_report(isa_path=None, unit=None):
     table load landing in the ring can never hit a compiler value.  Compiles the kernel source to gfx950 assembly and
     scans it.  Returns {function: highest VGPR named outside inline asm}; raises if a ring-using function reaches its ring, and if
     a function that is not one of RING_FUNCTIONS (nor an integrating kernel, which only calls them) loads into the ring at all.
-    unit: None = the product kernels' unit (ros3_kernel.hip), one (mechanism, method) of METHOD_UNITS or one (mechanism, None) of TRACE_UNITS."""
+    unit: None = the product kernels' unit (ros3_kernel.hip), one (mechanism, method) of METHOD_UNITS, one (mechanism, None) of TRACE_UNITS or
+    ("user", slot) of a user mechanism slot (its traits header must be in the build directory: prepare_user_mechs)."""
     import re
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:

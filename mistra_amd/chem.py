@@ -21,7 +21,21 @@ from .mechtab import MECH_IDS, MECH_NAMES
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MISTRA_CHEM_LIB", os.path.join(_PKG, "lib", "libmistra_chem.so"))   # override: diagnostic builds
 
-DIMS = {"gas": (102, 3, 331, 1110), "aer": (257, 5, 979, 6579), "tot": (417, 7, 1627, 13503)}
+USER_IDS = {"user0": 3, "user1": 4}      # the user mechanism slots (include/mistra_chem.h: MISTRA_MECH_USER0, _USER1)
+
+
+class _Dims(dict):
+    """(NVAR, NFIX, NREACT, LU_NONZERO) by mechanism name; the sizes of a user slot's table are asked of the library the first time."""
+
+    def __missing__(self, name):
+        mid, name = _mech_id(name)
+        n = [C.c_int32(0) for _ in range(4)]
+        _check(lib().mistra_chem_dims(mid, *(C.byref(x) for x in n)))
+        self[name] = tuple(x.value for x in n)
+        return self[name]
+
+
+DIMS = _Dims({"gas": (102, 3, 331, 1110), "aer": (257, 5, 979, 6579), "tot": (417, 7, 1627, 13503)})
 STAT_NAMES = ("Nfun", "Njac", "Nstp", "Nacc", "Nrej", "Ndec", "Nsol", "Nsng")   # COMMON /Statistics/, gas.f:913
 IERR_TEXT = {1: "success", -6: "too many steps", -7: "step size too small", -8: "matrix repeatedly singular"}
 
@@ -108,6 +122,9 @@ def lib():
             L.mistra_chem_method_table.argtypes = [C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp, _dp, _dp, _ip, _dp]
             L.mistra_chem_rosenbrock_trace_ex.argtypes = L.mistra_chem_rosenbrock_ex.argtypes + [C.c_int, _dp, _ip, _ip, _ip]
             L.mistra_chem_rosenbrock_trace_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [C.c_int, vp, vp, vp, vp]
+        if hasattr(L, "mistra_chem_user_mechs"):
+            L.mistra_chem_mech_name.restype = C.c_char_p
+            L.mistra_chem_mech_name.argtypes = [C.c_int]
         L.mistra_chem_last_error.restype = C.c_char_p
         L.mistra_chem_describe.restype = C.c_char_p
         L.mistra_chem_describe.argtypes = [C.c_int]
@@ -148,13 +165,35 @@ def finalize():
 
 
 def describe(mech):
-    return lib().mistra_chem_describe(MECH_IDS[mech]).decode()
+    return lib().mistra_chem_describe(_mech_id(mech)[0]).decode()
+
+
+def user_mechs():
+    """The names of the user mechanism slots this library was built with (mistra_chem_user_mechs, mistra_chem_mech_name): ids 3 and 4."""
+    L = lib()
+    if not hasattr(L, "mistra_chem_user_mechs"):      # (an older build loaded for a same-box A/B)
+        return []
+    return [L.mistra_chem_mech_name(3 + i).decode() for i in range(L.mistra_chem_user_mechs())]
 
 
 def _mech_id(mech):
+    """-> (mechanism id, name).  "gas" | "aer" | "tot" | 0..2, and for a user slot its table's name, "user0" / "user1", or 3 / 4."""
     if isinstance(mech, str):
-        return MECH_IDS[mech], mech
-    return int(mech), MECH_NAMES[int(mech)]
+        if mech in MECH_IDS:
+            return MECH_IDS[mech], mech
+        users = user_mechs()
+        if mech in USER_IDS and USER_IDS[mech] - 3 < len(users):
+            return USER_IDS[mech], users[USER_IDS[mech] - 3]
+        if mech in users:
+            return 3 + users.index(mech), mech
+        raise MistraChemError("unknown mechanism %r (this library has gas, aer, tot%s)" % (mech, "".join(", " + u for u in users)))
+    mid = int(mech)
+    if mid < len(MECH_NAMES):
+        return mid, MECH_NAMES[mid]
+    users = user_mechs()
+    if mid - 3 < len(users):
+        return mid, users[mid - 3]
+    raise MistraChemError("unknown mechanism id %d" % mid)
 
 
 def integrate(mech, var, fix, rconst, tin=0.0, tout=10.0, device=None):

@@ -23,6 +23,7 @@
 #include "ros3_kernel.hpp"
 #include "ros_methods.hpp"
 #include "schedule.hpp"
+#include "user_mechs.hpp"
 
 using namespace mistra;
 
@@ -44,14 +45,77 @@ int fail(const std::string& msg) {
     if (e_ != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e_));          \
   } while (0)
 
-const char* kMechName[3] = {"gas", "aer", "tot"};
 // the sizes of gas_Parameters.h | aer_Parameters.h | tot_Parameters.h, as the kernel is compiled for them (mistra_chem_dims needs no init)
 struct MechDims {
   int nvar, nfix, nreact, lu_nonzero;
 };
 template <class MT>
-constexpr MechDims dims_of() { return MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}; }
-constexpr MechDims kDims[3] = {dims_of<GasTraits>(), dims_of<AerTraits>(), dims_of<TotTraits>()};
+bool traits_match(const MechTables& t, int n_jnz, int tail_regs, bool scale_pass, const DenseTail& dense) {
+  return dense.nd == MT::DENSE_ND && dense.kb == MT::DENSE_KB && tail_regs == MT::TAIL_REGS && scale_pass == MT::SCALE_PASS && t.nvar == MT::NVAR && t.nfix == MT::NFIX && t.nreact == MT::NREACT && t.nnz == MT::NNZ && t.nb == MT::NB &&
+         t.nconst == MT::NCONST && n_jnz == MT::NJNZ;
+}
+// method: IPAR(4) resolved (ros_methods.hpp); anything but Ros3 runs its method kernel, which reads a.opt
+template <class MT, int NT>
+hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bool* configured);
+
+// ---- ONE ROW PER MECHANISM: everything the entries below need to know about a compiled kernel.  gas, aer, tot, then the user slots this library was
+// built with (user_mechs.hpp: traits generated from the slots' tables at build time).  A user slot has the product, first-step-dump and options
+// (Ros3) kernels and no method or trace kernels; its table is <mech dir>/<name>.mech and it never runs the dense tail block.
+using LaunchFn = hipError_t (*)(const KernelArgs&, hipStream_t, bool*);
+struct MechDesc {
+  const char* name;
+  MechDims dims;
+  int nt;                          // workgroup size the kernels are instantiated with
+  uint32_t ab_base, jb_base;       // LDS byte addresses of the A/B product array and of Jac_SP's B products (the gather-sum tables hold addresses)
+  int max_temps;
+  bool user;
+  bool (*match)(const MechTables&, int, int, bool, const DenseTail&);      // the loaded table against the compiled sizes
+  LaunchFn ros3;                                                           // product | phase timing | first-step dump | options (Ros3)
+  hipError_t (*method)(int, const KernelArgs&, hipStream_t, bool*);        // Ros2, Ros4, Rodas3, Rodas4 (nullptr: not built)
+  LaunchFn trace;                                                          // the step-control trace kernel (nullptr: not built)
+};
+template <class MT, int NT>
+constexpr MechDesc builtin_mech(const char* name) {
+  return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
+                  MT::MAX_TEMPS, false, &traits_match<MT>, &launch_ros3<MT, NT>, &launch_method<MT, NT>, &launch_ros_trace<MT, NT>};
+}
+template <class MT, int NT>
+constexpr MechDesc user_mech(const char* name) {
+  return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
+                  MT::MAX_TEMPS, true, &traits_match<MT>, &launch_ros3<MT, NT>, nullptr, nullptr};
+}
+constexpr int kBuiltinMechs = 3, kMaxMechs = 5;
+constexpr int kNumMechs = kBuiltinMechs + MISTRA_USER_MECHS;
+const MechDesc kMech[kNumMechs] = {
+    builtin_mech<GasTraits, kGasNT>("gas"), builtin_mech<AerTraits, kAerNT>("aer"), builtin_mech<TotTraits, kTotNT>("tot"),
+#if MISTRA_USER_MECHS >= 1
+    user_mech<User0Traits, kUser0NT>(kUser0Name),
+#endif
+#if MISTRA_USER_MECHS >= 2
+    user_mech<User1Traits, kUser1NT>(kUser1Name),
+#endif
+};
+static_assert(MISTRA_MECH_USER0 == kBuiltinMechs && MISTRA_MECH_USER1 == kBuiltinMechs + 1 && kMaxMechs == kBuiltinMechs + 2, "mechanism ids of the user slots");
+bool known_mech(int mech) { return mech >= 0 && mech < kNumMechs; }
+// "Rosenbrock_g" | "Rosenbrock_a" | "Rosenbrock_t" | "Rosenbrock (<table>)"
+std::string rosenbrock_name(int mech) { return kMech[mech].user ? std::string("Rosenbrock (") + kMech[mech].name + ")" : std::string("Rosenbrock_") + "gat"[mech]; }
+// What a user slot does not have: every entry but dims, describe, the integrate family on rate constants, singular_rows, the first-step dump, the
+// options and Rosenbrock_x with Ros3.  One text, before anything touches a device.
+int fail_user_slot(int mech, const char* what) {
+  g_err = std::string("user mechanism slot ") + std::to_string(mech - kBuiltinMechs) + " (" + kMech[mech].name + ") has no " + what +
+          ": a user slot integrates (INTEGRATE_x on rate constants, Rosenbrock_x with Ros3 and its options, the first-step dump) and nothing else";
+  return 1;
+}
+// Rosenbrock_x on a user slot: a valid method other than Ros3 (IPAR(4) = 0 selects Ros4) is refused before anything touches a device
+int user_slot_method(int mech, const int32_t* ipar) {
+  if (!known_mech(mech) || !kMech[mech].user || !ipar || ipar[3] == 2 || ipar[3] < 0 || ipar[3] > 5) return 0;
+  return fail_user_slot(mech, "kernel for this Rosenbrock method (Ros2, Ros4, Rodas3, Rodas4)");
+}
+// -> 0 for gas, aer, tot; the refusal for a user slot and for an id that is no mechanism
+int builtin_only(int mech, const char* what) {
+  if (!known_mech(mech)) return fail("unknown mechanism id");
+  return kMech[mech].user ? fail_user_slot(mech, what) : 0;
+}
 
 template <class T>
 struct DevBuf {
@@ -632,10 +696,10 @@ struct MechState {
 // Slot 0 is the primary device: the host-buffer entry points and mistra_chem_describe use it.
 struct DeviceState {
   int id = -1;
-  MechState mech[3];
-  bool lds_configured[3] = {false, false, false};     // hipFuncAttributeMaxDynamicSharedMemorySize is per device
-  bool lds_method[3][6] = {};                         // ... and per kernel: the method kernels' [mechanism][IPAR(4)] (launch_ros_method)
-  bool lds_trace[3] = {false, false, false};          //     and the step-control trace kernels' (launch_ros_trace)
+  MechState mech[kMaxMechs];                          // (the rows of kMech: the slots past kNumMechs are never set up)
+  bool lds_configured[kMaxMechs] = {};                // hipFuncAttributeMaxDynamicSharedMemorySize is per device
+  bool lds_method[kMaxMechs][6] = {};                 // ... and per kernel: the method kernels' [mechanism][IPAR(4)] (launch_ros_method)
+  bool lds_trace[kMaxMechs] = {};                     //     and the step-control trace kernels' (launch_ros_trace)
   void release() {
     if (id >= 0) (void)hipSetDevice(id);
     for (auto& m : mech) m.release();
@@ -664,11 +728,11 @@ struct RosOptions {
   double rpar[20] = {0.0};
   RosResolved r;
   std::vector<double> block;      // the device block: RosOptSlot scalars, then AbsTol(1:NVAR), RelTol(1:NVAR) as the integrator uses them
-} g_opts[3];
+} g_opts[kMaxMechs];
 
 // ---- OPT-IN step reuse of the batched driver (mistra_chem_set_step_reuse): per mechanism, process-wide host state; MISTRA_CHEM_HSTART_REUSE=1 in the
 // environment turns all three on, read once — by the first initialisation or the first look at the flags, whichever comes first (g_mu held)
-bool g_step_reuse[3] = {false, false, false};
+bool g_step_reuse[kBuiltinMechs] = {false, false, false};      // (a user slot has no batched driver)
 bool g_step_env_read = false;
 void read_step_env() {
   if (g_step_env_read) return;
@@ -716,42 +780,29 @@ std::string mech_dir() {
   return "mech";
 }
 
-int default_nt(int mech) { return mech == MISTRA_MECH_GAS ? kGasNT : mech == MISTRA_MECH_AER ? kAerNT : kTotNT; }      // the workgroup sizes ros3_kernel.hip instantiates
-
-template <class MT>
-bool traits_match(const MechTables& t, int n_jnz, int tail_regs, bool scale_pass, const DenseTail& dense) {
-  return dense.nd == MT::DENSE_ND && dense.kb == MT::DENSE_KB && tail_regs == MT::TAIL_REGS && scale_pass == MT::SCALE_PASS && t.nvar == MT::NVAR && t.nfix == MT::NFIX && t.nreact == MT::NREACT && t.nnz == MT::NNZ && t.nb == MT::NB &&
-         t.nconst == MT::NCONST && n_jnz == MT::NJNZ;
-}
-
 int setup_mech(DeviceState& D, int mech) {
   MechState& S = D.mech[mech];
-  const std::string name = kMechName[mech], base = mech_dir() + "/" + name;
+  const MechDesc& M = kMech[mech];
+  const std::string name = M.name, base = mech_dir() + "/" + name;
   std::string err;
+  if (M.user) {      // a mechanism directory without the slot's table (a caller's own MISTRA_MECH_DIR with gas, aer and tot alone): the library comes up
+                     // as it did before it had slots, and the slot's entries say that its table was not there (check_call).  A table that is there and
+                     // cannot be read or has other sizes fails the init like any other.
+    FILE* f = std::fopen((base + ".mech").c_str(), "rb");
+    if (!f) return 0;
+    std::fclose(f);
+  }
   if (!S.tab.load(base + ".mech", &err)) return fail(err);
-  S.nt = default_nt(mech);
-  const bool nt_ok = (mech == MISTRA_MECH_GAS && S.nt == kGasNT) || (mech == MISTRA_MECH_AER && S.nt == kAerNT) ||
-                     (mech == MISTRA_MECH_TOT && S.nt == kTotNT);
-  if (!nt_ok) return fail(std::string("no kernel instantiated for workgroup size ") + std::to_string(S.nt) + " of " + kMechName[mech]);
-  // LDS byte address of the A/B product array for this <mechanism, workgroup size> (the gather-sum tables hold addresses)
-  const uint32_t ab_base = 8u * (uint32_t)(mech == MISTRA_MECH_GAS   ? LdsLayout<GasTraits, kGasNT>::AB
-                                           : mech == MISTRA_MECH_AER ? LdsLayout<AerTraits, kAerNT>::AB
-                                                                     : LdsLayout<TotTraits, kTotNT>::AB);
+  S.nt = M.nt;
   KernelSchedule K;
   try {
-    const int max_temps = mech == MISTRA_MECH_GAS ? GasTraits::MAX_TEMPS : mech == MISTRA_MECH_AER ? AerTraits::MAX_TEMPS : TotTraits::MAX_TEMPS;
-    const DenseConfig dc = dense_config(S.tab);
-    const uint32_t jb_base = 8u * (uint32_t)(mech == MISTRA_MECH_GAS   ? LdsLayout<GasTraits, kGasNT>::JB
-                                             : mech == MISTRA_MECH_AER ? LdsLayout<AerTraits, kAerNT>::JB
-                                                                       : LdsLayout<TotTraits, kTotNT>::JB);
-    K = build_kernel_schedule(S.tab, S.nt, ab_base, max_temps, dc.nd, dc.kb, jb_base);
+    // (a user slot never runs the dense tail block, whatever its NVAR: its kernels are compiled without it)
+    const DenseConfig dc = M.user ? DenseConfig{0, 0} : dense_config(S.tab);
+    K = build_kernel_schedule(S.tab, S.nt, M.ab_base, M.max_temps, dc.nd, dc.kb, M.jb_base);
   } catch (const std::exception& ex) {
     return fail(std::string("schedule compiler: ") + ex.what());
   }
-  bool ok = mech == MISTRA_MECH_GAS   ? traits_match<GasTraits>(S.tab, K.n_jnz, K.tail.regs, K.lu_scale.nslots > 0, K.dense)
-            : mech == MISTRA_MECH_AER ? traits_match<AerTraits>(S.tab, K.n_jnz, K.tail.regs, K.lu_scale.nslots > 0, K.dense)
-                                      : traits_match<TotTraits>(S.tab, K.n_jnz, K.tail.regs, K.lu_scale.nslots > 0, K.dense);
-  if (!ok) return fail(name + ": mechanism table does not match the compiled kernel sizes");
+  if (!M.match(S.tab, K.n_jnz, K.tail.regs, K.lu_scale.nslots > 0, K.dense)) return fail(name + ": mechanism table does not match the compiled kernel sizes");
   S.text = name + ": " + describe(K);
   if (int rc = S.k.upload(S.tab, K)) return rc;
   // the optional tables: a mechanism without the file has no such routine (the entries that need one say so)
@@ -840,25 +891,25 @@ int resolve_options(int mech, const int32_t* ipar, const double* rpar, const dou
     else return -4;
   }
   const double roundoff = 2.220446049250313e-16;                  // epsilon(ONE), gas.f:973
-  const int uplim = r->vector ? kDims[mech].nvar : 1;
+  const int uplim = r->vector ? kMech[mech].dims.nvar : 1;
   for (int i = 0; i < uplim; i++)                                 // gas.f:1045 (written so that a NaN passes, as it does there)
     if (atol[i] <= 0.0 || rtol[i] <= 10.0 * roundoff || rtol[i] >= 1.0) return -5;
   return 1;
 }
 
 std::string options_refusal(int mech, int ierr) {
-  return std::string("Rosenbrock_") + "gat"[mech] + " would refuse these options, IERR = " + std::to_string(ierr) + " " + ros_error_text(ierr);
+  return rosenbrock_name(mech) + " would refuse these options, IERR = " + std::to_string(ierr) + " " + ros_error_text(ierr);
 }
 int method_built(int mech, const int32_t* ipar) {
   static const char* names[6] = {"Ros4 (IPAR(4) = 0 selects it)", "Ros2", "Ros3", "Ros4", "Rodas3", "Rodas4"};
   if (ipar[3] == 2) return 0;
-  return fail(std::string("the ") + kMechName[mech] + " kernel is built for Ros3 (IPAR(4) = 2) only: " + names[ipar[3]] + " is a valid method of Rosenbrock_" +
-              "gat"[mech] + " that this library does not have");
+  return fail(std::string("the ") + kMech[mech].name + " kernel is built for Ros3 (IPAR(4) = 2) only: " + names[ipar[3]] + " is a valid method of " +
+              rosenbrock_name(mech) + " that this library does not have");
 }
 
 // the options block the options kernels read, from a decode that returned 1
 std::vector<double> options_block(int mech, const RosResolved& r, const double* atol, const double* rtol) {
-  const size_t nv = (size_t)kDims[mech].nvar;
+  const size_t nv = (size_t)kMech[mech].dims.nvar;
   std::vector<double> b((size_t)kOptTol + 2 * nv, 0.0);
   b[kOptHmin] = r.hmin; b[kOptHmax] = r.hmax; b[kOptHstart] = r.hstart;
   b[kOptFacMin] = r.facmin; b[kOptFacMax] = r.facmax; b[kOptFacRej] = r.facrej; b[kOptFacSafe] = r.facsafe;
@@ -902,7 +953,6 @@ RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const dou
   return c;
 }
 
-// method: IPAR(4) resolved (ros_methods.hpp); anything but Ros3 runs its method kernel, which reads a.opt
 template <class MT, int NT>
 hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bool* configured) {
   switch (method) {
@@ -915,22 +965,19 @@ hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bo
 }
 
 int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, int method = kRos3) {
+  const MechDesc& M = kMech[mech];
   hipError_t e = hipErrorInvalidValue;
   if (a.ntrace) {      // the step-control trace kernel (Ros3 with options)
+    if (!M.trace) return fail_user_slot(mech, "step-control trace");
     if (method != kRos3 || !a.opt || a.dump || a.prof) return fail("no trace kernel for this Rosenbrock method");
-    bool* c = &D.lds_trace[mech];
-    e = mech == MISTRA_MECH_GAS   ? launch_ros_trace<GasTraits, kGasNT>(a, stream, c)
-        : mech == MISTRA_MECH_AER ? launch_ros_trace<AerTraits, kAerNT>(a, stream, c)
-                                  : launch_ros_trace<TotTraits, kTotNT>(a, stream, c);
+    e = M.trace(a, stream, &D.lds_trace[mech]);
   } else if (method != kRos3) {
+    if (!M.method) return fail_user_slot(mech, "kernel for this Rosenbrock method (Ros2, Ros4, Rodas3, Rodas4)");      // (never a quiet Ros3)
     if (method < kRos2 || method > kRodas4 || !a.opt || a.dump || a.prof) return fail("no kernel for this Rosenbrock method");      // (never a quiet Ros3)
-    bool* c = &D.lds_method[mech][method];
-    e = mech == MISTRA_MECH_GAS   ? launch_method<GasTraits, kGasNT>(method, a, stream, c)
-        : mech == MISTRA_MECH_AER ? launch_method<AerTraits, kAerNT>(method, a, stream, c)
-                                  : launch_method<TotTraits, kTotNT>(method, a, stream, c);
-  } else if (mech == MISTRA_MECH_GAS) e = launch_ros3<GasTraits, kGasNT>(a, stream, &D.lds_configured[mech]);
-  else if (mech == MISTRA_MECH_AER) e = launch_ros3<AerTraits, kAerNT>(a, stream, &D.lds_configured[mech]);
-  else e = launch_ros3<TotTraits, kTotNT>(a, stream, &D.lds_configured[mech]);
+    e = M.method(method, a, stream, &D.lds_method[mech][method]);
+  } else {
+    e = M.ros3(a, stream, &D.lds_configured[mech]);
+  }
   if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
   return 0;
 }
@@ -959,16 +1006,21 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
 
 PackDev pack_dev(const MechState& S) { return S.pack.dev(S.tab.nreact, S.k.consts.p); }
 
-int check_call(int mech, int ncell) {
-  if (mech < 0 || mech > 2) return fail("unknown mechanism id");
+// user_ok: the entry exists for a user slot (the integrate family); every other entry refuses one here, before it looks at a device
+int check_call(int mech, int ncell, bool user_ok = false, const char* what = "such routine") {
+  if (!known_mech(mech)) return fail("unknown mechanism id");
+  if (kMech[mech].user && !user_ok) return fail_user_slot(mech, what);
   if (ncell < 0) return fail("negative cell count");
+  if (g_inited && !g_devs.empty() && kMech[mech].user && !g_devs[0].mech[mech].ready)
+    return fail(std::string("user mechanism slot ") + std::to_string(mech - kBuiltinMechs) + ": " + kMech[mech].name + ".mech was not in the mechanism directory (" + mech_dir() +
+                ") when mistra_chem_init ran");
   if (!g_inited || g_devs.empty() || !g_devs[0].mech[mech].ready) return fail("mistra_chem_init has not been called (or failed)");
   return 0;
 }
 
 // the groups of tables an entry needs are there
 int require(const MechState& S, int mech, unsigned need) {
-  const std::string m = kMechName[mech];
+  const std::string m = kMech[mech].name;
   if ((need & kNeedPackTable) && !S.pack.ready) return fail("no hand-over table for the " + m + " mechanism");
   if ((need & kNeedMaps) && !S.pack.maps_ready) return fail("mistra_chem_set_species_maps has not been called for the " + m + " mechanism");
   if ((need & kNeedRates) && !S.rates.ready) return fail("no device rate table for the " + m + " mechanism");
@@ -988,7 +1040,7 @@ struct Slot {
 // The preamble of a device-pointer entry: the buffers decide the device.  The call runs on the slot `p` lives on — the first slot set up
 // on that device — with the tables `need` names; the calling thread is switched to that device.
 int on_device(int mech, int ncell, const void* p, const char* what, unsigned need, Slot* t) {
-  if (int rc = check_call(mech, ncell)) return rc;
+  if (int rc = check_call(mech, ncell, need == 0)) return rc;
   hipPointerAttribute_t attr;
   if (hipPointerGetAttributes(&attr, p) != hipSuccess) return fail(std::string(what) + " is not a device pointer");
   DeviceState* D = nullptr;
@@ -1005,7 +1057,7 @@ int on_device(int mech, int ncell, const void* p, const char* what, unsigned nee
 // mechanism's staging, species maps or singular-row record, which a column step issued by mistra_chem_drive_begin may still be using —
 // refused while such a step is open.
 int step_is_open(int mech) {
-  return fail(std::string("a column step of the ") + kMechName[mech] + " mechanism is open (mistra_chem_drive_begin): fetch it with mistra_chem_drive_end first");
+  return fail(std::string("a column step of the ") + kMech[mech].name + " mechanism is open (mistra_chem_drive_begin): fetch it with mistra_chem_drive_end first");
 }
 int on_primary(int mech, unsigned need, bool mutates, Slot* t) {
   DeviceState& D = g_devs[0];
@@ -1041,7 +1093,7 @@ int init_locked(int n, const int* ids) {
   for (size_t i = 0; i < want.size(); i++) {
     HIP_TRY(hipSetDevice(want[i]));
     g_devs[i].id = want[i];
-    for (int mech = 0; mech < 3; mech++)
+    for (int mech = 0; mech < kNumMechs; mech++)
       if (int rc = setup_mech(g_devs[i], mech)) return rc;
   }
   HIP_TRY(hipSetDevice(g_devs[0].id));      // the calling thread ends up on the primary device
@@ -1057,7 +1109,7 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
                       const double* env = nullptr, const double* hstart = nullptr, const RosCall* call = nullptr) {
   HIP_TRY(hipSetDevice(D.id));
   MechState& S = D.mech[mech];
-  const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact, nc = (size_t)ncell;
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nc = (size_t)ncell;
   HIP_TRY(S.s_var.reserve(nc * nv));
   HIP_TRY(S.s_fix.reserve(nc * nf));
   HIP_TRY(S.s_rct.reserve(nc * nr));
@@ -1131,7 +1183,7 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     for (size_t c = 0; c < nc; c++)
       for (int k = 0; k < kProfSlots; k++) sum[k] += (double)h[c * kProfSlots + k];
     const char* names[kProfSlots] = {"fun", "jac", "prepare", "lu", "solve(rest)", "norm", "other", "total", "solve_head_fwd", "solve_tail", "solve_head_bwd", "lu_scale", "lu_dense", "jac_products", "jac_sums", "fun_products"};
-    std::fprintf(stderr, "[mistra_chem profile] %s, %zu cells, mean shader-clock ticks per cell:", kMechName[mech], nc);
+    std::fprintf(stderr, "[mistra_chem profile] %s, %zu cells, mean shader-clock ticks per cell:", kMech[mech].name, nc);
     for (int k = 0; k < kProfSlots; k++) std::fprintf(stderr, " %s=%.0f (%.1f%%)", names[k], sum[k] / nc, 100.0 * sum[k] / sum[7]);
     std::fprintf(stderr, "\n");
     prof.release();
@@ -1181,7 +1233,7 @@ int column_step(DeviceState& D, int mech, int ncell, const ColumnDev& c, double 
   const PackDev P = pack_dev(S);
   LAUNCH_TRY(launch_pack(P, ncell, c.s1, c.s3, c.sl1, c.sion1, c.scal, c.var, c.fix, st));
   if (c.c_packed) {      // [ncell][NVAR + NFIX]
-    const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nl = (size_t)ncell;
+    const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nl = (size_t)ncell;
     HIP_TRY(hipMemcpy2DAsync(c.c_packed, (nv + nf) * sizeof(double), c.var, nv * sizeof(double), nv * sizeof(double), nl, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpy2DAsync(c.c_packed + nv, (nv + nf) * sizeof(double), c.fix, nf * sizeof(double), nf * sizeof(double), nl, hipMemcpyDeviceToDevice, st));
   }
@@ -1208,7 +1260,7 @@ DriveLayout drive_layout(const MechState& S, int mech, size_t nl, bool bg, bool 
   const PackTable& T = S.pack.tab;
   DriveLayout L;
   L.nl = nl; L.j1 = (size_t)S.pack.j1; L.j5 = (size_t)S.pack.j5; L.nsl = (size_t)T.j2 * T.nkc; L.nsi = (size_t)T.j6 * T.nkc;
-  L.nv = (size_t)kDims[mech].nvar; L.nf = (size_t)kDims[mech].nfix; L.nr = (size_t)kDims[mech].nreact; L.ne = (size_t)S.rates.nenv;
+  L.nv = (size_t)kMech[mech].dims.nvar; L.nf = (size_t)kMech[mech].dims.nfix; L.nr = (size_t)kMech[mech].dims.nreact; L.ne = (size_t)S.rates.nenv;
   const size_t d8 = sizeof(double), nb = 2 * (size_t)kBudSlots;
   Layout B;
   L.s1 = B.take(nl * L.j1 * d8); L.s3 = B.take(nl * L.j5 * d8); L.sl1 = B.take(nl * L.nsl * d8); L.si = B.take(nl * L.nsi * d8);
@@ -1313,13 +1365,17 @@ extern "C" {
 const char* mistra_chem_last_error(void) { return g_err.c_str(); }
 
 int mistra_chem_dims(int mech, int* nvar, int* nfix, int* nreact, int* lu_nonzero) {
-  if (mech < 0 || mech > 2) return fail("unknown mechanism id");
-  if (nvar) *nvar = kDims[mech].nvar;
-  if (nfix) *nfix = kDims[mech].nfix;
-  if (nreact) *nreact = kDims[mech].nreact;
-  if (lu_nonzero) *lu_nonzero = kDims[mech].lu_nonzero;
+  if (!known_mech(mech)) return fail("unknown mechanism id");
+  if (nvar) *nvar = kMech[mech].dims.nvar;
+  if (nfix) *nfix = kMech[mech].dims.nfix;
+  if (nreact) *nreact = kMech[mech].dims.nreact;
+  if (lu_nonzero) *lu_nonzero = kMech[mech].dims.lu_nonzero;
   return 0;
 }
+
+int mistra_chem_user_mechs(void) { return MISTRA_USER_MECHS; }
+
+const char* mistra_chem_mech_name(int mech) { return known_mech(mech) ? kMech[mech].name : nullptr; }
 
 int mistra_chem_init(int device) {
   std::lock_guard<std::mutex> lock(g_mu);
@@ -1342,7 +1398,7 @@ void mistra_chem_finalize(void) {
 }
 
 const char* mistra_chem_describe(int mech) {
-  if (mech < 0 || mech > 2 || !g_inited || g_devs.empty() || !g_devs[0].mech[mech].ready) return "";
+  if (!known_mech(mech) || !g_inited || g_devs.empty() || !g_devs[0].mech[mech].ready) return "";
   return g_devs[0].mech[mech].text.c_str();
 }
 
@@ -1356,7 +1412,7 @@ int mistra_chem_integrate_device(int mech, int ncell, const double* d_var_in, co
 int mistra_chem_integrate_device_hstart(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
                                         double tin, double tout, double* d_var_out, int32_t* d_ierr, int32_t* d_stats,
                                         double* d_texit_hexit, const double* d_hstart, void* hip_stream) {
-  if (ncell == 0) return check_call(mech, 0);      // (nothing to do, but an uninitialised library says so)
+  if (ncell == 0) return check_call(mech, 0, true);      // (nothing to do, but an uninitialised library says so)
   if (!d_var_in || !d_fix || !d_rconst || !d_var_out || !d_ierr || !d_stats) return fail("null device pointer");
   Slot t;
   if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
@@ -1384,11 +1440,12 @@ int mistra_chem_table_stack_depth(const char* path, int stcoeff) {
 }
 
 int mistra_chem_rates_env_size(int mech) {
-  if (mech < 0 || mech > 2 || !g_inited || g_devs.empty() || !g_devs[0].mech[mech].rates.ready) return 0;
+  if (!known_mech(mech) || !g_inited || g_devs.empty() || !g_devs[0].mech[mech].rates.ready) return 0;
   return g_devs[0].mech[mech].rates.nenv;
 }
 
 int mistra_chem_update_rconst_device(int mech, int ncell, const double* d_env, double* d_rconst, void* hip_stream) {
+  if (int rc = builtin_only(mech, "rate table")) return rc;
   if (ncell == 0) return check_call(mech, 0);
   if (!d_env || !d_rconst) return fail("null device pointer");
   Slot t;
@@ -1398,6 +1455,7 @@ int mistra_chem_update_rconst_device(int mech, int ncell, const double* d_env, d
 }
 
 int mistra_chem_update_rconst(int mech, int ncell, const double* env, double* rconst) {
+  if (int rc = builtin_only(mech, "rate table")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, ncell)) return rc;
   if (ncell == 0) return 0;
@@ -1419,6 +1477,7 @@ int mistra_chem_update_rconst(int mech, int ncell, const double* env, double* rc
 // ---- the hand-over halves of x_drive (pack.hip)
 
 int mistra_chem_drive_dims(int mech, int* j2, int* j6, int* nkc, int* nbgs) {
+  if (int rc = builtin_only(mech, "hand-over tables")) return rc;
   if (int rc = check_call(mech, 1)) return rc;
   const MechState& S = g_devs[0].mech[mech];
   if (int rc = require(S, mech, kNeedPackTable)) return rc;
@@ -1431,10 +1490,11 @@ int mistra_chem_drive_dims(int mech, int* j2, int* j6, int* nkc, int* nbgs) {
 
 int mistra_chem_set_species_maps(int mech, int j1, const int32_t* gas_m2k, const int32_t* gas_k2m, int j5, const int32_t* rad_m2k,
                                  const int32_t* rad_k2m) {
+  if (int rc = builtin_only(mech, "hand-over tables")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, 1)) return rc;
   if (j1 < 0 || j5 < 0 || (j1 > 0 && (!gas_m2k || !gas_k2m)) || (j5 > 0 && (!rad_m2k || !rad_k2m))) return fail("bad species maps");
-  const int nvar = kDims[mech].nvar;
+  const int nvar = kMech[mech].dims.nvar;
   std::lock_guard<std::mutex> lock(g_mu);
   Slot t;
   if (int rc = on_primary(mech, kNeedPackTable, true, &t)) return rc;      // (the maps are the same on every slot)
@@ -1465,6 +1525,7 @@ int mistra_chem_set_species_maps(int mech, int j1, const int32_t* gas_m2k, const
 
 int mistra_chem_pack_device(int mech, int ncell, const double* d_s1, const double* d_s3, double* d_sl1, double* d_sion1, const double* d_scal,
                             double* d_var, double* d_fix, void* hip_stream) {
+  if (int rc = builtin_only(mech, "hand-over tables")) return rc;
   if (ncell == 0) return 0;
   if (!d_s1 || !d_s3 || !d_sl1 || !d_sion1 || !d_scal || !d_var || !d_fix) return fail("null device pointer");
   Slot t;
@@ -1474,6 +1535,7 @@ int mistra_chem_pack_device(int mech, int ncell, const double* d_s1, const doubl
 }
 
 int mistra_chem_unpack_device(int mech, int ncell, const double* d_var, double* d_s1, double* d_s3, double* d_sl1, double* d_sion1, void* hip_stream) {
+  if (int rc = builtin_only(mech, "hand-over tables")) return rc;
   if (ncell == 0) return 0;
   if (!d_var || !d_s1 || !d_s3 || !d_sl1 || !d_sion1) return fail("null device pointer");
   Slot t;
@@ -1484,6 +1546,7 @@ int mistra_chem_unpack_device(int mech, int ncell, const double* d_var, double* 
 
 int mistra_chem_budgets_device(int mech, int ncell, const double* d_var, const double* d_fix, const double* d_rconst, double dt, double* d_bg,
                                double* d_bgs, void* hip_stream) {
+  if (int rc = builtin_only(mech, "hand-over tables")) return rc;
   if (ncell == 0) return 0;
   if (!d_var || !d_fix || !d_rconst) return fail("null device pointer");
   Slot t;
@@ -1493,6 +1556,7 @@ int mistra_chem_budgets_device(int mech, int ncell, const double* d_var, const d
 }
 
 int mistra_chem_rates_env_from_c_device(int mech, int ncell, const double* d_var, const double* d_fix, double* d_env, void* hip_stream) {
+  if (int rc = builtin_only(mech, "hand-over tables")) return rc;
   if (ncell == 0) return 0;
   if (!d_var || !d_fix || !d_env) return fail("null device pointer");
   Slot t;
@@ -1504,6 +1568,7 @@ int mistra_chem_rates_env_from_c_device(int mech, int ncell, const double* d_var
 int mistra_chem_drive_device(int mech, int ncell, double* d_s1, double* d_s3, double* d_sl1, double* d_sion1, const double* d_scal, double* d_env,
                              double* d_var, double* d_fix, double tin, double dt, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                              double* d_bg, double* d_bgs, void* hip_stream) {
+  if (int rc = builtin_only(mech, "batched driver")) return rc;
   if (ncell == 0) return 0;
   if (!d_s1 || !d_s3 || !d_sl1 || !d_sion1 || !d_scal || !d_env || !d_var || !d_fix || !d_ierr || !d_stats) return fail("null device pointer");
   Slot t;
@@ -1521,11 +1586,12 @@ int mistra_chem_drive_device(int mech, int ncell, double* d_s1, double* d_s3, do
 int mistra_chem_drive_begin(int mech, int nlayer, const int32_t* layer, int n, double* s1, double* s3, double* sl1, double* sion1, const double* scal,
                             const double* env, double tin, double dt, int32_t* ierr, int32_t* stats, double* t_h, double* bg, int nrxn,
                             const int32_t* bg_level, double* bgs, double* c_packed) {
+  if (int rc = builtin_only(mech, "batched driver")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, nlayer)) return rc;
   if (nlayer == 0) return 0;
   if (!layer || !s1 || !s3 || !sl1 || !sion1 || !scal || !env) return fail("null host pointer");
-  if (bg && (!bg_level || nrxn < kDims[mech].nreact)) return fail("bg needs bg_level and nrxn >= NREACT");
+  if (bg && (!bg_level || nrxn < kMech[mech].dims.nreact)) return fail("bg needs bg_level and nrxn >= NREACT");
   std::lock_guard<std::mutex> lock(g_mu);
   Slot t;
   if (int rc = on_primary(mech, kNeedPack | kNeedRates, true, &t)) return rc;
@@ -1583,6 +1649,7 @@ int mistra_chem_drive_begin(int mech, int nlayer, const int32_t* layer, int n, d
 }
 
 int mistra_chem_drive_end(int mech) {
+  if (int rc = builtin_only(mech, "batched driver")) return rc;
   if (int rc = check_call(mech, 1)) return rc;
   std::lock_guard<std::mutex> lock(g_mu);
   DeviceState& D = g_devs[0];
@@ -1626,6 +1693,7 @@ int mistra_chem_drive(int mech, int nlayer, const int32_t* layer, int n, double*
 int mistra_chem_fast_k_mt_device(int mech, int nlayer, const double* d_ff, const double* d_rq, const int32_t* kw, int nkw, int ka, int ifeed,
                                  int nkc_l, const double* d_cw, const double* d_cm, const double* d_freep, const double* d_alpha,
                                  const double* d_vmean, double* d_xkmt, const double* d_t, const double* d_p, double* d_vt, void* hip_stream) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (nlayer == 0) return check_call(mech, 0);
   if (!d_ff || !d_rq || !kw || !d_cw || !d_cm || !d_freep || !d_alpha || !d_vmean || !d_xkmt) return fail("null pointer");
   if (d_vt && (!d_t || !d_p)) return fail("the sedimentation velocity needs the layers' temperature and pressure (d_t, d_p)");
@@ -1638,6 +1706,7 @@ int mistra_chem_fast_k_mt_device(int mech, int nlayer, const double* d_ff, const
 }
 
 int mistra_chem_henry_device(int mech, int nlayer, const double* d_tt, double* d_henry, void* hip_stream) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (nlayer == 0) return check_call(mech, 0);
   if (!d_tt || !d_henry) return fail("null pointer");
   Slot t;
@@ -1647,6 +1716,7 @@ int mistra_chem_henry_device(int mech, int nlayer, const double* d_tt, double* d
 }
 
 int mistra_chem_st_coeff_device(int mech, int nlayer, int lp_joyce14bc, int lp_buxmann15alph, const double* d_env, double* d_alpha, void* hip_stream) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (nlayer == 0) return check_call(mech, 0);
   if (!d_env || !d_alpha) return fail("null pointer");
   Slot t;
@@ -1657,6 +1727,7 @@ int mistra_chem_st_coeff_device(int mech, int nlayer, int lp_joyce14bc, int lp_b
 }
 
 int mistra_chem_v_mean_device(int mech, int nlayer, const double* d_tt, double* d_vmean, void* hip_stream) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (nlayer == 0) return check_call(mech, 0);
   if (!d_tt || !d_vmean) return fail("null pointer");
   Slot t;
@@ -1668,6 +1739,7 @@ int mistra_chem_v_mean_device(int mech, int nlayer, const double* d_tt, double* 
 
 int mistra_chem_equil_co_device(int mech, int nlayer, int nkc, int j6, const double* d_tt, const double* d_conv2, const double* d_xgamma,
                                 double* d_xkef, double* d_xkeb, void* hip_stream) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (nlayer == 0) return check_call(mech, 0);
   if (!d_tt || !d_conv2 || !d_xgamma || !d_xkef || !d_xkeb) return fail("null pointer");
   Slot t;
@@ -1705,6 +1777,7 @@ int mistra_chem_unpin_host(void* p) {
 int mistra_chem_fast_k_mt(int mech, int nlayer, const double* ff, const double* rq, const int32_t* kw, int nkw, int ka, int ifeed, int nkc_l,
                           const double* cw, const double* cm, const double* freep, const double* alpha, const double* vmean, double* xkmt,
                           const double* t, const double* p, double* vt) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, nlayer)) return rc;
   if (nlayer == 0) return 0;
@@ -1734,6 +1807,7 @@ int mistra_chem_fast_k_mt(int mech, int nlayer, const double* ff, const double* 
 }
 
 int mistra_chem_henry(int mech, int nlayer, const double* tt, double* henry) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, nlayer)) return rc;
   if (nlayer == 0) return 0;
@@ -1810,6 +1884,7 @@ int mistra_chem_cw_rc(int nlayer, int nkt, int nka, int dry, const double* ff, c
 }
 
 int mistra_chem_st_coeff(int mech, int nlayer, int lp_joyce14bc, int lp_buxmann15alph, const double* env, double* alpha) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, nlayer)) return rc;
   if (nlayer == 0) return 0;
@@ -1831,6 +1906,7 @@ int mistra_chem_st_coeff(int mech, int nlayer, int lp_joyce14bc, int lp_buxmann1
 }
 
 int mistra_chem_v_mean(int mech, int nlayer, const double* tt, double* vmean) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, nlayer)) return rc;
   if (nlayer == 0) return 0;
@@ -1852,6 +1928,7 @@ int mistra_chem_v_mean(int mech, int nlayer, const double* tt, double* vmean) {
 }
 
 int mistra_chem_equil_co(int mech, int nlayer, int nkc, int j6, const double* tt, const double* conv2, const double* xgamma, double* xkef, double* xkeb) {
+  if (int rc = builtin_only(mech, "liquid-phase routines")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, nlayer)) return rc;
   if (nlayer == 0) return 0;
@@ -1875,7 +1952,7 @@ int mistra_chem_equil_co(int mech, int nlayer, int nkc, int j6, const double* tt
 // ---- OPT-IN step reuse of the batched driver
 
 int mistra_chem_set_step_reuse(int mech, int on) {
-  if (mech < 0 || mech > 2) return fail("unknown mechanism id");
+  if (int rc = builtin_only(mech, "step reuse")) return rc;
   std::lock_guard<std::mutex> lock(g_mu);
   read_step_env();
   if (g_inited && !g_devs.empty() && g_devs[0].mech[mech].pend.active) return step_is_open(mech);
@@ -1887,13 +1964,14 @@ int mistra_chem_set_step_reuse(int mech, int on) {
 }
 
 int mistra_chem_get_step_reuse(int mech) {
-  if (mech < 0 || mech > 2) return 0;
+  if (!known_mech(mech) || kMech[mech].user) return 0;
   std::lock_guard<std::mutex> lock(g_mu);
   read_step_env();
   return g_step_reuse[mech] ? 1 : 0;
 }
 
 int mistra_chem_get_step_memory(int mech, int n, double* h) {
+  if (int rc = builtin_only(mech, "step reuse")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, n)) return rc;
   if (n == 0) return 0;
@@ -1906,12 +1984,13 @@ int mistra_chem_get_step_memory(int mech, int n, double* h) {
     std::memset(h, 0, (size_t)n * sizeof(double));
     return 0;
   }
-  if (S.step_n != n) return fail("the step memory of the " + std::string(kMechName[mech]) + " mechanism holds " + std::to_string(S.step_n) + " layers, not " + std::to_string(n));
+  if (S.step_n != n) return fail("the step memory of the " + std::string(kMech[mech].name) + " mechanism holds " + std::to_string(S.step_n) + " layers, not " + std::to_string(n));
   HIP_TRY(hipMemcpy(h, S.step_mem.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
 int mistra_chem_set_step_memory(int mech, int n, const double* h) {
+  if (int rc = builtin_only(mech, "step reuse")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, n)) return rc;
   if (n == 0) return fail("mistra_chem_set_step_memory: n must be the model's layer count");
@@ -1937,7 +2016,7 @@ int mistra_chem_debug_set_max_steps(int max_steps) {
 
 int mistra_chem_check_options(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, double interval,
                               int32_t* ierr, double* resolved_r, int32_t* resolved_i) {
-  if (mech < 0 || mech > 2) return fail("unknown mechanism id");
+  if (!known_mech(mech)) return fail("unknown mechanism id");
   if (!ipar || !rpar || !atol || !rtol || !ierr) return fail("null pointer");
   *ierr = 0;
   RosResolved r;
@@ -1959,7 +2038,7 @@ int mistra_chem_check_options(int mech, const int32_t* ipar, const double* rpar,
 
 int mistra_chem_set_options(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, int32_t* ierr) {
   if (int rc = lazy_init()) return rc;
-  if (int rc = check_call(mech, 0)) return rc;
+  if (int rc = check_call(mech, 0, true)) return rc;
   if (ierr) *ierr = 0;
   if (ipar && (!rpar || !atol || !rtol)) return fail("null pointer");
   std::lock_guard<std::mutex> lock(g_mu);
@@ -2003,13 +2082,13 @@ int mistra_chem_set_options(int mech, const int32_t* ipar, const double* rpar, c
 }
 
 int mistra_chem_get_options(int mech, int32_t* is_set, int32_t* ipar, double* rpar, double* atol, double* rtol) {
-  if (mech < 0 || mech > 2) return fail("unknown mechanism id");
+  if (!known_mech(mech)) return fail("unknown mechanism id");
   if (!is_set) return fail("null pointer");
   std::lock_guard<std::mutex> lock(g_mu);
   const RosOptions& o = g_opts[mech];
   *is_set = o.set ? 1 : 0;
   if (!o.set) return 0;
-  const size_t nv = (size_t)kDims[mech].nvar;
+  const size_t nv = (size_t)kMech[mech].dims.nvar;
   if (ipar) std::memcpy(ipar, o.ipar, sizeof o.ipar);
   if (rpar) std::memcpy(rpar, o.rpar, sizeof o.rpar);
   if (atol) std::memcpy(atol, o.block.data() + kOptTol, nv * sizeof(double));
@@ -2024,7 +2103,7 @@ int mistra_chem_debug_first_step(int mech, int ncell, const double* var_in, cons
 
 int mistra_chem_debug_first_step_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                                     double tout, const double* hstart, double* dump, double* var_out, int32_t* ierr, int32_t* stats) {
-  if (int rc = check_call(mech, ncell)) return rc;
+  if (int rc = check_call(mech, ncell, true)) return rc;
   if (ncell == 0) return 0;
   if (!var_in || !fix || !rconst || !dump) return fail("null host pointer");
   std::lock_guard<std::mutex> lock(g_mu);
@@ -2032,8 +2111,8 @@ int mistra_chem_debug_first_step_ex(int mech, int ncell, const double* var_in, c
   if (int rc = on_primary(mech, 0, true, &t)) return rc;
   MechState& S = *t.S;
   if (S.opt.p) return fail("the first-step dump keeps INTEGRATE_x's values: clear the options (mistra_chem_set_options) first");
-  const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact, nc = (size_t)ncell;
-  const size_t per = 5 * nv + 2 * (size_t)kDims[mech].lu_nonzero + 2;
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nc = (size_t)ncell;
+  const size_t per = 5 * nv + 2 * (size_t)kMech[mech].dims.lu_nonzero + 2;
   DevBuf<double> d_dump, d_hstart;
   HIP_TRY(S.s_var.reserve(nc * nv));
   HIP_TRY(S.s_fix.reserve(nc * nf));
@@ -2089,6 +2168,7 @@ int mistra_chem_integrate_ex(int mech, int ncell, const double* var_in, const do
 
 int mistra_chem_integrate_env_ex(int mech, int ncell, const double* var_in, const double* fix, const double* env, double tin, double tout,
                                  double* var_out, int32_t* ierr, int32_t* stats, double* t_h) {
+  if (int rc = builtin_only(mech, "rate table")) return rc;
   return integrate_host(mech, ncell, var_in, fix, nullptr, env, tin, tout, var_out, ierr, stats, t_h);
 }
 
@@ -2100,14 +2180,15 @@ int mistra_chem_integrate_hstart_ex(int mech, int ncell, const double* var_in, c
 
 static int integrate_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, const double* env, double tin,
                           double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart, const RosCall* call) {
+  if (env && known_mech(mech) && kMech[mech].user) return fail_user_slot(mech, "rate table");      // (mistra_chem_integrate_hstart_ex with env)
   if (int rc = lazy_init()) return rc;
-  if (int rc = check_call(mech, ncell)) return rc;
+  if (int rc = check_call(mech, ncell, true)) return rc;
   if (ncell == 0) return 0;
   if (!var_in || !fix || !var_out || (!rconst && !env)) return fail("null host pointer");
   std::lock_guard<std::mutex> lock(g_mu);
   Slot t;
   if (int rc = on_primary(mech, env ? kNeedRates : 0, true, &t)) return rc;
-  const size_t nv = (size_t)kDims[mech].nvar, nf = (size_t)kDims[mech].nfix, nr = (size_t)kDims[mech].nreact;
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact;
   const size_t ne = env ? (size_t)t.S->rates.nenv : 0;
   const int ndev = (int)g_devs.size();
   for (auto& d : g_devs) d.mech[mech].sing_count = 0;
@@ -2162,8 +2243,9 @@ int mistra_chem_method_table(int method, int* S, double* A15, double* C15, doubl
 static int rosenbrock_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                            const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
                            int32_t* stats, double* t_h, const RosCall* tr) {
+  if (int rc = user_slot_method(mech, ipar)) return rc;
   if (int rc = lazy_init()) return rc;
-  if (int rc = check_call(mech, ncell)) return rc;
+  if (int rc = check_call(mech, ncell, true)) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
   if (ncell == 0) return 0;
   if (!var_in || !fix || !rconst || !var_out) return fail("null host pointer");
@@ -2175,7 +2257,7 @@ static int rosenbrock_host(int mech, int ncell, const double* var_in, const doub
   }
   if (tr) { call.trace = true; call.cap = tr->cap; call.trace_d = tr->trace_d; call.trace_i = tr->trace_i; call.ntrace = tr->ntrace; call.ctrl = tr->ctrl; }
   if (call.ierr != 1) {      // Rosenbrock_x returns before it touches Y or the statistics (gas.f:936-1053): a result, nothing is launched
-    const size_t nv = (size_t)kDims[mech].nvar, nc = (size_t)ncell;
+    const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
     if (tr) std::fill(tr->ntrace, tr->ntrace + nc, 0);      // no attempt was made: the logs and ctrl stay as they are
     if (var_out != var_in) std::memmove(var_out, var_in, nc * nv * sizeof(double));
     if (ierr) std::fill(ierr, ierr + nc, (int32_t)call.ierr);
@@ -2195,6 +2277,7 @@ int mistra_chem_rosenbrock_ex(int mech, int ncell, const double* var_in, const d
 int mistra_chem_rosenbrock_trace_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                                     const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
                                     int32_t* stats, double* t_h, int cap, double* trace_d, int32_t* trace_i, int32_t* ntrace, int32_t* ctrl) {
+  if (int rc = builtin_only(mech, "step-control trace")) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
   if (int rc = check_trace_args(ipar, cap, trace_d, trace_i, ntrace)) return rc;
   RosCall tr;
@@ -2206,7 +2289,8 @@ int mistra_chem_rosenbrock_trace_ex(int mech, int ncell, const double* var_in, c
 static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                 double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
                                 int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream, const RosCall* tr) {
-  if (ncell == 0) return check_call(mech, 0);
+  if (int rc = user_slot_method(mech, ipar)) return rc;
+  if (ncell == 0) return check_call(mech, 0, true);
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
   if (!d_var_in || !d_fix || !d_rconst || !d_var_out || !d_ierr || !d_stats) return fail("null device pointer");
   Slot t;
@@ -2214,7 +2298,7 @@ static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, con
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of options blocks)
   const RosCall call = decode_call(mech, ipar, rpar, atol, rtol);
-  const size_t nv = (size_t)kDims[mech].nvar, nc = (size_t)ncell;
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
   if (call.ierr != 1) {      // the refusal as a result, in stream order; no kernel of the library runs
     if (d_var_out != d_var_in) HIP_TRY(hipMemcpyAsync(d_var_out, d_var_in, nc * nv * sizeof(double), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_ierr), call.ierr, nc, st));
@@ -2253,6 +2337,7 @@ int mistra_chem_rosenbrock_trace_device(int mech, int ncell, const double* d_var
                                         double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                                         double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
                                         void* hip_stream, int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl) {
+  if (int rc = builtin_only(mech, "step-control trace")) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
   if (int rc = check_trace_args(ipar, cap, d_trace_d, d_trace_i, d_ntrace)) return rc;
   RosCall tr;
@@ -2263,10 +2348,11 @@ int mistra_chem_rosenbrock_trace_device(int mech, int ncell, const double* d_var
 
 int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, double* tout, int32_t* ierr_out, double* t_err,
                                         double* h_err, int32_t* nsng) {
+  if (int rc = builtin_only(mech, "COMMON-block entry")) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, 1)) return rc;
   if (!gdata || !tin || !tout) return fail("null pointer");
-  const int nv = kDims[mech].nvar, nf = kDims[mech].nfix, nr = kDims[mech].nreact;
+  const int nv = kMech[mech].dims.nvar, nf = kMech[mech].dims.nfix, nr = kMech[mech].dims.nreact;
   double* c = static_cast<double*>(gdata);          // C(NSPEC) = VAR | FIX
   double* atol = c + nv + nf + nr + 2;              // after RCONST(NREACT), TIME, DT
   double* rtol = atol + nv;
@@ -2312,7 +2398,7 @@ int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, doub
 }
 
 int mistra_chem_singular_rows(int mech, int cell, int32_t* rows8) {
-  if (int rc = check_call(mech, 1)) return rc;
+  if (int rc = check_call(mech, 1, true)) return rc;
   if (!rows8 || cell < 0) return fail("bad argument");
   std::lock_guard<std::mutex> lock(g_mu);
   Slot t;
