@@ -38,7 +38,8 @@ extern "C" {
  * leaves the slot out and the rest of the library as it is.
  * A user slot has: mistra_chem_dims, _mech_name, _describe, _integrate, _integrate_ex, _integrate_device, _integrate_device_hstart,
  * _integrate_hstart_ex (rate constants, not env), _singular_rows, _debug_first_step(_ex), _check_options, _set_options, _get_options,
- * _rosenbrock_ex and _rosenbrock_device with Ros3 (ipar[3] = 2), and the split of a host batch over the device slots.  Every other entry that
+ * _rosenbrock_ex and _rosenbrock_device with Ros3 (ipar[3] = 2), their per-cell tolerance forms _rosenbrock_cells_ex / _cells_device likewise,
+ * _cell_atol_device, and the split of a host batch over the device slots.  Every other entry that
  * takes a mechanism id (rates, hand-over, drive, liq_parm, the COMMON-block entry, step reuse, the step-control trace, the four other methods)
  * fails for it with one text that names the slot, before it touches a device.  An id of a slot the library was not built with is an
  * "unknown mechanism id", as 5 and up are. */
@@ -227,6 +228,48 @@ int mistra_chem_rosenbrock_trace_device(int mech, int ncell, const double* d_var
                                         double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                         const double* d_hstart, void* hip_stream,
                                         int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl);
+
+/* ---- Tolerances PER CELL: the four calls above with atol[ncell][ntol], rtol[ncell][ntol] in place of the shared pair; everything else is as documented
+ * there (the options block of the call — ipar, rpar — travels as it does, MISTRA_ROSENBROCK_CALLS_IN_FLIGHT of them; d_hstart; the trace is Ros3 only;
+ * a user slot runs Ros3 and refuses the other methods and the trace with its text).  Cell c integrates with row c.
+ *   ntol is 1 or NVAR.  ipar[1] = 0 (vector tolerances) needs ntol = NVAR and reads every entry of a row; ipar[1] /= 0 reads entry 0 of each row, with
+ *   either width, and never looks at the others.  Any other ntol, a NULL tolerance array or a negative ncell fail with a text and a non-zero return
+ *   before a device is touched: these are the entries' rule, not codes of Rosenbrock_x.
+ *   IERR = -5 is a result PER CELL: a cell whose row holds, in an entry that is read, AbsTol <= 0, RelTol <= 10*eps or RelTol >= 1 (gas.f:1045-1053,
+ *   compared as written there: a NaN passes) leaves as a refused call leaves — var_out = var_in (aliasing stays legal), ierr = -5, stats, t_h /
+ *   d_texit_hexit zero, ntrace = 0, its log rows and ctrl not written — and the other cells run.  The kernel makes that check, since the rows may live
+ *   on the device.  -1 .. -4 depend on ipar / rpar alone: whole-call results decided on the host, ahead of -5 as Rosenbrock_x orders its checks, no kernel.
+ * _cells_ex / _trace_cells_ex: host arrays; the batch is split over the device slots, each block with its own tolerance rows; they fail while a column
+ * step of the mechanism is open.
+ * _cells_device / _trace_cells_device: d_atol, d_rtol are DEVICE arrays on the cells' device, read by the kernel IN STREAM ORDER without a copy: they
+ * must stay valid and unchanged until the kernel has run (rpar, ipar stay host arrays read before the call returns).  Host memory the device cannot
+ * reach is refused with a text. */
+int mistra_chem_rosenbrock_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                    double tstart, double tend, const double* atol, const double* rtol, int ntol,
+                                    const double* rpar, const int32_t* ipar,
+                                    double* var_out, int32_t* ierr, int32_t* stats, double* t_h);
+int mistra_chem_rosenbrock_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                        double tstart, double tend, const double* d_atol, const double* d_rtol, int ntol,   /* device arrays */
+                                        const double* rpar, const int32_t* ipar,                                            /* host arrays */
+                                        double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                        const double* d_hstart, void* hip_stream);
+int mistra_chem_rosenbrock_trace_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                          double tstart, double tend, const double* atol, const double* rtol, int ntol,
+                                          const double* rpar, const int32_t* ipar,
+                                          double* var_out, int32_t* ierr, int32_t* stats, double* t_h,
+                                          int cap, double* trace_d, int32_t* trace_i, int32_t* ntrace, int32_t* ctrl);
+int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                              double tstart, double tend, const double* d_atol, const double* d_rtol, int ntol,   /* device arrays */
+                                              const double* rpar, const int32_t* ipar,                                            /* host arrays */
+                                              double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                              const double* d_hstart, void* hip_stream,
+                                              int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl);
+
+/* AbsTol from each cell's own state, on the device in stream order: d_atol[c] = max(floor, factor * max_i |d_var[c][i]|), i over NVAR.  NaN entries
+ * are ignored; a cell with no positive entry gets floor.  The product is one rounding of two exact operands, so the host restatement
+ * max(floor, factor * fmax-reduction of |var|) gives the same bits.  factor or floor that is not finite and positive fails with a text before a device
+ * is touched.  Needs NVAR alone: user slots have it.  d_atol is a tolerance array of width ntol = 1 for the cells entries above. */
+int mistra_chem_cell_atol_device(int mech, int ncell, const double* d_var, double factor, double floor, double* d_atol, void* hip_stream);
 
 /* The method tables the kernels were compiled with (Ros2_x .. Rodas4_x, gas.f:1514-1895), pure host, works before init: method 1 .. 5, 0 = 3.
  * *S = ros_S; A15 / C15 = ros_A / ros_C, row-wise lower triangle, S*(S-1)/2 entries; M6, E6, gamma6 = ros_M, ros_E, ros_Gamma; newf6 =

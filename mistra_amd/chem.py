@@ -122,6 +122,13 @@ def lib():
             L.mistra_chem_method_table.argtypes = [C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp, _dp, _dp, _ip, _dp]
             L.mistra_chem_rosenbrock_trace_ex.argtypes = L.mistra_chem_rosenbrock_ex.argtypes + [C.c_int, _dp, _ip, _ip, _ip]
             L.mistra_chem_rosenbrock_trace_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [C.c_int, vp, vp, vp, vp]
+            L.mistra_chem_rosenbrock_cells_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, _dp, _dp, C.c_int, _dp, _ip, _dp, _ip,
+                                                          _ip, _dp]
+            L.mistra_chem_rosenbrock_cells_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, vp, vp, C.c_int, _dp, _ip, vp, vp, vp,
+                                                              vp, vp, vp]
+            L.mistra_chem_rosenbrock_trace_cells_ex.argtypes = L.mistra_chem_rosenbrock_cells_ex.argtypes + [C.c_int, _dp, _ip, _ip, _ip]
+            L.mistra_chem_rosenbrock_trace_cells_device.argtypes = L.mistra_chem_rosenbrock_cells_device.argtypes + [C.c_int, vp, vp, vp, vp]
+            L.mistra_chem_cell_atol_device.argtypes = [C.c_int, C.c_int, vp, C.c_double, C.c_double, vp, vp]
         if hasattr(L, "mistra_chem_user_mechs"):
             L.mistra_chem_mech_name.restype = C.c_char_p
             L.mistra_chem_mech_name.argtypes = [C.c_int]
@@ -551,6 +558,144 @@ def rosenbrock_trace(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None,
                                                  ti.ctypes.data_as(_ip) if rows else None, nt.ctypes.data_as(_ip),
                                                  None if ct is None else ct.ctypes.data_as(_ip)))
     return IntegrateResult(out, ierr, stats), th, Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct)
+
+
+# ---- tolerances per cell (include/mistra_chem.h: mistra_chem_rosenbrock_cells_ex / _device, their trace forms, mistra_chem_cell_atol_device)
+def _is_torch(x):
+    try:
+        import torch
+        return isinstance(x, torch.Tensor)
+    except ImportError:      # pragma: no cover
+        return False
+
+
+def _ros_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, trace):
+    """rosenbrock_cells (trace None) and rosenbrock_trace_cells (trace = (cap, ctrl, trace_d, trace_i))"""
+    mid, name = _mech_id(mech)
+    nvar, nfix, nreact, _ = DIMS[name]
+    ip, rp, _, _ = _option_args(name, ipar, rpar, None, None)
+    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
+    L = lib()
+    if trace is not None:
+        cap, ctrl, trace_d, trace_i = trace
+        cap = int(cap)
+        rows = max(cap, 0)
+    if _is_torch(var):
+        import torch
+        if not var.is_cuda:
+            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
+        init(var.device.index or 0)
+        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
+                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
+        ncell = var.numel() // nvar
+        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
+            raise MistraChemError("cell counts of var / fix / rconst differ")
+        for x in (atol, rtol):
+            if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.ndim != 2 or x.shape[0] != ncell or x.device != var.device:
+                raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
+        if atol.shape != rtol.shape:
+            raise MistraChemError("atol and rtol differ in shape")
+        ntol = int(atol.shape[1])
+        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
+            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
+        if trace is not None:
+            td = torch.zeros((ncell, rows, 4), dtype=torch.float64, device=var.device) if trace_d is None else trace_d
+            ti = torch.zeros((ncell, rows, 2), dtype=torch.int32, device=var.device) if trace_i is None else trace_i
+            for x, dt, k in ((td, torch.float64, 4), (ti, torch.int32, 2)):
+                if x.dtype != dt or not x.is_contiguous() or x.numel() != ncell * rows * k or x.device != var.device:
+                    raise MistraChemError("trace_d / trace_i: contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] tensors on the cells' device expected")
+            td, ti = td.view(ncell, rows, 4), ti.view(ncell, rows, 2)
+            nt = torch.empty(ncell, dtype=torch.int32, device=var.device)
+            ct = torch.zeros((ncell, nvar), dtype=torch.int32, device=var.device) if ctrl else None
+        out = torch.empty_like(var)
+        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
+        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
+        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
+        stream = torch.cuda.current_stream(var.device).cuda_stream
+        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), atol.data_ptr(), rtol.data_ptr(), ntol,
+                *popts, out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), None if hstart is None else hstart.data_ptr(),
+                C.c_void_p(stream))
+        if trace is None:
+            rc = L.mistra_chem_rosenbrock_cells_device(*head)
+        else:
+            rc = L.mistra_chem_rosenbrock_trace_cells_device(*head, cap, td.data_ptr() if rows else None, ti.data_ptr() if rows else None,
+                                                             nt.data_ptr(), None if ct is None else ct.data_ptr())
+        _check(rc)
+        if trace is None:
+            return IntegrateResult(out, ierr, stats), th
+        return IntegrateResult(out, ierr, stats), th, Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct)
+    if hstart is not None:
+        raise MistraChemError("hstart goes with the device entry: pass torch CUDA tensors (host buffers: rpar[2] is the first step size of every cell)")
+    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+    ncell = v.shape[0]
+    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
+    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
+    at, rt = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
+    if at.ndim != 2 or at.shape[0] != ncell or rt.shape != at.shape:
+        raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
+    ntol = int(at.shape[1])
+    out = np.empty_like(v)
+    ierr = np.zeros(ncell, np.int32)
+    stats = np.zeros((ncell, 8), np.int32)
+    th = np.zeros((ncell, 3))
+    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend), at.ctypes.data_as(_dp),
+            rt.ctypes.data_as(_dp), ntol, *popts, out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp))
+    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
+    if trace is None:
+        _check(L.mistra_chem_rosenbrock_cells_ex(*head))
+        return IntegrateResult(out, ierr, stats), th
+    td = np.zeros((ncell, rows, 4)) if trace_d is None else trace_d
+    ti = np.zeros((ncell, rows, 2), np.int32) if trace_i is None else trace_i
+    for x, dt, k in ((td, np.float64, 4), (ti, np.int32, 2)):
+        if not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags.c_contiguous or x.size != ncell * rows * k:
+            raise MistraChemError("trace_d / trace_i: C-contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] arrays expected")
+    td, ti = td.reshape(ncell, rows, 4), ti.reshape(ncell, rows, 2)
+    nt = np.zeros(ncell, np.int32)
+    ct = np.zeros((ncell, nvar), np.int32) if ctrl else None
+    _check(L.mistra_chem_rosenbrock_trace_cells_ex(*head, cap, td.ctypes.data_as(_dp) if rows else None, ti.ctypes.data_as(_ip) if rows else None,
+                                                   nt.ctypes.data_as(_ip), None if ct is None else ct.ctypes.data_as(_ip)))
+    return IntegrateResult(out, ierr, stats), th, Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct)
+
+
+def rosenbrock_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart=None):
+    """rosenbrock() with tolerances PER CELL: atol, rtol shaped (ncell, 1) or (ncell, NVAR), cell c integrates with row c.  ipar[1] = 0 (vector
+    tolerances) needs NVAR columns; scalar tolerances read column 0 alone, whatever the width.  numpy arrays: the host entry; torch CUDA tensors
+    (the tolerances too, read by the kernel in stream order): the device entry.  ipar, rpar: None = INTEGRATE_x's values.  IERR = -5 is a result per
+    cell: a cell whose row Rosenbrock_x would refuse comes back unchanged with ierr = -5 and zero stats / t_h, the others run."""
+    return _ros_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, None)
+
+
+def rosenbrock_trace_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart=None, cap=256, ctrl=True, trace_d=None, trace_i=None):
+    """rosenbrock_trace() with tolerances per cell as rosenbrock_cells takes them; a cell refused with -5 has n = 0 and its log rows untouched."""
+    return _ros_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, (cap, ctrl, trace_d, trace_i))
+
+
+def cell_atol(mech, var, factor, floor):
+    """AbsTol from each cell's own state -> [ncell, 1]: max(floor, factor * max_i |var[c, i]|), NaN entries ignored, a cell with no positive entry
+    gets floor.  torch CUDA tensors: the device kernel on torch's current stream (the result feeds rosenbrock_cells without leaving the device);
+    numpy arrays: the same formula on the host, bit for bit what the kernel gives."""
+    mid, name = _mech_id(mech)
+    nvar = DIMS[name][0]
+    factor, floor = float(factor), float(floor)
+    if _is_torch(var):
+        import torch
+        if not var.is_cuda or var.dtype != torch.float64 or not var.is_contiguous() or var.shape[-1] != nvar:
+            raise MistraChemError("expected a contiguous float64 [ncell,%d] tensor on the GPU" % nvar)
+        ncell = var.numel() // nvar
+        out = torch.empty((ncell, 1), dtype=torch.float64, device=var.device)
+        stream = torch.cuda.current_stream(var.device).cuda_stream
+        args = (mid, ncell, var.data_ptr(), factor, floor, out.data_ptr(), C.c_void_p(stream))
+        init(var.device.index or 0)
+        _check(lib().mistra_chem_cell_atol_device(*args))
+        return out
+    for x, what in ((factor, "factor"), (floor, "floor")):
+        if not (np.isfinite(x) and x > 0.0):
+            raise MistraChemError("cell_atol: %s must be finite and positive" % what)
+    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+    with np.errstate(invalid="ignore", over="ignore"):
+        m = factor * np.fmax.reduce(np.abs(v), axis=1)
+    return np.where(m > floor, m, floor).reshape(-1, 1)
 
 
 # ---- OPT-IN: every layer's step size carried from one column step to the next (include/mistra_chem.h: mistra_chem_set_step_reuse)

@@ -658,6 +658,7 @@ struct MechState {
   int step_n = 0;
   // staging of the batched host-buffer entries (grow-only)
   DevBuf<double> s_var, s_fix, s_rct, s_th, s_env, s_hst;
+  DevBuf<double> s_tol;                    // ... and of mistra_chem_rosenbrock_cells_ex: the block's AbsTol rows, then its RelTol rows
   DevBuf<int32_t> s_ierr, s_stats, s_sing;
   DevBuf<double> s_trd;                    // ... and of mistra_chem_rosenbrock_trace_ex: the records, the attempt counts, the per-species counts
   DevBuf<int32_t> s_tri, s_ntr, s_ctl;
@@ -682,7 +683,7 @@ struct MechState {
     opt.release(); opt_max_steps = 0;
     call_opt.release(); call_ring.release();
     step_mem.release(); step_n = 0;
-    s_hst.release();
+    s_hst.release(); s_tol.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
     s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release();
     sing_count = 0; sing_one = false;
@@ -933,7 +934,27 @@ struct RosCall {
   int cap = 0;
   double* trace_d = nullptr;
   int32_t *trace_i = nullptr, *ntrace = nullptr, *ctrl = nullptr;
+  // mistra_chem_rosenbrock_cells_ex / _device: tolerances per cell, [ncell][ntol] each, the caller's arrays for the whole batch (host or device as the
+  // entry's other arrays); null: the shared pair of the block
+  const double *cell_atol = nullptr, *cell_rtol = nullptr;
+  int ntol = 0;
+  bool vector = false;            // IPAR(2) = 0: every entry of a row is read; else entry 0 alone
 };
+struct CellTol {      // the per-cell tolerance arguments of a cells entry
+  const double *atol, *rtol;
+  int ntol;
+};
+// ... checked before anything touches a device: the widths are the entries' own rule, not codes of Rosenbrock_x
+int check_cell_tol(int mech, int ncell, const CellTol& ct, const double* rpar, const int32_t* ipar) {
+  if (!known_mech(mech)) return fail("unknown mechanism id");
+  if (ncell < 0) return fail("negative cell count");
+  if (!rpar || !ipar) return fail("null options pointer");
+  if (!ct.atol || !ct.rtol) return fail("null tolerance array (atol / rtol: [ncell][ntol] each)");
+  const int nv = kMech[mech].dims.nvar;
+  if (ct.ntol != 1 && ct.ntol != nv) return fail("ntol = " + std::to_string(ct.ntol) + ": a tolerance row holds 1 or NVAR = " + std::to_string(nv) + " entries");
+  if (ipar[1] == 0 && ct.ntol != nv) return fail("vector tolerances (ipar[1] = 0) need rows of NVAR = " + std::to_string(nv) + " entries, ntol = " + std::to_string(ct.ntol));
+  return 0;
+}
 // the arguments of the trace entries, checked before anything touches a device
 int check_trace_args(const int32_t* ipar, int cap, const double* trace_d, const int32_t* trace_i, const int32_t* ntrace) {
   if (cap < 0) return fail("negative trace capacity");
@@ -942,9 +963,19 @@ int check_trace_args(const int32_t* ipar, int cap, const double* trace_d, const 
   if (ipar[3] != 2) return fail("the step-control trace is built for Ros3 (ipar[3] = 2) only");
   return 0;
 }
-RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol) {
+// ct: the tolerances come per cell (atol, rtol are not read).  The refusals -1 .. -4 depend on ipar / rpar alone and stay whole-call results decided here;
+// -5 is then the kernel's, per cell, and the block's pair is a placeholder no kernel reads.
+RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, const CellTol* ct = nullptr) {
   RosCall c;
   RosResolved r;
+  std::vector<double> one_a, one_r;
+  if (ct) {
+    one_a.assign((size_t)kMech[mech].dims.nvar, 1.0);
+    one_r.assign((size_t)kMech[mech].dims.nvar, 1.0e-3);
+    atol = one_a.data(); rtol = one_r.data();
+    c.cell_atol = ct->atol; c.cell_rtol = ct->rtol; c.ntol = ct->ntol;
+    c.vector = ipar[1] == 0;
+  }
   c.ierr = resolve_options(mech, ipar, rpar, atol, rtol, &r);
   if (c.ierr != 1) return c;
   c.method = ipar[3] == 0 ? (int)kRos4 : (int)ipar[3];
@@ -1000,6 +1031,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.lu_scale = ScaleDev{k.lu_scale.p, k.lu_scale_slots, k.lu_scale_slots + VM_LOOKAHEAD_ROWS};
   a.dense = DenseDev{k.dense_rows.p, k.schur_cells.p};
   a.trace_d = nullptr; a.trace_i = nullptr; a.ntrace = nullptr; a.ctrl = nullptr; a.trace_cap = 0;      // (the trace entries set them)
+  a.tol_abs = nullptr; a.tol_rel = nullptr; a.tol_cell_stride = 0; a.tol_spec_stride = 0;      // (the cells entries set them)
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
@@ -1134,6 +1166,15 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     HIP_TRY(hipMemcpy(S.call_opt.p, call->block.data(), call->block.size() * sizeof(double), hipMemcpyHostToDevice));
     a.opt = S.call_opt.p;
     a.max_steps = call->max_steps;
+    if (call->cell_atol) {      // this block's tolerance rows
+      const size_t nt = (size_t)call->ntol;
+      HIP_TRY(S.s_tol.reserve(2 * nc * nt));
+      HIP_TRY(hipMemcpy(S.s_tol.p, call->cell_atol + batch_start * nt, nc * nt * sizeof(double), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(S.s_tol.p + nc * nt, call->cell_rtol + batch_start * nt, nc * nt * sizeof(double), hipMemcpyHostToDevice));
+      a.tol_abs = S.s_tol.p; a.tol_rel = S.s_tol.p + nc * nt;
+      a.tol_cell_stride = call->ntol;
+      a.tol_spec_stride = call->vector ? 1 : 0;
+    }
   }
   const bool trace = call && call->trace;
   const size_t cap = trace ? (size_t)call->cap : 0;
@@ -1152,6 +1193,8 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     if (call->ctrl) {
       HIP_TRY(S.s_ctl.reserve(nc * nv));
       a.ctrl = S.s_ctl.p;
+      if (call->cell_atol)      // (a cell refused with -5 writes no row: the caller's goes up, as the logs do)
+        HIP_TRY(hipMemcpy(S.s_ctl.p, call->ctrl + batch_start * nv, nc * nv * sizeof(int32_t), hipMemcpyHostToDevice));
     }
   }
   if (hstart) {      // OPT-IN: the caller's first step size per cell (mistra_chem_integrate_hstart_ex)
@@ -2242,7 +2285,7 @@ int mistra_chem_method_table(int method, int* S, double* A15, double* C15, doubl
 // mistra_chem_rosenbrock_ex and, with tr set (its trace members filled in), mistra_chem_rosenbrock_trace_ex
 static int rosenbrock_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                            const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
-                           int32_t* stats, double* t_h, const RosCall* tr) {
+                           int32_t* stats, double* t_h, const RosCall* tr, const CellTol* ct = nullptr) {
   if (int rc = user_slot_method(mech, ipar)) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, ncell, true)) return rc;
@@ -2253,7 +2296,7 @@ static int rosenbrock_host(int mech, int ncell, const double* var_in, const doub
   {
     std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps)
     if (g_devs[0].mech[mech].pend.active) return step_is_open(mech);
-    call = decode_call(mech, ipar, rpar, atol, rtol);
+    call = decode_call(mech, ipar, rpar, atol, rtol, ct);
   }
   if (tr) { call.trace = true; call.cap = tr->cap; call.trace_d = tr->trace_d; call.trace_i = tr->trace_i; call.ntrace = tr->ntrace; call.ctrl = tr->ctrl; }
   if (call.ierr != 1) {      // Rosenbrock_x returns before it touches Y or the statistics (gas.f:936-1053): a result, nothing is launched
@@ -2288,7 +2331,8 @@ int mistra_chem_rosenbrock_trace_ex(int mech, int ncell, const double* var_in, c
 // mistra_chem_rosenbrock_device and, with tr set (device arrays), mistra_chem_rosenbrock_trace_device
 static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                 double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
-                                int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream, const RosCall* tr) {
+                                int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream, const RosCall* tr,
+                                const CellTol* ct = nullptr) {
   if (int rc = user_slot_method(mech, ipar)) return rc;
   if (ncell == 0) return check_call(mech, 0, true);
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
@@ -2296,8 +2340,15 @@ static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, con
   Slot t;
   if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (ct) {      // the kernel reads these itself: memory the device cannot reach is refused here, not met there
+    for (const double* p : {ct->atol, ct->rtol}) {
+      hipPointerAttribute_t attr;
+      if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type == hipMemoryTypeUnregistered || (attr.type == hipMemoryTypeDevice && attr.device != t.D->id))
+        return fail("d_atol / d_rtol are not device arrays on the cells' device");
+    }
+  }
   std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of options blocks)
-  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol);
+  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
   const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
   if (call.ierr != 1) {      // the refusal as a result, in stream order; no kernel of the library runs
     if (d_var_out != d_var_in) HIP_TRY(hipMemcpyAsync(d_var_out, d_var_in, nc * nv * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -2320,6 +2371,11 @@ static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, con
   a.hstart = d_hstart;
   a.opt = db;
   a.max_steps = call.max_steps;
+  if (ct) {      // the caller's device arrays, read by the kernel in stream order: no copy
+    a.tol_abs = ct->atol; a.tol_rel = ct->rtol;
+    a.tol_cell_stride = ct->ntol;
+    a.tol_spec_stride = call.vector ? 1 : 0;
+  }
   if (tr) { a.trace_cap = tr->cap; a.trace_d = tr->trace_d; a.trace_i = tr->trace_i; a.ntrace = tr->ntrace; a.ctrl = tr->ctrl; }
   const int rc = launch(*t.D, mech, a, st, call.method);
   if (hipEventRecord(R.ev[i], st) == hipSuccess) R.pending[i] = true;      // (also behind a failed launch: the copy is queued)
@@ -2344,6 +2400,66 @@ int mistra_chem_rosenbrock_trace_device(int mech, int ncell, const double* d_var
   tr.cap = cap; tr.trace_d = d_trace_d; tr.trace_i = d_trace_i; tr.ntrace = d_ntrace; tr.ctrl = d_ctrl;
   return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
                               d_hstart, hip_stream, &tr);
+}
+
+// ---- tolerances per cell: the same two paths, the rows in place of the pair
+int mistra_chem_rosenbrock_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                    const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar, double* var_out,
+                                    int32_t* ierr, int32_t* stats, double* t_h) {
+  if (int rc = user_slot_method(mech, ipar)) return rc;
+  const CellTol ct{atol, rtol, ntol};
+  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
+  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, &ct);
+}
+
+int mistra_chem_rosenbrock_trace_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                          const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar, double* var_out,
+                                          int32_t* ierr, int32_t* stats, double* t_h, int cap, double* trace_d, int32_t* trace_i, int32_t* ntrace,
+                                          int32_t* ctrl) {
+  if (int rc = builtin_only(mech, "step-control trace")) return rc;
+  const CellTol ct{atol, rtol, ntol};
+  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
+  if (int rc = check_trace_args(ipar, cap, trace_d, trace_i, ntrace)) return rc;
+  RosCall tr;
+  tr.cap = cap; tr.trace_d = trace_d; tr.trace_i = trace_i; tr.ntrace = ntrace; tr.ctrl = ctrl;
+  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, &tr, &ct);
+}
+
+int mistra_chem_rosenbrock_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                        double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar,
+                                        double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
+                                        void* hip_stream) {
+  if (int rc = user_slot_method(mech, ipar)) return rc;
+  const CellTol ct{d_atol, d_rtol, ntol};
+  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
+  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                              d_hstart, hip_stream, nullptr, &ct);
+}
+
+int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                              double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar,
+                                              double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
+                                              void* hip_stream, int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl) {
+  if (int rc = builtin_only(mech, "step-control trace")) return rc;
+  const CellTol ct{d_atol, d_rtol, ntol};
+  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
+  if (int rc = check_trace_args(ipar, cap, d_trace_d, d_trace_i, d_ntrace)) return rc;
+  RosCall tr;
+  tr.cap = cap; tr.trace_d = d_trace_d; tr.trace_i = d_trace_i; tr.ntrace = d_ntrace; tr.ctrl = d_ctrl;
+  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                              d_hstart, hip_stream, &tr, &ct);
+}
+
+int mistra_chem_cell_atol_device(int mech, int ncell, const double* d_var, double factor, double floor, double* d_atol, void* hip_stream) {
+  if (!known_mech(mech)) return fail("unknown mechanism id");
+  if (!(factor > 0.0) || !std::isfinite(factor)) return fail("cell_atol: factor must be finite and positive");
+  if (!(floor > 0.0) || !std::isfinite(floor)) return fail("cell_atol: floor must be finite and positive");
+  if (ncell == 0) return check_call(mech, 0, true);
+  if (!d_var || !d_atol) return fail("null device pointer");
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var, "d_var", 0, &t)) return rc;
+  LAUNCH_TRY(launch_cell_atol(kMech[mech].dims.nvar, ncell, d_var, factor, floor, d_atol, static_cast<hipStream_t>(hip_stream)));
+  return 0;
 }
 
 int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, double* tout, int32_t* ierr_out, double* t_err,

@@ -91,6 +91,13 @@ struct KernelArgs {
   int32_t* ntrace;             // [ncell]: the TRUE number of attempts (records past trace_cap are not written)
   int32_t* ctrl;               // [ncell][NVAR] or null: attempts each species controlled
   int32_t trace_cap;
+  // tolerances per cell (mistra_chem_rosenbrock_cells_ex / _device and their trace forms; options instantiations only): species s of cell c reads
+  // entry c*tol_cell_stride + s*tol_spec_stride of each array instead of the pair in the options block, and the kernel makes Rosenbrock_x's
+  // check of them (gas.f:1045-1053, IERR = -5) per cell.  Null = the block's pair, checked by the host (capi.cpp: make_args).
+  const double* tol_abs;       // [ncell][tol_cell_stride] or null
+  const double* tol_rel;       // [ncell][tol_cell_stride] or null
+  int32_t tol_cell_stride;     // the row width ntol: 1 or NVAR
+  int32_t tol_spec_stride;     // 1: vector tolerances (IPAR(2) = 0), 0: scalar ones (entry 0 of the row for every species)
 };
 
 }  // namespace mistra

@@ -516,4 +516,59 @@ hipError_t launch_step_store(double* mem, int n, const int32_t* layer, int nlaye
   return hipGetLastError();
 }
 
+// ---- AbsTol from the cell's own state (mistra_chem_cell_atol_device): atol[c] = max(floor, factor * max_i |VAR(i, c)|).  One wave per cell, the lanes
+//      striding over NVAR; NaN entries are ignored (no comparison with one holds), so a cell without a positive entry gets the floor.  The wave's maximum
+//      comes by the cross-lane operations of the integrator's wave_sum (ros3_kernel.hip): DPP inside a lane row, v_permlane16/32_swap across rows.
+namespace {
+constexpr int kAtolWaves = 4;
+template <int CTRL>
+__device__ __forceinline__ double dpp_partner(double v) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
+  return __builtin_bit_cast(double, (uint64_t)(uint32_t)lo | ((uint64_t)(uint32_t)hi << 32));
+}
+__device__ __forceinline__ double max_nn(double a, double b) { return b > a ? b : a; }      // (neither is a NaN here)
+__device__ __forceinline__ double wave_max(double v) {
+  v = max_nn(v, dpp_partner<0xB1>(v));       // quad_perm [1,0,3,2]
+  v = max_nn(v, dpp_partner<0x4E>(v));       // quad_perm [2,3,0,1]
+  v = max_nn(v, dpp_partner<0x141>(v));      // row_half_mirror
+  v = max_nn(v, dpp_partner<0x140>(v));      // row_mirror
+  {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const auto l = __builtin_amdgcn_permlane16_swap((uint32_t)u, (uint32_t)u, false, false);
+    const auto h = __builtin_amdgcn_permlane16_swap((uint32_t)(u >> 32), (uint32_t)(u >> 32), false, false);
+    v = max_nn(__builtin_bit_cast(double, (uint64_t)l[0] | ((uint64_t)h[0] << 32)), __builtin_bit_cast(double, (uint64_t)l[1] | ((uint64_t)h[1] << 32)));
+  }
+  {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const auto l = __builtin_amdgcn_permlane32_swap((uint32_t)u, (uint32_t)u, false, false);
+    const auto h = __builtin_amdgcn_permlane32_swap((uint32_t)(u >> 32), (uint32_t)(u >> 32), false, false);
+    v = max_nn(__builtin_bit_cast(double, (uint64_t)l[0] | ((uint64_t)h[0] << 32)), __builtin_bit_cast(double, (uint64_t)l[1] | ((uint64_t)h[1] << 32)));
+  }
+  return v;
+}
+__global__ __launch_bounds__(kAtolWaves * 64) void cell_atol_kernel(int nvar, int ncell, const double* __restrict__ var, double factor, double floor_,
+                                                                    double* __restrict__ atol) {
+  const int lane = threadIdx.x & 63;
+  const int cell = blockIdx.x * kAtolWaves + (threadIdx.x >> 6);      // (uniform over the wave)
+  if (cell >= ncell) return;
+  const double* v = var + (size_t)cell * (size_t)nvar;
+  double m = 0.0;
+  for (int i = lane; i < nvar; i += 64) {
+    const double a = fabs(v[i]);
+    if (a > m) m = a;      // a NaN stays out
+  }
+  m = wave_max(m);
+  const double r = factor * m;
+  if (lane == 0) atol[cell] = r > floor_ ? r : floor_;
+}
+}  // namespace
+hipError_t launch_cell_atol(int nvar, int ncell, const double* var, double factor, double floor, double* atol, hipStream_t stream) {
+  if (ncell <= 0) return hipSuccess;
+  hipLaunchKernelGGL(cell_atol_kernel, dim3((unsigned)((ncell + kAtolWaves - 1) / kAtolWaves)), dim3(kAtolWaves * 64), 0, stream, nvar, ncell, var, factor, floor,
+                     atol);
+  return hipGetLastError();
+}
+
 }  // namespace mistra

@@ -49,6 +49,8 @@ hipError_t launch_env_from_c(const PackDev& P, int ncell, int nenv, const double
 hipError_t launch_step_gather(const double* mem, int n, const int32_t* layer, int nlayer, double* hstart, hipStream_t stream);
 // mem[layer[i] - 1] = texit_hexit[2 i + 1] where ierr[i] == 1, after the caller has cleared mem on the same stream
 hipError_t launch_step_store(double* mem, int n, const int32_t* layer, int nlayer, const int32_t* ierr, const double* texit_hexit, hipStream_t stream);
+// atol[c] = max(floor, factor * max_i |var[c][i]|), NaN entries ignored (mistra_chem_cell_atol_device)
+hipError_t launch_cell_atol(int nvar, int ncell, const double* var, double factor, double floor, double* atol, hipStream_t stream);
 
 }  // namespace mistra
 

@@ -1250,7 +1250,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     const int s = q * NT + t;
     y[q] = s < NVAR ? G_(a.var_in)[(size_t)cell * NVAR + s] : 0.0;
   }
-  // VARIANT 3: AbsTol / RelTol of this thread's species, one vector pair per call shared by all cells as in KPP.  Fetched once, here:
+  // VARIANT 3: AbsTol / RelTol of this thread's species, out of the call's options block: one vector pair shared by all cells as in KPP.  Fetched once, here:
   // a global load in the middle of a step would wait behind the table streams.  The scalars of the block are fetched where the step
   // control uses them (opt), not kept across the step loop.
   [[maybe_unused]] double atol_r[SPT], rtol_r[SPT];
@@ -1260,14 +1260,57 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     asm volatile("" : "+s"(ob));      // opaque: the load stays where the value is used
     return G_(ob)[slot];
   };
+  // a.tol_abs set: the cell's own rows instead (kernel_args.hpp), and Rosenbrock_x's check of them (gas.f:1045-1053) is made here, per cell: the
+  // arrays may live on the device, the host has not seen them.  Every thread tests the entries it reads (vector mode: all NVAR between them;
+  // scalar mode: entry 0 of the row), the cell takes the OR.  A refused cell leaves as a call the host refuses leaves: Y untouched, IERR = -5,
+  // statistics, Texit / Hexit and H zero, no trace record.  All of it in front of the step loop: nothing of it is live inside.
   if constexpr (OPT) {
+    const bool cells = a.tol_abs != nullptr;
+    const double* ta = cells ? a.tol_abs + (size_t)cell * (size_t)a.tol_cell_stride : a.opt + kOptTol;
+    const double* tr = cells ? a.tol_rel + (size_t)cell * (size_t)a.tol_cell_stride : a.opt + kOptTol + NVAR;
+    const int ss = cells ? a.tol_spec_stride : 1;
 #pragma unroll
     for (int q = 0; q < SPT; q++) {
       const int s = q * NT + t;
-      atol_r[q] = s < NVAR ? G_(a.opt)[kOptTol + s] : 1.0;
-      rtol_r[q] = s < NVAR ? G_(a.opt)[kOptTol + NVAR + s] : 0.0;
+      atol_r[q] = s < NVAR ? G_(ta)[s * ss] : 1.0;
+      rtol_r[q] = s < NVAR ? G_(tr)[s * ss] : 0.0;
     }
     autonomous = opt(kOptAutonomous) != 0.0;
+    if (cells) {      // (uniform over the workgroup)
+      bool bad = false;
+#pragma unroll
+      for (int q = 0; q < SPT; q++) {      // as the reference writes the tests: a NaN passes
+        if (q * NT + t < NVAR) bad = bad || atol_r[q] <= 0.0 || rtol_r[q] <= 10.0 * 2.220446049250313e-16 || rtol_r[q] >= 1.0;
+      }
+      bool refused = __builtin_amdgcn_ballot_w64(bad) != 0ull;
+      if constexpr (NW > 1) {      // one cell of red[] per wave, written by its lane 0; the error norm's first use of red[] is behind a barrier of its own
+        if (lane == 0) red[wave] = refused ? 1.0 : 0.0;
+        lds_barrier();
+        refused = false;
+#pragma unroll
+        for (int w = 0; w < NW; w++) refused = refused || red[w] != 0.0;
+      }
+      if (refused) {
+#pragma unroll
+        for (int q = 0; q < SPT; q++) {
+          const int s = q * NT + t;
+          if (s < NVAR) GM_(a.var_out)[(size_t)cell * NVAR + s] = y[q];
+        }
+        if (t == 0) {
+          GM_(a.ierr)[cell] = -5;
+          gptr_mut<int32_t> st = GM_(a.stats) + (size_t)cell * 8;
+#pragma unroll
+          for (int k = 0; k < 8; k++) st[k] = 0;
+          if (a.texit_hexit) {
+            GM_(a.texit_hexit)[(size_t)cell * 2] = 0.0;
+            GM_(a.texit_hexit)[(size_t)cell * 2 + 1] = 0.0;
+          }
+          if (a.h_last) GM_(a.h_last)[cell] = 0.0;
+          if constexpr (TRACE) GM_(a.ntrace)[cell] = 0;
+        }
+        return;
+      }
+    }
   }
   // (the register-starved kernels fetch them per use, like their factor words)
   constexpr bool RCT_PER_USE = MT::WAVES_PER_SIMD > kResidentMaxWps || L::RCT_IN_LDS;

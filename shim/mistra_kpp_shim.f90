@@ -32,6 +32,9 @@
 ! in force are neither read nor changed.
 !     SUBROUTINE ROSENBROCK_BATCH_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
 ! IERR(k) = 1 or Rosenbrock_x's code, also for options it refuses (-1 .. -5: VAR untouched); ros_ErrorMsg_x's lines go to unit 6 for every failed cell.
+! The same with tolerances PER CELL (mistra_chem_rosenbrock_cells_ex): ATOL(NTOL,NCELL), RTOL(NTOL,NCELL), NTOL = 1 or NVAR (IPAR(2) = 0 needs NVAR).
+! IERR = -5 is then a cell's own result: the cell is reported as ROSENBROCK_BATCH_x reports it, the others run.
+!     SUBROUTINE ROSENBROCK_BATCH_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
 module mistra_chem_c_api
   use iso_c_binding
   implicit none
@@ -103,6 +106,17 @@ module mistra_chem_c_api
        integer(c_int32_t) :: ierr(*), stats(*)
        integer(c_int) :: rc
      end function mistra_chem_rosenbrock_ex
+     function mistra_chem_rosenbrock_cells_ex(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, ntol, rpar, ipar, var_out, ierr, stats, t_h) &
+          bind(C, name="mistra_chem_rosenbrock_cells_ex") result(rc)
+       import :: c_int, c_double, c_int32_t
+       integer(c_int), value :: mech, ncell, ntol
+       real(c_double), value :: tstart, tend
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_out(*), t_h(*)
+       real(c_double), intent(in) :: atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_cells_ex
      function mistra_chem_set_step_reuse(mech, on) bind(C, name="mistra_chem_set_step_reuse") result(rc)
        import :: c_int
        integer(c_int), value :: mech, on
@@ -269,8 +283,10 @@ contains
 
   ! Rosenbrock_x for NCELL cells with the call's own options; the messages in cell order, as a serial loop over Rosenbrock_x would have written them
   ! (ros_PrepareMatrix_x's warnings, then ros_ErrorMsg_x's lines: a refusal is reported at T = Tstart, H = 0 as Rosenbrock_x does, gas.f:955)
-  subroutine rosenbrock_batch(mech, sfx, NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+  ! NTOL present: ATOL / RTOL hold a row of NTOL entries per cell (ROSENBROCK_BATCH_CELLS_x)
+  subroutine rosenbrock_batch(mech, sfx, NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL)
     integer, intent(in) :: mech, NCELL
+    integer, intent(in), optional :: NTOL
     character(len=1), intent(in) :: sfx
     real(c_double) :: VAR(*), FIX(*), RCONST(*), TEXIT(NCELL), HEXIT(NCELL)
     real(c_double), intent(in) :: TSTART, TEND, ATOL(*), RTOL(*), RPAR(20)
@@ -281,8 +297,13 @@ contains
     integer :: k, i
     if (NCELL <= 0) return
     allocate (th(3, NCELL))
-    if (mistra_chem_rosenbrock_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, VAR, IERR, ISTAT, th) /= 0) &
-         call mistra_chem_fail('ROSENBROCK_BATCH_'//sfx)
+    if (present(NTOL)) then
+       if (mistra_chem_rosenbrock_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, int(NTOL, c_int), RPAR, IPAR, &
+            VAR, IERR, ISTAT, th) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_CELLS_'//sfx)
+    else
+       if (mistra_chem_rosenbrock_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, VAR, IERR, ISTAT, th) /= 0) &
+            call mistra_chem_fail('ROSENBROCK_BATCH_'//sfx)
+    end if
     do k = 1, NCELL
        TEXIT(k) = th(1, k)
        HEXIT(k) = th(2, k)
@@ -569,3 +590,34 @@ subroutine ROSENBROCK_BATCH_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL,
   integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
   call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
 end subroutine ROSENBROCK_BATCH_t
+
+! ---- ... with tolerances per cell: ATOL(NTOL,NCELL), RTOL(NTOL,NCELL)
+subroutine ROSENBROCK_BATCH_CELLS_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), TEXIT(*), HEXIT(*)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(0, 'g', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL)
+end subroutine ROSENBROCK_BATCH_CELLS_g
+
+subroutine ROSENBROCK_BATCH_CELLS_a(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), TEXIT(*), HEXIT(*)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(1, 'a', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL)
+end subroutine ROSENBROCK_BATCH_CELLS_a
+
+subroutine ROSENBROCK_BATCH_CELLS_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), TEXIT(*), HEXIT(*)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL)
+end subroutine ROSENBROCK_BATCH_CELLS_t

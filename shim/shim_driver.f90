@@ -10,6 +10,8 @@
 !          shim_driver <XG|XA|XT> <in.bin> <out.bin>   Rosenbrock_x itself, batched, any of its five methods: in.bin = IPAR(20), RPAR(20), ATOL(NVAR), RTOL(NVAR),
 !                                                      TSTART, TEND, ncell, then the cells as for <G|A|T> (float64), all handed to ONE call of ROSENBROCK_BATCH_x;
 !                                                      out.bin = per cell VAR, TEXIT, HEXIT, then per cell IERR and the 8 statistics
+!          shim_driver <YG|YA|YT> <in.bin> <out.bin>   the same with tolerances per cell: in.bin = IPAR(20), RPAR(20), TSTART, TEND, ncell, ntol, then per cell VAR,
+!                                                      FIX, RCONST, ATOL(ntol), RTOL(ntol), all handed to ONE call of ROSENBROCK_BATCH_CELLS_x; out.bin as for <XG|XA|XT>
 !          shim_driver <Eg|Ea|Et> <in.bin> <out.bin>   in.bin = ncell, then per cell VAR, FIX, ENV (the vector MISTRA_RATES_ENV_x packs,
 !                                                      mistra_kpp_rates.f90): UPDATE_RCONST_BATCH_x, then INTEGRATE_BATCH_ENV_x (rates and
 !                                                      integrator on the device, RCONST never crosses PCIe); out.bin = per cell VAR,
@@ -58,6 +60,13 @@ program shim_driver
      case ('G'); call run_rosenbrock(0, 102, 3, 331, trim(fin), trim(fout))
      case ('A'); call run_rosenbrock(1, 257, 5, 979, trim(fin), trim(fout))
      case ('T'); call run_rosenbrock(2, 417, 7, 1627, trim(fin), trim(fout))
+     case default; stop 'mechanism must be G, A or T'
+     end select
+  case ('Y')
+     select case (a1(2:2))
+     case ('G'); call run_rosenbrock_cells(0, 102, 3, 331, trim(fin), trim(fout))
+     case ('A'); call run_rosenbrock_cells(1, 257, 5, 979, trim(fin), trim(fout))
+     case ('T'); call run_rosenbrock_cells(2, 417, 7, 1627, trim(fin), trim(fout))
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('K', 'H', 'Q', 'V', 'S', 'C', 'R')
@@ -228,6 +237,42 @@ contains
     end do
     close (11); close (12)
   end subroutine run_rosenbrock
+  subroutine run_rosenbrock_cells(mech, NVAR, NFIX, NREACT, fin, fout)
+    integer, intent(in) :: mech, NVAR, NFIX, NREACT
+    character(len=*), intent(in) :: fin, fout
+    double precision :: ropt(40), tt(4)
+    double precision, allocatable :: ATOL(:, :), RTOL(:, :), VAR(:, :), FIX(:, :), RCONST(:, :), TEXIT(:), HEXIT(:), rec(:)
+    integer :: IPAR(20), n, ntol, i
+    integer, allocatable :: IERR(:), ISTAT(:, :)
+    open (11, file=fin, access='stream', form='unformatted', status='old')
+    open (12, file=fout, access='stream', form='unformatted', status='replace')
+    read (11) ropt, tt      ! tt: TSTART, TEND, ncell, ntol
+    IPAR = int(ropt(1:20))
+    n = int(tt(3))
+    ntol = int(tt(4))
+    allocate (VAR(NVAR, n), FIX(NFIX, n), RCONST(NREACT, n), ATOL(ntol, n), RTOL(ntol, n), TEXIT(n), HEXIT(n), IERR(n), ISTAT(8, n))
+    allocate (rec(NVAR + NFIX + NREACT + 2 * ntol))
+    do i = 1, n
+       read (11) rec
+       VAR(:, i) = rec(1:NVAR)
+       FIX(:, i) = rec(NVAR + 1:NVAR + NFIX)
+       RCONST(:, i) = rec(NVAR + NFIX + 1:NVAR + NFIX + NREACT)
+       ATOL(:, i) = rec(NVAR + NFIX + NREACT + 1:NVAR + NFIX + NREACT + ntol)
+       RTOL(:, i) = rec(NVAR + NFIX + NREACT + ntol + 1:)
+    end do
+    select case (mech)
+    case (0); call ROSENBROCK_BATCH_CELLS_g(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ntol, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT)
+    case (1); call ROSENBROCK_BATCH_CELLS_a(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ntol, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT)
+    case (2); call ROSENBROCK_BATCH_CELLS_t(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ntol, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT)
+    end select
+    do i = 1, n
+       write (12) VAR(:, i), TEXIT(i), HEXIT(i)
+    end do
+    do i = 1, n
+       write (12) dble(IERR(i)), dble(ISTAT(:, i))
+    end do
+    close (11); close (12)
+  end subroutine run_rosenbrock_cells
   subroutine run_env(mech, NVAR, NFIX, NREACT, NENV, fin, fout)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT, NENV
     character(len=*), intent(in) :: fin, fout

@@ -4,14 +4,21 @@
 
     python tools/step_control.py tot --golden tests/golden/column_BTZ96.npz                 the tot cells of a captured column step, INTEGRATE_x's options
     python tools/step_control.py tot --golden tests/golden/column_BTZ96.npz --atol 1e-15     ... with a scalar AbsTol
-    python tools/step_control.py tot --golden tests/golden/integrate_tot.npz --atol-rel 1e-13    AbsTol = 1e-13 x the cell's largest concentration (one call per cell)
+    python tools/step_control.py tot --golden tests/golden/integrate_tot.npz --atol-rel 1e-13    AbsTol = 1e-13 x the cell's largest concentration: ONE batched
+                                                                                             call with tolerances per cell (cell_atol + rosenbrock_trace_cells)
+    ... --yardstick                                                                          also the distance of the end state from Rodas4 at RelTol 1e-7
     python tools/step_control.py aer --workload 4096                                         cells 0 .. 4095 of the synthetic workload (mistra_amd/workload.py)
     ... --cpu                                                                                the Python restatement (tests/ros_trace_py.py) instead of the GPU
 
 Prints the attempts per cell and, for the species that controlled the most attempts (the species with the largest term of ros_ErrorNorm_x's sum):
 the attempts it controlled, how many of those were rejected, in how many cells, and the median over those cells of its concentration relative to the
 cell's largest — the concentration being max(|VAR in|, |VAR out|) of the call.  Species are numbered as in VAR (1-based); --names FILE (one name per
-line, in that order) prints names, the mechanism tables carry none."""
+line, in that order) prints names, the mechanism tables carry none.
+
+--yardstick integrates the same cells once more with Rodas4 at scalar RelTol = 1e-7 and INTEGRATE_x's AbsTol (the yardstick of
+profiles/r02_hstart_reuse_study.txt; one batched call) and prints how far the run's end state lies from it: the largest relative difference over the
+species above 1e-3 of their cell's maximum, and over all species with the floor 1e-12 x max|c| (tests/conftest.py: rel_diff).  These are properties of
+the reference algorithm at the run's tolerances, not of this library: nothing is asserted on them."""
 import argparse
 import os
 import sys
@@ -54,39 +61,85 @@ def options(mech, atol=None, rtol=None):
     return ipar, rpar, np.full(nvar, 1.0e-25 if atol is None else float(atol)), np.full(nvar, 1.0e-3 if rtol is None else float(rtol))
 
 
-def trace_gpu(mech, var, fix, rconst, tstart, tend, opts_of_cell, cap):
-    """-> (var_out, [(species, code, n) per cell]) from the kernel; opts_of_cell(c) -> (ipar, rpar, atol, rtol), or None: one set for the batch"""
+YARDSTICK_METHOD, YARDSTICK_RTOL = 5, 1.0e-7      # Rodas4 at RelTol 1e-7, AbsTol INTEGRATE_x's 1e-25
+ATOL_FLOOR = 1.0e-300                             # cell_atol's floor: a cell without a positive concentration still gets an AbsTol Rosenbrock_x accepts
+
+
+def cell_atol_rows(mech, var, factor):
+    """[ncell, 1]: factor x the cell's largest |concentration| (chem.cell_atol's host formula; the GPU path runs the kernel on the device instead)"""
     from mistra_amd import chem
-    n = var.shape[0]
-    if callable(opts_of_cell):
-        groups = [(slice(c, c + 1), opts_of_cell(c)) for c in range(n)]
+    return chem.cell_atol(mech, var, factor, ATOL_FLOOR)
+
+
+def trace_gpu(mech, var, fix, rconst, tstart, tend, opts, cap, atol_rel=None):
+    """-> (var_out, [(species, code, n) per cell]) from the kernel, ONE batched call: opts = (ipar, rpar, atol, rtol) shared by the batch, or with
+    atol_rel AbsTol per cell formed on the device from each cell's own state (cell_atol) and handed to rosenbrock_trace_cells without leaving it"""
+    import torch
+    from mistra_amd import chem
+    ipar, rpar, atol, rtol = opts
+    if atol_rel is None:
+        res, _, tr = chem.rosenbrock_trace(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, cap=cap, ctrl=False)
+        out, species, code, n = res.var, tr.species, tr.code, tr.n
     else:
-        groups = [(slice(0, n), opts_of_cell)]
-    out, rows = np.empty_like(var), []
-    for sl, o in groups:
-        res, _, tr = chem.rosenbrock_trace(mech, var[sl], fix[sl], rconst[sl], tstart, tend, *o, cap=cap, ctrl=False)
-        out[sl] = res.var
-        for c in range(res.var.shape[0]):
-            k = min(int(tr.n[c]), cap)
-            rows.append((tr.species[c, :k].copy(), tr.code[c, :k].copy(), int(tr.n[c])))
+        dev = torch.device("cuda", 0)
+        dv, df, dk = (torch.tensor(x, device=dev) for x in (var, fix, rconst))
+        d_atol = chem.cell_atol(mech, dv, atol_rel, ATOL_FLOOR)
+        d_rtol = torch.full((var.shape[0], 1), float(rtol[0]), dtype=torch.float64, device=dev)
+        res, _, tr = chem.rosenbrock_trace_cells(mech, dv, df, dk, tstart, tend, ipar, rpar, d_atol, d_rtol, cap=cap, ctrl=False)
+        torch.cuda.synchronize()
+        out, species, code, n = (x.cpu().numpy() for x in (res.var, tr.species, tr.code, tr.n))
+    rows = []
+    for c in range(out.shape[0]):
+        k = min(int(n[c]), cap)
+        rows.append((species[c, :k].copy(), code[c, :k].copy(), int(n[c])))
     return out, rows
 
 
-def trace_cpu(mech, var, fix, rconst, tstart, tend, opts_of_cell, cap):
-    """the same from the restatement (tests/ros_trace_py.py over the C oracle)"""
+def trace_cpu(mech, var, fix, rconst, tstart, tend, opts, cap, atol_rel=None):
+    """the same from the restatement (tests/ros_trace_py.py over the C oracle), cell by cell"""
     sys.path.insert(0, os.path.join(REPO, "tests"))
     import ros_trace_py as RT
     from mistra_amd import mechtab
     from oracle.oracle import Oracle
     o, diag = Oracle(mech), mechtab.load(mech).diag
+    ipar, rpar, atol, rtol = opts
+    per_cell = None if atol_rel is None else cell_atol_rows(mech, var, atol_rel)
     out, rows = np.empty_like(var), []
     for c in range(var.shape[0]):
-        opt = opts_of_cell(c) if callable(opts_of_cell) else opts_of_cell
-        r = RT.rosenbrock_trace(o, diag, var[c], fix[c], rconst[c], *opt, tstart=tstart, tend=tend)
+        at = atol if per_cell is None else np.full_like(atol, per_cell[c, 0])
+        r = RT.rosenbrock_trace(o, diag, var[c], fix[c], rconst[c], ipar, rpar, at, rtol, tstart=tstart, tend=tend)
         out[c] = r[0]
         tr = r[5]
         rows.append((tr.species[:cap].copy(), tr.code[:cap].copy(), len(tr.species)))
     return out, rows
+
+
+def yardstick(mech, var, fix, rconst, tstart, tend, cpu):
+    """the cells' end state by Rodas4 at RelTol 1e-7 and INTEGRATE_x's AbsTol -> var_out: one batched call, or the restatement under --cpu"""
+    ipar, rpar, atol, rtol = options(mech, None, YARDSTICK_RTOL)
+    ipar[3] = YARDSTICK_METHOD
+    if not cpu:
+        from mistra_amd import chem
+        return chem.rosenbrock(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol)[0].var
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import ros_methods_py as RM
+    from mistra_amd import mechtab
+    from oracle.oracle import Oracle
+    o, diag = Oracle(mech), mechtab.load(mech).diag
+    return np.array([RM.rosenbrock(o, diag, var[c], fix[c], rconst[c], ipar, rpar, atol, rtol, tstart, tend)[0] for c in range(var.shape[0])])
+
+
+def distances(got, want):
+    """-> (largest relative difference over the species above 1e-3 of their cell's maximum, largest over all species with the floor 1e-12 x max|c|):
+    the two measures of tests/conftest.py (rel_diff), NaN where nothing can be compared"""
+    got, want = np.atleast_2d(got), np.atleast_2d(want)
+    top = np.abs(want).max(axis=1, keepdims=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rel = np.abs(got - want) / np.abs(want)
+        major = np.abs(want) > 1.0e-3 * top
+        a = float(rel[major].max()) if major.any() else float("nan")
+        b = float((np.abs(got - want) / (np.abs(want) + 1.0e-12 * top)).max())
+    return a, b
 
 
 def control_table(var_in, var_out, rows, top=8):
@@ -148,22 +201,23 @@ def main(argv=None):
     ap.add_argument("--top", type=int, default=8, help="species listed")
     ap.add_argument("--names", help="file with one species name per line, in VAR's order")
     ap.add_argument("--cpu", action="store_true", help="run the Python restatement instead of the GPU")
+    ap.add_argument("--yardstick", action="store_true", help="also print the end state's distance from Rodas4 at RelTol 1e-7, INTEGRATE_x's AbsTol")
     a = ap.parse_args(argv)
     if a.atol is not None and a.atol_rel is not None:
         ap.error("--atol and --atol-rel exclude each other")
     var, fix, rconst = load_cells(a.mech, a.golden, a.workload, a.cells)
-    if a.atol_rel is not None:
-        opts = lambda c: options(a.mech, a.atol_rel * np.abs(var[c]).max(), a.rtol)  # noqa: E731
-        what = "AbsTol = %g x the cell's largest concentration" % a.atol_rel
-    else:
-        opts = options(a.mech, a.atol, a.rtol)
-        what = "AbsTol = %g" % opts[2][0]
+    opts = options(a.mech, a.atol, a.rtol)
+    what = "AbsTol = %g" % opts[2][0] if a.atol_rel is None else "AbsTol = %g x the cell's largest concentration" % a.atol_rel
     run = trace_cpu if a.cpu else trace_gpu
-    out, rows = run(a.mech, var, fix, rconst, a.tstart, a.tend, opts, a.cap)
+    out, rows = run(a.mech, var, fix, rconst, a.tstart, a.tend, opts, a.cap, a.atol_rel)
     names = [l.strip() for l in open(a.names)] if a.names else None
     print("%s, %d cells, %g -> %g s, Ros3, %s, RelTol = %g (%s)" % (a.mech, var.shape[0], a.tstart, a.tend, what, 1.0e-3 if a.rtol is None else a.rtol,
                                                                    "CPU restatement" if a.cpu else "GPU trace"))
     print(format_table(control_table(var, out, rows, a.top), names))
+    if a.yardstick:
+        major, every = distances(out, yardstick(a.mech, var, fix, rconst, a.tstart, a.tend, a.cpu))
+        print("distance from the yardstick (Rodas4, RelTol = %g, AbsTol = 1e-25): species above 1e-3 of the cell's maximum: %.3e   all species, floor "
+              "1e-12 x max|c|: %.3e" % (YARDSTICK_RTOL, major, every))
     return 0
 
 
