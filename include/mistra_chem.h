@@ -271,6 +271,32 @@ int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double*
  * is touched.  Needs NVAR alone: user slots have it.  d_atol is a tolerance array of width ntol = 1 for the cells entries above. */
 int mistra_chem_cell_atol_device(int mech, int ncell, const double* d_var, double factor, double floor, double* d_atol, void* hip_stream);
 
+/* OPT-IN integrator policy, one per mechanism, process-wide, off by default: what the entries that carry no options of their own
+ * run instead of Ros3 and the options' AbsTol.  While none is set nothing differs from a library without these entries.
+ *   method       1 .. 5 in IPAR(4)'s numbering: Ros2, Ros3, Ros4, Rodas3, Rodas4.  0 is refused with a text (in Rosenbrock_x it selects Ros4: a quiet
+ *                default here would be a trap); 2 keeps Ros3 and sets the tolerance part alone.  A user slot has Ros3 only.
+ *   atol_factor  0: no cell-relative AbsTol, the options in force supply AbsTol.  Otherwise atol_factor and atol_floor are finite and positive
+ *                (mistra_chem_cell_atol_device's rule and texts), and every species of a cell gets AbsTol = max(atol_floor, atol_factor * max_i |VAR(i)|),
+ *                the maximum over the state the integrator receives, NaN entries ignored, formed once per call inside the integrator kernel.
+ * Everything else — RelTol, Hmin / Hmax / Hstart, the four factors, Max_no_steps, the autonomous flag — stays the options in force:
+ * mistra_chem_set_options' when set, else INTEGRATE_x's values.  Options and policy are kept apart: setting or clearing one keeps the other, and
+ * mistra_chem_set_options goes on refusing the four other methods.
+ * Honoured by mistra_chem_integrate, _integrate_ex, _integrate_env_ex, _integrate_hstart_ex, _integrate_device, _integrate_device_hstart,
+ * _integrate_common(_status) (ATOL / RTOL written to the COMMON block stay the options' values), mistra_chem_drive_device and mistra_chem_drive / _begin /
+ * _end, on every device slot.  Ignored by the entries whose options travel with the call (mistra_chem_rosenbrock*) and by mistra_chem_debug_first_step(_ex),
+ * which stays the Ros3 diagnostic.  Step reuse works with a policy (a remembered step goes before Hstart); set and clear empty the step memory and fail
+ * while a column step of the mechanism is open.
+ * mistra_chem_check_policy: the checks alone, no device, works before init.  mistra_chem_get_policy: *is_set = 0 | 1, the rest written when set; any of
+ * them may be NULL; works before init.
+ * Environment, read once by the first initialisation or the first policy entry: MISTRA_CHEM_METHOD and MISTRA_CHEM_ATOL_REL set gas, aer and tot,
+ * MISTRA_CHEM_METHOD_G / _A / _T and MISTRA_CHEM_ATOL_REL_G / _A / _T one of them and go before the former.  A method is a name (ros2, ros3, ros4, rodas3,
+ * rodas4, any letter case) or 1 .. 5; ATOL_REL is `factor` or `factor,floor` (floor 1e-25 when left out).  A value that cannot be read makes
+ * mistra_chem_init and every policy entry fail with a text that names the variable.  mistra_chem_finalize puts the environment's policy back. */
+int mistra_chem_set_policy(int mech, int method, double atol_factor, double atol_floor);
+int mistra_chem_clear_policy(int mech);
+int mistra_chem_get_policy(int mech, int32_t* is_set, int32_t* method, double* atol_factor, double* atol_floor);
+int mistra_chem_check_policy(int mech, int method, double atol_factor, double atol_floor);
+
 /* The method tables the kernels were compiled with (Ros2_x .. Rodas4_x, gas.f:1514-1895), pure host, works before init: method 1 .. 5, 0 = 3.
  * *S = ros_S; A15 / C15 = ros_A / ros_C, row-wise lower triangle, S*(S-1)/2 entries; M6, E6, gamma6 = ros_M, ros_E, ros_Gamma; newf6 =
  * ros_NewF (0/1); *elo = ros_ELO.  Entries past the method's own are zero; any pointer may be NULL.  (ros_Alpha is not kept: Fun_x ignores T.) */

@@ -129,6 +129,11 @@ def lib():
             L.mistra_chem_rosenbrock_trace_cells_ex.argtypes = L.mistra_chem_rosenbrock_cells_ex.argtypes + [C.c_int, _dp, _ip, _ip, _ip]
             L.mistra_chem_rosenbrock_trace_cells_device.argtypes = L.mistra_chem_rosenbrock_cells_device.argtypes + [C.c_int, vp, vp, vp, vp]
             L.mistra_chem_cell_atol_device.argtypes = [C.c_int, C.c_int, vp, C.c_double, C.c_double, vp, vp]
+        if hasattr(L, "mistra_chem_set_policy"):
+            L.mistra_chem_set_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
+            L.mistra_chem_check_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
+            L.mistra_chem_clear_policy.argtypes = [C.c_int]
+            L.mistra_chem_get_policy.argtypes = [C.c_int, _ip, _ip, _dp, _dp]
         if hasattr(L, "mistra_chem_user_mechs"):
             L.mistra_chem_mech_name.restype = C.c_char_p
             L.mistra_chem_mech_name.argtypes = [C.c_int]
@@ -423,6 +428,54 @@ def method_table(method):
                                           e.ctypes.data_as(_dp), g.ctypes.data_as(_dp), nf.ctypes.data_as(_ip), C.byref(elo)))
     n, low = s.value, s.value * (s.value - 1) // 2
     return MethodTable(n, a[:low].copy(), c[:low].copy(), m[:n].copy(), e[:n].copy(), g[:n].copy(), nf[:n].astype(bool), elo.value)
+
+
+# ---- the integrator policy (include/mistra_chem.h: mistra_chem_set_policy): opt-in, per mechanism; what the integrate family and the column driver
+#      run instead of Ros3 and the options' AbsTol
+Policy = namedtuple("Policy", "method atol_rel atol_floor")
+
+
+def _policy_args(method, atol_rel, atol_floor):
+    if isinstance(method, str):
+        by_name = {v.lower(): k for k, v in METHOD_NAMES.items()}
+        if method.lower() not in by_name:
+            raise MistraChemError("policy: unknown method %r (%s)" % (method, ", ".join(METHOD_NAMES.values())))
+        method = by_name[method.lower()]
+    return int(method), 0.0 if atol_rel is None else float(atol_rel), float(atol_floor)
+
+
+def check_policy(mech, method=2, atol_rel=None, atol_floor=1.0e-25):
+    """The checks of set_policy alone (mistra_chem_check_policy): raises with the library's text where set_policy would.  Needs no GPU."""
+    mid, _ = _mech_id(mech)
+    _check(lib().mistra_chem_check_policy(mid, *_policy_args(method, atol_rel, atol_floor)))
+
+
+def set_policy(mech, method=2, atol_rel=None, atol_floor=1.0e-25):
+    """The integrator policy of `mech` (mistra_chem_set_policy) for every later integrate call and column step: `method` 1 .. 5 or a METHOD_NAMES
+    string (2 / "Ros3" keeps the method), `atol_rel` None or 0 = the options' AbsTol, else AbsTol = max(atol_floor, atol_rel * max|VAR|) per cell.
+    Everything else stays the options in force.  The rosenbrock* calls and debug_first_step ignore it."""
+    mid, _ = _mech_id(mech)
+    args = _policy_args(method, atol_rel, atol_floor)
+    _check(lib().mistra_chem_check_policy(mid, *args))      # (a refusal needs no device)
+    if _inited_device is None:
+        init(0)
+    _check(lib().mistra_chem_set_policy(mid, *args))
+
+
+def clear_policy(mech):
+    """No policy for `mech`: Ros3 and the options' AbsTol, as without these calls."""
+    mid, _ = _mech_id(mech)
+    if _inited_device is None:
+        return
+    _check(lib().mistra_chem_clear_policy(mid))
+
+
+def get_policy(mech):
+    """-> Policy(method, atol_rel, atol_floor) in force for `mech` (atol_rel 0.0 = none), or None.  Needs no GPU."""
+    mid, _ = _mech_id(mech)
+    is_set, method, factor, floor = C.c_int32(0), C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
+    _check(lib().mistra_chem_get_policy(mid, C.byref(is_set), C.byref(method), C.byref(factor), C.byref(floor)))
+    return Policy(method.value, factor.value, floor.value) if is_set.value else None
 
 
 def rosenbrock(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None, atol=None, rtol=None, hstart=None):

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -649,6 +650,11 @@ struct MechState {
   // none are set, and IPAR(3) (0: the library's Max_no_steps)
   DevBuf<double> opt;
   int opt_max_steps = 0;
+  // the integrator policy on this slot (mistra_chem_set_policy): method 0 = none; pol_opt: INTEGRATE_x's values as an options block, read while a policy
+  // is set and no options are
+  int pol_method = 0;
+  double pol_factor = 0.0, pol_floor = 0.0;
+  DevBuf<double> pol_opt;
   // the per-call options of mistra_chem_rosenbrock_ex (host buffers: one block, the call is synchronous) and mistra_chem_rosenbrock_device
   DevBuf<double> call_opt;
   RosCallRing call_ring;
@@ -681,6 +687,7 @@ struct MechState {
     k.release(); rates.release(); pack.release(); kmt.release(); liq.release(); stc.release(); vmean.release();
     d_rct.release();
     opt.release(); opt_max_steps = 0;
+    pol_opt.release(); pol_method = 0; pol_factor = pol_floor = 0.0;
     call_opt.release(); call_ring.release();
     step_mem.release(); step_n = 0;
     s_hst.release(); s_tol.release();
@@ -730,6 +737,107 @@ struct RosOptions {
   RosResolved r;
   std::vector<double> block;      // the device block: RosOptSlot scalars, then AbsTol(1:NVAR), RelTol(1:NVAR) as the integrator uses them
 } g_opts[kMaxMechs];
+
+// ---- OPT-IN integrator policy (mistra_chem_set_policy): per mechanism, process-wide.  What the entries that carry no options of their own — the
+// integrate family and the column driver — run instead of Ros3 with the options' AbsTol: a method of Rosenbrock_x's five and / or a cell-relative
+// AbsTol (kernel_args.hpp: tol_cell_factor).  Everything else stays the options in force; with none set, INTEGRATE_x's values go into a block of the
+// library's own (MechState::pol_opt), which gives the product kernel's bits (DESIGN.md §8 a2').  Like the options it outlives a re-initialisation;
+// mistra_chem_finalize puts back what the environment asked for (read_policy_env).
+struct Policy {
+  bool set = false;
+  int method = kRos3;
+  double factor = 0.0, floor = 0.0;
+} g_policy[kMaxMechs], g_policy_env[kMaxMechs];
+
+// the checks of a policy, no device: 0, or the refusal
+int check_policy(int mech, int method, double factor, double floor) {
+  if (!known_mech(mech)) return fail("unknown mechanism id");
+  if (method == 0)
+    return fail("policy: method 0 is refused: in " + rosenbrock_name(mech) + " IPAR(4) = 0 selects Ros4; name the method, 1 .. 5 (Ros2, Ros3, Ros4, Rodas3, Rodas4; 2 keeps Ros3)");
+  if (method < 1 || method > 5) return fail("policy: method " + std::to_string(method) + " is none of " + rosenbrock_name(mech) + "'s: 1 .. 5 (Ros2, Ros3, Ros4, Rodas3, Rodas4)");
+  if (kMech[mech].user && method != kRos3) return fail_user_slot(mech, "kernel for this Rosenbrock method (Ros2, Ros4, Rodas3, Rodas4)");
+  if (factor != 0.0) {      // mistra_chem_cell_atol_device's rule and texts
+    if (!(factor > 0.0) || !std::isfinite(factor)) return fail("cell_atol: factor must be finite and positive");
+    if (!(floor > 0.0) || !std::isfinite(floor)) return fail("cell_atol: floor must be finite and positive");
+  }
+  return 0;
+}
+
+// INTEGRATE_x's values as an options block (gas.f:745-756): RTOL 1e-3, ATOL 1e-25, RPAR(3) = 1e-3, everything else Rosenbrock_x's default
+std::vector<double> options_block(int mech, const RosResolved& r, const double* atol, const double* rtol);
+int resolve_options(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, RosResolved* r);
+std::vector<double> base_options_block(int mech) {
+  int32_t ipar[20] = {0};
+  double rpar[20] = {0.0};
+  ipar[1] = 1; ipar[3] = 2;
+  rpar[2] = 1.0e-3;
+  const double atol = 1.0e-25, rtol = 1.0e-3;
+  RosResolved r;
+  (void)resolve_options(mech, ipar, rpar, &atol, &rtol, &r);
+  return options_block(mech, r, &atol, &rtol);
+}
+
+// The environment of a model binary that is already linked, read once (g_mu held) beside read_step_env: MISTRA_CHEM_METHOD and MISTRA_CHEM_ATOL_REL for
+// gas, aer and tot, MISTRA_CHEM_METHOD_G / _A / _T and MISTRA_CHEM_ATOL_REL_G / _A / _T for one of them (they go before the former).  A method is a name
+// (ros2, ros3, ros4, rodas3, rodas4, any letter case) or 1 .. 5; ATOL_REL is `factor` or `factor,floor` (floor: INTEGRATE_x's ATOL, 1e-25).  A value that
+// cannot be read that way is an error every initialisation and every policy entry reports with the variable's name: never a quiet run with something else.
+bool g_policy_env_read = false;
+std::string g_policy_env_err;
+bool parse_method(const char* s, int* method) {
+  static const char* names[5] = {"ros2", "ros3", "ros4", "rodas3", "rodas4"};
+  std::string v;
+  for (const char* p = s; *p; p++) v += (char)std::tolower((unsigned char)*p);
+  for (int i = 0; i < 5; i++)
+    if (v == names[i]) { *method = i + 1; return true; }
+  if (v.size() == 1 && v[0] >= '1' && v[0] <= '5') { *method = v[0] - '0'; return true; }
+  return false;
+}
+bool parse_double(const std::string& s, double* v) {
+  if (s.empty() || std::isspace((unsigned char)s[0])) return false;
+  char* end = nullptr;
+  *v = std::strtod(s.c_str(), &end);
+  return end && *end == '\0';
+}
+bool parse_atol_rel(const char* s, double* factor, double* floor) {
+  const std::string v = s;
+  const size_t k = v.find(',');
+  *floor = 1.0e-25;
+  if (!parse_double(v.substr(0, k), factor)) return false;
+  if (k != std::string::npos && !parse_double(v.substr(k + 1), floor)) return false;
+  return *factor > 0.0 && std::isfinite(*factor) && *floor > 0.0 && std::isfinite(*floor);
+}
+int read_policy_env() {
+  if (!g_policy_env_read) {
+    g_policy_env_read = true;
+    for (int mech = 0; mech < kBuiltinMechs; mech++) {
+      Policy p;
+      const std::string sfx = std::string("_") + "GAT"[mech];
+      for (const std::string& name : {std::string("MISTRA_CHEM_METHOD"), "MISTRA_CHEM_METHOD" + sfx}) {
+        const char* e = std::getenv(name.c_str());
+        if (!e) continue;
+        if (!parse_method(e, &p.method)) {
+          g_policy_env_err = name + "=" + e + ": a method is a name (ros2, ros3, ros4, rodas3, rodas4) or a number 1 .. 5";
+          break;
+        }
+        p.set = true;
+      }
+      for (const std::string& name : {std::string("MISTRA_CHEM_ATOL_REL"), "MISTRA_CHEM_ATOL_REL" + sfx}) {
+        const char* e = std::getenv(name.c_str());
+        if (!e) continue;
+        if (!parse_atol_rel(e, &p.factor, &p.floor)) {
+          g_policy_env_err = name + "=" + e + ": a cell-relative AbsTol is `factor` or `factor,floor`, both finite and positive";
+          break;
+        }
+        p.set = true;
+      }
+      if (!g_policy_env_err.empty()) break;
+      g_policy_env[mech] = p;
+    }
+    if (g_policy_env_err.empty())
+      for (int mech = 0; mech < kBuiltinMechs; mech++) g_policy[mech] = g_policy_env[mech];
+  }
+  return g_policy_env_err.empty() ? 0 : fail(g_policy_env_err);
+}
 
 // ---- OPT-IN step reuse of the batched driver (mistra_chem_set_step_reuse): per mechanism, process-wide host state; MISTRA_CHEM_HSTART_REUSE=1 in the
 // environment turns all three on, read once — by the first initialisation or the first look at the flags, whichever comes first (g_mu held)
@@ -846,6 +954,10 @@ int setup_mech(DeviceState& D, int mech) {
   if (g_opts[mech].set) {      // options set before this (re-)initialisation stay in force
     HIP_TRY(S.opt.upload(g_opts[mech].block));
     S.opt_max_steps = g_opts[mech].ipar[2];
+  }
+  if (g_policy[mech].set) {      // ... and so does a policy
+    HIP_TRY(S.pol_opt.upload(base_options_block(mech)));
+    S.pol_method = g_policy[mech].method; S.pol_factor = g_policy[mech].factor; S.pol_floor = g_policy[mech].floor;
   }
   S.ready = true;
   return 0;
@@ -1032,8 +1144,19 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.dense = DenseDev{k.dense_rows.p, k.schur_cells.p};
   a.trace_d = nullptr; a.trace_i = nullptr; a.ntrace = nullptr; a.ctrl = nullptr; a.trace_cap = 0;      // (the trace entries set them)
   a.tol_abs = nullptr; a.tol_rel = nullptr; a.tol_cell_stride = 0; a.tol_spec_stride = 0;      // (the cells entries set them)
+  a.tol_cell_factor = 0.0; a.tol_cell_floor = 0.0;      // (policy_args sets them)
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
+}
+
+// The integrator policy of the slot laid over the arguments of an entry that carries no options of its own (the integrate family, the column driver,
+// the COMMON-block entry) -> the method to launch.  No policy: nothing changes, Ros3.  The entries whose options travel with the call and the Ros3
+// diagnostics (first-step dump, phase timing) do not come here.
+int policy_args(const MechState& S, KernelArgs* a) {
+  if (!S.pol_method) return kRos3;
+  if (!a->opt) a->opt = S.pol_opt.p;      // INTEGRATE_x's values: a policy runs the options instantiations
+  a->tol_cell_factor = S.pol_factor; a->tol_cell_floor = S.pol_floor;
+  return S.pol_method;
 }
 
 PackDev pack_dev(const MechState& S) { return S.pack.dev(S.tab.nreact, S.k.consts.p); }
@@ -1103,6 +1226,7 @@ int on_primary(int mech, unsigned need, bool mutates, Slot* t) {
 
 int init_locked(int n, const int* ids) {
   read_step_env();
+  if (int rc = read_policy_env()) return rc;
   int count = 0;
   hipError_t e = hipGetDeviceCount(&count);
   if (e != hipSuccess || count <= 0) return fail("no HIP device available (this library has no CPU path)");
@@ -1176,6 +1300,7 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
       a.tol_spec_stride = call->vector ? 1 : 0;
     }
   }
+  const int method = call ? call->method : policy_args(S, &a);
   const bool trace = call && call->trace;
   const size_t cap = trace ? (size_t)call->cap : 0;
   if (trace) {      // the caller's log arrays go up first: rows the kernel does not write come back as they were
@@ -1217,7 +1342,7 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     HIP_TRY(prof.reserve(nc * kProfSlots));
     a.prof = prof.p;
   }
-  if (int rc = launch(D, mech, a, nullptr, call ? call->method : (int)kRos3)) return rc;
+  if (int rc = launch(D, mech, a, nullptr, method)) return rc;
   HIP_TRY(hipDeviceSynchronize());
   if (profile) {
     std::vector<unsigned long long> h(nc * kProfSlots);
@@ -1289,7 +1414,7 @@ int column_step(DeviceState& D, int mech, int ncell, const ColumnDev& c, double 
     LAUNCH_TRY(launch_step_gather(c.mem, c.mem_n, c.layer, ncell, c.hstart, st));
     a.hstart = c.hstart;
   }
-  if (int rc = launch(D, mech, a, st)) return rc;
+  if (int rc = launch(D, mech, a, st, policy_args(S, &a))) return rc;
   if (c.mem) {
     HIP_TRY(hipMemsetAsync(c.mem, 0, (size_t)c.mem_n * sizeof(double), st));
     LAUNCH_TRY(launch_step_store(c.mem, c.mem_n, c.layer, ncell, c.ierr, c.th, st));
@@ -1437,6 +1562,7 @@ int mistra_chem_device_count(void) { return g_inited ? (int)g_devs.size() : 0; }
 void mistra_chem_finalize(void) {
   std::lock_guard<std::mutex> lock(g_mu);
   for (auto& o : g_opts) o = RosOptions{};
+  for (int m = 0; m < kMaxMechs; m++) g_policy[m] = g_policy_env[m];      // (what the environment asked for stays)
   release_all();
 }
 
@@ -1461,7 +1587,7 @@ int mistra_chem_integrate_device_hstart(int mech, int ncell, const double* d_var
   if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
   KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, tin, tout, d_var_out, d_ierr, d_stats, d_texit_hexit);
   a.hstart = d_hstart;
-  return launch(*t.D, mech, a, static_cast<hipStream_t>(hip_stream));
+  return launch(*t.D, mech, a, static_cast<hipStream_t>(hip_stream), policy_args(*t.S, &a));
 }
 
 int mistra_chem_table_stack_depth(const char* path, int stcoeff) {
@@ -2139,6 +2265,74 @@ int mistra_chem_get_options(int mech, int32_t* is_set, int32_t* ipar, double* rp
   return 0;
 }
 
+// ---- OPT-IN integrator policy
+int mistra_chem_check_policy(int mech, int method, double atol_factor, double atol_floor) {
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    if (int rc = read_policy_env()) return rc;      // (a value in the environment that cannot be read is reported by every policy entry)
+  }
+  return check_policy(mech, method, atol_factor, atol_floor);
+}
+
+// next.set = false: clear.  Every slot, walked and synchronised as mistra_chem_set_options walks them
+static int install_policy(int mech, const Policy& next) {
+  if (int rc = lazy_init()) return rc;
+  if (int rc = check_call(mech, 0, true)) return rc;
+  std::lock_guard<std::mutex> lock(g_mu);
+  if (int rc = read_policy_env()) return rc;
+  Slot t;
+  if (int rc = on_primary(mech, 0, true, &t)) return rc;      // (a column step in flight reads the block that would be freed here)
+  const std::vector<double> block = next.set ? base_options_block(mech) : std::vector<double>();
+  int rc = 0;
+  for (auto& D : g_devs) {
+    MechState& S = D.mech[mech];
+    if (hipSetDevice(D.id) != hipSuccess) { rc = fail("hipSetDevice failed"); break; }
+    if (hipDeviceSynchronize() != hipSuccess) { rc = fail("hipDeviceSynchronize failed"); break; }      // (launches of the device-buffer entries that still read the old block)
+    S.pol_opt.release();
+    S.pol_method = 0; S.pol_factor = S.pol_floor = 0.0;
+    S.step_n = 0;      // another method or AbsTol: the step sizes remembered under the old ones are forgotten
+    if (next.set) {
+      if (hipError_t e = S.pol_opt.upload(block)) { rc = fail(std::string("uploading the policy's options block: ") + hipGetErrorString(e)); break; }
+      S.pol_method = next.method; S.pol_factor = next.factor; S.pol_floor = next.floor;
+    }
+  }
+  (void)hipSetDevice(g_devs[0].id);
+  if (rc) {      // a failed upload leaves no slot with a policy the others do not have
+    for (auto& D : g_devs) { MechState& S = D.mech[mech]; S.pol_opt.release(); S.pol_method = 0; S.pol_factor = S.pol_floor = 0.0; }
+    g_policy[mech] = Policy{};
+    return rc;
+  }
+  g_policy[mech] = next;
+  return 0;
+}
+
+int mistra_chem_set_policy(int mech, int method, double atol_factor, double atol_floor) {
+  if (int rc = check_policy(mech, method, atol_factor, atol_floor)) return rc;      // (before a device is touched)
+  Policy next;
+  next.set = true; next.method = method; next.factor = atol_factor;
+  next.floor = atol_factor != 0.0 ? atol_floor : 0.0;      // (not read without a factor)
+  return install_policy(mech, next);
+}
+
+int mistra_chem_clear_policy(int mech) {
+  if (!known_mech(mech)) return fail("unknown mechanism id");
+  return install_policy(mech, Policy{});
+}
+
+int mistra_chem_get_policy(int mech, int32_t* is_set, int32_t* method, double* atol_factor, double* atol_floor) {
+  if (!known_mech(mech)) return fail("unknown mechanism id");
+  if (!is_set) return fail("null pointer");
+  std::lock_guard<std::mutex> lock(g_mu);
+  if (int rc = read_policy_env()) return rc;
+  const Policy& p = g_policy[mech];
+  *is_set = p.set ? 1 : 0;
+  if (!p.set) return 0;
+  if (method) *method = p.method;
+  if (atol_factor) *atol_factor = p.factor;
+  if (atol_floor) *atol_floor = p.floor;
+  return 0;
+}
+
 int mistra_chem_debug_first_step(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                                  double tout, double* dump) {
   return mistra_chem_debug_first_step_ex(mech, ncell, var_in, fix, rconst, tin, tout, nullptr, dump, nullptr, nullptr, nullptr);
@@ -2496,7 +2690,7 @@ int mistra_chem_integrate_common_status(int mech, void* gdata, double* tin, doub
   KernelArgs a = make_args(S, 1, A.d(o_in), A.d(o_in) + nv, A.d(o_in) + nv + nf, *tin, *tout, A.d(o_var), A.d<int32_t>(o_ierr), A.d<int32_t>(o_stats), A.d(o_th));
   a.h_last = A.d(o_hl);
   a.sing_rows = A.d<int32_t>(o_sing);
-  if (int rc = launch(*t.D, mech, a, A.st)) return rc;
+  if (int rc = launch(*t.D, mech, a, A.st, policy_args(S, &a))) return rc;
   HIP_TRY(hipMemcpyAsync(A.h(o_var), A.d(o_var), B.end - o_var, hipMemcpyDeviceToHost, A.st));
   HIP_TRY(hipStreamSynchronize(A.st));
   std::memcpy(c, A.h(o_var), (size_t)nv * d8);

@@ -98,6 +98,11 @@ struct KernelArgs {
   const double* tol_rel;       // [ncell][tol_cell_stride] or null
   int32_t tol_cell_stride;     // the row width ntol: 1 or NVAR
   int32_t tol_spec_stride;     // 1: vector tolerances (IPAR(2) = 0), 0: scalar ones (entry 0 of the row for every species)
+  // the integrator policy's cell-relative AbsTol (mistra_chem_set_policy; options instantiations only, tol_abs null): every species of a cell gets
+  // max(tol_cell_floor, tol_cell_factor * max_i |VAR(i)|), formed by the kernel from the state it receives, once per call; RelTol stays the block's.
+  // 0 = off: the block's AbsTol.  The host has validated both (capi.cpp: check_policy); the entries whose options travel with the call pass 0.
+  double tol_cell_factor;
+  double tol_cell_floor;
 };
 
 }  // namespace mistra

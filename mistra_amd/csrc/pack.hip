@@ -9,6 +9,7 @@
 // Integer / index work and plain products: every result is bit-identical to the reference's (built with -ffp-contract=off; the
 // float32 literals 0.21, 0.79, 55.55 spelled out).  Memory-bound: a layer is ~10 KB in, ~4 KB out.
 #include "pack.hpp"
+#include "wave_ops.hpp"
 
 namespace mistra {
 
@@ -518,36 +519,9 @@ hipError_t launch_step_store(double* mem, int n, const int32_t* layer, int nlaye
 
 // ---- AbsTol from the cell's own state (mistra_chem_cell_atol_device): atol[c] = max(floor, factor * max_i |VAR(i, c)|).  One wave per cell, the lanes
 //      striding over NVAR; NaN entries are ignored (no comparison with one holds), so a cell without a positive entry gets the floor.  The wave's maximum
-//      comes by the cross-lane operations of the integrator's wave_sum (ros3_kernel.hip): DPP inside a lane row, v_permlane16/32_swap across rows.
+//      comes by wave_max (wave_ops.hpp), which the integrator's options kernels use for the same maximum.
 namespace {
 constexpr int kAtolWaves = 4;
-template <int CTRL>
-__device__ __forceinline__ double dpp_partner(double v) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
-  return __builtin_bit_cast(double, (uint64_t)(uint32_t)lo | ((uint64_t)(uint32_t)hi << 32));
-}
-__device__ __forceinline__ double max_nn(double a, double b) { return b > a ? b : a; }      // (neither is a NaN here)
-__device__ __forceinline__ double wave_max(double v) {
-  v = max_nn(v, dpp_partner<0xB1>(v));       // quad_perm [1,0,3,2]
-  v = max_nn(v, dpp_partner<0x4E>(v));       // quad_perm [2,3,0,1]
-  v = max_nn(v, dpp_partner<0x141>(v));      // row_half_mirror
-  v = max_nn(v, dpp_partner<0x140>(v));      // row_mirror
-  {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const auto l = __builtin_amdgcn_permlane16_swap((uint32_t)u, (uint32_t)u, false, false);
-    const auto h = __builtin_amdgcn_permlane16_swap((uint32_t)(u >> 32), (uint32_t)(u >> 32), false, false);
-    v = max_nn(__builtin_bit_cast(double, (uint64_t)l[0] | ((uint64_t)h[0] << 32)), __builtin_bit_cast(double, (uint64_t)l[1] | ((uint64_t)h[1] << 32)));
-  }
-  {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const auto l = __builtin_amdgcn_permlane32_swap((uint32_t)u, (uint32_t)u, false, false);
-    const auto h = __builtin_amdgcn_permlane32_swap((uint32_t)(u >> 32), (uint32_t)(u >> 32), false, false);
-    v = max_nn(__builtin_bit_cast(double, (uint64_t)l[0] | ((uint64_t)h[0] << 32)), __builtin_bit_cast(double, (uint64_t)l[1] | ((uint64_t)h[1] << 32)));
-  }
-  return v;
-}
 __global__ __launch_bounds__(kAtolWaves * 64) void cell_atol_kernel(int nvar, int ncell, const double* __restrict__ var, double factor, double floor_,
                                                                     double* __restrict__ atol) {
   const int lane = threadIdx.x & 63;

@@ -20,6 +20,7 @@
 #include "kernel_args.hpp"
 #include "ros3_kernel.hpp"
 #include "ros_methods.hpp"
+#include "wave_ops.hpp"
 
 namespace mistra {
 
@@ -119,13 +120,6 @@ __device__ __forceinline__ double scalar_const(double v) {
 // agree bit for bit).  Inside a lane row the partner's value comes by DPP (quad swaps, half-row mirror, row mirror: ~10 cycles a step),
 // across lane rows by v_permlane16/32_swap; __shfl_xor went through ds_bpermute, an LDS round trip per step (six of them: ~800 cycles of
 // every step's error norm).
-template <int CTRL>
-__device__ __forceinline__ double dpp_partner(double v) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
-  return __builtin_bit_cast(double, (uint64_t)(uint32_t)lo | ((uint64_t)(uint32_t)hi << 32));
-}
 __device__ __forceinline__ double wave_sum(double v) {
   v += dpp_partner<0xB1>(v);       // quad_perm [1,0,3,2]
   v += dpp_partner<0x4E>(v);       // quad_perm [2,3,0,1]
@@ -1274,6 +1268,30 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       const int s = q * NT + t;
       atol_r[q] = s < NVAR ? G_(ta)[s * ss] : 1.0;
       rtol_r[q] = s < NVAR ? G_(tr)[s * ss] : 0.0;
+    }
+    // a.tol_cell_factor != 0 (the integrator policy, capi.cpp: policy_args): AbsTol of every species = max(floor, factor * max_i |Y(i)|) over the state as
+    // received, as cell_atol_kernel (pack.hip) forms it — a NaN stays out of the maximum, the padding entries are 0.  Each thread over its own species,
+    // the wave by wave_max, the workgroup through one cell of red[] per wave and one barrier (as the -5 check below).  The host has validated factor,
+    // floor and RelTol: no check here.  In front of the step loop like the rest: only atol_r leaves.
+    if (!cells && a.tol_cell_factor != 0.0) {      // (uniform over the call)
+      double m = 0.0;
+#pragma unroll
+      for (int q = 0; q < SPT; q++) {
+        const double v = fabs(y[q]);
+        if (v > m) m = v;
+      }
+      m = wave_max(m);
+      if constexpr (NW > 1) {
+        if (lane == 0) red[wave] = m;
+        lds_barrier();
+        m = red[0];
+#pragma unroll
+        for (int w = 1; w < NW; w++) m = max_nn(m, red[w]);
+      }
+      const double r = a.tol_cell_factor * m;
+      const double at = r > a.tol_cell_floor ? r : a.tol_cell_floor;
+#pragma unroll
+      for (int q = 0; q < SPT; q++) atol_r[q] = q * NT + t < NVAR ? at : 1.0;
     }
     autonomous = opt(kOptAutonomous) != 0.0;
     if (cells) {      // (uniform over the workgroup)

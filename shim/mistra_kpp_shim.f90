@@ -27,6 +27,13 @@
 ! and for a caller that orders its own batches, the batched form with a first step size per cell (<= 0: the reference's), HEXIT of one call being HSTART of the next:
 !     SUBROUTINE INTEGRATE_BATCH_H_g / _a / _t (NCELL, VAR, FIX, RCONST, TIN, TOUT, HSTART, TEXIT, HEXIT, IERR, ISTAT)
 !
+! OPT-IN, not the reference's behaviour (include/mistra_chem.h: mistra_chem_set_policy; INTEGRATION.md 4l): another of Rosenbrock_x's five methods and / or
+! a cell-relative AbsTol = MAX(ATOL_FLOOR, ATOL_FACTOR * MAXVAL(ABS(VAR))) for every call above and for the single-pass batched driver (KPP_DRIVE_RUN);
+! everything else stays the options in force.  Call once after start-up, next to MISTRA_SET_OPTIONS_x if that is called:
+!     SUBROUTINE MISTRA_SET_POLICY_g / _a / _t (METHOD, ATOL_FACTOR, ATOL_FLOOR, IERR)  METHOD 1 .. 5 (2 keeps Ros3; 0 is refused), ATOL_FACTOR 0 = the options' AbsTol
+!     SUBROUTINE MISTRA_CLEAR_POLICY_g / _a / _t ()
+! IERR = 0, or 1 where the library refuses the values: its text goes to unit 6 and the previous policy stays.
+!
 ! One layer below INTEGRATE_x: Rosenbrock_x itself for NCELL cells, with its own argument list and ALL FIVE methods (IPAR(4) = 1 Ros2, 2 Ros3, 3 Ros4,
 ! 4 Rodas3, 5 Rodas4, 0 = Ros4; include/mistra_chem.h: mistra_chem_rosenbrock_ex).  The options are the call's alone: the ones MISTRA_SET_OPTIONS_x put
 ! in force are neither read nor changed.
@@ -122,6 +129,23 @@ module mistra_chem_c_api
        integer(c_int), value :: mech, on
        integer(c_int) :: rc
      end function mistra_chem_set_step_reuse
+     function mistra_chem_set_policy(mech, method, atol_factor, atol_floor) bind(C, name="mistra_chem_set_policy") result(rc)
+       import :: c_int, c_double
+       integer(c_int), value :: mech, method
+       real(c_double), value :: atol_factor, atol_floor
+       integer(c_int) :: rc
+     end function mistra_chem_set_policy
+     function mistra_chem_check_policy(mech, method, atol_factor, atol_floor) bind(C, name="mistra_chem_check_policy") result(rc)
+       import :: c_int, c_double
+       integer(c_int), value :: mech, method
+       real(c_double), value :: atol_factor, atol_floor
+       integer(c_int) :: rc
+     end function mistra_chem_check_policy
+     function mistra_chem_clear_policy(mech) bind(C, name="mistra_chem_clear_policy") result(rc)
+       import :: c_int
+       integer(c_int), value :: mech
+       integer(c_int) :: rc
+     end function mistra_chem_clear_policy
      function mistra_chem_last_error() bind(C, name="mistra_chem_last_error") result(msg)
        import :: c_ptr
        type(c_ptr) :: msg
@@ -231,6 +255,37 @@ contains
     logical, intent(in) :: ON
     if (mistra_chem_set_step_reuse(int(mech, c_int), int(merge(1, 0, ON), c_int)) /= 0) call mistra_chem_fail('MISTRA_STEP_REUSE_'//sfx)
   end subroutine step_reuse
+
+  ! The integrator policy of the mechanism.  Values the library refuses (its checks alone, no device) leave the previous policy in force: the text goes to
+  ! unit 6 and IERR = 1; anything else that fails stops the program like every other failure.
+  subroutine set_policy(mech, sfx, METHOD, ATOL_FACTOR, ATOL_FLOOR, IERR)
+    integer, intent(in) :: mech
+    character(len=1), intent(in) :: sfx
+    integer, intent(in) :: METHOD
+    real(c_double), intent(in) :: ATOL_FACTOR, ATOL_FLOOR
+    integer :: IERR
+    character(kind=c_char), pointer :: txt(:)
+    integer :: i
+    IERR = 0
+    if (mistra_chem_check_policy(int(mech, c_int), int(METHOD, c_int), ATOL_FACTOR, ATOL_FLOOR) /= 0) then
+       call c_f_pointer(mistra_chem_last_error(), txt, [512])
+       write (6, '(3a)', advance='no') ' MISTRA_SET_POLICY_', sfx, ': '
+       do i = 1, 512
+          if (txt(i) == c_null_char) exit
+          write (6, '(a)', advance='no') txt(i)
+       end do
+       write (6, *)
+       IERR = 1
+       return
+    end if
+    if (mistra_chem_set_policy(int(mech, c_int), int(METHOD, c_int), ATOL_FACTOR, ATOL_FLOOR) /= 0) call mistra_chem_fail('MISTRA_SET_POLICY_'//sfx)
+  end subroutine set_policy
+
+  subroutine clear_policy(mech, sfx)
+    integer, intent(in) :: mech
+    character(len=1), intent(in) :: sfx
+    if (mistra_chem_clear_policy(int(mech, c_int)) /= 0) call mistra_chem_fail('MISTRA_CLEAR_POLICY_'//sfx)
+  end subroutine clear_policy
 
   ! the three one-cell routines and the three batched ones differ in sizes only
   subroutine integrate_one(mech, sfx, gdata, TIN, TOUT)
@@ -559,6 +614,52 @@ subroutine MISTRA_STEP_REUSE_t(ON)
   logical :: ON
   call step_reuse(2, 't', ON)
 end subroutine MISTRA_STEP_REUSE_t
+
+! ---- OPT-IN integrator policy (include/mistra_chem.h: mistra_chem_set_policy): call once after start-up
+subroutine MISTRA_SET_POLICY_g(METHOD, ATOL_FACTOR, ATOL_FLOOR, IERR)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: METHOD, IERR
+  real(c_double) :: ATOL_FACTOR, ATOL_FLOOR
+  call set_policy(0, 'g', METHOD, ATOL_FACTOR, ATOL_FLOOR, IERR)
+end subroutine MISTRA_SET_POLICY_g
+
+subroutine MISTRA_CLEAR_POLICY_g()
+  use mistra_chem_c_api
+  implicit none
+  call clear_policy(0, 'g')
+end subroutine MISTRA_CLEAR_POLICY_g
+
+subroutine MISTRA_SET_POLICY_a(METHOD, ATOL_FACTOR, ATOL_FLOOR, IERR)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: METHOD, IERR
+  real(c_double) :: ATOL_FACTOR, ATOL_FLOOR
+  call set_policy(1, 'a', METHOD, ATOL_FACTOR, ATOL_FLOOR, IERR)
+end subroutine MISTRA_SET_POLICY_a
+
+subroutine MISTRA_CLEAR_POLICY_a()
+  use mistra_chem_c_api
+  implicit none
+  call clear_policy(1, 'a')
+end subroutine MISTRA_CLEAR_POLICY_a
+
+subroutine MISTRA_SET_POLICY_t(METHOD, ATOL_FACTOR, ATOL_FLOOR, IERR)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: METHOD, IERR
+  real(c_double) :: ATOL_FACTOR, ATOL_FLOOR
+  call set_policy(2, 't', METHOD, ATOL_FACTOR, ATOL_FLOOR, IERR)
+end subroutine MISTRA_SET_POLICY_t
+
+subroutine MISTRA_CLEAR_POLICY_t()
+  use mistra_chem_c_api
+  implicit none
+  call clear_policy(2, 't')
+end subroutine MISTRA_CLEAR_POLICY_t
 
 ! ---- Rosenbrock_x, batched: the reference's argument list (gas.f:777) in front of the per-cell results.  ATOL / RTOL: NVAR entries (IPAR(2) = 0) or one.
 subroutine ROSENBROCK_BATCH_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)

@@ -28,6 +28,8 @@
 !          shim_driver D2 <in.bin> <out.bin>           the same column step TWICE in a row under step reuse: MISTRA_STEP_REUSE_g/_a/_t(.true.) first, the second
 !                                                      step on the arrays the first one left (tkpp = 10).  in.bin as for D (nrep is not used).  out.bin: the arrays
 !                                                      after the second step | per step and layer: mech, k, ierr, 8 statistics, texit, hexit, H
+!          shim_driver DP <in.bin> <out.bin>           the column step of D under an integrator policy: in.bin starts with METHOD, ATOL_FACTOR, ATOL_FLOOR (float64),
+!                                                      handed to MISTRA_SET_POLICY_g/_a/_t for the mechanisms the step has layers of, and goes on as for D; out.bin as for D
 !          shim_driver <Ka|Kt|Ha|Ht|Va|Vt|Sa|St|Qa|Qt|Ca|Rg|Ra|Rt> <in.bin> <out.bin>   liq_parm's kernels through shim/mistra_kpp_liq.f90 (SURVEY §8 f3): K = FAST_K_MT_BATCH
 !                                                      (in: nlayer, nka, nkt, nkc, nspec, ka, ifeed, nkc_l | kw | rq | ff cw cm freep alpha vmean xkmt t p vt;
 !                                                      out: xkmt, vt), H = HENRY_BATCH (in: nlayer, nspec | tt; out: henry), V = V_MEAN_BATCH (the same shapes; out: vmean), S = ST_COEFF_BATCH (in: nlayer, nspec, lpJoyce14bc, lpBuxmann15alph | env(5,nlayer); out: alpha), R = DRY_RATES_BATCH (in: nlayer | tt, freep, rcd(2,nlayer), vmean4 / henry4 (4,nlayer); out: xkmtd, xeq, henry4), C = CW_RC_BATCH (in: nlayer, nkt, nka, dry, ka, ifeed | kw, rq, e, crys4, ff, feu, cloud; out: rc, cw, cm, conv2, below), Q = EQUIL_CO_BATCH (in: nlayer,
@@ -47,7 +49,7 @@ program shim_driver
   case ('G'); call run_batch(0, 102, 3, 331, trim(fin), trim(fout))
   case ('A'); call run_batch(1, 257, 5, 979, trim(fin), trim(fout))
   case ('T'); call run_batch(2, 417, 7, 1627, trim(fin), trim(fout))
-  case ('D'); call run_drive(trim(fin), trim(fout), a1(2:2) == '2')
+  case ('D'); call run_drive(trim(fin), trim(fout), a1(2:2) == '2', a1(2:2) == 'P')
   case ('O')
      select case (a1(2:2))
      case ('G'); call run_batch(0, 102, 3, 331, trim(fin), trim(fout), .true.)
@@ -406,10 +408,14 @@ contains
     call CW_RC_BATCH(nl, nkt, nka, dry, ff, rq, e, kw, ka, ifeed, feu, cloud, crys4, rc, cw, cm, conv2, below)
     write (12) rc, cw, cm, conv2, dble(below)
   end subroutine run_cw_rc
-  subroutine run_drive(fin, fout, twice)
+  subroutine run_drive(fin, fout, twice, policy)
     use mistra_kpp_drive
     character(len=*), intent(in) :: fin, fout
     logical, intent(in) :: twice      ! two consecutive steps under step reuse instead of nrep repetitions of one
+    logical, intent(in) :: policy     ! the step under an integrator policy, read in front of the header
+    double precision :: pol(3)
+    integer :: ierr_pol
+    external :: MISTRA_SET_POLICY_g, MISTRA_SET_POLICY_a, MISTRA_SET_POLICY_t
     integer, parameter :: j2 = 121, j6 = 55, nkc = 4, nbgs = 122      ! global_params.f90:96-103, bud_s_g.f:63
     integer, parameter :: nenv(3) = [nenv_g, nenv_a, nenv_t]
     double precision :: hdr(7)
@@ -425,6 +431,7 @@ contains
     external :: MISTRA_RATES_ENV_SET_g, MISTRA_RATES_ENV_SET_a, MISTRA_RATES_ENV_SET_t, KPP_DRIVE_STAGE_g, KPP_DRIVE_STAGE_a, KPP_DRIVE_STAGE_t
     open (11, file=fin, access='stream', form='unformatted', status='old')
     open (12, file=fout, access='stream', form='unformatted', status='replace')
+    if (policy) read (11) pol
     read (11) hdr
     n = int(hdr(1)); j1 = int(hdr(2)); j5 = int(hdr(3)); nlev = int(hdr(4)); nrxn = int(hdr(5)); nl = int(hdr(6)); nrep = int(hdr(7))
     allocate (gm(2, j1, 3), gk(j1, 3), rm(2, j5, 3), rk(j5, 3), il(nlev), tmp(max(2 * j1, 2 * j5, nlev)))
@@ -447,6 +454,13 @@ contains
     do m = 1, 3      ! once per run, as KPP_DRIVE_RUN does on its first call (here only for the mechanisms the recorded step has layers of: the
        if (any(lmech == m)) call kpp_drive_maps(m, j1, gm(:, :, m), gk(:, m), j5, rm(:, :, m), rk(:, m))      ! file holds real maps only for those)
     end do
+    if (policy) then
+       ierr_pol = 0
+       if (any(lmech == 1)) call MISTRA_SET_POLICY_g(int(pol(1)), pol(2), pol(3), ierr_pol)
+       if (ierr_pol == 0 .and. any(lmech == 2)) call MISTRA_SET_POLICY_a(int(pol(1)), pol(2), pol(3), ierr_pol)
+       if (ierr_pol == 0 .and. any(lmech == 3)) call MISTRA_SET_POLICY_t(int(pol(1)), pol(2), pol(3), ierr_pol)
+       if (ierr_pol /= 0) stop 'the policy was refused'
+    end if
     if (twice) then
        nrep = 2
        deallocate (times); allocate (times(2, nrep), steps(14, nl, nrep))
