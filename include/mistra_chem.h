@@ -265,6 +265,49 @@ int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double*
                                               const double* d_hstart, void* hip_stream,
                                               int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl);
 
+/* A SERIES: several output times in one call and one kernel launch, the cell's state, FIX and the rate constants on chip from the first time to the
+ * last.  nleg >= 1 legs over times[0 .. nleg]; leg k is one call of Rosenbrock_x(Y, times[k], times[k+1], AbsTol, RelTol, RPAR,
+ * IPAR, IERR) on the state leg k-1 left, and returns what that call returns into block k of the per-leg outputs:
+ *     var_series [nleg][ncell][NVAR]   ierr [nleg][ncell]   stats [nleg][ncell][8]   t_h [nleg][ncell][3] (host: Texit, Hexit, H)
+ *     d_texit_hexit [nleg][ncell][2] (device).  ierr, stats, t_h (host) and d_texit_hexit (device) may be NULL.
+ * The results are bit for bit those of the nleg calls of mistra_chem_rosenbrock_ex / _device (the cells forms: mistra_chem_rosenbrock_cells_ex /
+ * _device) they replace.  Every per-call quantity starts afresh in every leg: T, Direction, Hmax and the first step from the leg's interval, the reject
+ * flags, the eight counters, IERR, Hexit, the run of singular decompositions, Max_no_steps.  A leg that ends with IERR < 0 (-6, -7, -8) does not end
+ * the series: the next leg starts at its own time times[k+1] from the state as left, as the next call would.
+ * First step: leg 0 as mistra_chem_rosenbrock_device decides it (hstart[c] > 0 goes before rpar[2]); a later leg takes the options' Hstart and no
+ * per-cell value (carry_h = 0: Rosenbrock_x called again), or the previous leg's Hexit of the cell where that is > 0 (carry_h /= 0: what passing the
+ * previous call's Hexit as d_hstart does).
+ * Refusals of Rosenbrock_x stay results: -1 .. -4, and -5 on a shared pair, fill every leg as nleg refused calls would (var = var_in, the code,
+ * zeros) and launch nothing; -5 on per-cell rows is the kernel's, once, and fills every leg of that cell alone.
+ * times: a HOST array, read before the call returns (it travels with the call's options block; calls queued back to back on one stream each run with
+ * their own, MISTRA_ROSENBROCK_CALLS_IN_FLIGHT of them); finite and strictly monotone, ascending or descending (descending: every leg integrates
+ * backward).  A time that is not finite, a repeated time, a change of direction, nleg < 1 or nleg > MISTRA_SERIES_MAX_LEGS, null times or var_series
+ * fail with a text before a device is touched.  MISTRA_SERIES_MAX_LEGS = 4096: the times ride behind the options in the call's block, 32 KiB of it
+ * per call in flight, pinned on the host and resident on the device per mechanism and device slot.
+ * Each cell's inputs are read before any of its outputs is written: var_in may alias the block of one leg of var_series.
+ * The entries ignore the options in force, the integrator policy and step reuse, have no trace form, record no zero-pivot rows
+ * (mistra_chem_singular_rows keeps describing the last call that is not a series) and do not exist for a user slot (both ids fail with the slot's
+ * text).  The _ex forms split the batch over the device slots and fail while a column step of the mechanism is open. */
+#define MISTRA_SERIES_MAX_LEGS 4096
+int mistra_chem_rosenbrock_series_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                     int nleg, const double* times, const double* atol, const double* rtol,
+                                     const double* rpar, const int32_t* ipar, int carry_h, const double* hstart /* [ncell] or NULL */,
+                                     double* var_series, int32_t* ierr, int32_t* stats, double* t_h);
+int mistra_chem_rosenbrock_series_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                         int nleg, const double* times, const double* atol, const double* rtol,
+                                         const double* rpar, const int32_t* ipar,                                                 /* host arrays */
+                                         double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                         int carry_h, const double* d_hstart, void* hip_stream);
+int mistra_chem_rosenbrock_series_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                           int nleg, const double* times, const double* atol, const double* rtol, int ntol,        /* rows per cell */
+                                           const double* rpar, const int32_t* ipar, int carry_h, const double* hstart,
+                                           double* var_series, int32_t* ierr, int32_t* stats, double* t_h);
+int mistra_chem_rosenbrock_series_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                               int nleg, const double* times, const double* d_atol, const double* d_rtol, int ntol,  /* device arrays */
+                                               const double* rpar, const int32_t* ipar,                                            /* host arrays */
+                                               double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                               int carry_h, const double* d_hstart, void* hip_stream);
+
 /* AbsTol from each cell's own state, on the device in stream order: d_atol[c] = max(floor, factor * max_i |d_var[c][i]|), i over NVAR.  NaN entries
  * are ignored; a cell with no positive entry gets floor.  The product is one rounding of two exact operands, so the host restatement
  * max(floor, factor * fmax-reduction of |var|) gives the same bits.  factor or floor that is not finite and positive fails with a text before a device

@@ -129,6 +129,13 @@ def lib():
             L.mistra_chem_rosenbrock_trace_cells_ex.argtypes = L.mistra_chem_rosenbrock_cells_ex.argtypes + [C.c_int, _dp, _ip, _ip, _ip]
             L.mistra_chem_rosenbrock_trace_cells_device.argtypes = L.mistra_chem_rosenbrock_cells_device.argtypes + [C.c_int, vp, vp, vp, vp]
             L.mistra_chem_cell_atol_device.argtypes = [C.c_int, C.c_int, vp, C.c_double, C.c_double, vp, vp]
+        if hasattr(L, "mistra_chem_rosenbrock_series_ex"):
+            L.mistra_chem_rosenbrock_series_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, C.c_int, _dp, _dp, _ip, _ip, _dp]
+            L.mistra_chem_rosenbrock_series_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, _dp, _dp, _dp, _dp, _ip, vp, vp, vp, vp, C.c_int, vp, vp]
+            L.mistra_chem_rosenbrock_series_cells_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _ip, C.c_int, _dp,
+                                                                 _dp, _ip, _ip, _dp]
+            L.mistra_chem_rosenbrock_series_cells_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, _dp, vp, vp, C.c_int, _dp, _ip, vp, vp, vp, vp,
+                                                                     C.c_int, vp, vp]
         if hasattr(L, "mistra_chem_set_policy"):
             L.mistra_chem_set_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
             L.mistra_chem_check_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
@@ -722,6 +729,90 @@ def rosenbrock_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rto
 def rosenbrock_trace_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart=None, cap=256, ctrl=True, trace_d=None, trace_i=None):
     """rosenbrock_trace() with tolerances per cell as rosenbrock_cells takes them; a cell refused with -5 has n = 0 and its log rows untouched."""
     return _ros_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, (cap, ctrl, trace_d, trace_i))
+
+
+# ---- a series: several output times in one call (include/mistra_chem.h: mistra_chem_rosenbrock_series_ex / _device and their cells forms)
+SERIES_MAX_LEGS = 4096      # MISTRA_SERIES_MAX_LEGS
+# var [nleg, ncell, NVAR]; ierr [nleg, ncell]; stats [nleg, ncell, 8]; t_h [nleg, ncell, 3] (host: Texit, Hexit, H) or [nleg, ncell, 2] (device)
+SeriesResult = namedtuple("SeriesResult", "var ierr stats t_h")
+
+
+def rosenbrock_series(mech, var, fix, rconst, times, ipar=None, rpar=None, atol=None, rtol=None, hstart=None, carry_h=False, out=None):
+    """nleg = len(times) - 1 calls of Rosenbrock_x in one launch: leg k integrates from times[k] to times[k+1] on the state leg k-1 left, with the
+    state, FIX and the rate constants on chip throughout -> SeriesResult of per-leg arrays, bit for bit what rosenbrock() / rosenbrock_cells() called
+    leg by leg return.  times: finite, strictly ascending or descending.  A 2-D atol / rtol ([ncell, 1] or [ncell, NVAR]) selects the cells form.
+    numpy arrays: the host entry; torch CUDA tensors: the device entry on torch's current stream.  hstart [ncell]: first step per cell of leg 0,
+    entries <= 0 = rpar[2].  carry_h: a later leg starts with the previous leg's Hexit of the cell where that is > 0, instead of rpar[2].  out
+    (device entry): a [nleg, ncell, NVAR] tensor to receive the states; var may be one leg's block of it.  Options Rosenbrock_x refuses are results
+    in every leg, as for rosenbrock()."""
+    mid, name = _mech_id(mech)
+    nvar, nfix, nreact, _ = DIMS[name]
+    cells = atol is not None and rtol is not None and getattr(atol, "ndim", 0) == 2 and getattr(rtol, "ndim", 0) == 2
+    ip, rp, at1, rt1 = _option_args(name, ipar, rpar, None if cells else atol, None if cells else rtol)
+    tm = np.ascontiguousarray(times, np.float64).reshape(-1)
+    nleg = tm.size - 1
+    tp = tm.ctypes.data_as(_dp)
+    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
+    L = lib()
+    rows = max(nleg, 0)
+    if _is_torch(var):
+        import torch
+        if not var.is_cuda:
+            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
+        init(var.device.index or 0)
+        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
+                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
+        ncell = var.numel() // nvar
+        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
+            raise MistraChemError("cell counts of var / fix / rconst differ")
+        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
+            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
+        if cells:
+            for x in (atol, rtol):
+                if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.shape[0] != ncell or x.device != var.device:
+                    raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
+            if atol.shape != rtol.shape:
+                raise MistraChemError("atol and rtol differ in shape")
+        if out is None:
+            out = torch.empty((rows, ncell, nvar), dtype=torch.float64, device=var.device)
+        elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != rows * ncell * nvar or out.device != var.device:
+            raise MistraChemError("out: a contiguous float64 [nleg, ncell, %d] tensor on the cells' device expected" % nvar)
+        ierr = torch.empty((rows, ncell), dtype=torch.int32, device=var.device)
+        stats = torch.empty((rows, ncell, 8), dtype=torch.int32, device=var.device)
+        th = torch.empty((rows, ncell, 2), dtype=torch.float64, device=var.device)
+        stream = torch.cuda.current_stream(var.device).cuda_stream
+        tail = (out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), int(bool(carry_h)), None if hstart is None else hstart.data_ptr(),
+                C.c_void_p(stream))
+        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), nleg, tp)
+        if cells:
+            _check(L.mistra_chem_rosenbrock_series_cells_device(*head, atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]), *popts, *tail))
+        else:
+            _check(L.mistra_chem_rosenbrock_series_device(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
+        return SeriesResult(out.view(rows, ncell, nvar), ierr, stats, th)
+    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+    ncell = v.shape[0]
+    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
+    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
+    hs = None if hstart is None else np.ascontiguousarray(hstart, np.float64).reshape(-1)
+    if hs is not None and hs.size != ncell:
+        raise MistraChemError("hstart: %d entries expected" % ncell)
+    res = np.empty((rows, ncell, nvar))
+    ierr = np.zeros((rows, ncell), np.int32)
+    stats = np.zeros((rows, ncell, 8), np.int32)
+    th = np.zeros((rows, ncell, 3))
+    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), nleg, tp)
+    tail = (int(bool(carry_h)), None if hs is None else hs.ctypes.data_as(_dp), res.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip),
+            stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp))
+    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
+    if cells:
+        a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
+        if a2.shape[0] != ncell or r2.shape != a2.shape:
+            raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
+        _check(L.mistra_chem_rosenbrock_series_cells_ex(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *popts, *tail))
+    else:
+        _check(L.mistra_chem_rosenbrock_series_ex(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
+    return SeriesResult(res, ierr, stats, th)
 
 
 def cell_atol(mech, var, factor, floor):

@@ -58,6 +58,9 @@ bool traits_match(const MechTables& t, int n_jnz, int tail_regs, bool scale_pass
 // method: IPAR(4) resolved (ros_methods.hpp); anything but Ros3 runs its method kernel, which reads a.opt
 template <class MT, int NT>
 hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bool* configured);
+// method: IPAR(4) resolved, Ros3 included: the series kernel of that method, which reads a.opt and a.times
+template <class MT, int NT>
+hipError_t launch_series(int method, const KernelArgs& a, hipStream_t stream, bool* configured);
 
 // ---- ONE ROW PER MECHANISM: everything the entries below need to know about a compiled kernel.  gas, aer, tot, then the user slots this library was
 // built with (user_mechs.hpp: traits generated from the slots' tables at build time).  A user slot has the product, first-step-dump and options
@@ -74,16 +77,17 @@ struct MechDesc {
   LaunchFn ros3;                                                           // product | phase timing | first-step dump | options (Ros3)
   hipError_t (*method)(int, const KernelArgs&, hipStream_t, bool*);        // Ros2, Ros4, Rodas3, Rodas4 (nullptr: not built)
   LaunchFn trace;                                                          // the step-control trace kernel (nullptr: not built)
+  hipError_t (*series)(int, const KernelArgs&, hipStream_t, bool*);        // the series kernels, all five methods (nullptr: not built)
 };
 template <class MT, int NT>
 constexpr MechDesc builtin_mech(const char* name) {
   return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
-                  MT::MAX_TEMPS, false, &traits_match<MT>, &launch_ros3<MT, NT>, &launch_method<MT, NT>, &launch_ros_trace<MT, NT>};
+                  MT::MAX_TEMPS, false, &traits_match<MT>, &launch_ros3<MT, NT>, &launch_method<MT, NT>, &launch_ros_trace<MT, NT>, &launch_series<MT, NT>};
 }
 template <class MT, int NT>
 constexpr MechDesc user_mech(const char* name) {
   return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
-                  MT::MAX_TEMPS, true, &traits_match<MT>, &launch_ros3<MT, NT>, nullptr, nullptr};
+                  MT::MAX_TEMPS, true, &traits_match<MT>, &launch_ros3<MT, NT>, nullptr, nullptr, nullptr};
 }
 constexpr int kBuiltinMechs = 3, kMaxMechs = 5;
 constexpr int kNumMechs = kBuiltinMechs + MISTRA_USER_MECHS;
@@ -658,6 +662,11 @@ struct MechState {
   // the per-call options of mistra_chem_rosenbrock_ex (host buffers: one block, the call is synchronous) and mistra_chem_rosenbrock_device
   DevBuf<double> call_opt;
   RosCallRing call_ring;
+  // ... and of the series entries: a block is the call's options, then its times (kernel_args.hpp: times).  A ring of its own: every block has room
+  // for MISTRA_SERIES_MAX_LEGS + 1 times, which the single calls' blocks need not carry
+  RosCallRing series_ring;
+  DevBuf<double> s_ser_var, s_ser_th;      // staging of mistra_chem_rosenbrock_series_ex: the legs' blocks of this slot's cells (grow-only)
+  DevBuf<int32_t> s_ser_ierr, s_ser_stats;
   // the step memory of the batched driver (mistra_chem_set_step_reuse): per model layer k = 1..step_n the last accepted step size of the layer's previous
   // column step of this mechanism, 0 = none.  step_n = 0: forgotten — the next column step under reuse sizes it to its n and zeroes it on the drive stream
   DevBuf<double> step_mem;
@@ -688,7 +697,8 @@ struct MechState {
     d_rct.release();
     opt.release(); opt_max_steps = 0;
     pol_opt.release(); pol_method = 0; pol_factor = pol_floor = 0.0;
-    call_opt.release(); call_ring.release();
+    call_opt.release(); call_ring.release(); series_ring.release();
+    s_ser_var.release(); s_ser_th.release(); s_ser_ierr.release(); s_ser_stats.release();
     step_mem.release(); step_n = 0;
     s_hst.release(); s_tol.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
@@ -708,6 +718,7 @@ struct DeviceState {
   bool lds_configured[kMaxMechs] = {};                // hipFuncAttributeMaxDynamicSharedMemorySize is per device
   bool lds_method[kMaxMechs][6] = {};                 // ... and per kernel: the method kernels' [mechanism][IPAR(4)] (launch_ros_method)
   bool lds_trace[kMaxMechs] = {};                     //     and the step-control trace kernels' (launch_ros_trace)
+  bool lds_series[kMaxMechs][6] = {};                 //     and the series kernels' [mechanism][IPAR(4)] (launch_ros_series)
   void release() {
     if (id >= 0) (void)hipSetDevice(id);
     for (auto& m : mech) m.release();
@@ -715,6 +726,8 @@ struct DeviceState {
     for (auto& m : lds_method)
       for (bool& c : m) c = false;
     for (bool& c : lds_trace) c = false;
+    for (auto& m : lds_series)
+      for (bool& c : m) c = false;
     id = -1;
   }
 };
@@ -1107,10 +1120,26 @@ hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bo
   return hipErrorInvalidValue;
 }
 
+template <class MT, int NT>
+hipError_t launch_series(int method, const KernelArgs& a, hipStream_t stream, bool* configured) {
+  switch (method) {
+    case kRos2: return launch_ros_series<MT, NT, kRos2>(a, stream, configured);
+    case kRos3: return launch_ros_series<MT, NT, kRos3>(a, stream, configured);
+    case kRos4: return launch_ros_series<MT, NT, kRos4>(a, stream, configured);
+    case kRodas3: return launch_ros_series<MT, NT, kRodas3>(a, stream, configured);
+    case kRodas4: return launch_ros_series<MT, NT, kRodas4>(a, stream, configured);
+  }
+  return hipErrorInvalidValue;
+}
+
 int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, int method = kRos3) {
   const MechDesc& M = kMech[mech];
   hipError_t e = hipErrorInvalidValue;
-  if (a.ntrace) {      // the step-control trace kernel (Ros3 with options)
+  if (a.times) {      // a series: the series kernel of the method, Ros3 included
+    if (!M.series) return fail_user_slot(mech, "series of Rosenbrock_x calls");
+    if (method < kRos2 || method > kRodas4 || !a.opt || a.dump || a.prof || a.ntrace) return fail("no series kernel for this Rosenbrock method");
+    e = M.series(method, a, stream, &D.lds_series[mech][method]);
+  } else if (a.ntrace) {      // the step-control trace kernel (Ros3 with options)
     if (!M.trace) return fail_user_slot(mech, "step-control trace");
     if (method != kRos3 || !a.opt || a.dump || a.prof) return fail("no trace kernel for this Rosenbrock method");
     e = M.trace(a, stream, &D.lds_trace[mech]);
@@ -1145,6 +1174,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.trace_d = nullptr; a.trace_i = nullptr; a.ntrace = nullptr; a.ctrl = nullptr; a.trace_cap = 0;      // (the trace entries set them)
   a.tol_abs = nullptr; a.tol_rel = nullptr; a.tol_cell_stride = 0; a.tol_spec_stride = 0;      // (the cells entries set them)
   a.tol_cell_factor = 0.0; a.tol_cell_floor = 0.0;      // (policy_args sets them)
+  a.times = nullptr; a.nleg = 0; a.carry_h = 0; a.leg_var = a.leg_ierr = a.leg_stats = a.leg_th = a.leg_h = 0;      // (the series entries set them)
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
@@ -2642,6 +2672,224 @@ int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double*
   tr.cap = cap; tr.trace_d = d_trace_d; tr.trace_i = d_trace_i; tr.ntrace = d_ntrace; tr.ctrl = d_ctrl;
   return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
                               d_hstart, hip_stream, &tr, &ct);
+}
+
+// ---- series: nleg calls of Rosenbrock_x over times[0 .. nleg] in one launch, the state on chip from leg to leg (kernel VARIANT 5).  One path for the
+//      four entries, as above: the shared-pair forms pass ct = nullptr.  The options in force, the integrator policy and step reuse are not read; the
+//      zero-pivot rows are not recorded (mistra_chem_singular_rows keeps describing the last call that is not a series).
+
+// what every series entry checks before anything touches a device, each refusal by its text
+static int check_series(int mech, int nleg, const double* times, const void* var_series) {
+  if (int rc = builtin_only(mech, "series of Rosenbrock_x calls")) return rc;
+  if (nleg < 1 || nleg > MISTRA_SERIES_MAX_LEGS)
+    return fail("series: nleg = " + std::to_string(nleg) + ": a series has 1 .. MISTRA_SERIES_MAX_LEGS = " + std::to_string(MISTRA_SERIES_MAX_LEGS) + " legs");
+  if (!times) return fail("series: null times pointer (times: [nleg + 1], a host array)");
+  if (!var_series) return fail("series: null var_series pointer (var_series: [nleg][ncell][NVAR])");
+  for (int k = 0; k <= nleg; k++)
+    if (!std::isfinite(times[k])) return fail("series: times[" + std::to_string(k) + "] is not finite");
+  for (int k = 1; k <= nleg; k++) {
+    if (times[k] == times[k - 1]) return fail("series: times[" + std::to_string(k) + "] repeats times[" + std::to_string(k - 1) + "]: the times are strictly monotone");
+    if ((times[k] > times[k - 1]) != (times[1] > times[0]))
+      return fail("series: the times change direction at times[" + std::to_string(k) + "]: ascending or descending, one of them for the whole series");
+  }
+  return 0;
+}
+
+// one device slot's share of mistra_chem_rosenbrock_series_ex: cells [start, start + ncell) of the caller's batch of `total` cells
+static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, size_t total, const double* var_in, const double* fix, const double* rconst,
+                          int nleg, const double* times, const RosCall& call, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
+                          int32_t* stats, double* t_h) {
+  HIP_TRY(hipSetDevice(D.id));
+  MechState& S = D.mech[mech];
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nc = (size_t)ncell, nl = (size_t)nleg;
+  const size_t nb = call.block.size();
+  HIP_TRY(S.s_var.reserve(nc * nv));
+  HIP_TRY(S.s_fix.reserve(nc * nf));
+  HIP_TRY(S.s_rct.reserve(nc * nr));
+  HIP_TRY(S.s_ser_var.reserve(nl * nc * nv));
+  HIP_TRY(S.s_ser_ierr.reserve(nl * nc));
+  HIP_TRY(S.s_ser_stats.reserve(nl * nc * 8));
+  if (t_h) HIP_TRY(S.s_ser_th.reserve(nl * nc * 3));
+  HIP_TRY(S.call_opt.reserve(nb + nl + 1));
+  HIP_TRY(hipMemcpy(S.s_var.p, var_in + start * nv, nc * nv * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.s_fix.p, fix + start * nf, nc * nf * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.s_rct.p, rconst + start * nr, nc * nr * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.call_opt.p, call.block.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.call_opt.p + nb, times, (nl + 1) * sizeof(double), hipMemcpyHostToDevice));
+  KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, times[0], times[nleg], S.s_ser_var.p, S.s_ser_ierr.p, S.s_ser_stats.p, t_h ? S.s_ser_th.p : nullptr);
+  if (t_h) a.h_last = S.s_ser_th.p + 2 * nl * nc;      // device: [nleg][ncell][2] (T, Hexit) then [nleg][ncell] (H)
+  a.opt = S.call_opt.p;
+  a.max_steps = call.max_steps;
+  a.times = S.call_opt.p + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
+  a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
+  if (call.cell_atol) {      // this block's tolerance rows
+    const size_t nt = (size_t)call.ntol;
+    HIP_TRY(S.s_tol.reserve(2 * nc * nt));
+    HIP_TRY(hipMemcpy(S.s_tol.p, call.cell_atol + start * nt, nc * nt * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(S.s_tol.p + nc * nt, call.cell_rtol + start * nt, nc * nt * sizeof(double), hipMemcpyHostToDevice));
+    a.tol_abs = S.s_tol.p; a.tol_rel = S.s_tol.p + nc * nt;
+    a.tol_cell_stride = call.ntol;
+    a.tol_spec_stride = call.vector ? 1 : 0;
+  }
+  if (hstart) {
+    HIP_TRY(S.s_hst.reserve(nc));
+    HIP_TRY(hipMemcpy(S.s_hst.p, hstart + start, nc * sizeof(double), hipMemcpyHostToDevice));
+    a.hstart = S.s_hst.p;
+  }
+  if (int rc = launch(D, mech, a, nullptr, call.method)) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  // the slot's [nleg][nc] blocks into the caller's [nleg][total] arrays
+  HIP_TRY(hipMemcpy2D(var_series + start * nv, total * nv * sizeof(double), S.s_ser_var.p, nc * nv * sizeof(double), nc * nv * sizeof(double), nl, hipMemcpyDeviceToHost));
+  if (ierr) HIP_TRY(hipMemcpy2D(ierr + start, total * sizeof(int32_t), S.s_ser_ierr.p, nc * sizeof(int32_t), nc * sizeof(int32_t), nl, hipMemcpyDeviceToHost));
+  if (stats)
+    HIP_TRY(hipMemcpy2D(stats + start * 8, total * 8 * sizeof(int32_t), S.s_ser_stats.p, nc * 8 * sizeof(int32_t), nc * 8 * sizeof(int32_t), nl, hipMemcpyDeviceToHost));
+  if (t_h) {
+    std::vector<double> h(nl * nc * 3);
+    HIP_TRY(hipMemcpy(h.data(), S.s_ser_th.p, nl * nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nl; k++)
+      for (size_t c = 0; c < nc; c++) {
+        double* o = t_h + (k * total + start + c) * 3;
+        o[0] = h[(k * nc + c) * 2]; o[1] = h[(k * nc + c) * 2 + 1]; o[2] = h[2 * nl * nc + k * nc + c];
+      }
+  }
+  return 0;
+}
+
+static int series_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int nleg, const double* times, const double* atol,
+                       const double* rtol, const double* rpar, const int32_t* ipar, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
+                       int32_t* stats, double* t_h, const CellTol* ct) {
+  if (int rc = check_series(mech, nleg, times, var_series)) return rc;
+  if (ct)
+    if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
+  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
+  if (int rc = lazy_init()) return rc;
+  if (int rc = check_call(mech, ncell)) return rc;
+  if (ncell == 0) return 0;
+  if (!var_in || !fix || !rconst) return fail("null host pointer");
+  std::lock_guard<std::mutex> lock(g_mu);
+  if (g_devs[0].mech[mech].pend.active) return step_is_open(mech);
+  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell, nl = (size_t)nleg;
+  if (call.ierr != 1) {      // nleg refused calls: var = var_in, the code, zeros; nothing is launched
+    for (size_t k = 0; k < nl; k++)
+      if (var_series + k * nc * nv != var_in) std::memmove(var_series + k * nc * nv, var_in, nc * nv * sizeof(double));
+    if (ierr) std::fill(ierr, ierr + nl * nc, (int32_t)call.ierr);
+    if (stats) std::fill(stats, stats + nl * nc * 8, 0);
+    if (t_h) std::fill(t_h, t_h + nl * nc * 3, 0.0);
+    return 0;
+  }
+  // var_in may alias one leg's block of var_series: every slot has its inputs on the device before any result comes back (below: all uploads of a
+  // slot precede its downloads, and slots own disjoint cells)
+  const int ndev = (int)g_devs.size();
+  if (ndev == 1 || ncell < 2 * ndev) {
+    const int rc = series_host_on(g_devs[0], mech, ncell, 0, nc, var_in, fix, rconst, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h);
+    (void)hipSetDevice(g_devs[0].id);
+    return rc;
+  }
+  std::vector<int> rcs((size_t)ndev, 0);
+  std::vector<std::string> errs((size_t)ndev);
+  std::vector<std::thread> workers;
+  for (int d = 0; d < ndev; d++) {
+    const int per = ncell / ndev, rem = ncell % ndev;
+    const size_t start = (size_t)d * per + (size_t)std::min(d, rem);
+    const int count = per + (d < rem ? 1 : 0);
+    workers.emplace_back([=, &rcs, &errs, &call]() {
+      rcs[(size_t)d] = series_host_on(g_devs[(size_t)d], mech, count, start, nc, var_in, fix, rconst, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h);
+      if (rcs[(size_t)d]) errs[(size_t)d] = g_err;
+    });
+  }
+  for (auto& w : workers) w.join();
+  (void)hipSetDevice(g_devs[0].id);
+  for (int d = 0; d < ndev; d++)
+    if (rcs[(size_t)d]) return fail("device " + std::to_string(g_devs[(size_t)d].id) + ": " + errs[(size_t)d]);
+  return 0;
+}
+
+static int series_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int nleg, const double* times,
+                            const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_series, int32_t* d_ierr,
+                            int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart, void* hip_stream, const CellTol* ct) {
+  if (int rc = check_series(mech, nleg, times, d_var_series)) return rc;
+  if (ct)
+    if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
+  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
+  if (ncell == 0) return check_call(mech, 0);
+  if (!d_var_in || !d_fix || !d_rconst || !d_ierr || !d_stats) return fail("null device pointer");
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (ct) {      // the kernel reads these itself: memory the device cannot reach is refused here, not met there
+    for (const double* p : {ct->atol, ct->rtol}) {
+      hipPointerAttribute_t attr;
+      if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type == hipMemoryTypeUnregistered || (attr.type == hipMemoryTypeDevice && attr.device != t.D->id))
+        return fail("d_atol / d_rtol are not device arrays on the cells' device");
+    }
+  }
+  std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of series blocks)
+  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell, nl = (size_t)nleg;
+  if (call.ierr != 1) {      // nleg refused calls as results, in stream order; no kernel of the library runs
+    for (size_t k = 0; k < nl; k++)
+      if (d_var_series + k * nc * nv != d_var_in) HIP_TRY(hipMemcpyAsync(d_var_series + k * nc * nv, d_var_in, nc * nv * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_ierr), call.ierr, nl * nc, st));
+    HIP_TRY(hipMemsetAsync(d_stats, 0, nl * nc * 8 * sizeof(int32_t), st));
+    if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nl * nc * 2 * sizeof(double), st));
+    return 0;
+  }
+  const size_t nb = call.block.size();
+  RosCallRing& R = t.S->series_ring;
+  HIP_TRY(R.ensure(nb + (size_t)MISTRA_SERIES_MAX_LEGS + 1));
+  const int i = R.next;
+  R.next = (i + 1) % kRosCallsInFlight;
+  if (R.pending[i]) HIP_TRY(hipEventSynchronize(R.ev[i]));      // the kernel that read this block kRosCallsInFlight series ago
+  R.pending[i] = false;
+  double *hb = R.host + (size_t)i * R.words, *db = R.dev + (size_t)i * R.words;
+  std::memcpy(hb, call.block.data(), nb * sizeof(double));
+  std::memcpy(hb + nb, times, (nl + 1) * sizeof(double));      // read here: the caller's array is free when the call returns
+  HIP_TRY(hipMemcpyAsync(db, hb, (nb + nl + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+  KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, times[0], times[nleg], d_var_series, d_ierr, d_stats, d_texit_hexit);
+  a.hstart = d_hstart;
+  a.opt = db;
+  a.max_steps = call.max_steps;
+  a.times = db + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
+  a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
+  if (ct) {      // the caller's device arrays, read by the kernel in stream order: no copy
+    a.tol_abs = ct->atol; a.tol_rel = ct->rtol;
+    a.tol_cell_stride = ct->ntol;
+    a.tol_spec_stride = call.vector ? 1 : 0;
+  }
+  const int rc = launch(*t.D, mech, a, st, call.method);
+  if (hipEventRecord(R.ev[i], st) == hipSuccess) R.pending[i] = true;      // (also behind a failed launch: the copy is queued)
+  return rc;
+}
+
+int mistra_chem_rosenbrock_series_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int nleg, const double* times,
+                                     const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int carry_h, const double* hstart,
+                                     double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
+  return series_host(mech, ncell, var_in, fix, rconst, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h, nullptr);
+}
+
+int mistra_chem_rosenbrock_series_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int nleg, const double* times,
+                                           const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar, int carry_h,
+                                           const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
+  const CellTol ct{atol, rtol, ntol};
+  return series_host(mech, ncell, var_in, fix, rconst, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h, &ct);
+}
+
+int mistra_chem_rosenbrock_series_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int nleg,
+                                         const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
+                                         double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h,
+                                         const double* d_hstart, void* hip_stream) {
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats, d_texit_hexit, carry_h,
+                          d_hstart, hip_stream, nullptr);
+}
+
+int mistra_chem_rosenbrock_series_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int nleg,
+                                               const double* times, const double* d_atol, const double* d_rtol, int ntol, const double* rpar,
+                                               const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                               int carry_h, const double* d_hstart, void* hip_stream) {
+  const CellTol ct{d_atol, d_rtol, ntol};
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr, d_stats, d_texit_hexit,
+                          carry_h, d_hstart, hip_stream, &ct);
 }
 
 int mistra_chem_cell_atol_device(int mech, int ncell, const double* d_var, double factor, double floor, double* d_atol, void* hip_stream) {

@@ -103,6 +103,14 @@ struct KernelArgs {
   // 0 = off: the block's AbsTol.  The host has validated both (capi.cpp: check_policy); the entries whose options travel with the call pass 0.
   double tol_cell_factor;
   double tol_cell_floor;
+  // a series (kernel VARIANT 5, ros_series_kernel.hip; mistra_chem_rosenbrock_series_ex / _device and their cells forms): nleg legs over times[0 .. nleg],
+  // leg k one call of Rosenbrock_x from times[k] to times[k+1] on the state leg k-1 left.  Read by the series kernels only, which do not read tin / tout;
+  // null / 0 everywhere else (capi.cpp: make_args).  Leg k writes var_out + k*leg_var, ierr + k*leg_ierr, stats + k*leg_stats, texit_hexit + k*leg_th and
+  // h_last + k*leg_h (strides in elements; the kernel forms the 64-bit offsets where it uses them).
+  const double* times;         // [nleg + 1]: the device copy, behind the call's options block; nothing writes it while the kernel runs (scalar loads)
+  int32_t nleg;
+  int32_t carry_h;             // /= 0: a later leg's first step is the previous leg's Hexit of the cell where that is > 0, else the options' Hstart
+  int64_t leg_var, leg_ierr, leg_stats, leg_th, leg_h;
 };
 
 }  // namespace mistra

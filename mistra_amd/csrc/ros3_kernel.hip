@@ -1188,12 +1188,15 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // parity tests (tests/test_gpu_parity.py); the integration itself is untouched.  3 = Rosenbrock_x's options (gas.f:936-1053) out of
 // a.opt instead of the values INTEGRATE_x fixes (kernel_args.hpp: RosOptSlot; capi.cpp: mistra_chem_set_options): every difference
 // from variant 0 sits behind `if constexpr (OPT)`, the other three compile from the statements they always had.
+// 5 = a series (ros_series_kernel.hip; mistra_chem_rosenbrock_series_ex / _device): variant 3 with the part from the step-control set-up to the
+// results inside a loop over a.nleg legs, leg k one call of Rosenbrock_x from a.times[k] to a.times[k+1] on the state leg k-1 left, its results in
+// block k of the output arrays.  Everything the loop adds sits behind `if constexpr (SERIES)`; for the others the loop is one pass.
 // METHOD (variant 3 only): the Rosenbrock method, IPAR(4) of Rosenbrock_x (ros_methods.hpp).  Ros3 is the kernel as it was; Ros2, Ros4, Rodas3
 // and Rodas4 (the method kernels, instantiated by ros_method_kernel.hip in translation units of their own) differ in the stage loop, in the
 // number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
 template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
-  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, OPT = VARIANT == 3 || TRACE;
+  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, OPT = VARIANT == 3 || TRACE || SERIES;
   static_assert(!TRACE || METHOD == kRos3, "the step-control trace is a Ros3 instantiation (ros_trace_kernel.hip)");
   static_assert(METHOD == kRos3 || (OPT && METHOD >= kRos2 && METHOD <= kRodas4), "the method kernels are options instantiations");
   constexpr double kGamma1 = METHOD == kRos3 ? kRosGamma1 : kRosMethod<METHOD>.Gamma[0];
@@ -1216,6 +1219,11 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   const int cell = blockIdx.x;
   if (cell >= a.ncell) return;
   if (lds_addr(lds) != 0u) {      // the VM and the tail chain address M by absolute LDS offsets
+    if constexpr (SERIES) {      // every leg's
+      if (t == 0)
+        for (int k = 0; k < a.nleg; k++) GM_(a.ierr)[(int64_t)k * a.leg_ierr + cell] = -99;
+      return;
+    }
     if (t == 0) GM_(a.ierr)[cell] = -99;
     if constexpr (TRACE) {
       if (t == 0) GM_(a.ntrace)[cell] = 0;
@@ -1307,6 +1315,29 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         refused = false;
 #pragma unroll
         for (int w = 0; w < NW; w++) refused = refused || red[w] != 0.0;
+      }
+      if constexpr (SERIES) {      // once, in front of the first leg: every leg of the cell leaves as the refused call does
+        if (refused) {
+          for (int k = 0; k < a.nleg; k++) {
+#pragma unroll
+            for (int q = 0; q < SPT; q++) {
+              const int s = q * NT + t;
+              if (s < NVAR) GM_(a.var_out)[(int64_t)k * a.leg_var + (int64_t)cell * NVAR + s] = y[q];
+            }
+            if (t == 0) {
+              GM_(a.ierr)[(int64_t)k * a.leg_ierr + cell] = -5;
+              gptr_mut<int32_t> st = GM_(a.stats) + ((int64_t)k * a.leg_stats + (int64_t)cell * 8);
+#pragma unroll
+              for (int j = 0; j < 8; j++) st[j] = 0;
+              if (a.texit_hexit) {
+                GM_(a.texit_hexit)[(int64_t)k * a.leg_th + (int64_t)cell * 2] = 0.0;
+                GM_(a.texit_hexit)[(int64_t)k * a.leg_th + (int64_t)cell * 2 + 1] = 0.0;
+              }
+              if (a.h_last) GM_(a.h_last)[(int64_t)k * a.leg_h + cell] = 0.0;
+            }
+          }
+          return;
+        }
       }
       if (refused) {
 #pragma unroll
@@ -1745,8 +1776,10 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   };
 
   // ---- RosenbrockIntegrator_x (gas.f:1180-1336); option values are the ones INTEGRATE_x/Rosenbrock_x fix
-  const double Tstart = a.tin, Tend = a.tout;
-  const double Roundoff = 2.220446049250313e-16, Hmin = 0.0, Hmax = wave_uniform(fabs(Tend - Tstart));
+  // VARIANT 5: Tstart, Tend and what follows from them (Hmax, Direction) are the leg's, set at the head of each leg (below)
+  double Tstart = a.tin, Tend = a.tout;
+  const double Roundoff = 2.220446049250313e-16, Hmin = 0.0;
+  double Hmax = wave_uniform(fabs(Tend - Tstart));
   const double FacMin = 0.2, FacMax = 6.0, FacRej = 0.1, FacSafe = 0.9;
   // VARIANT 3: the same seven out of the options block, fetched where they are used
   auto hmin = [&]() -> double { if constexpr (OPT) return opt(kOptHmin); else return Hmin; };
@@ -1755,14 +1788,13 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   auto facmax = [&]() -> double { if constexpr (OPT) return opt(kOptFacMax); else return FacMax; };
   auto facrej = [&]() -> double { if constexpr (OPT) return opt(kOptFacRej); else return scalar_const(FacRej); };
   auto facsafe = [&]() -> double { if constexpr (OPT) return opt(kOptFacSafe); else return FacSafe; };
-  const double Direction = (Tend >= Tstart) ? 1.0 : -1.0;
-  double T = Tstart;
+  double Direction = (Tend >= Tstart) ? 1.0 : -1.0;
   // Hstart: INTEGRATE_x fixes RPAR(3) = 1e-3 (gas.f:743).  Opt-in departure from the reference: a caller that keeps
   // each cell's last step size from one chemistry timestep to the next passes it in a.hstart; <= 0 means the reference's value.
   // VARIANT 3: RPAR(3) as resolved by the host (gas.f:996-999) in its place; a per-cell a.hstart > 0 still goes first.
   double hstart_call = 1.0e-3;
   if constexpr (OPT) hstart_call = opt(kOptHstart);
-  const double hstart0 = (a.hstart && G_(a.hstart)[cell] > 0.0) ? G_(a.hstart)[cell] : hstart_call;
+  double hstart0 = (a.hstart && G_(a.hstart)[cell] > 0.0) ? G_(a.hstart)[cell] : hstart_call;
   // The step size H lives across the whole step loop, and the compiler carried a vector-register copy of it (and of Hexit) around
   // the loop through scratch: 8-16 bytes per lane and step, stored through to HBM — most of aer's memory traffic in rounds 2 and 3.
   // So it lives in LDS: one cell per wave behind the error norm's partial sums, written by the wave's lane 0 and read back by the
@@ -1779,331 +1811,373 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     if (lane == 0) *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_H + wv)) = v;
   };
   static_assert(NW <= L::RED_H && L::RED_H + NW <= L::RED_HEXIT, "red[]: partial sums | H per wave | Hexit");
-  if (t == 0) *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT)) = 0.0;
-  {
-    double H0 = fmin_f(fmin_f(hstart0, fabs(Tend - Tstart)), hmax());
-    if (fabs(H0) <= 10.0 * Roundoff) H0 = 1.0e-5;
-    Hset(H0);
-  }
-  bool RejectLastH = false, RejectMoreH = false;
-  int nfun = 0, njac = 0, nstp = 0, nacc = 0, nrej = 0, ndec = 0, nsol = 0, nsng = 0;
-  int ierr = 1;
-
-  double ynew[SPT], fcn0[SPT], fcn[SPT], k1[SPT], k2[SPT], k3[SPT], yerr[SPT];
-  [[maybe_unused]] double k4[SPT], k5[SPT], k6[SPT];      // the method kernels' further stage vectors (Ros4, Rodas3: k4; Rodas4: k4..k6)
-  // stage vector J (0-based) by its compile-time number: named register arrays, never an array indexed at run time (that one would live in scratch)
-  [[maybe_unused]] auto stage_k = [&](auto J) -> double (&)[SPT] {
-    constexpr int j = decltype(J)::value;
-    static_assert(j >= 0 && j < 6, "stage vector");
-    if constexpr (j == 0) return k1;
-    else if constexpr (j == 1) return k2;
-    else if constexpr (j == 2) return k3;
-    else if constexpr (j == 3) return k4;
-    else if constexpr (j == 4) return k5;
-    else return k6;
-  };
-
-  while (fabs(Tend - T) >= Roundoff) {
-    if (nstp > a.max_steps) { ierr = -6; break; }      // Max_no_steps: 100000 (gas.f:1042, 1199)
-    {
-      const double H = Hget();
-      if (((T + scalar_const(0.1) * H) == T) || (H <= Roundoff)) { ierr = -7; break; }
-      if (t == 0) *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT)) = H;
-      Hset(fmin_f(H, fabs(Tend - T)));
-    }
-
-    lap(6);
-    if constexpr (!RESIDENT) {      // (Jac_SP below defines every entry.  Said here with an empty statement that "writes" them, so that no value — not even an
-#pragma unroll                     //  undefined one — is carried around the step loop: the 128-register kernels carried one through scratch)
-      for (int q = 0; q < JPT; q++) asm volatile("" : "=v"(jac0[q]));
-    }
-    if constexpr (L::MERGE_FUN_JAC) {
-      fun_jac(y, fcn0);
-      dump_vec(0, fcn0);
-    } else {
-      fun(y, fcn0);
-      dump_vec(0, fcn0);
-      lap(0);
-      jac();
-    }
-    // ros_FunTimeDerivative_x (gas.f:1375): Fun_x does not depend on T and RCONST is frozen, so
-    // dFdT = (1/Delta)*(Fun - Fcn0) is an exact +0.0; the evaluation is skipped, its count and its "+ HG*0.0" are kept.
-    if constexpr (OPT) nfun += autonomous ? 1 : 2;      // Autonomous: no ros_FunTimeDerivative_x, no Fun call of its own (gas.f:1221)
-    else nfun += 2;
-    njac += 1;
-    lap(1);
-
-    bool accepted = false;
-    while (!accepted) {
-      if constexpr (TRACE) tr_halved = 0;
-      {
-        // K1's right-hand side, Fcn0 + HG*dFdT with dFdT = +0.0 (see above); independent of H
-#pragma unroll
-        for (int q = 0; q < SPT; q++) {
-          if constexpr (METHOD != kRos3) k1[q] = autonomous ? fcn0[q] : fcn0[q] + Direction * 0.0;      // (Direction*H*Gamma(1))*dFdT: a zero of Direction's sign (Gamma(1) > 0 in all five)
-          else if constexpr (OPT) k1[q] = autonomous ? fcn0[q] : fcn0[q] + 0.0;      // Autonomous: the HG*dFdT terms are not added at all (gas.f:1268)
-          else k1[q] = fcn0[q] + 0.0;
+  // ---- the legs (VARIANT 5; one pass for every other variant).  The leg's bookkeeping is wave-uniform and stays in scalar registers: the leg index, the
+  //      leg's two times (scalar loads out of the call's options block, which nothing writes while the kernel runs) and the offsets of its output blocks,
+  //      formed where they are used.  Every per-call quantity of Rosenbrock_x starts afresh below.  Nothing is carried around the loop in a vector
+  //      register: with a.carry_h the leg's first step is read from the Hexit cell, in LDS, before thread 0 resets it.
+  [[maybe_unused]] int leg = 0;
+  do {
+    if constexpr (SERIES) {
+      const auto times = (const double __attribute__((address_space(4)))*)a.times;
+      Tstart = times[leg];
+      Tend = times[leg + 1];
+      Hmax = wave_uniform(fabs(Tend - Tstart));
+      Direction = (Tend >= Tstart) ? 1.0 : -1.0;
+      if (leg > 0) {      // Rosenbrock_x called again: the options' Hstart and no per-cell value; a.carry_h: the previous leg's Hexit where it is > 0
+        hstart0 = opt(kOptHstart);
+        if (a.carry_h) {
+          lds_barrier();      // thread 0's last store to the cell (a leg that made no step leaves only its reset, with no barrier behind it)
+          const double hx =wave_uniform(*(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT)));
+          if (hx > 0.0) hstart0 = hx;
+          lds_barrier();      // every wave has read the cell before thread 0 resets it
         }
-        int nconsecutive = 0;
-        bool singular = true;
-        while (singular) {
-          const double ghinv = wave_uniform(1.0 / (Direction * Hget() * kGamma1));
-          singular = prepare(ghinv, k1);
-          dump_matrix(NVAR);      // Ghimj = 1/(H*gamma) - Jac0
-          ndec += 1;
-          lap(2);
-          if (singular) {
-            // which row: KppDecomp_x returns the FIRST row whose diagonal is exactly zero as it reaches it (IER = k, gas.f:6157 — rows are
-            // untouched until their own turn, so the test sees the prepared value); ros_PrepareMatrix_x prints it (gas.f:1456).  Rare
-            // path: Ghimj is still as prepared (no LU ran), every species' thread looks at its diagonal slot.
-            if (a.sing_rows && nsng < 8) {
-#pragma unroll
-              for (int q = 0; q < SPT; q++) {      // every species' thread looks at its diagonal slot(s)
-                const int sp = q * NT + t;
-                const uint32_t dp = sp < NVAR ? (uint32_t)G_(a.diag_pos)[sp] : (uint32_t)kPosNone;
-                if (dp != kPosNone && M[dp] == 0.0) atomicMin(&flags[1], sp + 1);
-              }
-              lds_barrier();
-              if (t == 0) GM_(a.sing_rows)[(size_t)cell * 8 + nsng] = flags[1];
-            }
-            lds_barrier();   // everyone has read flags[0] (and flags[1]) before the retry clears them
-            nsng += 1;
-            nconsecutive += 1;
-            if constexpr (TRACE) tr_halved += 1;
-            if (nconsecutive <= 5) Hset(Hget() * 0.5);
-            else { ierr = -8; break; }
-          } else {
-            vm_run<NT, 4>(a.lu, hdr.lu_row0, lane);
-            if constexpr (MT::SCALE_PASS) {      // else the scaling is the LU program's last round
-              lap(3);
-              scale_run<NT, MT::RING_LOW>(a.lu_scale, wave, lane);      // L(k,j) *= R(j); tail block: U(i,c) *= R(i)
-              lds_barrier();
-              lap(11);
-            }
-            if constexpr (MT::DENSE_ND > 0) {
-              static_assert(MT::SCALE_PASS, "the Schur steps read what the scaling pass leaves");
-              lap(3);
-              const f64x4 tile = dense_lu<MT, NT>(lane);      // tile (3,3) of the block with pivots 0 .. 47 applied, in wave 7
-              if (wave == 7) dense_finish<MT, NT>(tile, lane);
-              lds_barrier();
-              lap(12);
-            }
-            lap(3);
-            if constexpr (DUMP) {
-              if (MT::DENSE_ND == 0) lds_barrier();      // (the dense tail's caller has just passed one)
-              dump_matrix(NVAR + NNZ);      // the factors as the kernel keeps them; R(k) = 1/U(k,k) behind them
-              if (dumping)
-                for (int i = t; i < NVAR; i += NT) dump[NVAR + 2 * NNZ + i] = M[NNZ + NVAR + 4 + i];
-            }
-          }
-        }
-        if (ierr == -8) break;
       }
-      const double dh = wave_uniform(Direction * Hget());
-      // stage 1: its right-hand side went through the LU program above, only the backward half of the solve is left
+    }
+    double T = Tstart;
+    if (t == 0) *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT)) = 0.0;
+    {
+      double H0 = fmin_f(fmin_f(hstart0, fabs(Tend - Tstart)), hmax());
+      if (fabs(H0) <= 10.0 * Roundoff) H0 = 1.0e-5;
+      Hset(H0);
+    }
+    bool RejectLastH = false, RejectMoreH = false;
+    int nfun = 0, njac = 0, nstp = 0, nacc = 0, nrej = 0, ndec = 0, nsol = 0, nsng = 0;
+    int ierr = 1;
+
+    double ynew[SPT], fcn0[SPT], fcn[SPT], k1[SPT], k2[SPT], k3[SPT], yerr[SPT];
+    [[maybe_unused]] double k4[SPT], k5[SPT], k6[SPT];      // the method kernels' further stage vectors (Ros4, Rodas3: k4; Rodas4: k4..k6)
+    // stage vector J (0-based) by its compile-time number: named register arrays, never an array indexed at run time (that one would live in scratch)
+    [[maybe_unused]] auto stage_k = [&](auto J) -> double (&)[SPT] {
+      constexpr int j = decltype(J)::value;
+      static_assert(j >= 0 && j < 6, "stage vector");
+      if constexpr (j == 0) return k1;
+      else if constexpr (j == 1) return k2;
+      else if constexpr (j == 2) return k3;
+      else if constexpr (j == 3) return k4;
+      else if constexpr (j == 4) return k5;
+      else return k6;
+    };
+
+    while (fabs(Tend - T) >= Roundoff) {
+      if (nstp > a.max_steps) { ierr = -6; break; }      // Max_no_steps: 100000 (gas.f:1042, 1199)
+      {
+        const double H = Hget();
+        if (((T + scalar_const(0.1) * H) == T) || (H <= Roundoff)) { ierr = -7; break; }
+        if (t == 0) *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT)) = H;
+        Hset(fmin_f(H, fabs(Tend - T)));
+      }
+
       lap(6);
-      solve(k1, true);
-      dump_vec(2 * NVAR + 2 * NNZ, k1);
-      lap(4);
-      if constexpr (METHOD == kRos3) {
-        // stage 2: new function value at Y + A21*K1
-#pragma unroll
-        for (int q = 0; q < SPT; q++) ynew[q] = y[q] + kRosA1 * k1[q];
-        lap(6);
-        fun(ynew, fcn);
-        lap(0);
-        nfun += 1;
-        {
-          const double hc = wave_uniform(kRosC1 / dh);
-#pragma unroll
-          for (int q = 0; q < SPT; q++) {
-            if constexpr (OPT) k2[q] = autonomous ? fcn[q] + hc * k1[q] : (fcn[q] + hc * k1[q]) + dh * 0.0;
-            else k2[q] = (fcn[q] + hc * k1[q]) + dh * 0.0;      // + HG*dFdT with dFdT = +0.0: (dh*gamma2)*0.0, a zero of dh's sign (gamma2 > 0)
-          }
-        }
-        lap(6);
-        solve(k2, false);
-        dump_vec(3 * NVAR + 2 * NNZ, k2);
-        lap(4);
-        // stage 3 reuses the stage-2 function value
-        {
-          const double hc1 = wave_uniform(kRosC2 / dh), hc2 = wave_uniform(kRosC3 / dh);
-#pragma unroll
-          for (int q = 0; q < SPT; q++) {
-            if constexpr (OPT) k3[q] = autonomous ? (fcn[q] + hc1 * k1[q]) + hc2 * k2[q] : ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;
-            else k3[q] = ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;      // (dh*gamma3)*0.0 likewise (gamma3 > 0)
-          }
-        }
-        lap(6);
-        solve(k3, false);
-        dump_vec(4 * NVAR + 2 * NNZ, k3);
-        lap(4);
-        nsol += 3;
-#pragma unroll
-        for (int q = 0; q < SPT; q++) {
-          ynew[q] = ((y[q] + kRosM1 * k1[q]) + kRosM2 * k2[q]) + kRosM3 * k3[q];
-          yerr[q] = ((0.0 + kRosE1 * k1[q]) + kRosE2 * k2[q]) + kRosE3 * k3[q];
-        }
+      if constexpr (!RESIDENT) {      // (Jac_SP below defines every entry.  Said here with an empty statement that "writes" them, so that no value — not even an
+#pragma unroll                     //  undefined one — is carried around the step loop: the 128-register kernels carried one through scratch)
+        for (int q = 0; q < JPT; q++) asm volatile("" : "=v"(jac0[q]));
+      }
+      if constexpr (L::MERGE_FUN_JAC) {
+        fun_jac(y, fcn0);
+        dump_vec(0, fcn0);
       } else {
-        // ---- the method kernels: stages 2 .. ros_S (gas.f:1241-1276), unrolled at compile time, in the reference's order of operations.
-        //      WAXPY_x returns at once for a zero coefficient (gas.f:6641): such a term is dropped, not multiplied out.
-        auto for_stages = [&](auto&& f, auto FROM, auto TO) {      // f(integral_constant<int, FROM>) ... f(integral_constant<int, TO - 1>)
-          auto go = [&](auto&& self, auto I) {
-            if constexpr (decltype(I)::value < decltype(TO)::value) {
-              f(I);
-              self(self, std::integral_constant<int, decltype(I)::value + 1>{});
-            }
-          };
-          go(go, FROM);
-        };
-        for_stages([&](auto I) {
-          constexpr int i = decltype(I)::value;      // stage i + 1
-          constexpr int row = i * (i - 1) / 2;       // A(i+1, j+1) = ros_A[row + j]
-          if constexpr (kRosMethod<METHOD>.NewF[i]) {
+        fun(y, fcn0);
+        dump_vec(0, fcn0);
+        lap(0);
+        jac();
+      }
+      // ros_FunTimeDerivative_x (gas.f:1375): Fun_x does not depend on T and RCONST is frozen, so
+      // dFdT = (1/Delta)*(Fun - Fcn0) is an exact +0.0; the evaluation is skipped, its count and its "+ HG*0.0" are kept.
+      if constexpr (OPT) nfun += autonomous ? 1 : 2;      // Autonomous: no ros_FunTimeDerivative_x, no Fun call of its own (gas.f:1221)
+      else nfun += 2;
+      njac += 1;
+      lap(1);
+
+      bool accepted = false;
+      while (!accepted) {
+        if constexpr (TRACE) tr_halved = 0;
+        {
+          // K1's right-hand side, Fcn0 + HG*dFdT with dFdT = +0.0 (see above); independent of H
 #pragma unroll
-            for (int q = 0; q < SPT; q++) ynew[q] = y[q];
-            for_stages([&](auto J) {
-              constexpr double aij = kRosMethod<METHOD>.A[row + decltype(J)::value];
-              if constexpr (aij != 0.0) {
-                const double (&kj)[SPT] = stage_k(J);
-#pragma unroll
-                for (int q = 0; q < SPT; q++) ynew[q] = ynew[q] + aij * kj[q];
-              }
-            }, std::integral_constant<int, 0>{}, I);
-            lap(6);
-            fun(ynew, fcn);
-            lap(0);
-            nfun += 1;
+          for (int q = 0; q < SPT; q++) {
+            if constexpr (METHOD != kRos3) k1[q] = autonomous ? fcn0[q] : fcn0[q] + Direction * 0.0;      // (Direction*H*Gamma(1))*dFdT: a zero of Direction's sign (Gamma(1) > 0 in all five)
+            else if constexpr (OPT) k1[q] = autonomous ? fcn0[q] : fcn0[q] + 0.0;      // Autonomous: the HG*dFdT terms are not added at all (gas.f:1268)
+            else k1[q] = fcn0[q] + 0.0;
           }
-          // Fcn: the last function value formed, Fcn0 while no stage of this step has formed one (Rodas3's stage 2)
-          constexpr bool fresh = ros_fresh_fcn(METHOD, i);
-          double (&ki)[SPT] = stage_k(I);
+          int nconsecutive = 0;
+          bool singular = true;
+          while (singular) {
+            const double ghinv = wave_uniform(1.0 / (Direction * Hget() * kGamma1));
+            singular = prepare(ghinv, k1);
+            dump_matrix(NVAR);      // Ghimj = 1/(H*gamma) - Jac0
+            ndec += 1;
+            lap(2);
+            if (singular) {
+              // which row: KppDecomp_x returns the FIRST row whose diagonal is exactly zero as it reaches it (IER = k, gas.f:6157 — rows are
+              // untouched until their own turn, so the test sees the prepared value); ros_PrepareMatrix_x prints it (gas.f:1456).  Rare
+              // path: Ghimj is still as prepared (no LU ran), every species' thread looks at its diagonal slot.
+              if (a.sing_rows && nsng < 8) {
 #pragma unroll
-          for (int q = 0; q < SPT; q++) ki[q] = fresh ? fcn[q] : fcn0[q];
-          for_stages([&](auto J) {
-            constexpr double cij = kRosMethod<METHOD>.C[row + decltype(J)::value];
-            if constexpr (cij != 0.0) {
-              const double hc = wave_uniform(cij / dh);
-              const double (&kj)[SPT] = stage_k(J);
-#pragma unroll
-              for (int q = 0; q < SPT; q++) ki[q] = ki[q] + hc * kj[q];
+                for (int q = 0; q < SPT; q++) {      // every species' thread looks at its diagonal slot(s)
+                  const int sp = q * NT + t;
+                  const uint32_t dp = sp < NVAR ? (uint32_t)G_(a.diag_pos)[sp] : (uint32_t)kPosNone;
+                  if (dp != kPosNone && M[dp] == 0.0) atomicMin(&flags[1], sp + 1);
+                }
+                lds_barrier();
+                if (t == 0) GM_(a.sing_rows)[(size_t)cell * 8 + nsng] = flags[1];
+              }
+              lds_barrier();   // everyone has read flags[0] (and flags[1]) before the retry clears them
+              nsng += 1;
+              nconsecutive += 1;
+              if constexpr (TRACE) tr_halved += 1;
+              if (nconsecutive <= 5) Hset(Hget() * 0.5);
+              else { ierr = -8; break; }
+            } else {
+              vm_run<NT, 4>(a.lu, hdr.lu_row0, lane);
+              if constexpr (MT::SCALE_PASS) {      // else the scaling is the LU program's last round
+                lap(3);
+                scale_run<NT, MT::RING_LOW>(a.lu_scale, wave, lane);      // L(k,j) *= R(j); tail block: U(i,c) *= R(i)
+                lds_barrier();
+                lap(11);
+              }
+              if constexpr (MT::DENSE_ND > 0) {
+                static_assert(MT::SCALE_PASS, "the Schur steps read what the scaling pass leaves");
+                lap(3);
+                const f64x4 tile = dense_lu<MT, NT>(lane);      // tile (3,3) of the block with pivots 0 .. 47 applied, in wave 7
+                if (wave == 7) dense_finish<MT, NT>(tile, lane);
+                lds_barrier();
+                lap(12);
+              }
+              lap(3);
+              if constexpr (DUMP) {
+                if (MT::DENSE_ND == 0) lds_barrier();      // (the dense tail's caller has just passed one)
+                dump_matrix(NVAR + NNZ);      // the factors as the kernel keeps them; R(k) = 1/U(k,k) behind them
+                if (dumping)
+                  for (int i = t; i < NVAR; i += NT) dump[NVAR + 2 * NNZ + i] = M[NNZ + NVAR + 4 + i];
+              }
             }
-          }, std::integral_constant<int, 0>{}, I);
-          constexpr double gi = kRosMethod<METHOD>.Gamma[i];
-          if constexpr (gi != 0.0) {      // + HG*dFdT with dFdT = +0.0: a zero with the sign of Direction*H*Gamma(i); nothing where Gamma(i) = 0 or autonomous (gas.f:1268)
-            const double hg0 = wave_uniform((dh * gi) * 0.0);
+          }
+          if (ierr == -8) break;
+        }
+        const double dh = wave_uniform(Direction * Hget());
+        // stage 1: its right-hand side went through the LU program above, only the backward half of the solve is left
+        lap(6);
+        solve(k1, true);
+        dump_vec(2 * NVAR + 2 * NNZ, k1);
+        lap(4);
+        if constexpr (METHOD == kRos3) {
+          // stage 2: new function value at Y + A21*K1
 #pragma unroll
-            for (int q = 0; q < SPT; q++) ki[q] = autonomous ? ki[q] : ki[q] + hg0;
+          for (int q = 0; q < SPT; q++) ynew[q] = y[q] + kRosA1 * k1[q];
+          lap(6);
+          fun(ynew, fcn);
+          lap(0);
+          nfun += 1;
+          {
+            const double hc = wave_uniform(kRosC1 / dh);
+#pragma unroll
+            for (int q = 0; q < SPT; q++) {
+              if constexpr (OPT) k2[q] = autonomous ? fcn[q] + hc * k1[q] : (fcn[q] + hc * k1[q]) + dh * 0.0;
+              else k2[q] = (fcn[q] + hc * k1[q]) + dh * 0.0;      // + HG*dFdT with dFdT = +0.0: (dh*gamma2)*0.0, a zero of dh's sign (gamma2 > 0)
+            }
           }
           lap(6);
-          solve(ki, false);
+          solve(k2, false);
+          dump_vec(3 * NVAR + 2 * NNZ, k2);
           lap(4);
-        }, std::integral_constant<int, 1>{}, std::integral_constant<int, kRosMethod<METHOD>.S>{});
-        { constexpr int S = kRosMethod<METHOD>.S; nsol += S; }
+          // stage 3 reuses the stage-2 function value
+          {
+            const double hc1 = wave_uniform(kRosC2 / dh), hc2 = wave_uniform(kRosC3 / dh);
 #pragma unroll
-        for (int q = 0; q < SPT; q++) { ynew[q] = y[q]; yerr[q] = 0.0; }
-        for_stages([&](auto J) {
-          constexpr double mj = kRosMethod<METHOD>.M[decltype(J)::value], ej = kRosMethod<METHOD>.E[decltype(J)::value];
-          const double (&kj)[SPT] = stage_k(J);
-          if constexpr (mj != 0.0) {
-#pragma unroll
-            for (int q = 0; q < SPT; q++) ynew[q] = ynew[q] + mj * kj[q];
+            for (int q = 0; q < SPT; q++) {
+              if constexpr (OPT) k3[q] = autonomous ? (fcn[q] + hc1 * k1[q]) + hc2 * k2[q] : ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;
+              else k3[q] = ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;      // (dh*gamma3)*0.0 likewise (gamma3 > 0)
+            }
           }
-          if constexpr (ej != 0.0) {
+          lap(6);
+          solve(k3, false);
+          dump_vec(4 * NVAR + 2 * NNZ, k3);
+          lap(4);
+          nsol += 3;
 #pragma unroll
-            for (int q = 0; q < SPT; q++) yerr[q] = yerr[q] + ej * kj[q];
+          for (int q = 0; q < SPT; q++) {
+            ynew[q] = ((y[q] + kRosM1 * k1[q]) + kRosM2 * k2[q]) + kRosM3 * k3[q];
+            yerr[q] = ((0.0 + kRosE1 * k1[q]) + kRosE2 * k2[q]) + kRosE3 * k3[q];
           }
-        }, std::integral_constant<int, 0>{}, std::integral_constant<int, kRosMethod<METHOD>.S>{});
-      }
-      lap(6);
-      const double Err = error_norm(y, ynew, yerr);
-      if constexpr (DUMP) {
-        if (dumping && t == 0) { dump[5 * NVAR + 2 * NNZ] = Err; dump[5 * NVAR + 2 * NNZ + 1] = Hget(); }
-        dumping = false;      // the first attempt only
-      }
-      lap(5);
-      double root;
-      if constexpr (METHOD != kRos3 && kRosMethod<METHOD>.ELO != kRosElo) {      // Err**(1/ros_ELO), ros_ELO = 2 or 4
-        constexpr double inv_elo = 1.0 / kRosMethod<METHOD>.ELO;
-        if constexpr (MT::WAVES_PER_SIMD > 2) root = err_root_elo(Err, inv_elo);
-        else root = pow(Err, inv_elo);
-      } else if constexpr (MT::WAVES_PER_SIMD > 2) root = err_root(Err);      // register-starved kernels: see err_root
-      else root = pow(Err, 1.0 / kRosElo);
-      const double Fac = fmin_f(facmax(), fmax_f(facmin(), facsafe() / root));
-      const double H = Hget();
-      double Hnew = H * Fac;
-      nstp += 1;
-      if constexpr (TRACE) {      // the attempt's record: T is still the step's start, H the step as attempted (after ros_PrepareMatrix_x's halvings)
-        const bool acc = (Err <= 1.0) || (H <= hmin());
-        if (t == 0 && nstp <= a.trace_cap) {
-          const size_t r = (size_t)cell * (size_t)a.trace_cap + (size_t)(nstp - 1);
-          gptr_mut<double> td = GM_(a.trace_d) + r * 4;
-          td[0] = T; td[1] = H; td[2] = Err;
-          td[3] = tr_idx > 0 ? tr_val / (((double)NVAR * Err) * Err) : 0.0;
-          gptr_mut<int32_t> ti2 = GM_(a.trace_i) + r * 2;
-          ti2[0] = tr_idx; ti2[1] = (acc ? 1 : 0) + 2 * tr_halved;
+        } else {
+          // ---- the method kernels: stages 2 .. ros_S (gas.f:1241-1276), unrolled at compile time, in the reference's order of operations.
+          //      WAXPY_x returns at once for a zero coefficient (gas.f:6641): such a term is dropped, not multiplied out.
+          auto for_stages = [&](auto&& f, auto FROM, auto TO) {      // f(integral_constant<int, FROM>) ... f(integral_constant<int, TO - 1>)
+            auto go = [&](auto&& self, auto I) {
+              if constexpr (decltype(I)::value < decltype(TO)::value) {
+                f(I);
+                self(self, std::integral_constant<int, decltype(I)::value + 1>{});
+              }
+            };
+            go(go, FROM);
+          };
+          for_stages([&](auto I) {
+            constexpr int i = decltype(I)::value;      // stage i + 1
+            constexpr int row = i * (i - 1) / 2;       // A(i+1, j+1) = ros_A[row + j]
+            if constexpr (kRosMethod<METHOD>.NewF[i]) {
+#pragma unroll
+              for (int q = 0; q < SPT; q++) ynew[q] = y[q];
+              for_stages([&](auto J) {
+                constexpr double aij = kRosMethod<METHOD>.A[row + decltype(J)::value];
+                if constexpr (aij != 0.0) {
+                  const double (&kj)[SPT] = stage_k(J);
+#pragma unroll
+                  for (int q = 0; q < SPT; q++) ynew[q] = ynew[q] + aij * kj[q];
+                }
+              }, std::integral_constant<int, 0>{}, I);
+              lap(6);
+              fun(ynew, fcn);
+              lap(0);
+              nfun += 1;
+            }
+            // Fcn: the last function value formed, Fcn0 while no stage of this step has formed one (Rodas3's stage 2)
+            constexpr bool fresh = ros_fresh_fcn(METHOD, i);
+            double (&ki)[SPT] = stage_k(I);
+#pragma unroll
+            for (int q = 0; q < SPT; q++) ki[q] = fresh ? fcn[q] : fcn0[q];
+            for_stages([&](auto J) {
+              constexpr double cij = kRosMethod<METHOD>.C[row + decltype(J)::value];
+              if constexpr (cij != 0.0) {
+                const double hc = wave_uniform(cij / dh);
+                const double (&kj)[SPT] = stage_k(J);
+#pragma unroll
+                for (int q = 0; q < SPT; q++) ki[q] = ki[q] + hc * kj[q];
+              }
+            }, std::integral_constant<int, 0>{}, I);
+            constexpr double gi = kRosMethod<METHOD>.Gamma[i];
+            if constexpr (gi != 0.0) {      // + HG*dFdT with dFdT = +0.0: a zero with the sign of Direction*H*Gamma(i); nothing where Gamma(i) = 0 or autonomous (gas.f:1268)
+              const double hg0 = wave_uniform((dh * gi) * 0.0);
+#pragma unroll
+              for (int q = 0; q < SPT; q++) ki[q] = autonomous ? ki[q] : ki[q] + hg0;
+            }
+            lap(6);
+            solve(ki, false);
+            lap(4);
+          }, std::integral_constant<int, 1>{}, std::integral_constant<int, kRosMethod<METHOD>.S>{});
+          { constexpr int S = kRosMethod<METHOD>.S; nsol += S; }
+#pragma unroll
+          for (int q = 0; q < SPT; q++) { ynew[q] = y[q]; yerr[q] = 0.0; }
+          for_stages([&](auto J) {
+            constexpr double mj = kRosMethod<METHOD>.M[decltype(J)::value], ej = kRosMethod<METHOD>.E[decltype(J)::value];
+            const double (&kj)[SPT] = stage_k(J);
+            if constexpr (mj != 0.0) {
+#pragma unroll
+              for (int q = 0; q < SPT; q++) ynew[q] = ynew[q] + mj * kj[q];
+            }
+            if constexpr (ej != 0.0) {
+#pragma unroll
+              for (int q = 0; q < SPT; q++) yerr[q] = yerr[q] + ej * kj[q];
+            }
+          }, std::integral_constant<int, 0>{}, std::integral_constant<int, kRosMethod<METHOD>.S>{});
         }
+        lap(6);
+        const double Err = error_norm(y, ynew, yerr);
+        if constexpr (DUMP) {
+          if (dumping && t == 0) { dump[5 * NVAR + 2 * NNZ] = Err; dump[5 * NVAR + 2 * NNZ + 1] = Hget(); }
+          dumping = false;      // the first attempt only
+        }
+        lap(5);
+        double root;
+        if constexpr (METHOD != kRos3 && kRosMethod<METHOD>.ELO != kRosElo) {      // Err**(1/ros_ELO), ros_ELO = 2 or 4
+          constexpr double inv_elo = 1.0 / kRosMethod<METHOD>.ELO;
+          if constexpr (MT::WAVES_PER_SIMD > 2) root = err_root_elo(Err, inv_elo);
+          else root = pow(Err, inv_elo);
+        } else if constexpr (MT::WAVES_PER_SIMD > 2) root = err_root(Err);      // register-starved kernels: see err_root
+        else root = pow(Err, 1.0 / kRosElo);
+        const double Fac = fmin_f(facmax(), fmax_f(facmin(), facsafe() / root));
+        const double H = Hget();
+        double Hnew = H * Fac;
+        nstp += 1;
+        if constexpr (TRACE) {      // the attempt's record: T is still the step's start, H the step as attempted (after ros_PrepareMatrix_x's halvings)
+          const bool acc = (Err <= 1.0) || (H <= hmin());
+          if (t == 0 && nstp <= a.trace_cap) {
+            const size_t r = (size_t)cell * (size_t)a.trace_cap + (size_t)(nstp - 1);
+            gptr_mut<double> td = GM_(a.trace_d) + r * 4;
+            td[0] = T; td[1] = H; td[2] = Err;
+            td[3] = tr_idx > 0 ? tr_val / (((double)NVAR * Err) * Err) : 0.0;
+            gptr_mut<int32_t> ti2 = GM_(a.trace_i) + r * 2;
+            ti2[0] = tr_idx; ti2[1] = (acc ? 1 : 0) + 2 * tr_halved;
+          }
 #pragma unroll
-        for (int q = 0; q < SPT; q++)
-          if (tr_idx == q * NT + t + 1) ctrl_r[q] += 1;
-      }
-      if ((Err <= 1.0) || (H <= hmin())) {
-        nacc += 1;
+          for (int q = 0; q < SPT; q++)
+            if (tr_idx == q * NT + t + 1) ctrl_r[q] += 1;
+        }
+        if ((Err <= 1.0) || (H <= hmin())) {
+          nacc += 1;
 #pragma unroll
-        for (int q = 0; q < SPT; q++) y[q] = ynew[q];
-        T = wave_uniform(T + dh);
-        Hnew = fmax_f(hmin(), fmin_f(Hnew, hmax()));
-        if (RejectLastH) Hnew = fmin_f(Hnew, H);
-        RejectLastH = false;
-        RejectMoreH = false;
-        Hset(Hnew);
-        accepted = true;
-      } else {
-        if (RejectMoreH) Hnew = H * facrej();
-        RejectMoreH = RejectLastH;
-        RejectLastH = true;
-        Hset(Hnew);
-        if (nacc >= 1) nrej += 1;
+          for (int q = 0; q < SPT; q++) y[q] = ynew[q];
+          T = wave_uniform(T + dh);
+          Hnew = fmax_f(hmin(), fmin_f(Hnew, hmax()));
+          if (RejectLastH) Hnew = fmin_f(Hnew, H);
+          RejectLastH = false;
+          RejectMoreH = false;
+          Hset(Hnew);
+          accepted = true;
+        } else {
+          if (RejectMoreH) Hnew = H * facrej();
+          RejectMoreH = RejectLastH;
+          RejectLastH = true;
+          Hset(Hnew);
+          if (nacc >= 1) nrej += 1;
+        }
       }
+      if (ierr < 0) break;
     }
-    if (ierr < 0) break;
-  }
 
-  // ---- results
-  {
-    int tt = t;
-    asm volatile("" : "+v"(tt));      // (the output offset is formed here: shared with the input load's it was a 64-bit value kept across the whole step loop — in scratch, in the 128-register kernels)
-#pragma unroll
-    for (int q = 0; q < SPT; q++) {
-      const int s = q * NT + tt;
-      if (s < NVAR) GM_(a.var_out)[(size_t)cell * NVAR + s] = y[q];
-    }
-  }
-  if constexpr (TRACE) {
-    if (a.ctrl) {
+    // ---- results
+    {
+      int tt = t;
+      asm volatile("" : "+v"(tt));      // (the output offset is formed here: shared with the input load's it was a 64-bit value kept across the whole step loop — in scratch, in the 128-register kernels)
 #pragma unroll
       for (int q = 0; q < SPT; q++) {
-        const int s = q * NT + t;
-        if (s < NVAR) GM_(a.ctrl)[(size_t)cell * NVAR + s] = ctrl_r[q];
+        const int s = q * NT + tt;
+        if constexpr (SERIES) {
+          if (s < NVAR) GM_(a.var_out)[(int64_t)leg * a.leg_var + (int64_t)cell * NVAR + s] = y[q];
+        } else {
+          if (s < NVAR) GM_(a.var_out)[(size_t)cell * NVAR + s] = y[q];
+        }
       }
     }
-    if (t == 0) GM_(a.ntrace)[cell] = nstp;
-  }
-  if (t == 0) {
-    GM_(a.ierr)[cell] = ierr;
-    gptr_mut<int32_t> st = GM_(a.stats) + (size_t)cell * 8;
-    st[0] = nfun; st[1] = njac; st[2] = nstp; st[3] = nacc; st[4] = nrej; st[5] = ndec; st[6] = nsol; st[7] = nsng;
-    if constexpr (profiling) {
-      lap(6);
-      pc[7] = clock64() - t_begin;
-      for (int k = 0; k < kProfSlots; k++) GM_(a.prof)[(size_t)cell * kProfSlots + k] = pc[k];
+    if constexpr (TRACE) {
+      if (a.ctrl) {
+#pragma unroll
+        for (int q = 0; q < SPT; q++) {
+          const int s = q * NT + t;
+          if (s < NVAR) GM_(a.ctrl)[(size_t)cell * NVAR + s] = ctrl_r[q];
+        }
+      }
+      if (t == 0) GM_(a.ntrace)[cell] = nstp;
     }
-    if (a.texit_hexit) {
-      GM_(a.texit_hexit)[(size_t)cell * 2] = T;
-      GM_(a.texit_hexit)[(size_t)cell * 2 + 1] = *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT));
+    if constexpr (SERIES) {      // the leg's results, into its block of every array
+      if (t == 0) {
+        GM_(a.ierr)[(int64_t)leg * a.leg_ierr + cell] = ierr;
+        gptr_mut<int32_t> st = GM_(a.stats) + ((int64_t)leg * a.leg_stats + (int64_t)cell * 8);
+        st[0] = nfun; st[1] = njac; st[2] = nstp; st[3] = nacc; st[4] = nrej; st[5] = ndec; st[6] = nsol; st[7] = nsng;
+        if (a.texit_hexit) {
+          GM_(a.texit_hexit)[(int64_t)leg * a.leg_th + (int64_t)cell * 2] = T;
+          GM_(a.texit_hexit)[(int64_t)leg * a.leg_th + (int64_t)cell * 2 + 1] = *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT));
+        }
+        if (a.h_last) GM_(a.h_last)[(int64_t)leg * a.leg_h + cell] = Hget();
+      }
+    } else if (t == 0) {
+      GM_(a.ierr)[cell] = ierr;
+      gptr_mut<int32_t> st = GM_(a.stats) + (size_t)cell * 8;
+      st[0] = nfun; st[1] = njac; st[2] = nstp; st[3] = nacc; st[4] = nrej; st[5] = ndec; st[6] = nsol; st[7] = nsng;
+      if constexpr (profiling) {
+        lap(6);
+        pc[7] = clock64() - t_begin;
+        for (int k = 0; k < kProfSlots; k++) GM_(a.prof)[(size_t)cell * kProfSlots + k] = pc[k];
+      }
+      if (a.texit_hexit) {
+        GM_(a.texit_hexit)[(size_t)cell * 2] = T;
+        GM_(a.texit_hexit)[(size_t)cell * 2 + 1] = *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT));
+      }
+      if (a.h_last) GM_(a.h_last)[cell] = Hget();
     }
-    if (a.h_last) GM_(a.h_last)[cell] = Hget();
-  }
+    if constexpr (SERIES) {
+      if (++leg >= a.nleg) break;
+    }
+  } while (SERIES);
 }
 
 #ifndef MISTRA_METHOD_TU      // (ros_method_kernel.hip and ros_trace_kernel.hip include this file for the kernel template alone)

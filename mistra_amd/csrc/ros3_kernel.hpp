@@ -105,4 +105,9 @@ hipError_t launch_ros_method(const KernelArgs& a, hipStream_t stream, bool* lds_
 template <class MT, int NT>
 hipError_t launch_ros_trace(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
 
+// The series kernels (VARIANT 5: the options kernel of any of the five methods with a loop over the legs; kernel_args.hpp: times, nleg): a.opt and
+// a.times must be set.  One explicit specialisation per <mechanism, method>, each in a translation unit of its own (ros_series_kernel.hip).
+template <class MT, int NT, int METHOD>
+hipError_t launch_ros_series(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
+
 }  // namespace mistra

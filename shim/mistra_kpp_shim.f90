@@ -42,6 +42,13 @@
 ! The same with tolerances PER CELL (mistra_chem_rosenbrock_cells_ex): ATOL(NTOL,NCELL), RTOL(NTOL,NCELL), NTOL = 1 or NVAR (IPAR(2) = 0 needs NVAR).
 ! IERR = -5 is then a cell's own result: the cell is reported as ROSENBROCK_BATCH_x reports it, the others run.
 !     SUBROUTINE ROSENBROCK_BATCH_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT)
+!
+! A SERIES of such calls in one launch (mistra_chem_rosenbrock_series_ex; INTEGRATION.md 4m): NLEG legs over TIMES(1:NLEG+1), leg l one call of Rosenbrock_x from
+! TIMES(l) to TIMES(l+1) on the state leg l-1 left, the state on the GPU from the first time to the last.  VAR is not changed; leg l returns VSER(:,k,l),
+! TEXIT(k,l), HEXIT(k,l), IERR(k,l), ISTAT(:,k,l), bit for bit what ROSENBROCK_BATCH_x called NLEG times returns.  CARRY (logical): a later leg starts with the
+! previous leg's HEXIT of the cell where that is > 0 instead of RPAR(3).  ros_ErrorMsg_x's lines go to unit 6 for every failed leg and cell, in leg order.
+!     SUBROUTINE ROSENBROCK_BATCH_SERIES_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+!     SUBROUTINE ROSENBROCK_BATCH_SERIES_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
 module mistra_chem_c_api
   use iso_c_binding
   implicit none
@@ -124,6 +131,28 @@ module mistra_chem_c_api
        integer(c_int32_t) :: ierr(*), stats(*)
        integer(c_int) :: rc
      end function mistra_chem_rosenbrock_cells_ex
+     function mistra_chem_rosenbrock_series_ex(mech, ncell, var_in, fix, rconst, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, &
+          stats, t_h) bind(C, name="mistra_chem_rosenbrock_series_ex") result(rc)
+       import :: c_int, c_double, c_int32_t, c_ptr
+       integer(c_int), value :: mech, ncell, nleg, carry_h
+       type(c_ptr), value :: hstart
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_series(*), t_h(*)
+       real(c_double), intent(in) :: times(*), atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_series_ex
+     function mistra_chem_rosenbrock_series_cells_ex(mech, ncell, var_in, fix, rconst, nleg, times, atol, rtol, ntol, rpar, ipar, carry_h, hstart, var_series, &
+          ierr, stats, t_h) bind(C, name="mistra_chem_rosenbrock_series_cells_ex") result(rc)
+       import :: c_int, c_double, c_int32_t, c_ptr
+       integer(c_int), value :: mech, ncell, nleg, ntol, carry_h
+       type(c_ptr), value :: hstart
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_series(*), t_h(*)
+       real(c_double), intent(in) :: times(*), atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_series_cells_ex
      function mistra_chem_set_step_reuse(mech, on) bind(C, name="mistra_chem_set_step_reuse") result(rc)
        import :: c_int
        integer(c_int), value :: mech, on
@@ -377,6 +406,43 @@ contains
     end do
     deallocate (th)
   end subroutine rosenbrock_batch
+
+  ! A series of Rosenbrock_x calls for NCELL cells in one launch; the messages leg by leg and in cell order, as NLEG calls of ROSENBROCK_BATCH_x would have
+  ! written ros_ErrorMsg_x's lines (a refusal at T = the leg's start, H = 0).  The rows of zero pivots are not recorded for a series: no warning lines.
+  ! NTOL present: ATOL / RTOL hold a row of NTOL entries per cell (ROSENBROCK_BATCH_SERIES_CELLS_x)
+  subroutine rosenbrock_series(mech, sfx, NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL)
+    integer, intent(in) :: mech, NCELL, NLEG
+    integer, intent(in), optional :: NTOL
+    character(len=1), intent(in) :: sfx
+    logical, intent(in) :: CARRY
+    real(c_double) :: VAR(*), FIX(*), RCONST(*), VSER(*), TEXIT(NCELL, *), HEXIT(NCELL, *)
+    real(c_double), intent(in) :: TIMES(*), ATOL(*), RTOL(*), RPAR(20)
+    integer(c_int32_t), intent(in) :: IPAR(20)
+    integer(c_int32_t) :: IERR(NCELL, *), ISTAT(8, NCELL, *)
+    real(c_double), allocatable :: th(:, :, :)
+    integer :: k, l
+    if (NCELL <= 0) return
+    allocate (th(3, NCELL, max(NLEG, 1)))
+    if (present(NTOL)) then
+       if (mistra_chem_rosenbrock_series_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NLEG, c_int), TIMES, ATOL, RTOL, int(NTOL, c_int), &
+            RPAR, IPAR, int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_SERIES_CELLS_'//sfx)
+    else
+       if (mistra_chem_rosenbrock_series_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NLEG, c_int), TIMES, ATOL, RTOL, RPAR, IPAR, &
+            int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_SERIES_'//sfx)
+    end if
+    do l = 1, NLEG
+       do k = 1, NCELL
+          TEXIT(k, l) = th(1, k, l)
+          HEXIT(k, l) = th(2, k, l)
+          if (IERR(k, l) < -5) then
+             call mistra_chem_error_lines(sfx, int(IERR(k, l)), th(1, k, l), th(3, k, l))
+          else if (IERR(k, l) < 0) then
+             call mistra_chem_error_lines(sfx, int(IERR(k, l)), TIMES(l), 0.d0)
+          end if
+       end do
+    end do
+    deallocate (th)
+  end subroutine rosenbrock_series
 end module mistra_chem_c_api
 
 subroutine INTEGRATE_g(TIN, TOUT)
@@ -722,3 +788,70 @@ subroutine ROSENBROCK_BATCH_CELLS_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL,
   integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
   call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL)
 end subroutine ROSENBROCK_BATCH_CELLS_t
+
+! ---- a series of Rosenbrock_x calls in one launch: the legs' results side by side, VSER(NVAR,NCELL,NLEG), TEXIT / HEXIT / IERR (NCELL,NLEG), ISTAT(8,NCELL,NLEG)
+subroutine ROSENBROCK_BATCH_SERIES_g(NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG
+  logical :: CARRY
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(102, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(0, 'g', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+end subroutine ROSENBROCK_BATCH_SERIES_g
+
+subroutine ROSENBROCK_BATCH_SERIES_CELLS_g(NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NTOL
+  logical :: CARRY
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TIMES(*), ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), VSER(102, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(0, 'g', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL)
+end subroutine ROSENBROCK_BATCH_SERIES_CELLS_g
+
+subroutine ROSENBROCK_BATCH_SERIES_a(NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG
+  logical :: CARRY
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(257, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(1, 'a', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+end subroutine ROSENBROCK_BATCH_SERIES_a
+
+subroutine ROSENBROCK_BATCH_SERIES_CELLS_a(NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NTOL
+  logical :: CARRY
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TIMES(*), ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), VSER(257, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(1, 'a', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL)
+end subroutine ROSENBROCK_BATCH_SERIES_CELLS_a
+
+subroutine ROSENBROCK_BATCH_SERIES_t(NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG
+  logical :: CARRY
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(417, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(2, 't', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+end subroutine ROSENBROCK_BATCH_SERIES_t
+
+subroutine ROSENBROCK_BATCH_SERIES_CELLS_t(NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NTOL
+  logical :: CARRY
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TIMES(*), ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), VSER(417, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(2, 't', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL)
+end subroutine ROSENBROCK_BATCH_SERIES_CELLS_t

@@ -12,6 +12,10 @@
 !                                                      out.bin = per cell VAR, TEXIT, HEXIT, then per cell IERR and the 8 statistics
 !          shim_driver <YG|YA|YT> <in.bin> <out.bin>   the same with tolerances per cell: in.bin = IPAR(20), RPAR(20), TSTART, TEND, ncell, ntol, then per cell VAR,
 !                                                      FIX, RCONST, ATOL(ntol), RTOL(ntol), all handed to ONE call of ROSENBROCK_BATCH_CELLS_x; out.bin as for <XG|XA|XT>
+!          shim_driver <ZG|ZA|ZT> <in.bin> <out.bin>   a series of Rosenbrock_x calls: in.bin = IPAR(20), RPAR(20), ATOL(NVAR), RTOL(NVAR), ncell, nleg, carry (0 | 1), ntol,
+!                                                      TIMES(nleg + 1), then the cells as for <G|A|T>.  ntol = 0: ONE call of ROSENBROCK_BATCH_SERIES_x with the pair; ntol = 1 or
+!                                                      NVAR: ONE call of ROSENBROCK_BATCH_SERIES_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin = per leg
+!                                                      and cell VAR, TEXIT, HEXIT, IERR, the 8 statistics
 !          shim_driver <Eg|Ea|Et> <in.bin> <out.bin>   in.bin = ncell, then per cell VAR, FIX, ENV (the vector MISTRA_RATES_ENV_x packs,
 !                                                      mistra_kpp_rates.f90): UPDATE_RCONST_BATCH_x, then INTEGRATE_BATCH_ENV_x (rates and
 !                                                      integrator on the device, RCONST never crosses PCIe); out.bin = per cell VAR,
@@ -69,6 +73,13 @@ program shim_driver
      case ('G'); call run_rosenbrock_cells(0, 102, 3, 331, trim(fin), trim(fout))
      case ('A'); call run_rosenbrock_cells(1, 257, 5, 979, trim(fin), trim(fout))
      case ('T'); call run_rosenbrock_cells(2, 417, 7, 1627, trim(fin), trim(fout))
+     case default; stop 'mechanism must be G, A or T'
+     end select
+  case ('Z')
+     select case (a1(2:2))
+     case ('G'); call run_series(0, 102, 3, 331, trim(fin), trim(fout))
+     case ('A'); call run_series(1, 257, 5, 979, trim(fin), trim(fout))
+     case ('T'); call run_series(2, 417, 7, 1627, trim(fin), trim(fout))
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('K', 'H', 'Q', 'V', 'S', 'C', 'R')
@@ -275,6 +286,57 @@ contains
     end do
     close (11); close (12)
   end subroutine run_rosenbrock_cells
+  subroutine run_series(mech, NVAR, NFIX, NREACT, fin, fout)
+    integer, intent(in) :: mech, NVAR, NFIX, NREACT
+    character(len=*), intent(in) :: fin, fout
+    double precision :: ropt(40), tt(4)
+    double precision, allocatable :: ATOL(:), RTOL(:), AROW(:, :), RROW(:, :), TIMES(:), VAR(:, :), FIX(:, :), RCONST(:, :), VSER(:, :, :), TEXIT(:, :), HEXIT(:, :), rec(:)
+    integer :: IPAR(20), n, nleg, ntol, i, l
+    logical :: carry
+    integer, allocatable :: IERR(:, :), ISTAT(:, :, :)
+    open (11, file=fin, access='stream', form='unformatted', status='old')
+    open (12, file=fout, access='stream', form='unformatted', status='replace')
+    allocate (ATOL(NVAR), RTOL(NVAR))
+    read (11) ropt, ATOL, RTOL, tt      ! tt: ncell, nleg, carry, ntol
+    IPAR = int(ropt(1:20))
+    n = int(tt(1))
+    nleg = int(tt(2))
+    carry = tt(3) /= 0.d0
+    ntol = int(tt(4))
+    allocate (TIMES(nleg + 1))
+    read (11) TIMES
+    allocate (VAR(NVAR, n), FIX(NFIX, n), RCONST(NREACT, n), VSER(NVAR, n, nleg), TEXIT(n, nleg), HEXIT(n, nleg), IERR(n, nleg), ISTAT(8, n, nleg))
+    allocate (rec(NVAR + NFIX + NREACT), AROW(max(ntol, 1), n), RROW(max(ntol, 1), n))
+    do i = 1, n
+       read (11) rec
+       VAR(:, i) = rec(1:NVAR)
+       FIX(:, i) = rec(NVAR + 1:NVAR + NFIX)
+       RCONST(:, i) = rec(NVAR + NFIX + 1:)
+       if (ntol > 0) then
+          AROW(:, i) = ATOL(1:ntol)
+          RROW(:, i) = RTOL(1:ntol)
+       end if
+    end do
+    if (ntol == 0) then
+       select case (mech)
+       case (0); call ROSENBROCK_BATCH_SERIES_g(n, VAR, FIX, RCONST, nleg, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       case (1); call ROSENBROCK_BATCH_SERIES_a(n, VAR, FIX, RCONST, nleg, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       case (2); call ROSENBROCK_BATCH_SERIES_t(n, VAR, FIX, RCONST, nleg, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       end select
+    else
+       select case (mech)
+       case (0); call ROSENBROCK_BATCH_SERIES_CELLS_g(n, VAR, FIX, RCONST, nleg, TIMES, AROW, RROW, ntol, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       case (1); call ROSENBROCK_BATCH_SERIES_CELLS_a(n, VAR, FIX, RCONST, nleg, TIMES, AROW, RROW, ntol, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       case (2); call ROSENBROCK_BATCH_SERIES_CELLS_t(n, VAR, FIX, RCONST, nleg, TIMES, AROW, RROW, ntol, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       end select
+    end if
+    do l = 1, nleg
+       do i = 1, n
+          write (12) VSER(:, i, l), TEXIT(i, l), HEXIT(i, l), dble(IERR(i, l)), dble(ISTAT(:, i, l))
+       end do
+    end do
+    close (11); close (12)
+  end subroutine run_series
   subroutine run_env(mech, NVAR, NFIX, NREACT, NENV, fin, fout)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT, NENV
     character(len=*), intent(in) :: fin, fout

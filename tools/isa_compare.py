@@ -5,6 +5,8 @@ mistra_amd/csrc/ros3_kernel.hip at two commits), and the resources of the method
     python tools/isa_compare.py PARENT.s NEW.s      per function: instructions in both, whether the bodies are identical
     python tools/isa_compare.py --methods           per method unit (mistra_amd/build.py: METHOD_UNITS): the kernel's registers, scratch and LDS
                                                     from the code object's metadata, compiled here as the build compiles them
+    python tools/isa_compare.py --series            per series unit (SERIES_UNITS): the same figures of the series kernel (VARIANT 5) beside its VARIANT 3
+                                                    sibling's — the product unit's options kernel for Ros3, the method unit's for the other four
 
 A kernel's mangled name carries its template arguments: the METHOD parameter added to ros3_integrate_kernel (default Ros3 = 2) is cut out of the
 new listing's names before the comparison; nothing else is normalised."""
@@ -71,8 +73,45 @@ def methods():
                                                         get("private_segment_fixed_size"), get("vgpr_spill_count"), get("group_segment_fixed_size")))
 
 
+def _kernels(path):
+    """[(kernel name, {metadata key: value})] of a listing's code object metadata"""
+    text = open(path).read()
+    out = []
+    for m in re.finditer(r"- \.agpr_count:.*?(?=\n  - \.agpr_count|\namdhsa\.target)", text, re.S):
+        k = m.group(0)
+        out.append((re.search(r"\.name:\s+(\S+)", k).group(1), {key: int(v) for key, v in re.findall(r"\.(\w+):\s+(\d+)\n", k)}))
+    return out
+
+
+def series():
+    from mistra_amd import build as B
+    names = {1: "Ros2", 2: "Ros3", 3: "Ros4", 4: "Rodas3", 5: "Rodas4"}
+    mechs = ("gas", "aer", "tot")
+    cols = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")
+    print("%-4s %-7s | %-40s | %s" % ("mech", "method", "VARIANT 3 (the options kernel)", "VARIANT 5 (the series kernel)"))
+    print("%-4s %-7s | %5s %5s %8s %7s %10s | %5s %5s %8s %7s %10s   (LDS: dynamic, LdsLayout<MT, NT>::TOTAL doubles, the same for both)" %
+          (("", "") + ("VGPRs", "SGPRs", "scratch", "spilled", "static LDS") * 2))
+    with tempfile.TemporaryDirectory() as tmp:
+        def listing(src, flags):
+            s = os.path.join(tmp, "u.s")
+            cmd = [B.hipcc(), "--offload-arch=" + B.ARCH] + [f for f in B.COMMON if f != "-fPIC"] + flags + ["-S", "--offload-device-only", os.path.join(B.CSRC, src), "-o", s]
+            subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+            return _kernels(s)
+        product = listing("ros3_kernel.hip", [])
+        for mech, method in B.SERIES_UNITS:
+            if method == 2:
+                sib = [k for n, k in product if re.search(r"ros3_integrate_kernelINS_\d+%sTraitsELi\d+ELi3ELi2E" % mechs[mech].capitalize(), n)]
+            else:
+                sib = [k for n, k in listing(B.METHOD_SOURCE, B.method_flags(mech, method)) if "ros3_integrate_kernel" in n]
+            new = [k for n, k in listing(B.SERIES_SOURCE, B.series_flags(mech, method)) if "ros3_integrate_kernel" in n]
+            assert len(sib) == 1 and len(new) == 1, (mech, method, len(sib), len(new))
+            print("%-4s %-7s | %5d %5d %8d %7d %10d | %5d %5d %8d %7d %10d" % ((mechs[mech], names[method]) + tuple(sib[0][c] for c in cols) + tuple(new[0][c] for c in cols)))
+
+
 if __name__ == "__main__":
     if "--methods" in sys.argv:
         methods()
+    elif "--series" in sys.argv:
+        series()
     else:
         sys.exit(0 if compare(sys.argv[1], sys.argv[2]) else 1)

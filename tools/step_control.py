@@ -8,6 +8,7 @@
                                                                                              call with tolerances per cell (cell_atol + rosenbrock_trace_cells)
     ... --yardstick                                                                          also the distance of the end state from Rodas4 at RelTol 1e-7
     python tools/step_control.py aer --workload 4096                                         cells 0 .. 4095 of the synthetic workload (mistra_amd/workload.py)
+    ... --series 4                                                                           the yardstick distance at 4 equal sub-times, not at the end only
     ... --cpu                                                                                the Python restatement (tests/ros_trace_py.py) instead of the GPU
 
 Prints the attempts per cell and, for the species that controlled the most attempts (the species with the largest term of ros_ErrorNorm_x's sum):
@@ -18,7 +19,12 @@ line, in that order) prints names, the mechanism tables carry none.
 --yardstick integrates the same cells once more with Rodas4 at scalar RelTol = 1e-7 and INTEGRATE_x's AbsTol (the yardstick of
 profiles/r02_hstart_reuse_study.txt; one batched call) and prints how far the run's end state lies from it: the largest relative difference over the
 species above 1e-3 of their cell's maximum, and over all species with the floor 1e-12 x max|c| (tests/conftest.py: rel_diff).  These are properties of
-the reference algorithm at the run's tolerances, not of this library: nothing is asserted on them."""
+the reference algorithm at the run's tolerances, not of this library: nothing is asserted on them.
+
+--series K prints that distance at K equal sub-times of the interval instead: the run's options and the yardstick's each as ONE series of K legs
+(mistra_chem_rosenbrock_series_ex, INTEGRATION.md §4m: K calls of Rosenbrock_x on the chained state in one launch), so the table shows where inside
+the chemistry step the run leaves the yardstick.  Every leg is a call of its own — its first step is RPAR(3) again — so the last row is the distance
+after K calls, not the single call's."""
 import argparse
 import os
 import sys
@@ -129,6 +135,30 @@ def yardstick(mech, var, fix, rconst, tstart, tend, cpu):
     return np.array([RM.rosenbrock(o, diag, var[c], fix[c], rconst[c], ipar, rpar, atol, rtol, tstart, tend)[0] for c in range(var.shape[0])])
 
 
+def series_states(mech, var, fix, rconst, times, opts, cpu, atol_rel=None):
+    """the cells' states at times[1:] by one series of Rosenbrock_x calls with opts = (ipar, rpar, atol, rtol) -> [nleg, ncell, NVAR]; atol_rel: AbsTol
+    per cell from the state the series receives, for every leg.  --cpu: the restatement called leg by leg on its chained state (tests/ros_series_py.py)"""
+    ipar, rpar, atol, rtol = opts
+    per_cell = None if atol_rel is None else cell_atol_rows(mech, var, atol_rel)
+    if not cpu:
+        from mistra_amd import chem
+        if per_cell is None:
+            return chem.rosenbrock_series(mech, var, fix, rconst, times, ipar, rpar, atol, rtol).var
+        return chem.rosenbrock_series(mech, var, fix, rconst, times, ipar, rpar, per_cell, np.full_like(per_cell, rtol[0])).var
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import ros_methods_py as RM
+    import ros_series_py as RS
+    from mistra_amd import mechtab
+    from oracle.oracle import Oracle
+    o, diag = Oracle(mech), mechtab.load(mech).diag
+    out = np.empty((len(times) - 1,) + var.shape)
+    for c in range(var.shape[0]):
+        at = atol if per_cell is None else np.full_like(atol, per_cell[c, 0])
+        s = RS.Series(ipar, rpar, at, rtol, np.asarray(times, np.float64), False)
+        out[:, c] = RS.chain(lambda y, rp, t0, t1: RM.rosenbrock(o, diag, y, fix[c], rconst[c], ipar, rp, at, rtol, t0, t1), var[c], s)[0]
+    return out
+
+
 def distances(got, want):
     """-> (largest relative difference over the species above 1e-3 of their cell's maximum, largest over all species with the floor 1e-12 x max|c|):
     the two measures of tests/conftest.py (rel_diff), NaN where nothing can be compared"""
@@ -202,6 +232,7 @@ def main(argv=None):
     ap.add_argument("--names", help="file with one species name per line, in VAR's order")
     ap.add_argument("--cpu", action="store_true", help="run the Python restatement instead of the GPU")
     ap.add_argument("--yardstick", action="store_true", help="also print the end state's distance from Rodas4 at RelTol 1e-7, INTEGRATE_x's AbsTol")
+    ap.add_argument("--series", type=int, metavar="K", help="print the yardstick distance at K equal sub-times (one series of K legs each)")
     a = ap.parse_args(argv)
     if a.atol is not None and a.atol_rel is not None:
         ap.error("--atol and --atol-rel exclude each other")
@@ -218,6 +249,19 @@ def main(argv=None):
         major, every = distances(out, yardstick(a.mech, var, fix, rconst, a.tstart, a.tend, a.cpu))
         print("distance from the yardstick (Rodas4, RelTol = %g, AbsTol = 1e-25): species above 1e-3 of the cell's maximum: %.3e   all species, floor "
               "1e-12 x max|c|: %.3e" % (YARDSTICK_RTOL, major, every))
+    if a.series:
+        if a.series < 1:
+            ap.error("--series K: K >= 1")
+        times = np.linspace(a.tstart, a.tend, a.series + 1)
+        yopts = options(a.mech, None, YARDSTICK_RTOL)
+        yopts[0][3] = YARDSTICK_METHOD
+        got = series_states(a.mech, var, fix, rconst, times, opts, a.cpu, a.atol_rel)
+        want = series_states(a.mech, var, fix, rconst, times, yopts, a.cpu)
+        print("distance from the yardstick at %d sub-times, each side one series of %d calls (Rodas4, RelTol = %g, AbsTol = 1e-25)" % (a.series, a.series, YARDSTICK_RTOL))
+        print("%12s  %-28s %s" % ("t [s]", "species above 1e-3 of cell max", "all species, floor 1e-12 x max|c|"))
+        for k in range(a.series):
+            major, every = distances(got[k], want[k])
+            print("%12g  %-28.3e %.3e" % (times[k + 1], major, every))
     return 0
 
 
