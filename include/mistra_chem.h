@@ -265,6 +265,36 @@ int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double*
                                               const double* d_hstart, void* hip_stream,
                                               int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl);
 
+/* THE REACTION FLUX: Rosenbrock_x as the four entries above run it, plus every reaction's rate integrated over the call.  One more
+ * output, flux [ncell][NREACT]; with the call's accepted states Y_0 = Y(Tstart), Y_1 .. Y_N, accepted step sizes H_0 .. H_(N-1) and D = Direction (+-1)
+ *     flux[r] = sum over n = 0 .. N-1, in time order, of (0.5 * (D*H_n)) * (A_r(Y_n) + A_r(Y_(n+1))),   A_r(Y) = RCT(r) * X * X * X as Fun_x forms it,
+ * every multiply and add rounded once, flux[r] starting at +0.0.  A_r(Y_n), n < N, is the product the step's own first Fun_x forms: rejected attempts and
+ * stage evaluations contribute nothing.  A_r(Y_N) takes one more evaluation of the A products at the state the call returns (a normal return, and -6 / -7
+ * at Texit; after -8 the failing step's own Fun_x has closed the last accepted step); it is not a Fun_x call and is not counted in Nfun.  A backward
+ * call carries the sign of D: S * flux (S: the stoichiometric matrix) approximates Y(Texit) - Y(Tstart) in either direction, to the trapezoid's accuracy.
+ * var_out, ierr, stats and t_h / d_texit_hexit are bit for bit those of mistra_chem_rosenbrock_ex / _device (the cells forms: _cells_ex / _cells_device)
+ * with the same arguments, d_hstart included.  A call that makes no accepted step returns zeros; so does a refusal (-1 .. -5, whole call or, in the cells
+ * forms, per cell) in the rows it covers.  The options travel with the call (MISTRA_ROSENBROCK_CALLS_IN_FLIGHT blocks); the options in force, the
+ * integrator policy and step reuse are not involved.  The _ex forms split the batch over the device slots and fail while a column step of the mechanism
+ * is open.  A null flux fails with a text before a device is touched.  There is no series form, no trace form and no user slot: both user ids fail with
+ * the slot's text. */
+int mistra_chem_rosenbrock_flux_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                   const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
+                                   int32_t* stats, double* t_h, double* flux /* [ncell][NREACT] */);
+int mistra_chem_rosenbrock_flux_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                       double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,   /* host arrays */
+                                       double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
+                                       void* hip_stream, double* d_flux);                                                            /* in stream order */
+int mistra_chem_rosenbrock_flux_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart,
+                                         double tend, const double* atol, const double* rtol, int ntol,                             /* rows per cell */
+                                         const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr, int32_t* stats, double* t_h,
+                                         double* flux);
+int mistra_chem_rosenbrock_flux_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                             double tend, const double* d_atol, const double* d_rtol, int ntol,                     /* device arrays */
+                                             const double* rpar, const int32_t* ipar,                                               /* host arrays */
+                                             double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                             const double* d_hstart, void* hip_stream, double* d_flux);
+
 /* A SERIES: several output times in one call and one kernel launch, the cell's state, FIX and the rate constants on chip from the first time to the
  * last.  nleg >= 1 legs over times[0 .. nleg]; leg k is one call of Rosenbrock_x(Y, times[k], times[k+1], AbsTol, RelTol, RPAR,
  * IPAR, IERR) on the state leg k-1 left, and returns what that call returns into block k of the per-leg outputs:

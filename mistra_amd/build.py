@@ -33,6 +33,11 @@ TRACE_UNITS = [(mech, None) for mech in (0, 1, 2)]
 # once per (mechanism, IPAR(4)), units of their own for the same reason.  In the unit lists below a series unit is ("series", (mechanism, method)).
 SERIES_SOURCE = "ros_series_kernel.hip"
 SERIES_UNITS = [(mech, method) for mech in (0, 1, 2) for method in (1, 2, 3, 4, 5)]
+# the flux kernels (kernel VARIANT 6: the options kernel of each of the five methods that also integrates every reaction's rate over the call):
+# ros_flux_kernel.hip once per (mechanism, IPAR(4)), units of their own for the same reason.  In the unit lists below a flux unit is
+# ("flux", (mechanism, method)).
+FLUX_SOURCE = "ros_flux_kernel.hip"
+FLUX_UNITS = [(mech, method) for mech in (0, 1, 2) for method in (1, 2, 3, 4, 5)]
 # the user mechanism slots (mechanism ids 3 and 4): MISTRA_USER_MECHS = at most two table paths separated by colons, default the two demo tables
 # (tools/derive_mech.py cuts them from gas and aer), empty = a library without user slots.  Per slot user_traits_gen (a host program built from the
 # schedule compiler) writes the traits header into the build directory and ros_user_kernel.hip is compiled against it, a unit of its own for the same
@@ -122,6 +127,8 @@ def method_flags(mech, method):
         return ["-DMISTRA_USER_SLOT=%d" % method, "-DMISTRA_USER_MECHS=%d" % (method + 1), "-I" + OBJDIR]
     if mech == "series":
         return series_flags(*method)
+    if mech == "flux":
+        return flux_flags(*method)
     if method is None:
         return ["-DMISTRA_TRACE_MECH=%d" % mech]
     return ["-DMISTRA_METHOD_MECH=%d" % mech, "-DMISTRA_METHOD=%d" % method]
@@ -131,11 +138,17 @@ def series_flags(mech, method):
     return ["-DMISTRA_SERIES_MECH=%d" % mech, "-DMISTRA_SERIES_METHOD=%d" % method]
 
 
+def flux_flags(mech, method):
+    return ["-DMISTRA_FLUX_MECH=%d" % mech, "-DMISTRA_FLUX_METHOD=%d" % method]
+
+
 def unit_source(unit):
     if unit[0] == "user":
         return USER_SOURCE
     if unit[0] == "series":
         return SERIES_SOURCE
+    if unit[0] == "flux":
+        return FLUX_SOURCE
     return TRACE_SOURCE if unit[1] is None else METHOD_SOURCE
 
 
@@ -175,6 +188,7 @@ def build_lib(force=False, verbose=False):
     units += [(TRACE_SOURCE, "ros_trace_%d.o" % u[0], method_flags(*u), [kernel_src]) for u in TRACE_UNITS]
     units += [(USER_SOURCE, "ros_user_%d.o" % u[1], method_flags(*u), [kernel_src] + user_files) for u in user_units]
     units += [(SERIES_SOURCE, "ros_series_%d_%d.o" % u, series_flags(*u), [kernel_src]) for u in SERIES_UNITS]
+    units += [(FLUX_SOURCE, "ros_flux_%d_%d.o" % u, flux_flags(*u), [kernel_src]) for u in FLUX_UNITS]
     if n_user:
         units.append(("capi.cpp", "capi_noslots.o", ["-DMISTRA_USER_MECHS=0", "-I" + OBJDIR], []))
     for src, name, flags, deps in units:
@@ -197,15 +211,15 @@ def build_lib(force=False, verbose=False):
     if force or _stale(LIB, objs) or (n_user and _stale(LIB_NOSLOTS, noslots_objs)):
         # the look-ahead rings of ros3_kernel.hip sit in registers the compiler does not know are busy: no library is linked
         # from a kernel object in which a ring-using function's own registers reach its ring (raises).  Every code object that
-        # holds the ring functions is checked: the product unit, the twelve method units, the three trace units, the user slots' units and the
-        # fifteen series units.
-        checked = [None] + METHOD_UNITS + TRACE_UNITS + user_units + [("series", u) for u in SERIES_UNITS]
+        # holds the ring functions is checked: the product unit, the twelve method units, the three trace units, the user slots' units, the
+        # fifteen series units and the fifteen flux units.
+        checked = [None] + METHOD_UNITS + TRACE_UNITS + user_units + [("series", u) for u in SERIES_UNITS] + [("flux", u) for u in FLUX_UNITS]
         with ThreadPoolExecutor(_jobs()) as pool:
             reports = list(pool.map(lambda u: ring_register_report(unit=u), checked))
         for u, isa in zip(checked, reports):
             hits = isa_hazard_report(isa["__isa_text__"])
             if hits:
-                raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly%s:\n  " % (" (method / trace / user / series unit %s)" % (u,) if u else "")
+                raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly%s:\n  " % (" (method / trace / user / series / flux unit %s)" % (u,) if u else "")
                                    + "\n  ".join(hits))
         cmd = [cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
         if verbose:
@@ -230,8 +244,8 @@ def ring_register_report(isa_path=None, unit=None):
     scans it.  Returns {function: highest VGPR named outside inline asm}; raises if a ring-using function reaches its ring, and if
     a function that is not one of RING_FUNCTIONS (nor an integrating kernel, which only calls them) loads into the ring at all.
     unit: None = the product kernels' unit (ros3_kernel.hip), one (mechanism, method) of METHOD_UNITS, one (mechanism, None) of TRACE_UNITS,
-    ("user", slot) of a user mechanism slot (its traits header must be in the build directory: prepare_user_mechs) or ("series", (mechanism, method))
-    of SERIES_UNITS."""
+    ("user", slot) of a user mechanism slot (its traits header must be in the build directory: prepare_user_mechs) ("series", (mechanism, method))
+    of SERIES_UNITS or ("flux", (mechanism, method)) of FLUX_UNITS."""
     import re
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:

@@ -136,6 +136,11 @@ def lib():
                                                                  _dp, _ip, _ip, _dp]
             L.mistra_chem_rosenbrock_series_cells_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, _dp, vp, vp, C.c_int, _dp, _ip, vp, vp, vp, vp,
                                                                      C.c_int, vp, vp]
+        if hasattr(L, "mistra_chem_rosenbrock_flux_ex"):
+            L.mistra_chem_rosenbrock_flux_ex.argtypes = L.mistra_chem_rosenbrock_ex.argtypes + [_dp]
+            L.mistra_chem_rosenbrock_flux_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [vp]
+            L.mistra_chem_rosenbrock_flux_cells_ex.argtypes = L.mistra_chem_rosenbrock_cells_ex.argtypes + [_dp]
+            L.mistra_chem_rosenbrock_flux_cells_device.argtypes = L.mistra_chem_rosenbrock_cells_device.argtypes + [vp]
         if hasattr(L, "mistra_chem_set_policy"):
             L.mistra_chem_set_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
             L.mistra_chem_check_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
@@ -729,6 +734,84 @@ def rosenbrock_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rto
 def rosenbrock_trace_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart=None, cap=256, ctrl=True, trace_d=None, trace_i=None):
     """rosenbrock_trace() with tolerances per cell as rosenbrock_cells takes them; a cell refused with -5 has n = 0 and its log rows untouched."""
     return _ros_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, (cap, ctrl, trace_d, trace_i))
+
+
+# ---- the reaction flux (include/mistra_chem.h: mistra_chem_rosenbrock_flux_ex / _device and their cells forms)
+def _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, cells):
+    """rosenbrock_flux (cells False: the shared pair) and rosenbrock_flux_cells (cells True: atol, rtol [ncell, ntol])"""
+    mid, name = _mech_id(mech)
+    nvar, nfix, nreact, _ = DIMS[name]
+    ip, rp, at, rt = _option_args(name, ipar, rpar, None if cells else atol, None if cells else rtol)
+    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
+    L = lib()
+    if _is_torch(var):
+        import torch
+        if not var.is_cuda:
+            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
+        init(var.device.index or 0)
+        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
+                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
+        ncell = var.numel() // nvar
+        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
+            raise MistraChemError("cell counts of var / fix / rconst differ")
+        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
+            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
+        if cells:
+            for x in (atol, rtol):
+                if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.ndim != 2 or x.shape[0] != ncell or x.device != var.device:
+                    raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
+            if atol.shape != rtol.shape:
+                raise MistraChemError("atol and rtol differ in shape")
+            tol = (atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]))
+        else:
+            tol = (at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp))
+        out = torch.empty_like(var)
+        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
+        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
+        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
+        flux = torch.empty((ncell, nreact), dtype=torch.float64, device=var.device)
+        stream = torch.cuda.current_stream(var.device).cuda_stream
+        entry = L.mistra_chem_rosenbrock_flux_cells_device if cells else L.mistra_chem_rosenbrock_flux_device
+        _check(entry(mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), *tol, *popts, out.data_ptr(),
+                     ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), None if hstart is None else hstart.data_ptr(), C.c_void_p(stream),
+                     flux.data_ptr()))
+        return IntegrateResult(out, ierr, stats), th, flux
+    if hstart is not None:
+        raise MistraChemError("hstart goes with the device entry: pass torch CUDA tensors (host buffers: rpar[2] is the first step size of every cell)")
+    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+    ncell = v.shape[0]
+    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
+    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
+    if cells:
+        a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
+        if a2.ndim != 2 or a2.shape[0] != ncell or r2.shape != a2.shape:
+            raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
+        tol = (a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]))
+    else:
+        tol = (at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp))
+    out = np.empty_like(v)
+    ierr = np.zeros(ncell, np.int32)
+    stats = np.zeros((ncell, 8), np.int32)
+    th = np.zeros((ncell, 3))
+    flux = np.zeros((ncell, nreact))
+    entry = L.mistra_chem_rosenbrock_flux_cells_ex if cells else L.mistra_chem_rosenbrock_flux_ex
+    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
+    _check(entry(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend), *tol, *popts,
+                 out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp), flux.ctypes.data_as(_dp)))
+    return IntegrateResult(out, ierr, stats), th, flux
+
+
+def rosenbrock_flux(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None, atol=None, rtol=None, hstart=None):
+    """rosenbrock() run by the kernel that also integrates every reaction's rate over the call -> rosenbrock's tuple + flux [ncell, NREACT]:
+    flux[r] = sum over the accepted steps of (0.5 * Direction * H) * (A_r(Y_n) + A_r(Y_n+1)), A_r the product Fun_x forms.  The first two results
+    are bit for bit rosenbrock()'s.  A refused call, and a call that makes no accepted step, return zeros.  Not for a user mechanism slot."""
+    return _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, False)
+
+
+def rosenbrock_flux_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart=None):
+    """rosenbrock_flux() with tolerances per cell as rosenbrock_cells takes them; a cell refused with -5 has a flux row of zeros."""
+    return _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, True)
 
 
 # ---- a series: several output times in one call (include/mistra_chem.h: mistra_chem_rosenbrock_series_ex / _device and their cells forms)

@@ -61,6 +61,9 @@ hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bo
 // method: IPAR(4) resolved, Ros3 included: the series kernel of that method, which reads a.opt and a.times
 template <class MT, int NT>
 hipError_t launch_series(int method, const KernelArgs& a, hipStream_t stream, bool* configured);
+// method: IPAR(4) resolved, Ros3 included: the flux kernel of that method, which reads a.opt and writes a.flux
+template <class MT, int NT>
+hipError_t launch_flux(int method, const KernelArgs& a, hipStream_t stream, bool* configured);
 
 // ---- ONE ROW PER MECHANISM: everything the entries below need to know about a compiled kernel.  gas, aer, tot, then the user slots this library was
 // built with (user_mechs.hpp: traits generated from the slots' tables at build time).  A user slot has the product, first-step-dump and options
@@ -78,16 +81,18 @@ struct MechDesc {
   hipError_t (*method)(int, const KernelArgs&, hipStream_t, bool*);        // Ros2, Ros4, Rodas3, Rodas4 (nullptr: not built)
   LaunchFn trace;                                                          // the step-control trace kernel (nullptr: not built)
   hipError_t (*series)(int, const KernelArgs&, hipStream_t, bool*);        // the series kernels, all five methods (nullptr: not built)
+  hipError_t (*flux)(int, const KernelArgs&, hipStream_t, bool*);          // the flux kernels, all five methods (nullptr: not built)
 };
 template <class MT, int NT>
 constexpr MechDesc builtin_mech(const char* name) {
   return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
-                  MT::MAX_TEMPS, false, &traits_match<MT>, &launch_ros3<MT, NT>, &launch_method<MT, NT>, &launch_ros_trace<MT, NT>, &launch_series<MT, NT>};
+                  MT::MAX_TEMPS, false, &traits_match<MT>, &launch_ros3<MT, NT>, &launch_method<MT, NT>, &launch_ros_trace<MT, NT>, &launch_series<MT, NT>,
+                  &launch_flux<MT, NT>};
 }
 template <class MT, int NT>
 constexpr MechDesc user_mech(const char* name) {
   return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
-                  MT::MAX_TEMPS, true, &traits_match<MT>, &launch_ros3<MT, NT>, nullptr, nullptr, nullptr};
+                  MT::MAX_TEMPS, true, &traits_match<MT>, &launch_ros3<MT, NT>, nullptr, nullptr, nullptr, nullptr};
 }
 constexpr int kBuiltinMechs = 3, kMaxMechs = 5;
 constexpr int kNumMechs = kBuiltinMechs + MISTRA_USER_MECHS;
@@ -677,6 +682,7 @@ struct MechState {
   DevBuf<int32_t> s_ierr, s_stats, s_sing;
   DevBuf<double> s_trd;                    // ... and of mistra_chem_rosenbrock_trace_ex: the records, the attempt counts, the per-species counts
   DevBuf<int32_t> s_tri, s_ntr, s_ctl;
+  DevBuf<double> s_flux;                   // ... and of mistra_chem_rosenbrock_flux_ex: the block's flux rows
   // where the zero-pivot rows of the LAST host-buffer call of this slot are (mistra_chem_singular_rows): cells [sing_start,
   // sing_start + sing_count) of the caller's batch in s_sing, or the one cell of the COMMON-block call in one_sing
   size_t sing_start = 0, sing_count = 0;
@@ -702,7 +708,7 @@ struct MechState {
     step_mem.release(); step_n = 0;
     s_hst.release(); s_tol.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
-    s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release();
+    s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release(); s_flux.release();
     sing_count = 0; sing_one = false;
     drive.release(); one.release();
     pend = PendingDrive{};      // (a step issued and never fetched dies with its buffers)
@@ -719,6 +725,7 @@ struct DeviceState {
   bool lds_method[kMaxMechs][6] = {};                 // ... and per kernel: the method kernels' [mechanism][IPAR(4)] (launch_ros_method)
   bool lds_trace[kMaxMechs] = {};                     //     and the step-control trace kernels' (launch_ros_trace)
   bool lds_series[kMaxMechs][6] = {};                 //     and the series kernels' [mechanism][IPAR(4)] (launch_ros_series)
+  bool lds_flux[kMaxMechs][6] = {};                   //     and the flux kernels' [mechanism][IPAR(4)] (launch_ros_flux)
   void release() {
     if (id >= 0) (void)hipSetDevice(id);
     for (auto& m : mech) m.release();
@@ -727,6 +734,8 @@ struct DeviceState {
       for (bool& c : m) c = false;
     for (bool& c : lds_trace) c = false;
     for (auto& m : lds_series)
+      for (bool& c : m) c = false;
+    for (auto& m : lds_flux)
       for (bool& c : m) c = false;
     id = -1;
   }
@@ -1064,6 +1073,8 @@ struct RosCall {
   const double *cell_atol = nullptr, *cell_rtol = nullptr;
   int ntol = 0;
   bool vector = false;            // IPAR(2) = 0: every entry of a row is read; else entry 0 alone
+  // mistra_chem_rosenbrock_flux_ex: every reaction's rate integrated over the call, the caller's HOST array [ncell][NREACT] for the whole batch
+  double* flux = nullptr;
 };
 struct CellTol {      // the per-cell tolerance arguments of a cells entry
   const double *atol, *rtol;
@@ -1132,6 +1143,18 @@ hipError_t launch_series(int method, const KernelArgs& a, hipStream_t stream, bo
   return hipErrorInvalidValue;
 }
 
+template <class MT, int NT>
+hipError_t launch_flux(int method, const KernelArgs& a, hipStream_t stream, bool* configured) {
+  switch (method) {
+    case kRos2: return launch_ros_flux<MT, NT, kRos2>(a, stream, configured);
+    case kRos3: return launch_ros_flux<MT, NT, kRos3>(a, stream, configured);
+    case kRos4: return launch_ros_flux<MT, NT, kRos4>(a, stream, configured);
+    case kRodas3: return launch_ros_flux<MT, NT, kRodas3>(a, stream, configured);
+    case kRodas4: return launch_ros_flux<MT, NT, kRodas4>(a, stream, configured);
+  }
+  return hipErrorInvalidValue;
+}
+
 int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, int method = kRos3) {
   const MechDesc& M = kMech[mech];
   hipError_t e = hipErrorInvalidValue;
@@ -1139,6 +1162,10 @@ int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, in
     if (!M.series) return fail_user_slot(mech, "series of Rosenbrock_x calls");
     if (method < kRos2 || method > kRodas4 || !a.opt || a.dump || a.prof || a.ntrace) return fail("no series kernel for this Rosenbrock method");
     e = M.series(method, a, stream, &D.lds_series[mech][method]);
+  } else if (a.flux) {      // the reaction flux: the flux kernel of the method, Ros3 included
+    if (!M.flux) return fail_user_slot(mech, "reaction-flux entries");
+    if (method < kRos2 || method > kRodas4 || !a.opt || a.dump || a.prof || a.ntrace) return fail("no flux kernel for this Rosenbrock method");
+    e = M.flux(method, a, stream, &D.lds_flux[mech][method]);
   } else if (a.ntrace) {      // the step-control trace kernel (Ros3 with options)
     if (!M.trace) return fail_user_slot(mech, "step-control trace");
     if (method != kRos3 || !a.opt || a.dump || a.prof) return fail("no trace kernel for this Rosenbrock method");
@@ -1175,6 +1202,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.tol_abs = nullptr; a.tol_rel = nullptr; a.tol_cell_stride = 0; a.tol_spec_stride = 0;      // (the cells entries set them)
   a.tol_cell_factor = 0.0; a.tol_cell_floor = 0.0;      // (policy_args sets them)
   a.times = nullptr; a.nleg = 0; a.carry_h = 0; a.leg_var = a.leg_ierr = a.leg_stats = a.leg_th = a.leg_h = 0;      // (the series entries set them)
+  a.flux = nullptr;      // (the flux entries set it)
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
@@ -1352,6 +1380,11 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
         HIP_TRY(hipMemcpy(S.s_ctl.p, call->ctrl + batch_start * nv, nc * nv * sizeof(int32_t), hipMemcpyHostToDevice));
     }
   }
+  const bool flux = call && call->flux;
+  if (flux) {      // every row is written by the kernel (a cell refused with -5: zeros): nothing goes up
+    HIP_TRY(S.s_flux.reserve(nc * nr));
+    a.flux = S.s_flux.p;
+  }
   if (hstart) {      // OPT-IN: the caller's first step size per cell (mistra_chem_integrate_hstart_ex)
     HIP_TRY(S.s_hst.reserve(nc));
     HIP_TRY(hipMemcpy(S.s_hst.p, hstart, nc * sizeof(double), hipMemcpyHostToDevice));
@@ -1397,6 +1430,7 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     }
     if (call->ctrl) HIP_TRY(hipMemcpy(call->ctrl + batch_start * nv, S.s_ctl.p, nc * nv * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
+  if (flux) HIP_TRY(hipMemcpy(call->flux + batch_start * nr, S.s_flux.p, nc * nr * sizeof(double), hipMemcpyDeviceToHost));
   if (t_h) {      // device: [ncell][2] (T, Hexit) then [ncell] (H)  ->  caller: [ncell][3]
     std::vector<double> h(nc * 3);
     HIP_TRY(hipMemcpy(h.data(), S.s_th.p, nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
@@ -2506,10 +2540,10 @@ int mistra_chem_method_table(int method, int* S, double* A15, double* C15, doubl
   return 0;
 }
 
-// mistra_chem_rosenbrock_ex and, with tr set (its trace members filled in), mistra_chem_rosenbrock_trace_ex
+// mistra_chem_rosenbrock_ex and, with tr set (its trace members filled in), mistra_chem_rosenbrock_trace_ex; flux set: mistra_chem_rosenbrock_flux_ex
 static int rosenbrock_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                            const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
-                           int32_t* stats, double* t_h, const RosCall* tr, const CellTol* ct = nullptr) {
+                           int32_t* stats, double* t_h, const RosCall* tr, const CellTol* ct = nullptr, double* flux = nullptr) {
   if (int rc = user_slot_method(mech, ipar)) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, ncell, true)) return rc;
@@ -2523,6 +2557,7 @@ static int rosenbrock_host(int mech, int ncell, const double* var_in, const doub
     call = decode_call(mech, ipar, rpar, atol, rtol, ct);
   }
   if (tr) { call.trace = true; call.cap = tr->cap; call.trace_d = tr->trace_d; call.trace_i = tr->trace_i; call.ntrace = tr->ntrace; call.ctrl = tr->ctrl; }
+  call.flux = flux;
   if (call.ierr != 1) {      // Rosenbrock_x returns before it touches Y or the statistics (gas.f:936-1053): a result, nothing is launched
     const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
     if (tr) std::fill(tr->ntrace, tr->ntrace + nc, 0);      // no attempt was made: the logs and ctrl stay as they are
@@ -2530,6 +2565,7 @@ static int rosenbrock_host(int mech, int ncell, const double* var_in, const doub
     if (ierr) std::fill(ierr, ierr + nc, (int32_t)call.ierr);
     if (stats) std::fill(stats, stats + nc * 8, 0);
     if (t_h) std::fill(t_h, t_h + nc * 3, 0.0);
+    if (flux) std::fill(flux, flux + nc * (size_t)kMech[mech].dims.nreact, 0.0);
     return 0;
   }
   return integrate_host(mech, ncell, var_in, fix, rconst, nullptr, tstart, tend, var_out, ierr, stats, t_h, nullptr, &call);
@@ -2552,11 +2588,11 @@ int mistra_chem_rosenbrock_trace_ex(int mech, int ncell, const double* var_in, c
   return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, &tr);
 }
 
-// mistra_chem_rosenbrock_device and, with tr set (device arrays), mistra_chem_rosenbrock_trace_device
+// mistra_chem_rosenbrock_device and, with tr set (device arrays), mistra_chem_rosenbrock_trace_device; d_flux set: mistra_chem_rosenbrock_flux_device
 static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                 double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
                                 int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream, const RosCall* tr,
-                                const CellTol* ct = nullptr) {
+                                const CellTol* ct = nullptr, double* d_flux = nullptr) {
   if (int rc = user_slot_method(mech, ipar)) return rc;
   if (ncell == 0) return check_call(mech, 0, true);
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
@@ -2580,6 +2616,7 @@ static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, con
     HIP_TRY(hipMemsetAsync(d_stats, 0, nc * 8 * sizeof(int32_t), st));
     if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nc * 2 * sizeof(double), st));
     if (tr) HIP_TRY(hipMemsetAsync(tr->ntrace, 0, nc * sizeof(int32_t), st));      // no attempt was made: the logs and ctrl stay as they are
+    if (d_flux) HIP_TRY(hipMemsetAsync(d_flux, 0, nc * (size_t)kMech[mech].dims.nreact * sizeof(double), st));
     return 0;
   }
   RosCallRing& R = t.S->call_ring;
@@ -2601,6 +2638,7 @@ static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, con
     a.tol_spec_stride = call.vector ? 1 : 0;
   }
   if (tr) { a.trace_cap = tr->cap; a.trace_d = tr->trace_d; a.trace_i = tr->trace_i; a.ntrace = tr->ntrace; a.ctrl = tr->ctrl; }
+  a.flux = d_flux;
   const int rc = launch(*t.D, mech, a, st, call.method);
   if (hipEventRecord(R.ev[i], st) == hipSuccess) R.pending[i] = true;      // (also behind a failed launch: the copy is queued)
   return rc;
@@ -2672,6 +2710,50 @@ int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double*
   tr.cap = cap; tr.trace_d = d_trace_d; tr.trace_i = d_trace_i; tr.ntrace = d_ntrace; tr.ctrl = d_ctrl;
   return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
                               d_hstart, hip_stream, &tr, &ct);
+}
+
+// ---- the reaction flux: Rosenbrock_x as above, plus every reaction's rate integrated over the call (kernel VARIANT 6).  The same two
+//      paths with one more output.  Checked before anything touches a device: the mechanism (no user slot) and the flux pointer.
+static int check_flux(int mech, const void* flux) {
+  if (int rc = builtin_only(mech, "reaction-flux entries")) return rc;
+  if (!flux) return fail("null flux pointer (flux: [ncell][NREACT])");
+  return 0;
+}
+
+int mistra_chem_rosenbrock_flux_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                   const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
+                                   int32_t* stats, double* t_h, double* flux) {
+  if (int rc = check_flux(mech, flux)) return rc;
+  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, nullptr, flux);
+}
+
+int mistra_chem_rosenbrock_flux_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                       double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
+                                       double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
+                                       void* hip_stream, double* d_flux) {
+  if (int rc = check_flux(mech, d_flux)) return rc;
+  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                              d_hstart, hip_stream, nullptr, nullptr, d_flux);
+}
+
+int mistra_chem_rosenbrock_flux_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart,
+                                         double tend, const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar,
+                                         double* var_out, int32_t* ierr, int32_t* stats, double* t_h, double* flux) {
+  if (int rc = check_flux(mech, flux)) return rc;
+  const CellTol ct{atol, rtol, ntol};
+  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
+  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, &ct, flux);
+}
+
+int mistra_chem_rosenbrock_flux_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                             double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar,
+                                             const int32_t* ipar, double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                             const double* d_hstart, void* hip_stream, double* d_flux) {
+  if (int rc = check_flux(mech, d_flux)) return rc;
+  const CellTol ct{d_atol, d_rtol, ntol};
+  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
+  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                              d_hstart, hip_stream, nullptr, &ct, d_flux);
 }
 
 // ---- series: nleg calls of Rosenbrock_x over times[0 .. nleg] in one launch, the state on chip from leg to leg (kernel VARIANT 5).  One path for the

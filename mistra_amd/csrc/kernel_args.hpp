@@ -111,6 +111,10 @@ struct KernelArgs {
   int32_t nleg;
   int32_t carry_h;             // /= 0: a later leg's first step is the previous leg's Hexit of the cell where that is > 0, else the options' Hstart
   int64_t leg_var, leg_ierr, leg_stats, leg_th, leg_h;
+  // the reaction flux (kernel VARIANT 6, ros_flux_kernel.hip; mistra_chem_rosenbrock_flux_ex / _device and their cells forms): [ncell][NREACT], every
+  // reaction's rate integrated over the call, written once per cell when it leaves (a cell refused with -5: +0.0).  Read by the flux kernels only; null
+  // everywhere else (capi.cpp: make_args).
+  double* flux;
 };
 
 }  // namespace mistra

@@ -1191,12 +1191,15 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // 5 = a series (ros_series_kernel.hip; mistra_chem_rosenbrock_series_ex / _device): variant 3 with the part from the step-control set-up to the
 // results inside a loop over a.nleg legs, leg k one call of Rosenbrock_x from a.times[k] to a.times[k+1] on the state leg k-1 left, its results in
 // block k of the output arrays.  Everything the loop adds sits behind `if constexpr (SERIES)`; for the others the loop is one pass.
+// 6 = the reaction flux (ros_flux_kernel.hip; mistra_chem_rosenbrock_flux_ex / _device): variant 3 of any of the five methods that also integrates every
+// reaction's rate over the call by the trapezoid rule on the accepted states and leaves one [NREACT] row per cell in a.flux.
+// Everything it adds sits behind `if constexpr (FLUX)`.
 // METHOD (variant 3 only): the Rosenbrock method, IPAR(4) of Rosenbrock_x (ros_methods.hpp).  Ros3 is the kernel as it was; Ros2, Ros4, Rodas3
 // and Rodas4 (the method kernels, instantiated by ros_method_kernel.hip in translation units of their own) differ in the stage loop, in the
 // number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
 template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
-  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, OPT = VARIANT == 3 || TRACE || SERIES;
+  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, FLUX = VARIANT == 6, OPT = VARIANT == 3 || TRACE || SERIES || FLUX;
   static_assert(!TRACE || METHOD == kRos3, "the step-control trace is a Ros3 instantiation (ros_trace_kernel.hip)");
   static_assert(METHOD == kRos3 || (OPT && METHOD >= kRos2 && METHOD <= kRodas4), "the method kernels are options instantiations");
   constexpr double kGamma1 = METHOD == kRos3 ? kRosGamma1 : kRosMethod<METHOD>.Gamma[0];
@@ -1357,6 +1360,13 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
           if (a.h_last) GM_(a.h_last)[cell] = 0.0;
           if constexpr (TRACE) GM_(a.ntrace)[cell] = 0;
         }
+        if constexpr (FLUX) {      // no step was made: the cell's row is +0.0
+#pragma unroll
+          for (int q = 0; q < RPT; q++) {
+            const int r = q * NT + t;
+            if (r < NREACT) GM_(a.flux)[(size_t)cell * NREACT + r] = 0.0;
+          }
+        }
         return;
       }
     }
@@ -1499,6 +1509,18 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       p = p * f1[q];
       p = p * f2[q];
       AB[slot[q]] = p;            // a slot without a reaction (rct = 0) writes a spare cell: no branch
+    }
+  };
+  // VARIANT 6: A(r) of this thread's reactions r = q*NT + t at the state X holds, as a_products forms them (the same operands in the same order, so the
+  // same bits), into registers instead of the product array.  Reads the factor words and rate constants the last Fun_x of the thread fetched.
+  [[maybe_unused]] auto flux_products = [&](double (&p)[RPT]) {
+#pragma unroll
+    for (int q = 0; q < RPT; q++) {
+      uint64_t w = ffac[q];
+      asm volatile("" : "+v"(w));
+      double v = rct[q] * X[w & 0xFFFFu];
+      v = v * X[(w >> 16) & 0xFFFFu];
+      p[q] = v * X[(w >> 32) & 0xFFFFu];
     }
   };
   auto load_jfac = [&](uint64_t (&jfac)[3 * RPT]) {
@@ -1840,6 +1862,25 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       if (fabs(H0) <= 10.0 * Roundoff) H0 = 1.0e-5;
       Hset(H0);
     }
+    // VARIANT 6: the running sum and A(r) at the last accepted state of this thread's reactions (thread-private: r = q*NT + t in every step), half the
+    // signed size of the accepted step that is still open (its end state's A is formed by the next step's first Fun_x, or behind the loop)
+    [[maybe_unused]] double fl_sum[RPT], fl_prev[RPT];
+    [[maybe_unused]] double fl_half = 0.0;
+    [[maybe_unused]] bool fl_open = false;
+    if constexpr (FLUX) {
+#pragma unroll
+      for (int q = 0; q < RPT; q++) { fl_sum[q] = 0.0; fl_prev[q] = 0.0; }
+    }
+    [[maybe_unused]] auto flux_close = [&]() {      // X holds the state the open step ended on (or, with none open, the call's first state)
+      double pa[RPT];
+      flux_products(pa);
+#pragma unroll
+      for (int q = 0; q < RPT; q++) {
+        if (fl_open) fl_sum[q] = fl_sum[q] + fl_half * (fl_prev[q] + pa[q]);
+        fl_prev[q] = pa[q];
+      }
+      fl_open = false;
+    };
     bool RejectLastH = false, RejectMoreH = false;
     int nfun = 0, njac = 0, nstp = 0, nacc = 0, nrej = 0, ndec = 0, nsol = 0, nsng = 0;
     int ierr = 1;
@@ -1881,6 +1922,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         lap(0);
         jac();
       }
+      if constexpr (FLUX) flux_close();      // X is Y_n until stage 2 stores into it, behind ros_PrepareMatrix's barriers
       // ros_FunTimeDerivative_x (gas.f:1375): Fun_x does not depend on T and RCONST is frozen, so
       // dFdT = (1/Delta)*(Fun - Fcn0) is an exact +0.0; the evaluation is skipped, its count and its "+ HG*0.0" are kept.
       if constexpr (OPT) nfun += autonomous ? 1 : 2;      // Autonomous: no ros_FunTimeDerivative_x, no Fun call of its own (gas.f:1221)
@@ -2112,6 +2154,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
           RejectLastH = false;
           RejectMoreH = false;
           Hset(Hnew);
+          if constexpr (FLUX) { fl_half = 0.5 * dh; fl_open = true; }
           accepted = true;
         } else {
           if (RejectMoreH) Hnew = H * facrej();
@@ -2124,6 +2167,23 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       if (ierr < 0) break;
     }
 
+    // VARIANT 6: the last accepted step is still open on a normal return and on -6 / -7 (on -8 the failing step's own Fun_x has closed it): one more
+    // evaluation of the A products, at the state the call returns.  Not a Fun_x call, not counted.  fl_open is uniform over the workgroup; every read
+    // of X by another thread lies in front of a barrier this thread has passed (the error norm's).
+    if constexpr (FLUX) {
+      if (fl_open) {
+        load_ffac();
+        if constexpr (RCT_PER_USE) load_rct(true);
+        store_x(y);
+        lds_barrier();
+        flux_close();
+      }
+#pragma unroll
+      for (int q = 0; q < RPT; q++) {
+        const int r = q * NT + t;
+        if (r < NREACT) GM_(a.flux)[(size_t)cell * NREACT + r] = fl_sum[q];
+      }
+    }
     // ---- results
     {
       int tt = t;

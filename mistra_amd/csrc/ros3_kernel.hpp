@@ -110,4 +110,10 @@ hipError_t launch_ros_trace(const KernelArgs& a, hipStream_t stream, bool* lds_c
 template <class MT, int NT, int METHOD>
 hipError_t launch_ros_series(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
 
+// The flux kernels (VARIANT 6: the options kernel of any of the five methods that also integrates every reaction's rate over the call;
+// kernel_args.hpp: flux): a.opt and a.flux must be set.  One explicit specialisation per <mechanism, method>, each in a translation unit of its own
+// (ros_flux_kernel.hip).
+template <class MT, int NT, int METHOD>
+hipError_t launch_ros_flux(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
+
 }  // namespace mistra

@@ -54,6 +54,21 @@ class MechTables:
     def nspec(self):
         return self.nvar + self.nfix
 
+    def stoich(self):
+        """S [NVAR, NREACT]: Vdot(i) = sum over the terms of species i of vd_coef * A(vd_idx) (Fun_x's signed sums), as a dense matrix"""
+        s = np.zeros((self.nvar, self.nreact))
+        np.add.at(s, (np.repeat(np.arange(self.nvar), np.diff(self.vd_ptr)), self.vd_idx), self.vd_coef)
+        return s
+
+    def products(self, var, fix, rconst):
+        """A [NREACT] = RCT(r) times the reaction's factors out of X = V | F | constants, multiplied in the table's order (Fun_x's products)"""
+        x = np.concatenate([np.asarray(var, np.float64), np.asarray(fix, np.float64), self.consts])
+        a = np.array(rconst, np.float64)
+        for k in range(int(np.diff(self.a_ptr).max())):
+            has = np.diff(self.a_ptr) > k
+            a[has] = a[has] * x[self.a_fac[self.a_ptr[:-1][has] + k]]
+        return a
+
 
 _cache = {}
 

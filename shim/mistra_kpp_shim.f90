@@ -49,6 +49,12 @@
 ! previous leg's HEXIT of the cell where that is > 0 instead of RPAR(3).  ros_ErrorMsg_x's lines go to unit 6 for every failed leg and cell, in leg order.
 !     SUBROUTINE ROSENBROCK_BATCH_SERIES_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
 !     SUBROUTINE ROSENBROCK_BATCH_SERIES_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+!
+! THE REACTION FLUX (mistra_chem_rosenbrock_flux_ex; INTEGRATION.md 4n): ROSENBROCK_BATCH_x / ROSENBROCK_BATCH_CELLS_x with one more result behind their
+! argument lists, FLUX(NREACT,NCELL): every reaction's rate integrated over the call by the trapezoid rule on the accepted states.  Everything else is what
+! those entries return, bit for bit, ros_ErrorMsg_x's lines and the zero-pivot warnings included; a refused cell's FLUX column is zero.
+!     SUBROUTINE ROSENBROCK_BATCH_FLUX_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
+!     SUBROUTINE ROSENBROCK_BATCH_FLUX_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
 module mistra_chem_c_api
   use iso_c_binding
   implicit none
@@ -131,6 +137,28 @@ module mistra_chem_c_api
        integer(c_int32_t) :: ierr(*), stats(*)
        integer(c_int) :: rc
      end function mistra_chem_rosenbrock_cells_ex
+     function mistra_chem_rosenbrock_flux_ex(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, flux) &
+          bind(C, name="mistra_chem_rosenbrock_flux_ex") result(rc)
+       import :: c_int, c_double, c_int32_t
+       integer(c_int), value :: mech, ncell
+       real(c_double), value :: tstart, tend
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_out(*), t_h(*), flux(*)
+       real(c_double), intent(in) :: atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_flux_ex
+     function mistra_chem_rosenbrock_flux_cells_ex(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, ntol, rpar, ipar, var_out, ierr, stats, t_h, &
+          flux) bind(C, name="mistra_chem_rosenbrock_flux_cells_ex") result(rc)
+       import :: c_int, c_double, c_int32_t
+       integer(c_int), value :: mech, ncell, ntol
+       real(c_double), value :: tstart, tend
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_out(*), t_h(*), flux(*)
+       real(c_double), intent(in) :: atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_flux_cells_ex
      function mistra_chem_rosenbrock_series_ex(mech, ncell, var_in, fix, rconst, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, &
           stats, t_h) bind(C, name="mistra_chem_rosenbrock_series_ex") result(rc)
        import :: c_int, c_double, c_int32_t, c_ptr
@@ -368,9 +396,11 @@ contains
   ! Rosenbrock_x for NCELL cells with the call's own options; the messages in cell order, as a serial loop over Rosenbrock_x would have written them
   ! (ros_PrepareMatrix_x's warnings, then ros_ErrorMsg_x's lines: a refusal is reported at T = Tstart, H = 0 as Rosenbrock_x does, gas.f:955)
   ! NTOL present: ATOL / RTOL hold a row of NTOL entries per cell (ROSENBROCK_BATCH_CELLS_x)
-  subroutine rosenbrock_batch(mech, sfx, NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL)
+  ! FLUX present: the flux entries, which return FLUX(NREACT,NCELL) besides (ROSENBROCK_BATCH_FLUX_x, ROSENBROCK_BATCH_FLUX_CELLS_x)
+  subroutine rosenbrock_batch(mech, sfx, NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL, FLUX)
     integer, intent(in) :: mech, NCELL
     integer, intent(in), optional :: NTOL
+    real(c_double), optional :: FLUX(*)
     character(len=1), intent(in) :: sfx
     real(c_double) :: VAR(*), FIX(*), RCONST(*), TEXIT(NCELL), HEXIT(NCELL)
     real(c_double), intent(in) :: TSTART, TEND, ATOL(*), RTOL(*), RPAR(20)
@@ -381,7 +411,13 @@ contains
     integer :: k, i
     if (NCELL <= 0) return
     allocate (th(3, NCELL))
-    if (present(NTOL)) then
+    if (present(FLUX) .and. present(NTOL)) then
+       if (mistra_chem_rosenbrock_flux_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, int(NTOL, c_int), RPAR, IPAR, &
+            VAR, IERR, ISTAT, th, FLUX) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_FLUX_CELLS_'//sfx)
+    else if (present(FLUX)) then
+       if (mistra_chem_rosenbrock_flux_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, VAR, IERR, ISTAT, th, &
+            FLUX) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_FLUX_'//sfx)
+    else if (present(NTOL)) then
        if (mistra_chem_rosenbrock_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, int(NTOL, c_int), RPAR, IPAR, &
             VAR, IERR, ISTAT, th) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_CELLS_'//sfx)
     else
@@ -855,3 +891,64 @@ subroutine ROSENBROCK_BATCH_SERIES_CELLS_t(NCELL, VAR, FIX, RCONST, NLEG, TIMES,
   integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
   call rosenbrock_series(2, 't', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL)
 end subroutine ROSENBROCK_BATCH_SERIES_CELLS_t
+
+! ---- the reaction flux: ROSENBROCK_BATCH_x / ROSENBROCK_BATCH_CELLS_x with FLUX(NREACT,NCELL) behind their argument lists
+subroutine ROSENBROCK_BATCH_FLUX_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), TEXIT(*), HEXIT(*), FLUX(331, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(0, 'g', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX=FLUX)
+end subroutine ROSENBROCK_BATCH_FLUX_g
+
+subroutine ROSENBROCK_BATCH_FLUX_CELLS_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), TEXIT(*), HEXIT(*), FLUX(331, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(0, 'g', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL, FLUX)
+end subroutine ROSENBROCK_BATCH_FLUX_CELLS_g
+
+subroutine ROSENBROCK_BATCH_FLUX_a(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), TEXIT(*), HEXIT(*), FLUX(979, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(1, 'a', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX=FLUX)
+end subroutine ROSENBROCK_BATCH_FLUX_a
+
+subroutine ROSENBROCK_BATCH_FLUX_CELLS_a(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), TEXIT(*), HEXIT(*), FLUX(979, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(1, 'a', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL, FLUX)
+end subroutine ROSENBROCK_BATCH_FLUX_CELLS_a
+
+subroutine ROSENBROCK_BATCH_FLUX_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), TEXIT(*), HEXIT(*), FLUX(1627, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX=FLUX)
+end subroutine ROSENBROCK_BATCH_FLUX_t
+
+subroutine ROSENBROCK_BATCH_FLUX_CELLS_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), TEXIT(*), HEXIT(*), FLUX(1627, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
+  call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL, FLUX)
+end subroutine ROSENBROCK_BATCH_FLUX_CELLS_t

@@ -7,6 +7,7 @@ mistra_amd/csrc/ros3_kernel.hip at two commits), and the resources of the method
                                                     from the code object's metadata, compiled here as the build compiles them
     python tools/isa_compare.py --series            per series unit (SERIES_UNITS): the same figures of the series kernel (VARIANT 5) beside its VARIANT 3
                                                     sibling's — the product unit's options kernel for Ros3, the method unit's for the other four
+    python tools/isa_compare.py --flux              per flux unit (FLUX_UNITS): the same table for the flux kernel (VARIANT 6)
 
 A kernel's mangled name carries its template arguments: the METHOD parameter added to ros3_integrate_kernel (default Ros3 = 2) is cut out of the
 new listing's names before the comparison; nothing else is normalised."""
@@ -83,12 +84,13 @@ def _kernels(path):
     return out
 
 
-def series():
+def series(variant=5, what="series"):
     from mistra_amd import build as B
+    units, source, flags_of = (B.SERIES_UNITS, B.SERIES_SOURCE, B.series_flags) if variant == 5 else (B.FLUX_UNITS, B.FLUX_SOURCE, B.flux_flags)
     names = {1: "Ros2", 2: "Ros3", 3: "Ros4", 4: "Rodas3", 5: "Rodas4"}
     mechs = ("gas", "aer", "tot")
     cols = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")
-    print("%-4s %-7s | %-40s | %s" % ("mech", "method", "VARIANT 3 (the options kernel)", "VARIANT 5 (the series kernel)"))
+    print("%-4s %-7s | %-40s | %s" % ("mech", "method", "VARIANT 3 (the options kernel)", "VARIANT %d (the %s kernel)" % (variant, what)))
     print("%-4s %-7s | %5s %5s %8s %7s %10s | %5s %5s %8s %7s %10s   (LDS: dynamic, LdsLayout<MT, NT>::TOTAL doubles, the same for both)" %
           (("", "") + ("VGPRs", "SGPRs", "scratch", "spilled", "static LDS") * 2))
     with tempfile.TemporaryDirectory() as tmp:
@@ -98,12 +100,12 @@ def series():
             subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
             return _kernels(s)
         product = listing("ros3_kernel.hip", [])
-        for mech, method in B.SERIES_UNITS:
+        for mech, method in units:
             if method == 2:
                 sib = [k for n, k in product if re.search(r"ros3_integrate_kernelINS_\d+%sTraitsELi\d+ELi3ELi2E" % mechs[mech].capitalize(), n)]
             else:
                 sib = [k for n, k in listing(B.METHOD_SOURCE, B.method_flags(mech, method)) if "ros3_integrate_kernel" in n]
-            new = [k for n, k in listing(B.SERIES_SOURCE, B.series_flags(mech, method)) if "ros3_integrate_kernel" in n]
+            new = [k for n, k in listing(source, flags_of(mech, method)) if "ros3_integrate_kernel" in n]
             assert len(sib) == 1 and len(new) == 1, (mech, method, len(sib), len(new))
             print("%-4s %-7s | %5d %5d %8d %7d %10d | %5d %5d %8d %7d %10d" % ((mechs[mech], names[method]) + tuple(sib[0][c] for c in cols) + tuple(new[0][c] for c in cols)))
 
@@ -113,5 +115,7 @@ if __name__ == "__main__":
         methods()
     elif "--series" in sys.argv:
         series()
+    elif "--flux" in sys.argv:
+        series(6, "flux")
     else:
         sys.exit(0 if compare(sys.argv[1], sys.argv[2]) else 1)
