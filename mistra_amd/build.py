@@ -3,6 +3,7 @@
 `python -m mistra_amd.build` or `build_lib()`.  hipcc cross-compiles for gfx950 without a GPU present.
 The library is written to mistra_amd/lib/ (git-ignored, shipped to the GPU box with the working tree).
 """
+import collections
 import os
 import shutil
 import subprocess
@@ -20,29 +21,26 @@ LIB_NOSLOTS = os.path.join(LIBDIR, "libmistra_chem_noslots.so")
 ARCH = "gfx950"
 # -ffp-contract=off: one rounding per multiply and per add, as in the reference built without FMA contraction
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
-SOURCES = ["mech_tables.cpp", "schedule.cpp", "capi.cpp", "ros3_kernel.hip", "rates.hip", "pack.hip"]
-# the method kernels (Ros2, Ros4, Rodas3, Rodas4 of Rosenbrock_x on gas, aer, tot): ros_method_kernel.hip once per (mechanism, IPAR(4)), each a
-# translation unit of its own — the product kernels' unit compiles as it does without them — and side by side
-METHOD_SOURCE = "ros_method_kernel.hip"
-METHOD_UNITS = [(mech, method) for mech in (0, 1, 2) for method in (1, 3, 4, 5)]
-# the step-control trace kernels (kernel VARIANT 4, Ros3): ros_trace_kernel.hip once per mechanism, units of their own for the same reason.  In the
-# unit lists below a trace unit is (mechanism, None).
-TRACE_SOURCE = "ros_trace_kernel.hip"
-TRACE_UNITS = [(mech, None) for mech in (0, 1, 2)]
-# the series kernels (kernel VARIANT 5: a loop over the legs of a series around the options kernel of each of the five methods): ros_series_kernel.hip
-# once per (mechanism, IPAR(4)), units of their own for the same reason.  In the unit lists below a series unit is ("series", (mechanism, method)).
-SERIES_SOURCE = "ros_series_kernel.hip"
-SERIES_UNITS = [(mech, method) for mech in (0, 1, 2) for method in (1, 2, 3, 4, 5)]
-# the flux kernels (kernel VARIANT 6: the options kernel of each of the five methods that also integrates every reaction's rate over the call):
-# ros_flux_kernel.hip once per (mechanism, IPAR(4)), units of their own for the same reason.  In the unit lists below a flux unit is
-# ("flux", (mechanism, method)).
-FLUX_SOURCE = "ros_flux_kernel.hip"
-FLUX_UNITS = [(mech, method) for mech in (0, 1, 2) for method in (1, 2, 3, 4, 5)]
-# the user mechanism slots (mechanism ids 3 and 4): MISTRA_USER_MECHS = at most two table paths separated by colons, default the two demo tables
-# (tools/derive_mech.py cuts them from gas and aer), empty = a library without user slots.  Per slot user_traits_gen (a host program built from the
-# schedule compiler) writes the traits header into the build directory and ros_user_kernel.hip is compiled against it, a unit of its own for the same
-# reason.  In the unit lists below a user unit is ("user", slot).
+SOURCES = ["mech_tables.cpp", "schedule.cpp", "capi.cpp", "rates.hip", "pack.hip"]
+# ---- THE KERNEL UNITS: every translation unit that holds ros3_integrate_kernel instantiations, as one list of uniform records.  Each is a unit of its
+# own because the non-inlined device functions the kernels share are compiled once per unit, under the register budget of all kernels in it: the product
+# kernels' unit compiles as it does without the others, and they side by side.
+#   Unit("product", None, None)      ros3_kernel.hip: the product, phase-timing, first-step-dump and options (Ros3) kernels of gas, aer and tot
+#   Unit(variant, mech, method)      ros_unit_kernel.hip once per kernel VARIANT 3 .. 6 (ros3_kernel.hip), mechanism 0 gas | 1 aer | 2 tot and IPAR(4):
+#                                    3 the method kernels (Ros2, Ros4, Rodas3, Rodas4; Ros3 with options is in the product unit), 4 the step-control trace
+#                                    (Ros3 only), 5 the series kernels and 6 the flux kernels (all five methods)
+#   Unit("user", slot, None)         ros_user_kernel.hip once per user mechanism slot (mechanism ids 3 and 4), against the slot's generated traits header
+# MISTRA_USER_MECHS = at most two table paths separated by colons, default the two demo tables (tools/derive_mech.py cuts them from gas and aer), empty =
+# a library without user slots.  Per slot user_traits_gen (a host program built from the schedule compiler) writes the traits header into the build
+# directory.
+Unit = collections.namedtuple("Unit", "variant mech method")
+PRODUCT = Unit("product", None, None)
+PRODUCT_SOURCE = "ros3_kernel.hip"
+UNIT_SOURCE = "ros_unit_kernel.hip"
 USER_SOURCE = "ros_user_kernel.hip"
+ROS3 = 2
+VARIANT_METHODS = {3: (1, 3, 4, 5), 4: (ROS3,), 5: (1, 2, 3, 4, 5), 6: (1, 2, 3, 4, 5)}
+VARIANT_UNITS = [Unit(v, mech, method) for v, methods in VARIANT_METHODS.items() for mech in (0, 1, 2) for method in methods]
 USER_GEN_SOURCES = ["user_traits_gen.cpp", "schedule.cpp", "mech_tables.cpp"]
 USER_DEFAULT = [os.path.join(PKG, "mech", "demo_g.mech"), os.path.join(PKG, "mech", "demo_a.mech")]
 MAX_USER_MECHS = 2
@@ -122,34 +120,29 @@ def prepare_user_mechs(force=False, verbose=False):
     return len(tables), files
 
 
-def method_flags(mech, method):
-    if mech == "user":
-        return ["-DMISTRA_USER_SLOT=%d" % method, "-DMISTRA_USER_MECHS=%d" % (method + 1), "-I" + OBJDIR]
-    if mech == "series":
-        return series_flags(*method)
-    if mech == "flux":
-        return flux_flags(*method)
-    if method is None:
-        return ["-DMISTRA_TRACE_MECH=%d" % mech]
-    return ["-DMISTRA_METHOD_MECH=%d" % mech, "-DMISTRA_METHOD=%d" % method]
+def kernel_units(n_user):
+    """The kernel units of a library with n_user user slots: what build_lib compiles and checks, what tools/isa_compare.py lists."""
+    return [PRODUCT] + VARIANT_UNITS + [Unit("user", slot, None) for slot in range(n_user)]
 
 
-def series_flags(mech, method):
-    return ["-DMISTRA_SERIES_MECH=%d" % mech, "-DMISTRA_SERIES_METHOD=%d" % method]
+def unit_build(unit):
+    """-> (source file, object name, flags) of a kernel unit.  Raises for a unit that does not exist: a VARIANT 3 unit of Ros3 (that kernel lives
+    in the product unit), a trace unit of another method, a mechanism, method or slot out of range."""
+    variant, mech, method = unit
+    if unit == PRODUCT:
+        return PRODUCT_SOURCE, "ros3_kernel.o", []
+    if variant == "user" and mech in range(MAX_USER_MECHS) and method is None:
+        return USER_SOURCE, "ros_user_%d.o" % mech, ["-DMISTRA_USER_SLOT=%d" % mech, "-DMISTRA_USER_MECHS=%d" % (mech + 1), "-I" + OBJDIR]
+    if variant not in VARIANT_METHODS or mech not in (0, 1, 2) or method not in VARIANT_METHODS[variant]:
+        raise ValueError("no kernel unit %r: VARIANT -> methods %r on mechanisms 0 .. 2, the product unit, user slots 0 .. %d" %
+                         (tuple(unit), VARIANT_METHODS, MAX_USER_MECHS - 1))
+    return UNIT_SOURCE, "ros_unit_%d_%d_%d.o" % unit, ["-DMISTRA_UNIT_VARIANT=%d" % variant, "-DMISTRA_UNIT_MECH=%d" % mech, "-DMISTRA_UNIT_METHOD=%d" % method]
 
 
-def flux_flags(mech, method):
-    return ["-DMISTRA_FLUX_MECH=%d" % mech, "-DMISTRA_FLUX_METHOD=%d" % method]
-
-
-def unit_source(unit):
-    if unit[0] == "user":
-        return USER_SOURCE
-    if unit[0] == "series":
-        return SERIES_SOURCE
-    if unit[0] == "flux":
-        return FLUX_SOURCE
-    return TRACE_SOURCE if unit[1] is None else METHOD_SOURCE
+def unit_listing_cmd(unit, out):
+    """-> the command that writes the gfx950 assembly of a kernel unit's device code to `out`, compiled as the build compiles it"""
+    src, _, flags = unit_build(unit)
+    return [hipcc(), "--offload-arch=" + ARCH] + [f for f in COMMON if f != "-fPIC"] + flags + ["-S", "--offload-device-only", os.path.join(CSRC, src), "-o", out]
 
 
 def _jobs():
@@ -170,6 +163,12 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _run(cmd, verbose=False):
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+
+
 def build_lib(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(OBJDIR, exist_ok=True)
@@ -179,16 +178,14 @@ def build_lib(force=False, verbose=False):
     headers.append(os.path.abspath(__file__))
     from concurrent.futures import ThreadPoolExecutor
     objs, cmds = [], []
-    kernel_src = os.path.join(CSRC, "ros3_kernel.hip")
+    kernel_src = os.path.join(CSRC, PRODUCT_SOURCE)
     n_user, user_files = prepare_user_mechs(force, verbose)
-    user_units = [("user", slot) for slot in range(n_user)]
+    kunits = kernel_units(n_user)
+    user_objs = {unit_build(u)[1] for u in kunits if u.variant == "user"}
     units = [(src, os.path.splitext(src)[0] + ".o", ["-DMISTRA_USER_MECHS=%d" % n_user, "-I" + OBJDIR] if src == "capi.cpp" else [],
               user_files if src == "capi.cpp" else []) for src in SOURCES]
-    units += [(METHOD_SOURCE, "ros_method_%d_%d.o" % u, method_flags(*u), [kernel_src]) for u in METHOD_UNITS]      # (the unit includes ros3_kernel.hip)
-    units += [(TRACE_SOURCE, "ros_trace_%d.o" % u[0], method_flags(*u), [kernel_src]) for u in TRACE_UNITS]
-    units += [(USER_SOURCE, "ros_user_%d.o" % u[1], method_flags(*u), [kernel_src] + user_files) for u in user_units]
-    units += [(SERIES_SOURCE, "ros_series_%d_%d.o" % u, series_flags(*u), [kernel_src]) for u in SERIES_UNITS]
-    units += [(FLUX_SOURCE, "ros_flux_%d_%d.o" % u, flux_flags(*u), [kernel_src]) for u in FLUX_UNITS]
+    # (every kernel unit but the product's includes ros3_kernel.hip; a user slot's its generated traits header too)
+    units += [unit_build(u) + (([] if u == PRODUCT else [kernel_src]) + (user_files if u.variant == "user" else []),) for u in kunits]
     if n_user:
         units.append(("capi.cpp", "capi_noslots.o", ["-DMISTRA_USER_MECHS=0", "-I" + OBJDIR], []))
     for src, name, flags, deps in units:
@@ -201,32 +198,22 @@ def build_lib(force=False, verbose=False):
                 cmd += ["-Rpass-analysis=kernel-resource-usage"] if verbose else []
             cmds.append(cmd)
     with ThreadPoolExecutor(_jobs()) as pool:
-        def compile_one(cmd):
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.run(cmd, check=True)
-        list(pool.map(compile_one, cmds))
-    noslots_objs = [o for o in objs if not os.path.basename(o).startswith("ros_user_") and os.path.basename(o) != "capi.o"] if n_user else []
+        list(pool.map(lambda cmd: _run(cmd, verbose), cmds))
+    noslots_objs = [o for o in objs if os.path.basename(o) not in user_objs and os.path.basename(o) != "capi.o"] if n_user else []
     objs = [o for o in objs if os.path.basename(o) != "capi_noslots.o"]
     if force or _stale(LIB, objs) or (n_user and _stale(LIB_NOSLOTS, noslots_objs)):
         # the look-ahead rings of ros3_kernel.hip sit in registers the compiler does not know are busy: no library is linked
         # from a kernel object in which a ring-using function's own registers reach its ring (raises).  Every code object that
-        # holds the ring functions is checked: the product unit, the twelve method units, the three trace units, the user slots' units, the
-        # fifteen series units and the fifteen flux units.
-        checked = [None] + METHOD_UNITS + TRACE_UNITS + user_units + [("series", u) for u in SERIES_UNITS] + [("flux", u) for u in FLUX_UNITS]
+        # holds the ring functions is checked: every kernel unit of the list.
         with ThreadPoolExecutor(_jobs()) as pool:
-            reports = list(pool.map(lambda u: ring_register_report(unit=u), checked))
-        for u, isa in zip(checked, reports):
+            reports = list(pool.map(lambda u: ring_register_report(unit=u), kunits))
+        for u, isa in zip(kunits, reports):
             hits = isa_hazard_report(isa["__isa_text__"])
             if hits:
-                raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly%s:\n  " % (" (method / trace / user / series / flux unit %s)" % (u,) if u else "")
-                                   + "\n  ".join(hits))
-        cmd = [cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
+                raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly (kernel unit %r):\n  " % (tuple(u),) + "\n  ".join(hits))
+        _run([cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"], verbose)
         if n_user:
-            subprocess.run([cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB_NOSLOTS] + noslots_objs + ["-ldl"], check=True)
+            _run([cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB_NOSLOTS] + noslots_objs + ["-ldl"])
     return LIB
 
 
@@ -236,25 +223,20 @@ RING_FUNCTIONS = ("gsum_run", "gsum_run_bar", "gsum_run_pair", "tail_solve", "sc
 RING_HIGH_SLOTS = (192, 196, 208, 212, 224, 228, 240, 244)      # ros3_kernel.hip: MISTRA_RING_HI<K>
 
 
-def ring_register_report(isa_path=None, unit=None):
+def ring_register_report(isa_path=None, unit=PRODUCT):
     """Checks the one assumption the table look-ahead ring of ros3_kernel.hip rests on (see the comment there): in the
     non-inlined device functions, every register the COMPILER allocates — named outside inline asm, or chosen by it for an asm
     statement's result — stays below the ring's blocks (v192.. or, in the low placement, v64..), so a
     table load landing in the ring can never hit a compiler value.  Compiles the kernel source to gfx950 assembly and
     scans it.  Returns {function: highest VGPR named outside inline asm}; raises if a ring-using function reaches its ring, and if
     a function that is not one of RING_FUNCTIONS (nor an integrating kernel, which only calls them) loads into the ring at all.
-    unit: None = the product kernels' unit (ros3_kernel.hip), one (mechanism, method) of METHOD_UNITS, one (mechanism, None) of TRACE_UNITS,
-    ("user", slot) of a user mechanism slot (its traits header must be in the build directory: prepare_user_mechs) ("series", (mechanism, method))
-    of SERIES_UNITS or ("flux", (mechanism, method)) of FLUX_UNITS."""
+    unit: one of kernel_units() (a user slot's traits header must be in the build directory: prepare_user_mechs); default the product kernels' unit."""
     import re
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         if isa_path is None:
-            isa_path = os.path.join(tmp, "ros3_kernel.s")
-            src, flags = ("ros3_kernel.hip", []) if unit is None else (unit_source(unit), method_flags(*unit))
-            cmd = [hipcc(), "--offload-arch=" + ARCH] + [f for f in COMMON if f != "-fPIC"] + flags + \
-                  ["-S", "--offload-device-only", os.path.join(CSRC, src), "-o", isa_path]
-            subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+            isa_path = os.path.join(tmp, "unit.s")
+            subprocess.run(unit_listing_cmd(unit, isa_path), check=True, stderr=subprocess.DEVNULL)
         lines = open(isa_path).read().split("\n")
     starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if re.match(r"^_ZN6mistra.*:", l)]
     starts.append((len(lines), "end"))

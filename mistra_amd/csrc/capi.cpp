@@ -15,8 +15,10 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
+#include "cell_split.hpp"
 #include "kernel_args.hpp"
 #include "mech_tables.hpp"
 #include "pack.hpp"
@@ -55,20 +57,28 @@ bool traits_match(const MechTables& t, int n_jnz, int tail_regs, bool scale_pass
   return dense.nd == MT::DENSE_ND && dense.kb == MT::DENSE_KB && tail_regs == MT::TAIL_REGS && scale_pass == MT::SCALE_PASS && t.nvar == MT::NVAR && t.nfix == MT::NFIX && t.nreact == MT::NREACT && t.nnz == MT::NNZ && t.nb == MT::NB &&
          t.nconst == MT::NCONST && n_jnz == MT::NJNZ;
 }
-// method: IPAR(4) resolved (ros_methods.hpp); anything but Ros3 runs its method kernel, which reads a.opt
-template <class MT, int NT>
-hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bool* configured);
-// method: IPAR(4) resolved, Ros3 included: the series kernel of that method, which reads a.opt and a.times
-template <class MT, int NT>
-hipError_t launch_series(int method, const KernelArgs& a, hipStream_t stream, bool* configured);
-// method: IPAR(4) resolved, Ros3 included: the flux kernel of that method, which reads a.opt and writes a.flux
-template <class MT, int NT>
-hipError_t launch_flux(int method, const KernelArgs& a, hipStream_t stream, bool* configured);
 
 // ---- ONE ROW PER MECHANISM: everything the entries below need to know about a compiled kernel.  gas, aer, tot, then the user slots this library was
 // built with (user_mechs.hpp: traits generated from the slots' tables at build time).  A user slot has the product, first-step-dump and options
 // (Ros3) kernels and no method or trace kernels; its table is <mech dir>/<name>.mech and it never runs the dense tail block.
 using LaunchFn = hipError_t (*)(const KernelArgs&, hipStream_t, bool*);
+// The kernels of ros_unit_kernel.hip, [kernel VARIANT 3 .. 6][IPAR(4) resolved, ros_methods.hpp]: 3 the method kernels (Ros2, Ros4, Rodas3, Rodas4), 4 the
+// step-control trace (Ros3), 5 the series and 6 the flux kernels (all five methods).  nullptr: not built.
+constexpr int kVariants = 7, kMethods = 6;
+struct UnitTable {
+  LaunchFn fn[kVariants][kMethods] = {};
+};
+template <class MT, int NT, int VARIANT, int METHOD>
+constexpr void add_unit(UnitTable& t) {
+  if constexpr ((VARIANT != 3 || METHOD != kRos3) && (VARIANT != 4 || METHOD == kRos3)) t.fn[VARIANT][METHOD] = &launch_ros_unit<MT, NT, VARIANT, METHOD>;
+}
+template <class MT, int NT, int... METHOD>
+constexpr UnitTable unit_table(std::integer_sequence<int, METHOD...>) {
+  UnitTable t;
+  (..., (add_unit<MT, NT, 3, METHOD + 1>(t), add_unit<MT, NT, 4, METHOD + 1>(t), add_unit<MT, NT, 5, METHOD + 1>(t), add_unit<MT, NT, 6, METHOD + 1>(t)));
+  return t;
+}
+static_assert(kRos2 == 1 && kRodas4 == 5, "IPAR(4) resolved: 1 .. 5");
 struct MechDesc {
   const char* name;
   MechDims dims;
@@ -78,21 +88,17 @@ struct MechDesc {
   bool user;
   bool (*match)(const MechTables&, int, int, bool, const DenseTail&);      // the loaded table against the compiled sizes
   LaunchFn ros3;                                                           // product | phase timing | first-step dump | options (Ros3)
-  hipError_t (*method)(int, const KernelArgs&, hipStream_t, bool*);        // Ros2, Ros4, Rodas3, Rodas4 (nullptr: not built)
-  LaunchFn trace;                                                          // the step-control trace kernel (nullptr: not built)
-  hipError_t (*series)(int, const KernelArgs&, hipStream_t, bool*);        // the series kernels, all five methods (nullptr: not built)
-  hipError_t (*flux)(int, const KernelArgs&, hipStream_t, bool*);          // the flux kernels, all five methods (nullptr: not built)
+  UnitTable unit;                                                          // every other options kernel (a user slot: none)
 };
 template <class MT, int NT>
 constexpr MechDesc builtin_mech(const char* name) {
   return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
-                  MT::MAX_TEMPS, false, &traits_match<MT>, &launch_ros3<MT, NT>, &launch_method<MT, NT>, &launch_ros_trace<MT, NT>, &launch_series<MT, NT>,
-                  &launch_flux<MT, NT>};
+                  MT::MAX_TEMPS, false, &traits_match<MT>, &launch_ros3<MT, NT>, unit_table<MT, NT>(std::make_integer_sequence<int, 5>{})};
 }
 template <class MT, int NT>
 constexpr MechDesc user_mech(const char* name) {
   return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
-                  MT::MAX_TEMPS, true, &traits_match<MT>, &launch_ros3<MT, NT>, nullptr, nullptr, nullptr, nullptr};
+                  MT::MAX_TEMPS, true, &traits_match<MT>, &launch_ros3<MT, NT>, UnitTable{}};
 }
 constexpr int kBuiltinMechs = 3, kMaxMechs = 5;
 constexpr int kNumMechs = kBuiltinMechs + MISTRA_USER_MECHS;
@@ -640,6 +646,22 @@ struct RosCallRing {
     if (host) (void)hipHostFree(host);
     dev = host = nullptr; words = 0; next = 0;
   }
+  // the next block in turn, `w` words at least (the ring is sized by its first call), once the kernel that read it kRosCallsInFlight calls ago has
+  // finished -> its index, host mirror and device block
+  hipError_t acquire(size_t w, int* i, double** hb, double** db) {
+    if (hipError_t e = ensure(w)) return e;
+    *i = next;
+    next = (next + 1) % kRosCallsInFlight;
+    if (pending[*i])
+      if (hipError_t e = hipEventSynchronize(ev[*i])) return e;
+    pending[*i] = false;
+    *hb = host + (size_t)*i * words; *db = dev + (size_t)*i * words;
+    return hipSuccess;
+  }
+  // behind the kernel that reads block i, also behind a failed launch: the copy is queued
+  void mark(int i, hipStream_t st) {
+    if (hipEventRecord(ev[i], st) == hipSuccess) pending[i] = true;
+  }
 };
 
 struct MechState {
@@ -721,22 +743,13 @@ struct MechState {
 struct DeviceState {
   int id = -1;
   MechState mech[kMaxMechs];                          // (the rows of kMech: the slots past kNumMechs are never set up)
-  bool lds_configured[kMaxMechs] = {};                // hipFuncAttributeMaxDynamicSharedMemorySize is per device
-  bool lds_method[kMaxMechs][6] = {};                 // ... and per kernel: the method kernels' [mechanism][IPAR(4)] (launch_ros_method)
-  bool lds_trace[kMaxMechs] = {};                     //     and the step-control trace kernels' (launch_ros_trace)
-  bool lds_series[kMaxMechs][6] = {};                 //     and the series kernels' [mechanism][IPAR(4)] (launch_ros_series)
-  bool lds_flux[kMaxMechs][6] = {};                   //     and the flux kernels' [mechanism][IPAR(4)] (launch_ros_flux)
+  // hipFuncAttributeMaxDynamicSharedMemorySize is per device and kernel: [mechanism][kernel VARIANT][IPAR(4)] as MechDesc::unit, [mechanism][0][0] the
+  // kernels of launch_ros3
+  bool lds_configured[kMaxMechs][kVariants][kMethods] = {};
   void release() {
     if (id >= 0) (void)hipSetDevice(id);
     for (auto& m : mech) m.release();
-    for (bool& c : lds_configured) c = false;
-    for (auto& m : lds_method)
-      for (bool& c : m) c = false;
-    for (bool& c : lds_trace) c = false;
-    for (auto& m : lds_series)
-      for (bool& c : m) c = false;
-    for (auto& m : lds_flux)
-      for (bool& c : m) c = false;
+    std::memset(lds_configured, 0, sizeof lds_configured);
     id = -1;
   }
 };
@@ -1099,6 +1112,37 @@ int check_trace_args(const int32_t* ipar, int cap, const double* trace_d, const 
   if (ipar[3] != 2) return fail("the step-control trace is built for Ros3 (ipar[3] = 2) only");
   return 0;
 }
+// ... and as the trace entries hand them on (host or device arrays, as the entry's others)
+RosCall trace_call(int cap, double* trace_d, int32_t* trace_i, int32_t* ntrace, int32_t* ctrl) {
+  RosCall tr;
+  tr.cap = cap; tr.trace_d = trace_d; tr.trace_i = trace_i; tr.ntrace = ntrace; tr.ctrl = ctrl;
+  return tr;
+}
+// the device entries' tolerance rows: the kernel reads these itself, memory the cells' device cannot reach is refused here, not met there
+int check_tol_reachable(const CellTol& ct, int device) {
+  for (const double* p : {ct.atol, ct.rtol}) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type == hipMemoryTypeUnregistered || (attr.type == hipMemoryTypeDevice && attr.device != device))
+      return fail("d_atol / d_rtol are not device arrays on the cells' device");
+  }
+  return 0;
+}
+// the kernel's tolerance arguments of a cells call: device rows [ncell][call.ntol]
+void set_cell_tol(KernelArgs* a, const RosCall& call, const double* d_atol, const double* d_rtol) {
+  a->tol_abs = d_atol; a->tol_rel = d_rtol;
+  a->tol_cell_stride = call.ntol;
+  a->tol_spec_stride = call.vector ? 1 : 0;
+}
+// ... of a host-buffer cells call (nothing where the call has the shared pair): rows [start, start + nc) of the caller's go up to the slot's staging
+int upload_cell_tol(MechState& S, const RosCall& call, size_t start, size_t nc, KernelArgs* a) {
+  if (!call.cell_atol) return 0;
+  const size_t n = nc * (size_t)call.ntol;
+  HIP_TRY(S.s_tol.reserve(2 * n));
+  HIP_TRY(hipMemcpy(S.s_tol.p, call.cell_atol + start * (size_t)call.ntol, n * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.s_tol.p + n, call.cell_rtol + start * (size_t)call.ntol, n * sizeof(double), hipMemcpyHostToDevice));
+  set_cell_tol(a, call, S.s_tol.p, S.s_tol.p + n);
+  return 0;
+}
 // ct: the tolerances come per cell (atol, rtol are not read).  The refusals -1 .. -4 depend on ipar / rpar alone and stay whole-call results decided here;
 // -5 is then the kernel's, per cell, and the block's pair is a placeholder no kernel reads.
 RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, const CellTol* ct = nullptr) {
@@ -1120,62 +1164,25 @@ RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const dou
   return c;
 }
 
-template <class MT, int NT>
-hipError_t launch_method(int method, const KernelArgs& a, hipStream_t stream, bool* configured) {
-  switch (method) {
-    case kRos2: return launch_ros_method<MT, NT, kRos2>(a, stream, configured);
-    case kRos4: return launch_ros_method<MT, NT, kRos4>(a, stream, configured);
-    case kRodas3: return launch_ros_method<MT, NT, kRodas3>(a, stream, configured);
-    case kRodas4: return launch_ros_method<MT, NT, kRodas4>(a, stream, configured);
-  }
-  return hipErrorInvalidValue;
-}
-
-template <class MT, int NT>
-hipError_t launch_series(int method, const KernelArgs& a, hipStream_t stream, bool* configured) {
-  switch (method) {
-    case kRos2: return launch_ros_series<MT, NT, kRos2>(a, stream, configured);
-    case kRos3: return launch_ros_series<MT, NT, kRos3>(a, stream, configured);
-    case kRos4: return launch_ros_series<MT, NT, kRos4>(a, stream, configured);
-    case kRodas3: return launch_ros_series<MT, NT, kRodas3>(a, stream, configured);
-    case kRodas4: return launch_ros_series<MT, NT, kRodas4>(a, stream, configured);
-  }
-  return hipErrorInvalidValue;
-}
-
-template <class MT, int NT>
-hipError_t launch_flux(int method, const KernelArgs& a, hipStream_t stream, bool* configured) {
-  switch (method) {
-    case kRos2: return launch_ros_flux<MT, NT, kRos2>(a, stream, configured);
-    case kRos3: return launch_ros_flux<MT, NT, kRos3>(a, stream, configured);
-    case kRos4: return launch_ros_flux<MT, NT, kRos4>(a, stream, configured);
-    case kRodas3: return launch_ros_flux<MT, NT, kRodas3>(a, stream, configured);
-    case kRodas4: return launch_ros_flux<MT, NT, kRodas4>(a, stream, configured);
-  }
-  return hipErrorInvalidValue;
-}
-
+// The kernel of a call: the VARIANT from the arguments (a series, else the flux, else the trace, else a method other than Ros3, else the product unit's
+// kernels), one guard, one slot of the mechanism's table.  A method other than Ros3 never runs as a quiet Ros3: what is not built is refused.
 int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, int method = kRos3) {
+  static const struct { const char *user, *refusal; } kText[kVariants] = {
+      {}, {}, {},
+      {"kernel for this Rosenbrock method (Ros2, Ros4, Rodas3, Rodas4)", "no kernel for this Rosenbrock method"},
+      {"step-control trace", "no trace kernel for this Rosenbrock method"},
+      {"series of Rosenbrock_x calls", "no series kernel for this Rosenbrock method"},
+      {"reaction-flux entries", "no flux kernel for this Rosenbrock method"}};
   const MechDesc& M = kMech[mech];
+  const int variant = a.times ? 5 : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
   hipError_t e = hipErrorInvalidValue;
-  if (a.times) {      // a series: the series kernel of the method, Ros3 included
-    if (!M.series) return fail_user_slot(mech, "series of Rosenbrock_x calls");
-    if (method < kRos2 || method > kRodas4 || !a.opt || a.dump || a.prof || a.ntrace) return fail("no series kernel for this Rosenbrock method");
-    e = M.series(method, a, stream, &D.lds_series[mech][method]);
-  } else if (a.flux) {      // the reaction flux: the flux kernel of the method, Ros3 included
-    if (!M.flux) return fail_user_slot(mech, "reaction-flux entries");
-    if (method < kRos2 || method > kRodas4 || !a.opt || a.dump || a.prof || a.ntrace) return fail("no flux kernel for this Rosenbrock method");
-    e = M.flux(method, a, stream, &D.lds_flux[mech][method]);
-  } else if (a.ntrace) {      // the step-control trace kernel (Ros3 with options)
-    if (!M.trace) return fail_user_slot(mech, "step-control trace");
-    if (method != kRos3 || !a.opt || a.dump || a.prof) return fail("no trace kernel for this Rosenbrock method");
-    e = M.trace(a, stream, &D.lds_trace[mech]);
-  } else if (method != kRos3) {
-    if (!M.method) return fail_user_slot(mech, "kernel for this Rosenbrock method (Ros2, Ros4, Rodas3, Rodas4)");      // (never a quiet Ros3)
-    if (method < kRos2 || method > kRodas4 || !a.opt || a.dump || a.prof) return fail("no kernel for this Rosenbrock method");      // (never a quiet Ros3)
-    e = M.method(method, a, stream, &D.lds_method[mech][method]);
+  if (variant) {
+    if (M.user) return fail_user_slot(mech, kText[variant].user);
+    const bool other = variant >= 5 && a.ntrace;      // (the trace is not an argument of a series or of the flux)
+    if (method < kRos2 || method > kRodas4 || !M.unit.fn[variant][method] || !a.opt || a.dump || a.prof || other) return fail(kText[variant].refusal);
+    e = M.unit.fn[variant][method](a, stream, &D.lds_configured[mech][variant][method]);
   } else {
-    e = M.ros3(a, stream, &D.lds_configured[mech]);
+    e = M.ros3(a, stream, &D.lds_configured[mech][0][0]);
   }
   if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
   return 0;
@@ -1315,6 +1322,23 @@ int init_locked(int n, const int* ids) {
   return 0;
 }
 
+// A host-buffer batch over the device slots (cell_split.hpp): block(slot, start, count) -> 0 or the refusal, whole on slot 0 where the batch is not
+// split.  The calling thread ends up on the primary device.  -> 0, the unsplit block's refusal as it is, or the first failed slot's behind "device N: "
+template <class F>
+int on_cell_blocks(int ncell, F&& block) {
+  std::vector<std::string> errs(g_devs.size());
+  const std::vector<int> rcs = run_cell_blocks(ncell, (int)g_devs.size(), [&](int d, size_t start, int count) {
+    const int rc = block(g_devs[(size_t)d], start, count);
+    if (rc) errs[(size_t)d] = g_err;      // g_err is thread-local: carry the text to the caller's thread
+    return rc;
+  });
+  (void)hipSetDevice(g_devs[0].id);
+  if (rcs.size() == 1) return rcs[0];      // (this thread ran it: g_err is its text)
+  for (size_t d = 0; d < rcs.size(); d++)
+    if (rcs[d]) return fail("device " + std::to_string(g_devs[d].id) + ": " + errs[d]);
+  return 0;
+}
+
 // one device's share of a host-buffer call: upload, integrate, download (synchronous on that device)
 // `env` != nullptr: the caller hands over the rate evaluator's inputs instead of the rate constants (rconst is then ignored): RCONST
 // is made on the device and never crosses PCIe
@@ -1348,15 +1372,7 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     HIP_TRY(hipMemcpy(S.call_opt.p, call->block.data(), call->block.size() * sizeof(double), hipMemcpyHostToDevice));
     a.opt = S.call_opt.p;
     a.max_steps = call->max_steps;
-    if (call->cell_atol) {      // this block's tolerance rows
-      const size_t nt = (size_t)call->ntol;
-      HIP_TRY(S.s_tol.reserve(2 * nc * nt));
-      HIP_TRY(hipMemcpy(S.s_tol.p, call->cell_atol + batch_start * nt, nc * nt * sizeof(double), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(S.s_tol.p + nc * nt, call->cell_rtol + batch_start * nt, nc * nt * sizeof(double), hipMemcpyHostToDevice));
-      a.tol_abs = S.s_tol.p; a.tol_rel = S.s_tol.p + nc * nt;
-      a.tol_cell_stride = call->ntol;
-      a.tol_spec_stride = call->vector ? 1 : 0;
-    }
+    if (int rc = upload_cell_tol(S, *call, batch_start, nc, &a)) return rc;
   }
   const int method = call ? call->method : policy_args(S, &a);
   const bool trace = call && call->trace;
@@ -2491,34 +2507,12 @@ static int integrate_host(int mech, int ncell, const double* var_in, const doubl
   if (int rc = on_primary(mech, env ? kNeedRates : 0, true, &t)) return rc;
   const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact;
   const size_t ne = env ? (size_t)t.S->rates.nenv : 0;
-  const int ndev = (int)g_devs.size();
   for (auto& d : g_devs) d.mech[mech].sing_count = 0;
-  if (ndev == 1 || ncell < 2 * ndev) {
-    int rc = integrate_host_on(g_devs[0], mech, ncell, var_in, fix, rconst, tin, tout, var_out, ierr, stats, t_h, 0, env, hstart, call);
-    (void)hipSetDevice(g_devs[0].id);
-    return rc;
-  }
-  // several devices: contiguous blocks of cells, one host thread per device (cells are independent, kpp.f90:4310-4470:
-  // nothing is exchanged, every device uploads, integrates and downloads its own block)
-  std::vector<int> rcs((size_t)ndev, 0);
-  std::vector<std::string> errs((size_t)ndev);
-  std::vector<std::thread> workers;
-  for (int d = 0; d < ndev; d++) {
-    const int per = ncell / ndev, rem = ncell % ndev;
-    const size_t start = (size_t)d * per + (size_t)std::min(d, rem);
-    const int count = per + (d < rem ? 1 : 0);
-    workers.emplace_back([=, &rcs, &errs]() {
-      rcs[(size_t)d] = integrate_host_on(g_devs[(size_t)d], mech, count, var_in + start * nv, fix + start * nf, rconst ? rconst + start * nr : nullptr, tin, tout,
-                                         var_out + start * nv, ierr ? ierr + start : nullptr, stats ? stats + start * 8 : nullptr, t_h ? t_h + start * 3 : nullptr, start,
-                                         env ? env + start * ne : nullptr, hstart ? hstart + start : nullptr, call);
-      if (rcs[(size_t)d]) errs[(size_t)d] = g_err;      // g_err is thread-local: carry the text to the caller's thread
-    });
-  }
-  for (auto& w : workers) w.join();
-  (void)hipSetDevice(g_devs[0].id);
-  for (int d = 0; d < ndev; d++)
-    if (rcs[(size_t)d]) return fail("device " + std::to_string(g_devs[(size_t)d].id) + ": " + errs[(size_t)d]);
-  return 0;
+  return on_cell_blocks(ncell, [=](DeviceState& D, size_t start, int count) {
+    return integrate_host_on(D, mech, count, var_in + start * nv, fix + start * nf, rconst ? rconst + start * nr : nullptr, tin, tout, var_out + start * nv,
+                             ierr ? ierr + start : nullptr, stats ? stats + start * 8 : nullptr, t_h ? t_h + start * 3 : nullptr, start,
+                             env ? env + start * ne : nullptr, hstart ? hstart + start : nullptr, call);
+  });
 }
 
 int mistra_chem_method_table(int method, int* S, double* A15, double* C15, double* M6, double* E6, double* gamma6, int32_t* newf6, double* elo) {
@@ -2583,8 +2577,7 @@ int mistra_chem_rosenbrock_trace_ex(int mech, int ncell, const double* var_in, c
   if (int rc = builtin_only(mech, "step-control trace")) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
   if (int rc = check_trace_args(ipar, cap, trace_d, trace_i, ntrace)) return rc;
-  RosCall tr;
-  tr.cap = cap; tr.trace_d = trace_d; tr.trace_i = trace_i; tr.ntrace = ntrace; tr.ctrl = ctrl;
+  const RosCall tr = trace_call(cap, trace_d, trace_i, ntrace, ctrl);
   return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, &tr);
 }
 
@@ -2600,13 +2593,8 @@ static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, con
   Slot t;
   if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (ct) {      // the kernel reads these itself: memory the device cannot reach is refused here, not met there
-    for (const double* p : {ct->atol, ct->rtol}) {
-      hipPointerAttribute_t attr;
-      if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type == hipMemoryTypeUnregistered || (attr.type == hipMemoryTypeDevice && attr.device != t.D->id))
-        return fail("d_atol / d_rtol are not device arrays on the cells' device");
-    }
-  }
+  if (ct)
+    if (int rc = check_tol_reachable(*ct, t.D->id)) return rc;
   std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of options blocks)
   const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
   const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
@@ -2620,27 +2608,20 @@ static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, con
     return 0;
   }
   RosCallRing& R = t.S->call_ring;
-  HIP_TRY(R.ensure(call.block.size()));
-  const int i = R.next;
-  R.next = (i + 1) % kRosCallsInFlight;
-  if (R.pending[i]) HIP_TRY(hipEventSynchronize(R.ev[i]));      // the kernel that read this block kRosCallsInFlight calls ago
-  R.pending[i] = false;
-  double *hb = R.host + (size_t)i * R.words, *db = R.dev + (size_t)i * R.words;
+  int i;
+  double *hb, *db;
+  HIP_TRY(R.acquire(call.block.size(), &i, &hb, &db));
   std::memcpy(hb, call.block.data(), call.block.size() * sizeof(double));
   HIP_TRY(hipMemcpyAsync(db, hb, call.block.size() * sizeof(double), hipMemcpyHostToDevice, st));
   KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_var_out, d_ierr, d_stats, d_texit_hexit);
   a.hstart = d_hstart;
   a.opt = db;
   a.max_steps = call.max_steps;
-  if (ct) {      // the caller's device arrays, read by the kernel in stream order: no copy
-    a.tol_abs = ct->atol; a.tol_rel = ct->rtol;
-    a.tol_cell_stride = ct->ntol;
-    a.tol_spec_stride = call.vector ? 1 : 0;
-  }
+  if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
   if (tr) { a.trace_cap = tr->cap; a.trace_d = tr->trace_d; a.trace_i = tr->trace_i; a.ntrace = tr->ntrace; a.ctrl = tr->ctrl; }
   a.flux = d_flux;
   const int rc = launch(*t.D, mech, a, st, call.method);
-  if (hipEventRecord(R.ev[i], st) == hipSuccess) R.pending[i] = true;      // (also behind a failed launch: the copy is queued)
+  R.mark(i, st);
   return rc;
 }
 
@@ -2658,8 +2639,7 @@ int mistra_chem_rosenbrock_trace_device(int mech, int ncell, const double* d_var
   if (int rc = builtin_only(mech, "step-control trace")) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
   if (int rc = check_trace_args(ipar, cap, d_trace_d, d_trace_i, d_ntrace)) return rc;
-  RosCall tr;
-  tr.cap = cap; tr.trace_d = d_trace_d; tr.trace_i = d_trace_i; tr.ntrace = d_ntrace; tr.ctrl = d_ctrl;
+  const RosCall tr = trace_call(cap, d_trace_d, d_trace_i, d_ntrace, d_ctrl);
   return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
                               d_hstart, hip_stream, &tr);
 }
@@ -2682,8 +2662,7 @@ int mistra_chem_rosenbrock_trace_cells_ex(int mech, int ncell, const double* var
   const CellTol ct{atol, rtol, ntol};
   if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
   if (int rc = check_trace_args(ipar, cap, trace_d, trace_i, ntrace)) return rc;
-  RosCall tr;
-  tr.cap = cap; tr.trace_d = trace_d; tr.trace_i = trace_i; tr.ntrace = ntrace; tr.ctrl = ctrl;
+  const RosCall tr = trace_call(cap, trace_d, trace_i, ntrace, ctrl);
   return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, &tr, &ct);
 }
 
@@ -2706,8 +2685,7 @@ int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double*
   const CellTol ct{d_atol, d_rtol, ntol};
   if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
   if (int rc = check_trace_args(ipar, cap, d_trace_d, d_trace_i, d_ntrace)) return rc;
-  RosCall tr;
-  tr.cap = cap; tr.trace_d = d_trace_d; tr.trace_i = d_trace_i; tr.ntrace = d_ntrace; tr.ctrl = d_ctrl;
+  const RosCall tr = trace_call(cap, d_trace_d, d_trace_i, d_ntrace, d_ctrl);
   return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
                               d_hstart, hip_stream, &tr, &ct);
 }
@@ -2804,15 +2782,7 @@ static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, siz
   a.max_steps = call.max_steps;
   a.times = S.call_opt.p + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
   a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
-  if (call.cell_atol) {      // this block's tolerance rows
-    const size_t nt = (size_t)call.ntol;
-    HIP_TRY(S.s_tol.reserve(2 * nc * nt));
-    HIP_TRY(hipMemcpy(S.s_tol.p, call.cell_atol + start * nt, nc * nt * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(S.s_tol.p + nc * nt, call.cell_rtol + start * nt, nc * nt * sizeof(double), hipMemcpyHostToDevice));
-    a.tol_abs = S.s_tol.p; a.tol_rel = S.s_tol.p + nc * nt;
-    a.tol_cell_stride = call.ntol;
-    a.tol_spec_stride = call.vector ? 1 : 0;
-  }
+  if (int rc = upload_cell_tol(S, call, start, nc, &a)) return rc;
   if (hstart) {
     HIP_TRY(S.s_hst.reserve(nc));
     HIP_TRY(hipMemcpy(S.s_hst.p, hstart + start, nc * sizeof(double), hipMemcpyHostToDevice));
@@ -2862,29 +2832,9 @@ static int series_host(int mech, int ncell, const double* var_in, const double* 
   }
   // var_in may alias one leg's block of var_series: every slot has its inputs on the device before any result comes back (below: all uploads of a
   // slot precede its downloads, and slots own disjoint cells)
-  const int ndev = (int)g_devs.size();
-  if (ndev == 1 || ncell < 2 * ndev) {
-    const int rc = series_host_on(g_devs[0], mech, ncell, 0, nc, var_in, fix, rconst, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h);
-    (void)hipSetDevice(g_devs[0].id);
-    return rc;
-  }
-  std::vector<int> rcs((size_t)ndev, 0);
-  std::vector<std::string> errs((size_t)ndev);
-  std::vector<std::thread> workers;
-  for (int d = 0; d < ndev; d++) {
-    const int per = ncell / ndev, rem = ncell % ndev;
-    const size_t start = (size_t)d * per + (size_t)std::min(d, rem);
-    const int count = per + (d < rem ? 1 : 0);
-    workers.emplace_back([=, &rcs, &errs, &call]() {
-      rcs[(size_t)d] = series_host_on(g_devs[(size_t)d], mech, count, start, nc, var_in, fix, rconst, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h);
-      if (rcs[(size_t)d]) errs[(size_t)d] = g_err;
-    });
-  }
-  for (auto& w : workers) w.join();
-  (void)hipSetDevice(g_devs[0].id);
-  for (int d = 0; d < ndev; d++)
-    if (rcs[(size_t)d]) return fail("device " + std::to_string(g_devs[(size_t)d].id) + ": " + errs[(size_t)d]);
-  return 0;
+  return on_cell_blocks(ncell, [=, &call](DeviceState& D, size_t start, int count) {
+    return series_host_on(D, mech, count, start, nc, var_in, fix, rconst, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h);
+  });
 }
 
 static int series_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int nleg, const double* times,
@@ -2899,13 +2849,8 @@ static int series_on_device(int mech, int ncell, const double* d_var_in, const d
   Slot t;
   if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (ct) {      // the kernel reads these itself: memory the device cannot reach is refused here, not met there
-    for (const double* p : {ct->atol, ct->rtol}) {
-      hipPointerAttribute_t attr;
-      if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type == hipMemoryTypeUnregistered || (attr.type == hipMemoryTypeDevice && attr.device != t.D->id))
-        return fail("d_atol / d_rtol are not device arrays on the cells' device");
-    }
-  }
+  if (ct)
+    if (int rc = check_tol_reachable(*ct, t.D->id)) return rc;
   std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of series blocks)
   const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
   const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell, nl = (size_t)nleg;
@@ -2919,12 +2864,9 @@ static int series_on_device(int mech, int ncell, const double* d_var_in, const d
   }
   const size_t nb = call.block.size();
   RosCallRing& R = t.S->series_ring;
-  HIP_TRY(R.ensure(nb + (size_t)MISTRA_SERIES_MAX_LEGS + 1));
-  const int i = R.next;
-  R.next = (i + 1) % kRosCallsInFlight;
-  if (R.pending[i]) HIP_TRY(hipEventSynchronize(R.ev[i]));      // the kernel that read this block kRosCallsInFlight series ago
-  R.pending[i] = false;
-  double *hb = R.host + (size_t)i * R.words, *db = R.dev + (size_t)i * R.words;
+  int i;
+  double *hb, *db;
+  HIP_TRY(R.acquire(nb + (size_t)MISTRA_SERIES_MAX_LEGS + 1, &i, &hb, &db));
   std::memcpy(hb, call.block.data(), nb * sizeof(double));
   std::memcpy(hb + nb, times, (nl + 1) * sizeof(double));      // read here: the caller's array is free when the call returns
   HIP_TRY(hipMemcpyAsync(db, hb, (nb + nl + 1) * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2934,13 +2876,9 @@ static int series_on_device(int mech, int ncell, const double* d_var_in, const d
   a.max_steps = call.max_steps;
   a.times = db + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
   a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
-  if (ct) {      // the caller's device arrays, read by the kernel in stream order: no copy
-    a.tol_abs = ct->atol; a.tol_rel = ct->rtol;
-    a.tol_cell_stride = ct->ntol;
-    a.tol_spec_stride = call.vector ? 1 : 0;
-  }
+  if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
   const int rc = launch(*t.D, mech, a, st, call.method);
-  if (hipEventRecord(R.ev[i], st) == hipSuccess) R.pending[i] = true;      // (also behind a failed launch: the copy is queued)
+  R.mark(i, st);
   return rc;
 }
 

@@ -84,7 +84,7 @@ struct KernelArgs {
   TailDev tail;
   DenseDev dense;
   const double* opt;           // [kOptTol + 2*NVAR] or null: Rosenbrock_x's options (RosOptSlot); set = the options instantiation runs (VARIANT 3)
-  // step-control trace (kernel VARIANT 4, ros_trace_kernel.hip; mistra_chem_rosenbrock_trace_ex / _device): one record per attempt that reaches
+  // step-control trace (kernel VARIANT 4, ros_unit_kernel.hip; mistra_chem_rosenbrock_trace_ex / _device): one record per attempt that reaches
   // ros_ErrorNorm_x.  Read by the trace kernels only; null / 0 everywhere else (capi.cpp: make_args).
   double* trace_d;             // [ncell][trace_cap][4] or null: T at the step's start, H as attempted, Err, share of the largest term in NVAR*Err**2
   int32_t* trace_i;            // [ncell][trace_cap][2] or null: species (1-based) of the largest term, 0 = none | code = accepted + 2 * zero pivots of the attempt
@@ -103,7 +103,7 @@ struct KernelArgs {
   // 0 = off: the block's AbsTol.  The host has validated both (capi.cpp: check_policy); the entries whose options travel with the call pass 0.
   double tol_cell_factor;
   double tol_cell_floor;
-  // a series (kernel VARIANT 5, ros_series_kernel.hip; mistra_chem_rosenbrock_series_ex / _device and their cells forms): nleg legs over times[0 .. nleg],
+  // a series (kernel VARIANT 5, ros_unit_kernel.hip; mistra_chem_rosenbrock_series_ex / _device and their cells forms): nleg legs over times[0 .. nleg],
   // leg k one call of Rosenbrock_x from times[k] to times[k+1] on the state leg k-1 left.  Read by the series kernels only, which do not read tin / tout;
   // null / 0 everywhere else (capi.cpp: make_args).  Leg k writes var_out + k*leg_var, ierr + k*leg_ierr, stats + k*leg_stats, texit_hexit + k*leg_th and
   // h_last + k*leg_h (strides in elements; the kernel forms the 64-bit offsets where it uses them).
@@ -111,7 +111,7 @@ struct KernelArgs {
   int32_t nleg;
   int32_t carry_h;             // /= 0: a later leg's first step is the previous leg's Hexit of the cell where that is > 0, else the options' Hstart
   int64_t leg_var, leg_ierr, leg_stats, leg_th, leg_h;
-  // the reaction flux (kernel VARIANT 6, ros_flux_kernel.hip; mistra_chem_rosenbrock_flux_ex / _device and their cells forms): [ncell][NREACT], every
+  // the reaction flux (kernel VARIANT 6, ros_unit_kernel.hip; mistra_chem_rosenbrock_flux_ex / _device and their cells forms): [ncell][NREACT], every
   // reaction's rate integrated over the call, written once per cell when it leaves (a cell refused with -5: +0.0).  Read by the flux kernels only; null
   // everywhere else (capi.cpp: make_args).
   double* flux;

@@ -1188,19 +1188,19 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // parity tests (tests/test_gpu_parity.py); the integration itself is untouched.  3 = Rosenbrock_x's options (gas.f:936-1053) out of
 // a.opt instead of the values INTEGRATE_x fixes (kernel_args.hpp: RosOptSlot; capi.cpp: mistra_chem_set_options): every difference
 // from variant 0 sits behind `if constexpr (OPT)`, the other three compile from the statements they always had.
-// 5 = a series (ros_series_kernel.hip; mistra_chem_rosenbrock_series_ex / _device): variant 3 with the part from the step-control set-up to the
+// 5 = a series (ros_unit_kernel.hip; mistra_chem_rosenbrock_series_ex / _device): variant 3 with the part from the step-control set-up to the
 // results inside a loop over a.nleg legs, leg k one call of Rosenbrock_x from a.times[k] to a.times[k+1] on the state leg k-1 left, its results in
 // block k of the output arrays.  Everything the loop adds sits behind `if constexpr (SERIES)`; for the others the loop is one pass.
-// 6 = the reaction flux (ros_flux_kernel.hip; mistra_chem_rosenbrock_flux_ex / _device): variant 3 of any of the five methods that also integrates every
+// 6 = the reaction flux (ros_unit_kernel.hip; mistra_chem_rosenbrock_flux_ex / _device): variant 3 of any of the five methods that also integrates every
 // reaction's rate over the call by the trapezoid rule on the accepted states and leaves one [NREACT] row per cell in a.flux.
 // Everything it adds sits behind `if constexpr (FLUX)`.
 // METHOD (variant 3 only): the Rosenbrock method, IPAR(4) of Rosenbrock_x (ros_methods.hpp).  Ros3 is the kernel as it was; Ros2, Ros4, Rodas3
-// and Rodas4 (the method kernels, instantiated by ros_method_kernel.hip in translation units of their own) differ in the stage loop, in the
+// and Rodas4 (the method kernels, instantiated by ros_unit_kernel.hip in translation units of their own) differ in the stage loop, in the
 // number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
 template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
   constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, FLUX = VARIANT == 6, OPT = VARIANT == 3 || TRACE || SERIES || FLUX;
-  static_assert(!TRACE || METHOD == kRos3, "the step-control trace is a Ros3 instantiation (ros_trace_kernel.hip)");
+  static_assert(!TRACE || METHOD == kRos3, "the step-control trace is a Ros3 instantiation (ros_unit_kernel.hip)");
   static_assert(METHOD == kRos3 || (OPT && METHOD >= kRos2 && METHOD <= kRodas4), "the method kernels are options instantiations");
   constexpr double kGamma1 = METHOD == kRos3 ? kRosGamma1 : kRosMethod<METHOD>.Gamma[0];
   constexpr int NVAR = MT::NVAR, NFIX = MT::NFIX, NREACT = MT::NREACT, NNZ = MT::NNZ, NCONST = MT::NCONST;
@@ -2240,7 +2240,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   } while (SERIES);
 }
 
-#ifndef MISTRA_METHOD_TU      // (ros_method_kernel.hip and ros_trace_kernel.hip include this file for the kernel template alone)
+#ifndef MISTRA_METHOD_TU      // (ros_unit_kernel.hip and ros_user_kernel.hip include this file for the kernel template alone)
 // ---- launchers (one explicit instantiation per supported <mechanism, workgroup size>)
 template <class MT, int NT>
 hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_configured) {

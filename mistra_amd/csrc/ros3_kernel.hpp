@@ -95,25 +95,14 @@ struct LdsLayout {
 template <class MT, int NT>
 hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
 
-// The method kernels (Ros2, Ros4, Rodas3, Rodas4; METHOD = IPAR(4), ros_methods.hpp): a.opt must be set.  One explicit specialisation per
-// <mechanism, method>, each in a translation unit of its own (ros_method_kernel.hip).  lds_configured: per device AND kernel.
-template <class MT, int NT, int METHOD>
-hipError_t launch_ros_method(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
-
-// The step-control trace kernels (VARIANT 4: the options kernel, Ros3, plus a record per attempt; kernel_args.hpp: trace_*): a.opt and a.ntrace
-// must be set.  One explicit specialisation per mechanism, each in a translation unit of its own (ros_trace_kernel.hip).
-template <class MT, int NT>
-hipError_t launch_ros_trace(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
-
-// The series kernels (VARIANT 5: the options kernel of any of the five methods with a loop over the legs; kernel_args.hpp: times, nleg): a.opt and
-// a.times must be set.  One explicit specialisation per <mechanism, method>, each in a translation unit of its own (ros_series_kernel.hip).
-template <class MT, int NT, int METHOD>
-hipError_t launch_ros_series(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
-
-// The flux kernels (VARIANT 6: the options kernel of any of the five methods that also integrates every reaction's rate over the call;
-// kernel_args.hpp: flux): a.opt and a.flux must be set.  One explicit specialisation per <mechanism, method>, each in a translation unit of its own
-// (ros_flux_kernel.hip).
-template <class MT, int NT, int METHOD>
-hipError_t launch_ros_flux(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
+// The options kernels the product unit does not hold (METHOD = IPAR(4), ros_methods.hpp), a.opt must be set for all of them:
+//   VARIANT 3  the method kernels, Ros2, Ros4, Rodas3, Rodas4 (Ros3 with options is launch_ros3's)
+//   VARIANT 4  the step-control trace, Ros3 only: plus a record per attempt (kernel_args.hpp: trace_*); a.ntrace must be set
+//   VARIANT 5  a series, any of the five methods: a loop over the legs (kernel_args.hpp: times, nleg); a.times must be set
+//   VARIANT 6  the reaction flux, any of the five methods: every reaction's rate integrated over the call (kernel_args.hpp: flux); a.flux must be set
+// One explicit specialisation per <mechanism, variant, method>, each in a translation unit of its own (ros_unit_kernel.hip).  lds_configured: per
+// device AND kernel.
+template <class MT, int NT, int VARIANT, int METHOD>
+hipError_t launch_ros_unit(const KernelArgs& a, hipStream_t stream, bool* lds_configured);
 
 }  // namespace mistra

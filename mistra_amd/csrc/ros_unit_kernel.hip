@@ -1,0 +1,55 @@
+// One kernel per translation unit: ros3_integrate_kernel<MT, NT, VARIANT, METHOD> for one of the options variants the product unit does not hold
+// (ros3_kernel.hip: 3 a method kernel, 4 the step-control trace, 5 a series, 6 the reaction flux) on gas, aer or tot, with its launcher.  Compiled
+// once per unit of mistra_amd/build.py: VARIANT_UNITS.  Units of their own because the non-inlined device functions the kernels share (vm_run,
+// gsum_run*, tail_solve, scale_run, dense_lu, dense_finish) are compiled once per unit, under the register budget of all kernels in it: the product
+// kernels' unit (ros3_kernel.hip) must compile as it does without these, and each of these as it does without the others.
+#if !defined(MISTRA_UNIT_VARIANT) || !defined(MISTRA_UNIT_MECH) || !defined(MISTRA_UNIT_METHOD)
+#error "build with -DMISTRA_UNIT_VARIANT=<3 method | 4 trace | 5 series | 6 flux> -DMISTRA_UNIT_MECH=<0 gas | 1 aer | 2 tot> -DMISTRA_UNIT_METHOD=<1 Ros2 | 2 Ros3 | 3 Ros4 | 4 Rodas3 | 5 Rodas4>"
+#endif
+#define MISTRA_METHOD_TU 1
+#include "ros3_kernel.hip"
+
+namespace mistra {
+
+#if MISTRA_UNIT_MECH == 0
+using UnitMT = GasTraits;
+constexpr int kUnitNT = kGasNT;
+#elif MISTRA_UNIT_MECH == 1
+using UnitMT = AerTraits;
+constexpr int kUnitNT = kAerNT;
+#else
+using UnitMT = TotTraits;
+constexpr int kUnitNT = kTotNT;
+#endif
+
+template <>
+hipError_t launch_ros_unit<UnitMT, kUnitNT, MISTRA_UNIT_VARIANT, MISTRA_UNIT_METHOD>(const KernelArgs& a, hipStream_t stream, bool* lds_configured) {
+  constexpr int VARIANT = MISTRA_UNIT_VARIANT, METHOD = MISTRA_UNIT_METHOD;
+  static_assert(VARIANT >= 3 && VARIANT <= 6, "the options variants: method, trace, series, flux");
+  static_assert(METHOD >= kRos2 && METHOD <= kRodas4, "IPAR(4) resolved: 1 .. 5");
+  static_assert(VARIANT != 3 || METHOD != kRos3, "Ros3 with options is the product unit's VARIANT 3 kernel");
+  static_assert(VARIANT != 4 || METHOD == kRos3, "the step-control trace is a Ros3 instantiation");
+  // the cell's state as the product kernels lay it out; the trace keeps the 2*NW cells of its largest-term reduction (value, species per wave) behind it
+  constexpr int NW = kUnitNT / 64;
+  constexpr size_t lds_bytes = (LdsLayout<UnitMT, kUnitNT>::TOTAL + (VARIANT == 4 ? 2 * NW : 0)) * sizeof(double);
+  static_assert(lds_bytes <= 160 * 1024, "cell state and the trace's reduction cells do not fit the 160 KiB LDS of a gfx950 CU");
+  auto kern = ros3_integrate_kernel<UnitMT, kUnitNT, VARIANT, METHOD>;
+  if (!a.opt) return hipErrorInvalidValue;      // all of these are options instantiations
+  if constexpr (VARIANT == 4) {
+    if (!a.ntrace || a.trace_cap < 0 || (a.trace_cap > 0 && (!a.trace_d || !a.trace_i))) return hipErrorInvalidValue;
+  } else if constexpr (VARIANT == 5) {
+    if (!a.times || a.nleg < 1) return hipErrorInvalidValue;
+  } else if constexpr (VARIANT == 6) {
+    if (!a.flux) return hipErrorInvalidValue;
+  }
+  if (!*lds_configured) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    *lds_configured = true;
+  }
+  if (a.ncell <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kern, dim3((unsigned)a.ncell), dim3(kUnitNT), lds_bytes, stream, a);
+  return hipGetLastError();
+}
+
+}  // namespace mistra

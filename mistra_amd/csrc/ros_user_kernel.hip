@@ -1,6 +1,6 @@
 // The kernels of one user mechanism slot per translation unit: ros3_integrate_kernel<UserMT, NT, VARIANT> for VARIANT 0 (product), 2 (first-step
 // dump) and 3 (Rosenbrock_x's options, Ros3) on the slot's generated traits (user_mechs.hpp), with their launcher.  Compiled once per slot
-// (mistra_amd/build.py: -DMISTRA_USER_SLOT=0|1).  A unit of its own for the reason the method kernels have theirs (ros_method_kernel.hip): the
+// (mistra_amd/build.py: -DMISTRA_USER_SLOT=0|1).  A unit of its own for the reason the method kernels have theirs (ros_unit_kernel.hip): the
 // product kernels' unit (ros3_kernel.hip) must compile as it does without the slots.  No phase-timing, method or trace instantiation: a user slot
 // has none of those entries (capi.cpp refuses them).
 #if !defined(MISTRA_USER_SLOT)

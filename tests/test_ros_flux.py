@@ -86,9 +86,10 @@ def test_flux_units_are_built_and_checked_like_every_unit():
     """fifteen units (three mechanisms x five methods); the gas Ros3 one compiled here passes the register-ring and hazard reports the build runs on
     every unit, and holds exactly one kernel, the VARIANT 6 instantiation"""
     from mistra_amd import build as B
-    assert sorted(B.FLUX_UNITS) == [(m, k) for m in (0, 1, 2) for k in (1, 2, 3, 4, 5)]
-    assert B.unit_source(("flux", (0, 2))) == B.FLUX_SOURCE and B.method_flags("flux", (2, 5)) == ["-DMISTRA_FLUX_MECH=2", "-DMISTRA_FLUX_METHOD=5"]
-    rep = B.ring_register_report(unit=("flux", (0, 2)))
+    assert sorted((u.mech, u.method) for u in B.VARIANT_UNITS if u.variant == 6) == [(m, k) for m in (0, 1, 2) for k in (1, 2, 3, 4, 5)]
+    assert B.unit_build(B.Unit(6, 0, 2))[0] == B.UNIT_SOURCE
+    assert B.unit_build(B.Unit(6, 2, 5))[2] == ["-DMISTRA_UNIT_VARIANT=6", "-DMISTRA_UNIT_MECH=2", "-DMISTRA_UNIT_METHOD=5"]
+    rep = B.ring_register_report(unit=B.Unit(6, 0, 2))
     assert B.isa_hazard_report(rep["__isa_text__"]) == []
     kernels = [k for k in rep if "ros3_integrate_kernel" in k]
     assert kernels == ["_ZN6mistra21ros3_integrate_kernelINS_9GasTraitsELi64ELi6ELi2EEEvNS_10KernelArgsE"], kernels

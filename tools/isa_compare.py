@@ -3,11 +3,13 @@
 mistra_amd/csrc/ros3_kernel.hip at two commits), and the resources of the method kernels' code objects.
 
     python tools/isa_compare.py PARENT.s NEW.s      per function: instructions in both, whether the bodies are identical
-    python tools/isa_compare.py --methods           per method unit (mistra_amd/build.py: METHOD_UNITS): the kernel's registers, scratch and LDS
+    python tools/isa_compare.py --listings DIR      the listing of every kernel unit (mistra_amd/build.py: kernel_units) into DIR, one .s each: run at
+                                                    two commits and compare the files pairwise
+    python tools/isa_compare.py --methods           per method unit (VARIANT_UNITS, variant 3): the kernel's registers, scratch and LDS
                                                     from the code object's metadata, compiled here as the build compiles them
-    python tools/isa_compare.py --series            per series unit (SERIES_UNITS): the same figures of the series kernel (VARIANT 5) beside its VARIANT 3
+    python tools/isa_compare.py --series            per series unit (variant 5): the same figures of the series kernel beside its VARIANT 3
                                                     sibling's — the product unit's options kernel for Ros3, the method unit's for the other four
-    python tools/isa_compare.py --flux              per flux unit (FLUX_UNITS): the same table for the flux kernel (VARIANT 6)
+    python tools/isa_compare.py --flux              per flux unit (variant 6): the same table for the flux kernel
 
 A kernel's mangled name carries its template arguments: the METHOD parameter added to ros3_integrate_kernel (default Ros3 = 2) is cut out of the
 new listing's names before the comparison; nothing else is normalised."""
@@ -20,6 +22,7 @@ import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+from mistra_amd import build as B  # noqa: E402
 
 
 def functions(path):
@@ -56,22 +59,9 @@ def compare(a, b):
     return same == len(names)
 
 
-def methods():
-    from mistra_amd import build as B
-    names = {1: "Ros2", 3: "Ros4", 4: "Rodas3", 5: "Rodas4"}
-    print("%-5s %-7s %6s %6s %8s %12s %10s  (LDS: dynamic, set at launch: LdsLayout<MT, NT>::TOTAL doubles, as the product kernels)" %
-          ("mech", "method", "VGPRs", "SGPRs", "scratch", "spilled VGPR", "static LDS"))
-    with tempfile.TemporaryDirectory() as tmp:
-        for mech, method in B.METHOD_UNITS:
-            s = os.path.join(tmp, "u.s")
-            cmd = [B.hipcc(), "--offload-arch=" + B.ARCH] + [f for f in B.COMMON if f != "-fPIC"] + B.method_flags(mech, method) + \
-                  ["-S", "--offload-device-only", os.path.join(B.CSRC, B.METHOD_SOURCE), "-o", s]
-            subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-            text = open(s).read()
-            k = re.search(r"- \.agpr_count:.*?\.name:\s+(\S*ros3_integrate_kernel\S*).*?(?=\n  - \.agpr_count|\namdhsa\.target)", text, re.S).group(0)
-            get = lambda key: int(re.search(r"\.%s:\s+(\d+)" % key, k).group(1))
-            print("%-5s %-7s %6d %6d %8d %12d %10d" % (("gas", "aer", "tot")[mech], names[method], get("vgpr_count"), get("sgpr_count"),
-                                                        get("private_segment_fixed_size"), get("vgpr_spill_count"), get("group_segment_fixed_size")))
+NAMES = {1: "Ros2", 2: "Ros3", 3: "Ros4", 4: "Rodas3", 5: "Rodas4"}
+MECHS = ("gas", "aer", "tot")
+COLS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")
 
 
 def _kernels(path):
@@ -84,38 +74,67 @@ def _kernels(path):
     return out
 
 
-def series(variant=5, what="series"):
-    from mistra_amd import build as B
-    units, source, flags_of = (B.SERIES_UNITS, B.SERIES_SOURCE, B.series_flags) if variant == 5 else (B.FLUX_UNITS, B.FLUX_SOURCE, B.flux_flags)
-    names = {1: "Ros2", 2: "Ros3", 3: "Ros4", 4: "Rodas3", 5: "Rodas4"}
-    mechs = ("gas", "aer", "tot")
-    cols = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")
+def unit_name(unit):
+    """file name of a kernel unit's listing: product | v<variant>_<mech>_<method> | user_<slot>"""
+    return unit.variant if unit == B.PRODUCT else "user_%d" % unit.mech if unit.variant == "user" else "v%d_%s_%s" % (unit.variant, MECHS[unit.mech], NAMES[unit.method])
+
+
+def listing(unit, path):
+    """the gfx950 assembly of a kernel unit (mistra_amd/build.py: kernel_units), compiled as the build compiles it -> path"""
+    subprocess.run(B.unit_listing_cmd(unit, path), check=True, stderr=subprocess.DEVNULL)
+    return path
+
+
+def listings(outdir):
+    """one .s per kernel unit of the library as it is configured (MISTRA_USER_MECHS), to be compared pairwise with another commit's"""
+    from concurrent.futures import ThreadPoolExecutor
+    os.makedirs(outdir, exist_ok=True)
+    units = B.kernel_units(B.prepare_user_mechs()[0])
+    with ThreadPoolExecutor(B._jobs()) as pool:
+        for path in pool.map(lambda u: listing(u, os.path.join(outdir, unit_name(u) + ".s")), units):
+            print(path)
+
+
+def _integrator(unit, tmp):
+    """the metadata of the one integrating kernel of a variant unit"""
+    ks = [k for n, k in _kernels(listing(unit, os.path.join(tmp, "u.s"))) if "ros3_integrate_kernel" in n]
+    assert len(ks) == 1, (unit, len(ks))
+    return ks[0]
+
+
+def methods():
+    print("%-5s %-7s %6s %6s %8s %12s %10s  (LDS: dynamic, set at launch: LdsLayout<MT, NT>::TOTAL doubles, as the product kernels)" %
+          ("mech", "method", "VGPRs", "SGPRs", "scratch", "spilled VGPR", "static LDS"))
+    with tempfile.TemporaryDirectory() as tmp:
+        for u in (u for u in B.VARIANT_UNITS if u.variant == 3):
+            k = _integrator(u, tmp)
+            print("%-5s %-7s %6d %6d %8d %12d %10d" % ((MECHS[u.mech], NAMES[u.method]) + tuple(k[c] for c in COLS)))
+
+
+def beside_variant_3(variant, what):
+    """per unit of `variant`: the kernel's figures beside its VARIANT 3 sibling's"""
     print("%-4s %-7s | %-40s | %s" % ("mech", "method", "VARIANT 3 (the options kernel)", "VARIANT %d (the %s kernel)" % (variant, what)))
     print("%-4s %-7s | %5s %5s %8s %7s %10s | %5s %5s %8s %7s %10s   (LDS: dynamic, LdsLayout<MT, NT>::TOTAL doubles, the same for both)" %
           (("", "") + ("VGPRs", "SGPRs", "scratch", "spilled", "static LDS") * 2))
     with tempfile.TemporaryDirectory() as tmp:
-        def listing(src, flags):
-            s = os.path.join(tmp, "u.s")
-            cmd = [B.hipcc(), "--offload-arch=" + B.ARCH] + [f for f in B.COMMON if f != "-fPIC"] + flags + ["-S", "--offload-device-only", os.path.join(B.CSRC, src), "-o", s]
-            subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-            return _kernels(s)
-        product = listing("ros3_kernel.hip", [])
-        for mech, method in units:
-            if method == 2:
-                sib = [k for n, k in product if re.search(r"ros3_integrate_kernelINS_\d+%sTraitsELi\d+ELi3ELi2E" % mechs[mech].capitalize(), n)]
+        product = _kernels(listing(B.PRODUCT, os.path.join(tmp, "p.s")))
+        for u in (u for u in B.VARIANT_UNITS if u.variant == variant):
+            if u.method == B.ROS3:
+                sib, = [k for n, k in product if re.search(r"ros3_integrate_kernelINS_\d+%sTraitsELi\d+ELi3ELi2E" % MECHS[u.mech].capitalize(), n)]
             else:
-                sib = [k for n, k in listing(B.METHOD_SOURCE, B.method_flags(mech, method)) if "ros3_integrate_kernel" in n]
-            new = [k for n, k in listing(source, flags_of(mech, method)) if "ros3_integrate_kernel" in n]
-            assert len(sib) == 1 and len(new) == 1, (mech, method, len(sib), len(new))
-            print("%-4s %-7s | %5d %5d %8d %7d %10d | %5d %5d %8d %7d %10d" % ((mechs[mech], names[method]) + tuple(sib[0][c] for c in cols) + tuple(new[0][c] for c in cols)))
+                sib = _integrator(u._replace(variant=3), tmp)
+            new = _integrator(u, tmp)
+            print("%-4s %-7s | %5d %5d %8d %7d %10d | %5d %5d %8d %7d %10d" % ((MECHS[u.mech], NAMES[u.method]) + tuple(sib[c] for c in COLS) + tuple(new[c] for c in COLS)))
 
 
 if __name__ == "__main__":
     if "--methods" in sys.argv:
         methods()
     elif "--series" in sys.argv:
-        series()
+        beside_variant_3(5, "series")
     elif "--flux" in sys.argv:
-        series(6, "flux")
+        beside_variant_3(6, "flux")
+    elif "--listings" in sys.argv:
+        listings(sys.argv[sys.argv.index("--listings") + 1])
     else:
         sys.exit(0 if compare(sys.argv[1], sys.argv[2]) else 1)
