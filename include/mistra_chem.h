@@ -338,6 +338,49 @@ int mistra_chem_rosenbrock_series_cells_device(int mech, int ncell, const double
                                                double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                                int carry_h, const double* d_hstart, void* hip_stream);
 
+/* DENSE OUTPUT: the state at ns sample times INSIDE one call of Rosenbrock_x, without changing the call (a series, above, is nleg calls).
+ * Everything mistra_chem_rosenbrock_ex / _device (the cells forms: _cells_ex / _cells_device) return with the same arguments, d_hstart included, bit for
+ * bit (var_out, ierr, stats, t_h / d_texit_hexit), plus
+ *     ysample [ns][ncell][NVAR]  (the series' block layout)      nout [ncell]: the number of samples reached, always a prefix of ts.
+ * The call's accepted states are Y_0 = Y(Tstart), Y_1 .. Y_N at the kernel's own times T_0 = Tstart, T_(n+1) = T_n + dh_n, dh_n = D*H_n the signed accepted
+ * step, D = Direction (Tend >= Tstart ? 1 : -1), F_n = Fun_x(Y_n) as the step's own first Fun_x forms it.  Samples are taken in order: after step n is
+ * accepted, every sample not yet taken with D*(ts[k] - T_(n+1)) <= 0 belongs to step n; on a normal return (IERR = 1) every sample still left belongs to the
+ * last accepted step (the loop ends with |Tend - T_N| < Roundoff: Tend may lie an ulp beyond T_N); on IERR = -6 / -7 / -8 the ones left are not reached; a
+ * call with no accepted step reaches none.  The value, per species, with th = (ts[k] - T_n) / dh_n, Y0 = Y_n, Y1 = Y_(n+1), F0 = F_n, F1 = F_(n+1), every
+ * multiply, add and subtract rounded once, in this order:
+ *     d = Y1 - Y0    hf0 = dh*F0    hf1 = dh*F1    om = 1.0 - th
+ *     c = ((1.0 - 2.0*th)*d - om*hf0) + th*hf1
+ *     u = (om*Y0 + th*Y1) - (th*om)*c
+ * — the cubic Hermite interpolant (local error O(H^4): Ros3's order; for the order-4 methods it is the interpolant's order, not the method's).  th = 1
+ * gives Y1 exactly: the last step of a completed call is clipped to |Tend - T|, so a sample at Tend equals var_out bit for bit.  F_(n+1) is the next
+ * step's first Fun_x; on a normal return, and on -6 / -7 with a step still open, it takes one more Fun_x at the state the call returns, not counted in
+ * Nfun (made only where a sample is still to be taken); after -8 the failing step's own Fun_x has closed the last accepted step.
+ * Rows >= nout[c] are written +0.0.  Refusals stay results: -1 .. -5 (whole call or, in the cells forms, per cell) give the sibling's result with nout = 0
+ * and +0.0 rows; the host-refused ones launch nothing.
+ * ts: a HOST array, read before the call returns (it travels behind the call's options block as a series' times do; queued calls each run with their
+ * own); 1 <= ns <= MISTRA_DENSE_MAX_TIMES; every ts[k] finite, strictly monotone in the call's direction, D*(ts[k] - Tstart) > 0 and D*(Tend - ts[k]) >= 0.
+ * A violation, a null ts, ysample or nout fails with its own text before a device is touched.  The options travel with the call; the options in force, the
+ * integrator policy and step reuse are not involved.  There is no series, flux or trace form, no driver hook and no user slot (both ids fail with the
+ * slot's text).  The _ex forms split the batch over the device slots and fail while a column step of the mechanism is open. */
+#define MISTRA_DENSE_MAX_TIMES MISTRA_SERIES_MAX_LEGS
+int mistra_chem_rosenbrock_dense_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                    const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
+                                    int32_t* stats, double* t_h, int ns, const double* ts, double* ysample, int32_t* nout);
+int mistra_chem_rosenbrock_dense_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                        double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,   /* host arrays */
+                                        double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
+                                        void* hip_stream, int ns, const double* ts /* host */, double* d_ysample, int32_t* d_nout);    /* in stream order */
+int mistra_chem_rosenbrock_dense_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart,
+                                          double tend, const double* atol, const double* rtol, int ntol,                             /* rows per cell */
+                                          const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr, int32_t* stats, double* t_h,
+                                          int ns, const double* ts, double* ysample, int32_t* nout);
+int mistra_chem_rosenbrock_dense_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                              double tend, const double* d_atol, const double* d_rtol, int ntol,                     /* device arrays */
+                                              const double* rpar, const int32_t* ipar,                                               /* host arrays */
+                                              double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                              const double* d_hstart, void* hip_stream, int ns, const double* ts /* host */, double* d_ysample,
+                                              int32_t* d_nout);
+
 /* AbsTol from each cell's own state, on the device in stream order: d_atol[c] = max(floor, factor * max_i |d_var[c][i]|), i over NVAR.  NaN entries
  * are ignored; a cell with no positive entry gets floor.  The product is one rounding of two exact operands, so the host restatement
  * max(floor, factor * fmax-reduction of |var|) gives the same bits.  factor or floor that is not finite and positive fails with a text before a device

@@ -141,6 +141,11 @@ def lib():
             L.mistra_chem_rosenbrock_flux_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [vp]
             L.mistra_chem_rosenbrock_flux_cells_ex.argtypes = L.mistra_chem_rosenbrock_cells_ex.argtypes + [_dp]
             L.mistra_chem_rosenbrock_flux_cells_device.argtypes = L.mistra_chem_rosenbrock_cells_device.argtypes + [vp]
+        if hasattr(L, "mistra_chem_rosenbrock_dense_ex"):
+            L.mistra_chem_rosenbrock_dense_ex.argtypes = L.mistra_chem_rosenbrock_ex.argtypes + [C.c_int, _dp, _dp, _ip]
+            L.mistra_chem_rosenbrock_dense_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [C.c_int, _dp, vp, vp]
+            L.mistra_chem_rosenbrock_dense_cells_ex.argtypes = L.mistra_chem_rosenbrock_cells_ex.argtypes + [C.c_int, _dp, _dp, _ip]
+            L.mistra_chem_rosenbrock_dense_cells_device.argtypes = L.mistra_chem_rosenbrock_cells_device.argtypes + [C.c_int, _dp, vp, vp]
         if hasattr(L, "mistra_chem_set_policy"):
             L.mistra_chem_set_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
             L.mistra_chem_check_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
@@ -737,8 +742,11 @@ def rosenbrock_trace_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, ato
 
 
 # ---- the reaction flux (include/mistra_chem.h: mistra_chem_rosenbrock_flux_ex / _device and their cells forms)
-def _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, cells):
-    """rosenbrock_flux (cells False: the shared pair) and rosenbrock_flux_cells (cells True: atol, rtol [ncell, ntol])"""
+def _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, cells, ts=None):
+    """rosenbrock_flux (cells False: the shared pair) and rosenbrock_flux_cells (cells True: atol, rtol [ncell, ntol]); ts set: the dense-output entries
+    (rosenbrock_dense / rosenbrock_dense_cells), which return samples [ns, ncell, NVAR] and nout [ncell] where the flux entries return the flux"""
+    if ts is not None:      # a host array whatever the cells are: it travels with the call's options
+        ts = np.ascontiguousarray(ts, np.float64).reshape(-1)
     mid, name = _mech_id(mech)
     nvar, nfix, nreact, _ = DIMS[name]
     ip, rp, at, rt = _option_args(name, ipar, rpar, None if cells else atol, None if cells else rtol)
@@ -770,8 +778,16 @@ def _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hsta
         ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
         stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
         th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
-        flux = torch.empty((ncell, nreact), dtype=torch.float64, device=var.device)
         stream = torch.cuda.current_stream(var.device).cuda_stream
+        if ts is not None:
+            samples = torch.empty((ts.size, ncell, nvar), dtype=torch.float64, device=var.device)
+            nout = torch.empty(ncell, dtype=torch.int32, device=var.device)
+            entry = L.mistra_chem_rosenbrock_dense_cells_device if cells else L.mistra_chem_rosenbrock_dense_device
+            _check(entry(mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), *tol, *popts, out.data_ptr(),
+                         ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), None if hstart is None else hstart.data_ptr(), C.c_void_p(stream),
+                         int(ts.size), ts.ctypes.data_as(_dp), samples.data_ptr(), nout.data_ptr()))
+            return IntegrateResult(out, ierr, stats), th, samples, nout
+        flux = torch.empty((ncell, nreact), dtype=torch.float64, device=var.device)
         entry = L.mistra_chem_rosenbrock_flux_cells_device if cells else L.mistra_chem_rosenbrock_flux_device
         _check(entry(mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), *tol, *popts, out.data_ptr(),
                      ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), None if hstart is None else hstart.data_ptr(), C.c_void_p(stream),
@@ -794,6 +810,14 @@ def _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hsta
     ierr = np.zeros(ncell, np.int32)
     stats = np.zeros((ncell, 8), np.int32)
     th = np.zeros((ncell, 3))
+    if ts is not None:
+        samples = np.zeros((ts.size, ncell, nvar))
+        nout = np.zeros(ncell, np.int32)
+        entry = L.mistra_chem_rosenbrock_dense_cells_ex if cells else L.mistra_chem_rosenbrock_dense_ex
+        _check(entry(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend), *tol, *popts,
+                     out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp), int(ts.size),
+                     ts.ctypes.data_as(_dp), samples.ctypes.data_as(_dp), nout.ctypes.data_as(_ip)))
+        return IntegrateResult(out, ierr, stats), th, samples, nout
     flux = np.zeros((ncell, nreact))
     entry = L.mistra_chem_rosenbrock_flux_cells_ex if cells else L.mistra_chem_rosenbrock_flux_ex
     # (the arguments are checked by the library before it looks for a device: no init() in front of them)
@@ -812,6 +836,21 @@ def rosenbrock_flux(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None, 
 def rosenbrock_flux_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart=None):
     """rosenbrock_flux() with tolerances per cell as rosenbrock_cells takes them; a cell refused with -5 has a flux row of zeros."""
     return _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, True)
+
+
+# ---- dense output (include/mistra_chem.h: mistra_chem_rosenbrock_dense_ex / _device and their cells forms)
+def rosenbrock_dense(mech, var, fix, rconst, tstart, tend, ts, ipar=None, rpar=None, atol=None, rtol=None, hstart=None):
+    """rosenbrock() run by the kernel that also leaves the state at the sample times ts (a host array: finite, strictly monotone from tstart towards
+    tend, tstart excluded, tend allowed) -> rosenbrock's tuple + samples [ns, ncell, NVAR] + nout [ncell].  The call itself is not changed by looking:
+    the first two results are bit for bit rosenbrock()'s.  A sample is the cubic Hermite interpolant between the two accepted states around it
+    (INTEGRATION.md 4o); nout[c] samples were reached (fewer than ns after IERR < 0), the rows behind them are zeros.  numpy arrays go to the host entry,
+    torch CUDA tensors to the device entry on the current stream.  Not for a user mechanism slot."""
+    return _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, False, ts)
+
+
+def rosenbrock_dense_cells(mech, var, fix, rconst, tstart, tend, ts, ipar, rpar, atol, rtol, hstart=None):
+    """rosenbrock_dense() with tolerances per cell as rosenbrock_cells takes them; a cell refused with -5 has nout = 0 and rows of zeros."""
+    return _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, True, ts)
 
 
 # ---- a series: several output times in one call (include/mistra_chem.h: mistra_chem_rosenbrock_series_ex / _device and their cells forms)

@@ -63,8 +63,9 @@ bool traits_match(const MechTables& t, int n_jnz, int tail_regs, bool scale_pass
 // (Ros3) kernels and no method or trace kernels; its table is <mech dir>/<name>.mech and it never runs the dense tail block.
 using LaunchFn = hipError_t (*)(const KernelArgs&, hipStream_t, bool*);
 // The kernels of ros_unit_kernel.hip, [kernel VARIANT 3 .. 6][IPAR(4) resolved, ros_methods.hpp]: 3 the method kernels (Ros2, Ros4, Rodas3, Rodas4), 4 the
-// step-control trace (Ros3), 5 the series and 6 the flux kernels (all five methods).  nullptr: not built.
-constexpr int kVariants = 7, kMethods = 6;
+// step-control trace (Ros3), 5 the series and 6 the flux kernels (all five methods), 7 the dense-output kernels (all five methods; they live in the series
+// units).  nullptr: not built.
+constexpr int kVariants = 8, kMethods = 6;
 struct UnitTable {
   LaunchFn fn[kVariants][kMethods] = {};
 };
@@ -75,7 +76,8 @@ constexpr void add_unit(UnitTable& t) {
 template <class MT, int NT, int... METHOD>
 constexpr UnitTable unit_table(std::integer_sequence<int, METHOD...>) {
   UnitTable t;
-  (..., (add_unit<MT, NT, 3, METHOD + 1>(t), add_unit<MT, NT, 4, METHOD + 1>(t), add_unit<MT, NT, 5, METHOD + 1>(t), add_unit<MT, NT, 6, METHOD + 1>(t)));
+  (..., (add_unit<MT, NT, 3, METHOD + 1>(t), add_unit<MT, NT, 4, METHOD + 1>(t), add_unit<MT, NT, 5, METHOD + 1>(t), add_unit<MT, NT, 6, METHOD + 1>(t),
+        add_unit<MT, NT, 7, METHOD + 1>(t)));
   return t;
 }
 static_assert(kRos2 == 1 && kRodas4 == 5, "IPAR(4) resolved: 1 .. 5");
@@ -705,6 +707,8 @@ struct MechState {
   DevBuf<double> s_trd;                    // ... and of mistra_chem_rosenbrock_trace_ex: the records, the attempt counts, the per-species counts
   DevBuf<int32_t> s_tri, s_ntr, s_ctl;
   DevBuf<double> s_flux;                   // ... and of mistra_chem_rosenbrock_flux_ex: the block's flux rows
+  DevBuf<double> s_dn_y;                   // ... and of mistra_chem_rosenbrock_dense_ex: the samples' blocks of this slot's cells, the numbers reached
+  DevBuf<int32_t> s_dn_n;
   // where the zero-pivot rows of the LAST host-buffer call of this slot are (mistra_chem_singular_rows): cells [sing_start,
   // sing_start + sing_count) of the caller's batch in s_sing, or the one cell of the COMMON-block call in one_sing
   size_t sing_start = 0, sing_count = 0;
@@ -730,7 +734,7 @@ struct MechState {
     step_mem.release(); step_n = 0;
     s_hst.release(); s_tol.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
-    s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release(); s_flux.release();
+    s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release(); s_flux.release(); s_dn_y.release(); s_dn_n.release();
     sing_count = 0; sing_one = false;
     drive.release(); one.release();
     pend = PendingDrive{};      // (a step issued and never fetched dies with its buffers)
@@ -1088,6 +1092,18 @@ struct RosCall {
   bool vector = false;            // IPAR(2) = 0: every entry of a row is read; else entry 0 alone
   // mistra_chem_rosenbrock_flux_ex: every reaction's rate integrated over the call, the caller's HOST array [ncell][NREACT] for the whole batch
   double* flux = nullptr;
+  // mistra_chem_rosenbrock_dense_ex: the state at ns sample times inside the call.  The times ride behind the options in `block`, at
+  // dense_at; ysample [ns][ncell][NVAR] and nout [ncell] are the caller's HOST arrays for the whole batch of dense_total cells
+  int dense_ns = 0;
+  size_t dense_at = 0, dense_total = 0;
+  double* dense_y = nullptr;
+  int32_t* dense_nout = nullptr;
+};
+struct DenseOut {      // the sample arguments of a dense-output entry (ysample, nout: host or device arrays, as the entry's others)
+  int ns;
+  const double* ts;
+  double* ysample;
+  int32_t* nout;
 };
 struct CellTol {      // the per-cell tolerance arguments of a cells entry
   const double *atol, *rtol;
@@ -1164,7 +1180,7 @@ RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const dou
   return c;
 }
 
-// The kernel of a call: the VARIANT from the arguments (a series, else the flux, else the trace, else a method other than Ros3, else the product unit's
+// The kernel of a call: the VARIANT from the arguments (dense output, else a series, else the flux, else the trace, else a method other than Ros3, else the product unit's
 // kernels), one guard, one slot of the mechanism's table.  A method other than Ros3 never runs as a quiet Ros3: what is not built is refused.
 int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, int method = kRos3) {
   static const struct { const char *user, *refusal; } kText[kVariants] = {
@@ -1172,9 +1188,10 @@ int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, in
       {"kernel for this Rosenbrock method (Ros2, Ros4, Rodas3, Rodas4)", "no kernel for this Rosenbrock method"},
       {"step-control trace", "no trace kernel for this Rosenbrock method"},
       {"series of Rosenbrock_x calls", "no series kernel for this Rosenbrock method"},
-      {"reaction-flux entries", "no flux kernel for this Rosenbrock method"}};
+      {"reaction-flux entries", "no flux kernel for this Rosenbrock method"},
+      {"dense-output entries", "no dense-output kernel for this Rosenbrock method"}};
   const MechDesc& M = kMech[mech];
-  const int variant = a.times ? 5 : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
+  const int variant = a.dense_nout ? 7 : a.times ? 5 : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
   hipError_t e = hipErrorInvalidValue;
   if (variant) {
     if (M.user) return fail_user_slot(mech, kText[variant].user);
@@ -1210,6 +1227,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.tol_cell_factor = 0.0; a.tol_cell_floor = 0.0;      // (policy_args sets them)
   a.times = nullptr; a.nleg = 0; a.carry_h = 0; a.leg_var = a.leg_ierr = a.leg_stats = a.leg_th = a.leg_h = 0;      // (the series entries set them)
   a.flux = nullptr;      // (the flux entries set it)
+  a.dense_out = nullptr; a.dense_nout = nullptr; a.dense_ns = 0; a.dense_block = 0;      // (the dense-output entries set them)
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
@@ -1401,6 +1419,13 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     HIP_TRY(S.s_flux.reserve(nc * nr));
     a.flux = S.s_flux.p;
   }
+  const bool dense = call && call->dense_nout;
+  if (dense) {      // every row is written by the kernel (the ones not reached: zeros): nothing goes up
+    HIP_TRY(S.s_dn_y.reserve((size_t)call->dense_ns * nc * nv));
+    HIP_TRY(S.s_dn_n.reserve(nc));
+    a.times = S.call_opt.p + call->dense_at;
+    a.dense_out = S.s_dn_y.p; a.dense_nout = S.s_dn_n.p; a.dense_ns = call->dense_ns; a.dense_block = (int64_t)(nc * nv);
+  }
   if (hstart) {      // OPT-IN: the caller's first step size per cell (mistra_chem_integrate_hstart_ex)
     HIP_TRY(S.s_hst.reserve(nc));
     HIP_TRY(hipMemcpy(S.s_hst.p, hstart, nc * sizeof(double), hipMemcpyHostToDevice));
@@ -1447,6 +1472,11 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
     if (call->ctrl) HIP_TRY(hipMemcpy(call->ctrl + batch_start * nv, S.s_ctl.p, nc * nv * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
   if (flux) HIP_TRY(hipMemcpy(call->flux + batch_start * nr, S.s_flux.p, nc * nr * sizeof(double), hipMemcpyDeviceToHost));
+  if (dense) {      // the slot's [ns][nc] blocks into the caller's [ns][total] array
+    HIP_TRY(hipMemcpy2D(call->dense_y + batch_start * nv, call->dense_total * nv * sizeof(double), S.s_dn_y.p, nc * nv * sizeof(double), nc * nv * sizeof(double),
+                        (size_t)call->dense_ns, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(call->dense_nout + batch_start, S.s_dn_n.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
   if (t_h) {      // device: [ncell][2] (T, Hexit) then [ncell] (H)  ->  caller: [ncell][3]
     std::vector<double> h(nc * 3);
     HIP_TRY(hipMemcpy(h.data(), S.s_th.p, nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
@@ -2534,10 +2564,11 @@ int mistra_chem_method_table(int method, int* S, double* A15, double* C15, doubl
   return 0;
 }
 
-// mistra_chem_rosenbrock_ex and, with tr set (its trace members filled in), mistra_chem_rosenbrock_trace_ex; flux set: mistra_chem_rosenbrock_flux_ex
+// mistra_chem_rosenbrock_ex and, with tr set (its trace members filled in), mistra_chem_rosenbrock_trace_ex; flux set: mistra_chem_rosenbrock_flux_ex;
+// dn set (checked by the caller: check_dense): mistra_chem_rosenbrock_dense_ex
 static int rosenbrock_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                            const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
-                           int32_t* stats, double* t_h, const RosCall* tr, const CellTol* ct = nullptr, double* flux = nullptr) {
+                           int32_t* stats, double* t_h, const RosCall* tr, const CellTol* ct = nullptr, double* flux = nullptr, const DenseOut* dn = nullptr) {
   if (int rc = user_slot_method(mech, ipar)) return rc;
   if (int rc = lazy_init()) return rc;
   if (int rc = check_call(mech, ncell, true)) return rc;
@@ -2552,6 +2583,10 @@ static int rosenbrock_host(int mech, int ncell, const double* var_in, const doub
   }
   if (tr) { call.trace = true; call.cap = tr->cap; call.trace_d = tr->trace_d; call.trace_i = tr->trace_i; call.ntrace = tr->ntrace; call.ctrl = tr->ctrl; }
   call.flux = flux;
+  if (dn) {      // the sample times behind the options: one upload, read by the kernel as a series reads its times
+    call.dense_ns = dn->ns; call.dense_at = call.block.size(); call.dense_total = (size_t)ncell; call.dense_y = dn->ysample; call.dense_nout = dn->nout;
+    if (call.ierr == 1) call.block.insert(call.block.end(), dn->ts, dn->ts + dn->ns);
+  }
   if (call.ierr != 1) {      // Rosenbrock_x returns before it touches Y or the statistics (gas.f:936-1053): a result, nothing is launched
     const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
     if (tr) std::fill(tr->ntrace, tr->ntrace + nc, 0);      // no attempt was made: the logs and ctrl stay as they are
@@ -2560,6 +2595,10 @@ static int rosenbrock_host(int mech, int ncell, const double* var_in, const doub
     if (stats) std::fill(stats, stats + nc * 8, 0);
     if (t_h) std::fill(t_h, t_h + nc * 3, 0.0);
     if (flux) std::fill(flux, flux + nc * (size_t)kMech[mech].dims.nreact, 0.0);
+    if (dn) {      // no step was made: no sample is reached
+      std::fill(dn->ysample, dn->ysample + (size_t)dn->ns * nc * nv, 0.0);
+      std::fill(dn->nout, dn->nout + nc, 0);
+    }
     return 0;
   }
   return integrate_host(mech, ncell, var_in, fix, rconst, nullptr, tstart, tend, var_out, ierr, stats, t_h, nullptr, &call);
@@ -2581,11 +2620,12 @@ int mistra_chem_rosenbrock_trace_ex(int mech, int ncell, const double* var_in, c
   return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, &tr);
 }
 
-// mistra_chem_rosenbrock_device and, with tr set (device arrays), mistra_chem_rosenbrock_trace_device; d_flux set: mistra_chem_rosenbrock_flux_device
+// mistra_chem_rosenbrock_device and, with tr set (device arrays), mistra_chem_rosenbrock_trace_device; d_flux set: mistra_chem_rosenbrock_flux_device;
+// dn set (checked by the caller: check_dense; device arrays): mistra_chem_rosenbrock_dense_device
 static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                 double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
                                 int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream, const RosCall* tr,
-                                const CellTol* ct = nullptr, double* d_flux = nullptr) {
+                                const CellTol* ct = nullptr, double* d_flux = nullptr, const DenseOut* dn = nullptr) {
   if (int rc = user_slot_method(mech, ipar)) return rc;
   if (ncell == 0) return check_call(mech, 0, true);
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
@@ -2605,14 +2645,22 @@ static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, con
     if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nc * 2 * sizeof(double), st));
     if (tr) HIP_TRY(hipMemsetAsync(tr->ntrace, 0, nc * sizeof(int32_t), st));      // no attempt was made: the logs and ctrl stay as they are
     if (d_flux) HIP_TRY(hipMemsetAsync(d_flux, 0, nc * (size_t)kMech[mech].dims.nreact * sizeof(double), st));
+    if (dn) {      // no step was made: no sample is reached
+      HIP_TRY(hipMemsetAsync(dn->ysample, 0, (size_t)dn->ns * nc * nv * sizeof(double), st));
+      HIP_TRY(hipMemsetAsync(dn->nout, 0, nc * sizeof(int32_t), st));
+    }
     return 0;
   }
-  RosCallRing& R = t.S->call_ring;
+  // a dense-output call keeps its sample times behind its options: a block of the series' ring, which has the room (MISTRA_DENSE_MAX_TIMES fits)
+  static_assert(MISTRA_DENSE_MAX_TIMES <= MISTRA_SERIES_MAX_LEGS + 1, "the sample times travel in a block of the series' ring");
+  const size_t nb = call.block.size(), ns = dn ? (size_t)dn->ns : 0;
+  RosCallRing& R = dn ? t.S->series_ring : t.S->call_ring;
   int i;
   double *hb, *db;
-  HIP_TRY(R.acquire(call.block.size(), &i, &hb, &db));
-  std::memcpy(hb, call.block.data(), call.block.size() * sizeof(double));
-  HIP_TRY(hipMemcpyAsync(db, hb, call.block.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(R.acquire(dn ? nb + (size_t)MISTRA_SERIES_MAX_LEGS + 1 : nb, &i, &hb, &db));
+  std::memcpy(hb, call.block.data(), nb * sizeof(double));
+  if (dn) std::memcpy(hb + nb, dn->ts, ns * sizeof(double));      // read here: the caller's array is free when the call returns
+  HIP_TRY(hipMemcpyAsync(db, hb, (nb + ns) * sizeof(double), hipMemcpyHostToDevice, st));
   KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_var_out, d_ierr, d_stats, d_texit_hexit);
   a.hstart = d_hstart;
   a.opt = db;
@@ -2620,6 +2668,7 @@ static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, con
   if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
   if (tr) { a.trace_cap = tr->cap; a.trace_d = tr->trace_d; a.trace_i = tr->trace_i; a.ntrace = tr->ntrace; a.ctrl = tr->ctrl; }
   a.flux = d_flux;
+  if (dn) { a.times = db + nb; a.dense_out = dn->ysample; a.dense_nout = dn->nout; a.dense_ns = dn->ns; a.dense_block = (int64_t)(nc * nv); }
   const int rc = launch(*t.D, mech, a, st, call.method);
   R.mark(i, st);
   return rc;
@@ -2732,6 +2781,72 @@ int mistra_chem_rosenbrock_flux_cells_device(int mech, int ncell, const double* 
   if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
   return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
                               d_hstart, hip_stream, nullptr, &ct, d_flux);
+}
+
+// ---- dense output: Rosenbrock_x as above, plus the state at ns sample times inside the call, by the cubic Hermite interpolant between the accepted states
+//      (kernel VARIANT 7).  The same two paths with two more outputs.  Checked before anything touches a device, each refusal by its
+//      text: the mechanism (no user slot), the pointers, the count and the times against the call's interval and direction (the kernel's: Tend >= Tstart).
+static int check_dense(int mech, double tstart, double tend, int ns, const double* ts, const void* ysample, const void* nout) {
+  if (int rc = builtin_only(mech, "dense-output entries")) return rc;
+  if (ns < 1 || ns > MISTRA_DENSE_MAX_TIMES)
+    return fail("dense output: ns = " + std::to_string(ns) + ": a call takes 1 .. MISTRA_DENSE_MAX_TIMES = " + std::to_string(MISTRA_DENSE_MAX_TIMES) + " sample times");
+  if (!ts) return fail("dense output: null ts pointer (ts: [ns], a host array)");
+  if (!ysample) return fail("dense output: null ysample pointer (ysample: [ns][ncell][NVAR])");
+  if (!nout) return fail("dense output: null nout pointer (nout: [ncell])");
+  const double dir = tend >= tstart ? 1.0 : -1.0;
+  for (int k = 0; k < ns; k++)
+    if (!std::isfinite(ts[k])) return fail("dense output: ts[" + std::to_string(k) + "] is not finite");
+  for (int k = 1; k < ns; k++) {
+    if (ts[k] == ts[k - 1]) return fail("dense output: ts[" + std::to_string(k) + "] repeats ts[" + std::to_string(k - 1) + "]: the sample times are strictly monotone");
+    if (!(dir * (ts[k] - ts[k - 1]) > 0.0))
+      return fail("dense output: the sample times change direction at ts[" + std::to_string(k) + "]: they run from Tstart towards Tend");
+  }
+  for (int k = 0; k < ns; k++) {
+    if (!(dir * (ts[k] - tstart) > 0.0)) return fail("dense output: ts[" + std::to_string(k) + "] does not lie behind Tstart in the call's direction (Tstart itself is no sample)");
+    if (!(dir * (tend - ts[k]) >= 0.0)) return fail("dense output: ts[" + std::to_string(k) + "] lies beyond Tend");
+  }
+  return 0;
+}
+
+int mistra_chem_rosenbrock_dense_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                    const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
+                                    int32_t* stats, double* t_h, int ns, const double* ts, double* ysample, int32_t* nout) {
+  if (int rc = check_dense(mech, tstart, tend, ns, ts, ysample, nout)) return rc;
+  const DenseOut dn{ns, ts, ysample, nout};
+  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, nullptr, nullptr, &dn);
+}
+
+int mistra_chem_rosenbrock_dense_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                        double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
+                                        double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
+                                        void* hip_stream, int ns, const double* ts, double* d_ysample, int32_t* d_nout) {
+  if (int rc = check_dense(mech, tstart, tend, ns, ts, d_ysample, d_nout)) return rc;
+  const DenseOut dn{ns, ts, d_ysample, d_nout};
+  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                              d_hstart, hip_stream, nullptr, nullptr, nullptr, &dn);
+}
+
+int mistra_chem_rosenbrock_dense_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart,
+                                          double tend, const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar,
+                                          double* var_out, int32_t* ierr, int32_t* stats, double* t_h, int ns, const double* ts, double* ysample,
+                                          int32_t* nout) {
+  if (int rc = check_dense(mech, tstart, tend, ns, ts, ysample, nout)) return rc;
+  const CellTol ct{atol, rtol, ntol};
+  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
+  const DenseOut dn{ns, ts, ysample, nout};
+  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, &ct, nullptr, &dn);
+}
+
+int mistra_chem_rosenbrock_dense_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                              double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar,
+                                              const int32_t* ipar, double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                              const double* d_hstart, void* hip_stream, int ns, const double* ts, double* d_ysample, int32_t* d_nout) {
+  if (int rc = check_dense(mech, tstart, tend, ns, ts, d_ysample, d_nout)) return rc;
+  const CellTol ct{d_atol, d_rtol, ntol};
+  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
+  const DenseOut dn{ns, ts, d_ysample, d_nout};
+  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                              d_hstart, hip_stream, nullptr, &ct, nullptr, &dn);
 }
 
 // ---- series: nleg calls of Rosenbrock_x over times[0 .. nleg] in one launch, the state on chip from leg to leg (kernel VARIANT 5).  One path for the

@@ -115,6 +115,15 @@ struct KernelArgs {
   // reaction's rate integrated over the call, written once per cell when it leaves (a cell refused with -5: +0.0).  Read by the flux kernels only; null
   // everywhere else (capi.cpp: make_args).
   double* flux;
+  // dense output (kernel VARIANT 7, in the series units of ros_unit_kernel.hip; mistra_chem_rosenbrock_dense_ex / _device and their cells forms): the state
+  // at dense_ns sample times inside the one call from tin to tout, by the cubic Hermite interpolant between the accepted states.  The
+  // sample times are `times`[0 .. dense_ns), behind the call's options block as a series keeps its own (nleg stays 0).  Sample k of cell c is the row
+  // dense_out + k*dense_block + c*NVAR; dense_nout[c] samples were reached, the rows behind them are written +0.0.  Read by the dense kernels only; null /
+  // 0 everywhere else (capi.cpp: make_args).
+  double* dense_out;           // [dense_ns][dense_block]
+  int32_t* dense_nout;         // [ncell]
+  int32_t dense_ns;
+  int64_t dense_block;         // elements from one sample's block to the next: ncell*NVAR of the launch
 };
 
 }  // namespace mistra

@@ -1194,12 +1194,15 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // 6 = the reaction flux (ros_unit_kernel.hip; mistra_chem_rosenbrock_flux_ex / _device): variant 3 of any of the five methods that also integrates every
 // reaction's rate over the call by the trapezoid rule on the accepted states and leaves one [NREACT] row per cell in a.flux.
 // Everything it adds sits behind `if constexpr (FLUX)`.
+// 7 = dense output (instantiated in the series units of ros_unit_kernel.hip; mistra_chem_rosenbrock_dense_ex / _device): variant 3 of any of the five methods
+// that also leaves the state at a.dense_ns sample times inside the call, by the cubic Hermite interpolant between the accepted states.
+// Everything it adds sits behind `if constexpr (DENSE)`.
 // METHOD (variant 3 only): the Rosenbrock method, IPAR(4) of Rosenbrock_x (ros_methods.hpp).  Ros3 is the kernel as it was; Ros2, Ros4, Rodas3
 // and Rodas4 (the method kernels, instantiated by ros_unit_kernel.hip in translation units of their own) differ in the stage loop, in the
 // number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
 template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
-  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, FLUX = VARIANT == 6, OPT = VARIANT == 3 || TRACE || SERIES || FLUX;
+  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, FLUX = VARIANT == 6, DENSE = VARIANT == 7, OPT = VARIANT == 3 || TRACE || SERIES || FLUX || DENSE;
   static_assert(!TRACE || METHOD == kRos3, "the step-control trace is a Ros3 instantiation (ros_unit_kernel.hip)");
   static_assert(METHOD == kRos3 || (OPT && METHOD >= kRos2 && METHOD <= kRodas4), "the method kernels are options instantiations");
   constexpr double kGamma1 = METHOD == kRos3 ? kRosGamma1 : kRosMethod<METHOD>.Gamma[0];
@@ -1231,6 +1234,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     if constexpr (TRACE) {
       if (t == 0) GM_(a.ntrace)[cell] = 0;
     }
+    if constexpr (DENSE) {
+      if (t == 0) GM_(a.dense_nout)[cell] = 0;
+    }
     return;
   }
 
@@ -1255,6 +1261,17 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     const int s = q * NT + t;
     y[q] = s < NVAR ? G_(a.var_in)[(size_t)cell * NVAR + s] : 0.0;
   }
+  // VARIANT 7: the rows of the samples k0 .. dense_ns-1 of this cell as +0.0 (not reached), and the number reached
+  [[maybe_unused]] auto dense_leave = [&](int k0) {
+    for (int k = k0; k < a.dense_ns; k++) {
+#pragma unroll
+      for (int q = 0; q < SPT; q++) {
+        const int s = q * NT + t;
+        if (s < NVAR) GM_(a.dense_out)[(int64_t)k * a.dense_block + (int64_t)cell * NVAR + s] = 0.0;
+      }
+    }
+    if (t == 0) GM_(a.dense_nout)[cell] = k0;
+  };
   // VARIANT 3: AbsTol / RelTol of this thread's species, out of the call's options block: one vector pair shared by all cells as in KPP.  Fetched once, here:
   // a global load in the middle of a step would wait behind the table streams.  The scalars of the block are fetched where the step
   // control uses them (opt), not kept across the step loop.
@@ -1367,6 +1384,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
             if (r < NREACT) GM_(a.flux)[(size_t)cell * NREACT + r] = 0.0;
           }
         }
+        if constexpr (DENSE) dense_leave(0);      // no step was made: no sample is reached
         return;
       }
     }
@@ -1881,6 +1899,33 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       }
       fl_open = false;
     };
+    // VARIANT 7: Y_n and F_n of this thread's species and T_n, dh of the accepted step that is still open (its end state's F is the next step's fcn0, or
+    // formed behind the loop), and the number of samples taken so far, uniform over the workgroup.  dense_take evaluates the samples of the open step
+    // while y and f1 hold Y_{n+1}, F_{n+1}: in order, every one with Direction*(ts[k] - T) <= 0, T being T_{n+1} (all: every one left).  The operations
+    // and their order are the definition's, each rounded once.  One coalesced [NVAR] row per sample; ts by scalar loads.
+    [[maybe_unused]] double dn_y0[SPT], dn_f0[SPT];
+    [[maybe_unused]] double dn_t0 = 0.0, dn_dh = 0.0;
+    [[maybe_unused]] bool dn_open = false;
+    [[maybe_unused]] int dn_k = 0;
+    [[maybe_unused]] auto dense_take = [&](const double (&f1)[SPT], double Tn1, bool all) {
+      const auto ts = (const double __attribute__((address_space(4)))*)a.times;
+      while (dn_k < a.dense_ns) {
+        const double tk = ts[dn_k];
+        if (!all && !(Direction * (tk - Tn1) <= 0.0)) break;
+        const double th = wave_uniform((tk - dn_t0) / dn_dh);
+        const double om = 1.0 - th, e = 1.0 - 2.0 * th, w = th * om;
+#pragma unroll
+        for (int q = 0; q < SPT; q++) {
+          const int s = q * NT + t;
+          const double d = y[q] - dn_y0[q], hf0 = dn_dh * dn_f0[q], hf1 = dn_dh * f1[q];
+          const double c = (e * d - om * hf0) + th * hf1;
+          const double u = (om * dn_y0[q] + th * y[q]) - w * c;
+          if (s < NVAR) GM_(a.dense_out)[(int64_t)dn_k * a.dense_block + (int64_t)cell * NVAR + s] = u;
+        }
+        dn_k += 1;
+      }
+      dn_open = false;
+    };
     bool RejectLastH = false, RejectMoreH = false;
     int nfun = 0, njac = 0, nstp = 0, nacc = 0, nrej = 0, ndec = 0, nsol = 0, nsng = 0;
     int ierr = 1;
@@ -1923,6 +1968,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         jac();
       }
       if constexpr (FLUX) flux_close();      // X is Y_n until stage 2 stores into it, behind ros_PrepareMatrix's barriers
+      if constexpr (DENSE) {
+        if (dn_open) dense_take(fcn0, T, false);
+      }
       // ros_FunTimeDerivative_x (gas.f:1375): Fun_x does not depend on T and RCONST is frozen, so
       // dFdT = (1/Delta)*(Fun - Fcn0) is an exact +0.0; the evaluation is skipped, its count and its "+ HG*0.0" are kept.
       if constexpr (OPT) nfun += autonomous ? 1 : 2;      // Autonomous: no ros_FunTimeDerivative_x, no Fun call of its own (gas.f:1221)
@@ -2146,6 +2194,11 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         }
         if ((Err <= 1.0) || (H <= hmin())) {
           nacc += 1;
+          if constexpr (DENSE) {      // the step opens: Y_n, F_n, T_n and the signed step
+#pragma unroll
+            for (int q = 0; q < SPT; q++) { dn_y0[q] = y[q]; dn_f0[q] = fcn0[q]; }
+            dn_t0 = T; dn_dh = dh; dn_open = true;
+          }
 #pragma unroll
           for (int q = 0; q < SPT; q++) y[q] = ynew[q];
           T = wave_uniform(T + dh);
@@ -2183,6 +2236,17 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         const int r = q * NT + t;
         if (r < NREACT) GM_(a.flux)[(size_t)cell * NREACT + r] = fl_sum[q];
       }
+    }
+    // VARIANT 7: the last accepted step is still open on a normal return and on -6 / -7 (on -8 the failing step's own Fun_x has closed it): one more Fun_x
+    // at the state the call returns, not counted, and only where a sample is still to be taken.  A normal return gives every sample left to that step
+    // (Tend may lie an ulp beyond T); after an error the ones left are not reached.  dn_open and dn_k are uniform over the workgroup; the closing Fun_x
+    // stands where a step's first one would (the loop left at its head).
+    if constexpr (DENSE) {
+      if (dn_open && dn_k < a.dense_ns) {
+        fun(y, fcn0);
+        dense_take(fcn0, T, ierr == 1);
+      }
+      dense_leave(dn_k);
     }
     // ---- results
     {

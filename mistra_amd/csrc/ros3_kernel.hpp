@@ -100,6 +100,8 @@ hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_config
 //   VARIANT 4  the step-control trace, Ros3 only: plus a record per attempt (kernel_args.hpp: trace_*); a.ntrace must be set
 //   VARIANT 5  a series, any of the five methods: a loop over the legs (kernel_args.hpp: times, nleg); a.times must be set
 //   VARIANT 6  the reaction flux, any of the five methods: every reaction's rate integrated over the call (kernel_args.hpp: flux); a.flux must be set
+//   VARIANT 7  dense output, any of the five methods: the state at sample times inside the call (kernel_args.hpp: dense_*); a.times, a.dense_out and
+//              a.dense_nout must be set.  No unit of its own: specialised in the series unit of its mechanism and method
 // One explicit specialisation per <mechanism, variant, method>, each in a translation unit of its own (ros_unit_kernel.hip).  lds_configured: per
 // device AND kernel.
 template <class MT, int NT, int VARIANT, int METHOD>

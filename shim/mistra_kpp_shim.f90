@@ -55,6 +55,13 @@
 ! those entries return, bit for bit, ros_ErrorMsg_x's lines and the zero-pivot warnings included; a refused cell's FLUX column is zero.
 !     SUBROUTINE ROSENBROCK_BATCH_FLUX_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
 !     SUBROUTINE ROSENBROCK_BATCH_FLUX_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)
+! DENSE OUTPUT (mistra_chem_rosenbrock_dense_ex; INTEGRATION.md 4o): ROSENBROCK_BATCH_x / ROSENBROCK_BATCH_CELLS_x with NS, TS(NS), YS(NVAR,NCELL,NS),
+! NOUT(NCELL) behind their argument lists: the state at the NS sample times TS inside the one call, by the cubic Hermite interpolant between the accepted
+! states; NOUT(k) samples of cell k were reached, the columns behind them are zero.  Everything else is what those entries return, bit for bit,
+! ros_ErrorMsg_x's lines and the zero-pivot warnings included.
+!     SUBROUTINE ROSENBROCK_BATCH_DENSE_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS, TS, YS, NOUT)
+!     SUBROUTINE ROSENBROCK_BATCH_DENSE_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT,
+!                                                          NS, TS, YS, NOUT)
 module mistra_chem_c_api
   use iso_c_binding
   implicit none
@@ -159,6 +166,28 @@ module mistra_chem_c_api
        integer(c_int32_t) :: ierr(*), stats(*)
        integer(c_int) :: rc
      end function mistra_chem_rosenbrock_flux_cells_ex
+     function mistra_chem_rosenbrock_dense_ex(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, ns, ts, &
+          ysample, nout) bind(C, name="mistra_chem_rosenbrock_dense_ex") result(rc)
+       import :: c_int, c_double, c_int32_t
+       integer(c_int), value :: mech, ncell, ns
+       real(c_double), value :: tstart, tend
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_out(*), t_h(*), ysample(*)
+       real(c_double), intent(in) :: atol(*), rtol(*), rpar(20), ts(*)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*), nout(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_dense_ex
+     function mistra_chem_rosenbrock_dense_cells_ex(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, ntol, rpar, ipar, var_out, ierr, stats, t_h, &
+          ns, ts, ysample, nout) bind(C, name="mistra_chem_rosenbrock_dense_cells_ex") result(rc)
+       import :: c_int, c_double, c_int32_t
+       integer(c_int), value :: mech, ncell, ntol, ns
+       real(c_double), value :: tstart, tend
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_out(*), t_h(*), ysample(*)
+       real(c_double), intent(in) :: atol(*), rtol(*), rpar(20), ts(*)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*), nout(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_dense_cells_ex
      function mistra_chem_rosenbrock_series_ex(mech, ncell, var_in, fix, rconst, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, &
           stats, t_h) bind(C, name="mistra_chem_rosenbrock_series_ex") result(rc)
        import :: c_int, c_double, c_int32_t, c_ptr
@@ -397,10 +426,13 @@ contains
   ! (ros_PrepareMatrix_x's warnings, then ros_ErrorMsg_x's lines: a refusal is reported at T = Tstart, H = 0 as Rosenbrock_x does, gas.f:955)
   ! NTOL present: ATOL / RTOL hold a row of NTOL entries per cell (ROSENBROCK_BATCH_CELLS_x)
   ! FLUX present: the flux entries, which return FLUX(NREACT,NCELL) besides (ROSENBROCK_BATCH_FLUX_x, ROSENBROCK_BATCH_FLUX_CELLS_x)
-  subroutine rosenbrock_batch(mech, sfx, NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL, FLUX)
+  ! NS, TS, YS, NOUT present: the dense-output entries, which return YS(NVAR,NCELL,NS) and NOUT(NCELL) besides (ROSENBROCK_BATCH_DENSE_x, _DENSE_CELLS_x)
+  subroutine rosenbrock_batch(mech, sfx, NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL, FLUX, NS, TS, YS, NOUT)
     integer, intent(in) :: mech, NCELL
-    integer, intent(in), optional :: NTOL
-    real(c_double), optional :: FLUX(*)
+    integer, intent(in), optional :: NTOL, NS
+    real(c_double), optional :: FLUX(*), YS(*)
+    real(c_double), intent(in), optional :: TS(*)
+    integer(c_int32_t), optional :: NOUT(*)
     character(len=1), intent(in) :: sfx
     real(c_double) :: VAR(*), FIX(*), RCONST(*), TEXIT(NCELL), HEXIT(NCELL)
     real(c_double), intent(in) :: TSTART, TEND, ATOL(*), RTOL(*), RPAR(20)
@@ -411,7 +443,13 @@ contains
     integer :: k, i
     if (NCELL <= 0) return
     allocate (th(3, NCELL))
-    if (present(FLUX) .and. present(NTOL)) then
+    if (present(NS) .and. present(NTOL)) then
+       if (mistra_chem_rosenbrock_dense_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, int(NTOL, c_int), RPAR, IPAR, &
+            VAR, IERR, ISTAT, th, int(NS, c_int), TS, YS, NOUT) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_DENSE_CELLS_'//sfx)
+    else if (present(NS)) then
+       if (mistra_chem_rosenbrock_dense_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, VAR, IERR, ISTAT, th, &
+            int(NS, c_int), TS, YS, NOUT) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_DENSE_'//sfx)
+    else if (present(FLUX) .and. present(NTOL)) then
        if (mistra_chem_rosenbrock_flux_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, int(NTOL, c_int), RPAR, IPAR, &
             VAR, IERR, ISTAT, th, FLUX) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_FLUX_CELLS_'//sfx)
     else if (present(FLUX)) then
@@ -952,3 +990,64 @@ subroutine ROSENBROCK_BATCH_FLUX_CELLS_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, 
   integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *)
   call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL, FLUX)
 end subroutine ROSENBROCK_BATCH_FLUX_CELLS_t
+
+! ---- dense output: ROSENBROCK_BATCH_x / ROSENBROCK_BATCH_CELLS_x with NS, TS(NS), YS(NVAR,NCELL,NS), NOUT(NCELL) behind their argument lists
+subroutine ROSENBROCK_BATCH_DENSE_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS, TS, YS, NOUT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NS
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), TEXIT(*), HEXIT(*), TS(*), YS(102, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *), NOUT(*)
+  call rosenbrock_batch(0, 'g', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS=NS, TS=TS, YS=YS, NOUT=NOUT)
+end subroutine ROSENBROCK_BATCH_DENSE_g
+
+subroutine ROSENBROCK_BATCH_DENSE_CELLS_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS, TS, YS, NOUT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL, NS
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), TEXIT(*), HEXIT(*), TS(*), YS(102, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *), NOUT(*)
+  call rosenbrock_batch(0, 'g', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL=NTOL, NS=NS, TS=TS, YS=YS, NOUT=NOUT)
+end subroutine ROSENBROCK_BATCH_DENSE_CELLS_g
+
+subroutine ROSENBROCK_BATCH_DENSE_a(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS, TS, YS, NOUT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NS
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), TEXIT(*), HEXIT(*), TS(*), YS(257, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *), NOUT(*)
+  call rosenbrock_batch(1, 'a', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS=NS, TS=TS, YS=YS, NOUT=NOUT)
+end subroutine ROSENBROCK_BATCH_DENSE_a
+
+subroutine ROSENBROCK_BATCH_DENSE_CELLS_a(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS, TS, YS, NOUT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL, NS
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), TEXIT(*), HEXIT(*), TS(*), YS(257, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *), NOUT(*)
+  call rosenbrock_batch(1, 'a', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL=NTOL, NS=NS, TS=TS, YS=YS, NOUT=NOUT)
+end subroutine ROSENBROCK_BATCH_DENSE_CELLS_a
+
+subroutine ROSENBROCK_BATCH_DENSE_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS, TS, YS, NOUT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NS
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), TEXIT(*), HEXIT(*), TS(*), YS(417, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *), NOUT(*)
+  call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS=NS, TS=TS, YS=YS, NOUT=NOUT)
+end subroutine ROSENBROCK_BATCH_DENSE_t
+
+subroutine ROSENBROCK_BATCH_DENSE_CELLS_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS, TS, YS, NOUT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL, NS
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), TEXIT(*), HEXIT(*), TS(*), YS(417, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *), NOUT(*)
+  call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL=NTOL, NS=NS, TS=TS, YS=YS, NOUT=NOUT)
+end subroutine ROSENBROCK_BATCH_DENSE_CELLS_t

@@ -20,6 +20,10 @@
 !                                                      the cells as for <G|A|T>.  ntol = 0: ONE call of ROSENBROCK_BATCH_FLUX_x with the pair; ntol = 1 or NVAR: ONE call of
 !                                                      ROSENBROCK_BATCH_FLUX_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin = per cell VAR, TEXIT,
 !                                                      HEXIT, IERR, the 8 statistics, FLUX(NREACT)
+!          shim_driver <IG|IA|IT> <in.bin> <out.bin>   Rosenbrock_x with dense output: in.bin = IPAR(20), RPAR(20), ATOL(NVAR), RTOL(NVAR), TSTART, TEND, ncell, ntol, ns, TS(ns),
+!                                                      then the cells as for <G|A|T>.  ntol = 0: ONE call of ROSENBROCK_BATCH_DENSE_x with the pair; ntol = 1 or NVAR: ONE call
+!                                                      of ROSENBROCK_BATCH_DENSE_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin = per cell VAR, TEXIT,
+!                                                      HEXIT, IERR, the 8 statistics, NOUT, then YS(NVAR, ncell, ns)
 !          shim_driver <Eg|Ea|Et> <in.bin> <out.bin>   in.bin = ncell, then per cell VAR, FIX, ENV (the vector MISTRA_RATES_ENV_x packs,
 !                                                      mistra_kpp_rates.f90): UPDATE_RCONST_BATCH_x, then INTEGRATE_BATCH_ENV_x (rates and
 !                                                      integrator on the device, RCONST never crosses PCIe); out.bin = per cell VAR,
@@ -91,6 +95,13 @@ program shim_driver
      case ('G'); call run_flux(0, 102, 3, 331, trim(fin), trim(fout))
      case ('A'); call run_flux(1, 257, 5, 979, trim(fin), trim(fout))
      case ('T'); call run_flux(2, 417, 7, 1627, trim(fin), trim(fout))
+     case default; stop 'mechanism must be G, A or T'
+     end select
+  case ('I')
+     select case (a1(2:2))
+     case ('G'); call run_dense(0, 102, 3, 331, trim(fin), trim(fout))
+     case ('A'); call run_dense(1, 257, 5, 979, trim(fin), trim(fout))
+     case ('T'); call run_dense(2, 417, 7, 1627, trim(fin), trim(fout))
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('K', 'H', 'Q', 'V', 'S', 'C', 'R')
@@ -342,6 +353,56 @@ contains
     end do
     close (11); close (12)
   end subroutine run_flux
+  subroutine run_dense(mech, NVAR, NFIX, NREACT, fin, fout)
+    integer, intent(in) :: mech, NVAR, NFIX, NREACT
+    character(len=*), intent(in) :: fin, fout
+    double precision :: ropt(40), tt(5)
+    double precision, allocatable :: ATOL(:), RTOL(:), AROW(:, :), RROW(:, :), VAR(:, :), FIX(:, :), RCONST(:, :), TEXIT(:), HEXIT(:), TS(:), YS(:, :, :), rec(:)
+    integer :: IPAR(20), n, ntol, ns, i
+    integer, allocatable :: IERR(:), ISTAT(:, :), NOUT(:)
+    open (11, file=fin, access='stream', form='unformatted', status='old')
+    open (12, file=fout, access='stream', form='unformatted', status='replace')
+    allocate (ATOL(NVAR), RTOL(NVAR))
+    read (11) ropt, ATOL, RTOL, tt      ! tt: TSTART, TEND, ncell, ntol, ns
+    IPAR = int(ropt(1:20))
+    n = int(tt(3))
+    ntol = int(tt(4))
+    ns = int(tt(5))
+    allocate (TS(ns))
+    read (11) TS
+    allocate (VAR(NVAR, n), FIX(NFIX, n), RCONST(NREACT, n), TEXIT(n), HEXIT(n), IERR(n), ISTAT(8, n), NOUT(n), YS(NVAR, n, ns))
+    allocate (rec(NVAR + NFIX + NREACT), AROW(max(ntol, 1), n), RROW(max(ntol, 1), n))
+    YS = -7.25d0
+    NOUT = -77
+    do i = 1, n
+       read (11) rec
+       VAR(:, i) = rec(1:NVAR)
+       FIX(:, i) = rec(NVAR + 1:NVAR + NFIX)
+       RCONST(:, i) = rec(NVAR + NFIX + 1:)
+       if (ntol > 0) then
+          AROW(:, i) = ATOL(1:ntol)
+          RROW(:, i) = RTOL(1:ntol)
+       end if
+    end do
+    if (ntol == 0) then
+       select case (mech)
+       case (0); call ROSENBROCK_BATCH_DENSE_g(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT, ns, TS, YS, NOUT)
+       case (1); call ROSENBROCK_BATCH_DENSE_a(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT, ns, TS, YS, NOUT)
+       case (2); call ROSENBROCK_BATCH_DENSE_t(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT, ns, TS, YS, NOUT)
+       end select
+    else
+       select case (mech)
+       case (0); call ROSENBROCK_BATCH_DENSE_CELLS_g(n, VAR, FIX, RCONST, tt(1), tt(2), AROW, RROW, ntol, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT, ns, TS, YS, NOUT)
+       case (1); call ROSENBROCK_BATCH_DENSE_CELLS_a(n, VAR, FIX, RCONST, tt(1), tt(2), AROW, RROW, ntol, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT, ns, TS, YS, NOUT)
+       case (2); call ROSENBROCK_BATCH_DENSE_CELLS_t(n, VAR, FIX, RCONST, tt(1), tt(2), AROW, RROW, ntol, ropt(21:40), IPAR, TEXIT, HEXIT, IERR, ISTAT, ns, TS, YS, NOUT)
+       end select
+    end if
+    do i = 1, n
+       write (12) VAR(:, i), TEXIT(i), HEXIT(i), dble(IERR(i)), dble(ISTAT(:, i)), dble(NOUT(i))
+    end do
+    write (12) YS
+    close (11); close (12)
+  end subroutine run_dense
   subroutine run_series(mech, NVAR, NFIX, NREACT, fin, fout)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT
     character(len=*), intent(in) :: fin, fout

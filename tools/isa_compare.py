@@ -10,6 +10,7 @@ mistra_amd/csrc/ros3_kernel.hip at two commits), and the resources of the method
     python tools/isa_compare.py --series            per series unit (variant 5): the same figures of the series kernel beside its VARIANT 3
                                                     sibling's — the product unit's options kernel for Ros3, the method unit's for the other four
     python tools/isa_compare.py --flux              per flux unit (variant 6): the same table for the flux kernel
+    python tools/isa_compare.py --dense             per series unit: the same table for the dense-output kernel (VARIANT 7) the unit also holds
 
 A kernel's mangled name carries its template arguments: the METHOD parameter added to ros3_integrate_kernel (default Ros3 = 2) is cut out of the
 new listing's names before the comparison; nothing else is normalised."""
@@ -95,10 +96,11 @@ def listings(outdir):
             print(path)
 
 
-def _integrator(unit, tmp):
-    """the metadata of the one integrating kernel of a variant unit"""
-    ks = [k for n, k in _kernels(listing(unit, os.path.join(tmp, "u.s"))) if "ros3_integrate_kernel" in n]
-    assert len(ks) == 1, (unit, len(ks))
+def _integrator(unit, tmp, variant=None):
+    """the metadata of the integrating kernel of a variant unit: the unit's own VARIANT, or the dense-output kernel (variant=7) a series unit also holds"""
+    tag = "ELi%dELi%dEEEv" % (variant or unit.variant, unit.method)
+    ks = [k for n, k in _kernels(listing(unit, os.path.join(tmp, "u.s"))) if "ros3_integrate_kernel" in n and tag in n]
+    assert len(ks) == 1, (unit, variant, len(ks))
     return ks[0]
 
 
@@ -111,9 +113,9 @@ def methods():
             print("%-5s %-7s %6d %6d %8d %12d %10d" % ((MECHS[u.mech], NAMES[u.method]) + tuple(k[c] for c in COLS)))
 
 
-def beside_variant_3(variant, what):
-    """per unit of `variant`: the kernel's figures beside its VARIANT 3 sibling's"""
-    print("%-4s %-7s | %-40s | %s" % ("mech", "method", "VARIANT 3 (the options kernel)", "VARIANT %d (the %s kernel)" % (variant, what)))
+def beside_variant_3(variant, what, kernel=None):
+    """per unit of `variant`: the figures of its kernel (kernel: of the VARIANT `kernel` instantiation it also holds) beside its VARIANT 3 sibling's"""
+    print("%-4s %-7s | %-40s | %s" % ("mech", "method", "VARIANT 3 (the options kernel)", "VARIANT %d (the %s kernel)" % (kernel or variant, what)))
     print("%-4s %-7s | %5s %5s %8s %7s %10s | %5s %5s %8s %7s %10s   (LDS: dynamic, LdsLayout<MT, NT>::TOTAL doubles, the same for both)" %
           (("", "") + ("VGPRs", "SGPRs", "scratch", "spilled", "static LDS") * 2))
     with tempfile.TemporaryDirectory() as tmp:
@@ -123,7 +125,7 @@ def beside_variant_3(variant, what):
                 sib, = [k for n, k in product if re.search(r"ros3_integrate_kernelINS_\d+%sTraitsELi\d+ELi3ELi2E" % MECHS[u.mech].capitalize(), n)]
             else:
                 sib = _integrator(u._replace(variant=3), tmp)
-            new = _integrator(u, tmp)
+            new = _integrator(u, tmp, kernel)
             print("%-4s %-7s | %5d %5d %8d %7d %10d | %5d %5d %8d %7d %10d" % ((MECHS[u.mech], NAMES[u.method]) + tuple(sib[c] for c in COLS) + tuple(new[c] for c in COLS)))
 
 
@@ -134,6 +136,8 @@ if __name__ == "__main__":
         beside_variant_3(5, "series")
     elif "--flux" in sys.argv:
         beside_variant_3(6, "flux")
+    elif "--dense" in sys.argv:
+        beside_variant_3(5, "dense-output", kernel=7)
     elif "--listings" in sys.argv:
         listings(sys.argv[sys.argv.index("--listings") + 1])
     else:

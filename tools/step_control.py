@@ -9,6 +9,7 @@
     ... --yardstick                                                                          also the distance of the end state from Rodas4 at RelTol 1e-7
     python tools/step_control.py aer --workload 4096                                         cells 0 .. 4095 of the synthetic workload (mistra_amd/workload.py)
     ... --series 4                                                                           the yardstick distance at 4 equal sub-times, not at the end only
+    ... --dense 4                                                                            the same table with the run's side sampled inside ONE call (dense output)
     ... --cpu                                                                                the Python restatement (tests/ros_trace_py.py) instead of the GPU
 
 Prints the attempts per cell and, for the species that controlled the most attempts (the species with the largest term of ros_ErrorNorm_x's sum):
@@ -24,7 +25,12 @@ the reference algorithm at the run's tolerances, not of this library: nothing is
 --series K prints that distance at K equal sub-times of the interval instead: the run's options and the yardstick's each as ONE series of K legs
 (mistra_chem_rosenbrock_series_ex, INTEGRATION.md §4m: K calls of Rosenbrock_x on the chained state in one launch), so the table shows where inside
 the chemistry step the run leaves the yardstick.  Every leg is a call of its own — its first step is RPAR(3) again — so the last row is the distance
-after K calls, not the single call's."""
+after K calls, not the single call's.
+
+--dense K prints the same table with the run's side taken from ONE call of Rosenbrock_x over the whole interval, sampled at the K sub-times by the dense
+output (mistra_chem_rosenbrock_dense_ex, INTEGRATION.md §4o: the cubic Hermite interpolant between the call's own accepted states).  Looking does not
+perturb the integration: the last row IS the single call's end state.  The yardstick stays a Rodas4 series.  Rows a cell does not reach (IERR < 0) are
+left out of the row's maximum and counted."""
 import argparse
 import os
 import sys
@@ -159,6 +165,31 @@ def series_states(mech, var, fix, rconst, times, opts, cpu, atol_rel=None):
     return out
 
 
+def dense_states(mech, var, fix, rconst, ts, tstart, tend, opts, cpu, atol_rel=None):
+    """the cells' states at ts inside ONE call of Rosenbrock_x from tstart to tend with opts -> (samples [ns, ncell, NVAR], nout [ncell]); atol_rel: AbsTol
+    per cell from the state the call receives.  --cpu: the restatement with the sampling (tests/ros_dense_py.py)"""
+    ipar, rpar, atol, rtol = opts
+    per_cell = None if atol_rel is None else cell_atol_rows(mech, var, atol_rel)
+    if not cpu:
+        from mistra_amd import chem
+        if per_cell is None:
+            r = chem.rosenbrock_dense(mech, var, fix, rconst, tstart, tend, ts, ipar, rpar, atol, rtol)
+        else:
+            r = chem.rosenbrock_dense_cells(mech, var, fix, rconst, tstart, tend, ts, ipar, rpar, per_cell, np.full_like(per_cell, rtol[0]))
+        return r[2], r[3]
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import ros_dense_py as RD
+    from mistra_amd import mechtab
+    from oracle.oracle import Oracle
+    o, diag = Oracle(mech), mechtab.load(mech).diag
+    out, nout = np.zeros((len(ts),) + var.shape), np.zeros(var.shape[0], np.int32)
+    for c in range(var.shape[0]):
+        at = atol if per_cell is None else np.full_like(atol, per_cell[c, 0])
+        r = RD.rosenbrock(o, diag, var[c], fix[c], rconst[c], ts, ipar, rpar, at, rtol, tstart, tend)
+        out[:, c], nout[c] = r[5], r[6]
+    return out, nout
+
+
 def distances(got, want):
     """-> (largest relative difference over the species above 1e-3 of their cell's maximum, largest over all species with the floor 1e-12 x max|c|):
     the two measures of tests/conftest.py (rel_diff), NaN where nothing can be compared"""
@@ -233,6 +264,7 @@ def main(argv=None):
     ap.add_argument("--cpu", action="store_true", help="run the Python restatement instead of the GPU")
     ap.add_argument("--yardstick", action="store_true", help="also print the end state's distance from Rodas4 at RelTol 1e-7, INTEGRATE_x's AbsTol")
     ap.add_argument("--series", type=int, metavar="K", help="print the yardstick distance at K equal sub-times (one series of K legs each)")
+    ap.add_argument("--dense", type=int, metavar="K", help="the same table, the run's side sampled at the K sub-times inside ONE call (dense output)")
     a = ap.parse_args(argv)
     if a.atol is not None and a.atol_rel is not None:
         ap.error("--atol and --atol-rel exclude each other")
@@ -262,6 +294,21 @@ def main(argv=None):
         for k in range(a.series):
             major, every = distances(got[k], want[k])
             print("%12g  %-28.3e %.3e" % (times[k + 1], major, every))
+    if a.dense:
+        if a.dense < 1:
+            ap.error("--dense K: K >= 1")
+        times = np.linspace(a.tstart, a.tend, a.dense + 1)
+        yopts = options(a.mech, None, YARDSTICK_RTOL)
+        yopts[0][3] = YARDSTICK_METHOD
+        got, nout = dense_states(a.mech, var, fix, rconst, times[1:], a.tstart, a.tend, opts, a.cpu, a.atol_rel)
+        want = series_states(a.mech, var, fix, rconst, times, yopts, a.cpu)
+        print("distance from the yardstick at %d sub-times, dense output: the run's side sampled inside ONE call, the yardstick one series of %d calls "
+              "(Rodas4, RelTol = %g, AbsTol = 1e-25)" % (a.dense, a.dense, YARDSTICK_RTOL))
+        print("%12s  %-28s %-34s %s" % ("t [s]", "species above 1e-3 of cell max", "all species, floor 1e-12 x max|c|", "cells that reached it"))
+        for k in range(a.dense):
+            hit = nout > k
+            major, every = distances(got[k][hit], want[k][hit]) if hit.any() else (float("nan"), float("nan"))
+            print("%12g  %-28.3e %-34.3e %d" % (times[k + 1], major, every, int(hit.sum())))
     return 0
 
 
