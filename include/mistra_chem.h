@@ -381,6 +381,33 @@ int mistra_chem_rosenbrock_dense_cells_device(int mech, int ncell, const double*
                                               const double* d_hstart, void* hip_stream, int ns, const double* ts /* host */, double* d_ysample,
                                               int32_t* d_nout);
 
+/* THE OPERATORS: KPP's four building blocks — Fun_x, Jac_SP_x, KppDecomp_x, KppSolve_x — at a state the caller gives, for a batch of cells, with no
+ * integration.  Per cell, V = var, F = fix, RCT = rconst:
+ *     vdot [ncell][NVAR]        Fun_x(V, F, RCT)
+ *     jvs  [ncell][LU_NONZERO]  Jac_SP_x(V, F, RCT) in KPP's slot order (LU_CROW / LU_ICOL: mistra_chem_jac_pattern); the fill-in slots are +0.0
+ *     x    [fun_rhs + nrhs][ncell][NVAR]  (the series' block layout)   A x_j = b_j with A = shift*I - J, J the matrix of jvs: ros_PrepareMatrix_x's Ghimj
+ *          for shift = 1/(Direction*H*gamma), backward Euler's matrix for shift = 1/h.  A is factorised once per cell, then solved for every right-hand
+ *          side: the cell's own vdot (fun_rhs /= 0: row 0 of x) followed by the nrhs rows of rhs [nrhs][ncell][NVAR].  shift may have any sign and be zero.
+ *     ising [ncell]             what KppDecomp_x returns in IER: the first row (1-based) whose PREPARED diagonal is exactly zero, otherwise 0.  Where
+ *          ising > 0 no factorisation runs and the cell's rows of x are +0.0; vdot and jvs are produced all the same.  A pivot that becomes zero, tiny
+ *          or non-finite DURING the elimination is not flagged, exactly as in KPP: the rows then hold what the arithmetic gives (inf / NaN).
+ * vdot and jvs are the values the integrator's own first Fun_x / Jac_SP_x of a step form, and the fun_rhs row is that step's K(1) for its shift, bit for bit
+ * (the right-hand side rides through the factorisation as a step's stage 1 does).  Every row of rhs goes through the full KppSolve_x: its result does not
+ * depend on where the row stands, on the other rows, or on what else the call asks for.
+ * vdot, jvs: each may be NULL (not wanted).  x NULL: no solve; nrhs, rhs, shift and ising are then not looked at.  nshift: 1 (one shift shared by all cells)
+ * or ncell.  Refused with a text of its own before a device is touched: x, vdot and jvs all NULL; x with fun_rhs + nrhs < 1; nrhs < 0 or above
+ * MISTRA_OPS_MAX_RHS; nrhs > 0 with a NULL rhs; a NULL ising or shift with x; nshift neither 1 nor ncell; (_ex) a shift that is not finite.
+ * _device: device arrays, shift included (nshift entries); asynchronous on the stream, no options block and so no in-flight limit.  _ex splits the batch
+ * over the device slots as mistra_chem_rosenbrock_ex does and fails while a column step of the mechanism is open.  Nothing process-wide is read: the
+ * options in force, the integrator policy and step reuse are not involved.  No user slot: both ids fail with the slot's text, mistra_chem_jac_pattern too.
+ * mistra_chem_jac_pattern needs no device and no mistra_chem_init: it reads <mechanism directory>/<name>.mech; each pointer may be NULL. */
+#define MISTRA_OPS_MAX_RHS 256
+int mistra_chem_jac_pattern(int mech, int32_t* crow /* [NVAR+1] */, int32_t* icol /* [LU_NONZERO] */, int32_t* diag /* [NVAR] */);   /* 1-based: LU_CROW, LU_ICOL, LU_DIAG */
+int mistra_chem_ops_ex(int mech, int ncell, const double* var, const double* fix, const double* rconst, double* vdot, double* jvs, int nshift,
+                       const double* shift, int fun_rhs, int nrhs, const double* rhs, double* x, int32_t* ising);
+int mistra_chem_ops_device(int mech, int ncell, const double* d_var, const double* d_fix, const double* d_rconst, double* d_vdot, double* d_jvs, int nshift,
+                           const double* d_shift, int fun_rhs, int nrhs, const double* d_rhs, double* d_x, int32_t* d_ising, void* hip_stream);
+
 /* AbsTol from each cell's own state, on the device in stream order: d_atol[c] = max(floor, factor * max_i |d_var[c][i]|), i over NVAR.  NaN entries
  * are ignored; a cell with no positive entry gets floor.  The product is one rounding of two exact operands, so the host restatement
  * max(floor, factor * fmax-reduction of |var|) gives the same bits.  factor or floor that is not finite and positive fails with a text before a device

@@ -146,6 +146,10 @@ def lib():
             L.mistra_chem_rosenbrock_dense_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [C.c_int, _dp, vp, vp]
             L.mistra_chem_rosenbrock_dense_cells_ex.argtypes = L.mistra_chem_rosenbrock_cells_ex.argtypes + [C.c_int, _dp, _dp, _ip]
             L.mistra_chem_rosenbrock_dense_cells_device.argtypes = L.mistra_chem_rosenbrock_cells_device.argtypes + [C.c_int, _dp, vp, vp]
+        if hasattr(L, "mistra_chem_ops_ex"):
+            L.mistra_chem_jac_pattern.argtypes = [C.c_int, _ip, _ip, _ip]
+            L.mistra_chem_ops_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip]
+            L.mistra_chem_ops_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
         if hasattr(L, "mistra_chem_set_policy"):
             L.mistra_chem_set_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
             L.mistra_chem_check_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
@@ -997,6 +1001,139 @@ def set_step_memory(mech, h):
 def debug_set_max_steps(n=0):
     """Test hook: Max_no_steps of the integrator (0 = the reference's 100000); makes IERR = -6 reachable (include/mistra_chem.h)."""
     _check(lib().mistra_chem_debug_set_max_steps(int(n)))
+
+
+# ---- the operators: KPP's building blocks at a state the caller gives (include/mistra_chem.h: mistra_chem_ops_ex / _device; INTEGRATION.md §4p)
+OPS_MAX_RHS = 256      # MISTRA_OPS_MAX_RHS
+OpsResult = namedtuple("OpsResult", "vdot jvs x ising")
+
+
+def jac_pattern(mech):
+    """-> (crow [NVAR+1], icol [LU_NONZERO], diag [NVAR]), KPP's LU_CROW, LU_ICOL and LU_DIAG, 1-based: slot k of jvs is entry (row with
+    crow[row-1] <= k+1 < crow[row], icol[k]) of the Jacobian.  Needs no device."""
+    mid, name = _mech_id(mech)
+    L = lib()
+    if mid >= 3:      # (a user slot: refused by the library with the slot's text)
+        _check(L.mistra_chem_jac_pattern(mid, None, None, None))
+    nvar, _, _, nnz = DIMS[name]
+    crow, icol, diag = np.zeros(nvar + 1, np.int32), np.zeros(nnz, np.int32), np.zeros(nvar, np.int32)
+    _check(L.mistra_chem_jac_pattern(mid, crow.ctypes.data_as(_ip), icol.ctypes.data_as(_ip), diag.ctypes.data_as(_ip)))
+    return crow, icol, diag
+
+
+def ops(mech, var, fix, rconst, want_vdot=True, want_jvs=False, shift=None, rhs=None, fun_rhs=False, vdot=None, jvs=None, x=None, ising=None):
+    """Fun_x, Jac_SP_x and solves with A = shift*I - J at the state given, per cell, without integrating -> OpsResult(vdot, jvs, x, ising); what is
+    not asked for is None.
+      want_vdot   vdot [ncell, NVAR] = Fun_x
+      want_jvs    jvs [ncell, LU_NONZERO] = Jac_SP_x in KPP's slot order (jac_pattern), fill-in slots +0.0
+      shift       set: the solve.  A number or one entry (shared by all cells), or [ncell].  x [fun_rhs + nrhs, ncell, NVAR]: the cell's own vdot as
+                  right-hand side (fun_rhs: row 0), then the rows of rhs [nrhs, ncell, NVAR] ([ncell, NVAR]: one row).  ising [ncell]: KppDecomp_x's IER,
+                  the first row (1-based) whose diagonal of A is exactly zero, else 0; such a cell's rows of x are +0.0.
+    numpy arrays go to the host entry, torch CUDA tensors to the device entry on the current stream (shift then a tensor of 1 or ncell entries, or a
+    number).  vdot, jvs, x, ising: the caller's own output arrays (contiguous, at least the size named above; the call writes the leading part and
+    nothing else).  Not for a user mechanism slot."""
+    mid, name = _mech_id(mech)
+    nvar, nfix, nreact, nnz = DIMS[name]
+    L = lib()
+    solve = shift is not None
+    tt = _is_torch(var)
+    if tt:
+        import torch
+        if not var.is_cuda:
+            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
+        for a, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
+            if a.dtype != torch.float64 or not a.is_contiguous() or a.shape[-1] != n or a.device != var.device:
+                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
+        ncell = var.numel() // nvar
+        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
+            raise MistraChemError("cell counts of var / fix / rconst differ")
+    else:
+        var = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+        ncell = var.shape[0]
+        fix = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
+        rconst = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
+
+    def own(a, dtype, what):      # a caller's input / output array as it stands
+        if tt:
+            if not _is_torch(a) or a.dtype != dtype or not a.is_contiguous() or a.device != var.device:
+                raise MistraChemError("%s: a contiguous %s tensor on the cells' device expected" % (what, dtype))
+        elif not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous:
+            raise MistraChemError("%s: a C-contiguous numpy array of %s expected" % (what, np.dtype(dtype).name))
+        return a
+
+    f64, i32 = (torch.float64, torch.int32) if tt else (np.float64, np.int32)
+
+    def new(shape, dtype):
+        return torch.empty(shape, dtype=dtype, device=var.device) if tt else np.zeros(shape, dtype)
+
+    def size(a):
+        return a.numel() if tt else a.size
+
+    def out_array(given, want, shape, dtype, what):
+        if not want:
+            return None, None
+        if given is None:
+            a = new(shape, dtype)
+            return a, a
+        a = own(given, dtype, what)
+        n = int(np.prod(shape))
+        if size(a) < n:
+            raise MistraChemError("%s: at least %d entries expected" % (what, n))
+        return a, a.reshape(-1)[:n].reshape(shape)
+
+    nrhs = 0
+    if solve and rhs is not None:
+        rhs = own(rhs if tt else np.ascontiguousarray(rhs, np.float64), f64, "rhs")
+        if size(rhs) % (ncell * nvar if ncell else 1) or (ncell == 0 and size(rhs)):
+            raise MistraChemError("rhs: [nrhs, ncell, NVAR] expected")
+        nrhs = size(rhs) // (ncell * nvar) if ncell else 0
+    nrow = (1 if fun_rhs else 0) + nrhs
+    if solve:
+        if not tt:
+            shift = np.ascontiguousarray(shift, np.float64).reshape(-1)
+        elif not _is_torch(shift):
+            shift = torch.tensor([float(shift)], dtype=torch.float64, device=var.device)
+        else:
+            shift = own(shift.reshape(-1), f64, "shift")
+        nshift = size(shift)
+    else:
+        nshift = 1
+    vd_a, vd = out_array(vdot, want_vdot, (ncell, nvar), f64, "vdot")
+    jv_a, jv = out_array(jvs, want_jvs, (ncell, nnz), f64, "jvs")
+    # (a solve without a right-hand side is the library's to refuse: the array still has to exist)
+    x_a, xv = out_array(x, solve, (max(nrow, 0), ncell, nvar), f64, "x")
+    is_a, isv = out_array(ising, solve, (ncell,), i32, "ising")
+    if solve and x_a is not None and size(x_a) == 0:
+        x_a = new((1,), f64)
+    if solve and size(is_a) == 0:
+        is_a = new((1,), i32)
+    if tt:
+        init(var.device.index or 0)
+        _check(L.mistra_chem_ops_device(mid, ncell, _p(var), _p(fix), _p(rconst), _p(vd_a), _p(jv_a), int(nshift), _p(shift) if solve else None,
+                                        1 if fun_rhs else 0, int(nrhs), _p(rhs) if nrhs else None, _p(x_a), _p(is_a), _stream(var)))
+    else:
+        def hp(a, t=_dp):
+            return None if a is None else a.ctypes.data_as(t)
+        # (the arguments are checked by the library before it looks for a device: no init() in front of them)
+        _check(L.mistra_chem_ops_ex(mid, ncell, hp(var), hp(fix), hp(rconst), hp(vd_a), hp(jv_a), int(nshift), hp(shift) if solve else None,
+                                    1 if fun_rhs else 0, int(nrhs), hp(rhs) if nrhs else None, hp(x_a), hp(is_a, _ip)))
+    return OpsResult(vd, jv, xv, isv)
+
+
+def fun(mech, var, fix, rconst):
+    """Fun_x per cell -> vdot [ncell, NVAR]"""
+    return ops(mech, var, fix, rconst, True, False).vdot
+
+
+def jac_sp(mech, var, fix, rconst):
+    """Jac_SP_x per cell -> jvs [ncell, LU_NONZERO] in KPP's slot order (jac_pattern)"""
+    return ops(mech, var, fix, rconst, False, True).jvs
+
+
+def linsolve(mech, var, fix, rconst, shift, rhs=None, fun_rhs=False):
+    """(shift*I - J) x = b per cell, J = Jac_SP_x at the state given; b: the cell's own Fun_x (fun_rhs), then the rows of rhs -> (x, ising)"""
+    r = ops(mech, var, fix, rconst, False, False, shift=shift, rhs=rhs, fun_rhs=fun_rhs)
+    return r.x, r.ising
 
 
 FirstStep = namedtuple("FirstStep", "fcn0 ghimj lu r k1 k2 k3 err h var ierr stats")

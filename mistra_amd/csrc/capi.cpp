@@ -64,20 +64,20 @@ bool traits_match(const MechTables& t, int n_jnz, int tail_regs, bool scale_pass
 using LaunchFn = hipError_t (*)(const KernelArgs&, hipStream_t, bool*);
 // The kernels of ros_unit_kernel.hip, [kernel VARIANT 3 .. 6][IPAR(4) resolved, ros_methods.hpp]: 3 the method kernels (Ros2, Ros4, Rodas3, Rodas4), 4 the
 // step-control trace (Ros3), 5 the series and 6 the flux kernels (all five methods), 7 the dense-output kernels (all five methods; they live in the series
-// units).  nullptr: not built.
-constexpr int kVariants = 8, kMethods = 6;
+// units), 8 the operator kernels (Ros3's slot; they live in the trace units).  nullptr: not built.
+constexpr int kVariants = 9, kMethods = 6;
 struct UnitTable {
   LaunchFn fn[kVariants][kMethods] = {};
 };
 template <class MT, int NT, int VARIANT, int METHOD>
 constexpr void add_unit(UnitTable& t) {
-  if constexpr ((VARIANT != 3 || METHOD != kRos3) && (VARIANT != 4 || METHOD == kRos3)) t.fn[VARIANT][METHOD] = &launch_ros_unit<MT, NT, VARIANT, METHOD>;
+  if constexpr ((VARIANT != 3 || METHOD != kRos3) && ((VARIANT != 4 && VARIANT != 8) || METHOD == kRos3)) t.fn[VARIANT][METHOD] = &launch_ros_unit<MT, NT, VARIANT, METHOD>;
 }
 template <class MT, int NT, int... METHOD>
 constexpr UnitTable unit_table(std::integer_sequence<int, METHOD...>) {
   UnitTable t;
   (..., (add_unit<MT, NT, 3, METHOD + 1>(t), add_unit<MT, NT, 4, METHOD + 1>(t), add_unit<MT, NT, 5, METHOD + 1>(t), add_unit<MT, NT, 6, METHOD + 1>(t),
-        add_unit<MT, NT, 7, METHOD + 1>(t)));
+        add_unit<MT, NT, 7, METHOD + 1>(t), add_unit<MT, NT, 8, METHOD + 1>(t)));
   return t;
 }
 static_assert(kRos2 == 1 && kRodas4 == 5, "IPAR(4) resolved: 1 .. 5");
@@ -709,6 +709,7 @@ struct MechState {
   DevBuf<double> s_flux;                   // ... and of mistra_chem_rosenbrock_flux_ex: the block's flux rows
   DevBuf<double> s_dn_y;                   // ... and of mistra_chem_rosenbrock_dense_ex: the samples' blocks of this slot's cells, the numbers reached
   DevBuf<int32_t> s_dn_n;
+  DevBuf<double> s_ops;                    // ... and of mistra_chem_ops_ex: vdot | jvs | shift | rhs | x of this slot's cells
   // where the zero-pivot rows of the LAST host-buffer call of this slot are (mistra_chem_singular_rows): cells [sing_start,
   // sing_start + sing_count) of the caller's batch in s_sing, or the one cell of the COMMON-block call in one_sing
   size_t sing_start = 0, sing_count = 0;
@@ -734,7 +735,7 @@ struct MechState {
     step_mem.release(); step_n = 0;
     s_hst.release(); s_tol.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
-    s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release(); s_flux.release(); s_dn_y.release(); s_dn_n.release();
+    s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release(); s_flux.release(); s_dn_y.release(); s_dn_n.release(); s_ops.release();
     sing_count = 0; sing_one = false;
     drive.release(); one.release();
     pend = PendingDrive{};      // (a step issued and never fetched dies with its buffers)
@@ -1189,7 +1190,8 @@ int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, in
       {"step-control trace", "no trace kernel for this Rosenbrock method"},
       {"series of Rosenbrock_x calls", "no series kernel for this Rosenbrock method"},
       {"reaction-flux entries", "no flux kernel for this Rosenbrock method"},
-      {"dense-output entries", "no dense-output kernel for this Rosenbrock method"}};
+      {"dense-output entries", "no dense-output kernel for this Rosenbrock method"},
+      {}};      // (8, the operators: launch_ops, not an integration)
   const MechDesc& M = kMech[mech];
   const int variant = a.dense_nout ? 7 : a.times ? 5 : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
   hipError_t e = hipErrorInvalidValue;
@@ -1228,6 +1230,8 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.times = nullptr; a.nleg = 0; a.carry_h = 0; a.leg_var = a.leg_ierr = a.leg_stats = a.leg_th = a.leg_h = 0;      // (the series entries set them)
   a.flux = nullptr;      // (the flux entries set it)
   a.dense_out = nullptr; a.dense_nout = nullptr; a.dense_ns = 0; a.dense_block = 0;      // (the dense-output entries set them)
+  a.ops_vdot = nullptr; a.ops_jvs = nullptr; a.ops_x = nullptr; a.ops_rhs = nullptr; a.ops_shift = nullptr; a.ops_ising = nullptr;      // (the operator entries set them)
+  a.ops_shift_stride = 0; a.ops_fun_rhs = 0; a.ops_nrhs = 0; a.ops_x_block = a.ops_rhs_block = 0;
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
@@ -2737,6 +2741,122 @@ int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double*
   const RosCall tr = trace_call(cap, d_trace_d, d_trace_i, d_ntrace, d_ctrl);
   return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
                               d_hstart, hip_stream, &tr, &ct);
+}
+
+// ---- the operators: Fun_x, Jac_SP_x and solves with shift*I - Jac_SP_x at a state the caller gives (kernel VARIANT 8).  No integration
+//      and nothing process-wide: neither the options in force, nor the integrator policy, nor step reuse.  Checked before anything touches a device, each
+//      with its own text: the mechanism (no user slot) and the arguments.
+int mistra_chem_jac_pattern(int mech, int32_t* crow, int32_t* icol, int32_t* diag) {
+  if (int rc = builtin_only(mech, "operator entries")) return rc;
+  MechTables T;      // read here: the pattern is the table's, the entry needs no device and no mistra_chem_init
+  std::string err;
+  if (!T.load(mech_dir() + "/" + kMech[mech].name + ".mech", &err)) return fail(err);
+  if (T.nvar != kMech[mech].dims.nvar || T.nnz != kMech[mech].dims.lu_nonzero) return fail(std::string(kMech[mech].name) + ".mech does not belong to this library");
+  for (int i = 0; crow && i <= T.nvar; i++) crow[i] = T.crow[(size_t)i] + 1;
+  for (int i = 0; icol && i < T.nnz; i++) icol[i] = T.icol[(size_t)i] + 1;
+  for (int i = 0; diag && i < T.nvar; i++) diag[i] = T.diag[(size_t)i] + 1;
+  return 0;
+}
+
+static int check_ops(int mech, const void* vdot, const void* jvs, int nshift, const void* shift, int fun_rhs, int nrhs, const void* rhs, const void* x,
+                     const void* ising, int ncell) {
+  if (int rc = builtin_only(mech, "operator entries")) return rc;
+  if (!x && !vdot && !jvs) return fail("mistra_chem_ops: nothing is asked for (vdot, jvs and x are all null)");
+  if (nrhs < 0) return fail("mistra_chem_ops: negative nrhs");
+  if (x && (fun_rhs ? 1 : 0) + nrhs < 1) return fail("mistra_chem_ops: a solve without a right-hand side (fun_rhs = 0 and nrhs = 0)");
+  if (nrhs > MISTRA_OPS_MAX_RHS) return fail("mistra_chem_ops: nrhs is above MISTRA_OPS_MAX_RHS (" + std::to_string(MISTRA_OPS_MAX_RHS) + ")");
+  if (x && nrhs > 0 && !rhs) return fail("mistra_chem_ops: null rhs pointer with nrhs > 0 (rhs: [nrhs][ncell][NVAR])");
+  if (x && !ising) return fail("mistra_chem_ops: null ising pointer (ising: [ncell])");
+  if (x && !shift) return fail("mistra_chem_ops: null shift pointer (shift: [nshift])");
+  if (nshift != 1 && nshift != ncell) return fail("mistra_chem_ops: nshift is neither 1 (shared) nor ncell (one per cell)");
+  return 0;
+}
+
+// the kernel's arguments of an operator call on device arrays; x null: no solve (rhs, shift, ising are not looked at)
+static KernelArgs ops_args(const MechState& S, int ncell, const double* var, const double* fix, const double* rconst, double* vdot, double* jvs, int nshift,
+                           const double* shift, int fun_rhs, int nrhs, const double* rhs, double* x, int32_t* ising, size_t block_cells, size_t nv) {
+  KernelArgs a = make_args(S, ncell, var, fix, rconst, 0.0, 0.0, nullptr, nullptr, nullptr, nullptr);
+  a.opt = nullptr;      // (the options in force are not the operators' business)
+  a.ops_vdot = vdot; a.ops_jvs = jvs;
+  if (x) {
+    a.ops_x = x; a.ops_rhs = nrhs > 0 ? rhs : nullptr; a.ops_shift = shift; a.ops_ising = ising;
+    a.ops_shift_stride = nshift == 1 ? 0 : 1; a.ops_fun_rhs = fun_rhs ? 1 : 0; a.ops_nrhs = nrhs;
+    a.ops_x_block = a.ops_rhs_block = (int64_t)(block_cells * nv);
+  }
+  return a;
+}
+
+static int launch_ops(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream) {
+  const LaunchFn fn = kMech[mech].unit.fn[8][kRos3];
+  if (!fn) return fail("no operator kernel for this mechanism");
+  const hipError_t e = fn(a, stream, &D.lds_configured[mech][8][kRos3]);
+  if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// one device's share of mistra_chem_ops_ex: its cells up, the kernel, the rows down (synchronous on that device).  The slot's staging is the batched
+// host-buffer entries'; the rows of rhs and x are blocks of the caller's [.][total][NVAR] arrays, moved as the dense-output samples are.
+static int ops_host_on(DeviceState& D, int mech, int ncell, size_t start, size_t total, const double* var, const double* fix, const double* rconst, double* vdot,
+                       double* jvs, int nshift, const double* shift, int fun_rhs, int nrhs, const double* rhs, double* x, int32_t* ising) {
+  HIP_TRY(hipSetDevice(D.id));
+  MechState& S = D.mech[mech];
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nz = (size_t)kMech[mech].dims.lu_nonzero;
+  const size_t nc = (size_t)ncell, nrow = x ? (size_t)((fun_rhs ? 1 : 0) + nrhs) : 0, nin = x ? (size_t)nrhs : 0, nsh = x ? (nshift == 1 ? 1 : nc) : 0;
+  HIP_TRY(S.s_var.reserve(nc * nv));
+  HIP_TRY(S.s_fix.reserve(nc * nf));
+  HIP_TRY(S.s_rct.reserve(nc * nr));
+  HIP_TRY(S.s_ierr.reserve(nc));
+  // one arena: vdot | jvs | shift | rhs | x
+  const size_t o_vdot = 0, o_jvs = o_vdot + (vdot ? nc * nv : 0), o_shift = o_jvs + (jvs ? nc * nz : 0), o_rhs = o_shift + nsh, o_x = o_rhs + nin * nc * nv;
+  HIP_TRY(S.s_ops.reserve(o_x + nrow * nc * nv + 1));
+  double* const B = S.s_ops.p;
+  HIP_TRY(hipMemcpy(S.s_var.p, var + start * nv, nc * nv * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.s_fix.p, fix + start * nf, nc * nf * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.s_rct.p, rconst + start * nr, nc * nr * sizeof(double), hipMemcpyHostToDevice));
+  if (nsh) HIP_TRY(hipMemcpy(B + o_shift, shift + (nshift == 1 ? 0 : start), nsh * sizeof(double), hipMemcpyHostToDevice));
+  if (nin) HIP_TRY(hipMemcpy2D(B + o_rhs, nc * nv * sizeof(double), rhs + start * nv, total * nv * sizeof(double), nc * nv * sizeof(double), nin, hipMemcpyHostToDevice));
+  const KernelArgs a = ops_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, vdot ? B + o_vdot : nullptr, jvs ? B + o_jvs : nullptr, nshift, B + o_shift, fun_rhs, nrhs,
+                                B + o_rhs, x ? B + o_x : nullptr, S.s_ierr.p, nc, nv);
+  if (int rc = launch_ops(D, mech, a, nullptr)) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (vdot) HIP_TRY(hipMemcpy(vdot + start * nv, B + o_vdot, nc * nv * sizeof(double), hipMemcpyDeviceToHost));
+  if (jvs) HIP_TRY(hipMemcpy(jvs + start * nz, B + o_jvs, nc * nz * sizeof(double), hipMemcpyDeviceToHost));
+  if (x) {
+    HIP_TRY(hipMemcpy2D(x + start * nv, total * nv * sizeof(double), B + o_x, nc * nv * sizeof(double), nc * nv * sizeof(double), nrow, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ising + start, S.s_ierr.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int mistra_chem_ops_ex(int mech, int ncell, const double* var, const double* fix, const double* rconst, double* vdot, double* jvs, int nshift,
+                       const double* shift, int fun_rhs, int nrhs, const double* rhs, double* x, int32_t* ising) {
+  if (int rc = check_ops(mech, vdot, jvs, nshift, shift, fun_rhs, nrhs, rhs, x, ising, ncell)) return rc;
+  if (x)
+    for (int i = 0; i < nshift; i++)
+      if (!std::isfinite(shift[i])) return fail("mistra_chem_ops_ex: shift[" + std::to_string(i) + "] is not finite");
+  if (int rc = lazy_init()) return rc;
+  if (int rc = check_call(mech, ncell)) return rc;
+  if (ncell == 0) return 0;
+  if (!var || !fix || !rconst) return fail("null host pointer");
+  std::lock_guard<std::mutex> lock(g_mu);
+  Slot t;
+  if (int rc = on_primary(mech, 0, true, &t)) return rc;      // (the slots' staging: refused while a column step is open)
+  return on_cell_blocks(ncell, [=](DeviceState& D, size_t start, int count) {
+    return ops_host_on(D, mech, count, start, (size_t)ncell, var, fix, rconst, vdot, jvs, nshift, shift, fun_rhs, nrhs, rhs, x, ising);
+  });
+}
+
+int mistra_chem_ops_device(int mech, int ncell, const double* d_var, const double* d_fix, const double* d_rconst, double* d_vdot, double* d_jvs, int nshift,
+                           const double* d_shift, int fun_rhs, int nrhs, const double* d_rhs, double* d_x, int32_t* d_ising, void* hip_stream) {
+  if (int rc = check_ops(mech, d_vdot, d_jvs, nshift, d_shift, fun_rhs, nrhs, d_rhs, d_x, d_ising, ncell)) return rc;
+  if (ncell == 0) return check_call(mech, 0);
+  if (!d_var || !d_fix || !d_rconst) return fail("null device pointer");
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var, "d_var", 0, &t)) return rc;
+  std::lock_guard<std::mutex> lock(g_mu);
+  const KernelArgs a = ops_args(*t.S, ncell, d_var, d_fix, d_rconst, d_vdot, d_jvs, nshift, d_shift, fun_rhs, nrhs, d_rhs, d_x, d_ising, (size_t)ncell,
+                                (size_t)kMech[mech].dims.nvar);
+  return launch_ops(*t.D, mech, a, static_cast<hipStream_t>(hip_stream));
 }
 
 // ---- the reaction flux: Rosenbrock_x as above, plus every reaction's rate integrated over the call (kernel VARIANT 6).  The same two

@@ -124,6 +124,20 @@ struct KernelArgs {
   int32_t* dense_nout;         // [ncell]
   int32_t dense_ns;
   int64_t dense_block;         // elements from one sample's block to the next: ncell*NVAR of the launch
+  // the operators (kernel VARIANT 8, in the trace units of ros_unit_kernel.hip; mistra_chem_ops_ex / _device): Fun_x, Jac_SP_x and solves with
+  // shift*I - Jac_SP_x at the state var_in holds, once, no integration.  The right-hand sides are the cell's own Fun_x (ops_fun_rhs:
+  // row 0 of ops_x) followed by ops_nrhs rows of ops_rhs; row j of cell c is at j*block + c*NVAR of either array.  Read by the operator kernels only,
+  // which read nothing of the integration's arguments but var_in, fix, rconst, ncell, n_temps and the schedule; null / 0 everywhere else (capi.cpp: make_args).
+  double* ops_vdot;            // [ncell][NVAR] or null: not wanted
+  double* ops_jvs;             // [ncell][LU_NONZERO] or null: not wanted; KPP's slot order, the fill-in slots +0.0
+  double* ops_x;               // [ops_fun_rhs + ops_nrhs][ops_x_block] or null: no solve
+  const double* ops_rhs;       // [ops_nrhs][ops_rhs_block]
+  const double* ops_shift;     // cell c reads entry c*ops_shift_stride
+  int32_t* ops_ising;          // [ncell]: KppDecomp_x's IER, the first row (1-based) whose prepared diagonal is exactly zero, else 0 (set with ops_x)
+  int32_t ops_shift_stride;    // 0: one shift shared by all cells, 1: one per cell
+  int32_t ops_fun_rhs;         // /= 0: the cell's Fun_x is right-hand side 0
+  int32_t ops_nrhs;
+  int64_t ops_x_block, ops_rhs_block;      // elements from one row's block to the next: ncell*NVAR of the caller's arrays
 };
 
 }  // namespace mistra

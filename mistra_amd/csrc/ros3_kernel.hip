@@ -1197,12 +1197,17 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // 7 = dense output (instantiated in the series units of ros_unit_kernel.hip; mistra_chem_rosenbrock_dense_ex / _device): variant 3 of any of the five methods
 // that also leaves the state at a.dense_ns sample times inside the call, by the cubic Hermite interpolant between the accepted states.
 // Everything it adds sits behind `if constexpr (DENSE)`.
+// 8 = the operators (instantiated in the trace units of ros_unit_kernel.hip; mistra_chem_ops_ex / _device): no integration — Fun_x, Jac_SP_x and solves with
+// shift*I - Jac_SP_x at the state given, by the step loop's own pieces, once.  One block behind the definitions of those pieces that ends
+// with a return; everything it adds sits behind `if constexpr (OPS)`.
 // METHOD (variant 3 only): the Rosenbrock method, IPAR(4) of Rosenbrock_x (ros_methods.hpp).  Ros3 is the kernel as it was; Ros2, Ros4, Rodas3
 // and Rodas4 (the method kernels, instantiated by ros_unit_kernel.hip in translation units of their own) differ in the stage loop, in the
 // number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
 template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
   constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, FLUX = VARIANT == 6, DENSE = VARIANT == 7, OPT = VARIANT == 3 || TRACE || SERIES || FLUX || DENSE;
+  constexpr bool OPS = VARIANT == 8;
+  static_assert(!OPS || METHOD == kRos3, "the operators are Ros3 instantiations (ros_unit_kernel.hip): no method is involved");
   static_assert(!TRACE || METHOD == kRos3, "the step-control trace is a Ros3 instantiation (ros_unit_kernel.hip)");
   static_assert(METHOD == kRos3 || (OPT && METHOD >= kRos2 && METHOD <= kRodas4), "the method kernels are options instantiations");
   constexpr double kGamma1 = METHOD == kRos3 ? kRosGamma1 : kRosMethod<METHOD>.Gamma[0];
@@ -1225,6 +1230,10 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   const int cell = blockIdx.x;
   if (cell >= a.ncell) return;
   if (lds_addr(lds) != 0u) {      // the VM and the tail chain address M by absolute LDS offsets
+    if constexpr (OPS) {      // (no ierr: the refusal goes where the call has an integer per cell)
+      if (t == 0 && a.ops_ising) GM_(a.ops_ising)[cell] = -99;
+      return;
+    }
     if constexpr (SERIES) {      // every leg's
       if (t == 0)
         for (int k = 0; k < a.nleg; k++) GM_(a.ierr)[(int64_t)k * a.leg_ierr + cell] = -99;
@@ -1814,6 +1823,109 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     for (int w = 0; w < NW; w++) sum += red[w];
     return sqrt(sum / (double)NVAR);
   };
+
+  // ---- VARIANT 8, the operators: the pieces above run once at the state the caller gave, and the kernel returns.  Fun_x (with
+  //      Jac_SP_x where the Jacobian or a solve is wanted: the evaluators a step opens with), Vdot and JVS to the caller's arrays, then
+  //      ros_PrepareMatrix_x's matrix with the caller's shift in place of 1/(H*gamma), KppDecomp_x as the step loop runs it, and one KppSolve_x per
+  //      right-hand side.  The cell's own Fun_x (a.ops_fun_rhs) rides through the LU program as a step's stage 1 does, so that row is K(1) of a step
+  //      with that matrix bit for bit; every caller row goes through the full solve (solve(k, false)) and so does not depend on where it stands or
+  //      on what else the call asks for.
+  if constexpr (OPS) {
+    const bool want_solve = a.ops_x != nullptr, want_jac = want_solve || a.ops_jvs != nullptr;
+    double f0[SPT];
+    if (want_jac) {
+      if constexpr (L::MERGE_FUN_JAC) {
+        fun_jac(y, f0);
+      } else {
+        fun(y, f0);
+        jac();
+      }
+    } else {
+      fun(y, f0);
+    }
+    if (a.ops_vdot) {
+#pragma unroll
+      for (int q = 0; q < SPT; q++) {
+        const int s = q * NT + t;
+        if (s < NVAR) GM_(a.ops_vdot)[(size_t)cell * NVAR + s] = f0[q];
+      }
+    }
+    if (a.ops_jvs) {      // every slot of the row once: the thread's sums to their Ghimj slots, the fill-in slots +0.0
+      if constexpr (!RESIDENT) load_pos();
+      gptr_mut<double> jrow = GM_(a.ops_jvs) + (size_t)cell * NNZ;
+#pragma unroll
+      for (int q = 0; q < JPT; q++) {
+        const uint32_t pw = jpos[q / 2], p = (q & 1) ? (pw >> 16) : (pw & 0xFFFFu);
+        if (p != kPosNone) jrow[p & 0x7FFFu] = jac0[q];
+      }
+#pragma unroll
+      for (int q = 0; q < ZPT; q++) {
+        const uint32_t pw = zpos[q / 2], p = (q & 1) ? (pw >> 16) : (pw & 0xFFFFu);
+        if (p != kPosNone) jrow[p & 0x7FFFu] = 0.0;
+      }
+    }
+    if (!want_solve) return;      // (uniform over the call)
+    const int nrow = (a.ops_fun_rhs ? 1 : 0) + a.ops_nrhs;
+    double kk[SPT];
+#pragma unroll
+    for (int q = 0; q < SPT; q++) kk[q] = f0[q] + 0.0;      // K1's right-hand side as the step loop forms it (Fcn0 + HG*dFdT, dFdT = +0.0)
+    const double shift = wave_uniform(G_(a.ops_shift)[(size_t)cell * (size_t)a.ops_shift_stride]);
+    if (prepare(shift, kk)) {
+      // KppDecomp_x's IER: the first row whose diagonal is exactly zero as prepared (see the step loop's singular path).  No factorisation runs:
+      // the cell's rows are +0.0
+#pragma unroll
+      for (int q = 0; q < SPT; q++) {
+        const int sp = q * NT + t;
+        const uint32_t dp = sp < NVAR ? (uint32_t)G_(a.diag_pos)[sp] : (uint32_t)kPosNone;
+        if (dp != kPosNone && M[dp] == 0.0) atomicMin(&flags[1], sp + 1);
+      }
+      lds_barrier();
+      if (t == 0) GM_(a.ops_ising)[cell] = flags[1];
+      for (int j = 0; j < nrow; j++) {
+#pragma unroll
+        for (int q = 0; q < SPT; q++) {
+          const int s = q * NT + t;
+          if (s < NVAR) GM_(a.ops_x)[(int64_t)j * a.ops_x_block + (int64_t)cell * NVAR + s] = 0.0;
+        }
+      }
+      return;
+    }
+    if (t == 0) GM_(a.ops_ising)[cell] = 0;
+    vm_run<NT, 4>(a.lu, hdr.lu_row0, lane);
+    if constexpr (MT::SCALE_PASS) {
+      scale_run<NT, MT::RING_LOW>(a.lu_scale, wave, lane);
+      lds_barrier();
+    }
+    if constexpr (MT::DENSE_ND > 0) {
+      const f64x4 tile = dense_lu<MT, NT>(lane);
+      if (wave == 7) dense_finish<MT, NT>(tile, lane);
+      lds_barrier();
+    }
+    int row = 0;
+    if (a.ops_fun_rhs) {      // its forward sweep went through the LU program
+      solve(kk, true);
+#pragma unroll
+      for (int q = 0; q < SPT; q++) {
+        const int s = q * NT + t;
+        if (s < NVAR) GM_(a.ops_x)[(int64_t)cell * NVAR + s] = kk[q];
+      }
+      row = 1;
+    }
+    for (int j = 0; j < a.ops_nrhs; j++) {
+#pragma unroll
+      for (int q = 0; q < SPT; q++) {
+        const int s = q * NT + t;
+        kk[q] = s < NVAR ? G_(a.ops_rhs)[(int64_t)j * a.ops_rhs_block + (int64_t)cell * NVAR + s] : 0.0;
+      }
+      solve(kk, false);
+#pragma unroll
+      for (int q = 0; q < SPT; q++) {
+        const int s = q * NT + t;
+        if (s < NVAR) GM_(a.ops_x)[(int64_t)(row + j) * a.ops_x_block + (int64_t)cell * NVAR + s] = kk[q];
+      }
+    }
+    return;
+  }
 
   // ---- RosenbrockIntegrator_x (gas.f:1180-1336); option values are the ones INTEGRATE_x/Rosenbrock_x fix
   // VARIANT 5: Tstart, Tend and what follows from them (Hmax, Direction) are the leg's, set at the head of each leg (below)

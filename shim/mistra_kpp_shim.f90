@@ -62,6 +62,13 @@
 !     SUBROUTINE ROSENBROCK_BATCH_DENSE_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NS, TS, YS, NOUT)
 !     SUBROUTINE ROSENBROCK_BATCH_DENSE_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT,
 !                                                          NS, TS, YS, NOUT)
+! THE OPERATORS (mistra_chem_ops_ex; INTEGRATION.md 4p): KPP's building blocks at the states the caller gives, NCELL cells per call, no integration; the
+! options in force, the policy and step reuse are not involved.  VDOT(NVAR,NCELL) = Fun_x; JVS(LU_NONZERO,NCELL) = Jac_SP_x in LU_CROW / LU_ICOL order, the
+! fill-in slots zero; X(NVAR,NCELL,j) solves (SHIFT*I - Jac_SP_x) X = B for the cell's own Fun_x (FUNRHS, logical: j = 1) followed by RHS(NVAR,NCELL,1:NRHS);
+! SHIFT(NSHIFT), NSHIFT = 1 (shared) or NCELL; ISING(NCELL) is KppDecomp_x's IER (a cell with ISING > 0 is not factorised: its X is zero).
+!     SUBROUTINE FUN_BATCH_g / _a / _t (NCELL, VAR, FIX, RCONST, VDOT)
+!     SUBROUTINE JAC_SP_BATCH_g / _a / _t (NCELL, VAR, FIX, RCONST, JVS)
+!     SUBROUTINE LINSOLVE_BATCH_g / _a / _t (NCELL, VAR, FIX, RCONST, NSHIFT, SHIFT, FUNRHS, NRHS, RHS, X, ISING)
 module mistra_chem_c_api
   use iso_c_binding
   implicit none
@@ -210,6 +217,14 @@ module mistra_chem_c_api
        integer(c_int32_t) :: ierr(*), stats(*)
        integer(c_int) :: rc
      end function mistra_chem_rosenbrock_series_cells_ex
+     function mistra_chem_ops_ex(mech, ncell, var, fix, rconst, vdot, jvs, nshift, shift, fun_rhs, nrhs, rhs, x, ising) &
+          bind(C, name="mistra_chem_ops_ex") result(rc)
+       import :: c_int, c_double, c_ptr
+       integer(c_int), value :: mech, ncell, nshift, fun_rhs, nrhs
+       real(c_double), intent(in) :: var(*), fix(*), rconst(*)
+       type(c_ptr), value :: vdot, jvs, shift, rhs, x, ising      ! each c_null_ptr where the call has none (include/mistra_chem.h)
+       integer(c_int) :: rc
+     end function mistra_chem_ops_ex
      function mistra_chem_set_step_reuse(mech, on) bind(C, name="mistra_chem_set_step_reuse") result(rc)
        import :: c_int
        integer(c_int), value :: mech, on
@@ -517,6 +532,30 @@ contains
     end do
     deallocate (th)
   end subroutine rosenbrock_series
+
+  ! FUN_BATCH_x, JAC_SP_BATCH_x, LINSOLVE_BATCH_x: the one C entry, what the call does not have as c_null_ptr
+  subroutine ops_batch(mech, what, NCELL, VAR, FIX, RCONST, VDOT, JVS, NSHIFT, SHIFT, FUNRHS, NRHS, RHS, X, ISING)
+    integer, intent(in) :: mech, NCELL
+    character(len=*), intent(in) :: what
+    real(c_double), intent(in) :: VAR(*), FIX(*), RCONST(*)
+    real(c_double), optional, target :: VDOT(*), JVS(*), SHIFT(*), RHS(*), X(*)
+    integer(c_int32_t), optional, target :: ISING(*)
+    integer, optional, intent(in) :: NSHIFT, NRHS
+    logical, optional, intent(in) :: FUNRHS
+    type(c_ptr) :: pv, pj, ps, pr, px, pi
+    integer(c_int) :: ns, nr, fr
+    pv = c_null_ptr; pj = c_null_ptr; ps = c_null_ptr; pr = c_null_ptr; px = c_null_ptr; pi = c_null_ptr
+    ns = 1; nr = 0; fr = 0
+    if (present(VDOT)) pv = c_loc(VDOT)
+    if (present(JVS)) pj = c_loc(JVS)
+    if (present(X)) then
+       px = c_loc(X); ps = c_loc(SHIFT); pi = c_loc(ISING)
+       ns = int(NSHIFT, c_int); nr = int(NRHS, c_int)
+       if (FUNRHS) fr = 1
+       if (nr > 0) pr = c_loc(RHS)
+    end if
+    if (mistra_chem_ops_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, pv, pj, ns, ps, fr, nr, pr, px, pi) /= 0) call mistra_chem_fail(what)
+  end subroutine ops_batch
 end module mistra_chem_c_api
 
 subroutine INTEGRATE_g(TIN, TOUT)
@@ -1051,3 +1090,91 @@ subroutine ROSENBROCK_BATCH_DENSE_CELLS_t(NCELL, VAR, FIX, RCONST, TSTART, TEND,
   integer(c_int32_t) :: IPAR(20), IERR(*), ISTAT(8, *), NOUT(*)
   call rosenbrock_batch(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, NTOL=NTOL, NS=NS, TS=TS, YS=YS, NOUT=NOUT)
 end subroutine ROSENBROCK_BATCH_DENSE_CELLS_t
+
+! ---- the operators (mistra_chem_ops_ex; INTEGRATION.md 4p): Fun_x, Jac_SP_x and solves with SHIFT*I - Jac_SP_x at the states given, no integration
+subroutine FUN_BATCH_g(NCELL, VAR, FIX, RCONST, VDOT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), VDOT(102, *)
+  call ops_batch(0, 'FUN_BATCH_g', NCELL, VAR, FIX, RCONST, VDOT=VDOT)
+end subroutine FUN_BATCH_g
+
+subroutine JAC_SP_BATCH_g(NCELL, VAR, FIX, RCONST, JVS)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), JVS(1110, *)
+  call ops_batch(0, 'JAC_SP_BATCH_g', NCELL, VAR, FIX, RCONST, JVS=JVS)
+end subroutine JAC_SP_BATCH_g
+
+subroutine LINSOLVE_BATCH_g(NCELL, VAR, FIX, RCONST, NSHIFT, SHIFT, FUNRHS, NRHS, RHS, X, ISING)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NSHIFT, NRHS
+  logical :: FUNRHS
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), SHIFT(*), RHS(102, NCELL, *), X(102, NCELL, *)
+  integer(c_int32_t) :: ISING(*)
+  call ops_batch(0, 'LINSOLVE_BATCH_g', NCELL, VAR, FIX, RCONST, NSHIFT=NSHIFT, SHIFT=SHIFT, FUNRHS=FUNRHS, NRHS=NRHS, RHS=RHS, X=X, ISING=ISING)
+end subroutine LINSOLVE_BATCH_g
+
+subroutine FUN_BATCH_a(NCELL, VAR, FIX, RCONST, VDOT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), VDOT(257, *)
+  call ops_batch(1, 'FUN_BATCH_a', NCELL, VAR, FIX, RCONST, VDOT=VDOT)
+end subroutine FUN_BATCH_a
+
+subroutine JAC_SP_BATCH_a(NCELL, VAR, FIX, RCONST, JVS)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), JVS(6579, *)
+  call ops_batch(1, 'JAC_SP_BATCH_a', NCELL, VAR, FIX, RCONST, JVS=JVS)
+end subroutine JAC_SP_BATCH_a
+
+subroutine LINSOLVE_BATCH_a(NCELL, VAR, FIX, RCONST, NSHIFT, SHIFT, FUNRHS, NRHS, RHS, X, ISING)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NSHIFT, NRHS
+  logical :: FUNRHS
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), SHIFT(*), RHS(257, NCELL, *), X(257, NCELL, *)
+  integer(c_int32_t) :: ISING(*)
+  call ops_batch(1, 'LINSOLVE_BATCH_a', NCELL, VAR, FIX, RCONST, NSHIFT=NSHIFT, SHIFT=SHIFT, FUNRHS=FUNRHS, NRHS=NRHS, RHS=RHS, X=X, ISING=ISING)
+end subroutine LINSOLVE_BATCH_a
+
+subroutine FUN_BATCH_t(NCELL, VAR, FIX, RCONST, VDOT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), VDOT(417, *)
+  call ops_batch(2, 'FUN_BATCH_t', NCELL, VAR, FIX, RCONST, VDOT=VDOT)
+end subroutine FUN_BATCH_t
+
+subroutine JAC_SP_BATCH_t(NCELL, VAR, FIX, RCONST, JVS)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), JVS(13503, *)
+  call ops_batch(2, 'JAC_SP_BATCH_t', NCELL, VAR, FIX, RCONST, JVS=JVS)
+end subroutine JAC_SP_BATCH_t
+
+subroutine LINSOLVE_BATCH_t(NCELL, VAR, FIX, RCONST, NSHIFT, SHIFT, FUNRHS, NRHS, RHS, X, ISING)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NSHIFT, NRHS
+  logical :: FUNRHS
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), SHIFT(*), RHS(417, NCELL, *), X(417, NCELL, *)
+  integer(c_int32_t) :: ISING(*)
+  call ops_batch(2, 'LINSOLVE_BATCH_t', NCELL, VAR, FIX, RCONST, NSHIFT=NSHIFT, SHIFT=SHIFT, FUNRHS=FUNRHS, NRHS=NRHS, RHS=RHS, X=X, ISING=ISING)
+end subroutine LINSOLVE_BATCH_t

@@ -24,6 +24,9 @@
 !                                                      then the cells as for <G|A|T>.  ntol = 0: ONE call of ROSENBROCK_BATCH_DENSE_x with the pair; ntol = 1 or NVAR: ONE call
 !                                                      of ROSENBROCK_BATCH_DENSE_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin = per cell VAR, TEXIT,
 !                                                      HEXIT, IERR, the 8 statistics, NOUT, then YS(NVAR, ncell, ns)
+!          shim_driver <PG|PA|PT> <in.bin> <out.bin>   the operators: in.bin = ncell, nshift, funrhs (0 | 1), nrhs, SHIFT(nshift), then the cells as for <G|A|T>, then
+!                                                      RHS(NVAR, ncell, nrhs); ONE call each of FUN_BATCH_x, JAC_SP_BATCH_x and LINSOLVE_BATCH_x.  out.bin = VDOT(NVAR, ncell),
+!                                                      JVS(LU_NONZERO, ncell), X(NVAR, ncell, funrhs + nrhs), ISING(ncell)
 !          shim_driver <Eg|Ea|Et> <in.bin> <out.bin>   in.bin = ncell, then per cell VAR, FIX, ENV (the vector MISTRA_RATES_ENV_x packs,
 !                                                      mistra_kpp_rates.f90): UPDATE_RCONST_BATCH_x, then INTEGRATE_BATCH_ENV_x (rates and
 !                                                      integrator on the device, RCONST never crosses PCIe); out.bin = per cell VAR,
@@ -102,6 +105,13 @@ program shim_driver
      case ('G'); call run_dense(0, 102, 3, 331, trim(fin), trim(fout))
      case ('A'); call run_dense(1, 257, 5, 979, trim(fin), trim(fout))
      case ('T'); call run_dense(2, 417, 7, 1627, trim(fin), trim(fout))
+     case default; stop 'mechanism must be G, A or T'
+     end select
+  case ('P')
+     select case (a1(2:2))
+     case ('G'); call run_ops(0, 102, 3, 331, 1110, trim(fin), trim(fout))
+     case ('A'); call run_ops(1, 257, 5, 979, 6579, trim(fin), trim(fout))
+     case ('T'); call run_ops(2, 417, 7, 1627, 13503, trim(fin), trim(fout))
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('K', 'H', 'Q', 'V', 'S', 'C', 'R')
@@ -353,6 +363,47 @@ contains
     end do
     close (11); close (12)
   end subroutine run_flux
+  subroutine run_ops(mech, NVAR, NFIX, NREACT, NNZ, fin, fout)
+    integer, intent(in) :: mech, NVAR, NFIX, NREACT, NNZ
+    character(len=*), intent(in) :: fin, fout
+    double precision :: hd(4)
+    double precision, allocatable :: SHIFT(:), VAR(:, :), FIX(:, :), RCONST(:, :), VDOT(:, :), JVS(:, :), RHS(:, :, :), X(:, :, :), rec(:)
+    integer :: n, nshift, nrhs, nrow, i
+    integer, allocatable :: ISING(:)
+    logical :: funrhs
+    open (11, file=fin, access='stream', form='unformatted', status='old')
+    open (12, file=fout, access='stream', form='unformatted', status='replace')
+    read (11) hd      ! ncell, nshift, funrhs, nrhs
+    n = int(hd(1)); nshift = int(hd(2)); funrhs = hd(3) /= 0.0d0; nrhs = int(hd(4))
+    nrow = nrhs + merge(1, 0, funrhs)
+    allocate (SHIFT(nshift), VAR(NVAR, n), FIX(NFIX, n), RCONST(NREACT, n), VDOT(NVAR, n), JVS(NNZ, n), RHS(NVAR, n, max(nrhs, 1)), X(NVAR, n, nrow), ISING(n))
+    allocate (rec(NVAR + NFIX + NREACT))
+    read (11) SHIFT
+    do i = 1, n
+       read (11) rec
+       VAR(:, i) = rec(1:NVAR)
+       FIX(:, i) = rec(NVAR + 1:NVAR + NFIX)
+       RCONST(:, i) = rec(NVAR + NFIX + 1:)
+    end do
+    if (nrhs > 0) read (11) RHS(:, :, 1:nrhs)
+    VDOT = -7.25d0; JVS = -7.25d0; X = -7.25d0; ISING = -7
+    select case (mech)
+    case (0)
+       call FUN_BATCH_g(n, VAR, FIX, RCONST, VDOT)
+       call JAC_SP_BATCH_g(n, VAR, FIX, RCONST, JVS)
+       call LINSOLVE_BATCH_g(n, VAR, FIX, RCONST, nshift, SHIFT, funrhs, nrhs, RHS, X, ISING)
+    case (1)
+       call FUN_BATCH_a(n, VAR, FIX, RCONST, VDOT)
+       call JAC_SP_BATCH_a(n, VAR, FIX, RCONST, JVS)
+       call LINSOLVE_BATCH_a(n, VAR, FIX, RCONST, nshift, SHIFT, funrhs, nrhs, RHS, X, ISING)
+    case (2)
+       call FUN_BATCH_t(n, VAR, FIX, RCONST, VDOT)
+       call JAC_SP_BATCH_t(n, VAR, FIX, RCONST, JVS)
+       call LINSOLVE_BATCH_t(n, VAR, FIX, RCONST, nshift, SHIFT, funrhs, nrhs, RHS, X, ISING)
+    end select
+    write (12) VDOT, JVS, X, dble(ISING)
+    close (11); close (12)
+  end subroutine run_ops
   subroutine run_dense(mech, NVAR, NFIX, NREACT, fin, fout)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT
     character(len=*), intent(in) :: fin, fout

@@ -11,6 +11,7 @@ mistra_amd/csrc/ros3_kernel.hip at two commits), and the resources of the method
                                                     sibling's — the product unit's options kernel for Ros3, the method unit's for the other four
     python tools/isa_compare.py --flux              per flux unit (variant 6): the same table for the flux kernel
     python tools/isa_compare.py --dense             per series unit: the same table for the dense-output kernel (VARIANT 7) the unit also holds
+    python tools/isa_compare.py --ops               per trace unit: the same table for the operator kernel (VARIANT 8) the unit also holds
 
 A kernel's mangled name carries its template arguments: the METHOD parameter added to ros3_integrate_kernel (default Ros3 = 2) is cut out of the
 new listing's names before the comparison; nothing else is normalised."""
@@ -138,6 +139,8 @@ if __name__ == "__main__":
         beside_variant_3(6, "flux")
     elif "--dense" in sys.argv:
         beside_variant_3(5, "dense-output", kernel=7)
+    elif "--ops" in sys.argv:
+        beside_variant_3(4, "operator", kernel=8)
     elif "--listings" in sys.argv:
         listings(sys.argv[sys.argv.index("--listings") + 1])
     else:
