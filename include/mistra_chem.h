@@ -338,6 +338,41 @@ int mistra_chem_rosenbrock_series_cells_device(int mech, int ncell, const double
                                                double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                                int carry_h, const double* d_hstart, void* hip_stream);
 
+/* A SERIES WITH RATE CONSTANTS AND FIX OF THE LEG'S OWN: Update_RCONST_x + INTEGRATE_x, nleg times, in one launch.  The series
+ * entries above with two counts behind rconst:
+ *     rconst [rconst_legs][ncell][NREACT]      fix [fix_legs][ncell][NFIX]      each count 1 (one block shared by all legs) or nleg.
+ * Leg k is one call of Rosenbrock_x from times[k] to times[k+1] on the state leg k-1 left, with RCONST = block k of rconst and FIX = block k of fix
+ * (block 0 where the count is 1): piecewise constant over the series, the model's operator splitting.  Everything else is the series': the outputs
+ * and their layout, the first step and carry_h, the refusals that stay results, the times, what is ignored.  The results are bit for bit those of
+ * mistra_chem_rosenbrock_ex / _device (the cells forms: mistra_chem_rosenbrock_cells_ex / _device) called leg by leg with leg k's rows; with both
+ * counts 1 the call IS the series entry of the same name without "_rates".
+ * A count that is neither 1 nor nleg fails with a text before a device is touched, as do the series' own refusals and a user slot (the slot's text).
+ * rconst and fix are read at the head of every leg, not once: they may not alias var_series, and the device forms' arrays must stay untouched until
+ * the kernel has finished (stream order).  The _ex forms upload each device slot's block of every leg with one 2-D copy.  The layout of rconst is the
+ * one mistra_chem_update_rconst_device writes for nleg*ncell rows, leg-major: its output goes in as it is. */
+int mistra_chem_rosenbrock_series_rates_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                           int rconst_legs, int fix_legs,
+                                           int nleg, const double* times, const double* atol, const double* rtol,
+                                           const double* rpar, const int32_t* ipar, int carry_h, const double* hstart /* [ncell] or NULL */,
+                                           double* var_series, int32_t* ierr, int32_t* stats, double* t_h);
+int mistra_chem_rosenbrock_series_rates_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                               int rconst_legs, int fix_legs,
+                                               int nleg, const double* times, const double* atol, const double* rtol,
+                                               const double* rpar, const int32_t* ipar,                                           /* host arrays */
+                                               double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                               int carry_h, const double* d_hstart, void* hip_stream);
+int mistra_chem_rosenbrock_series_rates_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                                 int rconst_legs, int fix_legs,
+                                                 int nleg, const double* times, const double* atol, const double* rtol, int ntol,  /* rows per cell */
+                                                 const double* rpar, const int32_t* ipar, int carry_h, const double* hstart,
+                                                 double* var_series, int32_t* ierr, int32_t* stats, double* t_h);
+int mistra_chem_rosenbrock_series_rates_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                                     int rconst_legs, int fix_legs,
+                                                     int nleg, const double* times, const double* d_atol, const double* d_rtol, int ntol,  /* device arrays */
+                                                     const double* rpar, const int32_t* ipar,                                      /* host arrays */
+                                                     double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                                     int carry_h, const double* d_hstart, void* hip_stream);
+
 /* DENSE OUTPUT: the state at ns sample times INSIDE one call of Rosenbrock_x, without changing the call (a series, above, is nleg calls).
  * Everything mistra_chem_rosenbrock_ex / _device (the cells forms: _cells_ex / _cells_device) return with the same arguments, d_hstart included, bit for
  * bit (var_out, ierr, stats, t_h / d_texit_hexit), plus

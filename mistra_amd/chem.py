@@ -136,6 +136,10 @@ def lib():
                                                                  _dp, _ip, _ip, _dp]
             L.mistra_chem_rosenbrock_series_cells_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, _dp, vp, vp, C.c_int, _dp, _ip, vp, vp, vp, vp,
                                                                      C.c_int, vp, vp]
+        if hasattr(L, "mistra_chem_rosenbrock_series_rates_ex"):      # the series entries' lists with rconst_legs, fix_legs behind rconst
+            for form in ("ex", "device", "cells_ex", "cells_device"):
+                at = getattr(L, "mistra_chem_rosenbrock_series_" + form).argtypes
+                getattr(L, "mistra_chem_rosenbrock_series_rates_" + form).argtypes = at[:5] + [C.c_int, C.c_int] + at[5:]
         if hasattr(L, "mistra_chem_rosenbrock_flux_ex"):
             L.mistra_chem_rosenbrock_flux_ex.argtypes = L.mistra_chem_rosenbrock_ex.argtypes + [_dp]
             L.mistra_chem_rosenbrock_flux_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [vp]
@@ -938,6 +942,94 @@ def rosenbrock_series(mech, var, fix, rconst, times, ipar=None, rpar=None, atol=
         _check(L.mistra_chem_rosenbrock_series_cells_ex(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *popts, *tail))
     else:
         _check(L.mistra_chem_rosenbrock_series_ex(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
+    return SeriesResult(res, ierr, stats, th)
+
+
+def rosenbrock_series_rates(mech, var, fix, rconst, times, ipar=None, rpar=None, atol=None, rtol=None, hstart=None, carry_h=False, out=None):
+    """rosenbrock_series() with FIX and the rate constants of the leg's own: Update_RCONST_x + INTEGRATE_x, nleg = len(times) - 1 times, in one launch
+    (include/mistra_chem.h: mistra_chem_rosenbrock_series_rates_ex / _device and their cells forms).  fix and rconst: 2-D [ncell, .] (one block shared
+    by all legs) or 3-D [nleg, ncell, .] (leg k integrates with block k; a leading 1 is the shared block), each on its own -> SeriesResult, bit for
+    bit what rosenbrock() / rosenbrock_cells() called leg by leg with leg k's rows return.  rconst [nleg, ncell, NREACT] is what update_rconst over
+    nleg*ncell env rows, leg-major, returns, reshaped or not.  Everything else as rosenbrock_series(): numpy arrays go to the host entry, torch CUDA
+    tensors to the device entry on torch's current stream (fix and rconst are read at the head of every leg: leave them untouched until the stream has
+    passed the call, and they may not overlap out); a 2-D atol / rtol selects the cells form."""
+    mid, name = _mech_id(mech)
+    nvar, nfix, nreact, _ = DIMS[name]
+    cells = atol is not None and rtol is not None and getattr(atol, "ndim", 0) == 2 and getattr(rtol, "ndim", 0) == 2
+    ip, rp, at1, rt1 = _option_args(name, ipar, rpar, None if cells else atol, None if cells else rtol)
+    tm = np.ascontiguousarray(times, np.float64).reshape(-1)
+    nleg = tm.size - 1
+    tp = tm.ctypes.data_as(_dp)
+    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
+    L = lib()
+    rows = max(nleg, 0)
+
+    def legs(x, what):      # the number of blocks of fix / rconst: the library refuses one that is neither 1 nor nleg, by its text
+        if x.ndim not in (2, 3):
+            raise MistraChemError("%s: a 2-D [ncell, .] array (shared by all legs) or a 3-D [nleg, ncell, .] one expected" % what)
+        return 1 if x.ndim == 2 else int(x.shape[0])
+
+    if _is_torch(var):
+        import torch
+        if not var.is_cuda:
+            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
+        init(var.device.index or 0)
+        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
+            if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
+                raise MistraChemError("expected contiguous float64 [..., ncell,%d] tensors on one device" % n)
+        ncell = var.numel() // nvar
+        nlf, nlr = legs(fix, "fix"), legs(rconst, "rconst")
+        if fix.numel() != nlf * ncell * nfix or rconst.numel() != nlr * ncell * nreact:
+            raise MistraChemError("cell counts of var / fix / rconst differ")
+        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
+            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
+        if cells:
+            for x in (atol, rtol):
+                if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.shape[0] != ncell or x.device != var.device:
+                    raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
+            if atol.shape != rtol.shape:
+                raise MistraChemError("atol and rtol differ in shape")
+        if out is None:
+            out = torch.empty((rows, ncell, nvar), dtype=torch.float64, device=var.device)
+        elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != rows * ncell * nvar or out.device != var.device:
+            raise MistraChemError("out: a contiguous float64 [nleg, ncell, %d] tensor on the cells' device expected" % nvar)
+        ierr = torch.empty((rows, ncell), dtype=torch.int32, device=var.device)
+        stats = torch.empty((rows, ncell, 8), dtype=torch.int32, device=var.device)
+        th = torch.empty((rows, ncell, 2), dtype=torch.float64, device=var.device)
+        stream = torch.cuda.current_stream(var.device).cuda_stream
+        tail = (out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), int(bool(carry_h)), None if hstart is None else hstart.data_ptr(),
+                C.c_void_p(stream))
+        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), nlr, nlf, nleg, tp)
+        if cells:
+            _check(L.mistra_chem_rosenbrock_series_rates_cells_device(*head, atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]), *popts, *tail))
+        else:
+            _check(L.mistra_chem_rosenbrock_series_rates_device(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
+        return SeriesResult(out.view(rows, ncell, nvar), ierr, stats, th)
+    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+    ncell = v.shape[0]
+    f = np.ascontiguousarray(fix, np.float64)
+    r = np.ascontiguousarray(rconst, np.float64)
+    nlf, nlr = legs(f, "fix"), legs(r, "rconst")
+    if f.size != nlf * ncell * nfix or r.size != nlr * ncell * nreact:
+        raise MistraChemError("cell counts of var / fix / rconst differ")
+    hs = None if hstart is None else np.ascontiguousarray(hstart, np.float64).reshape(-1)
+    if hs is not None and hs.size != ncell:
+        raise MistraChemError("hstart: %d entries expected" % ncell)
+    res = np.empty((rows, ncell, nvar))
+    ierr = np.zeros((rows, ncell), np.int32)
+    stats = np.zeros((rows, ncell, 8), np.int32)
+    th = np.zeros((rows, ncell, 3))
+    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), nlr, nlf, nleg, tp)
+    tail = (int(bool(carry_h)), None if hs is None else hs.ctypes.data_as(_dp), res.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip),
+            stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp))
+    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
+    if cells:
+        a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
+        if a2.shape[0] != ncell or r2.shape != a2.shape:
+            raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
+        _check(L.mistra_chem_rosenbrock_series_rates_cells_ex(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *popts, *tail))
+    else:
+        _check(L.mistra_chem_rosenbrock_series_rates_ex(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
     return SeriesResult(res, ierr, stats, th)
 
 

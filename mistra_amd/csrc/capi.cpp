@@ -1227,7 +1227,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.trace_d = nullptr; a.trace_i = nullptr; a.ntrace = nullptr; a.ctrl = nullptr; a.trace_cap = 0;      // (the trace entries set them)
   a.tol_abs = nullptr; a.tol_rel = nullptr; a.tol_cell_stride = 0; a.tol_spec_stride = 0;      // (the cells entries set them)
   a.tol_cell_factor = 0.0; a.tol_cell_floor = 0.0;      // (policy_args sets them)
-  a.times = nullptr; a.nleg = 0; a.carry_h = 0; a.leg_var = a.leg_ierr = a.leg_stats = a.leg_th = a.leg_h = 0;      // (the series entries set them)
+  a.times = nullptr; a.nleg = 0; a.carry_h = 0; a.leg_var = a.leg_ierr = a.leg_stats = a.leg_th = a.leg_h = 0; a.leg_rconst = a.leg_fix = 0;      // (the series entries set them)
   a.flux = nullptr;      // (the flux entries set it)
   a.dense_out = nullptr; a.dense_nout = nullptr; a.dense_ns = 0; a.dense_block = 0;      // (the dense-output entries set them)
   a.ops_vdot = nullptr; a.ops_jvs = nullptr; a.ops_x = nullptr; a.ops_rhs = nullptr; a.ops_shift = nullptr; a.ops_ising = nullptr;      // (the operator entries set them)
@@ -2974,10 +2974,15 @@ int mistra_chem_rosenbrock_dense_cells_device(int mech, int ncell, const double*
 //      zero-pivot rows are not recorded (mistra_chem_singular_rows keeps describing the last call that is not a series).
 
 // what every series entry checks before anything touches a device, each refusal by its text
-static int check_series(int mech, int nleg, const double* times, const void* var_series) {
+// (rconst_legs, fix_legs: the blocks of rconst and fix, 1 = shared by all legs or nleg = the leg's own; the entries without them pass 1, 1)
+static int check_series(int mech, int nleg, const double* times, const void* var_series, int rconst_legs = 1, int fix_legs = 1) {
   if (int rc = builtin_only(mech, "series of Rosenbrock_x calls")) return rc;
   if (nleg < 1 || nleg > MISTRA_SERIES_MAX_LEGS)
     return fail("series: nleg = " + std::to_string(nleg) + ": a series has 1 .. MISTRA_SERIES_MAX_LEGS = " + std::to_string(MISTRA_SERIES_MAX_LEGS) + " legs");
+  if (rconst_legs != 1 && rconst_legs != nleg)
+    return fail("series: rconst_legs = " + std::to_string(rconst_legs) + ": rconst has 1 block (shared by all legs) or nleg = " + std::to_string(nleg) + " blocks");
+  if (fix_legs != 1 && fix_legs != nleg)
+    return fail("series: fix_legs = " + std::to_string(fix_legs) + ": fix has 1 block (shared by all legs) or nleg = " + std::to_string(nleg) + " blocks");
   if (!times) return fail("series: null times pointer (times: [nleg + 1], a host array)");
   if (!var_series) return fail("series: null var_series pointer (var_series: [nleg][ncell][NVAR])");
   for (int k = 0; k <= nleg; k++)
@@ -2992,23 +2997,25 @@ static int check_series(int mech, int nleg, const double* times, const void* var
 
 // one device slot's share of mistra_chem_rosenbrock_series_ex: cells [start, start + ncell) of the caller's batch of `total` cells
 static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, size_t total, const double* var_in, const double* fix, const double* rconst,
-                          int nleg, const double* times, const RosCall& call, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
+                          int rconst_legs, int fix_legs, int nleg, const double* times, const RosCall& call, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
                           int32_t* stats, double* t_h) {
   HIP_TRY(hipSetDevice(D.id));
   MechState& S = D.mech[mech];
   const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nc = (size_t)ncell, nl = (size_t)nleg;
   const size_t nb = call.block.size();
   HIP_TRY(S.s_var.reserve(nc * nv));
-  HIP_TRY(S.s_fix.reserve(nc * nf));
-  HIP_TRY(S.s_rct.reserve(nc * nr));
+  const size_t nlf = (size_t)fix_legs, nlr = (size_t)rconst_legs;
+  HIP_TRY(S.s_fix.reserve(nlf * nc * nf));
+  HIP_TRY(S.s_rct.reserve(nlr * nc * nr));
   HIP_TRY(S.s_ser_var.reserve(nl * nc * nv));
   HIP_TRY(S.s_ser_ierr.reserve(nl * nc));
   HIP_TRY(S.s_ser_stats.reserve(nl * nc * 8));
   if (t_h) HIP_TRY(S.s_ser_th.reserve(nl * nc * 3));
   HIP_TRY(S.call_opt.reserve(nb + nl + 1));
   HIP_TRY(hipMemcpy(S.s_var.p, var_in + start * nv, nc * nv * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(S.s_fix.p, fix + start * nf, nc * nf * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(S.s_rct.p, rconst + start * nr, nc * nr * sizeof(double), hipMemcpyHostToDevice));
+  // the slot's cells of every block of fix and rconst, [legs][total][.] of the caller's into [legs][nc][.] here: one 2-D copy each (one block: one row)
+  HIP_TRY(hipMemcpy2D(S.s_fix.p, nc * nf * sizeof(double), fix + start * nf, total * nf * sizeof(double), nc * nf * sizeof(double), nlf, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy2D(S.s_rct.p, nc * nr * sizeof(double), rconst + start * nr, total * nr * sizeof(double), nc * nr * sizeof(double), nlr, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(S.call_opt.p, call.block.data(), nb * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(S.call_opt.p + nb, times, (nl + 1) * sizeof(double), hipMemcpyHostToDevice));
   KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, times[0], times[nleg], S.s_ser_var.p, S.s_ser_ierr.p, S.s_ser_stats.p, t_h ? S.s_ser_th.p : nullptr);
@@ -3017,6 +3024,7 @@ static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, siz
   a.max_steps = call.max_steps;
   a.times = S.call_opt.p + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
   a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
+  a.leg_rconst = rconst_legs > 1 ? (int64_t)(nc * nr) : 0; a.leg_fix = fix_legs > 1 ? (int64_t)(nc * nf) : 0;      // the block's stride, not the caller's
   if (int rc = upload_cell_tol(S, call, start, nc, &a)) return rc;
   if (hstart) {
     HIP_TRY(S.s_hst.reserve(nc));
@@ -3042,10 +3050,10 @@ static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, siz
   return 0;
 }
 
-static int series_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int nleg, const double* times, const double* atol,
-                       const double* rtol, const double* rpar, const int32_t* ipar, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
-                       int32_t* stats, double* t_h, const CellTol* ct) {
-  if (int rc = check_series(mech, nleg, times, var_series)) return rc;
+static int series_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs, int fix_legs, int nleg,
+                       const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int carry_h,
+                       const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h, const CellTol* ct) {
+  if (int rc = check_series(mech, nleg, times, var_series, rconst_legs, fix_legs)) return rc;
   if (ct)
     if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
@@ -3068,14 +3076,15 @@ static int series_host(int mech, int ncell, const double* var_in, const double* 
   // var_in may alias one leg's block of var_series: every slot has its inputs on the device before any result comes back (below: all uploads of a
   // slot precede its downloads, and slots own disjoint cells)
   return on_cell_blocks(ncell, [=, &call](DeviceState& D, size_t start, int count) {
-    return series_host_on(D, mech, count, start, nc, var_in, fix, rconst, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h);
+    return series_host_on(D, mech, count, start, nc, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h);
   });
 }
 
-static int series_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int nleg, const double* times,
-                            const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_series, int32_t* d_ierr,
-                            int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart, void* hip_stream, const CellTol* ct) {
-  if (int rc = check_series(mech, nleg, times, d_var_series)) return rc;
+static int series_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int rconst_legs, int fix_legs,
+                            int nleg, const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
+                            double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart,
+                            void* hip_stream, const CellTol* ct) {
+  if (int rc = check_series(mech, nleg, times, d_var_series, rconst_legs, fix_legs)) return rc;
   if (ct)
     if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
@@ -3111,6 +3120,8 @@ static int series_on_device(int mech, int ncell, const double* d_var_in, const d
   a.max_steps = call.max_steps;
   a.times = db + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
   a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
+  a.leg_rconst = rconst_legs > 1 ? (int64_t)(nc * (size_t)kMech[mech].dims.nreact) : 0;      // the caller's arrays, read at the head of every leg
+  a.leg_fix = fix_legs > 1 ? (int64_t)(nc * (size_t)kMech[mech].dims.nfix) : 0;
   if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
   const int rc = launch(*t.D, mech, a, st, call.method);
   R.mark(i, st);
@@ -3120,21 +3131,21 @@ static int series_on_device(int mech, int ncell, const double* d_var_in, const d
 int mistra_chem_rosenbrock_series_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int nleg, const double* times,
                                      const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int carry_h, const double* hstart,
                                      double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
-  return series_host(mech, ncell, var_in, fix, rconst, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h, nullptr);
+  return series_host(mech, ncell, var_in, fix, rconst, 1, 1, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h, nullptr);
 }
 
 int mistra_chem_rosenbrock_series_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int nleg, const double* times,
                                            const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar, int carry_h,
                                            const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
   const CellTol ct{atol, rtol, ntol};
-  return series_host(mech, ncell, var_in, fix, rconst, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h, &ct);
+  return series_host(mech, ncell, var_in, fix, rconst, 1, 1, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h, &ct);
 }
 
 int mistra_chem_rosenbrock_series_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int nleg,
                                          const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                                          double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h,
                                          const double* d_hstart, void* hip_stream) {
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats, d_texit_hexit, carry_h,
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, 1, 1, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats, d_texit_hexit, carry_h,
                           d_hstart, hip_stream, nullptr);
 }
 
@@ -3143,8 +3154,43 @@ int mistra_chem_rosenbrock_series_cells_device(int mech, int ncell, const double
                                                const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                                int carry_h, const double* d_hstart, void* hip_stream) {
   const CellTol ct{d_atol, d_rtol, ntol};
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr, d_stats, d_texit_hexit,
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, 1, 1, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr, d_stats, d_texit_hexit,
                           carry_h, d_hstart, hip_stream, &ct);
+}
+
+// ---- the series with rate constants and FIX of the leg's own: the same path, the two counts the caller's
+int mistra_chem_rosenbrock_series_rates_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs, int fix_legs,
+                                           int nleg, const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
+                                           int carry_h, const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
+  return series_host(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
+                     t_h, nullptr);
+}
+
+int mistra_chem_rosenbrock_series_rates_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs,
+                                                 int fix_legs, int nleg, const double* times, const double* atol, const double* rtol, int ntol,
+                                                 const double* rpar, const int32_t* ipar, int carry_h, const double* hstart, double* var_series,
+                                                 int32_t* ierr, int32_t* stats, double* t_h) {
+  const CellTol ct{atol, rtol, ntol};
+  return series_host(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
+                     t_h, &ct);
+}
+
+int mistra_chem_rosenbrock_series_rates_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int rconst_legs,
+                                               int fix_legs, int nleg, const double* times, const double* atol, const double* rtol, const double* rpar,
+                                               const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                               int carry_h, const double* d_hstart, void* hip_stream) {
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats,
+                          d_texit_hexit, carry_h, d_hstart, hip_stream, nullptr);
+}
+
+int mistra_chem_rosenbrock_series_rates_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                                     int rconst_legs, int fix_legs, int nleg, const double* times, const double* d_atol,
+                                                     const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar, double* d_var_series,
+                                                     int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart,
+                                                     void* hip_stream) {
+  const CellTol ct{d_atol, d_rtol, ntol};
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr,
+                          d_stats, d_texit_hexit, carry_h, d_hstart, hip_stream, &ct);
 }
 
 int mistra_chem_cell_atol_device(int mech, int ncell, const double* d_var, double factor, double floor, double* d_atol, void* hip_stream) {

@@ -138,6 +138,10 @@ struct KernelArgs {
   int32_t ops_fun_rhs;         // /= 0: the cell's Fun_x is right-hand side 0
   int32_t ops_nrhs;
   int64_t ops_x_block, ops_rhs_block;      // elements from one row's block to the next: ncell*NVAR of the caller's arrays
+  // a series with rate constants and FIX of the leg's own (the series kernels; mistra_chem_rosenbrock_series_rates_ex / _device and their cells forms):
+  // leg k reads rconst + k*leg_rconst and fix + k*leg_fix (strides in elements), piecewise constant over the series as Update_RCONST_x in front of
+  // every call leaves them.  0 = one block for every leg.  Read by the series kernels only; 0 everywhere else (capi.cpp: make_args).
+  int64_t leg_rconst, leg_fix;
 };
 
 }  // namespace mistra

@@ -1190,7 +1190,9 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // from variant 0 sits behind `if constexpr (OPT)`, the other three compile from the statements they always had.
 // 5 = a series (ros_unit_kernel.hip; mistra_chem_rosenbrock_series_ex / _device): variant 3 with the part from the step-control set-up to the
 // results inside a loop over a.nleg legs, leg k one call of Rosenbrock_x from a.times[k] to a.times[k+1] on the state leg k-1 left, its results in
-// block k of the output arrays.  Everything the loop adds sits behind `if constexpr (SERIES)`; for the others the loop is one pass.
+// block k of the output arrays.  Everything the loop adds sits behind `if constexpr (SERIES)`; for the others the loop is one pass.  With a.leg_rconst /
+// a.leg_fix /= 0 (mistra_chem_rosenbrock_series_rates_ex / _device) leg k integrates with the rate constants at a.rconst +
+// k*a.leg_rconst and FIX at a.fix + k*a.leg_fix: a run-time form of the same fifteen kernels, taken up at the head of every leg behind the first.
 // 6 = the reaction flux (ros_unit_kernel.hip; mistra_chem_rosenbrock_flux_ex / _device): variant 3 of any of the five methods that also integrates every
 // reaction's rate over the call by the trapezoid rule on the accepted states and leaves one [NREACT] row per cell in a.flux.
 // Everything it adds sits behind `if constexpr (FLUX)`.
@@ -1400,8 +1402,12 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   }
   // (the register-starved kernels fetch them per use, like their factor words)
   constexpr bool RCT_PER_USE = MT::WAVES_PER_SIMD > kResidentMaxWps || L::RCT_IN_LDS;
+  // VARIANT 5: the leg index (the legs' loop, below).  Declared here because the leg's own rate constants (a.leg_rconst, kernel_args.hpp) start at
+  // a.rconst + leg*a.leg_rconst: a base formed from two scalars where the fetch uses it, never a vector value kept across the step loop.
+  [[maybe_unused]] int leg = 0;
   auto load_rct = [&](bool opaque) {      // this thread's rate constants; opaque: the per-use fetch (RCT_PER_USE)
     const double* rc = a.rconst;
+    if constexpr (SERIES) rc += (int64_t)leg * a.leg_rconst;
     if (opaque) asm volatile("" : "+s"(rc));
     int tt = t;
     if (opaque) asm volatile("" : "+v"(tt));      // (addresses derived where they are used: hoisted out of the step loop they are registers that spill)
@@ -1967,7 +1973,6 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   //      leg's two times (scalar loads out of the call's options block, which nothing writes while the kernel runs) and the offsets of its output blocks,
   //      formed where they are used.  Every per-call quantity of Rosenbrock_x starts afresh below.  Nothing is carried around the loop in a vector
   //      register: with a.carry_h the leg's first step is read from the Hexit cell, in LDS, before thread 0 resets it.
-  [[maybe_unused]] int leg = 0;
   do {
     if constexpr (SERIES) {
       const auto times = (const double __attribute__((address_space(4)))*)a.times;
@@ -1982,6 +1987,24 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
           const double hx =wave_uniform(*(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT)));
           if (hx > 0.0) hstart0 = hx;
           lds_barrier();      // every wave has read the cell before thread 0 resets it
+        }
+        // RCONST and FIX of the leg's own (a.leg_rconst / a.leg_fix /= 0, uniform over the call): what Update_RCONST_x left in front of this call of
+        // Rosenbrock_x.  The per-use fetch out of global memory needs nothing here: load_rct forms the leg's base itself.
+        if (a.leg_rconst != 0) {
+          if constexpr (L::RCT_IN_LDS) {      // the cell's copy in LDS: every thread rewrites the cells it reads back itself (r = q*NT + t): no barrier involved
+            const double* rc = a.rconst + (int64_t)leg * a.leg_rconst;
+#pragma unroll
+            for (int q = 0; q < RPT; q++) {
+              const int r = q * NT + t;
+              if (r < NREACT) lds[L::RCT + r] = G_(rc)[(size_t)cell * NREACT + r];
+            }
+          } else if constexpr (!RCT_PER_USE) {      // resident registers (a lane whose r >= NREACT keeps 0.0)
+            load_rct(false);
+          }
+        }
+        if (a.leg_fix != 0) {      // other threads read these cells (the A and B products): the write goes behind a barrier that follows the previous
+          if (!a.carry_h) lds_barrier();      // leg's last read of X (a.carry_h: its two, above) and in front of the one the leg's first Fun_x passes behind store_x
+          if (t < NFIX) X[NVAR + t] = G_(a.fix + (int64_t)leg * a.leg_fix)[(size_t)cell * NFIX + t];
         }
       }
     }

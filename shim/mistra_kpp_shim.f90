@@ -49,6 +49,13 @@
 ! previous leg's HEXIT of the cell where that is > 0 instead of RPAR(3).  ros_ErrorMsg_x's lines go to unit 6 for every failed leg and cell, in leg order.
 !     SUBROUTINE ROSENBROCK_BATCH_SERIES_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
 !     SUBROUTINE ROSENBROCK_BATCH_SERIES_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+! The same with RATE CONSTANTS AND FIX OF THE LEG'S OWN (mistra_chem_rosenbrock_series_rates_ex; INTEGRATION.md 4q): Update_RCONST_x + INTEGRATE_x, NLEG times, in
+! one launch.  RCONST(NREACT,NCELL,NRCLEG), FIX(NFIX,NCELL,NFIXLEG), each count 1 (shared by all legs) or NLEG: leg l integrates with RCONST(:,:,l) and FIX(:,:,l),
+! bit for bit what ROSENBROCK_BATCH_x called NLEG times with those returns.  The printed lines are the series'.
+!     SUBROUTINE ROSENBROCK_BATCH_SERIES_RATES_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT,
+!                                                            IERR, ISTAT)
+!     SUBROUTINE ROSENBROCK_BATCH_SERIES_RATES_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER,
+!                                                                  TEXIT, HEXIT, IERR, ISTAT)
 !
 ! THE REACTION FLUX (mistra_chem_rosenbrock_flux_ex; INTEGRATION.md 4n): ROSENBROCK_BATCH_x / ROSENBROCK_BATCH_CELLS_x with one more result behind their
 ! argument lists, FLUX(NREACT,NCELL): every reaction's rate integrated over the call by the trapezoid rule on the accepted states.  Everything else is what
@@ -217,6 +224,28 @@ module mistra_chem_c_api
        integer(c_int32_t) :: ierr(*), stats(*)
        integer(c_int) :: rc
      end function mistra_chem_rosenbrock_series_cells_ex
+     function mistra_chem_rosenbrock_series_rates_ex(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, &
+          var_series, ierr, stats, t_h) bind(C, name="mistra_chem_rosenbrock_series_rates_ex") result(rc)
+       import :: c_int, c_double, c_int32_t, c_ptr
+       integer(c_int), value :: mech, ncell, rconst_legs, fix_legs, nleg, carry_h
+       type(c_ptr), value :: hstart
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_series(*), t_h(*)
+       real(c_double), intent(in) :: times(*), atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_series_rates_ex
+     function mistra_chem_rosenbrock_series_rates_cells_ex(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, ntol, rpar, ipar, &
+          carry_h, hstart, var_series, ierr, stats, t_h) bind(C, name="mistra_chem_rosenbrock_series_rates_cells_ex") result(rc)
+       import :: c_int, c_double, c_int32_t, c_ptr
+       integer(c_int), value :: mech, ncell, rconst_legs, fix_legs, nleg, ntol, carry_h
+       type(c_ptr), value :: hstart
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_series(*), t_h(*)
+       real(c_double), intent(in) :: times(*), atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_series_rates_cells_ex
      function mistra_chem_ops_ex(mech, ncell, var, fix, rconst, vdot, jvs, nshift, shift, fun_rhs, nrhs, rhs, x, ising) &
           bind(C, name="mistra_chem_ops_ex") result(rc)
        import :: c_int, c_double, c_ptr
@@ -499,9 +528,10 @@ contains
   ! A series of Rosenbrock_x calls for NCELL cells in one launch; the messages leg by leg and in cell order, as NLEG calls of ROSENBROCK_BATCH_x would have
   ! written ros_ErrorMsg_x's lines (a refusal at T = the leg's start, H = 0).  The rows of zero pivots are not recorded for a series: no warning lines.
   ! NTOL present: ATOL / RTOL hold a row of NTOL entries per cell (ROSENBROCK_BATCH_SERIES_CELLS_x)
-  subroutine rosenbrock_series(mech, sfx, NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL)
+  ! NRCLEG and NFIXLEG present: RCONST and FIX hold that many blocks of NCELL cells, 1 or NLEG (ROSENBROCK_BATCH_SERIES_RATES_x / _RATES_CELLS_x)
+  subroutine rosenbrock_series(mech, sfx, NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL, NRCLEG, NFIXLEG)
     integer, intent(in) :: mech, NCELL, NLEG
-    integer, intent(in), optional :: NTOL
+    integer, intent(in), optional :: NTOL, NRCLEG, NFIXLEG
     character(len=1), intent(in) :: sfx
     logical, intent(in) :: CARRY
     real(c_double) :: VAR(*), FIX(*), RCONST(*), VSER(*), TEXIT(NCELL, *), HEXIT(NCELL, *)
@@ -512,7 +542,17 @@ contains
     integer :: k, l
     if (NCELL <= 0) return
     allocate (th(3, NCELL, max(NLEG, 1)))
-    if (present(NTOL)) then
+    if (present(NRCLEG) .and. present(NFIXLEG)) then
+       if (present(NTOL)) then
+          if (mistra_chem_rosenbrock_series_rates_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NRCLEG, c_int), int(NFIXLEG, c_int), &
+               int(NLEG, c_int), TIMES, ATOL, RTOL, int(NTOL, c_int), RPAR, IPAR, int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th) /= 0) &
+               call mistra_chem_fail('ROSENBROCK_BATCH_SERIES_RATES_CELLS_'//sfx)
+       else
+          if (mistra_chem_rosenbrock_series_rates_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NRCLEG, c_int), int(NFIXLEG, c_int), &
+               int(NLEG, c_int), TIMES, ATOL, RTOL, RPAR, IPAR, int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th) /= 0) &
+               call mistra_chem_fail('ROSENBROCK_BATCH_SERIES_RATES_'//sfx)
+       end if
+    else if (present(NTOL)) then
        if (mistra_chem_rosenbrock_series_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NLEG, c_int), TIMES, ATOL, RTOL, int(NTOL, c_int), &
             RPAR, IPAR, int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_SERIES_CELLS_'//sfx)
     else
@@ -968,6 +1008,79 @@ subroutine ROSENBROCK_BATCH_SERIES_CELLS_t(NCELL, VAR, FIX, RCONST, NLEG, TIMES,
   integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
   call rosenbrock_series(2, 't', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL)
 end subroutine ROSENBROCK_BATCH_SERIES_CELLS_t
+
+! ---- the series with rate constants and FIX of the leg's own: RCONST(NREACT,NCELL,NRCLEG), FIX(NFIX,NCELL,NFIXLEG), each count 1 or NLEG
+subroutine ROSENBROCK_BATCH_SERIES_RATES_g(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG
+  logical :: CARRY
+  real(c_double) :: VAR(102, *), FIX(3, NCELL, *), RCONST(331, NCELL, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(102, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(0, 'g', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NRCLEG=NRCLEG, NFIXLEG=NFIXLEG)
+end subroutine ROSENBROCK_BATCH_SERIES_RATES_g
+
+subroutine ROSENBROCK_BATCH_SERIES_RATES_CELLS_g(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, &
+     ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG, NTOL
+  logical :: CARRY
+  real(c_double) :: VAR(102, *), FIX(3, NCELL, *), RCONST(331, NCELL, *), TIMES(*), ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), VSER(102, NCELL, *), TEXIT(NCELL, *), &
+       HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(0, 'g', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL, NRCLEG, NFIXLEG)
+end subroutine ROSENBROCK_BATCH_SERIES_RATES_CELLS_g
+
+subroutine ROSENBROCK_BATCH_SERIES_RATES_a(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG
+  logical :: CARRY
+  real(c_double) :: VAR(257, *), FIX(5, NCELL, *), RCONST(979, NCELL, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(257, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(1, 'a', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NRCLEG=NRCLEG, NFIXLEG=NFIXLEG)
+end subroutine ROSENBROCK_BATCH_SERIES_RATES_a
+
+subroutine ROSENBROCK_BATCH_SERIES_RATES_CELLS_a(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, &
+     ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG, NTOL
+  logical :: CARRY
+  real(c_double) :: VAR(257, *), FIX(5, NCELL, *), RCONST(979, NCELL, *), TIMES(*), ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), VSER(257, NCELL, *), TEXIT(NCELL, *), &
+       HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(1, 'a', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL, NRCLEG, NFIXLEG)
+end subroutine ROSENBROCK_BATCH_SERIES_RATES_CELLS_a
+
+subroutine ROSENBROCK_BATCH_SERIES_RATES_t(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG
+  logical :: CARRY
+  real(c_double) :: VAR(417, *), FIX(7, NCELL, *), RCONST(1627, NCELL, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(417, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(2, 't', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NRCLEG=NRCLEG, NFIXLEG=NFIXLEG)
+end subroutine ROSENBROCK_BATCH_SERIES_RATES_t
+
+subroutine ROSENBROCK_BATCH_SERIES_RATES_CELLS_t(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, &
+     ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG, NTOL
+  logical :: CARRY
+  real(c_double) :: VAR(417, *), FIX(7, NCELL, *), RCONST(1627, NCELL, *), TIMES(*), ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), VSER(417, NCELL, *), TEXIT(NCELL, *), &
+       HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(2, 't', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL, NRCLEG, NFIXLEG)
+end subroutine ROSENBROCK_BATCH_SERIES_RATES_CELLS_t
 
 ! ---- the reaction flux: ROSENBROCK_BATCH_x / ROSENBROCK_BATCH_CELLS_x with FLUX(NREACT,NCELL) behind their argument lists
 subroutine ROSENBROCK_BATCH_FLUX_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, TEXIT, HEXIT, IERR, ISTAT, FLUX)

@@ -16,6 +16,10 @@
 !                                                      TIMES(nleg + 1), then the cells as for <G|A|T>.  ntol = 0: ONE call of ROSENBROCK_BATCH_SERIES_x with the pair; ntol = 1 or
 !                                                      NVAR: ONE call of ROSENBROCK_BATCH_SERIES_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin = per leg
 !                                                      and cell VAR, TEXIT, HEXIT, IERR, the 8 statistics
+!          shim_driver <NG|NA|NT> <in.bin> <out.bin>   the series with rate constants and FIX of the leg's own: in.bin = IPAR(20), RPAR(20), ATOL(NVAR), RTOL(NVAR), ncell,
+!                                                      nleg, carry (0 | 1), ntol, nrcleg, nfixleg, TIMES(nleg + 1), VAR(NVAR, ncell), FIX(NFIX, ncell, nfixleg),
+!                                                      RCONST(NREACT, ncell, nrcleg).  ntol = 0: ONE call of ROSENBROCK_BATCH_SERIES_RATES_x; ntol = 1 or NVAR: ONE call of
+!                                                      ROSENBROCK_BATCH_SERIES_RATES_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin as for <ZG|ZA|ZT>
 !          shim_driver <WG|WA|WT> <in.bin> <out.bin>   Rosenbrock_x with the reaction flux: in.bin = IPAR(20), RPAR(20), ATOL(NVAR), RTOL(NVAR), TSTART, TEND, ncell, ntol, then
 !                                                      the cells as for <G|A|T>.  ntol = 0: ONE call of ROSENBROCK_BATCH_FLUX_x with the pair; ntol = 1 or NVAR: ONE call of
 !                                                      ROSENBROCK_BATCH_FLUX_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin = per cell VAR, TEXIT,
@@ -91,6 +95,13 @@ program shim_driver
      case ('G'); call run_series(0, 102, 3, 331, trim(fin), trim(fout))
      case ('A'); call run_series(1, 257, 5, 979, trim(fin), trim(fout))
      case ('T'); call run_series(2, 417, 7, 1627, trim(fin), trim(fout))
+     case default; stop 'mechanism must be G, A or T'
+     end select
+  case ('N')
+     select case (a1(2:2))
+     case ('G'); call run_series_rates(0, 102, 3, 331, trim(fin), trim(fout))
+     case ('A'); call run_series_rates(1, 257, 5, 979, trim(fin), trim(fout))
+     case ('T'); call run_series_rates(2, 417, 7, 1627, trim(fin), trim(fout))
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('W')
@@ -505,6 +516,59 @@ contains
     end do
     close (11); close (12)
   end subroutine run_series
+  subroutine run_series_rates(mech, NVAR, NFIX, NREACT, fin, fout)
+    integer, intent(in) :: mech, NVAR, NFIX, NREACT
+    character(len=*), intent(in) :: fin, fout
+    double precision :: ropt(40), tt(6)
+    double precision, allocatable :: ATOL(:), RTOL(:), AROW(:, :), RROW(:, :), TIMES(:), VAR(:, :), FIX(:, :, :), RCONST(:, :, :), VSER(:, :, :), TEXIT(:, :), HEXIT(:, :)
+    integer :: IPAR(20), n, nleg, ntol, nrc, nfx, i, l
+    logical :: carry
+    integer, allocatable :: IERR(:, :), ISTAT(:, :, :)
+    open (11, file=fin, access='stream', form='unformatted', status='old')
+    open (12, file=fout, access='stream', form='unformatted', status='replace')
+    allocate (ATOL(NVAR), RTOL(NVAR))
+    read (11) ropt, ATOL, RTOL, tt      ! tt: ncell, nleg, carry, ntol, nrcleg, nfixleg
+    IPAR = int(ropt(1:20))
+    n = int(tt(1))
+    nleg = int(tt(2))
+    carry = tt(3) /= 0.d0
+    ntol = int(tt(4))
+    nrc = int(tt(5))
+    nfx = int(tt(6))
+    allocate (TIMES(nleg + 1))
+    read (11) TIMES
+    allocate (VAR(NVAR, n), FIX(NFIX, n, nfx), RCONST(NREACT, n, nrc), VSER(NVAR, n, nleg), TEXIT(n, nleg), HEXIT(n, nleg), IERR(n, nleg), ISTAT(8, n, nleg))
+    allocate (AROW(max(ntol, 1), n), RROW(max(ntol, 1), n))
+    read (11) VAR, FIX, RCONST
+    do i = 1, n
+       if (ntol > 0) then
+          AROW(:, i) = ATOL(1:ntol)
+          RROW(:, i) = RTOL(1:ntol)
+       end if
+    end do
+    if (ntol == 0) then
+       select case (mech)
+       case (0); call ROSENBROCK_BATCH_SERIES_RATES_g(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       case (1); call ROSENBROCK_BATCH_SERIES_RATES_a(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       case (2); call ROSENBROCK_BATCH_SERIES_RATES_t(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       end select
+    else
+       select case (mech)
+       case (0); call ROSENBROCK_BATCH_SERIES_RATES_CELLS_g(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, AROW, RROW, ntol, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, &
+            IERR, ISTAT)
+       case (1); call ROSENBROCK_BATCH_SERIES_RATES_CELLS_a(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, AROW, RROW, ntol, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, &
+            IERR, ISTAT)
+       case (2); call ROSENBROCK_BATCH_SERIES_RATES_CELLS_t(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, AROW, RROW, ntol, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, &
+            IERR, ISTAT)
+       end select
+    end if
+    do l = 1, nleg
+       do i = 1, n
+          write (12) VSER(:, i, l), TEXIT(i, l), HEXIT(i, l), dble(IERR(i, l)), dble(ISTAT(:, i, l))
+       end do
+    end do
+    close (11); close (12)
+  end subroutine run_series_rates
   subroutine run_env(mech, NVAR, NFIX, NREACT, NENV, fin, fout)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT, NENV
     character(len=*), intent(in) :: fin, fout

@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
-"""One series against the sequence of calls it replaces (profiles/r13_series_kernels.txt): per mechanism, `--cells` cells of the
-synthetic workload (mistra_amd/workload.py), Ros3 at INTEGRATE_x's options, `--legs` equal legs over 0 -> 10 s — once as ONE call of the series device
-entry, once as `--legs` queued calls of mistra_chem_rosenbrock_device on the chained state.  `--repeats` timed repeats of each behind one warm-up, taken
-in turn.  Per repeat: the time between two events on the stream around the call(s) — the kernels and the copies of the options blocks in front of
-them — and the wall time from the first call to the end of the synchronisation.  The two sides' states are compared bit for bit first.
+"""One series against the sequence of calls it replaces (profiles/r13_series_kernels.txt, r17_series_rates_kernels.txt): per
+mechanism, `--cells` cells of the synthetic workload (mistra_amd/workload.py), Ros3 at INTEGRATE_x's options, `--legs` equal legs over 0 -> 10 s — once
+as ONE call of the series device entry, once as `--legs` queued calls of mistra_chem_rosenbrock_device on the chained state.  `--repeats` timed repeats
+of each behind one warm-up, taken in turn.  Per repeat: the time between two events on the stream around the call(s) — the kernels and the copies of
+the options blocks in front of them — and the wall time from the first call to the end of the synchronisation.  The two sides' states are compared bit
+for bit first.
 
-    python tools/bench_series.py [--cells 4096] [--legs 8] [--repeats 5] [--mechs gas aer tot]"""
+    python tools/bench_series.py [--cells 4096] [--legs 8] [--repeats 5] [--mechs gas aer tot]
+    python tools/bench_series.py --rates            every leg with rate constants and FIX of its own (chem.rosenbrock_series_rates): leg k's rate
+                                                    constants are the workload's times 1 + 0.02*k, FIX a copy per leg; the sequence passes leg k's rows
+    python tools/bench_series.py --against LIB      the plain series of this tree's library against the plain series of another build of the library
+                                                    (a second copy of mistra_amd/chem.py bound to LIB, in the same process), taken in turn"""
 import argparse
+import importlib.util
 import os
 import sys
 import time
@@ -17,31 +23,54 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
+def other_build(path):
+    """a second copy of mistra_amd.chem bound to the library at `path`"""
+    spec = importlib.util.spec_from_file_location("mistra_amd.chem_other", os.path.join(REPO, "mistra_amd", "chem.py"))
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[spec.name] = mod
+    spec.loader.exec_module(mod)
+    mod.LIB_PATH = os.path.abspath(path)
+    return mod
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--cells", type=int, default=4096)
     ap.add_argument("--legs", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--mechs", nargs="+", default=["gas", "aer", "tot"])
+    ap.add_argument("--rates", action="store_true")
+    ap.add_argument("--against", metavar="LIB")
     a = ap.parse_args(argv)
     import torch
     from mistra_amd import chem
     from mistra_amd import workload as W
     dev = torch.device("cuda", 0)
     chem.init(0)
+    other = None
+    if a.against:
+        other = other_build(a.against)
+        other.init(0)
     times = np.linspace(0.0, 10.0, a.legs + 1)
-    print("%d cells, Ros3 at INTEGRATE_x's options, %d legs of %g s; %d repeats behind one warm-up; ms: median [min .. max]" %
-          (a.cells, a.legs, 10.0 / a.legs, a.repeats))
+    print("%d cells, Ros3 at INTEGRATE_x's options, %d legs of %g s%s; %d repeats behind one warm-up; ms: median [min .. max]" %
+          (a.cells, a.legs, 10.0 / a.legs, ", rate constants and FIX of the leg's own" if a.rates else "", a.repeats))
     for mech in a.mechs:
         V, F, K = W.make_batch(mech, 0, a.cells, dev)
+        if a.rates:
+            scale = torch.tensor(1.0 + 0.02 * np.arange(a.legs), device=dev).view(-1, 1, 1)
+            LK, LF = (K.unsqueeze(0) * scale).contiguous(), F.unsqueeze(0).repeat(a.legs, 1, 1).contiguous()
 
         def series():
+            if a.rates:
+                return chem.rosenbrock_series_rates(mech, V, LF, LK, times).var[-1]
             return chem.rosenbrock_series(mech, V, F, K, times).var[-1]
 
         def sequence():
+            if other is not None:
+                return other.rosenbrock_series(mech, V, F, K, times).var[-1]
             y = V
             for k in range(a.legs):
-                y = chem.rosenbrock(mech, y, F, K, float(times[k]), float(times[k + 1]))[0].var
+                y = chem.rosenbrock(mech, y, LF[k] if a.rates else F, LK[k] if a.rates else K, float(times[k]), float(times[k + 1]))[0].var
             return y
 
         def timed(f):
@@ -54,22 +83,23 @@ def main(argv=None):
             torch.cuda.synchronize()
             return e0.elapsed_time(e1), 1.0e3 * (time.perf_counter() - t0), y
 
+        a_name, b_name = ("this", "other") if other is not None else ("series", "sequence")
         ys, yq = timed(series)[2], timed(sequence)[2]      # warm-up
         same = ys.cpu().numpy().tobytes() == yq.cpu().numpy().tobytes()
-        rows = {"series": [], "sequence": []}
+        rows = {a_name: [], b_name: []}
         for _ in range(a.repeats):
-            rows["series"].append(timed(series)[:2])
-            rows["sequence"].append(timed(sequence)[:2])
+            rows[a_name].append(timed(series)[:2])
+            rows[b_name].append(timed(sequence)[:2])
         fmt = lambda x: "%9.3f [%9.3f .. %9.3f]" % (float(np.median(x)), min(x), max(x))
         print("%s: end states of the two sides %s" % (mech, "identical bit for bit" if same else "DIFFER"))
-        for side in ("series", "sequence"):
+        for side in (a_name, b_name):
             ev, wall = [r[0] for r in rows[side]], [r[1] for r in rows[side]]
             print("  %-9s stream %s   wall %s" % (side, fmt(ev), fmt(wall)))
-        ev_s, ev_q = np.array([r[0] for r in rows["series"]]), np.array([r[0] for r in rows["sequence"]])
-        wl_s, wl_q = np.array([r[1] for r in rows["series"]]), np.array([r[1] for r in rows["sequence"]])
-        print("  series / sequence: stream %.4f, wall %.4f (medians); the sequence's own spread (max - min) / median: stream %.4f, wall %.4f" %
-              (np.median(ev_s) / np.median(ev_q), np.median(wl_s) / np.median(wl_q), (ev_q.max() - ev_q.min()) / np.median(ev_q),
-               (wl_q.max() - wl_q.min()) / np.median(wl_q)))
+        ev_s, ev_q = np.array([r[0] for r in rows[a_name]]), np.array([r[0] for r in rows[b_name]])
+        wl_s, wl_q = np.array([r[1] for r in rows[a_name]]), np.array([r[1] for r in rows[b_name]])
+        print("  %s / %s: stream %.4f, wall %.4f (medians); the %s's own spread (max - min) / median: stream %.4f, wall %.4f" %
+              (a_name, b_name, np.median(ev_s) / np.median(ev_q), np.median(wl_s) / np.median(wl_q), b_name if other is None else "other build",
+               (ev_q.max() - ev_q.min()) / np.median(ev_q), (wl_q.max() - wl_q.min()) / np.median(wl_q)))
     return 0
 
 
