@@ -787,7 +787,7 @@ __device__ __attribute__((noinline)) void scale_run(const ScaleDev P, int wave, 
 //      dependent f64 operation, 72 for the IEEE reciprocal, ~30 for a same-wave LDS write -> read (which is why the
 //      eliminating wave passes pivot rows lane to lane through LDS: v_readlane into an SGPR and back costs ~60).
 #ifdef MISTRA_DIAG_STAMPS      // diagnostic builds only (tools/diag_dense.sh): cycles of wave 0 per section of dense_lu, summed over calls
-__device__ unsigned long long g_dense_stamps[16];
+__device__ unsigned long long g_dense_stamps[24];
 #define MISTRA_STAMP(var) const unsigned long long var = clock64();
 #define MISTRA_STAMP_ADD(slot, expr) if (threadIdx.x == 0) atomicAdd(&g_dense_stamps[slot], (unsigned long long)(expr));
 #else
@@ -970,21 +970,22 @@ __device__ __forceinline__ void dense_panel(f64x4& T0, f64x4& T1, const int P, c
 // left the pivot row's inf alone.  After such an overflow the stored U'(j,c) of that row differ from the panel form's (NaN for
 // inf); a factorisation holding either makes the solves' result non-finite, the error norm with it, and `Err <= 1` rejects the step.
 #define MISTRA_FIN_F(J, C) "v_fmac_f64_dpp %[x" #C "], -%[x" #C "], %[l] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
-#define MISTRA_FIN_FROM_15(J) MISTRA_FIN_F(J, 15)
-#define MISTRA_FIN_FROM_14(J) MISTRA_FIN_F(J, 14) MISTRA_FIN_FROM_15(J)
-#define MISTRA_FIN_FROM_13(J) MISTRA_FIN_F(J, 13) MISTRA_FIN_FROM_14(J)
-#define MISTRA_FIN_FROM_12(J) MISTRA_FIN_F(J, 12) MISTRA_FIN_FROM_13(J)
-#define MISTRA_FIN_FROM_11(J) MISTRA_FIN_F(J, 11) MISTRA_FIN_FROM_12(J)
-#define MISTRA_FIN_FROM_10(J) MISTRA_FIN_F(J, 10) MISTRA_FIN_FROM_11(J)
-#define MISTRA_FIN_FROM_9(J) MISTRA_FIN_F(J, 9) MISTRA_FIN_FROM_10(J)
-#define MISTRA_FIN_FROM_8(J) MISTRA_FIN_F(J, 8) MISTRA_FIN_FROM_9(J)
-#define MISTRA_FIN_FROM_7(J) MISTRA_FIN_F(J, 7) MISTRA_FIN_FROM_8(J)
-#define MISTRA_FIN_FROM_6(J) MISTRA_FIN_F(J, 6) MISTRA_FIN_FROM_7(J)
-#define MISTRA_FIN_FROM_5(J) MISTRA_FIN_F(J, 5) MISTRA_FIN_FROM_6(J)
-#define MISTRA_FIN_FROM_4(J) MISTRA_FIN_F(J, 4) MISTRA_FIN_FROM_5(J)
-#define MISTRA_FIN_FROM_3(J) MISTRA_FIN_F(J, 3) MISTRA_FIN_FROM_4(J)
-#define MISTRA_FIN_FROM_2(J) MISTRA_FIN_F(J, 2) MISTRA_FIN_FROM_3(J)
-#define MISTRA_FIN_FROM_1(J) MISTRA_FIN_F(J, 1) MISTRA_FIN_FROM_2(J)
+#define MISTRA_DPP_FROM_15(F, J) F(J, 15)
+#define MISTRA_DPP_FROM_14(F, J) F(J, 14) MISTRA_DPP_FROM_15(F, J)
+#define MISTRA_DPP_FROM_13(F, J) F(J, 13) MISTRA_DPP_FROM_14(F, J)
+#define MISTRA_DPP_FROM_12(F, J) F(J, 12) MISTRA_DPP_FROM_13(F, J)
+#define MISTRA_DPP_FROM_11(F, J) F(J, 11) MISTRA_DPP_FROM_12(F, J)
+#define MISTRA_DPP_FROM_10(F, J) F(J, 10) MISTRA_DPP_FROM_11(F, J)
+#define MISTRA_DPP_FROM_9(F, J) F(J, 9) MISTRA_DPP_FROM_10(F, J)
+#define MISTRA_DPP_FROM_8(F, J) F(J, 8) MISTRA_DPP_FROM_9(F, J)
+#define MISTRA_DPP_FROM_7(F, J) F(J, 7) MISTRA_DPP_FROM_8(F, J)
+#define MISTRA_DPP_FROM_6(F, J) F(J, 6) MISTRA_DPP_FROM_7(F, J)
+#define MISTRA_DPP_FROM_5(F, J) F(J, 5) MISTRA_DPP_FROM_6(F, J)
+#define MISTRA_DPP_FROM_4(F, J) F(J, 4) MISTRA_DPP_FROM_5(F, J)
+#define MISTRA_DPP_FROM_3(F, J) F(J, 3) MISTRA_DPP_FROM_4(F, J)
+#define MISTRA_DPP_FROM_2(F, J) F(J, 2) MISTRA_DPP_FROM_3(F, J)
+#define MISTRA_DPP_FROM_1(F, J) F(J, 1) MISTRA_DPP_FROM_2(F, J)
+#define MISTRA_DPP_FROM_16(F, J)
 #define MISTRA_FIN_XS [x0] "+v"(x0), [x1] "+v"(x1), [x2] "+v"(x2), [x3] "+v"(x3), [x4] "+v"(x4), [x5] "+v"(x5), [x6] "+v"(x6), [x7] "+v"(x7), \
                       [x8] "+v"(x8), [x9] "+v"(x9), [x10] "+v"(x10), [x11] "+v"(x11), [x12] "+v"(x12), [x13] "+v"(x13), [x14] "+v"(x14), [x15] "+v"(x15)
 // pivot J (J1 = J + 1): the diagonal to every lane of its row (the wait states: the register was written two instructions back
@@ -1001,15 +1002,18 @@ __device__ __forceinline__ void dense_panel(f64x4& T0, f64x4& T1, const int P, c
                  "v_mul_f64 %[l], %[x" #J "], %[R]\n\t"                                                                               \
                  "v_mul_f64 %[x" #J "], %[x" #J "], %[R]\n\t"                                                                         \
                  "s_mov_b32 exec_lo, %[ge]\n\ts_mov_b32 exec_hi, %[ge]\n\t"                                                           \
-                 MISTRA_FIN_FROM_##J1(J)                                                                                              \
+                 MISTRA_DPP_FROM_##J1(MISTRA_FIN_F, J)                                                                                             \
                  "s_mov_b64 exec, -1"                                                                                                 \
                  : [l] "=&v"(l), MISTRA_FIN_XS : [R] "v"(R), [nz] "v"(nz), [gt] "i"((int)GT), [ge] "i"((int)GE));                               \
   }
-template <class MT, int NT>
-__device__ __attribute__((noinline)) void dense_finish(const f64x4 T, const int lane) {
+// A diagonal tile in its owner's accumulator registers T, factorised through the 16 rows of the LDS buffer BUF (144 bytes apart) and left
+// there row by row, L below the diagonal and U from it on.  LAST: the block's last tile, (3,3): its entries and reciprocals go to their Ghimj slots
+// from here.  Else the tile of a tile step (dense_lu): the waves that solve the step's panels read the rows, and one of them stores them.
+template <class MT, int NT, bool LAST>
+__device__ __forceinline__ void dense_diag_tile(const f64x4 T, const int lane, const uint32_t BUF) {
   constexpr uint32_t NNZ = MT::NNZ, NVAR = MT::NVAR, H = NVAR - 64, ZERO = 8u * (NNZ + NVAR);
   constexpr uint32_t INFO = 8u * (uint32_t)LdsLayout<MT, NT>::DINFO, RDIAG = 8u * (NNZ + NVAR + 4u);
-  constexpr uint32_t BUF = 8u * (uint32_t)LdsLayout<MT, NT>::PANEL, STRIDE = 144u;      // the panel buffers' even half: panel 11 and its storers use the odd one; rows 16 bytes apart in the banks
+  constexpr uint32_t STRIDE = 144u;      // rows 16 bytes apart in the banks
   const uint32_t lrow = (uint32_t)(lane >> 4), i = (uint32_t)(lane & 15);
   MISTRA_STAMP(tf0)
   // accumulator layout (lane l, element r = row (l>>4) + 4r, column l&15) -> lane = row: through LDS; one wave, in-order LDS
@@ -1019,15 +1023,17 @@ __device__ __attribute__((noinline)) void dense_finish(const f64x4 T, const int 
   double x0 = q0[0], x1 = q0[1], x2 = q0[2], x3 = q0[3], x4 = q1[0], x5 = q1[1], x6 = q1[2], x7 = q1[3];
   double x8 = q2[0], x9 = q2[1], x10 = q2[2], x11 = q2[3], x12 = q3[0], x13 = q3[1], x14 = q3[2], x15 = q3[3];
   // the lane's four slots: row 48 + i, columns 48 + 4 lrow .. + 3 (dense_slot for four columns in a row, all in the table's high word)
-  const u32x4 info = lds_ldu4(INFO + 16u * (48u + i));
-  const uint32_t cb = 16u + 4u * lrow;
-  uint32_t idx = info.x + 32u + cb - (uint32_t)__builtin_popcount(info.y) - (uint32_t)__builtin_popcount(info.z & ((1u << cb) - 1u));
   uint32_t at[4];
+  if constexpr (LAST) {
+    const u32x4 info = lds_ldu4(INFO + 16u * (48u + i));
+    const uint32_t cb = 16u + 4u * lrow;
+    uint32_t idx = info.x + 32u + cb - (uint32_t)__builtin_popcount(info.y) - (uint32_t)__builtin_popcount(info.z & ((1u << cb) - 1u));
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const uint32_t absent = (info.z >> (cb + (uint32_t)k)) & 1u;
-    at[k] = absent ? ZERO : 8u * idx;
-    idx += 1u - absent;
+    for (int k = 0; k < 4; k++) {
+      const uint32_t absent = (info.z >> (cb + (uint32_t)k)) & 1u;
+      at[k] = absent ? ZERO : 8u * idx;
+      idx += 1u - absent;
+    }
   }
   const double nz = -0.0;
   MISTRA_FIN_PIVOT(0, 1) MISTRA_FIN_PIVOT(1, 2) MISTRA_FIN_PIVOT(2, 3) MISTRA_FIN_PIVOT(3, 4) MISTRA_FIN_PIVOT(4, 5)
@@ -1038,37 +1044,166 @@ __device__ __attribute__((noinline)) void dense_finish(const f64x4 T, const int 
   // lanes of a row takes its four columns and the row's own diagonal without sixteen-way selects
   lds_st4_a16(BUF + STRIDE * i, f64x4{x0, x1, x2, x3}); lds_st4_a16(BUF + STRIDE * i + 32u, f64x4{x4, x5, x6, x7});
   lds_st4_a16(BUF + STRIDE * i + 64u, f64x4{x8, x9, x10, x11}); lds_st4_a16(BUF + STRIDE * i + 96u, f64x4{x12, x13, x14, x15});
-  const f64x4 v = lds_ld4_a16(BUF + STRIDE * i + 32u * lrow);
-  const double R = 1.0 / lds_ld(BUF + STRIDE * i + 8u * i);      // R(i) = 1/U(i,i): the pivot's own division again, in the row's lanes
+  if constexpr (LAST) {
+    const f64x4 v = lds_ld4_a16(BUF + STRIDE * i + 32u * lrow);
+    const double R = 1.0 / lds_ld(BUF + STRIDE * i + 8u * i);      // R(i) = 1/U(i,i): the pivot's own division again, in the row's lanes
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const uint32_t c = 4u * lrow + (uint32_t)k;
-    if (at[k] != ZERO) lds_st(at[k], c > i ? v[k] * R : v[k]);      // U'(i,c) = U(i,c) * R(i); the diagonal and L(i,c) as they are
+    for (int k = 0; k < 4; k++) {
+      const uint32_t c = 4u * lrow + (uint32_t)k;
+      if (at[k] != ZERO) lds_st(at[k], c > i ? v[k] * R : v[k]);      // U'(i,c) = U(i,c) * R(i); the diagonal and L(i,c) as they are
+    }
+    if (lrow == 0) lds_st(RDIAG + 8u * (H + 48u + i), R);
   }
-  if (lrow == 0) lds_st(RDIAG + 8u * (H + 48u + i), R);
   MISTRA_STAMP(tf2)
 #ifdef MISTRA_DIAG_STAMPS
-  if ((lane & 63) == 0) { atomicAdd(&g_dense_stamps[13], tf1 - tf0); atomicAdd(&g_dense_stamps[14], tf2 - tf1); }
+  if ((lane & 63) == 0) { atomicAdd(&g_dense_stamps[LAST ? 13 : 16], tf1 - tf0); atomicAdd(&g_dense_stamps[LAST ? 14 : 17], tf2 - tf1); }
 #endif
 }
+// the block's last 16 pivots: called by the kernel (a call from dense_lu would make that function save registers of its own)
+template <class MT, int NT>
+__device__ __attribute__((noinline)) void dense_finish(const f64x4 T, const int lane) {
+  typedef LdsLayout<MT, NT> L;
+  // with tile steps in front: the odd diagonal buffer, which the step of block column 1 used last (its storer read it two barriers ago; the storer
+  // of block column 2 reads the even one meanwhile).  Else the panel buffers' even half: panel 11 and its storers use the odd one
+  constexpr uint32_t BUF = 8u * (uint32_t)(L::DENSE_TILES ? L::TILE_D + L::TILE_CELLS : L::PANEL);
+  dense_diag_tile<MT, NT, true>(T, lane, BUF);
+}
 #undef MISTRA_FIN_PIVOT
-#undef MISTRA_FIN_XS
 #undef MISTRA_FIN_F
-#undef MISTRA_FIN_FROM_1
-#undef MISTRA_FIN_FROM_2
-#undef MISTRA_FIN_FROM_3
-#undef MISTRA_FIN_FROM_4
-#undef MISTRA_FIN_FROM_5
-#undef MISTRA_FIN_FROM_6
-#undef MISTRA_FIN_FROM_7
-#undef MISTRA_FIN_FROM_8
-#undef MISTRA_FIN_FROM_9
-#undef MISTRA_FIN_FROM_10
-#undef MISTRA_FIN_FROM_11
-#undef MISTRA_FIN_FROM_12
-#undef MISTRA_FIN_FROM_13
-#undef MISTRA_FIN_FROM_14
-#undef MISTRA_FIN_FROM_15
+
+// ---- a tile step: the sixteen pivots 16K .. 16K+15 of block column K < 3 in one go (dense_lu; MISTRA_DENSE_TILE_FROM), in place of four panels.
+//   1. the owner of tile (K,K) factorises it by itself (dense_diag_tile) and leaves it in the diagonal buffer; meanwhile the owners of the open tiles
+//      of block column K put them into the L buffers as rows, those of block row K theirs into the U buffers as columns; barrier
+//   2. one wave solves the L panel, lane = row, its four 16-lane rows one tile each: for pivot j ascending  x_j *= R(j),  x_c = fma(-x_j, U(j,c), x_c)
+//      for c > j.  A wave on another SIMD solves the U panel, lane = column: for pivot m ascending  b_i = fma(-L(i,m), b_m, b_i)  for i > m.  Both hold
+//      row (lane & 15) of the finished diagonal tile in registers, and the other lanes' entry reaches the multiply-add by row_newbcast — every lane
+//      is live, so no EXEC handling.  Per entry these are the panels' operations in the panels' order (tests/emu/schedule_emu.cpp).  The results go
+//      back over the buffers they came from; barrier
+//   3. every open tile takes four MFMAs, k ascending, operands straight from the buffers: whole tiles, so no zero masks
+//   4. the stores to the Ghimj slots, for the solves, all off the chain's path: the diagonal tile (L below, the unscaled diagonal, U'(j,c) = U(j,c)*R(j)
+//      right of it, and R(j)) by its owner beside step 2 — it has no panel and no open tile in its own step —, the panels L(i,j) and U'(j,c) by the waves
+//      that solved them, beside step 3 — they have no open tile in any step
+// The buffers are single: the next step's entry barrier stands between a step's MFMA reads and the next step's writers.
+struct DenseRow { double x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, x10, x11, x12, x13, x14, x15; };
+__device__ __forceinline__ void dense_row_load(DenseRow& X, const uint32_t at) {
+  const f64x4 q0 = lds_ld4_a16(at), q1 = lds_ld4_a16(at + 32u), q2 = lds_ld4_a16(at + 64u), q3 = lds_ld4_a16(at + 96u);
+  X.x0 = q0[0]; X.x1 = q0[1]; X.x2 = q0[2]; X.x3 = q0[3]; X.x4 = q1[0]; X.x5 = q1[1]; X.x6 = q1[2]; X.x7 = q1[3];
+  X.x8 = q2[0]; X.x9 = q2[1]; X.x10 = q2[2]; X.x11 = q2[3]; X.x12 = q3[0]; X.x13 = q3[1]; X.x14 = q3[2]; X.x15 = q3[3];
+}
+__device__ __forceinline__ void dense_row_store(const DenseRow& X, const uint32_t at) {
+  lds_st4_a16(at, f64x4{X.x0, X.x1, X.x2, X.x3}); lds_st4_a16(at + 32u, f64x4{X.x4, X.x5, X.x6, X.x7});
+  lds_st4_a16(at + 64u, f64x4{X.x8, X.x9, X.x10, X.x11}); lds_st4_a16(at + 96u, f64x4{X.x12, X.x13, X.x14, X.x15});
+}
+#define MISTRA_TS_L(J, C) "v_fmac_f64_dpp %[x" #C "], -%[d" #C "], %[x" #J "] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"
+#define MISTRA_TS_U(J, C) "v_fmac_f64_dpp %[x" #C "], -%[d" #J "], %[x" #J "] row_newbcast:" #C " row_mask:0xf bank_mask:0xf\n\t"
+#define MISTRA_TS_LP(J, J1) "v_mov_b64_dpp %[rj], %[R] row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\tv_mul_f64 %[x" #J "], %[x" #J "], %[rj]\n\t" MISTRA_DPP_FROM_##J1(MISTRA_TS_L, J)
+#define MISTRA_TS_UP(J, J1) MISTRA_DPP_FROM_##J1(MISTRA_TS_U, J)
+#define MISTRA_TS_ALL(P) P(0, 1) P(1, 2) P(2, 3) P(3, 4) P(4, 5) P(5, 6) P(6, 7) P(7, 8) P(8, 9) P(9, 10) P(10, 11) P(11, 12) P(12, 13) P(13, 14) P(14, 15) P(15, 16)
+#define MISTRA_TS_XS [x0] "+v"(X.x0), [x1] "+v"(X.x1), [x2] "+v"(X.x2), [x3] "+v"(X.x3), [x4] "+v"(X.x4), [x5] "+v"(X.x5), [x6] "+v"(X.x6), [x7] "+v"(X.x7), \
+                     [x8] "+v"(X.x8), [x9] "+v"(X.x9), [x10] "+v"(X.x10), [x11] "+v"(X.x11), [x12] "+v"(X.x12), [x13] "+v"(X.x13), [x14] "+v"(X.x14), [x15] "+v"(X.x15)
+#define MISTRA_TS_DS [d0] "v"(D.x0), [d1] "v"(D.x1), [d2] "v"(D.x2), [d3] "v"(D.x3), [d4] "v"(D.x4), [d5] "v"(D.x5), [d6] "v"(D.x6), [d7] "v"(D.x7), \
+                     [d8] "v"(D.x8), [d9] "v"(D.x9), [d10] "v"(D.x10), [d11] "v"(D.x11), [d12] "v"(D.x12), [d13] "v"(D.x13), [d14] "v"(D.x14), [d15] "v"(D.x15)
+// step 2 for the lane's row (LSIDE) or column of the tile buffer at XB, against the finished diagonal tile at DB.  LSIDE: R = R(lane & 15) = 1/U(i,i),
+// the pivot's own division again, and left behind the tile's row for the wave that stores the U rows.  (The s_nop: the wait states of a DPP source that
+// a VALU instruction wrote — the division's result, or a copy the compiler put in front.)
+template <bool LSIDE>
+__device__ __forceinline__ void dense_tile_solve(DenseRow& X, double& R, const uint32_t DB, const uint32_t XB, const int lane) {
+  const uint32_t i = (uint32_t)(lane & 15);
+  DenseRow D;
+  dense_row_load(D, DB + 144u * i);
+  dense_row_load(X, XB + 144u * i);
+  if constexpr (LSIDE) {
+    R = 1.0 / lds_ld(DB + 144u * i + 8u * i);
+    double rj;      // R(j) in every lane (v_mul_f64 has no DPP form)
+    asm volatile("s_nop 1\n\t" MISTRA_TS_ALL(MISTRA_TS_LP) : [rj] "=&v"(rj), MISTRA_TS_XS : [R] "v"(R), MISTRA_TS_DS);
+  } else {
+    asm volatile("s_nop 1\n\t" MISTRA_TS_ALL(MISTRA_TS_UP) : MISTRA_TS_XS : MISTRA_TS_DS);
+  }
+  dense_row_store(X, XB + 144u * i);
+  if constexpr (LSIDE)
+    if (lane < 16) lds_st(DB + 144u * i + 128u, R);
+}
+#undef MISTRA_TS_L
+#undef MISTRA_TS_U
+#undef MISTRA_TS_LP
+#undef MISTRA_TS_UP
+#undef MISTRA_TS_ALL
+#undef MISTRA_TS_XS
+#undef MISTRA_TS_DS
+#undef MISTRA_FIN_XS
+#undef MISTRA_DPP_FROM_1
+#undef MISTRA_DPP_FROM_2
+#undef MISTRA_DPP_FROM_3
+#undef MISTRA_DPP_FROM_4
+#undef MISTRA_DPP_FROM_5
+#undef MISTRA_DPP_FROM_6
+#undef MISTRA_DPP_FROM_7
+#undef MISTRA_DPP_FROM_8
+#undef MISTRA_DPP_FROM_9
+#undef MISTRA_DPP_FROM_10
+#undef MISTRA_DPP_FROM_11
+#undef MISTRA_DPP_FROM_12
+#undef MISTRA_DPP_FROM_13
+#undef MISTRA_DPP_FROM_14
+#undef MISTRA_DPP_FROM_15
+#undef MISTRA_DPP_FROM_16
+
+// step 4, branch-free: an entry the pattern does not have goes to the trash cell.
+// The diagonal tile of block column K, by its owner behind barrier 1, while the panels are solved: from its buffer DB, four columns per lane, with the
+// row's R(i) = 1/U(i,i), the pivot's own division again (what dense_diag_tile does for the last tile)
+template <class MT, int NT>
+__device__ __forceinline__ void dense_tile_store_d(const int K, const uint32_t DB, const int lane) {
+  constexpr uint32_t NNZ = MT::NNZ, NVAR = MT::NVAR, H = NVAR - 64, TRASH = 8u * (NNZ + NVAR + 2u);
+  constexpr uint32_t INFO = 8u * (uint32_t)LdsLayout<MT, NT>::DINFO, RDIAG = 8u * (NNZ + NVAR + 4u);
+  const uint32_t q = (uint32_t)(lane >> 4), i = (uint32_t)(lane & 15), c0 = 16u * (uint32_t)K, cb = c0 + 4u * q;
+  const u32x4 info = lds_ldu4(INFO + 16u * (c0 + i));
+  const f64x4 v = lds_ld4_a16(DB + 144u * i + 32u * q);
+  const double R = 1.0 / lds_ld(DB + 144u * i + 8u * i);
+  const uint64_t absent = (uint64_t)info.y | ((uint64_t)info.z << 32);
+  uint32_t idx = info.x + cb - (uint32_t)__builtin_popcountll(absent & ((1ull << cb) - 1ull));
+  const uint32_t ab = (uint32_t)(absent >> cb);
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t a = (ab >> k) & 1u, c = 4u * q + (uint32_t)k;
+    lds_st(a ? TRASH : 8u * idx, c > i ? v[k] * R : v[k]);      // U'(i,c) = U(i,c) * R(i); the diagonal and L(i,c) as they are
+    idx += 1u - a;
+  }
+  if (q == 0) lds_st(RDIAG + 8u * (H + c0 + i), R);
+}
+// the sixteen entries X of row `row` of the block from column c0 on, each times f
+__device__ __forceinline__ void dense_row_to_slots(const DenseRow& X, const double f, const bool scaled, const uint32_t row, const uint32_t c0, const uint32_t INFO, const uint32_t TRASH) {
+  const u32x4 info = lds_ldu4(INFO + 16u * row);
+  const uint64_t absent = (uint64_t)info.y | ((uint64_t)info.z << 32);
+  uint32_t idx = info.x + c0 - (uint32_t)__builtin_popcountll(absent & ((1ull << c0) - 1ull));
+  const uint32_t ab = (uint32_t)(absent >> c0);
+#define MISTRA_TS_ST(k) { const uint32_t a = (ab >> k) & 1u; lds_st(a ? TRASH : 8u * idx, scaled ? X.x##k * f : X.x##k); idx += 1u - a; }
+  MISTRA_TS_ST(0) MISTRA_TS_ST(1) MISTRA_TS_ST(2) MISTRA_TS_ST(3) MISTRA_TS_ST(4) MISTRA_TS_ST(5) MISTRA_TS_ST(6) MISTRA_TS_ST(7)
+  MISTRA_TS_ST(8) MISTRA_TS_ST(9) MISTRA_TS_ST(10) MISTRA_TS_ST(11) MISTRA_TS_ST(12) MISTRA_TS_ST(13) MISTRA_TS_ST(14) MISTRA_TS_ST(15)
+#undef MISTRA_TS_ST
+}
+// The L panel, behind barrier 2 in the wave that solved it, from its registers: the lane's row of L(16(K+1+q)+i, 16K ..), q = lane >> 4 (lane rows past
+// the block's last tile row hold a copy of the last one and store the same values to the same slots)
+template <class MT, int NT>
+__device__ __forceinline__ void dense_tile_store_l(const DenseRow& X, const int K, const int lane) {
+  constexpr uint32_t NNZ = MT::NNZ, NVAR = MT::NVAR;
+  const int q = (lane >> 4) < 2 - K ? (lane >> 4) : 2 - K;
+  dense_row_to_slots(X, 0.0, false, 16u * (uint32_t)(K + 1 + q) + (uint32_t)(lane & 15), 16u * (uint32_t)K, 8u * (uint32_t)LdsLayout<MT, NT>::DINFO, 8u * (NNZ + NVAR + 2u));
+}
+// ... and the U panel in the wave that solved it: row by row as well, so that a lane finds its sixteen slots by counting on from the first — the
+// wave reads its tiles back from the buffers UB (tile K+1+q at UB + q * TB), where it left them as columns, lane = row; U'(i,c) = U(i,c) * R(i) with
+// R(i) from behind the diagonal tile's row, where the other solving wave left it in front of barrier 2
+template <class MT, int NT>
+__device__ __forceinline__ void dense_tile_store_u(const int K, const uint32_t DB, const uint32_t UB, const uint32_t TB, const int lane) {
+  constexpr uint32_t NNZ = MT::NNZ, NVAR = MT::NVAR;
+  const int q = (lane >> 4) < 2 - K ? (lane >> 4) : 2 - K;
+  const uint32_t i = (uint32_t)(lane & 15), at = UB + TB * (uint32_t)q + 8u * i;
+  DenseRow Y;
+  Y.x0 = lds_ld(at); Y.x1 = lds_ld(at + 144u); Y.x2 = lds_ld(at + 2u * 144u); Y.x3 = lds_ld(at + 3u * 144u);
+  Y.x4 = lds_ld(at + 4u * 144u); Y.x5 = lds_ld(at + 5u * 144u); Y.x6 = lds_ld(at + 6u * 144u); Y.x7 = lds_ld(at + 7u * 144u);
+  Y.x8 = lds_ld(at + 8u * 144u); Y.x9 = lds_ld(at + 9u * 144u); Y.x10 = lds_ld(at + 10u * 144u); Y.x11 = lds_ld(at + 11u * 144u);
+  Y.x12 = lds_ld(at + 12u * 144u); Y.x13 = lds_ld(at + 13u * 144u); Y.x14 = lds_ld(at + 14u * 144u); Y.x15 = lds_ld(at + 15u * 144u);
+  dense_row_to_slots(Y, lds_ld(DB + 144u * i + 128u), true, 16u * (uint32_t)K + i, 16u * (uint32_t)(K + 1 + q), 8u * (uint32_t)LdsLayout<MT, NT>::DINFO, 8u * (NNZ + NVAR + 2u));
+}
 
 // The dense tail block after the LU program and the scaling pass: Schur steps, then the block's own factorisation.  Every
 // Ghimj slot it touches is found by arithmetic on the row table in LDS: a global load issued here, in the middle of a cell's
@@ -1158,21 +1293,116 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 #define MISTRA_DIAG_DENSE_PANELS 12
 #endif
   static_assert(MISTRA_DIAG_DENSE_PANELS <= 12, "the panels end where the in-wave finish begins");
+  // ... of which the block columns from MISTRA_DENSE_TILE_FROM on go as tile steps instead (below), four panels each
+  constexpr int FROM = MISTRA_DENSE_TILE_FROM, NPANEL = MISTRA_DIAG_DENSE_PANELS < 4 * FROM ? MISTRA_DIAG_DENSE_PANELS : 4 * FROM;
 #ifdef MISTRA_DIAG_STAMPS
   unsigned long long acc[5] = {0, 0, 0, 0, 0};
   MISTRA_STAMP(tp0)
 #pragma unroll 1
-  for (int P = 0; P < MISTRA_DIAG_DENSE_PANELS; P++) dense_panel<MT, NT>(T0, T1, P, wave, lane, acc);
+  for (int P = 0; P < NPANEL; P++) dense_panel<MT, NT>(T0, T1, P, wave, lane, acc);
   MISTRA_STAMP(tp1)
   MISTRA_STAMP_ADD(2, acc[0]) MISTRA_STAMP_ADD(3, acc[1]) MISTRA_STAMP_ADD(4, acc[2]) MISTRA_STAMP_ADD(5, acc[3]) MISTRA_STAMP_ADD(8, acc[4]) MISTRA_STAMP_ADD(12, tp1 - tp0)
 #else
 #pragma unroll MISTRA_DENSE_UNROLL
-  for (int P = 0; P < MISTRA_DIAG_DENSE_PANELS; P++) dense_panel<MT, NT>(T0, T1, P, wave, lane);
+  for (int P = 0; P < NPANEL; P++) dense_panel<MT, NT>(T0, T1, P, wave, lane);
 #endif
-  // behind panel 11's second barrier: its entries go to their Ghimj slots from the odd panel buffers, while wave 7 takes its tile
-  // to dense_finish (the caller's call: a call from here would make this function save registers of its own) and works in the even
-  // ones; everybody else goes on to the caller's barrier
-  if (dense_is_storer(wave)) dense_store_panel<MT, NT>(11, wave, lane);
+  if constexpr (FROM == 3) {
+    // behind panel 11's second barrier: its entries go to their Ghimj slots from the odd panel buffers, while wave 7 takes its tile
+    // to dense_finish (the caller's call: a call from here would make this function save registers of its own) and works in the even
+    // ones; everybody else goes on to the caller's barrier
+    if (dense_is_storer(wave)) dense_store_panel<MT, NT>(11, wave, lane);
+  } else {
+    typedef LdsLayout<MT, NT> L;
+    constexpr uint32_t TB = 8u * (uint32_t)L::TILE_CELLS, DBUF = 8u * (uint32_t)L::TILE_D, LBUF = 8u * (uint32_t)L::TILE_L, UBUF = 8u * (uint32_t)L::TILE_U;
+    // (the panels' buffers lie where the tile buffers do: the last panel's entries are stored in front of the first step's entry barrier)
+    if constexpr (FROM > 0)
+      if (dense_is_storer(wave)) dense_store_panel<MT, NT>(4 * FROM - 1, wave, lane);
+    // the solving waves, LS for the L panel and US for the U panel: two of the waves 1, 4 and 6, whose own tiles are never open, on two SIMDs and neither
+    // on the SIMD of the step's diagonal owner (waves 0, 2, 5: SIMDs 0, 2, 1), which stores its tile while they solve
+#ifndef MISTRA_DENSE_TILE_UNROLL      // 3: a copy of the body per step, every choice among the tile registers and the solving waves made at compile time (44 KB
+#define MISTRA_DENSE_TILE_UNROLL 3    // of code).  1: one body of 19 KB, the choices selects on K — measured 0.5 % slower (profiles/r18_ab_dense_tiles.txt)
+#endif
+#pragma unroll MISTRA_DENSE_TILE_UNROLL
+    for (int K = FROM; K < 3; K++) {
+      const int LS = K == 0 ? 1 : 4, US = K == 1 ? 1 : 6;
+      if (K > FROM || FROM > 0) lds_barrier();      // entry: the buffers' readers of the step before (its MFMAs, or the last panel's) are done
+      {
+        const bool odd = K & 1;
+        const f64x4 TK = odd ? T1 : T0;      // the wave's tile in block column K, if it has one
+        if ((int)I > K && (wave & 1) == (K >> 1)) {
+          const uint32_t at = LBUF + TB * (I - 1u) + 8u * lcol;
+#pragma unroll
+          for (int r = 0; r < 4; r++) lds_st(at + 144u * (lrow + 4u * r), TK[r]);
+        }
+        if ((int)I == K) {
+          if ((int)J0 > K) {
+            const uint32_t at = UBUF + TB * (J0 - 1u) + 144u * lcol + 8u * lrow;
+#pragma unroll
+            for (int r = 0; r < 4; r++) lds_st(at + 32u * r, T0[r]);
+          }
+          if ((int)J0 + 1 > K) {
+            const uint32_t at = UBUF + TB * J0 + 144u * lcol + 8u * lrow;
+#pragma unroll
+            for (int r = 0; r < 4; r++) lds_st(at + 32u * r, T1[r]);
+          }
+        }
+#ifdef MISTRA_DIAG_STAMPS
+        if (wave == 4 && lane == 0) atomicAdd(&g_dense_stamps[23], 1ull);
+#endif
+      }
+      {
+        DenseRow X;      // the solving waves' row or column of their panel
+        double R;
+        const uint32_t DB = DBUF + TB * (uint32_t)(K & 1);
+        MISTRA_STAMP(tc0)
+        if (wave == 2 * K + (K >> 1)) dense_diag_tile<MT, NT, false>((K & 1) ? T1 : T0, lane, DB);
+        MISTRA_STAMP(tc1)
+        lds_barrier();
+        MISTRA_STAMP(tc2)
+        const uint32_t xt = TB * (uint32_t)(K + ((lane >> 4) < 2 - K ? (lane >> 4) : 2 - K));      // tile K+1+q, the last one again in the lane rows behind it
+        if (wave == LS) dense_tile_solve<true>(X, R, DB, LBUF + xt, lane);
+        else if (wave == US) dense_tile_solve<false>(X, R, DB, UBUF + xt, lane);
+        else if (wave == 2 * K + (K >> 1)) dense_tile_store_d<MT, NT>(K, DB, lane);      // (the owner has no open tile in its own step)
+        MISTRA_STAMP(tc3)
+        lds_barrier();
+        MISTRA_STAMP(tc4)
+        if ((int)I > K) {
+          const uint32_t la = LBUF + TB * (I - 1u) + 144u * lcol + 8u * lrow;
+          const double a0 = -lds_ld(la), a1 = -lds_ld(la + 32u), a2 = -lds_ld(la + 64u), a3 = -lds_ld(la + 96u);
+          if ((int)J0 > K) {
+            const uint32_t ua = UBUF + TB * (J0 - 1u) + 144u * lcol + 8u * lrow;
+            const double b0 = lds_ld(ua), b1 = lds_ld(ua + 32u), b2 = lds_ld(ua + 64u), b3 = lds_ld(ua + 96u);
+            T0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, T0, 0, 0, 0);
+            T0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, T0, 0, 0, 0);
+            T0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, T0, 0, 0, 0);
+            T0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a3, b3, T0, 0, 0, 0);
+          }
+          if ((int)J0 + 1 > K) {
+            const uint32_t ua = UBUF + TB * J0 + 144u * lcol + 8u * lrow;
+            const double b0 = lds_ld(ua), b1 = lds_ld(ua + 32u), b2 = lds_ld(ua + 64u), b3 = lds_ld(ua + 96u);
+            T1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, T1, 0, 0, 0);
+            T1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, T1, 0, 0, 0);
+            T1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, T1, 0, 0, 0);
+            T1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a3, b3, T1, 0, 0, 0);
+          }
+        }
+        MISTRA_STAMP(tc5)
+#ifdef MISTRA_DIAG_STAMPS      // the diagonal tile's owner: slots 16, 17 (dense_diag_tile) and its wait at barrier 1; wave 4: the solve and barrier 2; wave 7: the MFMAs
+        if (wave == 2 * K + (K >> 1) && lane == 0) atomicAdd(&g_dense_stamps[18], tc2 - tc1);
+        if (wave == LS && lane == 0) { atomicAdd(&g_dense_stamps[19], tc3 - tc2); atomicAdd(&g_dense_stamps[20], tc4 - tc3); }
+        if (wave == 7 && lane == 0) atomicAdd(&g_dense_stamps[21], tc5 - tc4);
+#endif
+        // step 4 beside the MFMAs, in the solving waves, which have no open tile in any step
+        MISTRA_STAMP(tq0)
+        if (wave == LS) dense_tile_store_l<MT, NT>(X, K, lane);
+        else if (wave == US) dense_tile_store_u<MT, NT>(K, DB, UBUF + TB * (uint32_t)K, TB, lane);
+        MISTRA_STAMP(tq1)
+#ifdef MISTRA_DIAG_STAMPS
+        if (wave == LS && lane == 0) atomicAdd(&g_dense_stamps[22], tq1 - tq0);
+#endif
+      }
+    }
+  }
 #ifdef MISTRA_DIAG_STAMPS
   lds_barrier();
   MISTRA_STAMP(tz)
@@ -2466,10 +2696,10 @@ hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_config
 }
 
 #ifdef MISTRA_DIAG_STAMPS
-extern "C" int mistra_diag_dense_stamps(unsigned long long* out16, int reset) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_dense_stamps), 16 * sizeof(unsigned long long)) != hipSuccess) return 1;
+extern "C" int mistra_diag_dense_stamps(unsigned long long* out24, int reset) {
+  if (hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_dense_stamps), 24 * sizeof(unsigned long long)) != hipSuccess) return 1;
   if (reset) {
-    unsigned long long z[16] = {0};
+    unsigned long long z[24] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_dense_stamps), z, sizeof z) != hipSuccess) return 1;
   }
   return 0;

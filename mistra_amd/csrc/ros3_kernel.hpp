@@ -38,6 +38,10 @@ namespace mistra {
 #ifndef MISTRA_TOT_WPS
 #define MISTRA_TOT_WPS 2
 #endif
+#ifndef MISTRA_DENSE_TILE_FROM        // tot's dense tail block: block columns K >= this value are factorised in 16-pivot tile steps, the ones before it in
+#define MISTRA_DENSE_TILE_FROM 0      // panels of four pivots (ros3_kernel.hip: dense_lu; 3 = panels only, the form before the tile steps)
+#endif
+static_assert(MISTRA_DENSE_TILE_FROM >= 0 && MISTRA_DENSE_TILE_FROM <= 3, "block columns 0 .. 2 have a tile step; 3 = none");
 constexpr int kGasNT = MISTRA_GAS_NT, kAerNT = MISTRA_AER_NT, kTotNT = MISTRA_TOT_NT;
 
 struct GasTraits { static constexpr int NVAR = 102, NFIX = 3, NREACT = 331, NNZ = 1110, NB = 568, NCONST = 2, NJNZ = 945, TAIL_REGS = 1, MAX_TEMPS = 10, WAVES_PER_SIMD = MISTRA_GAS_WPS, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = true, SCALE_PASS = false, RCT_LDS = false; };
@@ -82,12 +86,23 @@ struct LdsLayout {
   static constexpr int DINFO = FLAGS + 2;                                               // dense tail block: row table of the block's 64 rows, 16 bytes each (schedule.hpp: DenseTail)
   static constexpr int SCHUR = DINFO + (MT::DENSE_ND > 0 ? 64 * 2 : 0);                 // ... and the Schur steps' operand cells, uint16 x 8 x DENSE_KB x 64
   static constexpr int SCHUR_WORDS = MT::DENSE_ND > 0 ? 8 * MT::DENSE_KB * 64 / 2 : 0;   // in 32-bit words
-  static constexpr int TOTAL = SCHUR + SCHUR_WORDS / 2;
+  // dense_lu's tile steps (MISTRA_DENSE_TILE_FROM < 3): tile buffers of 16 rows, 18 cells (144 bytes) apart — 16 entries and the row's pivot
+  // reciprocal; the stride keeps the rows 16 bytes apart in the banks.  Five in the A/B product array (below): the diagonal tile's two
+  // alternating buffers and the L tiles of block rows 1 .. 3; the U tiles of block columns 1 .. 3 behind the Schur table.  Single buffers: a
+  // workgroup barrier stands between a step's last reader and the next step's writers.
+  static constexpr bool DENSE_TILES = MT::DENSE_ND > 0 && MISTRA_DENSE_TILE_FROM < 3;
+  static constexpr int TILE_STRIDE = 18, TILE_CELLS = 16 * TILE_STRIDE;
+  static constexpr int TILE_U = SCHUR + SCHUR_WORDS / 2;                                // U tile of block column J at TILE_U + (J - 1) * TILE_CELLS
+  static constexpr int TOTAL = TILE_U + (DENSE_TILES ? 3 * TILE_CELLS : 0);
   // dense_lu's panel buffers live in the A/B product array, which nothing reads between Jac_SP and the next Fun:
   // two buffers of [64][4] panel columns + [64][4] panel rows, two 64-entry broadcast rows of the eliminating wave
   static constexpr int PANEL = AB;
   static constexpr int PANEL_CELLS = 2 * 2 * 64 * 4 + 2 * 64 + 4;      // (+ the panel's four pivot reciprocals)
   static_assert(MT::DENSE_ND == 0 || PANEL_CELLS <= A_CELLS + SPARE, "panel buffers must fit the product array");
+  static constexpr int TILE_D = AB;                                                     // diagonal tile of block column K at TILE_D + (K & 1) * TILE_CELLS
+  static constexpr int TILE_L = TILE_D + 2 * TILE_CELLS;                                // L tile of block row I at TILE_L + (I - 1) * TILE_CELLS
+  static_assert(!DENSE_TILES || 5 * TILE_CELLS <= A_CELLS + SPARE, "tile buffers must fit the product array");
+  static_assert((TOTAL + 2 * (NT / 64)) * 8 <= 160 * 1024, "cell state and the trace kernel's cells behind it do not fit the 160 KiB LDS of a gfx950 CU");
   static_assert(TOTAL * 8 <= 160 * 1024, "cell state does not fit the 160 KiB LDS of a gfx950 CU");
   static_assert(NT % 64 == 0 && NT <= 1024 && NT / 64 <= 32, "workgroup size");
 };

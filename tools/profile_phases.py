@@ -4,7 +4,7 @@ such switch).  GPU box: python tools/profile_phases.py [tot]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from _diag import use_diag_lib
-use_diag_lib('libdiag_env.so', MISTRA_CHEM_PROFILE='1')
+use_diag_lib(os.environ.get('DIAG_LIB', 'libdiag_env.so'), MISTRA_CHEM_PROFILE='1')      # DIAG_LIB=libdiag_envN.so: the kernels of MISTRA_DENSE_TILE_FROM=N
 from mistra_amd import chem
 from mistra_amd.workload import make_batch
 chem.init(0)
