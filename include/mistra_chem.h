@@ -740,6 +740,17 @@ int mistra_chem_debug_set_max_steps(int max_steps);
 /* Text of the last error on this thread ("" if none). */
 const char* mistra_chem_last_error(void);
 
+/* The gather-sum programs of a mechanism as the schedule compiler builds them, for tests; needs no device and no mistra_chem_init.
+ * which: 0 the Vdot program in full, 1 the JVS program, 2 Vdot as the kernel runs it (the full program without the terms of the sums
+ * that run as chain passes), 3 those chain passes.  info[14] = workgroup size, waves, outputs per lane, words in recs, chain passes
+ * on (0 | 1), number of passes, rows of the longest wave in full / as run, modelled ticks of the slowest wave in full / as run, LDS
+ * byte address of the 0.0 cell, of the trash cell, of the program's source array, of XS.  wave_base[waves], rows[waves]: of program
+ * `which`; mask[waves]: lanes whose species is chained; chained[4 * passes]: the chained species (0-based) in pass order, one per
+ * 16-lane row, -1 = none; pass_wave[passes].  recs: the records, [(wave_base[w] + row) * 64 + lane][8], four LDS byte addresses and
+ * four float coefficients.  Every array but info may be null.  Returns 0, or -1 with mistra_chem_last_error. */
+int mistra_chem_gsum_program(int mech, int which, int64_t* info, uint32_t* wave_base, int32_t* rows, uint64_t* mask, int32_t* chained,
+                             int32_t* pass_wave, uint32_t* recs, int64_t recs_cap);
+
 /* One line describing the schedule built for a mechanism (rounds, slots); for logs. */
 const char* mistra_chem_describe(int mech);
 

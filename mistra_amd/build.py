@@ -17,6 +17,10 @@ LIB = os.path.join(LIBDIR, "libmistra_chem.so")
 # the same library WITHOUT user slots, linked beside it whenever the library has slots (capi.cpp compiled once more, every other object shared):
 # what tests/test_gpu_user_mech.py holds gas, aer and tot of the library with slots to, bit for bit.  Nothing loads it otherwise.
 LIB_NOSLOTS = os.path.join(LIBDIR, "libmistra_chem_noslots.so")
+# ... and the library without user slots whose tot product kernels and tot Rodas4 unit are compiled with -DMISTRA_GSUM_CHAIN=0 (no chain passes in the
+# gather-sum machine): what tests/test_gpu_gsum_chain.py holds the product to, bit for bit.  Nothing loads it otherwise.
+LIB_NOCHAIN = os.path.join(LIBDIR, "libmistra_chem_nochain.so")
+NOCHAIN_FLAG = "-DMISTRA_GSUM_CHAIN=0"
 
 ARCH = "gfx950"
 # -ffp-contract=off: one rounding per multiply and per add, as in the reference built without FMA contraction
@@ -35,6 +39,7 @@ SOURCES = ["mech_tables.cpp", "schedule.cpp", "capi.cpp", "rates.hip", "pack.hip
 # directory.
 Unit = collections.namedtuple("Unit", "variant mech method")
 PRODUCT = Unit("product", None, None)
+NOCHAIN_UNIT = Unit(3, 2, 5)      # the method kernels, tot, Rodas4
 PRODUCT_SOURCE = "ros3_kernel.hip"
 UNIT_SOURCE = "ros_unit_kernel.hip"
 USER_SOURCE = "ros_user_kernel.hip"
@@ -217,9 +222,39 @@ def build_lib(force=False, verbose=False):
     return LIB
 
 
+def build_nochain_twin(force=False, verbose=False):
+    """Links LIB_NOCHAIN from the objects build_lib has made (call it first): the library without user slots, with the product unit, tot's Rodas4 unit
+    and the C ABI — which hands the kernels' trait to the schedule compiler — compiled once more with NOCHAIN_FLAG (the
+    product unit then holds the instructions it had before there were chain passes)."""
+    cc = hipcc()
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))] + [os.path.abspath(__file__)]
+    kernel_src = os.path.join(CSRC, PRODUCT_SOURCE)
+    twins = {}      # object of build_lib -> (source, flags) of its twin
+    for u in (PRODUCT, NOCHAIN_UNIT):
+        src, name, flags = unit_build(u)
+        twins[name] = (src, flags)
+    twins["capi.o"] = ("capi.cpp", ["-DMISTRA_USER_MECHS=0", "-I" + OBJDIR])
+    objs, cmds = [], []
+    for name in [os.path.splitext(s)[0] + ".o" for s in SOURCES] + [unit_build(u)[1] for u in kernel_units(0)]:
+        if name not in twins:
+            objs.append(os.path.join(OBJDIR, name))
+            continue
+        src, flags = twins[name]
+        obj = os.path.join(OBJDIR, "nochain_" + name)      # (not ros_unit_*.o: the variant and diagnostic builds link that pattern)
+        objs.append(obj)
+        if force or _stale(obj, [os.path.join(CSRC, src), kernel_src] + headers):
+            cmds.append([cc, "--offload-arch=" + ARCH] + COMMON + flags + [NOCHAIN_FLAG, "-c", os.path.join(CSRC, src), "-o", obj])
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(_jobs()) as pool:
+        list(pool.map(lambda cmd: _run(cmd, verbose), cmds))
+    if force or _stale(LIB_NOCHAIN, objs):
+        _run([cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB_NOCHAIN] + objs + ["-ldl"], verbose)
+    return LIB_NOCHAIN
+
+
 # the non-inlined device functions of ros3_kernel.hip in which table loads are in flight in the look-ahead ring (their last template
 # argument is the ring's placement).  In gsum_run_pair a FILLED ring outlives compiler code: the statements between its two programs.
-RING_FUNCTIONS = ("gsum_run", "gsum_run_bar", "gsum_run_pair", "tail_solve", "scale_run")
+RING_FUNCTIONS = ("gsum_run", "gsum_run_bar", "gsum_run_pair", "gsum_pass_run", "tail_solve", "scale_run")
 RING_HIGH_SLOTS = (192, 196, 208, 212, 224, 228, 240, 244)      # ros3_kernel.hip: MISTRA_RING_HI<K>
 
 
@@ -396,3 +431,4 @@ def isa_hazard_report(isa_text, sgpr_vmem_wait=5, dpp_wait=2, seen=None):
 
 if __name__ == "__main__":
     print(build_lib(force="--force" in sys.argv, verbose=True))
+    print(build_nochain_twin(force="--force" in sys.argv, verbose=True))

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -88,6 +89,7 @@ struct MechDesc {
   uint32_t ab_base, jb_base;       // LDS byte addresses of the A/B product array and of Jac_SP's B products (the gather-sum tables hold addresses)
   int max_temps;
   bool user;
+  bool gsum_chain;                 // the kernels' trait GSUM_CHAIN: the long Vdot sums run as chain passes (schedule.hpp: GsumChain)
   bool (*match)(const MechTables&, int, int, bool, const DenseTail&);      // the loaded table against the compiled sizes
   LaunchFn ros3;                                                           // product | phase timing | first-step dump | options (Ros3)
   UnitTable unit;                                                          // every other options kernel (a user slot: none)
@@ -95,12 +97,12 @@ struct MechDesc {
 template <class MT, int NT>
 constexpr MechDesc builtin_mech(const char* name) {
   return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
-                  MT::MAX_TEMPS, false, &traits_match<MT>, &launch_ros3<MT, NT>, unit_table<MT, NT>(std::make_integer_sequence<int, 5>{})};
+                  MT::MAX_TEMPS, false, MT::GSUM_CHAIN, &traits_match<MT>, &launch_ros3<MT, NT>, unit_table<MT, NT>(std::make_integer_sequence<int, 5>{})};
 }
 template <class MT, int NT>
 constexpr MechDesc user_mech(const char* name) {
   return MechDesc{name, MechDims{MT::NVAR, MT::NFIX, MT::NREACT, MT::NNZ}, NT, 8u * (uint32_t)LdsLayout<MT, NT>::AB, 8u * (uint32_t)LdsLayout<MT, NT>::JB,
-                  MT::MAX_TEMPS, true, &traits_match<MT>, &launch_ros3<MT, NT>, UnitTable{}};
+                  MT::MAX_TEMPS, true, MT::GSUM_CHAIN, &traits_match<MT>, &launch_ros3<MT, NT>, UnitTable{}};
 }
 constexpr int kBuiltinMechs = 3, kMaxMechs = 5;
 constexpr int kNumMechs = kBuiltinMechs + MISTRA_USER_MECHS;
@@ -407,7 +409,8 @@ struct KernelBufs {      // the integrator's (ros3_kernel.hip; make_args)
   DevBuf<double> consts;
   DevBuf<uint64_t> fun_fac, jac_fac;
   DevBuf<uint16_t> jvs_pos, zero_pos, diag_pos, schur_cells;
-  GsBufs vdot, jvs;
+  GsBufs vdot, jvs, vdot_pass;      // vdot: the program the kernel runs (KernelSchedule::vdot_chain.lean: the full one where the mechanism has no chain passes)
+  DevBuf<uint64_t> vdot_chain_mask;
   VmBufs lu, solve_head_fwd, solve_head_bwd;
   DevBuf<uint32_t> tail_fwd, tail_bwd, tail_fwd_addr[2], tail_bwd_addr[2], lu_scale, dense_rows;
   int upload(const MechTables& t, const KernelSchedule& K) {
@@ -419,7 +422,9 @@ struct KernelBufs {      // the integrator's (ros3_kernel.hip; make_args)
     HIP_TRY(jvs_pos.upload(K.jvs_pos));
     HIP_TRY(zero_pos.upload(K.zero_pos));
     HIP_TRY(diag_pos.upload(K.diag_pos));
-    HIP_TRY(vdot.upload(K.vdot));
+    HIP_TRY(vdot.upload(K.vdot_chain.lean));
+    HIP_TRY(vdot_pass.upload(K.vdot_chain.pass));
+    HIP_TRY(vdot_chain_mask.upload(K.vdot_chain.mask));
     HIP_TRY(jvs.upload(K.jvs));
     HIP_TRY(lu.upload(K.lu));
     HIP_TRY(solve_head_fwd.upload(K.solve_head_fwd));
@@ -437,7 +442,7 @@ struct KernelBufs {      // the integrator's (ros3_kernel.hip; make_args)
   }
   void release() {
     consts.release(); fun_fac.release(); jac_fac.release(); jvs_pos.release(); zero_pos.release(); diag_pos.release(); schur_cells.release();
-    vdot.release(); jvs.release(); lu.release(); solve_head_fwd.release(); solve_head_bwd.release();
+    vdot.release(); vdot_pass.release(); vdot_chain_mask.release(); jvs.release(); lu.release(); solve_head_fwd.release(); solve_head_bwd.release();
     tail_fwd.release(); tail_bwd.release(); lu_scale.release(); dense_rows.release();
     for (int r = 0; r < 2; r++) { tail_fwd_addr[r].release(); tail_bwd_addr[r].release(); }
   }
@@ -947,7 +952,7 @@ int setup_mech(DeviceState& D, int mech) {
   try {
     // (a user slot never runs the dense tail block, whatever its NVAR: its kernels are compiled without it)
     const DenseConfig dc = M.user ? DenseConfig{0, 0} : dense_config(S.tab);
-    K = build_kernel_schedule(S.tab, S.nt, M.ab_base, M.max_temps, dc.nd, dc.kb, M.jb_base);
+    K = build_kernel_schedule(S.tab, S.nt, M.ab_base, M.max_temps, dc.nd, dc.kb, M.jb_base, M.gsum_chain);
   } catch (const std::exception& ex) {
     return fail(std::string("schedule compiler: ") + ex.what());
   }
@@ -1215,7 +1220,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.texit_hexit = th; a.h_last = nullptr; a.hstart = nullptr; a.prof = nullptr; a.dump = nullptr; a.sing_rows = nullptr; a.n_temps = k.n_temps; a.max_steps = S.opt_max_steps ? S.opt_max_steps : g_max_steps; a.tin = tin; a.tout = tout; a.ncell = ncell;
   a.consts = k.consts.p; a.fun_fac = k.fun_fac.p; a.jac_fac = k.jac_fac.p; a.jvs_pos = k.jvs_pos.p;
   a.zero_pos = k.zero_pos.p; a.diag_pos = k.diag_pos.p;
-  a.vdot = k.vdot.dev(); a.jvs = k.jvs.dev(); a.lu = k.lu.dev();
+  a.vdot = k.vdot.dev(); a.vdot_pass = k.vdot_pass.dev(); a.vdot_chain_mask = k.vdot_chain_mask.p; a.jvs = k.jvs.dev(); a.lu = k.lu.dev();
 #ifdef MISTRA_DIAG_ENV      // diagnostic builds only (tools/diag_dense.sh env): never in the product library
   if (const char* cut = std::getenv("MISTRA_DIAG_LU_ROUNDS"))      // timing diagnostic (tools/profile_lu_rounds.py): results are garbage
     a.lu.nrounds = std::max(1, std::min(a.lu.nrounds, std::atoi(cut)));
@@ -1447,21 +1452,41 @@ int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in,
 #endif
   if (profile) {
     if (a.opt) return fail("the profiling kernel keeps INTEGRATE_x's values: clear the options (mistra_chem_set_options) first");
-    HIP_TRY(prof.reserve(nc * kProfSlots));
+    HIP_TRY(prof.reserve(nc * kProfStride));
+    HIP_TRY(hipMemset(prof.p, 0, nc * kProfStride * sizeof(unsigned long long)));      // (a workgroup of fewer than kProfWaves waves leaves the rest unwritten)
     a.prof = prof.p;
   }
   if (int rc = launch(D, mech, a, nullptr, method)) return rc;
   HIP_TRY(hipDeviceSynchronize());
   if (profile) {
-    std::vector<unsigned long long> h(nc * kProfSlots);
-    HIP_TRY(hipMemcpy(h.data(), prof.p, nc * kProfSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double sum[kProfSlots] = {0};
+    std::vector<unsigned long long> h(nc * kProfStride);
+    HIP_TRY(hipMemcpy(h.data(), prof.p, nc * kProfStride * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    double sum[kProfStride] = {0};
     for (size_t c = 0; c < nc; c++)
-      for (int k = 0; k < kProfSlots; k++) sum[k] += (double)h[c * kProfSlots + k];
+      for (int k = 0; k < kProfStride; k++) sum[k] += (double)h[c * kProfStride + k];
     const char* names[kProfSlots] = {"fun", "jac", "prepare", "lu", "solve(rest)", "norm", "other", "total", "solve_head_fwd", "solve_tail", "solve_head_bwd", "lu_scale", "lu_dense", "jac_products", "jac_sums", "fun_products"};
     std::fprintf(stderr, "[mistra_chem profile] %s, %zu cells, mean shader-clock ticks per cell:", kMech[mech].name, nc);
     for (int k = 0; k < kProfSlots; k++) std::fprintf(stderr, " %s=%.0f (%.1f%%)", names[k], sum[k] / nc, 100.0 * sum[k] / sum[7]);
     std::fprintf(stderr, "\n");
+    // the gather-sum machine per wave (kernel_args.hpp: kProfStride): mean ticks per call since wave 0 entered the evaluator.  The sums'
+    // barrier opens when the last wave reaches the call, so `sums` = left - latest reach is the wave's own fill, rows and drain, and
+    // `waits` = latest left - left is what the wave then idles at the next barrier behind the slowest one.
+    const char* evaluator[2] = {"fun", "fun_jac"};
+    for (int e = 0; e < 2; e++) {
+      const double calls = sum[kProfSlots + 4 * kProfWaves + e];
+      if (calls <= 0) continue;
+      double reach[kProfWaves], left[kProfWaves], opens = 0, last = 0;
+      for (int w = 0; w < kProfWaves; w++) {
+        reach[w] = sum[kProfSlots + 4 * w + 2 * e] / calls;
+        left[w] = sum[kProfSlots + 4 * w + 2 * e + 1] / calls;
+        opens = std::max(opens, reach[w]);
+        last = std::max(last, left[w]);
+      }
+      std::fprintf(stderr, "[mistra_chem profile] %s, sums per wave: %.1f calls per cell, ticks per call, barrier opens at %.0f:", evaluator[e], calls / nc, opens);
+      for (int w = 0; w < kProfWaves; w++)
+        if (left[w] > 0) std::fprintf(stderr, " w%d reach=%.0f left=%.0f sums=%.0f waits=%.0f |", w, reach[w], left[w], left[w] - opens, last - left[w]);
+      std::fprintf(stderr, "\n");
+    }
     prof.release();
   }
   HIP_TRY(hipMemcpy(var_out, S.s_var.p, nc * nv * sizeof(double), hipMemcpyDeviceToHost));
@@ -1678,6 +1703,54 @@ void mistra_chem_finalize(void) {
   for (auto& o : g_opts) o = RosOptions{};
   for (int m = 0; m < kMaxMechs; m++) g_policy[m] = g_policy_env[m];      // (what the environment asked for stays)
   release_all();
+}
+
+static std::map<int, std::pair<int, int>>& cache_dims() { static std::map<int, std::pair<int, int>> d; return d; }      // (nnz, nvar) of the mechanisms compiled below
+// The gather-sum programs of a mechanism as the schedule compiler builds them (tests/test_gsum_chain.py restates them on the host).  Needs
+// no device: the mechanism's table is read from the mechanism directory and compiled here, once per mechanism and process.
+int mistra_chem_gsum_program(int mech, int which, int64_t* info, uint32_t* wave_base, int32_t* rows, uint64_t* mask, int32_t* chained,
+                             int32_t* pass_wave, uint32_t* recs, int64_t recs_cap) {
+  if (!known_mech(mech)) return fail("mistra_chem_gsum_program: no such mechanism");
+  if (which < 0 || which > 3 || !info) return fail("mistra_chem_gsum_program: which = 0 Vdot (full) | 1 JVS | 2 Vdot (lean rows) | 3 Vdot (chain passes), info is required");
+  static std::mutex mu;
+  static std::map<int, KernelSchedule> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(mech);
+  if (it == cache.end()) {
+    const MechDesc& M = kMech[mech];
+    MechTables tab;
+    std::string err;
+    if (!tab.load(mech_dir() + "/" + M.name + ".mech", &err)) return fail(err);
+    try {
+      const DenseConfig dc = M.user ? DenseConfig{0, 0} : dense_config(tab);
+      it = cache.emplace(mech, build_kernel_schedule(tab, M.nt, M.ab_base, M.max_temps, dc.nd, dc.kb, M.jb_base, M.gsum_chain)).first;
+    } catch (const std::exception& ex) {
+      return fail(std::string("schedule compiler: ") + ex.what());
+    }
+    cache_dims()[mech] = {tab.nnz, tab.nvar};
+  }
+  const KernelSchedule& K = it->second;
+  const GsumChain& C = K.vdot_chain;
+  const GsumProgram& P = which == 0 ? K.vdot : which == 1 ? K.jvs : which == 2 ? C.lean : C.pass;
+  const VmLayout lay{cache_dims()[mech].first, cache_dims()[mech].second, 0};
+  const int64_t vals[14] = {P.nt, P.nw, P.nq, (int64_t)P.recs.size(), C.on ? 1 : 0, (int64_t)C.pass_wave.size(), C.pole_rows_full, C.pole_rows_lean,
+                            C.pole_cycles_full, C.pole_cycles_lean, 8 * (int64_t)lay.zero(), 8 * (int64_t)lay.trash(),
+                            which == 1 ? (int64_t)K.jb_base_bytes : (int64_t)K.ab_base_bytes, 8 * (int64_t)lay.xs()};
+  std::memcpy(info, vals, sizeof vals);
+  for (int w = 0; w < P.nw; w++) {
+    if (wave_base) wave_base[w] = P.wave_base[(size_t)w];
+    if (rows) rows[w] = P.rows[(size_t)w];
+    if (mask) mask[w] = C.mask[(size_t)w];
+  }
+  for (size_t i = 0; i < C.outputs.size(); i++)
+    if (chained) chained[i] = C.outputs[i];
+  for (size_t i = 0; i < C.pass_wave.size(); i++)
+    if (pass_wave) pass_wave[i] = C.pass_wave[i];
+  if (recs) {
+    if (recs_cap < (int64_t)P.recs.size()) return fail("mistra_chem_gsum_program: recs_cap is below info[3]");
+    std::memcpy(recs, P.recs.data(), P.recs.size() * sizeof(uint32_t));
+  }
+  return 0;
 }
 
 const char* mistra_chem_describe(int mech) {

@@ -5,6 +5,11 @@
 namespace mistra {
 
 constexpr int kProfSlots = 16;   // phase counters of the profiling kernel variant
+// ... and behind them, per cell, the gather-sum machine's per-wave stamps (lap() stamps wave 0 only): for each of the first kProfWaves
+// waves four sums of cycles since wave 0 entered the evaluator — {fun: reached the sums' call, left it; fun_jac: likewise} — then the
+// number of fun and of fun_jac calls.  All waves of a workgroup read one clock (one CU).
+constexpr int kProfWaves = 8;
+constexpr int kProfStride = kProfSlots + 4 * kProfWaves + 2;
 constexpr int kVmSweepUpdPerRec = 3;   // updates per record of the sweep programs (schedule.hpp: VM_SWEEP_UPD_PER_REC; ros3_kernel.hip: vm_run)
 
 struct VmDev {                 // LDS VM program in device memory (see schedule.hpp)
@@ -66,7 +71,7 @@ struct KernelArgs {
                                //   IER it returns and ros_PrepareMatrix_x prints (gas.f:6157, 1456); entries past min(Nsng, 8) are not written
   double* dump;                // [ncell][5*NVAR + 2*LU_NONZERO + 2] or null: first-step dump (kernel VARIANT 2): Fcn0 | Ghimj prepared |
                                //   Ghimj factorised (kernel form) | R | K1 | K2 | K3 | Err, H  of the first attempt of the first step
-  unsigned long long* prof;    // [ncell][kProfSlots] or null: shader-clock cycles per phase (diagnostics, see capi.cpp)
+  unsigned long long* prof;    // [ncell][kProfStride] or null: shader-clock cycles per phase, then per wave of the sums (diagnostics, see capi.cpp)
   double tin, tout;
   int32_t ncell;
   int32_t n_temps;             // partial-sum cells the solve programs use (zeroed per solve)
@@ -142,6 +147,10 @@ struct KernelArgs {
   // leg k reads rconst + k*leg_rconst and fix + k*leg_fix (strides in elements), piecewise constant over the series as Update_RCONST_x in front of
   // every call leaves them.  0 = one block for every leg.  Read by the series kernels only; 0 everywhere else (capi.cpp: make_args).
   int64_t leg_rconst, leg_fix;
+  // chain passes of the Vdot sums (schedule.hpp: GsumChain), read by the kernels of a mechanism whose trait enables them; `vdot` above is
+  // then the lean program.  (At the end of the block: every other argument keeps its offset.)
+  GsDev vdot_pass;
+  const uint64_t* vdot_chain_mask;      // [NW] lanes whose species is chained
 };
 
 }  // namespace mistra

@@ -701,6 +701,23 @@ __device__ __attribute__((noinline)) void gsum_run_bar(const GsDev P, uint32_t r
   static_assert(!LOW, "generated for the high placement of the ring only (gsum_exec_asm.inc)");
   asm volatile(MISTRA_GSUM_ASM_HIGH_BAR : MISTRA_GSUM_OPERANDS : "memory", "scc", MISTRA_GSUM_CLOBBER_HIGH);
 }
+// A wave's chain passes (schedule.hpp: GsumChain; the instruction stream: tools/gen_gsum_asm.py, pass_variant): the long sums four at a
+// time, one per 16-lane row, the running sum taking the products in term order by v_fmac_f64_dpp row_newbcast.  Each pass stores its
+// sums to the cells its table names.  rows > 0, whole ring turns.  BARRIER (0 | 1): as gsum_run_bar.
+template <int NT, int BARRIER, bool LOW>
+__device__ __attribute__((noinline)) void gsum_pass_run(const GsDev P, uint32_t row0, int rows, int lane) {
+  static_assert(!LOW, "generated for the high placement of the ring only (gsum_exec_asm.inc)");
+  int n = __builtin_amdgcn_readfirstlane(rows);
+  const uint64_t b0 = gsum_base(P, row0), b1 = b0 + 4096u;
+  uint32_t voff = (uint32_t)lane * 32u, out_addr = 0;
+  const uint32_t out_stride = 0;
+  double acc = -0.0;
+  const double mzero = -0.0, one = 1.0;
+  double xA0, xA1, xA2, xA3, xB0, xB1, xB2, xB3, cA0, cA1, cA2, cA3, cB0, cB1, cB2, cB3;
+  uint32_t ad, flA, flB;
+  if constexpr (BARRIER) asm volatile(MISTRA_GSUM_ASM_HIGH_PASS_BAR : MISTRA_GSUM_OPERANDS, [one] "v"(one) : "memory", "scc", MISTRA_GSUM_CLOBBER_HIGH);
+  else asm volatile(MISTRA_GSUM_ASM_HIGH_PASS : MISTRA_GSUM_OPERANDS, [one] "v"(one) : "memory", "scc", MISTRA_GSUM_CLOBBER_HIGH);
+}
 #undef MISTRA_GSUM_OPERANDS
 // Two programs back to back (fun_jac: the Vdot sums, then the JVS sums): in its last ring turn the first stream's refills fetch the
 // second one's first four rows where they fetched slack rows, it returns without draining them, and the second stream enters on
@@ -1483,7 +1500,8 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
 
   // ---- where this wave's stream starts in each table program (and how long the gather-sum ones are): the same for the whole
   //      call, kept in scalar registers
-  struct { uint32_t lu_row0, fwd_row0, bwd_row0, vdot_row0, jvs_row0; int vdot_rows, jvs_rows; } hdr;
+  struct { uint32_t lu_row0, fwd_row0, bwd_row0, vdot_row0, jvs_row0, pass_row0, mask_lo, mask_hi; int vdot_rows, jvs_rows, pass_rows; } hdr;
+  constexpr bool kGsumPass = MT::GSUM_CHAIN;      // the long Vdot sums as chain passes (schedule.hpp: GsumChain)
   {
     const auto u = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     hdr.lu_row0 = u(G_(a.lu.wave_base)[wave]);
@@ -1493,6 +1511,14 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     hdr.jvs_row0 = u(G_(a.jvs.wave_base)[wave]);
     hdr.vdot_rows = (int)u(G_(a.vdot.rows)[wave]);
     hdr.jvs_rows = (int)u(G_(a.jvs.rows)[wave]);
+    hdr.pass_row0 = hdr.mask_lo = hdr.mask_hi = 0; hdr.pass_rows = 0;
+    if constexpr (kGsumPass) {      // this wave's chain passes (most waves have none) and which of its lanes' species are chained
+      hdr.pass_row0 = u(G_(a.vdot_pass.wave_base)[wave]);
+      hdr.pass_rows = (int)u(G_(a.vdot_pass.rows)[wave]);
+      const uint64_t mask = G_(a.vdot_chain_mask)[wave];
+      hdr.mask_lo = u((uint32_t)mask);
+      hdr.mask_hi = u((uint32_t)(mask >> 32));
+    }
   }
 
   // ---- per-cell inputs: coalesced cell-major reads, once
@@ -1718,6 +1744,18 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       t_last = now;
     }
   };
+  // ... and per wave around the gather-sum machine (kernel_args.hpp: kProfStride): thread 0 leaves its clock in the spare half of the flags'
+  // cells in front of the evaluator's first barrier, every wave reads it behind that barrier and stamps against it
+  unsigned long long pw[4] = {0, 0, 0, 0}, pw_calls[2] = {0, 0}, pw_ref = 0;
+  auto wave_ref_put = [&]() {
+    if constexpr (profiling) { if (t == 0) *reinterpret_cast<volatile unsigned long long*>(flags + 2) = clock64(); }
+  };
+  auto wave_ref_get = [&](int which) {
+    if constexpr (profiling) { pw_ref = *reinterpret_cast<volatile unsigned long long*>(flags + 2); pw_calls[which]++; }
+  };
+  auto wave_stamp = [&](int slot) {
+    if constexpr (profiling) pw[slot] += clock64() - pw_ref;
+  };
 
   // first-step dump (VARIANT 2): one block of doubles per cell, see DumpLayout in kernel_args.hpp
   bool dumping = DUMP;
@@ -1823,12 +1861,23 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     if constexpr (!RESIDENT) asm volatile("" : "+v"(tt));      // (derived here: kept across the step loop, the stride was one more register stored to scratch per step)
     constexpr uint32_t trash = 8u * (uint32_t)(NNZ + NVAR + 2);
     addr = tt < NVAR ? 8u * (uint32_t)(NNZ + tt) : trash;
+    if constexpr (kGsumPass) {      // a chained species: its wave's pass writes XS[s], the owner's (empty) sum must not land on it
+      static_assert(!kGsumPass || SPT == 1, "chain passes: one species per lane");
+      if (((lane < 32 ? hdr.mask_lo : hdr.mask_hi) >> (lane & 31)) & 1u) addr = trash;
+    }
     if constexpr (SPT == 1) stride = tt < NVAR ? 8u * (uint32_t)NT : 0u;
     else stride = tt + NT < NVAR ? 8u * (uint32_t)NT : trash - addr;
   };
   auto vdot_sums = [&](auto barrier_tag) {      // barrier: in place of the lds_barrier() in front
     uint32_t addr, stride;
     vdot_out(addr, stride);
+    if constexpr (kGsumPass) {
+      if (hdr.pass_rows > 0) {      // (wave-uniform) the passes first, the barrier inside them; then this wave's rows, if it has any
+        gsum_pass_run<NT, decltype(barrier_tag)::value ? 1 : 0, MT::RING_LOW>(a.vdot_pass, hdr.pass_row0, hdr.pass_rows, lane);
+        if (hdr.vdot_rows > 0) gsum_run<NT, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, lane, addr, stride);
+        return;
+      }
+    }
     if constexpr (decltype(barrier_tag)::value) gsum_run_bar<NT, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, lane, addr, stride);
     else gsum_run<NT, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, lane, addr, stride);
   };
@@ -1846,6 +1895,14 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     if constexpr (kGsumChain) {
       uint32_t addr, stride;
       vdot_out(addr, stride);
+      if constexpr (kGsumPass) {
+        if (hdr.pass_rows > 0) {      // (wave-uniform) the passes take the barrier, the pair enters without one
+          gsum_pass_run<NT, kGsumBarrier ? 1 : 0, MT::RING_LOW>(a.vdot_pass, hdr.pass_row0, hdr.pass_rows, lane);
+          gsum_run_pair<NT, 0, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, addr, stride,
+                                             a.jvs, hdr.jvs_row0, hdr.jvs_rows, 8u * (uint32_t)t, 8u * (uint32_t)NT, lane);
+          return;
+        }
+      }
       gsum_run_pair<NT, kGsumBarrier ? 1 : 0, MT::RING_LOW>(a.vdot, hdr.vdot_row0, hdr.vdot_rows, addr, stride,
                                                     a.jvs, hdr.jvs_row0, hdr.jvs_rows, 8u * (uint32_t)t, 8u * (uint32_t)NT, lane);
     }
@@ -1859,11 +1916,16 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     load_ffac();
     if constexpr (RCT_PER_USE) load_rct(true);
     store_x(v);
+    wave_ref_put();
     lds_barrier();
+    wave_ref_get(0);
     a_products();
     if constexpr (!kGsumBarrier) lds_barrier();      // (else: inside the sums' executor, behind its ring fill)
     lap(15);
+    wave_stamp(0);
     vdot_sums(std::bool_constant<kGsumBarrier>{});
+    wave_stamp(1);
+    if constexpr (kGsumPass) lds_barrier();      // a chained species' owner reads a cell another wave wrote
     read_vdot(out);
   };
   auto jac = [&]() {
@@ -1888,17 +1950,22 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     load_ffac();
     if constexpr (RCT_PER_USE) load_rct(true);
     store_x(v);
+    wave_ref_put();
     lds_barrier();   // X is complete; nobody reads the Ghimj area any more (the last solve's sweeps are behind the error norm's barriers)
+    wave_ref_get(1);
     a_products();
     b_products(jfac);
     if constexpr (!kGsumBarrier) lds_barrier();      // (else: inside the sums' executor, behind its ring fill)
     lap(13);
+    wave_stamp(2);
     if constexpr (kGsumChain) {
       vdot_jvs_sums();
     } else {
       vdot_sums(std::bool_constant<kGsumBarrier>{});
       jvs_sums();      // (other cells, another source array: no barrier between)
     }
+    wave_stamp(3);
+    if constexpr (kGsumPass) lds_barrier();      // (as in fun)
     lap(14);
     read_vdot(out);
     read_jvs();
@@ -2655,13 +2722,18 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       if constexpr (profiling) {
         lap(6);
         pc[7] = clock64() - t_begin;
-        for (int k = 0; k < kProfSlots; k++) GM_(a.prof)[(size_t)cell * kProfSlots + k] = pc[k];
+        for (int k = 0; k < kProfSlots; k++) GM_(a.prof)[(size_t)cell * kProfStride + k] = pc[k];
+        for (int k = 0; k < 2; k++) GM_(a.prof)[(size_t)cell * kProfStride + kProfSlots + 4 * kProfWaves + k] = pw_calls[k];
       }
       if (a.texit_hexit) {
         GM_(a.texit_hexit)[(size_t)cell * 2] = T;
         GM_(a.texit_hexit)[(size_t)cell * 2 + 1] = *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT));
       }
       if (a.h_last) GM_(a.h_last)[cell] = Hget();
+    }
+    if constexpr (profiling) {
+      if (lane == 0 && wave < kProfWaves)
+        for (int k = 0; k < 4; k++) GM_(a.prof)[(size_t)cell * kProfStride + kProfSlots + 4 * wave + k] = pw[k];
     }
     if constexpr (SERIES) {
       if (++leg >= a.nleg) break;

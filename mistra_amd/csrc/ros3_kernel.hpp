@@ -42,11 +42,14 @@ namespace mistra {
 #define MISTRA_DENSE_TILE_FROM 0      // panels of four pivots (ros3_kernel.hip: dense_lu; 3 = panels only, the form before the tile steps)
 #endif
 static_assert(MISTRA_DENSE_TILE_FROM >= 0 && MISTRA_DENSE_TILE_FROM <= 3, "block columns 0 .. 2 have a tile step; 3 = none");
+#ifndef MISTRA_GSUM_CHAIN             // 0: A/B builds without the chain passes of tot's long Vdot sums (schedule.hpp: GsumChain; capi.cpp hands the trait to the schedule compiler)
+#define MISTRA_GSUM_CHAIN 1
+#endif
 constexpr int kGasNT = MISTRA_GAS_NT, kAerNT = MISTRA_AER_NT, kTotNT = MISTRA_TOT_NT;
 
-struct GasTraits { static constexpr int NVAR = 102, NFIX = 3, NREACT = 331, NNZ = 1110, NB = 568, NCONST = 2, NJNZ = 945, TAIL_REGS = 1, MAX_TEMPS = 10, WAVES_PER_SIMD = MISTRA_GAS_WPS, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = true, SCALE_PASS = false, RCT_LDS = false; };
-struct AerTraits { static constexpr int NVAR = 257, NFIX = 5, NREACT = 979, NNZ = 6579, NB = 1598, NCONST = 2, NJNZ = 2831, TAIL_REGS = 2, MAX_TEMPS = 192, WAVES_PER_SIMD = MISTRA_AER_WPS, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = false, SCALE_PASS = MISTRA_AER_SCALE_PASS, RCT_LDS = true; };
-struct TotTraits { static constexpr int NVAR = 417, NFIX = 7, NREACT = 1627, NNZ = 13503, NB = 2628, NCONST = 2, NJNZ = 4709, TAIL_REGS = 2, MAX_TEMPS = 768, WAVES_PER_SIMD = MISTRA_TOT_WPS, DENSE_ND = MISTRA_TOT_DENSE ? 64 : 0, DENSE_KB = MISTRA_TOT_DENSE ? 14 : 0; static constexpr bool RING_LOW = false, SCALE_PASS = true, RCT_LDS = false; };
+struct GasTraits { static constexpr int NVAR = 102, NFIX = 3, NREACT = 331, NNZ = 1110, NB = 568, NCONST = 2, NJNZ = 945, TAIL_REGS = 1, MAX_TEMPS = 10, WAVES_PER_SIMD = MISTRA_GAS_WPS, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = true, SCALE_PASS = false, RCT_LDS = false, GSUM_CHAIN = false; };
+struct AerTraits { static constexpr int NVAR = 257, NFIX = 5, NREACT = 979, NNZ = 6579, NB = 1598, NCONST = 2, NJNZ = 2831, TAIL_REGS = 2, MAX_TEMPS = 192, WAVES_PER_SIMD = MISTRA_AER_WPS, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = false, SCALE_PASS = MISTRA_AER_SCALE_PASS, RCT_LDS = true, GSUM_CHAIN = false; };
+struct TotTraits { static constexpr int NVAR = 417, NFIX = 7, NREACT = 1627, NNZ = 13503, NB = 2628, NCONST = 2, NJNZ = 4709, TAIL_REGS = 2, MAX_TEMPS = 768, WAVES_PER_SIMD = MISTRA_TOT_WPS, DENSE_ND = MISTRA_TOT_DENSE ? 64 : 0, DENSE_KB = MISTRA_TOT_DENSE ? 14 : 0; static constexpr bool RING_LOW = false, SCALE_PASS = true, RCT_LDS = false, GSUM_CHAIN = MISTRA_GSUM_CHAIN != 0; };
 // RING_LOW: placement of the table look-ahead ring (ros3_kernel.hip): v64.. in the kernel that runs more than two waves per SIMD
 // (gas; its tail chain is one register), v192.. in the 256-register ones.
 // Kernels with more waves per SIMD than this fetch their static per-thread words where they are used (ros3_kernel.hip)

@@ -901,7 +901,7 @@ DenseTail build_dense_tail(const MechTables& m, const VmLayout& lay, int nd, int
 // ---------------------------------------------------------------------------------------------------------------
 GsumProgram build_gsum_program(const std::vector<std::vector<std::pair<int, double>>>& outputs,
                                const std::vector<int>& slot_of_output, int nq, int nt, uint32_t src_base_bytes,
-                               uint32_t zero_cell_bytes) {
+                               uint32_t zero_cell_bytes, bool skip_idle_waves) {
   GsumProgram P;
   P.nt = nt;
   P.nw = nt / 64;
@@ -928,7 +928,10 @@ GsumProgram build_gsum_program(const std::vector<std::vector<std::pair<int, doub
   for (int w = 0; w < P.nw; w++) {
     P.wave_base[(size_t)w] = (uint32_t)(P.recs.size() / 512);
     size_t wave_rows = 0;
-    for (int q = 0; q < nq; q++) {
+    bool idle = skip_idle_waves;      // a wave none of whose lanes has an output: no rows at all (the kernel then skips the call)
+    for (int s = w * 64; s < w * 64 + 64 && idle; s++)
+      for (int q = 0; q < nq; q++) idle = idle && output_of_slot[(size_t)q * nt + s] < 0;
+    for (int q = 0; q < (idle ? 0 : nq); q++) {
       size_t n = 0;
       for (int l = 0; l < 64; l++) {
         int o = output_of_slot[(size_t)q * nt + w * 64 + l];
@@ -969,6 +972,163 @@ GsumProgram build_gsum_program(const std::vector<std::vector<std::pair<int, doub
   return P;
 }
 
+// Chain passes (schedule.hpp: GsumChain).  Which outputs: the candidates are taken longest first, a whole prefix of that order at a
+// time; for every prefix length the lean rows per wave and the passes (four outputs each, in that order) are costed with the model of
+// schedule.hpp, every pass dealt — longest first — to the wave that is cheapest with it, and the prefix with the lowest modelled pole wins
+// (ties: the shorter one).  A wave that runs both passes and rows starts two streams.
+GsumChain build_gsum_chain(const std::vector<std::vector<std::pair<int, double>>>& outputs, const std::vector<int>& slot_of_output, int nq, int nt,
+                           uint32_t src_base_bytes, uint32_t zero_cell_bytes, uint32_t trash_bytes, const std::vector<uint32_t>& out_bytes,
+                           const std::vector<uint16_t>& extra_rows, bool enable) {
+  GsumChain C;
+  const int nw = nt / 64;
+  C.mask.assign((size_t)nw, 0);
+  const std::vector<char> none(outputs.size(), 0);
+  auto turn = [](size_t rows) { return (rows + GS_ROW_ALIGN - 1) / GS_ROW_ALIGN * GS_ROW_ALIGN; };
+  auto extra = [&](int w) { return (size_t)w < extra_rows.size() ? (int64_t)extra_rows[(size_t)w] : 0; };
+  // rows per wave of the program without the outputs marked in `out`
+  auto wave_rows = [&](const std::vector<char>& out) {
+    std::vector<size_t> rows((size_t)nw, 0);
+    for (int w = 0; w < nw; w++) {
+      for (int q = 0; q < nq; q++) {
+        size_t n = 0;
+        for (size_t o = 0; o < outputs.size(); o++) {
+          const int s = slot_of_output[o];
+          if (s / nt == q && (s % nt) / 64 == w && !out[o]) n = std::max(n, outputs[o].size());
+        }
+        rows[(size_t)w] += std::max<size_t>(1, (n + 3) / 4);
+      }
+      bool idle = &out != &none;      // (the lean program gives a wave without outputs no rows)
+      for (size_t o = 0; o < outputs.size() && idle; o++) idle = (slot_of_output[o] % nt) / 64 != w;
+      rows[(size_t)w] = idle ? 0 : turn(rows[(size_t)w]);
+    }
+    return rows;
+  };
+  auto pass_groups = [&](const std::vector<int>& cand, size_t p, size_t k) {      // groups of pass p of the first k candidates
+    size_t n = 0;
+    for (size_t i = 4 * p; i < std::min(k, 4 * p + 4); i++) n = std::max(n, outputs[(size_t)cand[i]].size());
+    return (int)std::max<size_t>(1, (n + 15) / 16);
+  };
+  // modelled ticks per wave for rows, with the passes dealt; -> pole, and the deal in pass_wave
+  auto model = [&](const std::vector<size_t>& rows, const std::vector<int>& groups, std::vector<int>* pass_wave) {
+    std::vector<int64_t> t((size_t)nw);
+    std::vector<char> has((size_t)nw, 0);
+    for (int w = 0; w < nw; w++) t[(size_t)w] = GS_COST_START + GS_COST_ROW * ((int64_t)rows[(size_t)w] + extra(w));
+    if (pass_wave) pass_wave->assign(groups.size(), 0);
+    for (size_t p = 0; p < groups.size(); p++) {       // (candidates are sorted longest first, so are the passes)
+      const int64_t cost = GS_COST_PASS + (int64_t)GS_COST_GROUP * groups[p];
+      int best = 0;
+      int64_t best_t = -1;
+      for (int w = 0; w < nw; w++) {
+        const int64_t with = t[(size_t)w] + cost + (has[(size_t)w] ? 0 : GS_COST_START / 2);      // the first pass of a wave: a second stream's start
+        if (best_t < 0 || with < best_t) { best = w; best_t = with; }
+      }
+      t[(size_t)best] = best_t;
+      has[(size_t)best] = 1;
+      if (pass_wave) (*pass_wave)[p] = best;
+    }
+    // ... the pole of the call with the rows behind it (dealt for), plus the pole of the call without them under the same deal
+    int64_t pole = 0, pole_alone = 0;
+    for (int w = 0; w < nw; w++) {
+      pole = std::max(pole, t[(size_t)w]);
+      pole_alone = std::max(pole_alone, t[(size_t)w] - GS_COST_ROW * extra(w));
+    }
+    return extra_rows.empty() ? pole : pole + pole_alone;
+  };
+  const std::vector<size_t> rows_full = wave_rows(none);
+  C.pole_rows_full = (int)*std::max_element(rows_full.begin(), rows_full.end());
+  C.pole_cycles_full = model(rows_full, {}, nullptr);
+  C.pole_rows_lean = C.pole_rows_full;
+  C.pole_cycles_lean = C.pole_cycles_full;
+  size_t best_k = 0;
+  std::vector<int> cand;
+  if (enable) {
+    if (nq != 1) throw std::logic_error("chain passes: one output per lane only (the owner's flush is masked per lane)");
+    for (size_t o = 0; o < outputs.size(); o++)
+      if (outputs[o].size() > 16 && outputs[o].size() <= (size_t)GS_PASS_MAX_TERMS) cand.push_back((int)o);
+    std::stable_sort(cand.begin(), cand.end(), [&](int a, int b) { return outputs[(size_t)a].size() > outputs[(size_t)b].size(); });
+    if (cand.size() > 64) cand.resize(64);
+    std::vector<char> out(outputs.size(), 0);
+    for (size_t k = 1; k <= cand.size(); k++) {
+      out[(size_t)cand[k - 1]] = 1;
+      std::vector<int> groups;
+      for (size_t p = 0; p < (k + 3) / 4; p++) groups.push_back(pass_groups(cand, p, k));
+      const std::vector<size_t> rows = wave_rows(out);
+      const int64_t pole = model(rows, groups, nullptr);
+      if (pole < C.pole_cycles_lean) {
+        C.pole_cycles_lean = pole;
+        C.pole_rows_lean = (int)*std::max_element(rows.begin(), rows.end());
+        best_k = k;
+      }
+    }
+  }
+  C.on = best_k > 0;
+  cand.resize(best_k);
+  // the lean program: the chained outputs keep their slots with no terms
+  std::vector<std::vector<std::pair<int, double>>> lean_outs = outputs;
+  std::vector<char> out(outputs.size(), 0);
+  for (int o : cand) {
+    lean_outs[(size_t)o].clear();
+    out[(size_t)o] = 1;
+    const int s = slot_of_output[(size_t)o];
+    C.mask[(size_t)((s % nt) / 64)] |= 1ull << (s % 64);
+  }
+  C.lean = build_gsum_program(lean_outs, slot_of_output, nq, nt, src_base_bytes, zero_cell_bytes, C.on);
+  // the passes
+  GsumProgram& P = C.pass;
+  P.nt = nt;
+  P.nw = nw;
+  P.nq = 0;
+  P.wave_base.assign((size_t)nw, 0);
+  P.rows.assign((size_t)nw, 0);
+  std::vector<int> groups;
+  for (size_t p = 0; p < (best_k + 3) / 4; p++) groups.push_back(pass_groups(cand, p, best_k));
+  model(wave_rows(out), groups, &C.pass_wave);
+  C.outputs.assign(4 * groups.size(), -1);
+  for (size_t i = 0; i < cand.size(); i++) C.outputs[i] = cand[i];
+  const float neg_zero = -0.0f;
+  uint32_t neg_zero_bits;
+  std::memcpy(&neg_zero_bits, &neg_zero, 4);
+  auto put_pass = [&](int p) {      // p < 0: an empty pass
+    for (int r = 0; r < GS_PASS_ROWS; r++)
+      for (int l = 0; l < 64; l++) {
+        const int o = p < 0 ? -1 : C.outputs[(size_t)4 * p + (l >> 4)];
+        uint32_t addr[4], cbits[4];
+        for (int k = 0; k < 4; k++) {
+          const int g = 4 * r + k;
+          const size_t s = (size_t)16 * g + (size_t)(l & 15);
+          addr[k] = zero_cell_bytes;
+          cbits[k] = neg_zero_bits;
+          if (g == GS_PASS_SLOTS) {
+            addr[k] = o >= 0 ? out_bytes[(size_t)o] : trash_bytes;
+            cbits[k] = 0;
+          } else if (o >= 0 && s < outputs[(size_t)o].size()) {
+            const auto& term = outputs[(size_t)o][s];
+            const float cf = (float)term.second;
+            if ((double)cf != term.second) throw std::logic_error("stoichiometric coefficient is not a float32 value");
+            if (term.first < 0 || term.first > 0xFFFF) throw std::logic_error("gsum source index out of range");
+            addr[k] = src_base_bytes + 8u * (uint32_t)term.first;
+            std::memcpy(&cbits[k], &cf, 4);
+            P.n_terms++;
+          }
+        }
+        if (r == 0) addr[0] |= (uint32_t)(p < 0 ? 0 : groups[(size_t)p]);
+        for (int k = 0; k < 4; k++) P.recs.push_back(addr[k]);
+        for (int k = 0; k < 4; k++) P.recs.push_back(cbits[k]);
+      }
+  };
+  for (int w = 0; w < nw; w++) {
+    P.wave_base[(size_t)w] = (uint32_t)(P.recs.size() / 512);
+    size_t rows = 0;
+    for (size_t p = 0; p < groups.size(); p++)
+      if (C.pass_wave[p] == w) { put_pass((int)p); rows += GS_PASS_ROWS; }
+    while (rows % GS_ROW_ALIGN) { put_pass(-1); rows += GS_PASS_ROWS; }
+    P.rows[(size_t)w] = (uint16_t)rows;
+    P.wave_rows += (int64_t)rows;
+    for (int rr = 0; rr < VM_LOOKAHEAD_ROWS / GS_PASS_ROWS; rr++) put_pass(-1);      // slack, as every table stream has it
+  }
+  return C;
+}
+
 ScaleProgram build_scale_program(const std::vector<std::pair<int, int>>& pairs, const VmLayout& lay, int nt) {
   ScaleProgram P;
   P.nt = nt;
@@ -991,7 +1151,7 @@ ScaleProgram build_scale_program(const std::vector<std::pair<int, int>>& pairs, 
 
 // ---------------------------------------------------------------------------------------------------------------
 KernelSchedule build_kernel_schedule(const MechTables& m, int nt, uint32_t ab_base_bytes, int max_temps, int dense_nd, int dense_kb,
-                                     uint32_t jb_base_bytes) {
+                                     uint32_t jb_base_bytes, bool gsum_chain) {
   if (nt % 64 != 0 || nt <= 0 || nt > 1024) throw std::invalid_argument("nt must be a multiple of 64 in (0,1024]");
   if (VmLayout{m.nnz, m.nvar, max_temps}.size() * 8 > 160 * 1024) throw std::invalid_argument("mechanism too large for the LDS VM");
   if (m.nx() > 0xFFFF || m.nb >= 0xFFFF || m.nreact > 0xFFFF) throw std::invalid_argument("mechanism too large");
@@ -1006,6 +1166,7 @@ KernelSchedule build_kernel_schedule(const MechTables& m, int nt, uint32_t ab_ba
   S.rpt = ceil_div(m.nreact, nt);
   const uint64_t one = (uint64_t)(m.nvar + m.nfix);       // X slot of the constant 1.0
 
+  std::vector<std::vector<std::pair<int, double>>> vdot_outs;      // (kept for the chain passes, which are dealt once the JVS rows are known)
   // ---- Fun_x products
   const uint64_t ab_trash = (uint64_t)std::max(m.nreact, m.nb);     // spare cells behind the B products (and the A products where they share the array), one per lane (LdsLayout::AB_TRASH)
   // where Jac_SP's B products have an array of their own (jb_base_bytes: inside the Ghimj area), the A array holds NREACT products and its
@@ -1030,6 +1191,7 @@ KernelSchedule build_kernel_schedule(const MechTables& m, int nt, uint32_t ab_ba
       for (int p = m.vd_ptr[s]; p < m.vd_ptr[s + 1]; p++) outs[(size_t)s].emplace_back(m.vd_idx[(size_t)p], m.vd_coef[(size_t)p]);
     }
     S.vdot = build_gsum_program(outs, slot, S.spt, nt, ab_base_bytes, zero_cell_bytes);
+    vdot_outs = std::move(outs);
   }
 
   // ---- Jac_SP_x products, under the owning reaction
@@ -1085,6 +1247,12 @@ KernelSchedule build_kernel_schedule(const MechTables& m, int nt, uint32_t ab_ba
   }
   S.diag_pos.assign((size_t)S.spt * nt, POS_NONE);
   for (int s = 0; s < m.nvar; s++) S.diag_pos[(size_t)s] = (uint16_t)m.diag[(size_t)s];
+  {      // Vdot as the kernel runs it: the long sums as chain passes where the mechanism enables them (output s lands in XS[s] either way)
+    std::vector<int> slot((size_t)m.nvar);
+    std::vector<uint32_t> out_bytes((size_t)m.nvar);
+    for (int s = 0; s < m.nvar; s++) { slot[(size_t)s] = s; out_bytes[(size_t)s] = 8u * (uint32_t)lay.xs(s); }
+    S.vdot_chain = build_gsum_chain(vdot_outs, slot, S.spt, nt, ab_base_bytes, zero_cell_bytes, 8u * (uint32_t)lay.trash(), out_bytes, S.jvs.rows, gsum_chain);
+  }
 
   if (dense_nd > 0) {
     if (nt < 512) throw std::invalid_argument("the dense tail block needs eight waves");

@@ -133,6 +133,39 @@ struct GsumProgram {
   int64_t n_terms = 0, wave_rows = 0;
 };
 
+// Chain passes (round 19): the longest sums of a gather-sum program, taken off the wave that walked them alone at four terms per row
+// and evaluated four at a time, one per 16-lane row of a wave with few rows of its own.  Lane l of a 16-lane row holds terms l, 16+l,
+// 32+l, ... of its row's sum (slot g = term 16g+l, at most GS_PASS_SLOTS slots); the running sum lives in every lane of the row and
+// takes the products in term order, one `A = fma(p[lane i], 1.0, A)` per term with the product broadcast over the row (v_fmac_f64_dpp
+// row_newbcast:i) — fma(p, 1.0, A) rounds p + A once, so the sum is bit for bit the one the full program forms (padding slots are the
+// identity -0.0f * M[0.0 cell], as there).  A pass is GS_PASS_ROWS rows of the 32-byte record format: slots 0-3 in its first row, 4-6 in
+// its second; the first address word of the first row carries the group count G = ceil(longest sum / 16) in its three low bits (0: an
+// empty pass that fills up a ring turn); the last address word of the second row is the output's LDS byte address, in every lane of
+// the 16-lane row (the trash cell where the row has no sum).  A wave's passes are a stream of their own (GsumChain::pass), run by
+// ros3_kernel.hip: gsum_pass_run in front of the wave's rows of the lean program (GsumChain::lean: the full program without the chained
+// outputs' terms — their owner lanes still flush an empty sum, which the kernel sends to the trash cell: GsumChain::mask).
+constexpr int GS_PASS_ROWS = 2, GS_PASS_SLOTS = 7, GS_PASS_MAX_TERMS = 16 * GS_PASS_SLOTS;
+// The deal's cost model, in shader-clock ticks of one wave: a stream's start-up and drain, a table row, a pass's gathers and products, a
+// group of 16 chain steps.  Start-up and row are fitted to the per-wave stamps of the parent (profiles/r19_gsum_waves_parent.txt: tot,
+// 4 / 8 / 12 / 24 / 28 rows leave the call 1 955 / 2 683 / 3 910 / 5 740 / 6 200 ticks behind the barrier); pass and group are the
+// instruction counts at the 10 ticks of a dependent DPP step (tools/ubench/dpp.hip), checked against profiles/r19_gsum_waves.txt.
+constexpr int GS_COST_START = 1230, GS_COST_ROW = 180, GS_COST_PASS = 200, GS_COST_GROUP = 160;
+
+struct GsumChain {
+  bool on = false;                              // false: no passes, `lean` is the full program record for record
+  GsumProgram lean;                             // what the kernel runs as the sum program
+  GsumProgram pass;                             // rows[w] = GS_PASS_ROWS per pass of wave w, filled up to whole ring turns; nq = 0
+  std::vector<uint64_t> mask;                   // [nw] bit l: the first output of lane l of wave w is chained
+  std::vector<int> outputs;                     // [4 * passes] the chained outputs in pass order, one per 16-lane row, -1 = none
+  std::vector<int> pass_wave;                   // [passes] the wave that runs the pass
+  int pole_rows_full = 0, pole_rows_lean = 0;   // rows of the longest wave before / after
+  int64_t pole_cycles_full = 0, pole_cycles_lean = 0;      // modelled ticks of the slowest wave, rows and passes
+};
+// extra_rows[w]: rows of a program the same call runs behind this one (fun_jac: the JVS rows), which the model counts in
+GsumChain build_gsum_chain(const std::vector<std::vector<std::pair<int, double>>>& outputs, const std::vector<int>& slot_of_output, int nq, int nt,
+                           uint32_t src_base_bytes, uint32_t zero_cell_bytes, uint32_t trash_bytes, const std::vector<uint32_t>& out_bytes,
+                           const std::vector<uint16_t>& extra_rows, bool enable);
+
 // Triangular solves, tail part.  The last m rows of the LU pattern (the gas-phase block every other species couples
 // to) form a nearly dense triangle whose substitution is an inherently serial chain; it is run by ONE wave with the
 // tail of the solution vector in registers (lane l holds rows h+l, h+64+l), the pivot value passed lane-to-lane in
@@ -225,6 +258,7 @@ struct KernelSchedule {
   int a_trash = 0;                              // first spare cell of the A array: nreact where B has an array of its own, else max(nreact, nb)
   std::vector<uint64_t> fun_fac;                // [rpt*nt]  f1 | f2<<16 | f3<<32 | out<<48   (out = reaction, or a spare cell a_trash + lane for a thread without one)
   GsumProgram vdot;                             // src = A (LDS), output (q,t) = species q*nt+t
+  GsumChain vdot_chain;                         // what the kernel runs for Vdot: lean rows + chain passes where the mechanism enables them (vdot itself stays the full program)
   // Jac_SP_x products, grouped under the reaction that owns the rate constant: up to 3 B's per reaction
   std::vector<uint64_t> jac_fac;                // [(q*3 + b)*nt + t]  f1 | f2<<16 | f3<<32 | out<<48 (the spare cell = none)
   GsumProgram jvs;                              // src = B (LDS), output (q,t) = jac0 register q of thread t
@@ -258,12 +292,13 @@ std::vector<VmEntry> solve_head_bwd_entries(const MechTables& m, const VmLayout&
 TailSolve build_tail_solve(const MechTables& m, const VmLayout& lay, int regs = 0);      // regs = 0: by mechanism size
 GsumProgram build_gsum_program(const std::vector<std::vector<std::pair<int, double>>>& outputs,
                                const std::vector<int>& slot_of_output, int nq, int nt, uint32_t src_base_bytes,
-                               uint32_t zero_cell_bytes);
+                               uint32_t zero_cell_bytes, bool skip_idle_waves = false);
 // ab_base_bytes: LDS byte address of the A/B product array the gather-sum tables point into (ros3_kernel.hpp: LdsLayout)
 // dense_nd = 64 with dense_kb Schur steps: the mechanism's last 64 rows are factorised as a dense block (DenseTail)
 // jb_base_bytes: ... of Jac_SP's B products (0: they share the A array)
+// gsum_chain: the longest Vdot sums become chain passes where the cost model finds a shorter pole (GsumChain; the kernels' trait GSUM_CHAIN, ros3_kernel.hpp)
 KernelSchedule build_kernel_schedule(const MechTables& m, int nt, uint32_t ab_base_bytes, int max_temps, int dense_nd = 0,
-                                     int dense_kb = 0, uint32_t jb_base_bytes = 0);
+                                     int dense_kb = 0, uint32_t jb_base_bytes = 0, bool gsum_chain = false);
 std::string describe(const KernelSchedule& s);
 
 }  // namespace mistra

@@ -114,7 +114,7 @@ int main(int argc, char** argv) {
     std::fprintf(o, "#pragma once\nnamespace mistra {\n");
     std::fprintf(o,
                  "struct User%dTraits { static constexpr int NVAR = %d, NFIX = %d, NREACT = %d, NNZ = %d, NB = %d, NCONST = %d, NJNZ = %d, TAIL_REGS = %d, "
-                 "MAX_TEMPS = %d, WAVES_PER_SIMD = %s, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = %s, SCALE_PASS = %s, RCT_LDS = %s; };\n",
+                 "MAX_TEMPS = %d, WAVES_PER_SIMD = %s, DENSE_ND = 0, DENSE_KB = 0; static constexpr bool RING_LOW = %s, SCALE_PASS = %s, RCT_LDS = %s, GSUM_CHAIN = false; };\n",
                  slot, t.nvar, t.nfix, t.nreact, t.nnz, t.nb, t.nconst, njnz, K.tail.regs, max_temps, nt == 64 ? "MISTRA_GAS_WPS" : "MISTRA_AER_WPS",
                  nt == 64 ? "true" : "false", scale_pass ? "true" : "false", rct_lds ? "true" : "false");
     std::fprintf(o, "constexpr int kUser%dNT = %d;\n", slot, nt);

@@ -137,6 +137,81 @@ def variant(name, fill=True, barrier=False, chain=False):
     return L, clob
 
 
+def pass_variant(name, barrier):
+    """The chain passes of a wave (schedule.hpp: GsumChain; ros3_kernel.hip: gsum_pass_run): a stream of whole ring turns, two passes of
+    two rows each per turn, no look-ahead beyond the turn (a wave has one or two passes).  Per pass: seven gathers and products as a
+    regular row forms them — slots 0-3 from the first row into set A, 4-6 from the second into set B, the products left in the
+    coefficient registers —, then the running sum takes them in term order, group by group: sixteen `acc = fma(p[lane i], 1.0, acc)`
+    with the product broadcast over its 16-lane row.  The DPP operand is a product written at least two instructions earlier, the
+    dependency runs through the destination only.  The group count G sits in the three low bits of the pass's first address word
+    (tested between the groups, wave-uniform; 0 = an empty pass), the output's address in the last address word of its second row.
+    n >= 4 on entry."""
+    slot = SLOTS[name]
+    L = []
+    emit = L.append
+
+    def load_turn():
+        for r in range(4):
+            base, off = ("%[b0]", r * 2048) if r < 2 else ("%[b1]", (r - 2) * 2048)
+            a, c = slot[2 * r], slot[2 * r + 1]
+            emit("global_load_dwordx4 v[%d:%d], %%[voff], %s offset:%d" % (a, a + 3, base, off))
+            emit("global_load_dwordx4 v[%d:%d], %%[voff], %s offset:%d" % (c, c + 3, base, off + 16))
+
+    def one_pass(ra, rb, tag):
+        a, c = slot[2 * ra], slot[2 * ra + 1]
+        b, d = slot[2 * rb], slot[2 * rb + 1]
+        prod = ["%%[cA%d]" % k for k in range(4)] + ["%%[cB%d]" % k for k in range(3)]
+        emit("v_readfirstlane_b32 %%[flA], v%d" % a)
+        emit("v_and_b32 %%[ad], -8, v%d" % a)
+        emit("ds_read_b64 %[xA0], %[ad]")
+        for k in (1, 2, 3):
+            emit("ds_read_b64 %%[xA%d], v%d" % (k, a + k))
+        for k in range(3):
+            emit("ds_read_b64 %%[xB%d], v%d" % (k, b + k))
+        for k in range(4):
+            emit("v_cvt_f64_f32 %%[cA%d], v%d" % (k, c + k))
+        for k in range(3):
+            emit("v_cvt_f64_f32 %%[cB%d], v%d" % (k, d + k))
+        emit("v_mov_b64 %[acc], %[mzero]")
+        emit("s_and_b32 %[flA], %[flA], 7")
+        emit("s_cmp_eq_u32 %[flA], 0")
+        emit("s_cbranch_scc1 Lgp_skip%s_%%=" % tag)
+        emit("s_waitcnt lgkmcnt(0)")
+        for k in range(4):
+            emit("v_mul_f64 %%[cA%d], %%[cA%d], %%[xA%d]" % (k, k, k))
+        for k in range(3):
+            emit("v_mul_f64 %%[cB%d], %%[cB%d], %%[xB%d]" % (k, k, k))
+        for g in range(7):
+            if g:
+                emit("s_cmp_lt_u32 %%[flA], %d" % (g + 1))
+                emit("s_cbranch_scc1 Lgp_st%s_%%=" % tag)
+            for i in range(16):
+                emit("v_fmac_f64_dpp %%[acc], %s, %%[one] row_newbcast:%d row_mask:0xf bank_mask:0xf" % (prod[g], i))
+        emit("Lgp_st%s_%%=:" % tag)
+        emit("ds_write_b64 v%d, %%[acc]" % (b + 3))
+        emit("Lgp_skip%s_%%=:" % tag)
+
+    emit("s_waitcnt vmcnt(0)")
+    emit("s_nop 4")
+    load_turn()
+    if barrier:
+        emit("s_waitcnt lgkmcnt(0)")
+        emit("s_barrier")
+    emit("Lgp_loop_%=:")
+    emit("v_add_u32 %[voff], 0x2000, %[voff]")
+    emit("s_waitcnt vmcnt(0)")
+    one_pass(0, 1, "0")
+    one_pass(2, 3, "1")
+    emit("s_waitcnt lgkmcnt(0)")            # the turn's gathers and stores have read their ring registers
+    emit("s_sub_i32 %[n], %[n], 4")
+    emit("s_cmp_lt_i32 %[n], 1")
+    emit("s_cbranch_scc1 Lgp_exit_%=")
+    load_turn()
+    emit("s_branch Lgp_loop_%=")
+    emit("Lgp_exit_%=:")
+    return L
+
+
 # the streams ros3_kernel.hip runs: suffix -> (fill, barrier, chain)
 FORMS = [("", (True, False, False)),                 # gsum_run: fill, run, drain
          ("_BAR", (True, True, False)),              # gsum_run_bar: fill, workgroup barrier, run, drain
@@ -152,6 +227,14 @@ def render():
             if name == "LOW" and suffix:      # the low placement (gas) runs the plain form only
                 continue
             lines, clob = variant(name, *form)
+            out.append("#define MISTRA_GSUM_ASM_%s%s \\" % (name, suffix))
+            for i, ln in enumerate(lines):
+                sep = "\\n" if ln.endswith(":") else "\\n\\t"
+                last = i == len(lines) - 1
+                out.append('  "%s%s"%s' % (ln, "" if last else sep, "" if last else " \\"))
+            out.append("")
+        for suffix, barrier in (("_PASS", False), ("_PASS_BAR", True)) if name == "HIGH" else ():
+            lines = pass_variant(name, barrier)
             out.append("#define MISTRA_GSUM_ASM_%s%s \\" % (name, suffix))
             for i, ln in enumerate(lines):
                 sep = "\\n" if ln.endswith(":") else "\\n\\t"
