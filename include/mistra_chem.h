@@ -443,6 +443,52 @@ int mistra_chem_ops_ex(int mech, int ncell, const double* var, const double* fix
 int mistra_chem_ops_device(int mech, int ncell, const double* d_var, const double* d_fix, const double* d_rconst, double* d_vdot, double* d_jvs, int nshift,
                            const double* d_shift, int fun_rhs, int nrhs, const double* d_rhs, double* d_x, int32_t* d_ising, void* hip_stream);
 
+/* THE REPLAY: Ros3 along a step sequence the caller prescribes.  Step n of a cell is made with H = hsteps[row][n] and accepted whatever
+ * its error estimate; the estimate (Rosenbrock_x's Err of that step under the call's tolerances) goes to err_log[cell][n].  The sequence is what the
+ * step-control trace hands out: the records of a traced call whose code has bit 0 set, H as attempted.  A replay of those steps under the traced call's
+ * arguments repeats that call's accepted steps operand for operand: var_out and Texit equal the traced call's bit for bit and err_log its accepted records'
+ * Err, provided no accepted step of the trace met a zero pivot.  Perturbed copies of a cell replayed along ONE sequence give a smooth map from the
+ * perturbation to the end state (internal numerical differentiation): central differences of them are good to round-off / eps, where differences of two
+ * adaptive calls carry the tolerance.
+ *   cap, hrows, hsteps [hrows][cap], nsteps [hrows]   the table: hrows = 1 (one sequence shared by all cells) or ncell (row and count per cell);
+ *          0 <= nsteps[r] <= cap.  Entries of hsteps behind a row's count are not read.
+ *   err_log [ncell][cap], may be NULL (not wanted)     entries behind a cell's count are not touched
+ * Of the options the call reads ipar[0] (Autonomous), ipar[1] and atol / rtol, and ipar[3], which must be 2 (Ros3); rpar is decoded as Rosenbrock_x decodes it
+ * (codes -1 .. -4 are whole-call results decided on the host, -5 as in the siblings) and then ignored: there are no Hmin, Hmax, Hstart and factors, no
+ * clipping to tend and no Max_no_steps.  tstart is where T starts; tend gives the direction (tend >= tstart: forward) and nothing else.
+ * Per cell: ierr = 1, or -7 where a step fails Rosenbrock_x's test (T + 0.1*H == T or H <= Roundoff; the cell leaves with the steps made so far), or -8 where
+ * a step's matrix has a zero pivot (no halving: Nsng = 1, the row in mistra_chem_singular_rows after _ex, the cell leaves at the last accepted state).
+ * stats: Nstp = Nacc = Njac = Ndec = the steps made, Nsol three times that, Nrej = 0 (a -8 exit: one more Njac and Ndec, Nsng = 1).  t_h [ncell][3] / d_texit_hexit [ncell][2]: the T reached, the last H
+ * made (0: none), and (t_h) the same H again.  nsteps = 0 is legal: var_out = var_in, ierr = 1, zeros.
+ * Refused with a text before a device is touched: cap < 0; hrows neither 1 nor ncell; NULL hsteps with cap > 0; NULL nsteps; a count outside 0 .. cap where
+ * the counts are host arrays; a method other than Ros3; a user slot.
+ * _ex: host arrays; the batch is split over the device slots as mistra_chem_rosenbrock_trace_ex splits it, each block with its rows; fails while a column
+ * step of the mechanism is open.  _device: the cell data are device arrays and the call is asynchronous on the stream; hsteps / nsteps are HOST arrays where
+ * hrows = 1 (read before the call returns; the nsteps[0] steps travel behind the call's options, MISTRA_ROSENBROCK_CALLS_IN_FLIGHT blocks: nsteps[0] <=
+ * MISTRA_REPLAY_MAX_SHARED, refused with a text otherwise)
+ * and DEVICE arrays where hrows = ncell > 1 (read in stream order; host memory the cells' device cannot reach is refused with a text; the kernel clamps a count
+ * above cap to cap and takes a negative one as 0).
+ * _cells: tolerances per cell as in mistra_chem_rosenbrock_cells_ex; a row refused with -5 leaves as there and its err_log row is not written.
+ * Nothing process-wide is read: the options in force, the integrator policy and step reuse are not involved. */
+#define MISTRA_REPLAY_MAX_SHARED MISTRA_SERIES_MAX_LEGS
+int mistra_chem_rosenbrock_replay_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                     const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int cap, int hrows,
+                                     const double* hsteps, const int32_t* nsteps, double* var_out, int32_t* ierr, int32_t* stats, double* t_h,
+                                     double* err_log);
+int mistra_chem_rosenbrock_replay_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                           const double* atol, const double* rtol, int ntol,                                         /* rows per cell */
+                                           const double* rpar, const int32_t* ipar, int cap, int hrows, const double* hsteps, const int32_t* nsteps,
+                                           double* var_out, int32_t* ierr, int32_t* stats, double* t_h, double* err_log);
+int mistra_chem_rosenbrock_replay_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                         double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,      /* host arrays */
+                                         int cap, int hrows, const double* hsteps, const int32_t* nsteps,      /* host (hrows = 1) or device (hrows = ncell) */
+                                         double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, double* d_err_log, void* hip_stream);
+int mistra_chem_rosenbrock_replay_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                               double tend, const double* d_atol, const double* d_rtol, int ntol,                     /* device arrays */
+                                               const double* rpar, const int32_t* ipar,                                               /* host arrays */
+                                               int cap, int hrows, const double* hsteps, const int32_t* nsteps, double* d_var_out, int32_t* d_ierr,
+                                               int32_t* d_stats, double* d_texit_hexit, double* d_err_log, void* hip_stream);
+
 /* AbsTol from each cell's own state, on the device in stream order: d_atol[c] = max(floor, factor * max_i |d_var[c][i]|), i over NVAR.  NaN entries
  * are ignored; a cell with no positive entry gets floor.  The product is one rounding of two exact operands, so the host restatement
  * max(floor, factor * fmax-reduction of |var|) gives the same bits.  factor or floor that is not finite and positive fails with a text before a device

@@ -154,6 +154,12 @@ def lib():
             L.mistra_chem_jac_pattern.argtypes = [C.c_int, _ip, _ip, _ip]
             L.mistra_chem_ops_ex.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip]
             L.mistra_chem_ops_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+        if hasattr(L, "mistra_chem_rosenbrock_replay_ex"):      # (hsteps, nsteps as addresses: host arrays, or device arrays for the device entries' rows per cell)
+            table = [C.c_int, C.c_int, vp, vp]
+            L.mistra_chem_rosenbrock_replay_ex.argtypes = L.mistra_chem_rosenbrock_ex.argtypes[:11] + table + [_dp, _ip, _ip, _dp, _dp]
+            L.mistra_chem_rosenbrock_replay_cells_ex.argtypes = L.mistra_chem_rosenbrock_cells_ex.argtypes[:12] + table + [_dp, _ip, _ip, _dp, _dp]
+            L.mistra_chem_rosenbrock_replay_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes[:11] + table + [vp, vp, vp, vp, vp, vp]
+            L.mistra_chem_rosenbrock_replay_cells_device.argtypes = L.mistra_chem_rosenbrock_cells_device.argtypes[:12] + table + [vp, vp, vp, vp, vp, vp]
         if hasattr(L, "mistra_chem_set_policy"):
             L.mistra_chem_set_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
             L.mistra_chem_check_policy.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
@@ -1226,6 +1232,200 @@ def linsolve(mech, var, fix, rconst, shift, rhs=None, fun_rhs=False):
     """(shift*I - J) x = b per cell, J = Jac_SP_x at the state given; b: the cell's own Fun_x (fun_rhs), then the rows of rhs -> (x, ising)"""
     r = ops(mech, var, fix, rconst, False, False, shift=shift, rhs=rhs, fun_rhs=fun_rhs)
     return r.x, r.ising
+
+
+# ---- the replay (include/mistra_chem.h: mistra_chem_rosenbrock_replay_ex / _device and their cells forms; INTEGRATION.md §4r)
+def accepted_steps(trace_d, trace_i, ntrace):
+    """The accepted steps of a step-control trace as a replay's table: trace_d [ncell, cap, 4], trace_i [ncell, cap, 2] and ntrace [ncell] as the trace
+    entries fill them (numpy arrays) -> (hsteps [ncell, cap], nsteps [ncell] int32): per cell the H of the records whose code has bit 0 set, in order,
+    padded with zeros.  Records past the log's capacity were never written: a cell whose ntrace exceeds it is refused, its sequence is not whole."""
+    td, ti = np.asarray(trace_d, np.float64), np.asarray(trace_i, np.int32)
+    nt = np.atleast_1d(np.asarray(ntrace, np.int64))
+    if td.ndim != 3 or td.shape[2] != 4 or ti.shape != td.shape[:2] + (2,) or nt.shape != td.shape[:1]:
+        raise MistraChemError("accepted_steps: trace_d [ncell, cap, 4], trace_i [ncell, cap, 2] and ntrace [ncell] expected")
+    ncell, cap = td.shape[:2]
+    hsteps, nsteps = np.zeros((ncell, cap)), np.zeros(ncell, np.int32)
+    for c in range(ncell):
+        if nt[c] > cap:
+            raise MistraChemError("accepted_steps: cell %d made %d attempts, the log holds %d: trace it again with a larger cap" % (c, nt[c], cap))
+        h = td[c, :nt[c], 1][(ti[c, :nt[c], 1] & 1) == 1]
+        hsteps[c, :h.size] = h
+        nsteps[c] = h.size
+    return hsteps, nsteps
+
+
+def _ros_replay(mech, var, fix, rconst, tstart, tend, hsteps, nsteps, ipar, rpar, atol, rtol, err_log, cells):
+    mid, name = _mech_id(mech)
+    nvar, nfix, nreact, _ = DIMS[name]
+    if cells:
+        ip, rp, _, _ = _option_args(name, ipar, rpar, None, None)
+    else:
+        ip, rp, at, rt = _option_args(name, ipar, rpar, atol, rtol)
+    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
+    L = lib()
+    if not hasattr(L, "mistra_chem_rosenbrock_replay_ex"):
+        raise MistraChemError("this build of the library has no replay entries")
+    if _is_torch(var):
+        import torch
+        if not var.is_cuda:
+            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
+        init(var.device.index or 0)
+        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
+                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
+        ncell = var.numel() // nvar
+        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
+            raise MistraChemError("cell counts of var / fix / rconst differ")
+        if _is_torch(hsteps) != _is_torch(nsteps):
+            raise MistraChemError("hsteps and nsteps: both numpy arrays (one shared sequence) or both tensors on the cells' device (a row per cell)")
+        if _is_torch(hsteps):      # rows per cell, read by the kernel in stream order
+            if hsteps.dtype != torch.float64 or not hsteps.is_contiguous() or hsteps.ndim != 2 or hsteps.device != var.device:
+                raise MistraChemError("hsteps: a contiguous float64 [ncell, cap] tensor on the cells' device expected")
+            if nsteps.dtype != torch.int32 or not nsteps.is_contiguous() or nsteps.ndim != 1 or nsteps.device != var.device:
+                raise MistraChemError("nsteps: a contiguous int32 [ncell] tensor on the cells' device expected")
+            hrows, cap = int(hsteps.shape[0]), int(hsteps.shape[1])
+            if nsteps.numel() != hrows:
+                raise MistraChemError("hsteps has %d rows, nsteps %d entries" % (hrows, nsteps.numel()))
+            if hrows == 1 and ncell == 1:      # (one cell: the library takes the table as the shared, host form)
+                hsteps, nsteps = hsteps.cpu().numpy(), nsteps.cpu().numpy()
+        if not _is_torch(hsteps):
+            hs = np.ascontiguousarray(hsteps, np.float64)
+            hs = hs.reshape(1, -1) if hs.ndim == 1 else hs
+            ns = np.ascontiguousarray(np.atleast_1d(nsteps), np.int32)
+            if hs.ndim != 2 or ns.ndim != 1:
+                raise MistraChemError("hsteps [hrows, cap] and nsteps [hrows] expected")
+            hrows, cap = int(ns.size), int(hs.shape[1])
+            if hs.shape[0] != hrows:
+                raise MistraChemError("hsteps has %d rows, nsteps %d entries" % (hs.shape[0], hrows))
+            if hrows == ncell and ncell > 1:      # rows per cell (what accepted_steps returns): the device entry reads them on the device, so they go up
+                hsteps = torch.tensor(hs, device=var.device)
+                nsteps = torch.tensor(ns, device=var.device)
+                hp, npt = hsteps.data_ptr(), nsteps.data_ptr()
+            else:      # one shared row travels with the call; any other row count is the library's to refuse, before it looks at the addresses
+                hp, npt = hs.ctypes.data_as(C.c_void_p), ns.ctypes.data_as(C.c_void_p)
+        else:
+            hp, npt = hsteps.data_ptr(), nsteps.data_ptr()
+        if err_log is None:
+            err_log = torch.zeros((ncell, cap), dtype=torch.float64, device=var.device)
+        if err_log.dtype != torch.float64 or not err_log.is_contiguous() or err_log.numel() != ncell * cap or err_log.device != var.device:
+            raise MistraChemError("err_log: a contiguous float64 [ncell, cap] tensor on the cells' device expected")
+        if cells:
+            for x in (atol, rtol):
+                if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.ndim != 2 or x.shape[0] != ncell or x.device != var.device:
+                    raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
+            if atol.shape != rtol.shape:
+                raise MistraChemError("atol and rtol differ in shape")
+        out = torch.empty_like(var)
+        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
+        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
+        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
+        stream = torch.cuda.current_stream(var.device).cuda_stream
+        tail = (*popts, cap, hrows, hp, npt, out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), err_log.data_ptr() if cap else None,
+                C.c_void_p(stream))
+        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend))
+        if cells:
+            _check(L.mistra_chem_rosenbrock_replay_cells_device(*head, atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]), *tail))
+        else:
+            _check(L.mistra_chem_rosenbrock_replay_device(*head, at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp), *tail))
+        return IntegrateResult(out, ierr, stats), th, err_log.view(ncell, cap)
+    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+    ncell = v.shape[0]
+    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
+    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
+    hs = None if hsteps is None else np.ascontiguousarray(hsteps, np.float64)
+    if hs is not None and hs.ndim == 1:
+        hs = hs.reshape(1, -1)
+    ns = None if nsteps is None else np.ascontiguousarray(np.atleast_1d(nsteps), np.int32)
+    if (hs is not None and hs.ndim != 2) or (ns is not None and ns.ndim != 1):
+        raise MistraChemError("hsteps [hrows, cap] and nsteps [hrows] expected")
+    hrows = int(ns.size) if ns is not None else int(hs.shape[0]) if hs is not None else 1
+    cap = int(hs.shape[1]) if hs is not None else 0
+    if hs is not None and ns is not None and hs.shape[0] != hrows:
+        raise MistraChemError("hsteps has %d rows, nsteps %d entries" % (hs.shape[0], hrows))
+    if err_log is None:
+        err_log = np.zeros((ncell, cap))
+    if not isinstance(err_log, np.ndarray) or err_log.dtype != np.float64 or not err_log.flags.c_contiguous or err_log.size != ncell * cap:
+        raise MistraChemError("err_log: a C-contiguous float64 [ncell, cap] array expected")
+    out = np.empty_like(v)
+    ierr = np.zeros(ncell, np.int32)
+    stats = np.zeros((ncell, 8), np.int32)
+    th = np.zeros((ncell, 3))
+    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend))
+    tail = (*popts, cap, hrows, None if hs is None or not cap else hs.ctypes.data_as(C.c_void_p), None if ns is None else ns.ctypes.data_as(C.c_void_p),
+            out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp), err_log.ctypes.data_as(_dp) if cap else None)
+    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
+    if cells:
+        a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
+        if a2.ndim != 2 or a2.shape[0] != ncell or r2.shape != a2.shape:
+            raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
+        _check(L.mistra_chem_rosenbrock_replay_cells_ex(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *tail))
+    else:
+        _check(L.mistra_chem_rosenbrock_replay_ex(*head, at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp), *tail))
+    return IntegrateResult(out, ierr, stats), th, err_log.reshape(ncell, cap)
+
+
+def rosenbrock_replay(mech, var, fix, rconst, tstart, tend, hsteps, nsteps, ipar=None, rpar=None, atol=None, rtol=None, err_log=None):
+    """Ros3 along a prescribed step sequence, every step accepted (mistra_chem_rosenbrock_replay_ex / _device) -> (IntegrateResult, t_h, err_log
+    [ncell, cap]: Rosenbrock_x's Err of every step made).  hsteps [hrows, cap], nsteps [hrows], hrows = 1 (a 1-D hsteps is one row: the sequence shared
+    by all cells) or ncell (see accepted_steps).  numpy cell data: the host entry, the table numpy too.  torch CUDA tensors: the device entry on torch's
+    current stream; a shared sequence stays numpy (it travels with the call), rows per cell are tensors on the cells' device — a numpy table of rows per cell, as
+    accepted_steps returns it, is uploaded first.  Of the options the call
+    reads ipar[0], ipar[1], ipar[3] (must be 2, Ros3) and the tolerances; rpar is decoded and ignored.  err_log: the caller's array, entries past a
+    cell's count stay as they are.  Replaying the accepted steps of rosenbrock_trace() under its arguments repeats that call bit for bit."""
+    return _ros_replay(mech, var, fix, rconst, tstart, tend, hsteps, nsteps, ipar, rpar, atol, rtol, err_log, False)
+
+
+def rosenbrock_replay_cells(mech, var, fix, rconst, tstart, tend, hsteps, nsteps, ipar, rpar, atol, rtol, err_log=None):
+    """rosenbrock_replay() with tolerances per cell as rosenbrock_cells takes them; a cell refused with -5 makes no step, its err_log row is untouched."""
+    return _ros_replay(mech, var, fix, rconst, tstart, tend, hsteps, nsteps, ipar, rpar, atol, rtol, err_log, True)
+
+
+Sensitivities = namedtuple("Sensitivities", "dy var max_err ierr nsteps")
+
+
+def sensitivity_cells(name, var, fix, rconst, params, eps):
+    """The 2P+1 cells of one internal-differentiation launch: cell 0 the base cell, cells 2k+1 / 2k+2 with parameter k at p*(1 + eps) / p*(1 - eps) ->
+    (var, fix, rconst [2P+1, .], p [P]).  params: ("var", i) | ("rconst", j) | ("fix", k), 0-based.  A parameter whose value is 0 is refused."""
+    nvar, nfix, nreact, _ = DIMS[name]
+    base = {"var": np.asarray(var, np.float64).reshape(nvar), "fix": np.asarray(fix, np.float64).reshape(nfix),
+            "rconst": np.asarray(rconst, np.float64).reshape(nreact)}
+    if not (np.isfinite(eps) and eps > 0.0):
+        raise MistraChemError("sensitivities: eps must be finite and positive")
+    P = len(params)
+    cells = {k: np.repeat(v[None, :], 2 * P + 1, axis=0) for k, v in base.items()}
+    p = np.zeros(P)
+    for k, par in enumerate(params):
+        if len(par) != 2 or par[0] not in base or not 0 <= int(par[1]) < base[par[0]].size:
+            raise MistraChemError("sensitivities: parameter %d is %r: (\"var\", i), (\"rconst\", j) or (\"fix\", k) inside the mechanism's sizes expected" % (k, par))
+        what, i = par[0], int(par[1])
+        p[k] = base[what][i]
+        if p[k] == 0.0 or not np.isfinite(p[k]):
+            raise MistraChemError("sensitivities: parameter %d, %s[%d], is %r: a relative perturbation needs a finite value other than 0" % (k, what, i, p[k]))
+        cells[what][2 * k + 1, i] = p[k] * (1.0 + eps)
+        cells[what][2 * k + 2, i] = p[k] * (1.0 - eps)
+    return cells["var"], cells["fix"], cells["rconst"], p
+
+
+def sensitivities(mech, var, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, params, eps=1.0e-6, cap=4096):
+    """Internal numerical differentiation of one cell (host arrays): one traced call of the base cell, then ONE replay launch of 2P+1 cells — the base
+    cell and p*(1 +- eps) for each parameter — along the traced call's accepted steps, shared -> Sensitivities: dy [P, NVAR] = (y+ - y-) / (2*eps*p),
+    var [NVAR] the replayed base state (the traced call's, bit for bit), max_err the largest Err over the perturbed cells' steps (above 1: the frozen
+    sequence no longer meets the tolerance for some copy — take a smaller eps), ierr [2P+1] of the replay, nsteps.  params: ("var", i), ("rconst", j),
+    ("fix", k), 0-based; a parameter that is 0 is refused.  The traced call's refusals and errors raise: there is no sequence to freeze."""
+    mid, name = _mech_id(mech)
+    v, f, r, p = sensitivity_cells(name, var, fix, rconst, params, eps)
+    res, _, tr = rosenbrock_trace(mech, v[:1], f[:1], r[:1], tstart, tend, ipar=ipar, rpar=rpar, atol=atol, rtol=rtol, cap=cap, ctrl=False)
+    if int(res.ierr[0]) != 1:
+        raise MistraChemError("sensitivities: the base cell's call returned IERR = %d: no step sequence to freeze" % int(res.ierr[0]))
+    td = np.stack([tr.t, tr.h, tr.err, tr.share], axis=-1)
+    ti = np.stack([tr.species, tr.code], axis=-1)
+    hsteps, nsteps = accepted_steps(td, ti, tr.n)
+    rep, _, err = rosenbrock_replay(mech, v, f, r, tstart, tend, hsteps[0], nsteps[:1], ipar=ipar, rpar=rpar, atol=atol, rtol=rtol)
+    y = rep.var
+    n = int(nsteps[0])
+    dy = (y[1::2] - y[2::2]) / (2.0 * eps * p)[:, None]
+    max_err = float(np.max(err[1:, :n])) if n and len(params) else 0.0
+    return Sensitivities(dy, y[0].copy(), max_err, rep.ierr.copy(), n)
 
 
 FirstStep = namedtuple("FirstStep", "fcn0 ghimj lu r k1 k2 k3 err h var ierr stats")

@@ -65,20 +65,20 @@ bool traits_match(const MechTables& t, int n_jnz, int tail_regs, bool scale_pass
 using LaunchFn = hipError_t (*)(const KernelArgs&, hipStream_t, bool*);
 // The kernels of ros_unit_kernel.hip, [kernel VARIANT 3 .. 6][IPAR(4) resolved, ros_methods.hpp]: 3 the method kernels (Ros2, Ros4, Rodas3, Rodas4), 4 the
 // step-control trace (Ros3), 5 the series and 6 the flux kernels (all five methods), 7 the dense-output kernels (all five methods; they live in the series
-// units), 8 the operator kernels (Ros3's slot; they live in the trace units).  nullptr: not built.
-constexpr int kVariants = 9, kMethods = 6;
+// units), 8 the operator kernels and 9 the replay kernels (Ros3's slot; they live in the trace units).  nullptr: not built.
+constexpr int kVariants = 10, kMethods = 6;
 struct UnitTable {
   LaunchFn fn[kVariants][kMethods] = {};
 };
 template <class MT, int NT, int VARIANT, int METHOD>
 constexpr void add_unit(UnitTable& t) {
-  if constexpr ((VARIANT != 3 || METHOD != kRos3) && ((VARIANT != 4 && VARIANT != 8) || METHOD == kRos3)) t.fn[VARIANT][METHOD] = &launch_ros_unit<MT, NT, VARIANT, METHOD>;
+  if constexpr ((VARIANT != 3 || METHOD != kRos3) && ((VARIANT != 4 && VARIANT != 8 && VARIANT != 9) || METHOD == kRos3)) t.fn[VARIANT][METHOD] = &launch_ros_unit<MT, NT, VARIANT, METHOD>;
 }
 template <class MT, int NT, int... METHOD>
 constexpr UnitTable unit_table(std::integer_sequence<int, METHOD...>) {
   UnitTable t;
   (..., (add_unit<MT, NT, 3, METHOD + 1>(t), add_unit<MT, NT, 4, METHOD + 1>(t), add_unit<MT, NT, 5, METHOD + 1>(t), add_unit<MT, NT, 6, METHOD + 1>(t),
-        add_unit<MT, NT, 7, METHOD + 1>(t), add_unit<MT, NT, 8, METHOD + 1>(t)));
+        add_unit<MT, NT, 7, METHOD + 1>(t), add_unit<MT, NT, 8, METHOD + 1>(t), add_unit<MT, NT, 9, METHOD + 1>(t)));
   return t;
 }
 static_assert(kRos2 == 1 && kRodas4 == 5, "IPAR(4) resolved: 1 .. 5");
@@ -715,6 +715,7 @@ struct MechState {
   DevBuf<double> s_dn_y;                   // ... and of mistra_chem_rosenbrock_dense_ex: the samples' blocks of this slot's cells, the numbers reached
   DevBuf<int32_t> s_dn_n;
   DevBuf<double> s_ops;                    // ... and of mistra_chem_ops_ex: vdot | jvs | shift | rhs | x of this slot's cells
+  DevBuf<double> s_rp;                     // ... and of mistra_chem_rosenbrock_replay_ex: this slot's cells' rows of steps | their Err rows | their counts
   // where the zero-pivot rows of the LAST host-buffer call of this slot are (mistra_chem_singular_rows): cells [sing_start,
   // sing_start + sing_count) of the caller's batch in s_sing, or the one cell of the COMMON-block call in one_sing
   size_t sing_start = 0, sing_count = 0;
@@ -740,7 +741,7 @@ struct MechState {
     step_mem.release(); step_n = 0;
     s_hst.release(); s_tol.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
-    s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release(); s_flux.release(); s_dn_y.release(); s_dn_n.release(); s_ops.release();
+    s_trd.release(); s_tri.release(); s_ntr.release(); s_ctl.release(); s_flux.release(); s_dn_y.release(); s_dn_n.release(); s_ops.release(); s_rp.release();
     sing_count = 0; sing_one = false;
     drive.release(); one.release();
     pend = PendingDrive{};      // (a step issued and never fetched dies with its buffers)
@@ -1196,7 +1197,7 @@ int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, in
       {"series of Rosenbrock_x calls", "no series kernel for this Rosenbrock method"},
       {"reaction-flux entries", "no flux kernel for this Rosenbrock method"},
       {"dense-output entries", "no dense-output kernel for this Rosenbrock method"},
-      {}};      // (8, the operators: launch_ops, not an integration)
+      {}, {}};      // (8, the operators: launch_ops, not an integration; 9, the replay: launch_replay)
   const MechDesc& M = kMech[mech];
   const int variant = a.dense_nout ? 7 : a.times ? 5 : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
   hipError_t e = hipErrorInvalidValue;
@@ -1237,6 +1238,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.dense_out = nullptr; a.dense_nout = nullptr; a.dense_ns = 0; a.dense_block = 0;      // (the dense-output entries set them)
   a.ops_vdot = nullptr; a.ops_jvs = nullptr; a.ops_x = nullptr; a.ops_rhs = nullptr; a.ops_shift = nullptr; a.ops_ising = nullptr;      // (the operator entries set them)
   a.ops_shift_stride = 0; a.ops_fun_rhs = 0; a.ops_nrhs = 0; a.ops_x_block = a.ops_rhs_block = 0;
+  a.replay_h = nullptr; a.replay_n = nullptr; a.replay_h_stride = 0; a.replay_cap = 0; a.replay_err = nullptr;      // (the replay entries set them)
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
@@ -2930,6 +2932,236 @@ int mistra_chem_ops_device(int mech, int ncell, const double* d_var, const doubl
   const KernelArgs a = ops_args(*t.S, ncell, d_var, d_fix, d_rconst, d_vdot, d_jvs, nshift, d_shift, fun_rhs, nrhs, d_rhs, d_x, d_ising, (size_t)ncell,
                                 (size_t)kMech[mech].dims.nvar);
   return launch_ops(*t.D, mech, a, static_cast<hipStream_t>(hip_stream));
+}
+
+// ---- the replay: Ros3 along a step sequence the caller prescribes, every step accepted, its Err handed back (kernel VARIANT 9).  The
+//      options of the call give AbsTol, RelTol and Autonomous; the options in force, the integrator policy and step reuse are not involved.  Checked before
+//      anything touches a device, each refusal by its text: the mechanism (no user slot), the table and the method.
+struct ReplayTable {      // the step table of a replay entry: hsteps [hrows][cap], nsteps [hrows]; err [ncell][cap] or null
+  int cap, hrows;
+  const double* hsteps;
+  const int32_t* nsteps;
+  double* err;
+};
+// counts_on_host: nsteps is a host array (always but for the device entries' per-cell rows)
+static int check_replay(int mech, int ncell, const double* rpar, const int32_t* ipar, const ReplayTable& rt, bool counts_on_host) {
+  if (int rc = builtin_only(mech, "replay entries")) return rc;
+  if (!rpar || !ipar) return fail("null options pointer");
+  if (rt.cap < 0) return fail("replay: negative step capacity");
+  if (rt.hrows != 1 && rt.hrows != ncell) return fail("replay: hrows = " + std::to_string(rt.hrows) + " is neither 1 (one sequence shared by all cells) nor ncell (one per cell)");
+  if (rt.cap > 0 && !rt.hsteps) return fail("replay: step capacity > 0 with a null hsteps pointer (hsteps: [hrows][cap])");
+  if (!rt.nsteps) return fail("replay: null nsteps pointer (nsteps: [hrows])");
+  if (counts_on_host)
+    for (int r = 0; r < rt.hrows; r++)
+      if (rt.nsteps[r] < 0 || rt.nsteps[r] > rt.cap)
+        return fail("replay: nsteps[" + std::to_string(r) + "] = " + std::to_string(rt.nsteps[r]) + " lies outside 0 .. cap = " + std::to_string(rt.cap));
+  if (ipar[3] != 2) return fail("the replay is built for Ros3 (ipar[3] = 2) only");
+  return 0;
+}
+
+static int launch_replay(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream) {
+  const LaunchFn fn = kMech[mech].unit.fn[9][kRos3];
+  if (!fn) return fail("no replay kernel for this mechanism");
+  const hipError_t e = fn(a, stream, &D.lds_configured[mech][9][kRos3]);
+  if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// a shared sequence behind a call's options block: the nsteps[0] steps the kernel reads, then the count in the first half of one more cell -> the words written
+static size_t put_shared_steps(double* at, const ReplayTable& rt) {
+  const size_t n = (size_t)rt.nsteps[0];      // (check_replay: 0 .. cap)
+  if (n) std::memcpy(at, rt.hsteps, n * sizeof(double));
+  at[n] = 0.0;
+  std::memcpy(at + n, rt.nsteps, sizeof(int32_t));
+  return n + 1;
+}
+// the device entries' rows per cell: the kernel reads these itself, memory the cells' device cannot reach is refused here, not met there
+static int check_rows_reachable(const ReplayTable& rt, int device) {
+  for (const void* p : {static_cast<const void*>(rt.hsteps), static_cast<const void*>(rt.nsteps)}) {
+    if (!p) continue;      // (hsteps with cap = 0)
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type == hipMemoryTypeUnregistered || (attr.type == hipMemoryTypeDevice && attr.device != device))
+      return fail("replay: hsteps / nsteps with hrows = ncell are not device arrays on the cells' device (a shared sequence, hrows = 1, is a host array)");
+  }
+  return 0;
+}
+
+// one device's share of mistra_chem_rosenbrock_replay_ex: its cells and its rows up, the kernel, the results down (synchronous on that device)
+static int replay_host_on(DeviceState& D, int mech, int ncell, size_t start, const double* var_in, const double* fix, const double* rconst, double tstart,
+                          double tend, const RosCall& call, const ReplayTable& rt, double* var_out, int32_t* ierr, int32_t* stats, double* t_h) {
+  HIP_TRY(hipSetDevice(D.id));
+  MechState& S = D.mech[mech];
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nc = (size_t)ncell;
+  const size_t cap = (size_t)rt.cap, nb = call.block.size();
+  const bool own = rt.hrows != 1;
+  HIP_TRY(S.s_var.reserve(nc * nv));
+  HIP_TRY(S.s_fix.reserve(nc * nf));
+  HIP_TRY(S.s_rct.reserve(nc * nr));
+  HIP_TRY(S.s_ierr.reserve(nc));
+  HIP_TRY(S.s_stats.reserve(nc * 8));
+  HIP_TRY(S.s_sing.reserve(nc * 8));
+  HIP_TRY(S.s_th.reserve(nc * 3));
+  // one arena: the cells' own rows | their Err rows | their counts
+  const size_t o_h = 0, o_err = o_h + (own ? nc * cap : 0), o_n = o_err + (rt.err ? nc * cap : 0);
+  HIP_TRY(S.s_rp.reserve(o_n + (own ? nc / 2 + 1 : 0) + 1));
+  double* const B = S.s_rp.p;
+  const size_t nshared = own ? 0 : (size_t)rt.nsteps[0];
+  HIP_TRY(S.call_opt.reserve(nb + nshared + 1));
+  HIP_TRY(hipMemcpy(S.s_var.p, var_in + start * nv, nc * nv * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.s_fix.p, fix + start * nf, nc * nf * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.s_rct.p, rconst + start * nr, nc * nr * sizeof(double), hipMemcpyHostToDevice));
+  std::vector<double> blk(call.block);
+  blk.resize(nb + nshared + 1, 0.0);
+  if (!own) put_shared_steps(blk.data() + nb, rt);
+  HIP_TRY(hipMemcpy(S.call_opt.p, blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (own) {
+    if (cap) HIP_TRY(hipMemcpy(B + o_h, rt.hsteps + start * cap, nc * cap * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(B + o_n, rt.nsteps + start, nc * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  if (rt.err && cap)      // the caller's rows go up first: entries past a cell's count come back as they were
+    HIP_TRY(hipMemcpy(B + o_err, rt.err + start * cap, nc * cap * sizeof(double), hipMemcpyHostToDevice));
+  KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, tstart, tend, S.s_var.p, S.s_ierr.p, S.s_stats.p, S.s_th.p);
+  a.h_last = S.s_th.p + 2 * nc;
+  a.opt = S.call_opt.p;
+  a.max_steps = call.max_steps;
+  if (int rc = upload_cell_tol(S, call, start, nc, &a)) return rc;
+  a.replay_cap = rt.cap;
+  a.replay_h = own ? B + o_h : S.call_opt.p + nb;
+  a.replay_n = reinterpret_cast<const int32_t*>(own ? B + o_n : S.call_opt.p + nb + nshared);
+  a.replay_h_stride = own ? (int64_t)cap : 0;
+  a.replay_err = rt.err && cap ? B + o_err : nullptr;
+  a.sing_rows = S.s_sing.p;
+  S.sing_start = start; S.sing_count = nc; S.sing_one = false;
+  if (int rc = launch_replay(D, mech, a, nullptr)) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(var_out + start * nv, S.s_var.p, nc * nv * sizeof(double), hipMemcpyDeviceToHost));
+  if (ierr) HIP_TRY(hipMemcpy(ierr + start, S.s_ierr.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (stats) HIP_TRY(hipMemcpy(stats + start * 8, S.s_stats.p, nc * 8 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (rt.err && cap) HIP_TRY(hipMemcpy(rt.err + start * cap, B + o_err, nc * cap * sizeof(double), hipMemcpyDeviceToHost));
+  if (t_h) {      // device: [ncell][2] (T, Hexit) then [ncell] (H)  ->  caller: [ncell][3]
+    std::vector<double> h(nc * 3);
+    HIP_TRY(hipMemcpy(h.data(), S.s_th.p, nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < nc; c++) { double* o = t_h + (start + c) * 3; o[0] = h[2 * c]; o[1] = h[2 * c + 1]; o[2] = h[2 * nc + c]; }
+  }
+  return 0;
+}
+
+static int replay_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend, const double* atol,
+                       const double* rtol, const double* rpar, const int32_t* ipar, const ReplayTable& rt, double* var_out, int32_t* ierr, int32_t* stats,
+                       double* t_h, const CellTol* ct) {
+  if (int rc = check_replay(mech, ncell, rpar, ipar, rt, true)) return rc;
+  if (ct)
+    if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
+  if (!atol || !rtol) return fail("null options pointer");
+  if (int rc = lazy_init()) return rc;
+  if (int rc = check_call(mech, ncell)) return rc;
+  if (ncell == 0) return 0;
+  if (!var_in || !fix || !rconst || !var_out) return fail("null host pointer");
+  std::lock_guard<std::mutex> lock(g_mu);
+  if (g_devs[0].mech[mech].pend.active) return step_is_open(mech);
+  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
+  if (call.ierr != 1) {      // Rosenbrock_x returns before it touches Y or the statistics: a result, nothing is launched, err_log stays as it is
+    if (var_out != var_in) std::memmove(var_out, var_in, nc * nv * sizeof(double));
+    if (ierr) std::fill(ierr, ierr + nc, (int32_t)call.ierr);
+    if (stats) std::fill(stats, stats + nc * 8, 0);
+    if (t_h) std::fill(t_h, t_h + nc * 3, 0.0);
+    return 0;
+  }
+  for (auto& d : g_devs) d.mech[mech].sing_count = 0;
+  return on_cell_blocks(ncell, [=, &call, &rt](DeviceState& D, size_t start, int count) {
+    return replay_host_on(D, mech, count, start, var_in, fix, rconst, tstart, tend, call, rt, var_out, ierr, stats, t_h);
+  });
+}
+
+static int replay_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart, double tend,
+                            const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, const ReplayTable& rt, double* d_var_out,
+                            int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, void* hip_stream, const CellTol* ct) {
+  const bool own = rt.hrows != 1;      // (one cell: the shared form, host arrays)
+  if (int rc = check_replay(mech, ncell, rpar, ipar, rt, !own)) return rc;
+  if (!own && rt.nsteps[0] > MISTRA_REPLAY_MAX_SHARED)
+    return fail("replay: nsteps[0] = " + std::to_string(rt.nsteps[0]) + ": a shared sequence of the device entries holds at most MISTRA_REPLAY_MAX_SHARED = " +
+                std::to_string(MISTRA_REPLAY_MAX_SHARED) + " steps (it travels in the call's block); give every cell its row");
+  if (ct)
+    if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
+  if (!atol || !rtol) return fail("null options pointer");
+  if (ncell == 0) return check_call(mech, 0);
+  if (!d_var_in || !d_fix || !d_rconst || !d_var_out || !d_ierr || !d_stats) return fail("null device pointer");
+  Slot t;
+  if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (ct)
+    if (int rc = check_tol_reachable(*ct, t.D->id)) return rc;
+  if (own)
+    if (int rc = check_rows_reachable(rt, t.D->id)) return rc;
+  std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of series blocks)
+  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
+  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
+  if (call.ierr != 1) {      // the refusal as a result, in stream order; no kernel of the library runs
+    if (d_var_out != d_var_in) HIP_TRY(hipMemcpyAsync(d_var_out, d_var_in, nc * nv * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_ierr), call.ierr, nc, st));
+    HIP_TRY(hipMemsetAsync(d_stats, 0, nc * 8 * sizeof(int32_t), st));
+    if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nc * 2 * sizeof(double), st));
+    return 0;
+  }
+  // the options and, behind them, a shared sequence: a block of the series' ring, which has the room
+  static_assert(MISTRA_REPLAY_MAX_SHARED + 1 <= MISTRA_SERIES_MAX_LEGS + 1, "a shared sequence and its count travel in a block of the series' ring");
+  const size_t nb = call.block.size(), cap = (size_t)rt.cap;
+  RosCallRing& R = t.S->series_ring;
+  int i;
+  double *hb, *db;
+  HIP_TRY(R.acquire(nb + (size_t)MISTRA_SERIES_MAX_LEGS + 1, &i, &hb, &db));
+  std::memcpy(hb, call.block.data(), nb * sizeof(double));
+  const size_t nshared = own ? 0 : put_shared_steps(hb + nb, rt);      // read here: the caller's arrays are free when the call returns
+  HIP_TRY(hipMemcpyAsync(db, hb, (nb + nshared) * sizeof(double), hipMemcpyHostToDevice, st));
+  KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_var_out, d_ierr, d_stats, d_texit_hexit);
+  a.opt = db;
+  a.max_steps = call.max_steps;
+  if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
+  a.replay_cap = rt.cap;
+  a.replay_h = own ? rt.hsteps : db + nb;
+  a.replay_n = own ? rt.nsteps : reinterpret_cast<const int32_t*>(db + nb + nshared - 1);
+  a.replay_h_stride = own ? (int64_t)cap : 0;
+  a.replay_err = cap ? rt.err : nullptr;
+  const int rc = launch_replay(*t.D, mech, a, st);
+  R.mark(i, st);
+  return rc;
+}
+
+int mistra_chem_rosenbrock_replay_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                     const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int cap, int hrows,
+                                     const double* hsteps, const int32_t* nsteps, double* var_out, int32_t* ierr, int32_t* stats, double* t_h,
+                                     double* err_log) {
+  const ReplayTable rt{cap, hrows, hsteps, nsteps, err_log};
+  return replay_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, rt, var_out, ierr, stats, t_h, nullptr);
+}
+
+int mistra_chem_rosenbrock_replay_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
+                                           const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar, int cap, int hrows,
+                                           const double* hsteps, const int32_t* nsteps, double* var_out, int32_t* ierr, int32_t* stats, double* t_h,
+                                           double* err_log) {
+  const ReplayTable rt{cap, hrows, hsteps, nsteps, err_log};
+  const CellTol ct{atol, rtol, ntol};
+  return replay_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, rt, var_out, ierr, stats, t_h, &ct);
+}
+
+int mistra_chem_rosenbrock_replay_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                         double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int cap, int hrows,
+                                         const double* hsteps, const int32_t* nsteps, double* d_var_out, int32_t* d_ierr, int32_t* d_stats,
+                                         double* d_texit_hexit, double* d_err_log, void* hip_stream) {
+  const ReplayTable rt{cap, hrows, hsteps, nsteps, d_err_log};
+  return replay_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, rt, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                          hip_stream, nullptr);
+}
+
+int mistra_chem_rosenbrock_replay_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
+                                               double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar,
+                                               int cap, int hrows, const double* hsteps, const int32_t* nsteps, double* d_var_out, int32_t* d_ierr,
+                                               int32_t* d_stats, double* d_texit_hexit, double* d_err_log, void* hip_stream) {
+  const ReplayTable rt{cap, hrows, hsteps, nsteps, d_err_log};
+  const CellTol ct{d_atol, d_rtol, ntol};
+  return replay_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, rt, d_var_out, d_ierr, d_stats, d_texit_hexit,
+                          hip_stream, &ct);
 }
 
 // ---- the reaction flux: Rosenbrock_x as above, plus every reaction's rate integrated over the call (kernel VARIANT 6).  The same two

@@ -151,6 +151,16 @@ struct KernelArgs {
   // then the lean program.  (At the end of the block: every other argument keeps its offset.)
   GsDev vdot_pass;
   const uint64_t* vdot_chain_mask;      // [NW] lanes whose species is chained
+  // the replay (kernel VARIANT 9, in the trace units of ros_unit_kernel.hip; mistra_chem_rosenbrock_replay_ex / _device and their cells forms): the cell makes
+  // the steps of its row of replay_h, all accepted, instead of choosing them.  replay_h_stride = 0: one row and one count shared by all
+  // cells, the row behind the call's options block (scalar loads: nothing writes it while the kernel runs); else cell c reads row c*replay_h_stride and
+  // replay_n[c], clamped to replay_cap.  Step n of cell c leaves its Err in replay_err[c*replay_cap + n]; entries past the cell's count are not written.
+  // Read by the replay kernels only; null / 0 everywhere else (capi.cpp: make_args).  (Behind the chain passes: every other argument keeps its offset.)
+  const double* replay_h;      // [replay_cap] or [ncell][replay_h_stride]
+  const int32_t* replay_n;     // [1] or [ncell]
+  int64_t replay_h_stride;
+  int32_t replay_cap;
+  double* replay_err;          // [ncell][replay_cap] or null: not wanted
 };
 
 }  // namespace mistra

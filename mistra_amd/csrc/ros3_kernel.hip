@@ -1449,13 +1449,18 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // 8 = the operators (instantiated in the trace units of ros_unit_kernel.hip; mistra_chem_ops_ex / _device): no integration — Fun_x, Jac_SP_x and solves with
 // shift*I - Jac_SP_x at the state given, by the step loop's own pieces, once.  One block behind the definitions of those pieces that ends
 // with a return; everything it adds sits behind `if constexpr (OPS)`.
+// 9 = the replay (instantiated in the trace units of ros_unit_kernel.hip; mistra_chem_rosenbrock_replay_ex / _device): variant 3 of Ros3 along a step
+// sequence the caller prescribes (a.replay_*): step n of the cell's row is made with H = hsteps[n] and accepted whatever its Err, which
+// goes to a.replay_err.  A step works as the options kernel's does, operand for operand; the step control around it (Hmin / Hmax / Hstart, the factors, the
+// clipping to Tend, Max_no_steps, the halving at a zero pivot) is not there.  Everything it adds sits behind `if constexpr (REPLAY)`.
 // METHOD (variant 3 only): the Rosenbrock method, IPAR(4) of Rosenbrock_x (ros_methods.hpp).  Ros3 is the kernel as it was; Ros2, Ros4, Rodas3
 // and Rodas4 (the method kernels, instantiated by ros_unit_kernel.hip in translation units of their own) differ in the stage loop, in the
 // number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
 template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
-  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, FLUX = VARIANT == 6, DENSE = VARIANT == 7, OPT = VARIANT == 3 || TRACE || SERIES || FLUX || DENSE;
+  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, FLUX = VARIANT == 6, DENSE = VARIANT == 7, REPLAY = VARIANT == 9, OPT = VARIANT == 3 || TRACE || SERIES || FLUX || DENSE || REPLAY;
   constexpr bool OPS = VARIANT == 8;
+  static_assert(!REPLAY || METHOD == kRos3, "the replay is a Ros3 instantiation (ros_unit_kernel.hip), as is the trace that supplies its sequence");
   static_assert(!OPS || METHOD == kRos3, "the operators are Ros3 instantiations (ros_unit_kernel.hip): no method is involved");
   static_assert(!TRACE || METHOD == kRos3, "the step-control trace is a Ros3 instantiation (ros_unit_kernel.hip)");
   static_assert(METHOD == kRos3 || (OPT && METHOD >= kRos2 && METHOD <= kRodas4), "the method kernels are options instantiations");
@@ -2064,6 +2069,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
   [[maybe_unused]] int tr_halved = 0;    // decompositions of the current attempt that returned a zero pivot.  (Declared here, not in the attempt's
                                          // own scope: a declaration there, unused, changed the product kernels' instructions.)
   [[maybe_unused]] int ctrl_r[SPT];      // attempts this thread's species controlled: stored once, at exit
+  // VARIANT 9 (the replay): the number of steps in the cell's row and the step in progress.  (Declared here, not inside the legs' loop: a declaration
+  // there, unused, changed the series kernels' instructions.)
+  [[maybe_unused]] int rp_n = 0, rp_i = 0;
   if constexpr (TRACE) {
 #pragma unroll
     for (int q = 0; q < SPT; q++) ctrl_r[q] = 0;
@@ -2376,9 +2384,24 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       else return k6;
     };
 
-    while (fabs(Tend - T) >= Roundoff) {
-      if (nstp > a.max_steps) { ierr = -6; break; }      // Max_no_steps: 100000 (gas.f:1042, 1199)
-      {
+    // VARIANT 9: the cell's row of step sizes and its count (a.replay_h_stride = 0: one row shared by all cells, behind the call's options block, read by
+    // scalar loads as a series reads its times; else the cell's own row and count, a count above the capacity clamped to it).  The H cell of each wave
+    // holds the step in progress, the Hexit cell the last step TAKEN: both start at 0, the second is written at acceptance.
+    if constexpr (REPLAY) {
+      const bool own = a.replay_h_stride != 0;
+      rp_n = __builtin_amdgcn_readfirstlane(G_(a.replay_n)[own ? cell : 0]);
+      if (rp_n > a.replay_cap) rp_n = a.replay_cap;
+      Hset(0.0);
+    }
+    while (REPLAY ? rp_i < rp_n : fabs(Tend - T) >= Roundoff) {
+      if constexpr (REPLAY) {      // no clipping to Tend, no Max_no_steps; the -7 test as written
+        double H;
+        if (a.replay_h_stride != 0) H = wave_uniform(G_(a.replay_h + (int64_t)cell * a.replay_h_stride)[rp_i]);
+        else H = ((const double __attribute__((address_space(4)))*)a.replay_h)[rp_i];
+        if (((T + scalar_const(0.1) * H) == T) || (H <= Roundoff)) { ierr = -7; break; }
+        Hset(H);
+      } else {
+        if (nstp > a.max_steps) { ierr = -6; break; }      // Max_no_steps: 100000 (gas.f:1042, 1199)
         const double H = Hget();
         if (((T + scalar_const(0.1) * H) == T) || (H <= Roundoff)) { ierr = -7; break; }
         if (t == 0) *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT)) = H;
@@ -2447,6 +2470,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
               nsng += 1;
               nconsecutive += 1;
               if constexpr (TRACE) tr_halved += 1;
+              if constexpr (REPLAY) { ierr = -8; break; }      // a prescribed step is not halved: the cell leaves at the last accepted state
               if (nconsecutive <= 5) Hset(Hget() * 0.5);
               else { ierr = -8; break; }
             } else {
@@ -2599,6 +2623,21 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
           dumping = false;      // the first attempt only
         }
         lap(5);
+        if constexpr (REPLAY) {      // every attempt is accepted: Fac, the root and Hnew are not formed
+          const double H = Hget();
+          if (t == 0) {
+            if (a.replay_err) GM_(a.replay_err)[(int64_t)cell * a.replay_cap + rp_i] = Err;
+            *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT)) = H;
+          }
+          rp_i += 1;
+          nstp += 1;
+          nacc += 1;
+#pragma unroll
+          for (int q = 0; q < SPT; q++) y[q] = ynew[q];
+          T = wave_uniform(T + dh);
+          accepted = true;
+          continue;
+        }
         double root;
         if constexpr (METHOD != kRos3 && kRosMethod<METHOD>.ELO != kRosElo) {      // Err**(1/ros_ELO), ros_ELO = 2 or 4
           constexpr double inv_elo = 1.0 / kRosMethod<METHOD>.ELO;
@@ -2729,7 +2768,11 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         GM_(a.texit_hexit)[(size_t)cell * 2] = T;
         GM_(a.texit_hexit)[(size_t)cell * 2 + 1] = *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT));
       }
-      if (a.h_last) GM_(a.h_last)[cell] = Hget();
+      if constexpr (REPLAY) {      // the last step taken, not the one in progress when an error ended the call
+        if (a.h_last) GM_(a.h_last)[cell] = *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_HEXIT));
+      } else {
+        if (a.h_last) GM_(a.h_last)[cell] = Hget();
+      }
     }
     if constexpr (profiling) {
       if (lane == 0 && wave < kProfWaves)

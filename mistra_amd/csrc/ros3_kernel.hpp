@@ -123,6 +123,8 @@ hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_config
 //   VARIANT 8  the operators, METHOD = Ros3 only and no options block: Fun_x, Jac_SP_x and solves with shift*I - Jac_SP_x at the state given
 //              (kernel_args.hpp: ops_*); at least one of a.ops_vdot, a.ops_jvs and a.ops_x must be set.  No unit of its own: specialised in the
 //              trace unit of its mechanism
+//   VARIANT 9  the replay, METHOD = Ros3 only: the steps of a prescribed sequence, all accepted (kernel_args.hpp: replay_*); a.replay_n must be set.  No
+//              unit of its own: specialised in the trace unit of its mechanism
 // One explicit specialisation per <mechanism, variant, method>, each in a translation unit of its own (ros_unit_kernel.hip).  lds_configured: per
 // device AND kernel.
 template <class MT, int NT, int VARIANT, int METHOD>

@@ -1,6 +1,6 @@
 // One kernel per translation unit: ros3_integrate_kernel<MT, NT, VARIANT, METHOD> for one of the options variants the product unit does not hold
 // (ros3_kernel.hip: 3 a method kernel, 4 the step-control trace, 5 a series, 6 the reaction flux) on gas, aer or tot, with its launcher; a series unit
-// holds the dense-output kernel (VARIANT 7) of its mechanism and method as well, a trace unit the operator kernel (VARIANT 8) of its mechanism (below).  Compiled
+// holds the dense-output kernel (VARIANT 7) of its mechanism and method as well, a trace unit the operator kernel (VARIANT 8) and the replay kernel (VARIANT 9) of its mechanism (below).  Compiled
 // once per unit of mistra_amd/build.py: VARIANT_UNITS.  Units of their own because the non-inlined device functions the kernels share (vm_run,
 // gsum_run*, tail_solve, scale_run, dense_lu, dense_finish) are compiled once per unit, under the register budget of all kernels in it: the product
 // kernels' unit (ros3_kernel.hip) must compile as it does without these, and each of these as it does without the others.
@@ -85,6 +85,25 @@ hipError_t launch_ros_unit<UnitMT, kUnitNT, 8, MISTRA_UNIT_METHOD>(const KernelA
   if (!a.var_in || !a.fix || !a.rconst || (!a.ops_vdot && !a.ops_jvs && !a.ops_x)) return hipErrorInvalidValue;
   if (a.ops_x && (!a.ops_shift || !a.ops_ising || (a.ops_shift_stride != 0 && a.ops_shift_stride != 1) || a.ops_nrhs < 0 ||
                   (a.ops_fun_rhs ? 1 : 0) + a.ops_nrhs < 1 || (a.ops_nrhs > 0 && !a.ops_rhs)))
+    return hipErrorInvalidValue;
+  if (!*lds_configured) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    *lds_configured = true;
+  }
+  if (a.ncell <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kern, dim3((unsigned)a.ncell), dim3(kUnitNT), lds_bytes, stream, a);
+  return hipGetLastError();
+}
+
+// The replay (VARIANT 9) likewise: Ros3 along a prescribed step sequence, the counterpart of the trace that hands the sequence out.  Its own argument guard
+// and its own lds_configured flag (capi.cpp: DeviceState, [mechanism][9][Ros3]); an options instantiation.
+template <>
+hipError_t launch_ros_unit<UnitMT, kUnitNT, 9, MISTRA_UNIT_METHOD>(const KernelArgs& a, hipStream_t stream, bool* lds_configured) {
+  constexpr size_t lds_bytes = LdsLayout<UnitMT, kUnitNT>::TOTAL * sizeof(double);
+  auto kern = ros3_integrate_kernel<UnitMT, kUnitNT, 9, MISTRA_UNIT_METHOD>;
+  if (!a.opt) return hipErrorInvalidValue;
+  if (!a.replay_n || a.replay_cap < 0 || a.replay_h_stride < 0 || (a.replay_cap > 0 && !a.replay_h) || (a.replay_h_stride != 0 && a.replay_h_stride < a.replay_cap))
     return hipErrorInvalidValue;
   if (!*lds_configured) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);

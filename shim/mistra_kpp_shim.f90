@@ -76,6 +76,16 @@
 !     SUBROUTINE FUN_BATCH_g / _a / _t (NCELL, VAR, FIX, RCONST, VDOT)
 !     SUBROUTINE JAC_SP_BATCH_g / _a / _t (NCELL, VAR, FIX, RCONST, JVS)
 !     SUBROUTINE LINSOLVE_BATCH_g / _a / _t (NCELL, VAR, FIX, RCONST, NSHIFT, SHIFT, FUNRHS, NRHS, RHS, X, ISING)
+! THE REPLAY (mistra_chem_rosenbrock_replay_ex; INTEGRATION.md 4r): Ros3 along the step sequences the caller prescribes, every step accepted.  HSTEPS(CAP,HROWS),
+! NSTEPS(HROWS), HROWS = 1 (one sequence shared by all cells) or NCELL; step n of cell k is made with H = HSTEPS(n, its row) and leaves Rosenbrock_x's Err in
+! ERRLOG(n,k), ERRLOG(CAP,NCELL); entries behind a cell's count are not touched.  IPAR(4) must be 2; RPAR is decoded and ignored; TEND gives the direction.
+! TEXIT: the T reached, HEXIT: the last step made.  ros_ErrorMsg_x's lines and the zero-pivot warning (IERR = -8, no halving) as ROSENBROCK_BATCH_x writes them,
+! with one difference: the H those lines print is the last step MADE (0 where none was), not the prescribed step that ended the cell — that one is
+! HSTEPS(ISTAT(3,k) + 1, the cell's row), which the caller holds.
+!     SUBROUTINE ROSENBROCK_BATCH_REPLAY_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT,
+!                                                     IERR, ISTAT, ERRLOG)
+!     SUBROUTINE ROSENBROCK_BATCH_REPLAY_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS,
+!                                                           TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
 module mistra_chem_c_api
   use iso_c_binding
   implicit none
@@ -254,6 +264,28 @@ module mistra_chem_c_api
        type(c_ptr), value :: vdot, jvs, shift, rhs, x, ising      ! each c_null_ptr where the call has none (include/mistra_chem.h)
        integer(c_int) :: rc
      end function mistra_chem_ops_ex
+     function mistra_chem_rosenbrock_replay_ex(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, cap, hrows, hsteps, nsteps, var_out, &
+          ierr, stats, t_h, err_log) bind(C, name="mistra_chem_rosenbrock_replay_ex") result(rc)
+       import :: c_int, c_double, c_int32_t
+       integer(c_int), value :: mech, ncell, cap, hrows
+       real(c_double), value :: tstart, tend
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_out(*), t_h(*), err_log(*)
+       real(c_double), intent(in) :: atol(*), rtol(*), rpar(20), hsteps(*)
+       integer(c_int32_t), intent(in) :: ipar(20), nsteps(*)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_replay_ex
+     function mistra_chem_rosenbrock_replay_cells_ex(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, ntol, rpar, ipar, cap, hrows, hsteps, nsteps, &
+          var_out, ierr, stats, t_h, err_log) bind(C, name="mistra_chem_rosenbrock_replay_cells_ex") result(rc)
+       import :: c_int, c_double, c_int32_t
+       integer(c_int), value :: mech, ncell, ntol, cap, hrows
+       real(c_double), value :: tstart, tend
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_out(*), t_h(*), err_log(*)
+       real(c_double), intent(in) :: atol(*), rtol(*), rpar(20), hsteps(*)
+       integer(c_int32_t), intent(in) :: ipar(20), nsteps(*)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_replay_cells_ex
      function mistra_chem_set_step_reuse(mech, on) bind(C, name="mistra_chem_set_step_reuse") result(rc)
        import :: c_int
        integer(c_int), value :: mech, on
@@ -572,6 +604,48 @@ contains
     end do
     deallocate (th)
   end subroutine rosenbrock_series
+
+  ! The replay for NCELL cells in one launch; the messages in cell order as ROSENBROCK_BATCH_x writes them.  NTOL present: ATOL / RTOL hold a row of NTOL
+  ! entries per cell (ROSENBROCK_BATCH_REPLAY_CELLS_x)
+  subroutine rosenbrock_replay(mech, sfx, NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, &
+       ERRLOG, NTOL)
+    integer, intent(in) :: mech, NCELL, CAP, HROWS
+    integer, intent(in), optional :: NTOL
+    character(len=1), intent(in) :: sfx
+    real(c_double) :: VAR(*), FIX(*), RCONST(*), TEXIT(NCELL), HEXIT(NCELL), ERRLOG(*)
+    real(c_double), intent(in) :: TSTART, TEND, ATOL(*), RTOL(*), RPAR(20), HSTEPS(*)
+    integer(c_int32_t), intent(in) :: IPAR(20), NSTEPS(*)
+    integer(c_int32_t) :: IERR(NCELL), ISTAT(8, NCELL)
+    real(c_double), allocatable :: th(:, :)
+    integer(c_int32_t) :: rows(8)
+    integer :: k, i
+    if (NCELL <= 0) return
+    allocate (th(3, NCELL))
+    if (present(NTOL)) then
+       if (mistra_chem_rosenbrock_replay_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, int(NTOL, c_int), RPAR, IPAR, &
+            int(CAP, c_int), int(HROWS, c_int), HSTEPS, NSTEPS, VAR, IERR, ISTAT, th, ERRLOG) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_REPLAY_CELLS_'//sfx)
+    else
+       if (mistra_chem_rosenbrock_replay_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, int(CAP, c_int), &
+            int(HROWS, c_int), HSTEPS, NSTEPS, VAR, IERR, ISTAT, th, ERRLOG) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_REPLAY_'//sfx)
+    end if
+    do k = 1, NCELL
+       TEXIT(k) = th(1, k)
+       HEXIT(k) = th(2, k)
+       if (ISTAT(8, k) > 0) then
+          rows = 0
+          if (mistra_chem_singular_rows(int(mech, c_int), int(k - 1, c_int), rows) /= 0) call mistra_chem_fail('mistra_chem_singular_rows')
+          do i = 1, ISTAT(8, k)
+             print *, 'Warning: LU Decomposition returned ising = ', int(rows(min(i, 8)))
+          end do
+       end if
+       if (IERR(k) < -5) then
+          call mistra_chem_error_lines(sfx, int(IERR(k)), th(1, k), th(3, k))
+       else if (IERR(k) < 0) then
+          call mistra_chem_error_lines(sfx, int(IERR(k)), TSTART, 0.d0)
+       end if
+    end do
+    deallocate (th)
+  end subroutine rosenbrock_replay
 
   ! FUN_BATCH_x, JAC_SP_BATCH_x, LINSOLVE_BATCH_x: the one C entry, what the call does not have as c_null_ptr
   subroutine ops_batch(mech, what, NCELL, VAR, FIX, RCONST, VDOT, JVS, NSHIFT, SHIFT, FUNRHS, NRHS, RHS, X, ISING)
@@ -1291,3 +1365,70 @@ subroutine LINSOLVE_BATCH_t(NCELL, VAR, FIX, RCONST, NSHIFT, SHIFT, FUNRHS, NRHS
   integer(c_int32_t) :: ISING(*)
   call ops_batch(2, 'LINSOLVE_BATCH_t', NCELL, VAR, FIX, RCONST, NSHIFT=NSHIFT, SHIFT=SHIFT, FUNRHS=FUNRHS, NRHS=NRHS, RHS=RHS, X=X, ISING=ISING)
 end subroutine LINSOLVE_BATCH_t
+
+! ---- the replay (mistra_chem_rosenbrock_replay_ex; INTEGRATION.md 4r): Ros3 along prescribed step sequences, every step accepted, its Err in ERRLOG
+subroutine ROSENBROCK_BATCH_REPLAY_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, CAP, HROWS
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TSTART, TEND, ATOL(102), RTOL(102), RPAR(20), HSTEPS(CAP, *), TEXIT(*), HEXIT(*), ERRLOG(CAP, *)
+  integer(c_int32_t) :: IPAR(20), NSTEPS(*), IERR(*), ISTAT(8, *)
+  call rosenbrock_replay(0, 'g', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
+end subroutine ROSENBROCK_BATCH_REPLAY_g
+
+subroutine ROSENBROCK_BATCH_REPLAY_CELLS_g(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, &
+     ISTAT, ERRLOG)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL, CAP, HROWS
+  real(c_double) :: VAR(102, *), FIX(3, *), RCONST(331, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), HSTEPS(CAP, *), TEXIT(*), HEXIT(*), ERRLOG(CAP, *)
+  integer(c_int32_t) :: IPAR(20), NSTEPS(*), IERR(*), ISTAT(8, *)
+  call rosenbrock_replay(0, 'g', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG, &
+       NTOL=NTOL)
+end subroutine ROSENBROCK_BATCH_REPLAY_CELLS_g
+
+subroutine ROSENBROCK_BATCH_REPLAY_a(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, CAP, HROWS
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TSTART, TEND, ATOL(257), RTOL(257), RPAR(20), HSTEPS(CAP, *), TEXIT(*), HEXIT(*), ERRLOG(CAP, *)
+  integer(c_int32_t) :: IPAR(20), NSTEPS(*), IERR(*), ISTAT(8, *)
+  call rosenbrock_replay(1, 'a', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
+end subroutine ROSENBROCK_BATCH_REPLAY_a
+
+subroutine ROSENBROCK_BATCH_REPLAY_CELLS_a(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, &
+     ISTAT, ERRLOG)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL, CAP, HROWS
+  real(c_double) :: VAR(257, *), FIX(5, *), RCONST(979, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), HSTEPS(CAP, *), TEXIT(*), HEXIT(*), ERRLOG(CAP, *)
+  integer(c_int32_t) :: IPAR(20), NSTEPS(*), IERR(*), ISTAT(8, *)
+  call rosenbrock_replay(1, 'a', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG, &
+       NTOL=NTOL)
+end subroutine ROSENBROCK_BATCH_REPLAY_CELLS_a
+
+subroutine ROSENBROCK_BATCH_REPLAY_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, CAP, HROWS
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TSTART, TEND, ATOL(417), RTOL(417), RPAR(20), HSTEPS(CAP, *), TEXIT(*), HEXIT(*), ERRLOG(CAP, *)
+  integer(c_int32_t) :: IPAR(20), NSTEPS(*), IERR(*), ISTAT(8, *)
+  call rosenbrock_replay(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
+end subroutine ROSENBROCK_BATCH_REPLAY_t
+
+subroutine ROSENBROCK_BATCH_REPLAY_CELLS_t(NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, NTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, &
+     ISTAT, ERRLOG)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NTOL, CAP, HROWS
+  real(c_double) :: VAR(417, *), FIX(7, *), RCONST(1627, *), TSTART, TEND, ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), HSTEPS(CAP, *), TEXIT(*), HEXIT(*), ERRLOG(CAP, *)
+  integer(c_int32_t) :: IPAR(20), NSTEPS(*), IERR(*), ISTAT(8, *)
+  call rosenbrock_replay(2, 't', NCELL, VAR, FIX, RCONST, TSTART, TEND, ATOL, RTOL, RPAR, IPAR, CAP, HROWS, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG, &
+       NTOL=NTOL)
+end subroutine ROSENBROCK_BATCH_REPLAY_CELLS_t

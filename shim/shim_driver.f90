@@ -31,6 +31,11 @@
 !          shim_driver <PG|PA|PT> <in.bin> <out.bin>   the operators: in.bin = ncell, nshift, funrhs (0 | 1), nrhs, SHIFT(nshift), then the cells as for <G|A|T>, then
 !                                                      RHS(NVAR, ncell, nrhs); ONE call each of FUN_BATCH_x, JAC_SP_BATCH_x and LINSOLVE_BATCH_x.  out.bin = VDOT(NVAR, ncell),
 !                                                      JVS(LU_NONZERO, ncell), X(NVAR, ncell, funrhs + nrhs), ISING(ncell)
+!          shim_driver <LG|LA|LT> <in.bin> <out.bin>   the replay: in.bin = IPAR(20), RPAR(20), ATOL(NVAR), RTOL(NVAR), TSTART, TEND, ncell, ntol, cap, hrows,
+!                                                      HSTEPS(cap, hrows), NSTEPS(hrows) as doubles, then the cells as for <G|A|T>.  ntol = 0: ONE call of
+!                                                      ROSENBROCK_BATCH_REPLAY_x with the pair; ntol = 1 or NVAR: ONE call of ROSENBROCK_BATCH_REPLAY_CELLS_x, every
+!                                                      cell's row the first ntol entries of the pair.  out.bin = per cell VAR, TEXIT, HEXIT, IERR, the 8 statistics,
+!                                                      ERRLOG(cap) (set to -7.25 in front of the call)
 !          shim_driver <Eg|Ea|Et> <in.bin> <out.bin>   in.bin = ncell, then per cell VAR, FIX, ENV (the vector MISTRA_RATES_ENV_x packs,
 !                                                      mistra_kpp_rates.f90): UPDATE_RCONST_BATCH_x, then INTEGRATE_BATCH_ENV_x (rates and
 !                                                      integrator on the device, RCONST never crosses PCIe); out.bin = per cell VAR,
@@ -116,6 +121,13 @@ program shim_driver
      case ('G'); call run_dense(0, 102, 3, 331, trim(fin), trim(fout))
      case ('A'); call run_dense(1, 257, 5, 979, trim(fin), trim(fout))
      case ('T'); call run_dense(2, 417, 7, 1627, trim(fin), trim(fout))
+     case default; stop 'mechanism must be G, A or T'
+     end select
+  case ('L')
+     select case (a1(2:2))
+     case ('G'); call run_replay(0, 102, 3, 331, trim(fin), trim(fout))
+     case ('A'); call run_replay(1, 257, 5, 979, trim(fin), trim(fout))
+     case ('T'); call run_replay(2, 417, 7, 1627, trim(fin), trim(fout))
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('P')
@@ -374,6 +386,57 @@ contains
     end do
     close (11); close (12)
   end subroutine run_flux
+  subroutine run_replay(mech, NVAR, NFIX, NREACT, fin, fout)
+    integer, intent(in) :: mech, NVAR, NFIX, NREACT
+    character(len=*), intent(in) :: fin, fout
+    double precision :: ropt(40), tt(6)
+    double precision, allocatable :: ATOL(:), RTOL(:), AROW(:, :), RROW(:, :), VAR(:, :), FIX(:, :), RCONST(:, :), TEXIT(:), HEXIT(:), HSTEPS(:, :), CNT(:), &
+         ERRLOG(:, :), rec(:)
+    integer :: IPAR(20), n, ntol, cap, hrows, i
+    integer, allocatable :: IERR(:), ISTAT(:, :), NSTEPS(:)
+    open (11, file=fin, access='stream', form='unformatted', status='old')
+    open (12, file=fout, access='stream', form='unformatted', status='replace')
+    allocate (ATOL(NVAR), RTOL(NVAR))
+    read (11) ropt, ATOL, RTOL, tt      ! tt: TSTART, TEND, ncell, ntol, cap, hrows
+    IPAR = int(ropt(1:20))
+    n = int(tt(3)); ntol = int(tt(4)); cap = int(tt(5)); hrows = int(tt(6))
+    allocate (HSTEPS(cap, hrows), CNT(hrows), NSTEPS(hrows))
+    read (11) HSTEPS, CNT
+    NSTEPS = int(CNT)
+    allocate (VAR(NVAR, n), FIX(NFIX, n), RCONST(NREACT, n), TEXIT(n), HEXIT(n), IERR(n), ISTAT(8, n), ERRLOG(cap, n))
+    allocate (rec(NVAR + NFIX + NREACT), AROW(max(ntol, 1), n), RROW(max(ntol, 1), n))
+    ERRLOG = -7.25d0
+    do i = 1, n
+       read (11) rec
+       VAR(:, i) = rec(1:NVAR)
+       FIX(:, i) = rec(NVAR + 1:NVAR + NFIX)
+       RCONST(:, i) = rec(NVAR + NFIX + 1:)
+       if (ntol > 0) then
+          AROW(:, i) = ATOL(1:ntol)
+          RROW(:, i) = RTOL(1:ntol)
+       end if
+    end do
+    if (ntol == 0) then
+       select case (mech)
+       case (0); call ROSENBROCK_BATCH_REPLAY_g(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ropt(21:40), IPAR, cap, hrows, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
+       case (1); call ROSENBROCK_BATCH_REPLAY_a(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ropt(21:40), IPAR, cap, hrows, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
+       case (2); call ROSENBROCK_BATCH_REPLAY_t(n, VAR, FIX, RCONST, tt(1), tt(2), ATOL, RTOL, ropt(21:40), IPAR, cap, hrows, HSTEPS, NSTEPS, TEXIT, HEXIT, IERR, ISTAT, ERRLOG)
+       end select
+    else
+       select case (mech)
+       case (0); call ROSENBROCK_BATCH_REPLAY_CELLS_g(n, VAR, FIX, RCONST, tt(1), tt(2), AROW, RROW, ntol, ropt(21:40), IPAR, cap, hrows, HSTEPS, NSTEPS, TEXIT, HEXIT, &
+            IERR, ISTAT, ERRLOG)
+       case (1); call ROSENBROCK_BATCH_REPLAY_CELLS_a(n, VAR, FIX, RCONST, tt(1), tt(2), AROW, RROW, ntol, ropt(21:40), IPAR, cap, hrows, HSTEPS, NSTEPS, TEXIT, HEXIT, &
+            IERR, ISTAT, ERRLOG)
+       case (2); call ROSENBROCK_BATCH_REPLAY_CELLS_t(n, VAR, FIX, RCONST, tt(1), tt(2), AROW, RROW, ntol, ropt(21:40), IPAR, cap, hrows, HSTEPS, NSTEPS, TEXIT, HEXIT, &
+            IERR, ISTAT, ERRLOG)
+       end select
+    end if
+    do i = 1, n
+       write (12) VAR(:, i), TEXIT(i), HEXIT(i), dble(IERR(i)), dble(ISTAT(:, i)), ERRLOG(:, i)
+    end do
+    close (11); close (12)
+  end subroutine run_replay
   subroutine run_ops(mech, NVAR, NFIX, NREACT, NNZ, fin, fout)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT, NNZ
     character(len=*), intent(in) :: fin, fout
