@@ -130,23 +130,24 @@ def kernel_units(n_user):
     return [PRODUCT] + VARIANT_UNITS + [Unit("user", slot, None) for slot in range(n_user)]
 
 
-def unit_build(unit):
+def unit_build(unit, incdir=None):
     """-> (source file, object name, flags) of a kernel unit.  Raises for a unit that does not exist: a VARIANT 3 unit of Ros3 (that kernel lives
-    in the product unit), a trace unit of another method, a mechanism, method or slot out of range."""
+    in the product unit), a trace unit of another method, a mechanism, method or slot out of range.  incdir: where a user slot's traits header
+    lies (default the build directory; an edge twin has a directory of its own)."""
     variant, mech, method = unit
     if unit == PRODUCT:
         return PRODUCT_SOURCE, "ros3_kernel.o", []
     if variant == "user" and mech in range(MAX_USER_MECHS) and method is None:
-        return USER_SOURCE, "ros_user_%d.o" % mech, ["-DMISTRA_USER_SLOT=%d" % mech, "-DMISTRA_USER_MECHS=%d" % (mech + 1), "-I" + OBJDIR]
+        return USER_SOURCE, "ros_user_%d.o" % mech, ["-DMISTRA_USER_SLOT=%d" % mech, "-DMISTRA_USER_MECHS=%d" % (mech + 1), "-I" + (incdir or OBJDIR)]
     if variant not in VARIANT_METHODS or mech not in (0, 1, 2) or method not in VARIANT_METHODS[variant]:
         raise ValueError("no kernel unit %r: VARIANT -> methods %r on mechanisms 0 .. 2, the product unit, user slots 0 .. %d" %
                          (tuple(unit), VARIANT_METHODS, MAX_USER_MECHS - 1))
     return UNIT_SOURCE, "ros_unit_%d_%d_%d.o" % unit, ["-DMISTRA_UNIT_VARIANT=%d" % variant, "-DMISTRA_UNIT_MECH=%d" % mech, "-DMISTRA_UNIT_METHOD=%d" % method]
 
 
-def unit_listing_cmd(unit, out):
+def unit_listing_cmd(unit, out, incdir=None):
     """-> the command that writes the gfx950 assembly of a kernel unit's device code to `out`, compiled as the build compiles it"""
-    src, _, flags = unit_build(unit)
+    src, _, flags = unit_build(unit, incdir)
     return [hipcc(), "--offload-arch=" + ARCH] + [f for f in COMMON if f != "-fPIC"] + flags + ["-S", "--offload-device-only", os.path.join(CSRC, src), "-o", out]
 
 
@@ -252,26 +253,94 @@ def build_nochain_twin(force=False, verbose=False):
     return LIB_NOCHAIN
 
 
+# ---- the edge twins: the library with tables at the edges of the user slots' size classes in its two slots (mistra_amd/mechderive.py:
+# EDGE_TABLES), what tests/test_gpu_user_edges.py runs in child processes.  Nothing loads them otherwise.  edge_a128 (one wave per cell WITH a
+# scaling pass) sits apart from edge_g64 and edge_a129, so that those two do not depend on its unit passing the ring-register check.
+EDGE_TWINS = collections.OrderedDict([("edge0", ("edge_g64", "edge_a129")), ("edge1", ("edge_a128", "edge_t417"))])
+
+
+def edge_twin_lib(twin):
+    return os.path.join(LIBDIR, "libmistra_chem_%s.so" % twin)
+
+
+def edge_twin_dir(twin):
+    """where a twin's traits headers, its two user units and its capi.o lie: the product's build/user_traits_*.hpp and user_mechs.cfg stay as they are"""
+    return os.path.join(OBJDIR, twin)
+
+
+def build_edge_twins(force=False, verbose=False):
+    """Links the edge twins from the objects build_lib has made (call it first): every object of the product but the two user units and capi.o, which
+    are compiled against the twin's own traits headers in edge_twin_dir.  The ring-register and hazard checks run on a twin's user units before it is
+    linked, as build_lib runs them on the product's.  -> the libraries' paths"""
+    from concurrent.futures import ThreadPoolExecutor
+    from . import mechderive
+    tables = mechderive.ensure_edge_tables()
+    cc = hipcc()
+    gen = build_traits_gen(force, verbose)
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))]
+    headers += [os.path.join(PKG, "..", "include", "mistra_chem.h"), os.path.abspath(__file__)]
+    kernel_src = os.path.join(CSRC, PRODUCT_SOURCE)
+    shared = [os.path.splitext(s)[0] + ".o" for s in SOURCES if s != "capi.cpp"] + [unit_build(u)[1] for u in kernel_units(0)]
+    libs = []
+    for twin, names in EDGE_TWINS.items():
+        tdir = edge_twin_dir(twin)
+        os.makedirs(tdir, exist_ok=True)
+        traits = []
+        for slot, name in enumerate(names):
+            final, tmp = os.path.join(tdir, "user_traits_%d.hpp" % slot), os.path.join(tdir, "user_traits_%d.hpp.new" % slot)
+            traits.append(final)
+            if not force and not _stale(final, [tables[name], gen]) and ('"%s"' % name) in open(final).read():
+                continue
+            user_traits(tables[name], slot, tmp, gen)
+            if not os.path.exists(final) or open(final).read() != open(tmp).read():
+                os.replace(tmp, final)
+            else:
+                os.remove(tmp)
+        uunits = [Unit("user", slot, None) for slot in range(len(names))]
+        own = [("capi.cpp", "capi.o", ["-DMISTRA_USER_MECHS=%d" % len(names), "-I" + tdir], traits)]
+        own += [unit_build(u, tdir) + ([kernel_src] + traits,) for u in uunits]
+        objs, cmds = [os.path.join(OBJDIR, name) for name in shared], []
+        for src, name, flags, deps in own:
+            obj = os.path.join(tdir, name)
+            objs.append(obj)
+            if force or _stale(obj, [os.path.join(CSRC, src)] + deps + headers):
+                cmds.append([cc, "--offload-arch=" + ARCH] + COMMON + flags + ["-c", os.path.join(CSRC, src), "-o", obj])
+        with ThreadPoolExecutor(_jobs()) as pool:
+            list(pool.map(lambda cmd: _run(cmd, verbose), cmds))
+        lib = edge_twin_lib(twin)
+        if force or _stale(lib, objs):
+            with ThreadPoolExecutor(_jobs()) as pool:
+                reports = list(pool.map(lambda u: ring_register_report(unit=u, incdir=tdir), uunits))
+            for u, isa in zip(uunits, reports):
+                hits = isa_hazard_report(isa["__isa_text__"])
+                if hits:
+                    raise RuntimeError("hazards the hardware does not interlock inside hand-written assembly (%s, kernel unit %r):\n  " % (twin, tuple(u)) + "\n  ".join(hits))
+            _run([cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs + ["-ldl"], verbose)
+        libs.append(lib)
+    return libs
+
+
 # the non-inlined device functions of ros3_kernel.hip in which table loads are in flight in the look-ahead ring (their last template
 # argument is the ring's placement).  In gsum_run_pair a FILLED ring outlives compiler code: the statements between its two programs.
 RING_FUNCTIONS = ("gsum_run", "gsum_run_bar", "gsum_run_pair", "gsum_pass_run", "tail_solve", "scale_run")
 RING_HIGH_SLOTS = (192, 196, 208, 212, 224, 228, 240, 244)      # ros3_kernel.hip: MISTRA_RING_HI<K>
 
 
-def ring_register_report(isa_path=None, unit=PRODUCT):
+def ring_register_report(isa_path=None, unit=PRODUCT, incdir=None):
     """Checks the one assumption the table look-ahead ring of ros3_kernel.hip rests on (see the comment there): in the
     non-inlined device functions, every register the COMPILER allocates — named outside inline asm, or chosen by it for an asm
     statement's result — stays below the ring's blocks (v192.. or, in the low placement, v64..), so a
     table load landing in the ring can never hit a compiler value.  Compiles the kernel source to gfx950 assembly and
     scans it.  Returns {function: highest VGPR named outside inline asm}; raises if a ring-using function reaches its ring, and if
     a function that is not one of RING_FUNCTIONS (nor an integrating kernel, which only calls them) loads into the ring at all.
-    unit: one of kernel_units() (a user slot's traits header must be in the build directory: prepare_user_mechs); default the product kernels' unit."""
+    unit: one of kernel_units() (a user slot's traits header must be in the build directory: prepare_user_mechs — or in `incdir`, an edge twin's
+    directory); default the product kernels' unit."""
     import re
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         if isa_path is None:
             isa_path = os.path.join(tmp, "unit.s")
-            subprocess.run(unit_listing_cmd(unit, isa_path), check=True, stderr=subprocess.DEVNULL)
+            subprocess.run(unit_listing_cmd(unit, isa_path, incdir), check=True, stderr=subprocess.DEVNULL)
         lines = open(isa_path).read().split("\n")
     starts = [(i, l.split(":")[0]) for i, l in enumerate(lines) if re.match(r"^_ZN6mistra.*:", l)]
     starts.append((len(lines), "end"))
@@ -432,3 +501,4 @@ def isa_hazard_report(isa_text, sgpr_vmem_wait=5, dpp_wait=2, seen=None):
 if __name__ == "__main__":
     print(build_lib(force="--force" in sys.argv, verbose=True))
     print(build_nochain_twin(force="--force" in sys.argv, verbose=True))
+    print(build_edge_twins(force="--force" in sys.argv, verbose=True))

@@ -786,10 +786,27 @@ __device__ __attribute__((noinline)) void scale_run(const ScaleDev P, int wave, 
       lds_st(a0.x, v0 * f0); lds_st(a0.z, v1 * f1); lds_st(a1.x, v2 * f2); lds_st(a1.z, v3 * f3); \
       lds_st(a2.x, v4 * f4); lds_st(a2.z, v5 * f5); lds_st(a3.x, v6 * f6); lds_st(a3.z, v7 * f7); \
     }
+    // the low placement (one wave per cell with a scaling pass: a user slot of 64 .. 128 species) leaves the function's own values the registers
+    // below v64: two slots at a time there, eight gathers in flight and four products — half the live values of a group of four (which reached
+    // v65).  The cells are distinct and every product is one multiply: the result is the same bits in any grouping.  Every slot is refilled behind
+    // its take (TRIM is the high placement's), so slot K is the oldest of the eight loads in flight: vmcnt(7), as in a refilled group of four.
+#define MISTRA_SCALE_PAIR(K)                                                         \
+    {                                                                                \
+      const u32x4 a0 = vm_ring_take<LOW, K, 7>();     vm_ring_load<LOW, K>(rp + K * 64);             \
+      const u32x4 a1 = vm_ring_take<LOW, K + 1, 7>(); vm_ring_load<LOW, K + 1>(rp + (K + 1) * 64);   \
+      const double v0 = lds_ld(a0.x), f0 = lds_ld(a0.y), v1 = lds_ld(a0.z), f1 = lds_ld(a0.w); \
+      const double v2 = lds_ld(a1.x), f2 = lds_ld(a1.y), v3 = lds_ld(a1.z), f3 = lds_ld(a1.w); \
+      lds_st(a0.x, v0 * f0); lds_st(a0.z, v1 * f1); lds_st(a1.x, v2 * f2); lds_st(a1.z, v3 * f3); \
+    }
   for (int i = 0; i < n_refilled; i += kRingSlots) {
-    MISTRA_SCALE_GROUP(0, true) MISTRA_SCALE_GROUP(4, true)
+    if constexpr (LOW) {
+      MISTRA_SCALE_PAIR(0) MISTRA_SCALE_PAIR(2) MISTRA_SCALE_PAIR(4) MISTRA_SCALE_PAIR(6)
+    } else {
+      MISTRA_SCALE_GROUP(0, true) MISTRA_SCALE_GROUP(4, true)
+    }
     rp += kRingSlots * 64;
   }
+#undef MISTRA_SCALE_PAIR
   if constexpr (TRIM) {
     if (n > 0) { MISTRA_SCALE_GROUP(0, false) MISTRA_SCALE_GROUP(4, false) }
   }

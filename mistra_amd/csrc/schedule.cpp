@@ -440,6 +440,10 @@ VmProgram build_vm_program(std::vector<VmEntry> entries, const VmLayout& lay, in
     phase_max = std::max(phase_max, f);
   }
 
+  // A program without a single update (the head sweeps of a mechanism of 64 species: the tail chain is its whole solve) still gets ONE round, of
+  // null rows: the executor leaves its loop where it has counted its rounds down to zero at a round's end and has no test at entry, so entered
+  // with none it would walk the slack rows and on past the end of the table.
+  if (rounds.empty()) rounds[1];
   P.nrounds = (int)rounds.size();
   P.blk_n.assign((size_t)P.nrounds * P.nw, 0);
   // Local rounds.  A round of a few dozen records costs a workgroup what every round costs it — all waves through a barrier and its LDS

@@ -195,6 +195,52 @@ def ensure_demo_tables(mech_dir=None):
     return paths
 
 
+# Tables at the edges of the user slots' size classes, for the twin libraries mistra_amd/build.py: build_edge_twins links and
+# tests/test_user_edges.py, tests/test_gpu_user_edges.py run: name -> (source, species handed to fewest_reactions_rule; None = the source's own
+# bytes under this name).  All are cut with the species left without a reaction REMOVED.  Neither the tables nor their maps are committed: both are
+# written into EDGE_DIR, beside copies of gas.mech, aer.mech and tot.mech, so that the directory serves as a mechanism directory.
+# tests/user_edge_cases.py pins a SHA-256 and the sizes of every table.
+EDGE_TABLES = {"edge_g64": ("gas", 37), "edge_a128": ("aer", 129), "edge_a129": ("aer", 128), "edge_t417": ("tot", None)}
+EDGE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "build", "edge_mech")
+
+
+def derive_edge(name, mech_dir=None):
+    """-> (tables dict, maps dict) of an edge table, derived from the source table in `mech_dir`"""
+    source, nspecies = EDGE_TABLES[name]
+    t = mechtab.MechTables(source, os.path.join(mech_dir or mechtab.MECH_DIR, source + ".mech"))
+    drop = () if nspecies is None else fewest_reactions_rule(t, nspecies)[1]
+    return derive(t, drop, remove_species=True)
+
+
+def _write_if_changed(path, want):
+    have = None
+    if os.path.exists(path):
+        with open(path, "rb") as f:
+            have = f.read()
+    if have != want:      # (whole file or nothing: another process may be reading the directory)
+        tmp = "%s.%d.tmp" % (path, os.getpid())
+        with open(tmp, "wb") as f:
+            f.write(want)
+        os.replace(tmp, path)
+
+
+def ensure_edge_tables(out_dir=None, mech_dir=None):
+    """Writes the edge tables, their .json maps and copies of gas.mech, aer.mech and tot.mech into `out_dir` (default EDGE_DIR) where a file is
+    missing or is not what the rule derives; a file that is already right is left untouched.  -> {name: the table's path}"""
+    out_dir, mech_dir = out_dir or EDGE_DIR, mech_dir or mechtab.MECH_DIR
+    os.makedirs(out_dir, exist_ok=True)
+    for source in sorted({s for s, _ in EDGE_TABLES.values()}):
+        with open(os.path.join(mech_dir, source + ".mech"), "rb") as f:
+            _write_if_changed(os.path.join(out_dir, source + ".mech"), f.read())
+    paths = {}
+    for name in EDGE_TABLES:
+        tab, maps = derive_edge(name, mech_dir)
+        paths[name] = os.path.join(out_dir, name + ".mech")
+        _write_if_changed(paths[name], table_bytes(tab))
+        _write_if_changed(os.path.join(out_dir, name + ".json"), maps_text(maps).encode())
+    return paths
+
+
 def fewest_reactions_rule(t, nspecies=16):
     """The cut the demo tables are made with: the `nspecies` variable species that take part in the fewest reactions (ties: the lower index;
     species that take part in none are skipped) and every reaction any of them takes part in.  -> (species, reactions to drop), sorted."""

@@ -34,12 +34,13 @@ TH_RTOL = {("demo_g", "base"): PARITY_FLOOR, ("demo_g", "rtol_1e-5"): 2.5e-13, (
            ("demo_a", "base"): 2.2e-4, ("demo_a", "rtol_1e-5"): 1.2e-3, ("demo_a", "vector_tol"): 1.8e-6}
 
 
-def options_for(name, run):
-    """IPAR, RPAR, AbsTol, RelTol of a run for a demo table (None for "base": INTEGRATE_x's values, no options in force)"""
+def options_for(name, run, nvar=None):
+    """IPAR, RPAR, AbsTol, RelTol of a run for a demo table (None for "base": INTEGRATE_x's values, no options in force).  nvar: the size of a
+    table that is not one of the demo tables (tests/user_edge_bounds.py)."""
     import user_mech_cases as uc
     if run in ("base", "hstart"):
         return None
-    nvar = uc.SIZES[name][0]
+    nvar = nvar or uc.SIZES[name][0]
     ipar, rpar = np.zeros(20, np.int32), np.zeros(20)      # over INTEGRATE_x's base, as ros_options_py.option_set builds its sets
     ipar[1], ipar[3] = 1, 2
     rpar[2] = 1.0e-3
