@@ -373,6 +373,45 @@ int mistra_chem_rosenbrock_series_rates_cells_device(int mech, int ncell, const 
                                                      double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                                      int carry_h, const double* d_hstart, void* hip_stream);
 
+/* A SERIES WITH RATE CONSTANTS LINEAR IN TIME OVER EACH LEG: Rosenbrock_x as the non-autonomous integrator it is.  The series with
+ * rates above with node blocks in place of rconst and its count:
+ *     rconst_nodes [nleg + 1][ncell][NREACT]      block k the rate constants AT times[k]: what mistra_chem_update_rconst_device writes for (nleg + 1)*ncell
+ *                                                 env rows, node-major
+ *     fix [fix_legs][ncell][NFIX]                 fix_legs 1 or nleg, piecewise constant as above.
+ * Inside leg k reaction r of a cell has, with R0 = rconst_nodes[k], R1 = rconst_nodes[k+1], w = 1/(times[k+1] - times[k]) and d = R1[r] - R0[r],
+ *     R_r(tau) = R0[r] + ((tau - times[k]) * w) * d      dR_r/dt = d * w      every operation rounded on its own (no fused multiply-add),
+ * so equal node blocks give R0 at every tau.  The step is RosenbrockIntegrator_x: Fcn0 and Jac0 read R(T), a stage that evaluates anew reads R(T +
+ * ros_Alpha(i)*Direction*H), and with ipar[0] = 0 every stage with ros_Gamma(i) /= 0 adds (Direction*H*ros_Gamma(i))*dFdT, where dFdT = Fun(Y, FIX, dR/dt)
+ * is the exact time derivative (Fun is linear in the rate constants) in the place of ros_FunTimeDerivative_x's finite difference: one Fun call, counted in
+ * Nfun as KPP counts its own.  With ipar[0] /= 0 there is no dFdT and no such term; the stages still read R(tau).  Everything else is the series': outputs
+ * and layout, the first step and carry_h, the refusals that stay results, the failure codes per leg.  With equal node blocks the results are those of the
+ * series with rates on the shared block, up to the sign of a zero.
+ * fix_legs not in {1, nleg}, a null rconst_nodes, the series' own refusals and a user slot (the slot's text) fail with a text before a device is touched.
+ * rconst_nodes is read at every function evaluation: it may not alias var_series, and the device forms' array must stay untouched until the kernel has
+ * finished (stream order).  The _ex forms upload each device slot's cells of the nleg + 1 blocks with one 2-D copy. */
+int mistra_chem_rosenbrock_series_linrates_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst_nodes,
+                                              int fix_legs,
+                                              int nleg, const double* times, const double* atol, const double* rtol,
+                                              const double* rpar, const int32_t* ipar, int carry_h, const double* hstart /* [ncell] or NULL */,
+                                              double* var_series, int32_t* ierr, int32_t* stats, double* t_h);
+int mistra_chem_rosenbrock_series_linrates_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst_nodes,
+                                                  int fix_legs,
+                                                  int nleg, const double* times, const double* atol, const double* rtol,
+                                                  const double* rpar, const int32_t* ipar,                                        /* host arrays */
+                                                  double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                                  int carry_h, const double* d_hstart, void* hip_stream);
+int mistra_chem_rosenbrock_series_linrates_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst_nodes,
+                                                    int fix_legs,
+                                                    int nleg, const double* times, const double* atol, const double* rtol, int ntol,  /* rows per cell */
+                                                    const double* rpar, const int32_t* ipar, int carry_h, const double* hstart,
+                                                    double* var_series, int32_t* ierr, int32_t* stats, double* t_h);
+int mistra_chem_rosenbrock_series_linrates_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst_nodes,
+                                                        int fix_legs,
+                                                        int nleg, const double* times, const double* d_atol, const double* d_rtol, int ntol,  /* device arrays */
+                                                        const double* rpar, const int32_t* ipar,                                   /* host arrays */
+                                                        double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                                        int carry_h, const double* d_hstart, void* hip_stream);
+
 /* DENSE OUTPUT: the state at ns sample times INSIDE one call of Rosenbrock_x, without changing the call (a series, above, is nleg calls).
  * Everything mistra_chem_rosenbrock_ex / _device (the cells forms: _cells_ex / _cells_device) return with the same arguments, d_hstart included, bit for
  * bit (var_out, ierr, stats, t_h / d_texit_hexit), plus

@@ -140,6 +140,8 @@ def lib():
             for form in ("ex", "device", "cells_ex", "cells_device"):
                 at = getattr(L, "mistra_chem_rosenbrock_series_" + form).argtypes
                 getattr(L, "mistra_chem_rosenbrock_series_rates_" + form).argtypes = at[:5] + [C.c_int, C.c_int] + at[5:]
+                if hasattr(L, "mistra_chem_rosenbrock_series_linrates_" + form):      # ... with fix_legs behind rconst_nodes
+                    getattr(L, "mistra_chem_rosenbrock_series_linrates_" + form).argtypes = at[:5] + [C.c_int] + at[5:]
         if hasattr(L, "mistra_chem_rosenbrock_flux_ex"):
             L.mistra_chem_rosenbrock_flux_ex.argtypes = L.mistra_chem_rosenbrock_ex.argtypes + [_dp]
             L.mistra_chem_rosenbrock_flux_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [vp]
@@ -959,6 +961,22 @@ def rosenbrock_series_rates(mech, var, fix, rconst, times, ipar=None, rpar=None,
     nleg*ncell env rows, leg-major, returns, reshaped or not.  Everything else as rosenbrock_series(): numpy arrays go to the host entry, torch CUDA
     tensors to the device entry on torch's current stream (fix and rconst are read at the head of every leg: leave them untouched until the stream has
     passed the call, and they may not overlap out); a 2-D atol / rtol selects the cells form."""
+    return _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, False)
+
+
+def rosenbrock_series_linrates(mech, var, fix, rconst_nodes, times, ipar=None, rpar=None, atol=None, rtol=None, hstart=None, carry_h=False, out=None):
+    """rosenbrock_series_rates() with rate constants LINEAR IN TIME over each leg (include/mistra_chem.h: mistra_chem_rosenbrock_series_linrates_ex /
+    _device and their cells forms).  rconst_nodes: 3-D [nleg + 1, ncell, NREACT], block k the rate constants AT times[k]: what
+    update_rconst over (nleg + 1)*ncell env rows, node-major, returns.  Inside leg k every function evaluation reads R0 + ((tau - times[k]) * w) * (R1 - R0)
+    at its own time tau, w = 1/(times[k+1] - times[k]), and with ipar[0] = 0 the stages add H*gamma_i * Fun(Y, FIX, dR/dt), the exact dFdT.  fix: 2-D
+    (shared) or 3-D [nleg, ncell, NFIX], piecewise constant.  Everything else as rosenbrock_series_rates() -> SeriesResult; equal node blocks give that
+    function's results on the shared block, up to the sign of a zero."""
+    return _series_rates(mech, var, fix, rconst_nodes, times, ipar, rpar, atol, rtol, hstart, carry_h, out, True)
+
+
+def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, lin):
+    """rosenbrock_series_rates (lin false) and rosenbrock_series_linrates (lin true: rconst holds the nleg + 1 node blocks, and the entries take no count
+    of them)"""
     mid, name = _mech_id(mech)
     nvar, nfix, nreact, _ = DIMS[name]
     cells = atol is not None and rtol is not None and getattr(atol, "ndim", 0) == 2 and getattr(rtol, "ndim", 0) == 2
@@ -975,6 +993,12 @@ def rosenbrock_series_rates(mech, var, fix, rconst, times, ipar=None, rpar=None,
             raise MistraChemError("%s: a 2-D [ncell, .] array (shared by all legs) or a 3-D [nleg, ncell, .] one expected" % what)
         return 1 if x.ndim == 2 else int(x.shape[0])
 
+    def nodes(x):           # (lin) the node blocks: exactly nleg + 1 of them; the library takes no count
+        if x.ndim != 3 or int(x.shape[0]) != rows + 1:
+            raise MistraChemError("rconst_nodes: a 3-D [nleg + 1, ncell, NREACT] array expected, block k the rate constants at times[k] (nleg = %d)" % nleg)
+        return rows + 1
+
+    entry = "mistra_chem_rosenbrock_series_%s_" % ("linrates" if lin else "rates")
     if _is_torch(var):
         import torch
         if not var.is_cuda:
@@ -984,7 +1008,7 @@ def rosenbrock_series_rates(mech, var, fix, rconst, times, ipar=None, rpar=None,
             if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
                 raise MistraChemError("expected contiguous float64 [..., ncell,%d] tensors on one device" % n)
         ncell = var.numel() // nvar
-        nlf, nlr = legs(fix, "fix"), legs(rconst, "rconst")
+        nlf, nlr = legs(fix, "fix"), nodes(rconst) if lin else legs(rconst, "rconst")
         if fix.numel() != nlf * ncell * nfix or rconst.numel() != nlr * ncell * nreact:
             raise MistraChemError("cell counts of var / fix / rconst differ")
         if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
@@ -1005,17 +1029,17 @@ def rosenbrock_series_rates(mech, var, fix, rconst, times, ipar=None, rpar=None,
         stream = torch.cuda.current_stream(var.device).cuda_stream
         tail = (out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), int(bool(carry_h)), None if hstart is None else hstart.data_ptr(),
                 C.c_void_p(stream))
-        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), nlr, nlf, nleg, tp)
+        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr()) + (() if lin else (nlr,)) + (nlf, nleg, tp)
         if cells:
-            _check(L.mistra_chem_rosenbrock_series_rates_cells_device(*head, atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]), *popts, *tail))
+            _check(getattr(L, entry + "cells_device")(*head, atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]), *popts, *tail))
         else:
-            _check(L.mistra_chem_rosenbrock_series_rates_device(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
+            _check(getattr(L, entry + "device")(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
         return SeriesResult(out.view(rows, ncell, nvar), ierr, stats, th)
     v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
     ncell = v.shape[0]
     f = np.ascontiguousarray(fix, np.float64)
     r = np.ascontiguousarray(rconst, np.float64)
-    nlf, nlr = legs(f, "fix"), legs(r, "rconst")
+    nlf, nlr = legs(f, "fix"), nodes(r) if lin else legs(r, "rconst")
     if f.size != nlf * ncell * nfix or r.size != nlr * ncell * nreact:
         raise MistraChemError("cell counts of var / fix / rconst differ")
     hs = None if hstart is None else np.ascontiguousarray(hstart, np.float64).reshape(-1)
@@ -1025,7 +1049,7 @@ def rosenbrock_series_rates(mech, var, fix, rconst, times, ipar=None, rpar=None,
     ierr = np.zeros((rows, ncell), np.int32)
     stats = np.zeros((rows, ncell, 8), np.int32)
     th = np.zeros((rows, ncell, 3))
-    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), nlr, nlf, nleg, tp)
+    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp)) + (() if lin else (nlr,)) + (nlf, nleg, tp)
     tail = (int(bool(carry_h)), None if hs is None else hs.ctypes.data_as(_dp), res.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip),
             stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp))
     # (the arguments are checked by the library before it looks for a device: no init() in front of them)
@@ -1033,9 +1057,9 @@ def rosenbrock_series_rates(mech, var, fix, rconst, times, ipar=None, rpar=None,
         a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
         if a2.shape[0] != ncell or r2.shape != a2.shape:
             raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
-        _check(L.mistra_chem_rosenbrock_series_rates_cells_ex(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *popts, *tail))
+        _check(getattr(L, entry + "cells_ex")(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *popts, *tail))
     else:
-        _check(L.mistra_chem_rosenbrock_series_rates_ex(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
+        _check(getattr(L, entry + "ex")(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
     return SeriesResult(res, ierr, stats, th)
 
 

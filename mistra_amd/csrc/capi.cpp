@@ -65,8 +65,9 @@ bool traits_match(const MechTables& t, int n_jnz, int tail_regs, bool scale_pass
 using LaunchFn = hipError_t (*)(const KernelArgs&, hipStream_t, bool*);
 // The kernels of ros_unit_kernel.hip, [kernel VARIANT 3 .. 6][IPAR(4) resolved, ros_methods.hpp]: 3 the method kernels (Ros2, Ros4, Rodas3, Rodas4), 4 the
 // step-control trace (Ros3), 5 the series and 6 the flux kernels (all five methods), 7 the dense-output kernels (all five methods; they live in the series
-// units), 8 the operator kernels and 9 the replay kernels (Ros3's slot; they live in the trace units).  nullptr: not built.
-constexpr int kVariants = 10, kMethods = 6;
+// units), 8 the operator kernels and 9 the replay kernels (Ros3's slot; they live in the trace units), 10 the series kernels with rate constants linear in
+// time (all five methods; they live in the method units, Ros3's in the trace units).  nullptr: not built.
+constexpr int kVariants = 11, kMethods = 6;
 struct UnitTable {
   LaunchFn fn[kVariants][kMethods] = {};
 };
@@ -78,7 +79,7 @@ template <class MT, int NT, int... METHOD>
 constexpr UnitTable unit_table(std::integer_sequence<int, METHOD...>) {
   UnitTable t;
   (..., (add_unit<MT, NT, 3, METHOD + 1>(t), add_unit<MT, NT, 4, METHOD + 1>(t), add_unit<MT, NT, 5, METHOD + 1>(t), add_unit<MT, NT, 6, METHOD + 1>(t),
-        add_unit<MT, NT, 7, METHOD + 1>(t), add_unit<MT, NT, 8, METHOD + 1>(t), add_unit<MT, NT, 9, METHOD + 1>(t)));
+        add_unit<MT, NT, 7, METHOD + 1>(t), add_unit<MT, NT, 8, METHOD + 1>(t), add_unit<MT, NT, 9, METHOD + 1>(t), add_unit<MT, NT, 10, METHOD + 1>(t)));
   return t;
 }
 static_assert(kRos2 == 1 && kRodas4 == 5, "IPAR(4) resolved: 1 .. 5");
@@ -1197,9 +1198,10 @@ int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, in
       {"series of Rosenbrock_x calls", "no series kernel for this Rosenbrock method"},
       {"reaction-flux entries", "no flux kernel for this Rosenbrock method"},
       {"dense-output entries", "no dense-output kernel for this Rosenbrock method"},
-      {}, {}};      // (8, the operators: launch_ops, not an integration; 9, the replay: launch_replay)
+      {}, {},      // (8, the operators: launch_ops, not an integration; 9, the replay: launch_replay)
+      {"series of Rosenbrock_x calls", "no series kernel with rate constants linear in time for this Rosenbrock method"}};
   const MechDesc& M = kMech[mech];
-  const int variant = a.dense_nout ? 7 : a.times ? 5 : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
+  const int variant = a.dense_nout ? 7 : a.times ? (a.lin_rates ? 10 : 5) : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
   hipError_t e = hipErrorInvalidValue;
   if (variant) {
     if (M.user) return fail_user_slot(mech, kText[variant].user);
@@ -1239,6 +1241,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.ops_vdot = nullptr; a.ops_jvs = nullptr; a.ops_x = nullptr; a.ops_rhs = nullptr; a.ops_shift = nullptr; a.ops_ising = nullptr;      // (the operator entries set them)
   a.ops_shift_stride = 0; a.ops_fun_rhs = 0; a.ops_nrhs = 0; a.ops_x_block = a.ops_rhs_block = 0;
   a.replay_h = nullptr; a.replay_n = nullptr; a.replay_h_stride = 0; a.replay_cap = 0; a.replay_err = nullptr;      // (the replay entries set them)
+  a.lin_rates = 0;      // (the series entries with rate constants linear in time set it)
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
@@ -3300,12 +3303,19 @@ static int check_series(int mech, int nleg, const double* times, const void* var
   return 0;
 }
 
+// the series with rate constants linear in time: the one argument of their own (the node blocks take the place of rconst and its count)
+static int check_nodes(const double* rconst_nodes) {
+  if (!rconst_nodes) return fail("series: null rconst_nodes pointer (rconst_nodes: [nleg + 1][ncell][NREACT], block k the rate constants at times[k])");
+  return 0;
+}
+
 // one device slot's share of mistra_chem_rosenbrock_series_ex: cells [start, start + ncell) of the caller's batch of `total` cells
 static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, size_t total, const double* var_in, const double* fix, const double* rconst,
                           int rconst_legs, int fix_legs, int nleg, const double* times, const RosCall& call, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
-                          int32_t* stats, double* t_h) {
+                          int32_t* stats, double* t_h, bool lin) {
   HIP_TRY(hipSetDevice(D.id));
   MechState& S = D.mech[mech];
+  if (lin) rconst_legs = nleg + 1;      // the node blocks: one more than there are legs
   const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nc = (size_t)ncell, nl = (size_t)nleg;
   const size_t nb = call.block.size();
   HIP_TRY(S.s_var.reserve(nc * nv));
@@ -3330,6 +3340,7 @@ static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, siz
   a.times = S.call_opt.p + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
   a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
   a.leg_rconst = rconst_legs > 1 ? (int64_t)(nc * nr) : 0; a.leg_fix = fix_legs > 1 ? (int64_t)(nc * nf) : 0;      // the block's stride, not the caller's
+  a.lin_rates = lin ? 1 : 0;
   if (int rc = upload_cell_tol(S, call, start, nc, &a)) return rc;
   if (hstart) {
     HIP_TRY(S.s_hst.reserve(nc));
@@ -3357,8 +3368,10 @@ static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, siz
 
 static int series_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs, int fix_legs, int nleg,
                        const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int carry_h,
-                       const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h, const CellTol* ct) {
+                       const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h, const CellTol* ct, bool lin = false) {
   if (int rc = check_series(mech, nleg, times, var_series, rconst_legs, fix_legs)) return rc;
+  if (lin)
+    if (int rc = check_nodes(rconst)) return rc;
   if (ct)
     if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
@@ -3381,15 +3394,17 @@ static int series_host(int mech, int ncell, const double* var_in, const double* 
   // var_in may alias one leg's block of var_series: every slot has its inputs on the device before any result comes back (below: all uploads of a
   // slot precede its downloads, and slots own disjoint cells)
   return on_cell_blocks(ncell, [=, &call](DeviceState& D, size_t start, int count) {
-    return series_host_on(D, mech, count, start, nc, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h);
+    return series_host_on(D, mech, count, start, nc, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h, lin);
   });
 }
 
 static int series_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int rconst_legs, int fix_legs,
                             int nleg, const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                             double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart,
-                            void* hip_stream, const CellTol* ct) {
+                            void* hip_stream, const CellTol* ct, bool lin = false) {
   if (int rc = check_series(mech, nleg, times, d_var_series, rconst_legs, fix_legs)) return rc;
+  if (lin)
+    if (int rc = check_nodes(d_rconst)) return rc;
   if (ct)
     if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
   if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
@@ -3425,7 +3440,8 @@ static int series_on_device(int mech, int ncell, const double* d_var_in, const d
   a.max_steps = call.max_steps;
   a.times = db + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
   a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
-  a.leg_rconst = rconst_legs > 1 ? (int64_t)(nc * (size_t)kMech[mech].dims.nreact) : 0;      // the caller's arrays, read at the head of every leg
+  a.leg_rconst = rconst_legs > 1 || lin ? (int64_t)(nc * (size_t)kMech[mech].dims.nreact) : 0;      // the caller's arrays, read at the head of every leg
+  a.lin_rates = lin ? 1 : 0;      // (... of every evaluation: the node blocks, nleg + 1 of them)
   a.leg_fix = fix_legs > 1 ? (int64_t)(nc * (size_t)kMech[mech].dims.nfix) : 0;
   if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
   const int rc = launch(*t.D, mech, a, st, call.method);
@@ -3496,6 +3512,41 @@ int mistra_chem_rosenbrock_series_rates_cells_device(int mech, int ncell, const 
   const CellTol ct{d_atol, d_rtol, ntol};
   return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr,
                           d_stats, d_texit_hexit, carry_h, d_hstart, hip_stream, &ct);
+}
+
+// ---- the series with rate constants linear in time over each leg (kernel VARIANT 10): the same path again, rconst_nodes holding
+//      nleg + 1 blocks, block k the rate constants AT times[k]; FIX stays piecewise constant (fix_legs = 1 or nleg)
+int mistra_chem_rosenbrock_series_linrates_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst_nodes, int fix_legs, int nleg,
+                                              const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
+                                              int carry_h, const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
+  return series_host(mech, ncell, var_in, fix, rconst_nodes, 1, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h,
+                     nullptr, true);
+}
+
+int mistra_chem_rosenbrock_series_linrates_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst_nodes, int fix_legs,
+                                                    int nleg, const double* times, const double* atol, const double* rtol, int ntol, const double* rpar,
+                                                    const int32_t* ipar, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
+                                                    int32_t* stats, double* t_h) {
+  const CellTol ct{atol, rtol, ntol};
+  return series_host(mech, ncell, var_in, fix, rconst_nodes, 1, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h,
+                     &ct, true);
+}
+
+int mistra_chem_rosenbrock_series_linrates_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst_nodes, int fix_legs,
+                                                  int nleg, const double* times, const double* atol, const double* rtol, const double* rpar,
+                                                  const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                                  int carry_h, const double* d_hstart, void* hip_stream) {
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst_nodes, 1, fix_legs, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats,
+                          d_texit_hexit, carry_h, d_hstart, hip_stream, nullptr, true);
+}
+
+int mistra_chem_rosenbrock_series_linrates_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst_nodes,
+                                                        int fix_legs, int nleg, const double* times, const double* d_atol, const double* d_rtol, int ntol,
+                                                        const double* rpar, const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats,
+                                                        double* d_texit_hexit, int carry_h, const double* d_hstart, void* hip_stream) {
+  const CellTol ct{d_atol, d_rtol, ntol};
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst_nodes, 1, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr, d_stats,
+                          d_texit_hexit, carry_h, d_hstart, hip_stream, &ct, true);
 }
 
 int mistra_chem_cell_atol_device(int mech, int ncell, const double* d_var, double factor, double floor, double* d_atol, void* hip_stream) {

@@ -161,6 +161,11 @@ struct KernelArgs {
   int64_t replay_h_stride;
   int32_t replay_cap;
   double* replay_err;          // [ncell][replay_cap] or null: not wanted
+  // a series with rate constants linear in time over each leg (kernel VARIANT 10, in the method and trace units of ros_unit_kernel.hip;
+  // mistra_chem_rosenbrock_series_linrates_ex / _device and their cells forms): rconst holds nleg + 1 node blocks leg_rconst elements
+  // apart, block k the rate constants at times[k]; leg k reads blocks k and k + 1.  /= 0 selects those kernels (capi.cpp: launch), which read the series'
+  // arguments and nothing else of their own; 0 everywhere else (capi.cpp: make_args).  (At the end of the block: every other argument keeps its offset.)
+  int32_t lin_rates;
 };
 
 }  // namespace mistra

@@ -1470,12 +1470,17 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // sequence the caller prescribes (a.replay_*): step n of the cell's row is made with H = hsteps[n] and accepted whatever its Err, which
 // goes to a.replay_err.  A step works as the options kernel's does, operand for operand; the step control around it (Hmin / Hmax / Hstart, the factors, the
 // clipping to Tend, Max_no_steps, the halving at a zero pivot) is not there.  Everything it adds sits behind `if constexpr (REPLAY)`.
+// 10 = a series whose rate constants are linear in time over each leg (instantiated in the method units and, for Ros3, the trace units of
+// ros_unit_kernel.hip; mistra_chem_rosenbrock_series_linrates_ex / _device): variant 5 of any of the five methods with a.rconst holding nleg + 1 node blocks, block k the rate
+// constants AT a.times[k] (a.leg_rconst: the node stride).  Every Fun_x / Jac_SP_x reads R(tau) at its own time — T at the head of a step, T +
+// ros_Alpha(i)*Direction*H in a stage that evaluates anew — and the step adds HG*dFdT with dFdT = Fun_x(Y, FIX, dR/dt), one more Fun_x per step, where
+// the others add their zero.  Everything it adds sits behind `if constexpr (LINR)`; what a series does it does as SERIES.
 // METHOD (variant 3 only): the Rosenbrock method, IPAR(4) of Rosenbrock_x (ros_methods.hpp).  Ros3 is the kernel as it was; Ros2, Ros4, Rodas3
 // and Rodas4 (the method kernels, instantiated by ros_unit_kernel.hip in translation units of their own) differ in the stage loop, in the
 // number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
 template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
-  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, SERIES = VARIANT == 5, FLUX = VARIANT == 6, DENSE = VARIANT == 7, REPLAY = VARIANT == 9, OPT = VARIANT == 3 || TRACE || SERIES || FLUX || DENSE || REPLAY;
+  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, LINR = VARIANT == 10, SERIES = VARIANT == 5 || LINR, FLUX = VARIANT == 6, DENSE = VARIANT == 7, REPLAY = VARIANT == 9, OPT = VARIANT == 3 || TRACE || SERIES || FLUX || DENSE || REPLAY;
   constexpr bool OPS = VARIANT == 8;
   static_assert(!REPLAY || METHOD == kRos3, "the replay is a Ros3 instantiation (ros_unit_kernel.hip), as is the trace that supplies its sequence");
   static_assert(!OPS || METHOD == kRos3, "the operators are Ros3 instantiations (ros_unit_kernel.hip): no method is involved");
@@ -1679,16 +1684,36 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     }
   }
   // (the register-starved kernels fetch them per use, like their factor words)
-  constexpr bool RCT_PER_USE = MT::WAVES_PER_SIMD > kResidentMaxWps || L::RCT_IN_LDS;
+  constexpr bool RCT_PER_USE = LINR || MT::WAVES_PER_SIMD > kResidentMaxWps || L::RCT_IN_LDS;      // (VARIANT 10: the rate constants are a function of the time, formed per use)
   // VARIANT 5: the leg index (the legs' loop, below).  Declared here because the leg's own rate constants (a.leg_rconst, kernel_args.hpp) start at
   // a.rconst + leg*a.leg_rconst: a base formed from two scalars where the fetch uses it, never a vector value kept across the step loop.
   [[maybe_unused]] int leg = 0;
+  // VARIANT 10: the rate constants linear in time over the leg, between the node blocks a.rconst + leg*a.leg_rconst (at times[leg]) and the one behind it
+  // (at times[leg + 1]).  lin_w = 1/(times[leg+1] - times[leg]) and lin_s = (tau - times[leg])*lin_w of the evaluation to come are wave-uniform (scalar
+  // registers); lin_dot: the evaluation to come takes the time derivative d*lin_w in place of the value.  load_rct forms R(tau) = R0 + lin_s*d, d = R1 - R0,
+  // every operation rounded on its own, of the reactions the thread owns: per use, out of global memory, for all three mechanisms (the cell's copy in LDS
+  // and the resident registers hold nothing here).
+  [[maybe_unused]] double lin_w = 0.0, lin_s = 0.0;
+  [[maybe_unused]] bool lin_dot = false;
   auto load_rct = [&](bool opaque) {      // this thread's rate constants; opaque: the per-use fetch (RCT_PER_USE)
     const double* rc = a.rconst;
     if constexpr (SERIES) rc += (int64_t)leg * a.leg_rconst;
     if (opaque) asm volatile("" : "+s"(rc));
     int tt = t;
     if (opaque) asm volatile("" : "+v"(tt));      // (addresses derived where they are used: hoisted out of the step loop they are registers that spill)
+    if constexpr (LINR) {
+#pragma clang fp contract(off)
+      const double* rc1 = rc + a.leg_rconst;
+#pragma unroll
+      for (int q = 0; q < RPT; q++) {
+        const int r = q * NT + tt;
+        const double r0 = r < NREACT ? G_(rc)[(size_t)cell * NREACT + r] : 0.0, r1 = r < NREACT ? G_(rc1)[(size_t)cell * NREACT + r] : 0.0;
+        const double d = r1 - r0;
+        const double up = lin_s * d;
+        rct[q] = lin_dot ? d * lin_w : r0 + up;
+      }
+      return;
+    }
 #pragma unroll
     for (int q = 0; q < RPT; q++) {
       const int r = q * NT + tt;
@@ -1698,7 +1723,10 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       rct[q] = r < NREACT ? G_(rc)[(size_t)cell * NREACT + r] : 0.0;
     }
   };
-  if constexpr (L::RCT_IN_LDS) {      // global -> LDS, once; read back by the same thread that wrote them (r = q*NT + t): no barrier involved
+  if constexpr (LINR) {      // formed in front of every evaluation (load_rct)
+#pragma unroll
+    for (int q = 0; q < RPT; q++) rct[q] = 0.0;
+  } else if constexpr (L::RCT_IN_LDS) {      // global -> LDS, once; read back by the same thread that wrote them (r = q*NT + t): no barrier involved
 #pragma unroll
     for (int q = 0; q < RPT; q++) {
       const int r = q * NT + t;
@@ -2291,6 +2319,14 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
     if (lane == 0) *(volatile lds_f64*)(uintptr_t)(8u * (uint32_t)(L::RED + L::RED_H + wv)) = v;
   };
   static_assert(NW <= L::RED_H && L::RED_H + NW <= L::RED_HEXIT, "red[]: partial sums | H per wave | Hexit");
+  // VARIANT 10: the next evaluation reads the rate constants at tau = T + alpha*dh (ros_Alpha(i)*Direction*H behind the step's T): its place in the leg,
+  // (tau - times[leg]) * w, each operation rounded on its own
+  [[maybe_unused]] auto lin_stage = [&](double T, double alpha, double dh) {
+#pragma clang fp contract(off)
+    const double up = alpha * dh;
+    const double tau = T + up;
+    lin_s = wave_uniform((tau - Tstart) * lin_w);
+  };
   // ---- the legs (VARIANT 5; one pass for every other variant).  The leg's bookkeeping is wave-uniform and stays in scalar registers: the leg index, the
   //      leg's two times (scalar loads out of the call's options block, which nothing writes while the kernel runs) and the offsets of its output blocks,
   //      formed where they are used.  Every per-call quantity of Rosenbrock_x starts afresh below.  Nothing is carried around the loop in a vector
@@ -2302,6 +2338,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
       Tend = times[leg + 1];
       Hmax = wave_uniform(fabs(Tend - Tstart));
       Direction = (Tend >= Tstart) ? 1.0 : -1.0;
+      if constexpr (LINR) lin_w = wave_uniform(1.0 / (Tend - Tstart));      // once per leg; the node blocks themselves are read per use (load_rct)
       if (leg > 0) {      // Rosenbrock_x called again: the options' Hstart and no per-cell value; a.carry_h: the previous leg's Hexit where it is > 0
         hstart0 = opt(kOptHstart);
         if (a.carry_h) {
@@ -2312,7 +2349,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         }
         // RCONST and FIX of the leg's own (a.leg_rconst / a.leg_fix /= 0, uniform over the call): what Update_RCONST_x left in front of this call of
         // Rosenbrock_x.  The per-use fetch out of global memory needs nothing here: load_rct forms the leg's base itself.
-        if (a.leg_rconst != 0) {
+        if (!LINR && a.leg_rconst != 0) {
           if constexpr (L::RCT_IN_LDS) {      // the cell's copy in LDS: every thread rewrites the cells it reads back itself (r = q*NT + t): no barrier involved
             const double* rc = a.rconst + (int64_t)leg * a.leg_rconst;
 #pragma unroll
@@ -2389,6 +2426,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
 
     double ynew[SPT], fcn0[SPT], fcn[SPT], k1[SPT], k2[SPT], k3[SPT], yerr[SPT];
     [[maybe_unused]] double k4[SPT], k5[SPT], k6[SPT];      // the method kernels' further stage vectors (Ros4, Rodas3: k4; Rodas4: k4..k6)
+    [[maybe_unused]] double dfdt[SPT];                      // VARIANT 10: the step's dFdT, live from its evaluation to the last stage
     // stage vector J (0-based) by its compile-time number: named register arrays, never an array indexed at run time (that one would live in scratch)
     [[maybe_unused]] auto stage_k = [&](auto J) -> double (&)[SPT] {
       constexpr int j = decltype(J)::value;
@@ -2430,6 +2468,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
 #pragma unroll                     //  undefined one — is carried around the step loop: the 128-register kernels carried one through scratch)
         for (int q = 0; q < JPT; q++) asm volatile("" : "=v"(jac0[q]));
       }
+      if constexpr (LINR) lin_stage(T, 0.0, 0.0);      // Fcn0 and Jac0 read R(T)
       if constexpr (L::MERGE_FUN_JAC) {
         fun_jac(y, fcn0);
         dump_vec(0, fcn0);
@@ -2438,6 +2477,18 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
         dump_vec(0, fcn0);
         lap(0);
         jac();
+      }
+      // VARIANT 10: dFdT = Fun(Y, FIX, dR/dt), the exact time derivative (Fun is linear in the rate constants, they are linear in the time): the Fun call
+      // ros_FunTimeDerivative_x makes, counted below as KPP counts it; not made where the call is autonomous.  Jac0 is in registers by now.
+      if constexpr (LINR) {
+        if (!autonomous) {
+          lin_dot = true;
+          fun(y, dfdt);
+          lin_dot = false;
+        } else {
+#pragma unroll
+          for (int q = 0; q < SPT; q++) dfdt[q] = 0.0;
+        }
       }
       if constexpr (FLUX) flux_close();      // X is Y_n until stage 2 stores into it, behind ros_PrepareMatrix's barriers
       if constexpr (DENSE) {
@@ -2457,6 +2508,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
           // K1's right-hand side, Fcn0 + HG*dFdT with dFdT = +0.0 (see above); independent of H
 #pragma unroll
           for (int q = 0; q < SPT; q++) {
+            if constexpr (LINR) continue;      // (formed inside the loop below)
             if constexpr (METHOD != kRos3) k1[q] = autonomous ? fcn0[q] : fcn0[q] + Direction * 0.0;      // (Direction*H*Gamma(1))*dFdT: a zero of Direction's sign (Gamma(1) > 0 in all five)
             else if constexpr (OPT) k1[q] = autonomous ? fcn0[q] : fcn0[q] + 0.0;      // Autonomous: the HG*dFdT terms are not added at all (gas.f:1268)
             else k1[q] = fcn0[q] + 0.0;
@@ -2464,6 +2516,11 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
           int nconsecutive = 0;
           bool singular = true;
           while (singular) {
+            if constexpr (LINR) {      // K1's right-hand side with its HG*dFdT term: it follows H through ros_PrepareMatrix_x's halvings
+              const double hg = wave_uniform((Direction * Hget()) * kGamma1);
+#pragma unroll
+              for (int q = 0; q < SPT; q++) k1[q] = autonomous ? fcn0[q] : fcn0[q] + hg * dfdt[q];
+            }
             const double ghinv = wave_uniform(1.0 / (Direction * Hget() * kGamma1));
             singular = prepare(ghinv, k1);
             dump_matrix(NVAR);      // Ghimj = 1/(H*gamma) - Jac0
@@ -2528,6 +2585,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
 #pragma unroll
           for (int q = 0; q < SPT; q++) ynew[q] = y[q] + kRosA1 * k1[q];
           lap(6);
+          if constexpr (LINR) lin_stage(T, kRosAlpha<kRos3>.Alpha[1], dh);      // ros_Alpha(2) = gamma (Ros3_x); stage 3 reuses the value
           fun(ynew, fcn);
           lap(0);
           nfun += 1;
@@ -2535,7 +2593,8 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
             const double hc = wave_uniform(kRosC1 / dh);
 #pragma unroll
             for (int q = 0; q < SPT; q++) {
-              if constexpr (OPT) k2[q] = autonomous ? fcn[q] + hc * k1[q] : (fcn[q] + hc * k1[q]) + dh * 0.0;
+              if constexpr (LINR) k2[q] = autonomous ? fcn[q] + hc * k1[q] : (fcn[q] + hc * k1[q]) + wave_uniform(dh * kRosGamma2) * dfdt[q];      // (a declaration of HG in this block changed the other kernels' instructions)
+              else if constexpr (OPT) k2[q] = autonomous ? fcn[q] + hc * k1[q] : (fcn[q] + hc * k1[q]) + dh * 0.0;
               else k2[q] = (fcn[q] + hc * k1[q]) + dh * 0.0;      // + HG*dFdT with dFdT = +0.0: (dh*gamma2)*0.0, a zero of dh's sign (gamma2 > 0)
             }
           }
@@ -2548,7 +2607,8 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
             const double hc1 = wave_uniform(kRosC2 / dh), hc2 = wave_uniform(kRosC3 / dh);
 #pragma unroll
             for (int q = 0; q < SPT; q++) {
-              if constexpr (OPT) k3[q] = autonomous ? (fcn[q] + hc1 * k1[q]) + hc2 * k2[q] : ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;
+              if constexpr (LINR) k3[q] = autonomous ? (fcn[q] + hc1 * k1[q]) + hc2 * k2[q] : ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + wave_uniform(dh * kRosGamma3) * dfdt[q];
+              else if constexpr (OPT) k3[q] = autonomous ? (fcn[q] + hc1 * k1[q]) + hc2 * k2[q] : ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;
               else k3[q] = ((fcn[q] + hc1 * k1[q]) + hc2 * k2[q]) + dh * 0.0;      // (dh*gamma3)*0.0 likewise (gamma3 > 0)
             }
           }
@@ -2589,6 +2649,7 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
                 }
               }, std::integral_constant<int, 0>{}, I);
               lap(6);
+              if constexpr (LINR) lin_stage(T, kRosAlpha<METHOD>.Alpha[i], dh);
               fun(ynew, fcn);
               lap(0);
               nfun += 1;
@@ -2609,9 +2670,9 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
             }, std::integral_constant<int, 0>{}, I);
             constexpr double gi = kRosMethod<METHOD>.Gamma[i];
             if constexpr (gi != 0.0) {      // + HG*dFdT with dFdT = +0.0: a zero with the sign of Direction*H*Gamma(i); nothing where Gamma(i) = 0 or autonomous (gas.f:1268)
-              const double hg0 = wave_uniform((dh * gi) * 0.0);
+              const double hg0 = wave_uniform(LINR ? dh * gi : (dh * gi) * 0.0);      // (VARIANT 10: HG itself, its dFdT is not a zero)
 #pragma unroll
-              for (int q = 0; q < SPT; q++) ki[q] = autonomous ? ki[q] : ki[q] + hg0;
+              for (int q = 0; q < SPT; q++) ki[q] = autonomous ? ki[q] : ki[q] + (LINR ? hg0 * dfdt[q] : hg0);
             }
             lap(6);
             solve(ki, false);

@@ -125,6 +125,8 @@ hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_config
 //              trace unit of its mechanism
 //   VARIANT 9  the replay, METHOD = Ros3 only: the steps of a prescribed sequence, all accepted (kernel_args.hpp: replay_*); a.replay_n must be set.  No
 //              unit of its own: specialised in the trace unit of its mechanism
+//   VARIANT 10 a series with rate constants linear in time over each leg, any of the five methods (kernel_args.hpp: lin_rates); a.times, a.lin_rates and
+//              a.leg_rconst (the node stride) must be set.  No unit of its own: specialised in the method unit of its mechanism and method, Ros3 in the trace unit of its mechanism
 // One explicit specialisation per <mechanism, variant, method>, each in a translation unit of its own (ros_unit_kernel.hip).  lds_configured: per
 // device AND kernel.
 template <class MT, int NT, int VARIANT, int METHOD>

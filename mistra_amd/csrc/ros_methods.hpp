@@ -1,6 +1,7 @@
 // The five Rosenbrock methods of Rosenbrock_x (gas.f:1514-1895 | aer.f | tot.f) as compile-time tables: what the method kernels
 // (ros3_kernel.hip: ros3_integrate_kernel<MT, NT, 3, METHOD>) are compiled with and what mistra_chem_method_table hands to the host.
-// Values typed in as data from Ros2_x .. Rodas4_x; ros_Alpha is left out (FunTemplate_x ignores T).  Plain C++: host and device.
+// Values typed in as data from Ros2_x .. Rodas4_x; ros_Alpha stands in a table of its own (below): FunTemplate_x ignores T, only the kernels whose rate
+// constants are linear in time read it.  Plain C++: host and device.
 #pragma once
 
 namespace mistra {
@@ -80,6 +81,24 @@ constexpr RosMethodTable ros_method_table(int method) {
 
 template <int METHOD>
 inline constexpr RosMethodTable kRosMethod = ros_method_table(METHOD);
+
+// ros_Alpha of the same five routines: stage i evaluates the function at T + ros_Alpha(i)*Direction*H.  A table of its own, read by the kernels whose
+// rate constants depend on the time (ros3_kernel.hip: VARIANT 10) and by nothing else: RosMethodTable keeps the layout mistra_chem_method_table hands out.
+struct RosAlphaTable {
+  double Alpha[6];
+};
+constexpr RosAlphaTable ros_alpha_table(int method) {
+  switch (method) {
+    case kRos2: return RosAlphaTable{{0.0, 1.0}};
+    case kRos3: return RosAlphaTable{{0.0, 0.43586652150845899941601945119356e+00, 0.43586652150845899941601945119356e+00}};
+    case kRos4: return RosAlphaTable{{0.0, 0.1145640000000000e+01, 0.6552168638155900e+00, 0.6552168638155900e+00}};
+    case kRodas3: return RosAlphaTable{{0.0, 0.0, 1.0, 1.0}};
+    case kRodas4: return RosAlphaTable{{0.0, 0.386, 0.21, 0.63, 1.0, 1.0}};
+  }
+  return RosAlphaTable{{}};
+}
+template <int METHOD>
+inline constexpr RosAlphaTable kRosAlpha = ros_alpha_table(METHOD);
 
 // whether stage i + 1 (i >= 1) works on a function value formed in this step's stages 2 .. i + 1, not on Fcn0 (gas.f:1247-1262)
 constexpr bool ros_fresh_fcn(int method, int i) {

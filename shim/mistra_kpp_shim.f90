@@ -56,6 +56,11 @@
 !                                                            IERR, ISTAT)
 !     SUBROUTINE ROSENBROCK_BATCH_SERIES_RATES_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER,
 !                                                                  TEXIT, HEXIT, IERR, ISTAT)
+! The same with RATE CONSTANTS LINEAR IN TIME OVER EACH LEG (mistra_chem_rosenbrock_series_linrates_ex; INTEGRATION.md 4s): RNODES(NREACT,NCELL,NLEG+1), block l the
+! rate constants AT TIMES(l); inside leg l every function evaluation reads them at its own time and the stages add H*gamma*dFdT (IPAR(1) = 0).  FIX(NFIX,NCELL,NFIXLEG)
+! stays piecewise constant, NFIXLEG 1 or NLEG.  The printed lines are the series'.
+!     SUBROUTINE ROSENBROCK_BATCH_SERIES_LINRATES_g / _a / _t (NCELL, VAR, FIX, RNODES, NLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT,
+!                                                               IERR, ISTAT)
 !
 ! THE REACTION FLUX (mistra_chem_rosenbrock_flux_ex; INTEGRATION.md 4n): ROSENBROCK_BATCH_x / ROSENBROCK_BATCH_CELLS_x with one more result behind their
 ! argument lists, FLUX(NREACT,NCELL): every reaction's rate integrated over the call by the trapezoid rule on the accepted states.  Everything else is what
@@ -256,6 +261,17 @@ module mistra_chem_c_api
        integer(c_int32_t) :: ierr(*), stats(*)
        integer(c_int) :: rc
      end function mistra_chem_rosenbrock_series_rates_cells_ex
+     function mistra_chem_rosenbrock_series_linrates_ex(mech, ncell, var_in, fix, rconst_nodes, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, &
+          var_series, ierr, stats, t_h) bind(C, name="mistra_chem_rosenbrock_series_linrates_ex") result(rc)
+       import :: c_int, c_double, c_int32_t, c_ptr
+       integer(c_int), value :: mech, ncell, fix_legs, nleg, carry_h
+       type(c_ptr), value :: hstart
+       real(c_double) :: var_in(*), fix(*), rconst_nodes(*), var_series(*), t_h(*)
+       real(c_double), intent(in) :: times(*), atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_series_linrates_ex
      function mistra_chem_ops_ex(mech, ncell, var, fix, rconst, vdot, jvs, nshift, shift, fun_rhs, nrhs, rhs, x, ising) &
           bind(C, name="mistra_chem_ops_ex") result(rc)
        import :: c_int, c_double, c_ptr
@@ -561,9 +577,12 @@ contains
   ! written ros_ErrorMsg_x's lines (a refusal at T = the leg's start, H = 0).  The rows of zero pivots are not recorded for a series: no warning lines.
   ! NTOL present: ATOL / RTOL hold a row of NTOL entries per cell (ROSENBROCK_BATCH_SERIES_CELLS_x)
   ! NRCLEG and NFIXLEG present: RCONST and FIX hold that many blocks of NCELL cells, 1 or NLEG (ROSENBROCK_BATCH_SERIES_RATES_x / _RATES_CELLS_x)
-  subroutine rosenbrock_series(mech, sfx, NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL, NRCLEG, NFIXLEG)
+  ! LINEAR present (with NFIXLEG): RCONST holds the NLEG + 1 node blocks of rate constants linear in time over each leg (ROSENBROCK_BATCH_SERIES_LINRATES_x)
+  subroutine rosenbrock_series(mech, sfx, NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL, NRCLEG, NFIXLEG, &
+       LINEAR)
     integer, intent(in) :: mech, NCELL, NLEG
     integer, intent(in), optional :: NTOL, NRCLEG, NFIXLEG
+    logical, intent(in), optional :: LINEAR
     character(len=1), intent(in) :: sfx
     logical, intent(in) :: CARRY
     real(c_double) :: VAR(*), FIX(*), RCONST(*), VSER(*), TEXIT(NCELL, *), HEXIT(NCELL, *)
@@ -574,7 +593,10 @@ contains
     integer :: k, l
     if (NCELL <= 0) return
     allocate (th(3, NCELL, max(NLEG, 1)))
-    if (present(NRCLEG) .and. present(NFIXLEG)) then
+    if (present(LINEAR) .and. present(NFIXLEG)) then
+       if (mistra_chem_rosenbrock_series_linrates_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NFIXLEG, c_int), int(NLEG, c_int), TIMES, ATOL, RTOL, &
+            RPAR, IPAR, int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_SERIES_LINRATES_'//sfx)
+    else if (present(NRCLEG) .and. present(NFIXLEG)) then
        if (present(NTOL)) then
           if (mistra_chem_rosenbrock_series_rates_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NRCLEG, c_int), int(NFIXLEG, c_int), &
                int(NLEG, c_int), TIMES, ATOL, RTOL, int(NTOL, c_int), RPAR, IPAR, int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th) /= 0) &
@@ -1082,6 +1104,40 @@ subroutine ROSENBROCK_BATCH_SERIES_CELLS_t(NCELL, VAR, FIX, RCONST, NLEG, TIMES,
   integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
   call rosenbrock_series(2, 't', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL)
 end subroutine ROSENBROCK_BATCH_SERIES_CELLS_t
+
+! ---- the series with rate constants linear in time over each leg: RNODES(NREACT,NCELL,NLEG+1) at TIMES(1:NLEG+1), FIX(NFIX,NCELL,NFIXLEG), NFIXLEG 1 or NLEG
+subroutine ROSENBROCK_BATCH_SERIES_LINRATES_g(NCELL, VAR, FIX, RNODES, NLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NFIXLEG
+  logical :: CARRY
+  real(c_double) :: VAR(102, *), FIX(3, NCELL, *), RNODES(331, NCELL, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(102, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(0, 'g', NCELL, VAR, FIX, RNODES, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NFIXLEG=NFIXLEG, LINEAR=.true.)
+end subroutine ROSENBROCK_BATCH_SERIES_LINRATES_g
+
+subroutine ROSENBROCK_BATCH_SERIES_LINRATES_a(NCELL, VAR, FIX, RNODES, NLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NFIXLEG
+  logical :: CARRY
+  real(c_double) :: VAR(257, *), FIX(5, NCELL, *), RNODES(979, NCELL, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(257, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(1, 'a', NCELL, VAR, FIX, RNODES, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NFIXLEG=NFIXLEG, LINEAR=.true.)
+end subroutine ROSENBROCK_BATCH_SERIES_LINRATES_a
+
+subroutine ROSENBROCK_BATCH_SERIES_LINRATES_t(NCELL, VAR, FIX, RNODES, NLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NFIXLEG
+  logical :: CARRY
+  real(c_double) :: VAR(417, *), FIX(7, NCELL, *), RNODES(1627, NCELL, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(417, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(2, 't', NCELL, VAR, FIX, RNODES, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NFIXLEG=NFIXLEG, LINEAR=.true.)
+end subroutine ROSENBROCK_BATCH_SERIES_LINRATES_t
 
 ! ---- the series with rate constants and FIX of the leg's own: RCONST(NREACT,NCELL,NRCLEG), FIX(NFIX,NCELL,NFIXLEG), each count 1 or NLEG
 subroutine ROSENBROCK_BATCH_SERIES_RATES_g(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)

@@ -20,6 +20,9 @@
 !                                                      nleg, carry (0 | 1), ntol, nrcleg, nfixleg, TIMES(nleg + 1), VAR(NVAR, ncell), FIX(NFIX, ncell, nfixleg),
 !                                                      RCONST(NREACT, ncell, nrcleg).  ntol = 0: ONE call of ROSENBROCK_BATCH_SERIES_RATES_x; ntol = 1 or NVAR: ONE call of
 !                                                      ROSENBROCK_BATCH_SERIES_RATES_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin as for <ZG|ZA|ZT>
+!          shim_driver <MG|MA|MT> <in.bin> <out.bin>   the series with rate constants linear in time over each leg: in.bin as for <NG|NA|NT> with ntol = 0 and nrcleg =
+!                                                      nleg + 1, RCONST(NREACT, ncell, nleg + 1) the node blocks at TIMES.  ONE call of
+!                                                      ROSENBROCK_BATCH_SERIES_LINRATES_x; out.bin as for <ZG|ZA|ZT>
 !          shim_driver <WG|WA|WT> <in.bin> <out.bin>   Rosenbrock_x with the reaction flux: in.bin = IPAR(20), RPAR(20), ATOL(NVAR), RTOL(NVAR), TSTART, TEND, ncell, ntol, then
 !                                                      the cells as for <G|A|T>.  ntol = 0: ONE call of ROSENBROCK_BATCH_FLUX_x with the pair; ntol = 1 or NVAR: ONE call of
 !                                                      ROSENBROCK_BATCH_FLUX_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin = per cell VAR, TEXIT,
@@ -104,9 +107,16 @@ program shim_driver
      end select
   case ('N')
      select case (a1(2:2))
-     case ('G'); call run_series_rates(0, 102, 3, 331, trim(fin), trim(fout))
-     case ('A'); call run_series_rates(1, 257, 5, 979, trim(fin), trim(fout))
-     case ('T'); call run_series_rates(2, 417, 7, 1627, trim(fin), trim(fout))
+     case ('G'); call run_series_rates(0, 102, 3, 331, trim(fin), trim(fout), .false.)
+     case ('A'); call run_series_rates(1, 257, 5, 979, trim(fin), trim(fout), .false.)
+     case ('T'); call run_series_rates(2, 417, 7, 1627, trim(fin), trim(fout), .false.)
+     case default; stop 'mechanism must be G, A or T'
+     end select
+  case ('M')
+     select case (a1(2:2))
+     case ('G'); call run_series_rates(0, 102, 3, 331, trim(fin), trim(fout), .true.)
+     case ('A'); call run_series_rates(1, 257, 5, 979, trim(fin), trim(fout), .true.)
+     case ('T'); call run_series_rates(2, 417, 7, 1627, trim(fin), trim(fout), .true.)
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('W')
@@ -579,9 +589,10 @@ contains
     end do
     close (11); close (12)
   end subroutine run_series
-  subroutine run_series_rates(mech, NVAR, NFIX, NREACT, fin, fout)
+  subroutine run_series_rates(mech, NVAR, NFIX, NREACT, fin, fout, lin)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT
     character(len=*), intent(in) :: fin, fout
+    logical, intent(in) :: lin      ! <MG|MA|MT>: RCONST holds nrcleg = nleg + 1 node blocks, rate constants linear in time over each leg
     double precision :: ropt(40), tt(6)
     double precision, allocatable :: ATOL(:), RTOL(:), AROW(:, :), RROW(:, :), TIMES(:), VAR(:, :), FIX(:, :, :), RCONST(:, :, :), VSER(:, :, :), TEXIT(:, :), HEXIT(:, :)
     integer :: IPAR(20), n, nleg, ntol, nrc, nfx, i, l
@@ -609,7 +620,14 @@ contains
           RROW(:, i) = RTOL(1:ntol)
        end if
     end do
-    if (ntol == 0) then
+    if (lin) then
+       if (ntol /= 0 .or. nrc /= nleg + 1) stop 'the series with rate constants linear in time: ntol = 0 and nrcleg = nleg + 1'
+       select case (mech)
+       case (0); call ROSENBROCK_BATCH_SERIES_LINRATES_g(n, VAR, FIX, RCONST, nleg, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       case (1); call ROSENBROCK_BATCH_SERIES_LINRATES_a(n, VAR, FIX, RCONST, nleg, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       case (2); call ROSENBROCK_BATCH_SERIES_LINRATES_t(n, VAR, FIX, RCONST, nleg, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
+       end select
+    else if (ntol == 0) then
        select case (mech)
        case (0); call ROSENBROCK_BATCH_SERIES_RATES_g(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
        case (1); call ROSENBROCK_BATCH_SERIES_RATES_a(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
