@@ -276,8 +276,8 @@ int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double*
  * with the same arguments, d_hstart included.  A call that makes no accepted step returns zeros; so does a refusal (-1 .. -5, whole call or, in the cells
  * forms, per cell) in the rows it covers.  The options travel with the call (MISTRA_ROSENBROCK_CALLS_IN_FLIGHT blocks); the options in force, the
  * integrator policy and step reuse are not involved.  The _ex forms split the batch over the device slots and fail while a column step of the mechanism
- * is open.  A null flux fails with a text before a device is touched.  There is no series form, no trace form and no user slot: both user ids fail with
- * the slot's text. */
+ * is open.  A null flux fails with a text before a device is touched.  The series form is mistra_chem_rosenbrock_series_flux_ex / _device (below: one row
+ * per leg); there is no trace form and no user slot: both user ids fail with the slot's text. */
 int mistra_chem_rosenbrock_flux_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                                    const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
                                    int32_t* stats, double* t_h, double* flux /* [ncell][NREACT] */);
@@ -411,6 +411,43 @@ int mistra_chem_rosenbrock_series_linrates_cells_device(int mech, int ncell, con
                                                         const double* rpar, const int32_t* ipar,                                   /* host arrays */
                                                         double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                                         int carry_h, const double* d_hstart, void* hip_stream);
+
+/* A SERIES WITH THE REACTION FLUX OF EVERY LEG: a budget time series in one launch.  The series with rates above (rconst_legs and
+ * fix_legs each 1 or nleg; with both 1 the plain series) with one more output behind its arguments:
+ *     flux_series [nleg][ncell][NREACT]      block k, row c: EXACTLY what mistra_chem_rosenbrock_flux_device returns in flux[c] for the call that leg k is —
+ * from times[k] to times[k+1] on the state leg k-1 left, with leg k's rate constants and FIX, the first step the series gives the leg (carry_h / hstart as
+ * above), the flux entries' trapezoid on the leg's accepted states.  Nothing is carried from one leg's sum into the next: every leg starts at +0.0 and
+ * its first evaluation only records A_r(Y_0).  After IERR = -6 / -7 the leg's sum is closed at Texit with the leg's own rate constants, after -8 it is
+ * closed as it stands; the next leg starts afresh (a failed leg does not end the series).  A refusal gives +0.0 rows in every leg it covers: -1 .. -5 on
+ * the whole call (nothing is launched; the device forms zero the rows in stream order) and -5 per cell in the cells forms.
+ * var_series, ierr, stats and t_h / d_texit_hexit are bit for bit those of mistra_chem_rosenbrock_series_rates_ex / _device (the cells forms likewise)
+ * with the same arguments.  flux_series may not alias any other array of the call.
+ * A null flux_series fails with its own text before a device is touched, as do the series' own refusals; a user slot fails with the slot's text ("has no
+ * reaction-flux entries").  There is no form with rate constants linear in time (mistra_chem_rosenbrock_series_linrates_* has no flux), no trace form
+ * and no dense-output form.  The _ex forms stage the rows per device slot and split the batch over the slots as the series does. */
+int mistra_chem_rosenbrock_series_flux_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                          int rconst_legs, int fix_legs,
+                                          int nleg, const double* times, const double* atol, const double* rtol,
+                                          const double* rpar, const int32_t* ipar, int carry_h, const double* hstart /* [ncell] or NULL */,
+                                          double* var_series, int32_t* ierr, int32_t* stats, double* t_h,
+                                          double* flux_series /* [nleg][ncell][NREACT] */);
+int mistra_chem_rosenbrock_series_flux_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                              int rconst_legs, int fix_legs,
+                                              int nleg, const double* times, const double* atol, const double* rtol,
+                                              const double* rpar, const int32_t* ipar,                                            /* host arrays */
+                                              double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                              int carry_h, const double* d_hstart, void* hip_stream, double* d_flux_series);      /* in stream order */
+int mistra_chem_rosenbrock_series_flux_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst,
+                                                int rconst_legs, int fix_legs,
+                                                int nleg, const double* times, const double* atol, const double* rtol, int ntol,   /* rows per cell */
+                                                const double* rpar, const int32_t* ipar, int carry_h, const double* hstart,
+                                                double* var_series, int32_t* ierr, int32_t* stats, double* t_h, double* flux_series);
+int mistra_chem_rosenbrock_series_flux_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                                    int rconst_legs, int fix_legs,
+                                                    int nleg, const double* times, const double* d_atol, const double* d_rtol, int ntol,  /* device arrays */
+                                                    const double* rpar, const int32_t* ipar,                                       /* host arrays */
+                                                    double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                                    int carry_h, const double* d_hstart, void* hip_stream, double* d_flux_series);
 
 /* DENSE OUTPUT: the state at ns sample times INSIDE one call of Rosenbrock_x, without changing the call (a series, above, is nleg calls).
  * Everything mistra_chem_rosenbrock_ex / _device (the cells forms: _cells_ex / _cells_device) return with the same arguments, d_hstart included, bit for

@@ -142,6 +142,8 @@ def lib():
                 getattr(L, "mistra_chem_rosenbrock_series_rates_" + form).argtypes = at[:5] + [C.c_int, C.c_int] + at[5:]
                 if hasattr(L, "mistra_chem_rosenbrock_series_linrates_" + form):      # ... with fix_legs behind rconst_nodes
                     getattr(L, "mistra_chem_rosenbrock_series_linrates_" + form).argtypes = at[:5] + [C.c_int] + at[5:]
+                if hasattr(L, "mistra_chem_rosenbrock_series_flux_" + form):          # ... the series with rates' list with flux_series behind it
+                    getattr(L, "mistra_chem_rosenbrock_series_flux_" + form).argtypes = at[:5] + [C.c_int, C.c_int] + at[5:] + [vp if "device" in form else _dp]
         if hasattr(L, "mistra_chem_rosenbrock_flux_ex"):
             L.mistra_chem_rosenbrock_flux_ex.argtypes = L.mistra_chem_rosenbrock_ex.argtypes + [_dp]
             L.mistra_chem_rosenbrock_flux_device.argtypes = L.mistra_chem_rosenbrock_device.argtypes + [vp]
@@ -974,9 +976,33 @@ def rosenbrock_series_linrates(mech, var, fix, rconst_nodes, times, ipar=None, r
     return _series_rates(mech, var, fix, rconst_nodes, times, ipar, rpar, atol, rtol, hstart, carry_h, out, True)
 
 
-def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, lin):
-    """rosenbrock_series_rates (lin false) and rosenbrock_series_linrates (lin true: rconst holds the nleg + 1 node blocks, and the entries take no count
-    of them)"""
+# rosenbrock_series_rates' result with the reaction flux of every leg: flux [nleg, ncell, NREACT]
+SeriesFluxResult = namedtuple("SeriesFluxResult", "var ierr stats t_h flux")
+
+
+def rosenbrock_series_flux(mech, var, fix, rconst, times, ipar=None, rpar=None, atol=None, rtol=None, hstart=None, carry_h=False, out=None):
+    """rosenbrock_series_rates() run by the kernels that also integrate every reaction's rate over each leg: a budget time series in one launch
+    (include/mistra_chem.h: mistra_chem_rosenbrock_series_flux_ex / _device).  fix and rconst as rosenbrock_series_rates
+    takes them: one block [ncell, .] shared by all legs, or one per leg [nleg, ncell, .], each on its own -> SeriesFluxResult: that function's result,
+    bit for bit, plus flux [nleg, ncell, NREACT], block k exactly what rosenbrock_flux() returns for the call that leg k is (from times[k] to times[k+1]
+    on the state leg k-1 left, with leg k's rows and the first step the series gives the leg).  No leg's sum is carried into the next; a refused call,
+    and in the cells form a refused cell, has rows of zeros in every leg.  numpy arrays go to the host entry, torch CUDA tensors to the device entry on
+    torch's current stream; a 2-D atol / rtol selects the cells form.  Not for a user mechanism slot, and there is no form with rate constants linear
+    in time."""
+    return _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, False, True)
+
+
+def rosenbrock_series_flux_cells(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart=None, carry_h=False, out=None):
+    """rosenbrock_series_flux() with tolerances per cell, atol / rtol [ncell, 1] or [ncell, NVAR] as rosenbrock_cells takes them; a cell refused with -5
+    has a flux row of zeros in every leg, its neighbours are not affected."""
+    if getattr(atol, "ndim", 0) != 2 or getattr(rtol, "ndim", 0) != 2:
+        raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
+    return _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, False, True)
+
+
+def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, lin, flux=False):
+    """rosenbrock_series_rates (lin false), rosenbrock_series_linrates (lin true: rconst holds the nleg + 1 node blocks, and the entries take no count
+    of them) and rosenbrock_series_flux (flux true: the entries take flux_series behind the series with rates' arguments)"""
     mid, name = _mech_id(mech)
     nvar, nfix, nreact, _ = DIMS[name]
     cells = atol is not None and rtol is not None and getattr(atol, "ndim", 0) == 2 and getattr(rtol, "ndim", 0) == 2
@@ -998,7 +1024,7 @@ def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart,
             raise MistraChemError("rconst_nodes: a 3-D [nleg + 1, ncell, NREACT] array expected, block k the rate constants at times[k] (nleg = %d)" % nleg)
         return rows + 1
 
-    entry = "mistra_chem_rosenbrock_series_%s_" % ("linrates" if lin else "rates")
+    entry = "mistra_chem_rosenbrock_series_%s_" % ("linrates" if lin else "flux" if flux else "rates")
     if _is_torch(var):
         import torch
         if not var.is_cuda:
@@ -1029,11 +1055,16 @@ def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart,
         stream = torch.cuda.current_stream(var.device).cuda_stream
         tail = (out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), int(bool(carry_h)), None if hstart is None else hstart.data_ptr(),
                 C.c_void_p(stream))
+        if flux:
+            fl = torch.empty((rows, ncell, nreact), dtype=torch.float64, device=var.device)
+            tail += (fl.data_ptr(),)
         head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr()) + (() if lin else (nlr,)) + (nlf, nleg, tp)
         if cells:
             _check(getattr(L, entry + "cells_device")(*head, atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]), *popts, *tail))
         else:
             _check(getattr(L, entry + "device")(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
+        if flux:
+            return SeriesFluxResult(out.view(rows, ncell, nvar), ierr, stats, th, fl)
         return SeriesResult(out.view(rows, ncell, nvar), ierr, stats, th)
     v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
     ncell = v.shape[0]
@@ -1052,6 +1083,9 @@ def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart,
     head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp)) + (() if lin else (nlr,)) + (nlf, nleg, tp)
     tail = (int(bool(carry_h)), None if hs is None else hs.ctypes.data_as(_dp), res.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip),
             stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp))
+    if flux:
+        fl = np.zeros((rows, ncell, nreact))
+        tail += (fl.ctypes.data_as(_dp),)
     # (the arguments are checked by the library before it looks for a device: no init() in front of them)
     if cells:
         a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
@@ -1060,6 +1094,8 @@ def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart,
         _check(getattr(L, entry + "cells_ex")(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *popts, *tail))
     else:
         _check(getattr(L, entry + "ex")(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
+    if flux:
+        return SeriesFluxResult(res, ierr, stats, th, fl)
     return SeriesResult(res, ierr, stats, th)
 
 

@@ -66,8 +66,9 @@ using LaunchFn = hipError_t (*)(const KernelArgs&, hipStream_t, bool*);
 // The kernels of ros_unit_kernel.hip, [kernel VARIANT 3 .. 6][IPAR(4) resolved, ros_methods.hpp]: 3 the method kernels (Ros2, Ros4, Rodas3, Rodas4), 4 the
 // step-control trace (Ros3), 5 the series and 6 the flux kernels (all five methods), 7 the dense-output kernels (all five methods; they live in the series
 // units), 8 the operator kernels and 9 the replay kernels (Ros3's slot; they live in the trace units), 10 the series kernels with rate constants linear in
-// time (all five methods; they live in the method units, Ros3's in the trace units).  nullptr: not built.
-constexpr int kVariants = 11, kMethods = 6;
+// time and 11 the series kernels with the reaction flux of every leg (all five methods; both live in the method units, Ros3's in the trace units).
+// nullptr: not built.
+constexpr int kVariants = 12, kMethods = 6;
 struct UnitTable {
   LaunchFn fn[kVariants][kMethods] = {};
 };
@@ -79,7 +80,8 @@ template <class MT, int NT, int... METHOD>
 constexpr UnitTable unit_table(std::integer_sequence<int, METHOD...>) {
   UnitTable t;
   (..., (add_unit<MT, NT, 3, METHOD + 1>(t), add_unit<MT, NT, 4, METHOD + 1>(t), add_unit<MT, NT, 5, METHOD + 1>(t), add_unit<MT, NT, 6, METHOD + 1>(t),
-        add_unit<MT, NT, 7, METHOD + 1>(t), add_unit<MT, NT, 8, METHOD + 1>(t), add_unit<MT, NT, 9, METHOD + 1>(t), add_unit<MT, NT, 10, METHOD + 1>(t)));
+        add_unit<MT, NT, 7, METHOD + 1>(t), add_unit<MT, NT, 8, METHOD + 1>(t), add_unit<MT, NT, 9, METHOD + 1>(t), add_unit<MT, NT, 10, METHOD + 1>(t),
+        add_unit<MT, NT, 11, METHOD + 1>(t)));
   return t;
 }
 static_assert(kRos2 == 1 && kRodas4 == 5, "IPAR(4) resolved: 1 .. 5");
@@ -702,6 +704,7 @@ struct MechState {
   RosCallRing series_ring;
   DevBuf<double> s_ser_var, s_ser_th;      // staging of mistra_chem_rosenbrock_series_ex: the legs' blocks of this slot's cells (grow-only)
   DevBuf<int32_t> s_ser_ierr, s_ser_stats;
+  DevBuf<double> s_ser_flux;               // ... and of mistra_chem_rosenbrock_series_flux_ex: the legs' flux rows of this slot's cells
   // the step memory of the batched driver (mistra_chem_set_step_reuse): per model layer k = 1..step_n the last accepted step size of the layer's previous
   // column step of this mechanism, 0 = none.  step_n = 0: forgotten — the next column step under reuse sizes it to its n and zeroes it on the drive stream
   DevBuf<double> step_mem;
@@ -738,7 +741,7 @@ struct MechState {
     opt.release(); opt_max_steps = 0;
     pol_opt.release(); pol_method = 0; pol_factor = pol_floor = 0.0;
     call_opt.release(); call_ring.release(); series_ring.release();
-    s_ser_var.release(); s_ser_th.release(); s_ser_ierr.release(); s_ser_stats.release();
+    s_ser_var.release(); s_ser_th.release(); s_ser_ierr.release(); s_ser_stats.release(); s_ser_flux.release();
     step_mem.release(); step_n = 0;
     s_hst.release(); s_tol.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
@@ -1188,7 +1191,7 @@ RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const dou
   return c;
 }
 
-// The kernel of a call: the VARIANT from the arguments (dense output, else a series, else the flux, else the trace, else a method other than Ros3, else the product unit's
+// The kernel of a call: the VARIANT from the arguments (dense output, else a series — with linear rates, with the flux of every leg or plain —, else the flux, else the trace, else a method other than Ros3, else the product unit's
 // kernels), one guard, one slot of the mechanism's table.  A method other than Ros3 never runs as a quiet Ros3: what is not built is refused.
 int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, int method = kRos3) {
   static const struct { const char *user, *refusal; } kText[kVariants] = {
@@ -1199,9 +1202,10 @@ int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, in
       {"reaction-flux entries", "no flux kernel for this Rosenbrock method"},
       {"dense-output entries", "no dense-output kernel for this Rosenbrock method"},
       {}, {},      // (8, the operators: launch_ops, not an integration; 9, the replay: launch_replay)
-      {"series of Rosenbrock_x calls", "no series kernel with rate constants linear in time for this Rosenbrock method"}};
+      {"series of Rosenbrock_x calls", "no series kernel with rate constants linear in time for this Rosenbrock method"},
+      {"reaction-flux entries", "no series kernel with the reaction flux for this Rosenbrock method"}};
   const MechDesc& M = kMech[mech];
-  const int variant = a.dense_nout ? 7 : a.times ? (a.lin_rates ? 10 : 5) : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
+  const int variant = a.dense_nout ? 7 : a.times ? (a.lin_rates ? 10 : a.flux ? 11 : 5) : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
   hipError_t e = hipErrorInvalidValue;
   if (variant) {
     if (M.user) return fail_user_slot(mech, kText[variant].user);
@@ -1242,6 +1246,7 @@ KernelArgs make_args(const MechState& S, int ncell, const double* var_in, const 
   a.ops_shift_stride = 0; a.ops_fun_rhs = 0; a.ops_nrhs = 0; a.ops_x_block = a.ops_rhs_block = 0;
   a.replay_h = nullptr; a.replay_n = nullptr; a.replay_h_stride = 0; a.replay_cap = 0; a.replay_err = nullptr;      // (the replay entries set them)
   a.lin_rates = 0;      // (the series entries with rate constants linear in time set it)
+  a.leg_flux = 0;       // (the series entries with the reaction flux set it)
   a.opt = S.opt.p;      // set: the options instantiation of the kernel runs (ros3_kernel.hip: launch_ros3), also where the values equal INTEGRATE_x's
   return a;
 }
@@ -3280,11 +3285,15 @@ int mistra_chem_rosenbrock_dense_cells_device(int mech, int ncell, const double*
 // ---- series: nleg calls of Rosenbrock_x over times[0 .. nleg] in one launch, the state on chip from leg to leg (kernel VARIANT 5).  One path for the
 //      four entries, as above: the shared-pair forms pass ct = nullptr.  The options in force, the integrator policy and step reuse are not read; the
 //      zero-pivot rows are not recorded (mistra_chem_singular_rows keeps describing the last call that is not a series).
+//      flux_series (the entries with the reaction flux of every leg, below): null = the series as it is; set = kernel VARIANT 11 writes leg k's flux rows
+//      at flux_series + k*ncell*NREACT, staged per device slot by the _ex forms as var_series is.
 
 // what every series entry checks before anything touches a device, each refusal by its text
 // (rconst_legs, fix_legs: the blocks of rconst and fix, 1 = shared by all legs or nleg = the leg's own; the entries without them pass 1, 1)
-static int check_series(int mech, int nleg, const double* times, const void* var_series, int rconst_legs = 1, int fix_legs = 1) {
-  if (int rc = builtin_only(mech, "series of Rosenbrock_x calls")) return rc;
+// (sflux: the entries with the reaction flux of every leg, which a user slot refuses as it refuses the flux entries; flux_series is theirs)
+static int check_series(int mech, int nleg, const double* times, const void* var_series, int rconst_legs = 1, int fix_legs = 1, bool sflux = false,
+                        const void* flux_series = nullptr) {
+  if (int rc = builtin_only(mech, sflux ? "reaction-flux entries" : "series of Rosenbrock_x calls")) return rc;
   if (nleg < 1 || nleg > MISTRA_SERIES_MAX_LEGS)
     return fail("series: nleg = " + std::to_string(nleg) + ": a series has 1 .. MISTRA_SERIES_MAX_LEGS = " + std::to_string(MISTRA_SERIES_MAX_LEGS) + " legs");
   if (rconst_legs != 1 && rconst_legs != nleg)
@@ -3293,6 +3302,7 @@ static int check_series(int mech, int nleg, const double* times, const void* var
     return fail("series: fix_legs = " + std::to_string(fix_legs) + ": fix has 1 block (shared by all legs) or nleg = " + std::to_string(nleg) + " blocks");
   if (!times) return fail("series: null times pointer (times: [nleg + 1], a host array)");
   if (!var_series) return fail("series: null var_series pointer (var_series: [nleg][ncell][NVAR])");
+  if (sflux && !flux_series) return fail("series: null flux_series pointer (flux_series: [nleg][ncell][NREACT])");
   for (int k = 0; k <= nleg; k++)
     if (!std::isfinite(times[k])) return fail("series: times[" + std::to_string(k) + "] is not finite");
   for (int k = 1; k <= nleg; k++) {
@@ -3312,7 +3322,7 @@ static int check_nodes(const double* rconst_nodes) {
 // one device slot's share of mistra_chem_rosenbrock_series_ex: cells [start, start + ncell) of the caller's batch of `total` cells
 static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, size_t total, const double* var_in, const double* fix, const double* rconst,
                           int rconst_legs, int fix_legs, int nleg, const double* times, const RosCall& call, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
-                          int32_t* stats, double* t_h, bool lin) {
+                          int32_t* stats, double* t_h, bool lin, double* flux_series) {
   HIP_TRY(hipSetDevice(D.id));
   MechState& S = D.mech[mech];
   if (lin) rconst_legs = nleg + 1;      // the node blocks: one more than there are legs
@@ -3326,6 +3336,7 @@ static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, siz
   HIP_TRY(S.s_ser_ierr.reserve(nl * nc));
   HIP_TRY(S.s_ser_stats.reserve(nl * nc * 8));
   if (t_h) HIP_TRY(S.s_ser_th.reserve(nl * nc * 3));
+  if (flux_series) HIP_TRY(S.s_ser_flux.reserve(nl * nc * nr));
   HIP_TRY(S.call_opt.reserve(nb + nl + 1));
   HIP_TRY(hipMemcpy(S.s_var.p, var_in + start * nv, nc * nv * sizeof(double), hipMemcpyHostToDevice));
   // the slot's cells of every block of fix and rconst, [legs][total][.] of the caller's into [legs][nc][.] here: one 2-D copy each (one block: one row)
@@ -3341,6 +3352,7 @@ static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, siz
   a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
   a.leg_rconst = rconst_legs > 1 ? (int64_t)(nc * nr) : 0; a.leg_fix = fix_legs > 1 ? (int64_t)(nc * nf) : 0;      // the block's stride, not the caller's
   a.lin_rates = lin ? 1 : 0;
+  if (flux_series) { a.flux = S.s_ser_flux.p; a.leg_flux = (int64_t)(nc * nr); }      // selects the series kernels with the flux (launch)
   if (int rc = upload_cell_tol(S, call, start, nc, &a)) return rc;
   if (hstart) {
     HIP_TRY(S.s_hst.reserve(nc));
@@ -3354,6 +3366,8 @@ static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, siz
   if (ierr) HIP_TRY(hipMemcpy2D(ierr + start, total * sizeof(int32_t), S.s_ser_ierr.p, nc * sizeof(int32_t), nc * sizeof(int32_t), nl, hipMemcpyDeviceToHost));
   if (stats)
     HIP_TRY(hipMemcpy2D(stats + start * 8, total * 8 * sizeof(int32_t), S.s_ser_stats.p, nc * 8 * sizeof(int32_t), nc * 8 * sizeof(int32_t), nl, hipMemcpyDeviceToHost));
+  if (flux_series)
+    HIP_TRY(hipMemcpy2D(flux_series + start * nr, total * nr * sizeof(double), S.s_ser_flux.p, nc * nr * sizeof(double), nc * nr * sizeof(double), nl, hipMemcpyDeviceToHost));
   if (t_h) {
     std::vector<double> h(nl * nc * 3);
     HIP_TRY(hipMemcpy(h.data(), S.s_ser_th.p, nl * nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
@@ -3368,8 +3382,10 @@ static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, siz
 
 static int series_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs, int fix_legs, int nleg,
                        const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int carry_h,
-                       const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h, const CellTol* ct, bool lin = false) {
-  if (int rc = check_series(mech, nleg, times, var_series, rconst_legs, fix_legs)) return rc;
+                       const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h, const CellTol* ct, bool lin = false,
+                       bool sflux = false, double* flux_series = nullptr) {
+  if (int rc = check_series(mech, nleg, times, var_series, rconst_legs, fix_legs, sflux, flux_series)) return rc;
+  if (!sflux) flux_series = nullptr;      // (the flux of every leg is the entries' own that ask for it)
   if (lin)
     if (int rc = check_nodes(rconst)) return rc;
   if (ct)
@@ -3389,20 +3405,23 @@ static int series_host(int mech, int ncell, const double* var_in, const double* 
     if (ierr) std::fill(ierr, ierr + nl * nc, (int32_t)call.ierr);
     if (stats) std::fill(stats, stats + nl * nc * 8, 0);
     if (t_h) std::fill(t_h, t_h + nl * nc * 3, 0.0);
+    if (flux_series) std::fill(flux_series, flux_series + nl * nc * (size_t)kMech[mech].dims.nreact, 0.0);
     return 0;
   }
   // var_in may alias one leg's block of var_series: every slot has its inputs on the device before any result comes back (below: all uploads of a
   // slot precede its downloads, and slots own disjoint cells)
   return on_cell_blocks(ncell, [=, &call](DeviceState& D, size_t start, int count) {
-    return series_host_on(D, mech, count, start, nc, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h, lin);
+    return series_host_on(D, mech, count, start, nc, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h, lin,
+                          flux_series);
   });
 }
 
 static int series_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int rconst_legs, int fix_legs,
                             int nleg, const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                             double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart,
-                            void* hip_stream, const CellTol* ct, bool lin = false) {
-  if (int rc = check_series(mech, nleg, times, d_var_series, rconst_legs, fix_legs)) return rc;
+                            void* hip_stream, const CellTol* ct, bool lin = false, bool sflux = false, double* d_flux_series = nullptr) {
+  if (int rc = check_series(mech, nleg, times, d_var_series, rconst_legs, fix_legs, sflux, d_flux_series)) return rc;
+  if (!sflux) d_flux_series = nullptr;
   if (lin)
     if (int rc = check_nodes(d_rconst)) return rc;
   if (ct)
@@ -3424,6 +3443,7 @@ static int series_on_device(int mech, int ncell, const double* d_var_in, const d
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_ierr), call.ierr, nl * nc, st));
     HIP_TRY(hipMemsetAsync(d_stats, 0, nl * nc * 8 * sizeof(int32_t), st));
     if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nl * nc * 2 * sizeof(double), st));
+    if (d_flux_series) HIP_TRY(hipMemsetAsync(d_flux_series, 0, nl * nc * (size_t)kMech[mech].dims.nreact * sizeof(double), st));
     return 0;
   }
   const size_t nb = call.block.size();
@@ -3443,6 +3463,7 @@ static int series_on_device(int mech, int ncell, const double* d_var_in, const d
   a.leg_rconst = rconst_legs > 1 || lin ? (int64_t)(nc * (size_t)kMech[mech].dims.nreact) : 0;      // the caller's arrays, read at the head of every leg
   a.lin_rates = lin ? 1 : 0;      // (... of every evaluation: the node blocks, nleg + 1 of them)
   a.leg_fix = fix_legs > 1 ? (int64_t)(nc * (size_t)kMech[mech].dims.nfix) : 0;
+  if (d_flux_series) { a.flux = d_flux_series; a.leg_flux = (int64_t)(nc * (size_t)kMech[mech].dims.nreact); }      // selects the series kernels with the flux (launch)
   if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
   const int rc = launch(*t.D, mech, a, st, call.method);
   R.mark(i, st);
@@ -3547,6 +3568,43 @@ int mistra_chem_rosenbrock_series_linrates_cells_device(int mech, int ncell, con
   const CellTol ct{d_atol, d_rtol, ntol};
   return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst_nodes, 1, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr, d_stats,
                           d_texit_hexit, carry_h, d_hstart, hip_stream, &ct, true);
+}
+
+// ---- the series with the reaction flux of every leg (kernel VARIANT 11): the series with rates' path and arguments, flux_series
+//      [nleg][ncell][NREACT] behind them, leg k's rows what mistra_chem_rosenbrock_flux_device returns for the call that leg k is
+int mistra_chem_rosenbrock_series_flux_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs, int fix_legs,
+                                          int nleg, const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
+                                          int carry_h, const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h,
+                                          double* flux_series) {
+  return series_host(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
+                     t_h, nullptr, false, true, flux_series);
+}
+
+int mistra_chem_rosenbrock_series_flux_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs,
+                                                int fix_legs, int nleg, const double* times, const double* atol, const double* rtol, int ntol,
+                                                const double* rpar, const int32_t* ipar, int carry_h, const double* hstart, double* var_series,
+                                                int32_t* ierr, int32_t* stats, double* t_h, double* flux_series) {
+  const CellTol ct{atol, rtol, ntol};
+  return series_host(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
+                     t_h, &ct, false, true, flux_series);
+}
+
+int mistra_chem_rosenbrock_series_flux_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int rconst_legs,
+                                              int fix_legs, int nleg, const double* times, const double* atol, const double* rtol, const double* rpar,
+                                              const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
+                                              int carry_h, const double* d_hstart, void* hip_stream, double* d_flux_series) {
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats,
+                          d_texit_hexit, carry_h, d_hstart, hip_stream, nullptr, false, true, d_flux_series);
+}
+
+int mistra_chem_rosenbrock_series_flux_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
+                                                    int rconst_legs, int fix_legs, int nleg, const double* times, const double* d_atol,
+                                                    const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar, double* d_var_series,
+                                                    int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart,
+                                                    void* hip_stream, double* d_flux_series) {
+  const CellTol ct{d_atol, d_rtol, ntol};
+  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr,
+                          d_stats, d_texit_hexit, carry_h, d_hstart, hip_stream, &ct, false, true, d_flux_series);
 }
 
 int mistra_chem_cell_atol_device(int mech, int ncell, const double* d_var, double factor, double floor, double* d_atol, void* hip_stream) {

@@ -117,8 +117,8 @@ struct KernelArgs {
   int32_t carry_h;             // /= 0: a later leg's first step is the previous leg's Hexit of the cell where that is > 0, else the options' Hstart
   int64_t leg_var, leg_ierr, leg_stats, leg_th, leg_h;
   // the reaction flux (kernel VARIANT 6, ros_unit_kernel.hip; mistra_chem_rosenbrock_flux_ex / _device and their cells forms): [ncell][NREACT], every
-  // reaction's rate integrated over the call, written once per cell when it leaves (a cell refused with -5: +0.0).  Read by the flux kernels only; null
-  // everywhere else (capi.cpp: make_args).
+  // reaction's rate integrated over the call, written once per cell when it leaves (a cell refused with -5: +0.0).  Read by the flux kernels and by the
+  // series kernels with the flux of every leg (VARIANT 11: [nleg][ncell][NREACT], leg_flux below); null everywhere else (capi.cpp: make_args).
   double* flux;
   // dense output (kernel VARIANT 7, in the series units of ros_unit_kernel.hip; mistra_chem_rosenbrock_dense_ex / _device and their cells forms): the state
   // at dense_ns sample times inside the one call from tin to tout, by the cubic Hermite interpolant between the accepted states.  The
@@ -166,6 +166,11 @@ struct KernelArgs {
   // apart, block k the rate constants at times[k]; leg k reads blocks k and k + 1.  /= 0 selects those kernels (capi.cpp: launch), which read the series'
   // arguments and nothing else of their own; 0 everywhere else (capi.cpp: make_args).  (At the end of the block: every other argument keeps its offset.)
   int32_t lin_rates;
+  // a series with the reaction flux of every leg (kernel VARIANT 11, beside VARIANT 10 in the method and trace units of ros_unit_kernel.hip;
+  // mistra_chem_rosenbrock_series_flux_ex / _device and their cells forms): leg k writes its [ncell][NREACT] rows at flux + k*leg_flux
+  // (a stride in elements, ncell*NREACT of the launch).  With a.times and a.flux both set, /= 0 selects those kernels (capi.cpp: launch), which read the
+  // series' arguments, flux and this; 0 everywhere else (capi.cpp: make_args).  (At the end of the block: every other argument keeps its offset.)
+  int64_t leg_flux;
 };
 
 }  // namespace mistra

@@ -1475,12 +1475,17 @@ __device__ __attribute__((noinline)) f64x4 dense_lu(int lane) {
 // constants AT a.times[k] (a.leg_rconst: the node stride).  Every Fun_x / Jac_SP_x reads R(tau) at its own time — T at the head of a step, T +
 // ros_Alpha(i)*Direction*H in a stage that evaluates anew — and the step adds HG*dFdT with dFdT = Fun_x(Y, FIX, dR/dt), one more Fun_x per step, where
 // the others add their zero.  Everything it adds sits behind `if constexpr (LINR)`; what a series does it does as SERIES.
+// 11 = a series with the reaction flux of every leg (instantiated beside variant 10, in the method units and, for Ros3, the trace units of
+// ros_unit_kernel.hip; mistra_chem_rosenbrock_series_flux_ex / _device): variant 5 (with a.leg_rconst / a.leg_fix as there) of any of the five methods that
+// also does per leg what variant 6 does per call — the flux state lives inside the legs' loop, starts afresh with every leg and is closed with the leg's own
+// rate constants in front of the leg's results — and leaves leg k's [NREACT] row of a cell at a.flux + k*a.leg_flux.  It is SERIES
+// and FLUX at once; what only the combination needs sits behind `if constexpr (SFLUX)`.
 // METHOD (variant 3 only): the Rosenbrock method, IPAR(4) of Rosenbrock_x (ros_methods.hpp).  Ros3 is the kernel as it was; Ros2, Ros4, Rodas3
 // and Rodas4 (the method kernels, instantiated by ros_unit_kernel.hip in translation units of their own) differ in the stage loop, in the
 // number of stage vectors a thread keeps and in the constants — every such difference sits behind `if constexpr (METHOD == kRos3) ... else`.
 template <class MT, int NT, int VARIANT, int METHOD = kRos3>
 __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(const KernelArgs a) {
-  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, LINR = VARIANT == 10, SERIES = VARIANT == 5 || LINR, FLUX = VARIANT == 6, DENSE = VARIANT == 7, REPLAY = VARIANT == 9, OPT = VARIANT == 3 || TRACE || SERIES || FLUX || DENSE || REPLAY;
+  constexpr bool PROF = VARIANT == 1, DUMP = VARIANT == 2, TRACE = VARIANT == 4, LINR = VARIANT == 10, SFLUX = VARIANT == 11, SERIES = VARIANT == 5 || LINR || SFLUX, FLUX = VARIANT == 6 || SFLUX, DENSE = VARIANT == 7, REPLAY = VARIANT == 9, OPT = VARIANT == 3 || TRACE || SERIES || FLUX || DENSE || REPLAY;
   constexpr bool OPS = VARIANT == 8;
   static_assert(!REPLAY || METHOD == kRos3, "the replay is a Ros3 instantiation (ros_unit_kernel.hip), as is the trace that supplies its sequence");
   static_assert(!OPS || METHOD == kRos3, "the operators are Ros3 instantiations (ros_unit_kernel.hip): no method is involved");
@@ -1648,6 +1653,13 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
                 GM_(a.texit_hexit)[(int64_t)k * a.leg_th + (int64_t)cell * 2 + 1] = 0.0;
               }
               if (a.h_last) GM_(a.h_last)[(int64_t)k * a.leg_h + cell] = 0.0;
+            }
+            if constexpr (SFLUX) {      // no step was made in any leg: the cell's row of every leg is +0.0
+#pragma unroll
+              for (int q = 0; q < RPT; q++) {
+                const int r = q * NT + t;
+                if (r < NREACT) GM_(a.flux)[(int64_t)k * a.leg_flux + (int64_t)cell * NREACT + r] = 0.0;
+              }
             }
           }
           return;
@@ -2347,6 +2359,11 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
           if (hx > 0.0) hstart0 = hx;
           lds_barrier();      // every wave has read the cell before thread 0 resets it
         }
+        // VARIANT 11: the previous leg ended on flux_close, which reads other threads' species out of X, and this leg's first Fun_x stores Y into X.  The
+        // a.carry_h pair above and the a.leg_fix barrier below lie between the two; where the call has neither, this one does.
+        if constexpr (SFLUX) {
+          if (!a.carry_h && a.leg_fix == 0) lds_barrier();
+        }
         // RCONST and FIX of the leg's own (a.leg_rconst / a.leg_fix /= 0, uniform over the call): what Update_RCONST_x left in front of this call of
         // Rosenbrock_x.  The per-use fetch out of global memory needs nothing here: load_rct forms the leg's base itself.
         if (!LINR && a.leg_rconst != 0) {
@@ -2783,7 +2800,11 @@ __global__ __launch_bounds__(NT, MT::WAVES_PER_SIMD) void ros3_integrate_kernel(
 #pragma unroll
       for (int q = 0; q < RPT; q++) {
         const int r = q * NT + t;
-        if (r < NREACT) GM_(a.flux)[(size_t)cell * NREACT + r] = fl_sum[q];
+        if constexpr (SFLUX) {      // the leg's row
+          if (r < NREACT) GM_(a.flux)[(int64_t)leg * a.leg_flux + (int64_t)cell * NREACT + r] = fl_sum[q];
+        } else {
+          if (r < NREACT) GM_(a.flux)[(size_t)cell * NREACT + r] = fl_sum[q];
+        }
       }
     }
     // VARIANT 7: the last accepted step is still open on a normal return and on -6 / -7 (on -8 the failing step's own Fun_x has closed it): one more Fun_x

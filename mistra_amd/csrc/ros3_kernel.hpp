@@ -127,6 +127,8 @@ hipError_t launch_ros3(const KernelArgs& a, hipStream_t stream, bool* lds_config
 //              unit of its own: specialised in the trace unit of its mechanism
 //   VARIANT 10 a series with rate constants linear in time over each leg, any of the five methods (kernel_args.hpp: lin_rates); a.times, a.lin_rates and
 //              a.leg_rconst (the node stride) must be set.  No unit of its own: specialised in the method unit of its mechanism and method, Ros3 in the trace unit of its mechanism
+//   VARIANT 11 a series with the reaction flux of every leg, any of the five methods (kernel_args.hpp: leg_flux); a.times, a.flux and a.leg_flux must be
+//              set, a.lin_rates not.  No unit of its own: specialised beside VARIANT 10
 // One explicit specialisation per <mechanism, variant, method>, each in a translation unit of its own (ros_unit_kernel.hip).  lds_configured: per
 // device AND kernel.
 template <class MT, int NT, int VARIANT, int METHOD>

@@ -1,7 +1,8 @@
 // One kernel per translation unit: ros3_integrate_kernel<MT, NT, VARIANT, METHOD> for one of the options variants the product unit does not hold
 // (ros3_kernel.hip: 3 a method kernel, 4 the step-control trace, 5 a series, 6 the reaction flux) on gas, aer or tot, with its launcher; a series unit
 // holds the dense-output kernel (VARIANT 7) of its mechanism and method as well, a trace unit the operator kernel (VARIANT 8) and the replay kernel (VARIANT 9) of its mechanism; a method unit
-// and (for Ros3) a trace unit the series kernel with rate constants linear in time (VARIANT 10) of its mechanism and method (below).  Compiled
+// and (for Ros3) a trace unit the series kernel with rate constants linear in time (VARIANT 10) and the series kernel with the reaction flux (VARIANT 11)
+// of its mechanism and method (below).  Compiled
 // once per unit of mistra_amd/build.py: VARIANT_UNITS.  Units of their own because the non-inlined device functions the kernels share (vm_run,
 // gsum_run*, tail_solve, scale_run, dense_lu, dense_finish) are compiled once per unit, under the register budget of all kernels in it: the product
 // kernels' unit (ros3_kernel.hip) must compile as it does without these, and each of these as it does without the others.
@@ -129,6 +130,25 @@ hipError_t launch_ros_unit<UnitMT, kUnitNT, 10, MISTRA_UNIT_METHOD>(const Kernel
   auto kern = ros3_integrate_kernel<UnitMT, kUnitNT, 10, MISTRA_UNIT_METHOD>;
   if (!a.opt) return hipErrorInvalidValue;
   if (!a.times || a.nleg < 1 || !a.lin_rates || a.leg_rconst <= 0 || !a.rconst || a.flux || a.dense_nout) return hipErrorInvalidValue;
+  if (!*lds_configured) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    *lds_configured = true;
+  }
+  if (a.ncell <= 0) return hipSuccess;
+  hipLaunchKernelGGL(kern, dim3((unsigned)a.ncell), dim3(kUnitNT), lds_bytes, stream, a);
+  return hipGetLastError();
+}
+
+// The series with the reaction flux of every leg (VARIANT 11) likewise, in the same units for the same reasons: the series kernel and the flux kernel of a
+// mechanism and method in one.  Its own argument guard and its own lds_configured flag (capi.cpp: DeviceState, [mechanism][11][method]).  (Behind every
+// other specialisation: the kernels in front of it keep their place in the unit.)
+template <>
+hipError_t launch_ros_unit<UnitMT, kUnitNT, 11, MISTRA_UNIT_METHOD>(const KernelArgs& a, hipStream_t stream, bool* lds_configured) {
+  constexpr size_t lds_bytes = LdsLayout<UnitMT, kUnitNT>::TOTAL * sizeof(double);
+  auto kern = ros3_integrate_kernel<UnitMT, kUnitNT, 11, MISTRA_UNIT_METHOD>;
+  if (!a.opt) return hipErrorInvalidValue;
+  if (!a.times || a.nleg < 1 || !a.flux || a.leg_flux <= 0 || a.lin_rates || a.dense_nout) return hipErrorInvalidValue;
   if (!*lds_configured) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;

@@ -61,6 +61,13 @@
 ! stays piecewise constant, NFIXLEG 1 or NLEG.  The printed lines are the series'.
 !     SUBROUTINE ROSENBROCK_BATCH_SERIES_LINRATES_g / _a / _t (NCELL, VAR, FIX, RNODES, NLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT,
 !                                                               IERR, ISTAT)
+! The series with rates WITH THE REACTION FLUX OF EVERY LEG (mistra_chem_rosenbrock_series_flux_ex; INTEGRATION.md 4t): FLUX(NREACT,NCELL,NLEG) behind the argument
+! lists of ROSENBROCK_BATCH_SERIES_RATES_x / _RATES_CELLS_x, FLUX(:,k,l) what ROSENBROCK_BATCH_FLUX_x returns for the call that leg l of cell k is; no leg's sum is
+! carried into the next, a refused leg's column is zero.  Everything else, the printed lines included, is what those entries return.
+!     SUBROUTINE ROSENBROCK_BATCH_SERIES_FLUX_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT,
+!                                                           IERR, ISTAT, FLUX)
+!     SUBROUTINE ROSENBROCK_BATCH_SERIES_FLUX_CELLS_g / _a / _t (NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER,
+!                                                                 TEXIT, HEXIT, IERR, ISTAT, FLUX)
 !
 ! THE REACTION FLUX (mistra_chem_rosenbrock_flux_ex; INTEGRATION.md 4n): ROSENBROCK_BATCH_x / ROSENBROCK_BATCH_CELLS_x with one more result behind their
 ! argument lists, FLUX(NREACT,NCELL): every reaction's rate integrated over the call by the trapezoid rule on the accepted states.  Everything else is what
@@ -272,6 +279,28 @@ module mistra_chem_c_api
        integer(c_int32_t) :: ierr(*), stats(*)
        integer(c_int) :: rc
      end function mistra_chem_rosenbrock_series_linrates_ex
+     function mistra_chem_rosenbrock_series_flux_ex(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, &
+          var_series, ierr, stats, t_h, flux_series) bind(C, name="mistra_chem_rosenbrock_series_flux_ex") result(rc)
+       import :: c_int, c_double, c_int32_t, c_ptr
+       integer(c_int), value :: mech, ncell, rconst_legs, fix_legs, nleg, carry_h
+       type(c_ptr), value :: hstart
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_series(*), t_h(*), flux_series(*)
+       real(c_double), intent(in) :: times(*), atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_series_flux_ex
+     function mistra_chem_rosenbrock_series_flux_cells_ex(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, ntol, rpar, ipar, &
+          carry_h, hstart, var_series, ierr, stats, t_h, flux_series) bind(C, name="mistra_chem_rosenbrock_series_flux_cells_ex") result(rc)
+       import :: c_int, c_double, c_int32_t, c_ptr
+       integer(c_int), value :: mech, ncell, rconst_legs, fix_legs, nleg, ntol, carry_h
+       type(c_ptr), value :: hstart
+       real(c_double) :: var_in(*), fix(*), rconst(*), var_series(*), t_h(*), flux_series(*)
+       real(c_double), intent(in) :: times(*), atol(*), rtol(*), rpar(20)
+       integer(c_int32_t), intent(in) :: ipar(20)
+       integer(c_int32_t) :: ierr(*), stats(*)
+       integer(c_int) :: rc
+     end function mistra_chem_rosenbrock_series_flux_cells_ex
      function mistra_chem_ops_ex(mech, ncell, var, fix, rconst, vdot, jvs, nshift, shift, fun_rhs, nrhs, rhs, x, ising) &
           bind(C, name="mistra_chem_ops_ex") result(rc)
        import :: c_int, c_double, c_ptr
@@ -578,11 +607,13 @@ contains
   ! NTOL present: ATOL / RTOL hold a row of NTOL entries per cell (ROSENBROCK_BATCH_SERIES_CELLS_x)
   ! NRCLEG and NFIXLEG present: RCONST and FIX hold that many blocks of NCELL cells, 1 or NLEG (ROSENBROCK_BATCH_SERIES_RATES_x / _RATES_CELLS_x)
   ! LINEAR present (with NFIXLEG): RCONST holds the NLEG + 1 node blocks of rate constants linear in time over each leg (ROSENBROCK_BATCH_SERIES_LINRATES_x)
+  ! FLUX present (with NRCLEG and NFIXLEG): the reaction flux of every leg, FLUX(NREACT,NCELL,NLEG) (ROSENBROCK_BATCH_SERIES_FLUX_x / _FLUX_CELLS_x)
   subroutine rosenbrock_series(mech, sfx, NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NTOL, NRCLEG, NFIXLEG, &
-       LINEAR)
+       LINEAR, FLUX)
     integer, intent(in) :: mech, NCELL, NLEG
     integer, intent(in), optional :: NTOL, NRCLEG, NFIXLEG
     logical, intent(in), optional :: LINEAR
+    real(c_double), optional :: FLUX(*)
     character(len=1), intent(in) :: sfx
     logical, intent(in) :: CARRY
     real(c_double) :: VAR(*), FIX(*), RCONST(*), VSER(*), TEXIT(NCELL, *), HEXIT(NCELL, *)
@@ -596,6 +627,16 @@ contains
     if (present(LINEAR) .and. present(NFIXLEG)) then
        if (mistra_chem_rosenbrock_series_linrates_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NFIXLEG, c_int), int(NLEG, c_int), TIMES, ATOL, RTOL, &
             RPAR, IPAR, int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th) /= 0) call mistra_chem_fail('ROSENBROCK_BATCH_SERIES_LINRATES_'//sfx)
+    else if (present(FLUX) .and. present(NRCLEG) .and. present(NFIXLEG)) then
+       if (present(NTOL)) then
+          if (mistra_chem_rosenbrock_series_flux_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NRCLEG, c_int), int(NFIXLEG, c_int), &
+               int(NLEG, c_int), TIMES, ATOL, RTOL, int(NTOL, c_int), RPAR, IPAR, int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th, FLUX) /= 0) &
+               call mistra_chem_fail('ROSENBROCK_BATCH_SERIES_FLUX_CELLS_'//sfx)
+       else
+          if (mistra_chem_rosenbrock_series_flux_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NRCLEG, c_int), int(NFIXLEG, c_int), &
+               int(NLEG, c_int), TIMES, ATOL, RTOL, RPAR, IPAR, int(merge(1, 0, CARRY), c_int), c_null_ptr, VSER, IERR, ISTAT, th, FLUX) /= 0) &
+               call mistra_chem_fail('ROSENBROCK_BATCH_SERIES_FLUX_'//sfx)
+       end if
     else if (present(NRCLEG) .and. present(NFIXLEG)) then
        if (present(NTOL)) then
           if (mistra_chem_rosenbrock_series_rates_cells_ex(int(mech, c_int), int(NCELL, c_int), VAR, FIX, RCONST, int(NRCLEG, c_int), int(NFIXLEG, c_int), &
@@ -1138,6 +1179,94 @@ subroutine ROSENBROCK_BATCH_SERIES_LINRATES_t(NCELL, VAR, FIX, RNODES, NLEG, NFI
   integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
   call rosenbrock_series(2, 't', NCELL, VAR, FIX, RNODES, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, NFIXLEG=NFIXLEG, LINEAR=.true.)
 end subroutine ROSENBROCK_BATCH_SERIES_LINRATES_t
+
+! ---- the series with rates with the reaction flux of every leg: FLUX(NREACT,NCELL,NLEG) behind the argument lists of ROSENBROCK_BATCH_SERIES_RATES_x / _RATES_CELLS_x
+subroutine ROSENBROCK_BATCH_SERIES_FLUX_g(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, &
+     IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG
+  logical :: CARRY
+  real(c_double) :: VAR(102, *), FIX(3, NCELL, *), RCONST(331, NCELL, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(102, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  real(c_double) :: FLUX(331, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(0, 'g', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, &
+       NRCLEG=NRCLEG, NFIXLEG=NFIXLEG, FLUX=FLUX)
+end subroutine ROSENBROCK_BATCH_SERIES_FLUX_g
+
+subroutine ROSENBROCK_BATCH_SERIES_FLUX_CELLS_g(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, &
+     IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG, NTOL
+  logical :: CARRY
+  real(c_double) :: VAR(102, *), FIX(3, NCELL, *), RCONST(331, NCELL, *), TIMES(*), ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), VSER(102, NCELL, *), TEXIT(NCELL, *), &
+       HEXIT(NCELL, *)
+  real(c_double) :: FLUX(331, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(0, 'g', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, &
+       NTOL=NTOL, NRCLEG=NRCLEG, NFIXLEG=NFIXLEG, FLUX=FLUX)
+end subroutine ROSENBROCK_BATCH_SERIES_FLUX_CELLS_g
+
+subroutine ROSENBROCK_BATCH_SERIES_FLUX_a(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, &
+     IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG
+  logical :: CARRY
+  real(c_double) :: VAR(257, *), FIX(5, NCELL, *), RCONST(979, NCELL, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(257, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  real(c_double) :: FLUX(979, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(1, 'a', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, &
+       NRCLEG=NRCLEG, NFIXLEG=NFIXLEG, FLUX=FLUX)
+end subroutine ROSENBROCK_BATCH_SERIES_FLUX_a
+
+subroutine ROSENBROCK_BATCH_SERIES_FLUX_CELLS_a(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, &
+     IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG, NTOL
+  logical :: CARRY
+  real(c_double) :: VAR(257, *), FIX(5, NCELL, *), RCONST(979, NCELL, *), TIMES(*), ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), VSER(257, NCELL, *), TEXIT(NCELL, *), &
+       HEXIT(NCELL, *)
+  real(c_double) :: FLUX(979, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(1, 'a', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, &
+       NTOL=NTOL, NRCLEG=NRCLEG, NFIXLEG=NFIXLEG, FLUX=FLUX)
+end subroutine ROSENBROCK_BATCH_SERIES_FLUX_CELLS_a
+
+subroutine ROSENBROCK_BATCH_SERIES_FLUX_t(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, &
+     IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG
+  logical :: CARRY
+  real(c_double) :: VAR(417, *), FIX(7, NCELL, *), RCONST(1627, NCELL, *), TIMES(*), ATOL(*), RTOL(*), RPAR(20), VSER(417, NCELL, *), TEXIT(NCELL, *), HEXIT(NCELL, *)
+  real(c_double) :: FLUX(1627, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(2, 't', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, &
+       NRCLEG=NRCLEG, NFIXLEG=NFIXLEG, FLUX=FLUX)
+end subroutine ROSENBROCK_BATCH_SERIES_FLUX_t
+
+subroutine ROSENBROCK_BATCH_SERIES_FLUX_CELLS_t(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, NTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, &
+     IERR, ISTAT, FLUX)
+  use iso_c_binding
+  use mistra_chem_c_api
+  implicit none
+  integer :: NCELL, NLEG, NRCLEG, NFIXLEG, NTOL
+  logical :: CARRY
+  real(c_double) :: VAR(417, *), FIX(7, NCELL, *), RCONST(1627, NCELL, *), TIMES(*), ATOL(NTOL, *), RTOL(NTOL, *), RPAR(20), VSER(417, NCELL, *), TEXIT(NCELL, *), &
+       HEXIT(NCELL, *)
+  real(c_double) :: FLUX(1627, NCELL, *)
+  integer(c_int32_t) :: IPAR(20), IERR(NCELL, *), ISTAT(8, NCELL, *)
+  call rosenbrock_series(2, 't', NCELL, VAR, FIX, RCONST, NLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT, &
+       NTOL=NTOL, NRCLEG=NRCLEG, NFIXLEG=NFIXLEG, FLUX=FLUX)
+end subroutine ROSENBROCK_BATCH_SERIES_FLUX_CELLS_t
 
 ! ---- the series with rate constants and FIX of the leg's own: RCONST(NREACT,NCELL,NRCLEG), FIX(NFIX,NCELL,NFIXLEG), each count 1 or NLEG
 subroutine ROSENBROCK_BATCH_SERIES_RATES_g(NCELL, VAR, FIX, RCONST, NLEG, NRCLEG, NFIXLEG, TIMES, ATOL, RTOL, RPAR, IPAR, CARRY, VSER, TEXIT, HEXIT, IERR, ISTAT)

@@ -23,6 +23,9 @@
 !          shim_driver <MG|MA|MT> <in.bin> <out.bin>   the series with rate constants linear in time over each leg: in.bin as for <NG|NA|NT> with ntol = 0 and nrcleg =
 !                                                      nleg + 1, RCONST(NREACT, ncell, nleg + 1) the node blocks at TIMES.  ONE call of
 !                                                      ROSENBROCK_BATCH_SERIES_LINRATES_x; out.bin as for <ZG|ZA|ZT>
+!          shim_driver <BG|BA|BT> <in.bin> <out.bin>   the series with rates with the reaction flux of every leg: in.bin as for <NG|NA|NT>.  ntol = 0: ONE call of
+!                                                      ROSENBROCK_BATCH_SERIES_FLUX_x; ntol = 1 or NVAR: ONE call of ROSENBROCK_BATCH_SERIES_FLUX_CELLS_x.  out.bin as for
+!                                                      <ZG|ZA|ZT> with FLUX(NREACT) of the leg and cell behind every record
 !          shim_driver <WG|WA|WT> <in.bin> <out.bin>   Rosenbrock_x with the reaction flux: in.bin = IPAR(20), RPAR(20), ATOL(NVAR), RTOL(NVAR), TSTART, TEND, ncell, ntol, then
 !                                                      the cells as for <G|A|T>.  ntol = 0: ONE call of ROSENBROCK_BATCH_FLUX_x with the pair; ntol = 1 or NVAR: ONE call of
 !                                                      ROSENBROCK_BATCH_FLUX_CELLS_x, every cell's row the first ntol entries of the pair.  out.bin = per cell VAR, TEXIT,
@@ -107,16 +110,23 @@ program shim_driver
      end select
   case ('N')
      select case (a1(2:2))
-     case ('G'); call run_series_rates(0, 102, 3, 331, trim(fin), trim(fout), .false.)
-     case ('A'); call run_series_rates(1, 257, 5, 979, trim(fin), trim(fout), .false.)
-     case ('T'); call run_series_rates(2, 417, 7, 1627, trim(fin), trim(fout), .false.)
+     case ('G'); call run_series_rates(0, 102, 3, 331, trim(fin), trim(fout), .false., .false.)
+     case ('A'); call run_series_rates(1, 257, 5, 979, trim(fin), trim(fout), .false., .false.)
+     case ('T'); call run_series_rates(2, 417, 7, 1627, trim(fin), trim(fout), .false., .false.)
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('M')
      select case (a1(2:2))
-     case ('G'); call run_series_rates(0, 102, 3, 331, trim(fin), trim(fout), .true.)
-     case ('A'); call run_series_rates(1, 257, 5, 979, trim(fin), trim(fout), .true.)
-     case ('T'); call run_series_rates(2, 417, 7, 1627, trim(fin), trim(fout), .true.)
+     case ('G'); call run_series_rates(0, 102, 3, 331, trim(fin), trim(fout), .true., .false.)
+     case ('A'); call run_series_rates(1, 257, 5, 979, trim(fin), trim(fout), .true., .false.)
+     case ('T'); call run_series_rates(2, 417, 7, 1627, trim(fin), trim(fout), .true., .false.)
+     case default; stop 'mechanism must be G, A or T'
+     end select
+  case ('B')
+     select case (a1(2:2))
+     case ('G'); call run_series_rates(0, 102, 3, 331, trim(fin), trim(fout), .false., .true.)
+     case ('A'); call run_series_rates(1, 257, 5, 979, trim(fin), trim(fout), .false., .true.)
+     case ('T'); call run_series_rates(2, 417, 7, 1627, trim(fin), trim(fout), .false., .true.)
      case default; stop 'mechanism must be G, A or T'
      end select
   case ('W')
@@ -589,10 +599,12 @@ contains
     end do
     close (11); close (12)
   end subroutine run_series
-  subroutine run_series_rates(mech, NVAR, NFIX, NREACT, fin, fout, lin)
+  subroutine run_series_rates(mech, NVAR, NFIX, NREACT, fin, fout, lin, flx)
     integer, intent(in) :: mech, NVAR, NFIX, NREACT
     character(len=*), intent(in) :: fin, fout
     logical, intent(in) :: lin      ! <MG|MA|MT>: RCONST holds nrcleg = nleg + 1 node blocks, rate constants linear in time over each leg
+    logical, intent(in) :: flx      ! <BG|BA|BT>: the reaction flux of every leg too
+    double precision, allocatable :: FLUX(:, :, :)
     double precision :: ropt(40), tt(6)
     double precision, allocatable :: ATOL(:), RTOL(:), AROW(:, :), RROW(:, :), TIMES(:), VAR(:, :), FIX(:, :, :), RCONST(:, :, :), VSER(:, :, :), TEXIT(:, :), HEXIT(:, :)
     integer :: IPAR(20), n, nleg, ntol, nrc, nfx, i, l
@@ -620,7 +632,28 @@ contains
           RROW(:, i) = RTOL(1:ntol)
        end if
     end do
-    if (lin) then
+    if (flx) then
+       allocate (FLUX(NREACT, n, nleg))
+       if (ntol == 0) then
+          select case (mech)
+          case (0); call ROSENBROCK_BATCH_SERIES_FLUX_g(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT, &
+               FLUX)
+          case (1); call ROSENBROCK_BATCH_SERIES_FLUX_a(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT, &
+               FLUX)
+          case (2); call ROSENBROCK_BATCH_SERIES_FLUX_t(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT, &
+               FLUX)
+          end select
+       else
+          select case (mech)
+          case (0); call ROSENBROCK_BATCH_SERIES_FLUX_CELLS_g(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, AROW, RROW, ntol, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, &
+               IERR, ISTAT, FLUX)
+          case (1); call ROSENBROCK_BATCH_SERIES_FLUX_CELLS_a(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, AROW, RROW, ntol, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, &
+               IERR, ISTAT, FLUX)
+          case (2); call ROSENBROCK_BATCH_SERIES_FLUX_CELLS_t(n, VAR, FIX, RCONST, nleg, nrc, nfx, TIMES, AROW, RROW, ntol, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, &
+               IERR, ISTAT, FLUX)
+          end select
+       end if
+    else if (lin) then
        if (ntol /= 0 .or. nrc /= nleg + 1) stop 'the series with rate constants linear in time: ntol = 0 and nrcleg = nleg + 1'
        select case (mech)
        case (0); call ROSENBROCK_BATCH_SERIES_LINRATES_g(n, VAR, FIX, RCONST, nleg, nfx, TIMES, ATOL, RTOL, ropt(21:40), IPAR, carry, VSER, TEXIT, HEXIT, IERR, ISTAT)
@@ -646,6 +679,7 @@ contains
     do l = 1, nleg
        do i = 1, n
           write (12) VSER(:, i, l), TEXIT(i, l), HEXIT(i, l), dble(IERR(i, l)), dble(ISTAT(:, i, l))
+          if (flx) write (12) FLUX(:, i, l)
        end do
     end do
     close (11); close (12)

@@ -10,7 +10,12 @@ for bit first.
     python tools/bench_series.py --rates            every leg with rate constants and FIX of its own (chem.rosenbrock_series_rates): leg k's rate
                                                     constants are the workload's times 1 + 0.02*k, FIX a copy per leg; the sequence passes leg k's rows
     python tools/bench_series.py --against LIB      the plain series of this tree's library against the plain series of another build of the library
-                                                    (a second copy of mistra_amd/chem.py bound to LIB, in the same process), taken in turn"""
+                                                    (a second copy of mistra_amd/chem.py bound to LIB, in the same process), taken in turn
+    python tools/bench_series.py --flux             the series with the reaction flux of every leg (chem.rosenbrock_series_flux), the legs'
+                                                    rows as for --rates: ONE call against the `--legs` queued calls of chem.rosenbrock_flux it replaces, and
+                                                    against the series-with-rates call without the flux.  The flux rows of the two flux sides and the end
+                                                    states of all three are compared bit for bit first.  With --against LIB the two baselines are the other
+                                                    build's (a parent build: what the call replaces there)"""
 import argparse
 import importlib.util
 import os
@@ -33,6 +38,67 @@ def other_build(path):
     return mod
 
 
+def main_flux(a, chem, other, dev):
+    """--flux: one series-flux call | the queued flux calls it replaces | the series with rates without the flux"""
+    import torch
+    from mistra_amd import workload as W
+    base = other if other is not None else chem
+    times = np.linspace(0.0, 10.0, a.legs + 1)
+    print("%d cells, Ros3 at INTEGRATE_x's options, %d legs of %g s, rate constants and FIX of the leg's own, with the reaction flux of every leg; "
+          "%d repeats behind one warm-up; ms: median [min .. max]%s" %
+          (a.cells, a.legs, 10.0 / a.legs, a.repeats, "; the two baselines run the library given with --against" if other is not None else ""))
+    for mech in a.mechs:
+        V, F, K = W.make_batch(mech, 0, a.cells, dev)
+        scale = torch.tensor(1.0 + 0.02 * np.arange(a.legs), device=dev).view(-1, 1, 1)
+        LK, LF = (K.unsqueeze(0) * scale).contiguous(), F.unsqueeze(0).repeat(a.legs, 1, 1).contiguous()
+
+        def series_flux():
+            r = chem.rosenbrock_series_flux(mech, V, LF, LK, times)
+            return r.var[-1], r.flux
+
+        def flux_calls():
+            y, rows = V, []
+            for k in range(a.legs):
+                r = base.rosenbrock_flux(mech, y, LF[k], LK[k], float(times[k]), float(times[k + 1]))
+                y = r[0].var
+                rows.append(r[2])
+            return y, rows
+
+        def series_rates():
+            return base.rosenbrock_series_rates(mech, V, LF, LK, times).var[-1], None
+
+        def timed(f):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            y = f()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1), 1.0e3 * (time.perf_counter() - t0), y
+
+        sides = (("series_flux", series_flux), ("flux_calls", flux_calls), ("series_rates", series_rates))
+        warm = {name: timed(f)[2] for name, f in sides}
+        same_y = all(warm[n][0].cpu().numpy().tobytes() == warm["series_flux"][0].cpu().numpy().tobytes() for n in warm)
+        same_f = torch.stack(warm["flux_calls"][1]).cpu().numpy().tobytes() == warm["series_flux"][1].cpu().numpy().tobytes()
+        rows = {name: [] for name, _ in sides}
+        for _ in range(a.repeats):
+            for name, f in sides:
+                rows[name].append(timed(f)[:2])
+        fmt = lambda x: "%9.3f [%9.3f .. %9.3f]" % (float(np.median(x)), min(x), max(x))
+        print("%s: end states of the three sides %s; flux rows of all legs, series against queued calls, %s" %
+              (mech, "identical bit for bit" if same_y else "DIFFER", "identical bit for bit" if same_f else "DIFFER"))
+        med = {}
+        for name, _ in sides:
+            ev, wall = np.array([r[0] for r in rows[name]]), np.array([r[1] for r in rows[name]])
+            med[name] = (np.median(ev), np.median(wall), (ev.max() - ev.min()) / np.median(ev), (wall.max() - wall.min()) / np.median(wall))
+            print("  %-12s stream %s   wall %s" % (name, fmt(ev), fmt(wall)))
+        for name in ("flux_calls", "series_rates"):
+            print("  series_flux / %s: stream %.4f, wall %.4f (medians); %s's own spread (max - min) / median: stream %.4f, wall %.4f" %
+                  (name, med["series_flux"][0] / med[name][0], med["series_flux"][1] / med[name][1], name, med[name][2], med[name][3]))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--cells", type=int, default=4096)
@@ -41,6 +107,7 @@ def main(argv=None):
     ap.add_argument("--mechs", nargs="+", default=["gas", "aer", "tot"])
     ap.add_argument("--rates", action="store_true")
     ap.add_argument("--against", metavar="LIB")
+    ap.add_argument("--flux", action="store_true")
     a = ap.parse_args(argv)
     import torch
     from mistra_amd import chem
@@ -51,6 +118,8 @@ def main(argv=None):
     if a.against:
         other = other_build(a.against)
         other.init(0)
+    if a.flux:
+        return main_flux(a, chem, other, dev)
     times = np.linspace(0.0, 10.0, a.legs + 1)
     print("%d cells, Ros3 at INTEGRATE_x's options, %d legs of %g s%s; %d repeats behind one warm-up; ms: median [min .. max]" %
           (a.cells, a.legs, 10.0 / a.legs, ", rate constants and FIX of the leg's own" if a.rates else "", a.repeats))

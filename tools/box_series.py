@@ -9,7 +9,12 @@ the largest species of the first cell are printed per leg.  Night and day cells 
     ... --cpu          the Python restatement called leg by leg (tests/ros_series_rates_py.py) instead of the GPU
     ... --linear       the same dawn with rate constants LINEAR IN TIME over each leg: legs + 1 node blocks at w = k / legs, ONE call of
                        chem.rosenbrock_series_linrates; FIX stays the staircase's.  With --compare: the staircase of the run without --linear beside it, the
-                       distance of the two states per leg and the step counts of both.  With --cpu: tests/ros_linrates_py.py's restatement"""
+                       distance of the two states per leg and the step counts of both.  With --cpu: tests/ros_linrates_py.py's restatement
+    ... --budget SPECIES[,SPECIES...] [--top N]
+                       the staircase run as ONE call of chem.rosenbrock_series_flux, and per leg and species (0-based, cell 0) the
+                       budget of the leg: the N reactions (1-based, KPP's numbering) that produced and destroyed most of it, S(i,r) * flux[k][r] with S =
+                       mechtab.load(mech).stoich(), the gross turnover and the net change (what the trapezoid gives: Y(t_k+1) - Y(t_k) up to its
+                       accuracy).  With --cpu: tests/ros_series_flux_py.py's restatement"""
 import argparse
 import os
 import sys
@@ -66,6 +71,55 @@ def run_cpu(mech, V, LF, LK, times):
     return np.stack([c[0] for c in cells], axis=1), np.stack([c[1] for c in cells], axis=1), np.stack([c[2] for c in cells], axis=1)
 
 
+def run_cpu_flux(mech, V, LF, LK, times):
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import ros_options_py as R
+    import ros_series_flux_py as SF
+    import ros_series_py as RS
+    from mistra_amd import mechtab
+    from oracle.oracle import Oracle
+    o, diag = Oracle(mech), mechtab.load(mech).diag
+    ipar, rpar, atol, rtol = R.base_options(mech)
+    s = RS.Series(ipar, rpar, atol, rtol, times, False)
+    cells = [SF.chain_flux(o, diag, V[c], s, LF[:, c], LK[:, c]) for c in range(V.shape[0])]
+    return tuple(np.stack([c[i] for c in cells], axis=1) for i in (0, 1, 2, 5))
+
+
+def main_budget(a, V, LF, LK, times):
+    """--budget: the staircase with the reaction flux of every leg, one launch; the budget of the species asked for, per leg"""
+    from mistra_amd import mechtab
+    species = [int(x) for x in a.budget.split(",") if x != ""]
+    S = mechtab.load(a.mech).stoich()
+    if not species or min(species) < 0 or max(species) >= S.shape[0]:
+        raise SystemExit("--budget: species are 0-based indices below NVAR = %d" % S.shape[0])
+    print("%s: %d cell(s), %d legs of %g s, night -> day rows blended per leg, with the reaction flux of every leg; %s" %
+          (a.mech, V.shape[0], a.legs, a.dt, "CPU restatement, leg by leg" if a.cpu else "one launch (chem.rosenbrock_series_flux)"))
+    if a.cpu:
+        var, ierr, stats, flux = run_cpu_flux(a.mech, V, LF, LK, times)
+    else:
+        import torch
+        from mistra_amd import chem
+        dev = torch.device("cuda", 0)
+        chem.init(0)
+        res = chem.rosenbrock_series_flux(a.mech, *(torch.tensor(x, device=dev) for x in (V, LF, LK)), times)
+        torch.cuda.synchronize()
+        var, ierr, stats, flux = (x.cpu().numpy() for x in (res.var, res.ierr, res.stats, res.flux))
+    report(a, V, times, var, ierr, stats)
+    print("cell 0: budget of the leg, S(i,r) * flux[leg][r] in the state's units; reactions 1-based")
+    for k in range(a.legs):
+        for i in species:
+            term = S[i] * flux[k, 0]
+            prod, dest = term[term > 0.0].sum(), term[term < 0.0].sum()
+            print("budget leg %d species %d | production %.9e destruction %.9e turnover %.9e net %.9e | Y(t_k+1) - Y(t_k) = %.9e" %
+                  (k, i, prod, dest, prod - dest, prod + dest, var[k, 0, i] - (V[0, i] if k == 0 else var[k - 1, 0, i])))
+            order = np.argsort(-term)
+            for r in [r for r in order[:a.top] if term[r] > 0.0]:
+                print("  + reaction %d %.9e" % (r + 1, term[r]))
+            for r in [r for r in order[::-1][:a.top] if term[r] < 0.0]:
+                print("  - reaction %d %.9e" % (r + 1, term[r]))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("mech", choices=("gas", "aer", "tot"))
@@ -76,9 +130,15 @@ def main(argv=None):
     ap.add_argument("--compare", action="store_true")
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--linear", action="store_true")
+    ap.add_argument("--budget", default=None, metavar="SPECIES[,SPECIES...]")
+    ap.add_argument("--top", type=int, default=3)
     a = ap.parse_args(argv)
     V, LF, LK = ramp(a.mech, a.legs, a.cells)
     times = a.dt * np.arange(a.legs + 1)
+    if a.budget is not None:
+        if a.linear:
+            raise SystemExit("--budget: there is no reaction flux with rate constants linear in time")
+        return main_budget(a, V, LF, LK, times)
     if a.linear:
         return main_linear(a, V, LF, LK, nodes(a.mech, a.legs, a.cells), times)
     print("%s: %d cell(s), %d legs of %g s, night -> day rows blended per leg; %s" %
