@@ -513,57 +513,156 @@ def get_policy(mech):
     return Policy(method.value, factor.value, floor.value) if is_set.value else None
 
 
+# ---- the front every Rosenbrock_x function shares: the cell arrays described once (_front), the tolerance arguments (_tol_args), the trace arrays
+#      (_trace_arrays).  A family function is then what is particular to it: its extra arrays and which library entry it calls.
+def _is_torch(x):
+    try:
+        import torch
+        return isinstance(x, torch.Tensor)
+    except ImportError:      # pragma: no cover
+        return False
+
+
+class _Front:
+    """The cell arrays of a call: torch CUDA tensors (torch: the module; the device entries, on torch's current stream) or numpy arrays (torch None: the
+    host entries).  ptrs: var, fix, rconst as the entries take them; hstart: None or the checked array; nlf, nlr: the blocks of fix and rconst."""
+
+    def __init__(self, name, torch, var, fix, rconst, hstart, ncell, nlf, nlr):
+        self.name, self.torch, self.var, self.hstart, self.ncell, self.nlf, self.nlr = name, torch, var, hstart, ncell, nlf, nlr
+        self.device = var.device if torch else None
+        self.ptrs = (self.ptr(var), self.ptr(fix), self.ptr(rconst))
+        self.stream = C.c_void_p(torch.cuda.current_stream(var.device).cuda_stream) if torch else None
+        self.form = "device" if torch else "ex"
+
+    def ptr(self, x):
+        if x is None:
+            return None
+        return x.data_ptr() if self.torch else x.ctypes.data_as(_ip if x.dtype == np.int32 else _dp)
+
+    def new(self, shape, dtype="float64", zero=False):
+        """an array of the cells' kind; a host array is zeroed in any case, a tensor where the entry leaves part of it unwritten"""
+        if self.torch:
+            return (self.torch.zeros if zero else self.torch.empty)(shape, dtype=getattr(self.torch, dtype), device=self.device)
+        return np.zeros(shape, getattr(np, dtype))
+
+    def results(self, rows=None, out=None):
+        """-> out, ierr, stats, th of one call (rows None) or of the `rows` legs of a series; th holds 2 entries per cell on the device, 3 on the host"""
+        lead = () if rows is None else (rows,)
+        nvar = DIMS[self.name][0]
+        if not self.torch:
+            out = np.empty(lead + (self.ncell, nvar))
+        elif out is None:
+            out = self.torch.empty_like(self.var) if rows is None else self.new(lead + (self.ncell, nvar))
+        elif out.dtype != self.torch.float64 or not out.is_contiguous() or out.numel() != rows * self.ncell * nvar or out.device != self.device:
+            raise MistraChemError("out: a contiguous float64 [nleg, ncell, %d] tensor on the cells' device expected" % nvar)
+        return out, self.new(lead + (self.ncell,), "int32"), self.new(lead + (self.ncell, 8), "int32"), self.new(lead + (self.ncell, 2 if self.torch else 3))
+
+
+def _front(name, var, fix, rconst, hstart, host_hstart=False, init_host=False, blocks=None):
+    """var, fix, rconst [ncell, .] and hstart [ncell] checked -> _Front.  A tensor var selects the device entries, and the library is brought up on its
+    device; numpy arrays select the host entries, whose arguments the library checks before it looks for a device: no init() in front of them unless
+    init_host.  host_hstart: the host entry takes hstart (else it goes with the device entry).  blocks(fix, rconst) -> (nlf, nlr): fix and rconst may
+    hold several blocks [nl, ncell, .] (the series with rates)."""
+    nvar, nfix, nreact, _ = DIMS[name]
+    torch = None
+    if _is_torch(var):
+        import torch
+        if not var.is_cuda:
+            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
+        init(var.device.index or 0)
+        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
+            if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
+                raise MistraChemError("expected contiguous float64 [%sncell,%d] tensors on one device" % ("..., " if blocks else "", n))
+        ncell = var.numel() // nvar
+        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
+            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
+    else:
+        if hstart is not None and not host_hstart:
+            raise MistraChemError("hstart goes with the device entry: pass torch CUDA tensors (host buffers: rpar[2] is the first step size of every cell)")
+        if init_host and _inited_device is None:
+            init(0)
+        var = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
+        ncell = var.shape[0]
+        fix, rconst = np.ascontiguousarray(fix, np.float64), np.ascontiguousarray(rconst, np.float64)
+        if not blocks:
+            fix, rconst = fix.reshape(ncell, nfix), rconst.reshape(ncell, nreact)
+        if hstart is not None:
+            hstart = np.ascontiguousarray(hstart, np.float64).reshape(-1)
+            if hstart.size != ncell:
+                raise MistraChemError("hstart: %d entries expected" % ncell)
+    nlf, nlr = blocks(fix, rconst) if blocks else (1, 1)
+    size = (lambda x: x.numel()) if torch else (lambda x: x.size)
+    if size(fix) != nlf * ncell * nfix or size(rconst) != nlr * ncell * nreact:
+        raise MistraChemError("cell counts of var / fix / rconst differ")
+    return _Front(name, torch, var, fix, rconst, hstart, ncell, nlf, nlr)
+
+
+def _options(name, cells, ipar, rpar, atol, rtol):
+    """_option_args for a call whose tolerances are the shared pair (cells false) or come in rows per cell (the pair is then INTEGRATE_x's, unread)"""
+    return _option_args(name, ipar, rpar, None if cells else atol, None if cells else rtol)
+
+
+def _tol_args(fr, opts, cells, atol, rtol):
+    """The tolerance and option arguments of an entry, opts from _options: the shared pair, or with cells the rows atol, rtol [ncell, ntol] of the
+    cells' kind -> (atol, rtol[, ntol], rpar, ipar) as the entry takes them"""
+    ip, rp, at, rt = opts
+    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
+    if not cells:
+        return (at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp)) + popts
+    if fr.torch:
+        for x in (atol, rtol):
+            if not _is_torch(x) or x.dtype != fr.torch.float64 or not x.is_contiguous() or x.ndim != 2 or x.shape[0] != fr.ncell or x.device != fr.device:
+                raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
+        if atol.shape != rtol.shape:
+            raise MistraChemError("atol and rtol differ in shape")
+    else:
+        atol, rtol = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
+        if atol.ndim != 2 or atol.shape[0] != fr.ncell or rtol.shape != atol.shape:
+            raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
+    return (fr.ptr(atol), fr.ptr(rtol), int(atol.shape[1])) + popts
+
+
+def _trace_arrays(fr, cap, ctrl, trace_d, trace_i):
+    """The log arrays of a trace entry, the caller's or new ones of the cells' kind -> (the entry's trace arguments, the Trace of views into them)"""
+    cap = int(cap)
+    rows, ncell = max(cap, 0), fr.ncell
+    td = fr.new((ncell, rows, 4), zero=True) if trace_d is None else trace_d
+    ti = fr.new((ncell, rows, 2), "int32", zero=True) if trace_i is None else trace_i
+    for x, dt, k in ((td, "float64", 4), (ti, "int32", 2)):
+        if fr.torch:
+            if x.dtype != getattr(fr.torch, dt) or not x.is_contiguous() or x.numel() != ncell * rows * k or x.device != fr.device:
+                raise MistraChemError("trace_d / trace_i: contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] tensors on the cells' device expected")
+        elif not isinstance(x, np.ndarray) or x.dtype != getattr(np, dt) or not x.flags.c_contiguous or x.size != ncell * rows * k:
+            raise MistraChemError("trace_d / trace_i: C-contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] arrays expected")
+    td, ti = td.reshape(ncell, rows, 4), ti.reshape(ncell, rows, 2)
+    nt = fr.new((ncell,), "int32")
+    ct = fr.new((ncell, DIMS[fr.name][0]), "int32", zero=True) if ctrl else None
+    args = (cap, fr.ptr(td) if rows else None, fr.ptr(ti) if rows else None, fr.ptr(nt), fr.ptr(ct))
+    return args, (Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct),)
+
+
+def _ros_single(stem, mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, cells, extra=None, init_host=False):
+    """One call through mistra_chem_<stem>[_cells]_ex / _device -> (IntegrateResult, t_h) + what the family adds.  extra(front) -> (the entry's arguments
+    behind the plain call's, the results behind rosenbrock's pair)"""
+    mid, name = _mech_id(mech)
+    opts = _options(name, cells, ipar, rpar, atol, rtol)
+    fr = _front(name, var, fix, rconst, hstart, init_host=init_host)
+    tol = _tol_args(fr, opts, cells, atol, rtol)
+    out, ierr, stats, th = fr.results()
+    args, more = extra(fr) if extra else ((), ())
+    tail = (fr.ptr(fr.hstart), fr.stream) if fr.torch else ()
+    entry = getattr(lib(), "mistra_chem_%s_%s%s" % (stem, "cells_" if cells else "", fr.form))
+    _check(entry(mid, fr.ncell, *fr.ptrs, float(tstart), float(tend), *tol, fr.ptr(out), fr.ptr(ierr), fr.ptr(stats), fr.ptr(th), *tail, *args))
+    return (IntegrateResult(out, ierr, stats), th) + more
+
+
 def rosenbrock(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None, atol=None, rtol=None, hstart=None):
     """Rosenbrock_x(Y, Tstart, Tend, AbsTol, RelTol, RPAR, IPAR, IERR) over a batch of cells, any of its five methods (ipar[3]); the options are this
     call's alone — None = INTEGRATE_x's value — and the ones in force (set_options) are neither read nor changed.  numpy arrays: the host entry,
     -> (IntegrateResult, t_h [ncell, 3]) as integrate_ex; torch CUDA tensors: the device entry on torch's current stream, -> (IntegrateResult,
     texit_hexit [ncell, 2]), hstart [ncell] (a tensor, device entry only): first step size per cell, entries <= 0 = rpar[2].  Options Rosenbrock_x
     refuses do not raise: every cell's ierr is its code (-1 .. -5), var comes back unchanged, stats and t_h are zero."""
-    mid, name = _mech_id(mech)
-    nvar, nfix, nreact, _ = DIMS[name]
-    ip, rp, at, rt = _option_args(name, ipar, rpar, atol, rtol)
-    opts = (at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp), rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
-    try:
-        import torch
-        is_torch = isinstance(var, torch.Tensor)
-    except ImportError:      # pragma: no cover
-        is_torch = False
-    if is_torch:
-        if not var.is_cuda:
-            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
-        init(var.device.index or 0)
-        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
-            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
-                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
-        ncell = var.numel() // nvar
-        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
-            raise MistraChemError("cell counts of var / fix / rconst differ")
-        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
-            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
-        out = torch.empty_like(var)
-        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
-        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
-        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
-        stream = torch.cuda.current_stream(var.device).cuda_stream
-        _check(lib().mistra_chem_rosenbrock_device(mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), *opts,
-                                                   out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(),
-                                                   None if hstart is None else hstart.data_ptr(), C.c_void_p(stream)))
-        return IntegrateResult(out, ierr, stats), th
-    if hstart is not None:
-        raise MistraChemError("hstart goes with the device entry: pass torch CUDA tensors (host buffers: rpar[2] is the first step size of every cell)")
-    if _inited_device is None:
-        init(0)
-    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
-    ncell = v.shape[0]
-    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
-    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
-    out = np.empty_like(v)
-    ierr = np.zeros(ncell, np.int32)
-    stats = np.zeros((ncell, 8), np.int32)
-    th = np.zeros((ncell, 3))
-    _check(lib().mistra_chem_rosenbrock_ex(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend),
-                                           *opts, out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp)))
-    return IntegrateResult(out, ierr, stats), th
+    return _ros_single("rosenbrock", mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, False, init_host=True)
 
 
 # ---- the step-control trace (include/mistra_chem.h: mistra_chem_rosenbrock_trace_ex / _device)
@@ -578,172 +677,15 @@ def rosenbrock_trace(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None,
     share of NVAR*err**2, code = accepted + 2 * zero pivots of the attempt.  cap: records kept per cell; n counts all attempts, records past cap
     are dropped, rows past min(n, cap) are as they were (zeros, or what the caller's trace_d [ncell, cap, 4] / trace_i [ncell, cap, 2] held).
     ctrl: whether the per-species count of controlled attempts is wanted.  The Trace's arrays are views of the log arrays, of the inputs' kind."""
-    mid, name = _mech_id(mech)
-    nvar, nfix, nreact, _ = DIMS[name]
-    ip, rp, at, rt = _option_args(name, ipar, rpar, atol, rtol)
-    opts = (at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp), rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
-    cap = int(cap)
-    try:
-        import torch
-        is_torch = isinstance(var, torch.Tensor)
-    except ImportError:      # pragma: no cover
-        is_torch = False
-    if is_torch:
-        if not var.is_cuda:
-            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
-        init(var.device.index or 0)
-        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
-            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
-                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
-        ncell = var.numel() // nvar
-        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
-            raise MistraChemError("cell counts of var / fix / rconst differ")
-        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
-            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
-        rows = max(cap, 0)
-        td = torch.zeros((ncell, rows, 4), dtype=torch.float64, device=var.device) if trace_d is None else trace_d
-        ti = torch.zeros((ncell, rows, 2), dtype=torch.int32, device=var.device) if trace_i is None else trace_i
-        for x, dt, k in ((td, torch.float64, 4), (ti, torch.int32, 2)):
-            if x.dtype != dt or not x.is_contiguous() or x.numel() != ncell * rows * k or x.device != var.device:
-                raise MistraChemError("trace_d / trace_i: contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] tensors on the cells' device expected")
-        td, ti = td.view(ncell, rows, 4), ti.view(ncell, rows, 2)
-        nt = torch.empty(ncell, dtype=torch.int32, device=var.device)
-        ct = torch.zeros((ncell, nvar), dtype=torch.int32, device=var.device) if ctrl else None
-        out = torch.empty_like(var)
-        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
-        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
-        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
-        stream = torch.cuda.current_stream(var.device).cuda_stream
-        _check(lib().mistra_chem_rosenbrock_trace_device(mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), *opts,
-                                                         out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(),
-                                                         None if hstart is None else hstart.data_ptr(), C.c_void_p(stream), cap,
-                                                         td.data_ptr() if rows else None, ti.data_ptr() if rows else None, nt.data_ptr(),
-                                                         None if ct is None else ct.data_ptr()))
-        return IntegrateResult(out, ierr, stats), th, Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct)
-    if hstart is not None:
-        raise MistraChemError("hstart goes with the device entry: pass torch CUDA tensors (host buffers: rpar[2] is the first step size of every cell)")
-    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
-    ncell = v.shape[0]
-    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
-    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
-    rows = max(cap, 0)
-    td = np.zeros((ncell, rows, 4)) if trace_d is None else trace_d
-    ti = np.zeros((ncell, rows, 2), np.int32) if trace_i is None else trace_i
-    for x, dt, k in ((td, np.float64, 4), (ti, np.int32, 2)):
-        if not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags.c_contiguous or x.size != ncell * rows * k:
-            raise MistraChemError("trace_d / trace_i: C-contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] arrays expected")
-    td, ti = td.reshape(ncell, rows, 4), ti.reshape(ncell, rows, 2)
-    nt = np.zeros(ncell, np.int32)
-    ct = np.zeros((ncell, nvar), np.int32) if ctrl else None
-    out = np.empty_like(v)
-    ierr = np.zeros(ncell, np.int32)
-    stats = np.zeros((ncell, 8), np.int32)
-    th = np.zeros((ncell, 3))
-    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
-    _check(lib().mistra_chem_rosenbrock_trace_ex(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart),
-                                                 float(tend), *opts, out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip),
-                                                 th.ctypes.data_as(_dp), cap, td.ctypes.data_as(_dp) if rows else None,
-                                                 ti.ctypes.data_as(_ip) if rows else None, nt.ctypes.data_as(_ip),
-                                                 None if ct is None else ct.ctypes.data_as(_ip)))
-    return IntegrateResult(out, ierr, stats), th, Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct)
+    return _ros_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, (cap, ctrl, trace_d, trace_i), False)
 
 
 # ---- tolerances per cell (include/mistra_chem.h: mistra_chem_rosenbrock_cells_ex / _device, their trace forms, mistra_chem_cell_atol_device)
-def _is_torch(x):
-    try:
-        import torch
-        return isinstance(x, torch.Tensor)
-    except ImportError:      # pragma: no cover
-        return False
-
-
-def _ros_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, trace):
-    """rosenbrock_cells (trace None) and rosenbrock_trace_cells (trace = (cap, ctrl, trace_d, trace_i))"""
-    mid, name = _mech_id(mech)
-    nvar, nfix, nreact, _ = DIMS[name]
-    ip, rp, _, _ = _option_args(name, ipar, rpar, None, None)
-    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
-    L = lib()
-    if trace is not None:
-        cap, ctrl, trace_d, trace_i = trace
-        cap = int(cap)
-        rows = max(cap, 0)
-    if _is_torch(var):
-        import torch
-        if not var.is_cuda:
-            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
-        init(var.device.index or 0)
-        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
-            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
-                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
-        ncell = var.numel() // nvar
-        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
-            raise MistraChemError("cell counts of var / fix / rconst differ")
-        for x in (atol, rtol):
-            if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.ndim != 2 or x.shape[0] != ncell or x.device != var.device:
-                raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
-        if atol.shape != rtol.shape:
-            raise MistraChemError("atol and rtol differ in shape")
-        ntol = int(atol.shape[1])
-        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
-            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
-        if trace is not None:
-            td = torch.zeros((ncell, rows, 4), dtype=torch.float64, device=var.device) if trace_d is None else trace_d
-            ti = torch.zeros((ncell, rows, 2), dtype=torch.int32, device=var.device) if trace_i is None else trace_i
-            for x, dt, k in ((td, torch.float64, 4), (ti, torch.int32, 2)):
-                if x.dtype != dt or not x.is_contiguous() or x.numel() != ncell * rows * k or x.device != var.device:
-                    raise MistraChemError("trace_d / trace_i: contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] tensors on the cells' device expected")
-            td, ti = td.view(ncell, rows, 4), ti.view(ncell, rows, 2)
-            nt = torch.empty(ncell, dtype=torch.int32, device=var.device)
-            ct = torch.zeros((ncell, nvar), dtype=torch.int32, device=var.device) if ctrl else None
-        out = torch.empty_like(var)
-        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
-        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
-        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
-        stream = torch.cuda.current_stream(var.device).cuda_stream
-        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), atol.data_ptr(), rtol.data_ptr(), ntol,
-                *popts, out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), None if hstart is None else hstart.data_ptr(),
-                C.c_void_p(stream))
-        if trace is None:
-            rc = L.mistra_chem_rosenbrock_cells_device(*head)
-        else:
-            rc = L.mistra_chem_rosenbrock_trace_cells_device(*head, cap, td.data_ptr() if rows else None, ti.data_ptr() if rows else None,
-                                                             nt.data_ptr(), None if ct is None else ct.data_ptr())
-        _check(rc)
-        if trace is None:
-            return IntegrateResult(out, ierr, stats), th
-        return IntegrateResult(out, ierr, stats), th, Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct)
-    if hstart is not None:
-        raise MistraChemError("hstart goes with the device entry: pass torch CUDA tensors (host buffers: rpar[2] is the first step size of every cell)")
-    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
-    ncell = v.shape[0]
-    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
-    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
-    at, rt = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
-    if at.ndim != 2 or at.shape[0] != ncell or rt.shape != at.shape:
-        raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
-    ntol = int(at.shape[1])
-    out = np.empty_like(v)
-    ierr = np.zeros(ncell, np.int32)
-    stats = np.zeros((ncell, 8), np.int32)
-    th = np.zeros((ncell, 3))
-    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend), at.ctypes.data_as(_dp),
-            rt.ctypes.data_as(_dp), ntol, *popts, out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp))
-    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
+def _ros_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, trace, cells=True):
+    """rosenbrock_cells (trace None) and rosenbrock_trace_cells (trace = (cap, ctrl, trace_d, trace_i)); cells false: rosenbrock_trace"""
     if trace is None:
-        _check(L.mistra_chem_rosenbrock_cells_ex(*head))
-        return IntegrateResult(out, ierr, stats), th
-    td = np.zeros((ncell, rows, 4)) if trace_d is None else trace_d
-    ti = np.zeros((ncell, rows, 2), np.int32) if trace_i is None else trace_i
-    for x, dt, k in ((td, np.float64, 4), (ti, np.int32, 2)):
-        if not isinstance(x, np.ndarray) or x.dtype != dt or not x.flags.c_contiguous or x.size != ncell * rows * k:
-            raise MistraChemError("trace_d / trace_i: C-contiguous float64 [ncell, cap, 4] / int32 [ncell, cap, 2] arrays expected")
-    td, ti = td.reshape(ncell, rows, 4), ti.reshape(ncell, rows, 2)
-    nt = np.zeros(ncell, np.int32)
-    ct = np.zeros((ncell, nvar), np.int32) if ctrl else None
-    _check(L.mistra_chem_rosenbrock_trace_cells_ex(*head, cap, td.ctypes.data_as(_dp) if rows else None, ti.ctypes.data_as(_ip) if rows else None,
-                                                   nt.ctypes.data_as(_ip), None if ct is None else ct.ctypes.data_as(_ip)))
-    return IntegrateResult(out, ierr, stats), th, Trace(td[..., 0], td[..., 1], td[..., 2], td[..., 3], ti[..., 0], ti[..., 1], nt, ct)
+        return _ros_single("rosenbrock", mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, cells)
+    return _ros_single("rosenbrock_trace", mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, cells, lambda fr: _trace_arrays(fr, *trace))
 
 
 def rosenbrock_cells(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart=None):
@@ -765,83 +707,16 @@ def _ros_flux(mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hsta
     (rosenbrock_dense / rosenbrock_dense_cells), which return samples [ns, ncell, NVAR] and nout [ncell] where the flux entries return the flux"""
     if ts is not None:      # a host array whatever the cells are: it travels with the call's options
         ts = np.ascontiguousarray(ts, np.float64).reshape(-1)
-    mid, name = _mech_id(mech)
-    nvar, nfix, nreact, _ = DIMS[name]
-    ip, rp, at, rt = _option_args(name, ipar, rpar, None if cells else atol, None if cells else rtol)
-    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
-    L = lib()
-    if _is_torch(var):
-        import torch
-        if not var.is_cuda:
-            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
-        init(var.device.index or 0)
-        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
-            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
-                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
-        ncell = var.numel() // nvar
-        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
-            raise MistraChemError("cell counts of var / fix / rconst differ")
-        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
-            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
-        if cells:
-            for x in (atol, rtol):
-                if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.ndim != 2 or x.shape[0] != ncell or x.device != var.device:
-                    raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
-            if atol.shape != rtol.shape:
-                raise MistraChemError("atol and rtol differ in shape")
-            tol = (atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]))
-        else:
-            tol = (at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp))
-        out = torch.empty_like(var)
-        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
-        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
-        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
-        stream = torch.cuda.current_stream(var.device).cuda_stream
-        if ts is not None:
-            samples = torch.empty((ts.size, ncell, nvar), dtype=torch.float64, device=var.device)
-            nout = torch.empty(ncell, dtype=torch.int32, device=var.device)
-            entry = L.mistra_chem_rosenbrock_dense_cells_device if cells else L.mistra_chem_rosenbrock_dense_device
-            _check(entry(mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), *tol, *popts, out.data_ptr(),
-                         ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), None if hstart is None else hstart.data_ptr(), C.c_void_p(stream),
-                         int(ts.size), ts.ctypes.data_as(_dp), samples.data_ptr(), nout.data_ptr()))
-            return IntegrateResult(out, ierr, stats), th, samples, nout
-        flux = torch.empty((ncell, nreact), dtype=torch.float64, device=var.device)
-        entry = L.mistra_chem_rosenbrock_flux_cells_device if cells else L.mistra_chem_rosenbrock_flux_device
-        _check(entry(mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend), *tol, *popts, out.data_ptr(),
-                     ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), None if hstart is None else hstart.data_ptr(), C.c_void_p(stream),
-                     flux.data_ptr()))
-        return IntegrateResult(out, ierr, stats), th, flux
-    if hstart is not None:
-        raise MistraChemError("hstart goes with the device entry: pass torch CUDA tensors (host buffers: rpar[2] is the first step size of every cell)")
-    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
-    ncell = v.shape[0]
-    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
-    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
-    if cells:
-        a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
-        if a2.ndim != 2 or a2.shape[0] != ncell or r2.shape != a2.shape:
-            raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
-        tol = (a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]))
-    else:
-        tol = (at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp))
-    out = np.empty_like(v)
-    ierr = np.zeros(ncell, np.int32)
-    stats = np.zeros((ncell, 8), np.int32)
-    th = np.zeros((ncell, 3))
-    if ts is not None:
-        samples = np.zeros((ts.size, ncell, nvar))
-        nout = np.zeros(ncell, np.int32)
-        entry = L.mistra_chem_rosenbrock_dense_cells_ex if cells else L.mistra_chem_rosenbrock_dense_ex
-        _check(entry(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend), *tol, *popts,
-                     out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp), int(ts.size),
-                     ts.ctypes.data_as(_dp), samples.ctypes.data_as(_dp), nout.ctypes.data_as(_ip)))
-        return IntegrateResult(out, ierr, stats), th, samples, nout
-    flux = np.zeros((ncell, nreact))
-    entry = L.mistra_chem_rosenbrock_flux_cells_ex if cells else L.mistra_chem_rosenbrock_flux_ex
-    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
-    _check(entry(mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend), *tol, *popts,
-                 out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp), flux.ctypes.data_as(_dp)))
-    return IntegrateResult(out, ierr, stats), th, flux
+
+    def extra(fr):
+        nvar, _, nreact, _ = DIMS[fr.name]
+        if ts is None:
+            flux = fr.new((fr.ncell, nreact))
+            return (fr.ptr(flux),), (flux,)
+        samples, nout = fr.new((ts.size, fr.ncell, nvar)), fr.new((fr.ncell,), "int32")
+        return (int(ts.size), ts.ctypes.data_as(_dp), fr.ptr(samples), fr.ptr(nout)), (samples, nout)
+
+    return _ros_single("rosenbrock_flux" if ts is None else "rosenbrock_dense", mech, var, fix, rconst, tstart, tend, ipar, rpar, atol, rtol, hstart, cells, extra)
 
 
 def rosenbrock_flux(mech, var, fix, rconst, tstart, tend, ipar=None, rpar=None, atol=None, rtol=None, hstart=None):
@@ -885,74 +760,7 @@ def rosenbrock_series(mech, var, fix, rconst, times, ipar=None, rpar=None, atol=
     entries <= 0 = rpar[2].  carry_h: a later leg starts with the previous leg's Hexit of the cell where that is > 0, instead of rpar[2].  out
     (device entry): a [nleg, ncell, NVAR] tensor to receive the states; var may be one leg's block of it.  Options Rosenbrock_x refuses are results
     in every leg, as for rosenbrock()."""
-    mid, name = _mech_id(mech)
-    nvar, nfix, nreact, _ = DIMS[name]
-    cells = atol is not None and rtol is not None and getattr(atol, "ndim", 0) == 2 and getattr(rtol, "ndim", 0) == 2
-    ip, rp, at1, rt1 = _option_args(name, ipar, rpar, None if cells else atol, None if cells else rtol)
-    tm = np.ascontiguousarray(times, np.float64).reshape(-1)
-    nleg = tm.size - 1
-    tp = tm.ctypes.data_as(_dp)
-    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
-    L = lib()
-    rows = max(nleg, 0)
-    if _is_torch(var):
-        import torch
-        if not var.is_cuda:
-            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
-        init(var.device.index or 0)
-        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
-            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
-                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
-        ncell = var.numel() // nvar
-        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
-            raise MistraChemError("cell counts of var / fix / rconst differ")
-        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
-            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
-        if cells:
-            for x in (atol, rtol):
-                if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.shape[0] != ncell or x.device != var.device:
-                    raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
-            if atol.shape != rtol.shape:
-                raise MistraChemError("atol and rtol differ in shape")
-        if out is None:
-            out = torch.empty((rows, ncell, nvar), dtype=torch.float64, device=var.device)
-        elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != rows * ncell * nvar or out.device != var.device:
-            raise MistraChemError("out: a contiguous float64 [nleg, ncell, %d] tensor on the cells' device expected" % nvar)
-        ierr = torch.empty((rows, ncell), dtype=torch.int32, device=var.device)
-        stats = torch.empty((rows, ncell, 8), dtype=torch.int32, device=var.device)
-        th = torch.empty((rows, ncell, 2), dtype=torch.float64, device=var.device)
-        stream = torch.cuda.current_stream(var.device).cuda_stream
-        tail = (out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), int(bool(carry_h)), None if hstart is None else hstart.data_ptr(),
-                C.c_void_p(stream))
-        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), nleg, tp)
-        if cells:
-            _check(L.mistra_chem_rosenbrock_series_cells_device(*head, atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]), *popts, *tail))
-        else:
-            _check(L.mistra_chem_rosenbrock_series_device(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
-        return SeriesResult(out.view(rows, ncell, nvar), ierr, stats, th)
-    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
-    ncell = v.shape[0]
-    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
-    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
-    hs = None if hstart is None else np.ascontiguousarray(hstart, np.float64).reshape(-1)
-    if hs is not None and hs.size != ncell:
-        raise MistraChemError("hstart: %d entries expected" % ncell)
-    res = np.empty((rows, ncell, nvar))
-    ierr = np.zeros((rows, ncell), np.int32)
-    stats = np.zeros((rows, ncell, 8), np.int32)
-    th = np.zeros((rows, ncell, 3))
-    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), nleg, tp)
-    tail = (int(bool(carry_h)), None if hs is None else hs.ctypes.data_as(_dp), res.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip),
-            stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp))
-    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
-    if cells:
-        a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
-        if a2.shape[0] != ncell or r2.shape != a2.shape:
-            raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
-        _check(L.mistra_chem_rosenbrock_series_cells_ex(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *popts, *tail))
-    else:
-        _check(L.mistra_chem_rosenbrock_series_ex(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
-    return SeriesResult(res, ierr, stats, th)
+    return _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, False, rates=False)
 
 
 def rosenbrock_series_rates(mech, var, fix, rconst, times, ipar=None, rpar=None, atol=None, rtol=None, hstart=None, carry_h=False, out=None):
@@ -1000,18 +808,16 @@ def rosenbrock_series_flux_cells(mech, var, fix, rconst, times, ipar, rpar, atol
     return _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, False, True)
 
 
-def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, lin, flux=False):
+def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart, carry_h, out, lin, flux=False, rates=True):
     """rosenbrock_series_rates (lin false), rosenbrock_series_linrates (lin true: rconst holds the nleg + 1 node blocks, and the entries take no count
-    of them) and rosenbrock_series_flux (flux true: the entries take flux_series behind the series with rates' arguments)"""
+    of them) and rosenbrock_series_flux (flux true: the entries take flux_series behind the series with rates' arguments); rates false:
+    rosenbrock_series, whose entries take one block of fix and of rconst and no counts"""
     mid, name = _mech_id(mech)
-    nvar, nfix, nreact, _ = DIMS[name]
+    nvar, _, nreact, _ = DIMS[name]
     cells = atol is not None and rtol is not None and getattr(atol, "ndim", 0) == 2 and getattr(rtol, "ndim", 0) == 2
-    ip, rp, at1, rt1 = _option_args(name, ipar, rpar, None if cells else atol, None if cells else rtol)
+    opts = _options(name, cells, ipar, rpar, atol, rtol)
     tm = np.ascontiguousarray(times, np.float64).reshape(-1)
     nleg = tm.size - 1
-    tp = tm.ctypes.data_as(_dp)
-    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
-    L = lib()
     rows = max(nleg, 0)
 
     def legs(x, what):      # the number of blocks of fix / rconst: the library refuses one that is neither 1 nor nleg, by its text
@@ -1024,79 +830,20 @@ def _series_rates(mech, var, fix, rconst, times, ipar, rpar, atol, rtol, hstart,
             raise MistraChemError("rconst_nodes: a 3-D [nleg + 1, ncell, NREACT] array expected, block k the rate constants at times[k] (nleg = %d)" % nleg)
         return rows + 1
 
-    entry = "mistra_chem_rosenbrock_series_%s_" % ("linrates" if lin else "flux" if flux else "rates")
-    if _is_torch(var):
-        import torch
-        if not var.is_cuda:
-            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
-        init(var.device.index or 0)
-        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
-            if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
-                raise MistraChemError("expected contiguous float64 [..., ncell,%d] tensors on one device" % n)
-        ncell = var.numel() // nvar
-        nlf, nlr = legs(fix, "fix"), nodes(rconst) if lin else legs(rconst, "rconst")
-        if fix.numel() != nlf * ncell * nfix or rconst.numel() != nlr * ncell * nreact:
-            raise MistraChemError("cell counts of var / fix / rconst differ")
-        if hstart is not None and (hstart.dtype != torch.float64 or not hstart.is_contiguous() or hstart.numel() != ncell or hstart.device != var.device):
-            raise MistraChemError("hstart: a contiguous float64 tensor of %d entries on the cells' device expected" % ncell)
-        if cells:
-            for x in (atol, rtol):
-                if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.shape[0] != ncell or x.device != var.device:
-                    raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
-            if atol.shape != rtol.shape:
-                raise MistraChemError("atol and rtol differ in shape")
-        if out is None:
-            out = torch.empty((rows, ncell, nvar), dtype=torch.float64, device=var.device)
-        elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != rows * ncell * nvar or out.device != var.device:
-            raise MistraChemError("out: a contiguous float64 [nleg, ncell, %d] tensor on the cells' device expected" % nvar)
-        ierr = torch.empty((rows, ncell), dtype=torch.int32, device=var.device)
-        stats = torch.empty((rows, ncell, 8), dtype=torch.int32, device=var.device)
-        th = torch.empty((rows, ncell, 2), dtype=torch.float64, device=var.device)
-        stream = torch.cuda.current_stream(var.device).cuda_stream
-        tail = (out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), int(bool(carry_h)), None if hstart is None else hstart.data_ptr(),
-                C.c_void_p(stream))
-        if flux:
-            fl = torch.empty((rows, ncell, nreact), dtype=torch.float64, device=var.device)
-            tail += (fl.data_ptr(),)
-        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr()) + (() if lin else (nlr,)) + (nlf, nleg, tp)
-        if cells:
-            _check(getattr(L, entry + "cells_device")(*head, atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]), *popts, *tail))
-        else:
-            _check(getattr(L, entry + "device")(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
-        if flux:
-            return SeriesFluxResult(out.view(rows, ncell, nvar), ierr, stats, th, fl)
-        return SeriesResult(out.view(rows, ncell, nvar), ierr, stats, th)
-    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
-    ncell = v.shape[0]
-    f = np.ascontiguousarray(fix, np.float64)
-    r = np.ascontiguousarray(rconst, np.float64)
-    nlf, nlr = legs(f, "fix"), nodes(r) if lin else legs(r, "rconst")
-    if f.size != nlf * ncell * nfix or r.size != nlr * ncell * nreact:
-        raise MistraChemError("cell counts of var / fix / rconst differ")
-    hs = None if hstart is None else np.ascontiguousarray(hstart, np.float64).reshape(-1)
-    if hs is not None and hs.size != ncell:
-        raise MistraChemError("hstart: %d entries expected" % ncell)
-    res = np.empty((rows, ncell, nvar))
-    ierr = np.zeros((rows, ncell), np.int32)
-    stats = np.zeros((rows, ncell, 8), np.int32)
-    th = np.zeros((rows, ncell, 3))
-    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp)) + (() if lin else (nlr,)) + (nlf, nleg, tp)
-    tail = (int(bool(carry_h)), None if hs is None else hs.ctypes.data_as(_dp), res.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip),
-            stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp))
-    if flux:
-        fl = np.zeros((rows, ncell, nreact))
-        tail += (fl.ctypes.data_as(_dp),)
-    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
-    if cells:
-        a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
-        if a2.shape[0] != ncell or r2.shape != a2.shape:
-            raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
-        _check(getattr(L, entry + "cells_ex")(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *popts, *tail))
-    else:
-        _check(getattr(L, entry + "ex")(*head, at1.ctypes.data_as(_dp), rt1.ctypes.data_as(_dp), *popts, *tail))
-    if flux:
-        return SeriesFluxResult(res, ierr, stats, th, fl)
-    return SeriesResult(res, ierr, stats, th)
+    fr = _front(name, var, fix, rconst, hstart, host_hstart=True,
+                blocks=(lambda f, r: (legs(f, "fix"), nodes(r) if lin else legs(r, "rconst"))) if rates else None)
+    tol = _tol_args(fr, opts, cells, atol, rtol)
+    res, ierr, stats, th = fr.results(rows, out)
+    fl = fr.new((rows, fr.ncell, nreact)) if flux else None
+    counts = ((() if lin else (fr.nlr,)) + (fr.nlf,)) if rates else ()
+    results = (fr.ptr(res), fr.ptr(ierr), fr.ptr(stats), fr.ptr(th))
+    start = (int(bool(carry_h)), fr.ptr(fr.hstart))
+    tail = results + start + (fr.stream,) if fr.torch else start + results      # (the two forms' own order)
+    stem = "series" + ("_linrates" if lin else "_flux" if flux else "_rates" if rates else "")
+    entry = getattr(lib(), "mistra_chem_rosenbrock_%s_%s%s" % (stem, "cells_" if cells else "", fr.form))
+    _check(entry(mid, fr.ncell, *fr.ptrs, *counts, nleg, tm.ctypes.data_as(_dp), *tol, *tail, *((fr.ptr(fl),) if flux else ())))
+    res = res.view(rows, fr.ncell, nvar) if fr.torch else res
+    return SeriesFluxResult(res, ierr, stats, th, fl) if flux else SeriesResult(res, ierr, stats, th)
 
 
 def cell_atol(mech, var, factor, floor):
@@ -1316,111 +1063,57 @@ def accepted_steps(trace_d, trace_i, ntrace):
 
 def _ros_replay(mech, var, fix, rconst, tstart, tend, hsteps, nsteps, ipar, rpar, atol, rtol, err_log, cells):
     mid, name = _mech_id(mech)
-    nvar, nfix, nreact, _ = DIMS[name]
-    if cells:
-        ip, rp, _, _ = _option_args(name, ipar, rpar, None, None)
-    else:
-        ip, rp, at, rt = _option_args(name, ipar, rpar, atol, rtol)
-    popts = (rp.ctypes.data_as(_dp), ip.ctypes.data_as(_ip))
+    opts = _options(name, cells, ipar, rpar, atol, rtol)
     L = lib()
     if not hasattr(L, "mistra_chem_rosenbrock_replay_ex"):
         raise MistraChemError("this build of the library has no replay entries")
-    if _is_torch(var):
-        import torch
-        if not var.is_cuda:
-            raise MistraChemError("torch tensors must live on the GPU (there is no CPU path); pass numpy arrays for host data")
-        init(var.device.index or 0)
-        for x, n in ((var, nvar), (fix, nfix), (rconst, nreact)):
-            if x.dtype != torch.float64 or not x.is_contiguous() or x.shape[-1] != n or x.device != var.device:
-                raise MistraChemError("expected contiguous float64 [ncell,%d] tensors on one device" % n)
-        ncell = var.numel() // nvar
-        if fix.numel() != ncell * nfix or rconst.numel() != ncell * nreact:
-            raise MistraChemError("cell counts of var / fix / rconst differ")
+    fr = _front(name, var, fix, rconst, None)
+    ncell, torch = fr.ncell, fr.torch
+    # the table: hp, npt as the entry takes them
+    if torch:
         if _is_torch(hsteps) != _is_torch(nsteps):
             raise MistraChemError("hsteps and nsteps: both numpy arrays (one shared sequence) or both tensors on the cells' device (a row per cell)")
         if _is_torch(hsteps):      # rows per cell, read by the kernel in stream order
-            if hsteps.dtype != torch.float64 or not hsteps.is_contiguous() or hsteps.ndim != 2 or hsteps.device != var.device:
+            if hsteps.dtype != torch.float64 or not hsteps.is_contiguous() or hsteps.ndim != 2 or hsteps.device != fr.device:
                 raise MistraChemError("hsteps: a contiguous float64 [ncell, cap] tensor on the cells' device expected")
-            if nsteps.dtype != torch.int32 or not nsteps.is_contiguous() or nsteps.ndim != 1 or nsteps.device != var.device:
+            if nsteps.dtype != torch.int32 or not nsteps.is_contiguous() or nsteps.ndim != 1 or nsteps.device != fr.device:
                 raise MistraChemError("nsteps: a contiguous int32 [ncell] tensor on the cells' device expected")
             hrows, cap = int(hsteps.shape[0]), int(hsteps.shape[1])
             if nsteps.numel() != hrows:
                 raise MistraChemError("hsteps has %d rows, nsteps %d entries" % (hrows, nsteps.numel()))
             if hrows == 1 and ncell == 1:      # (one cell: the library takes the table as the shared, host form)
                 hsteps, nsteps = hsteps.cpu().numpy(), nsteps.cpu().numpy()
-        if not _is_torch(hsteps):
-            hs = np.ascontiguousarray(hsteps, np.float64)
-            hs = hs.reshape(1, -1) if hs.ndim == 1 else hs
-            ns = np.ascontiguousarray(np.atleast_1d(nsteps), np.int32)
-            if hs.ndim != 2 or ns.ndim != 1:
-                raise MistraChemError("hsteps [hrows, cap] and nsteps [hrows] expected")
-            hrows, cap = int(ns.size), int(hs.shape[1])
-            if hs.shape[0] != hrows:
-                raise MistraChemError("hsteps has %d rows, nsteps %d entries" % (hs.shape[0], hrows))
-            if hrows == ncell and ncell > 1:      # rows per cell (what accepted_steps returns): the device entry reads them on the device, so they go up
-                hsteps = torch.tensor(hs, device=var.device)
-                nsteps = torch.tensor(ns, device=var.device)
-                hp, npt = hsteps.data_ptr(), nsteps.data_ptr()
-            else:      # one shared row travels with the call; any other row count is the library's to refuse, before it looks at the addresses
-                hp, npt = hs.ctypes.data_as(C.c_void_p), ns.ctypes.data_as(C.c_void_p)
-        else:
-            hp, npt = hsteps.data_ptr(), nsteps.data_ptr()
-        if err_log is None:
-            err_log = torch.zeros((ncell, cap), dtype=torch.float64, device=var.device)
-        if err_log.dtype != torch.float64 or not err_log.is_contiguous() or err_log.numel() != ncell * cap or err_log.device != var.device:
-            raise MistraChemError("err_log: a contiguous float64 [ncell, cap] tensor on the cells' device expected")
-        if cells:
-            for x in (atol, rtol):
-                if not _is_torch(x) or x.dtype != torch.float64 or not x.is_contiguous() or x.ndim != 2 or x.shape[0] != ncell or x.device != var.device:
-                    raise MistraChemError("atol / rtol: contiguous float64 [ncell, 1] or [ncell, NVAR] tensors on the cells' device expected")
-            if atol.shape != rtol.shape:
-                raise MistraChemError("atol and rtol differ in shape")
-        out = torch.empty_like(var)
-        ierr = torch.empty(ncell, dtype=torch.int32, device=var.device)
-        stats = torch.empty((ncell, 8), dtype=torch.int32, device=var.device)
-        th = torch.empty((ncell, 2), dtype=torch.float64, device=var.device)
-        stream = torch.cuda.current_stream(var.device).cuda_stream
-        tail = (*popts, cap, hrows, hp, npt, out.data_ptr(), ierr.data_ptr(), stats.data_ptr(), th.data_ptr(), err_log.data_ptr() if cap else None,
-                C.c_void_p(stream))
-        head = (mid, ncell, var.data_ptr(), fix.data_ptr(), rconst.data_ptr(), float(tstart), float(tend))
-        if cells:
-            _check(L.mistra_chem_rosenbrock_replay_cells_device(*head, atol.data_ptr(), rtol.data_ptr(), int(atol.shape[1]), *tail))
-        else:
-            _check(L.mistra_chem_rosenbrock_replay_device(*head, at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp), *tail))
-        return IntegrateResult(out, ierr, stats), th, err_log.view(ncell, cap)
-    v = np.ascontiguousarray(var, np.float64).reshape(-1, nvar)
-    ncell = v.shape[0]
-    f = np.ascontiguousarray(fix, np.float64).reshape(ncell, nfix)
-    r = np.ascontiguousarray(rconst, np.float64).reshape(ncell, nreact)
-    hs = None if hsteps is None else np.ascontiguousarray(hsteps, np.float64)
-    if hs is not None and hs.ndim == 1:
-        hs = hs.reshape(1, -1)
-    ns = None if nsteps is None else np.ascontiguousarray(np.atleast_1d(nsteps), np.int32)
-    if (hs is not None and hs.ndim != 2) or (ns is not None and ns.ndim != 1):
-        raise MistraChemError("hsteps [hrows, cap] and nsteps [hrows] expected")
-    hrows = int(ns.size) if ns is not None else int(hs.shape[0]) if hs is not None else 1
-    cap = int(hs.shape[1]) if hs is not None else 0
-    if hs is not None and ns is not None and hs.shape[0] != hrows:
-        raise MistraChemError("hsteps has %d rows, nsteps %d entries" % (hs.shape[0], hrows))
+    if not _is_torch(hsteps):
+        hs = None if hsteps is None else np.ascontiguousarray(hsteps, np.float64)
+        if hs is not None and hs.ndim == 1:
+            hs = hs.reshape(1, -1)
+        ns = None if nsteps is None else np.ascontiguousarray(np.atleast_1d(nsteps), np.int32)
+        if (hs is not None and hs.ndim != 2) or (ns is not None and ns.ndim != 1) or (torch and (hs is None or ns is None)):
+            raise MistraChemError("hsteps [hrows, cap] and nsteps [hrows] expected")
+        hrows = int(ns.size) if ns is not None else int(hs.shape[0]) if hs is not None else 1
+        cap = int(hs.shape[1]) if hs is not None else 0
+        if hs is not None and ns is not None and hs.shape[0] != hrows:
+            raise MistraChemError("hsteps has %d rows, nsteps %d entries" % (hs.shape[0], hrows))
+        if torch and hs is not None and ns is not None and hrows == ncell and ncell > 1:
+            # rows per cell (what accepted_steps returns): the device entry reads them on the device, so they go up
+            hsteps, nsteps = torch.tensor(hs, device=fr.device), torch.tensor(ns, device=fr.device)
+        else:      # one shared row travels with the call; any other row count is the library's to refuse, before it looks at the addresses
+            hp = None if hs is None or not (cap or torch) else hs.ctypes.data_as(C.c_void_p)
+            npt = None if ns is None else ns.ctypes.data_as(C.c_void_p)
+    if _is_torch(hsteps):
+        hp, npt = hsteps.data_ptr(), nsteps.data_ptr()
     if err_log is None:
-        err_log = np.zeros((ncell, cap))
-    if not isinstance(err_log, np.ndarray) or err_log.dtype != np.float64 or not err_log.flags.c_contiguous or err_log.size != ncell * cap:
+        err_log = fr.new((ncell, cap), zero=True)
+    if torch:
+        if err_log.dtype != torch.float64 or not err_log.is_contiguous() or err_log.numel() != ncell * cap or err_log.device != fr.device:
+            raise MistraChemError("err_log: a contiguous float64 [ncell, cap] tensor on the cells' device expected")
+    elif not isinstance(err_log, np.ndarray) or err_log.dtype != np.float64 or not err_log.flags.c_contiguous or err_log.size != ncell * cap:
         raise MistraChemError("err_log: a C-contiguous float64 [ncell, cap] array expected")
-    out = np.empty_like(v)
-    ierr = np.zeros(ncell, np.int32)
-    stats = np.zeros((ncell, 8), np.int32)
-    th = np.zeros((ncell, 3))
-    head = (mid, ncell, v.ctypes.data_as(_dp), f.ctypes.data_as(_dp), r.ctypes.data_as(_dp), float(tstart), float(tend))
-    tail = (*popts, cap, hrows, None if hs is None or not cap else hs.ctypes.data_as(C.c_void_p), None if ns is None else ns.ctypes.data_as(C.c_void_p),
-            out.ctypes.data_as(_dp), ierr.ctypes.data_as(_ip), stats.ctypes.data_as(_ip), th.ctypes.data_as(_dp), err_log.ctypes.data_as(_dp) if cap else None)
-    # (the arguments are checked by the library before it looks for a device: no init() in front of them)
-    if cells:
-        a2, r2 = np.ascontiguousarray(atol, np.float64), np.ascontiguousarray(rtol, np.float64)
-        if a2.ndim != 2 or a2.shape[0] != ncell or r2.shape != a2.shape:
-            raise MistraChemError("atol / rtol: [ncell, 1] or [ncell, NVAR] arrays of one shape expected")
-        _check(L.mistra_chem_rosenbrock_replay_cells_ex(*head, a2.ctypes.data_as(_dp), r2.ctypes.data_as(_dp), int(a2.shape[1]), *tail))
-    else:
-        _check(L.mistra_chem_rosenbrock_replay_ex(*head, at.ctypes.data_as(_dp), rt.ctypes.data_as(_dp), *tail))
+    tol = _tol_args(fr, opts, cells, atol, rtol)
+    out, ierr, stats, th = fr.results()
+    entry = getattr(L, "mistra_chem_rosenbrock_replay_%s%s" % ("cells_" if cells else "", fr.form))
+    _check(entry(mid, ncell, *fr.ptrs, float(tstart), float(tend), *tol, cap, hrows, hp, npt, fr.ptr(out), fr.ptr(ierr), fr.ptr(stats), fr.ptr(th),
+                 fr.ptr(err_log) if cap else None, *((fr.stream,) if torch else ())))
     return IntegrateResult(out, ierr, stats), th, err_log.reshape(ncell, cap)
 
 

@@ -12,10 +12,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -702,9 +704,9 @@ struct MechState {
   // ... and of the series entries: a block is the call's options, then its times (kernel_args.hpp: times).  A ring of its own: every block has room
   // for MISTRA_SERIES_MAX_LEGS + 1 times, which the single calls' blocks need not carry
   RosCallRing series_ring;
-  DevBuf<double> s_ser_var, s_ser_th;      // staging of mistra_chem_rosenbrock_series_ex: the legs' blocks of this slot's cells (grow-only)
-  DevBuf<int32_t> s_ser_ierr, s_ser_stats;
-  DevBuf<double> s_ser_flux;               // ... and of mistra_chem_rosenbrock_series_flux_ex: the legs' flux rows of this slot's cells
+  // staging of the series' _ex entries: the legs' states of this slot's cells (grow-only).  Their other outputs — ierr, stats, th, the flux — take nleg
+  // blocks of the single calls' buffers below: a host call is synchronous under g_mu and the buffers only grow, so no call finds them smaller than it left them
+  DevBuf<double> s_ser_var;
   // the step memory of the batched driver (mistra_chem_set_step_reuse): per model layer k = 1..step_n the last accepted step size of the layer's previous
   // column step of this mechanism, 0 = none.  step_n = 0: forgotten — the next column step under reuse sizes it to its n and zeroes it on the drive stream
   DevBuf<double> step_mem;
@@ -714,12 +716,12 @@ struct MechState {
   DevBuf<double> s_tol;                    // ... and of mistra_chem_rosenbrock_cells_ex: the block's AbsTol rows, then its RelTol rows
   DevBuf<int32_t> s_ierr, s_stats, s_sing;
   DevBuf<double> s_trd;                    // ... and of mistra_chem_rosenbrock_trace_ex: the records, the attempt counts, the per-species counts
-  DevBuf<int32_t> s_tri, s_ntr, s_ctl;
+  DevBuf<int32_t> s_tri, s_ntr, s_ctl;      // (s_ntr also: the cells' own step counts of a replay call, which has no trace)
   DevBuf<double> s_flux;                   // ... and of mistra_chem_rosenbrock_flux_ex: the block's flux rows
   DevBuf<double> s_dn_y;                   // ... and of mistra_chem_rosenbrock_dense_ex: the samples' blocks of this slot's cells, the numbers reached
   DevBuf<int32_t> s_dn_n;
   DevBuf<double> s_ops;                    // ... and of mistra_chem_ops_ex: vdot | jvs | shift | rhs | x of this slot's cells
-  DevBuf<double> s_rp;                     // ... and of mistra_chem_rosenbrock_replay_ex: this slot's cells' rows of steps | their Err rows | their counts
+  DevBuf<double> s_rp;                     // ... and of mistra_chem_rosenbrock_replay_ex: this slot's cells' rows of steps | their Err rows
   // where the zero-pivot rows of the LAST host-buffer call of this slot are (mistra_chem_singular_rows): cells [sing_start,
   // sing_start + sing_count) of the caller's batch in s_sing, or the one cell of the COMMON-block call in one_sing
   size_t sing_start = 0, sing_count = 0;
@@ -741,7 +743,7 @@ struct MechState {
     opt.release(); opt_max_steps = 0;
     pol_opt.release(); pol_method = 0; pol_factor = pol_floor = 0.0;
     call_opt.release(); call_ring.release(); series_ring.release();
-    s_ser_var.release(); s_ser_th.release(); s_ser_ierr.release(); s_ser_stats.release(); s_ser_flux.release();
+    s_ser_var.release();
     step_mem.release(); step_n = 0;
     s_hst.release(); s_tol.release();
     s_var.release(); s_fix.release(); s_rct.release(); s_th.release(); s_env.release(); s_ierr.release(); s_stats.release(); s_sing.release();
@@ -1084,114 +1086,154 @@ std::vector<double> options_block(int mech, const RosResolved& r, const double* 
   return b;
 }
 
-// One call of Rosenbrock_x with its own options (mistra_chem_rosenbrock_ex / _device): nothing of it is kept, nothing process-wide is read but
-// Max_no_steps' default (mistra_chem_debug_set_max_steps, which ipar[2] /= 0 goes before)
-struct RosCall {
-  int ierr = 0;                   // the decode's: 1, or the refusal -1 .. -5
-  int method = kRos3;             // IPAR(4), 0 resolved to Ros4 (gas.f:1057)
-  int max_steps = 0;
-  std::vector<double> block;
-  // mistra_chem_rosenbrock_trace_ex: the step-control trace of the call, the caller's HOST arrays for the whole batch
+// One call of Rosenbrock_x as its entry describes it: the plain call and whatever the entry's family adds to it.  Every extern "C" entry fills one of
+// these and hands it to ros_host (host buffers: every array the caller's host array for the whole batch) or ros_device (device pointers).  Nothing of it is
+// kept, nothing process-wide is read but Max_no_steps' default (mistra_chem_debug_set_max_steps, which ipar[2] /= 0 goes before).
+struct RosRequest {
+  int mech = 0, ncell = 0;
+  const double *var_in = nullptr, *fix = nullptr, *rconst = nullptr;
+  const double* env = nullptr;      // the integrate family: the rate evaluator's inputs in place of rconst, RCONST is made on the device
+  double tstart = 0.0, tend = 0.0;
+  // the call's own options; options = false: the integrate family, which runs under the options and the policy in force
+  bool options = false;
+  const double *atol = nullptr, *rtol = nullptr, *rpar = nullptr;
+  const int32_t* ipar = nullptr;
+  bool per_cell = false;            // the cells entries: atol, rtol are rows [ncell][ntol]; else the shared pair
+  int ntol = 0;
+  double* var_out = nullptr;        // a series: var_series [nleg][ncell][NVAR]; ierr, stats, th then hold nleg blocks as well
+  int32_t *ierr = nullptr, *stats = nullptr;
+  double* th = nullptr;             // host: [ncell][3]; device: [ncell][2]
+  const double* hstart = nullptr;   // the first step size per cell
+  bool record_sing = false;         // the host call records its zero-pivot rows for mistra_chem_singular_rows (the series does not)
+  // the step-control trace
   bool trace = false;
   int cap = 0;
   double* trace_d = nullptr;
   int32_t *trace_i = nullptr, *ntrace = nullptr, *ctrl = nullptr;
-  // mistra_chem_rosenbrock_cells_ex / _device: tolerances per cell, [ncell][ntol] each, the caller's arrays for the whole batch (host or device as the
-  // entry's other arrays); null: the shared pair of the block
-  const double *cell_atol = nullptr, *cell_rtol = nullptr;
-  int ntol = 0;
-  bool vector = false;            // IPAR(2) = 0: every entry of a row is read; else entry 0 alone
-  // mistra_chem_rosenbrock_flux_ex: every reaction's rate integrated over the call, the caller's HOST array [ncell][NREACT] for the whole batch
+  // every reaction's rate integrated over the call [ncell][NREACT]; a series with the flux: over each leg, [nleg][ncell][NREACT]
+  bool wants_flux = false;
   double* flux = nullptr;
-  // mistra_chem_rosenbrock_dense_ex: the state at ns sample times inside the call.  The times ride behind the options in `block`, at
-  // dense_at; ysample [ns][ncell][NVAR] and nout [ncell] are the caller's HOST arrays for the whole batch of dense_total cells
-  int dense_ns = 0;
-  size_t dense_at = 0, dense_total = 0;
-  double* dense_y = nullptr;
-  int32_t* dense_nout = nullptr;
+  // dense output: the state at ns sample times (ts: a host array) -> ysample [ns][ncell][NVAR], nout [ncell]
+  bool dense = false;
+  int ns = 0;
+  const double* ts = nullptr;
+  double* ysample = nullptr;
+  int32_t* nout = nullptr;
+  // a series: nleg legs over times[0 .. nleg] (a host array); rconst and fix in rconst_legs and fix_legs blocks (1 or nleg); lin: rconst holds nleg + 1
+  // node blocks, linear in time over each leg
+  int nleg = 0;
+  bool series = false, lin = false;
+  const double* times = nullptr;
+  int carry_h = 0, rconst_legs = 1, fix_legs = 1;
+  // the replay: hsteps [hrows][replay_cap], nsteps [hrows], err [ncell][replay_cap] or null.  hrows = 1: one sequence shared by all cells, host arrays
+  bool replay = false;
+  int replay_cap = 0, hrows = 0;
+  const double* hsteps = nullptr;
+  const int32_t* nsteps = nullptr;
+  double* err = nullptr;
+
+  bool own_rows() const { return replay && hrows != 1; }
+  size_t legs() const { return series ? (size_t)nleg : 1; }
+  RosRequest& cells(int n) { per_cell = true; ntol = n; return *this; }
+  RosRequest& traced(int c, double* d, int32_t* i, int32_t* n, int32_t* ct) { trace = true; cap = c; trace_d = d; trace_i = i; ntrace = n; ctrl = ct; return *this; }
+  RosRequest& with_flux(double* f) { wants_flux = true; flux = f; return *this; }
+  RosRequest& sampled(int n, const double* t, double* y, int32_t* no) { dense = true; ns = n; ts = t; ysample = y; nout = no; return *this; }
+  RosRequest& over(int n, const double* t, int carry, int rlegs = 1, int flegs = 1) { series = true; nleg = n; times = t; carry_h = carry; rconst_legs = rlegs; fix_legs = flegs; return *this; }
+  RosRequest& linear() { lin = true; return *this; }
+  RosRequest& replayed(int c, int rows, const double* h, const int32_t* n, double* e) { replay = true; replay_cap = c; hrows = rows; hsteps = h; nsteps = n; err = e; return *this; }
 };
-struct DenseOut {      // the sample arguments of a dense-output entry (ysample, nout: host or device arrays, as the entry's others)
-  int ns;
-  const double* ts;
-  double* ysample;
-  int32_t* nout;
-};
-struct CellTol {      // the per-cell tolerance arguments of a cells entry
-  const double *atol, *rtol;
-  int ntol;
-};
-// ... checked before anything touches a device: the widths are the entries' own rule, not codes of Rosenbrock_x
-int check_cell_tol(int mech, int ncell, const CellTol& ct, const double* rpar, const int32_t* ipar) {
-  if (!known_mech(mech)) return fail("unknown mechanism id");
-  if (ncell < 0) return fail("negative cell count");
-  if (!rpar || !ipar) return fail("null options pointer");
-  if (!ct.atol || !ct.rtol) return fail("null tolerance array (atol / rtol: [ncell][ntol] each)");
-  const int nv = kMech[mech].dims.nvar;
-  if (ct.ntol != 1 && ct.ntol != nv) return fail("ntol = " + std::to_string(ct.ntol) + ": a tolerance row holds 1 or NVAR = " + std::to_string(nv) + " entries");
-  if (ipar[1] == 0 && ct.ntol != nv) return fail("vector tolerances (ipar[1] = 0) need rows of NVAR = " + std::to_string(nv) + " entries, ntol = " + std::to_string(ct.ntol));
+// the plain call of an entry with options of its own
+RosRequest ros_request(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend, const double* atol,
+                       const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr, int32_t* stats, double* th,
+                       const double* hstart = nullptr) {
+  RosRequest q;
+  q.mech = mech; q.ncell = ncell; q.var_in = var_in; q.fix = fix; q.rconst = rconst; q.tstart = tstart; q.tend = tend;
+  q.options = true; q.atol = atol; q.rtol = rtol; q.rpar = rpar; q.ipar = ipar;
+  q.var_out = var_out; q.ierr = ierr; q.stats = stats; q.th = th; q.hstart = hstart;
+  return q;
+}
+
+// the per-cell tolerance arguments, checked before anything touches a device: the widths are the entries' own rule, not codes of Rosenbrock_x
+int check_cell_tol(const RosRequest& q) {
+  if (!known_mech(q.mech)) return fail("unknown mechanism id");
+  if (q.ncell < 0) return fail("negative cell count");
+  if (!q.rpar || !q.ipar) return fail("null options pointer");
+  if (!q.atol || !q.rtol) return fail("null tolerance array (atol / rtol: [ncell][ntol] each)");
+  const int nv = kMech[q.mech].dims.nvar;
+  if (q.ntol != 1 && q.ntol != nv) return fail("ntol = " + std::to_string(q.ntol) + ": a tolerance row holds 1 or NVAR = " + std::to_string(nv) + " entries");
+  if (q.ipar[1] == 0 && q.ntol != nv) return fail("vector tolerances (ipar[1] = 0) need rows of NVAR = " + std::to_string(nv) + " entries, ntol = " + std::to_string(q.ntol));
   return 0;
 }
 // the arguments of the trace entries, checked before anything touches a device
-int check_trace_args(const int32_t* ipar, int cap, const double* trace_d, const int32_t* trace_i, const int32_t* ntrace) {
-  if (cap < 0) return fail("negative trace capacity");
-  if (!ntrace) return fail("null ntrace pointer");
-  if (cap > 0 && (!trace_d || !trace_i)) return fail("trace capacity > 0 with a null trace_d or trace_i pointer");
-  if (ipar[3] != 2) return fail("the step-control trace is built for Ros3 (ipar[3] = 2) only");
+int check_trace_args(const RosRequest& q) {
+  if (q.cap < 0) return fail("negative trace capacity");
+  if (!q.ntrace) return fail("null ntrace pointer");
+  if (q.cap > 0 && (!q.trace_d || !q.trace_i)) return fail("trace capacity > 0 with a null trace_d or trace_i pointer");
+  if (q.ipar[3] != 2) return fail("the step-control trace is built for Ros3 (ipar[3] = 2) only");
   return 0;
 }
-// ... and as the trace entries hand them on (host or device arrays, as the entry's others)
-RosCall trace_call(int cap, double* trace_d, int32_t* trace_i, int32_t* ntrace, int32_t* ctrl) {
-  RosCall tr;
-  tr.cap = cap; tr.trace_d = trace_d; tr.trace_i = trace_i; tr.ntrace = ntrace; tr.ctrl = ctrl;
-  return tr;
-}
-// the device entries' tolerance rows: the kernel reads these itself, memory the cells' device cannot reach is refused here, not met there
-int check_tol_reachable(const CellTol& ct, int device) {
-  for (const double* p : {ct.atol, ct.rtol}) {
+// arrays of a device entry that the kernel reads itself: memory the cells' device cannot reach is refused here, not met there
+int check_reachable(std::initializer_list<const void*> arrays, int device, const char* refusal) {
+  for (const void* p : arrays) {
+    if (!p) continue;      // (hsteps with cap = 0)
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type == hipMemoryTypeUnregistered || (attr.type == hipMemoryTypeDevice && attr.device != device))
-      return fail("d_atol / d_rtol are not device arrays on the cells' device");
+      return fail(refusal);
   }
   return 0;
 }
-// the kernel's tolerance arguments of a cells call: device rows [ncell][call.ntol]
-void set_cell_tol(KernelArgs* a, const RosCall& call, const double* d_atol, const double* d_rtol) {
-  a->tol_abs = d_atol; a->tol_rel = d_rtol;
-  a->tol_cell_stride = call.ntol;
-  a->tol_spec_stride = call.vector ? 1 : 0;
-}
-// ... of a host-buffer cells call (nothing where the call has the shared pair): rows [start, start + nc) of the caller's go up to the slot's staging
-int upload_cell_tol(MechState& S, const RosCall& call, size_t start, size_t nc, KernelArgs* a) {
-  if (!call.cell_atol) return 0;
-  const size_t n = nc * (size_t)call.ntol;
-  HIP_TRY(S.s_tol.reserve(2 * n));
-  HIP_TRY(hipMemcpy(S.s_tol.p, call.cell_atol + start * (size_t)call.ntol, n * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(S.s_tol.p + n, call.cell_rtol + start * (size_t)call.ntol, n * sizeof(double), hipMemcpyHostToDevice));
-  set_cell_tol(a, call, S.s_tol.p, S.s_tol.p + n);
-  return 0;
-}
-// ct: the tolerances come per cell (atol, rtol are not read).  The refusals -1 .. -4 depend on ipar / rpar alone and stay whole-call results decided here;
-// -5 is then the kernel's, per cell, and the block's pair is a placeholder no kernel reads.
-RosCall decode_call(int mech, const int32_t* ipar, const double* rpar, const double* atol, const double* rtol, const CellTol* ct = nullptr) {
+
+// What Rosenbrock_x's decode makes of a request's options.  Per-cell tolerances: the refusals -1 .. -4 depend on ipar / rpar alone and stay whole-call
+// results decided here; -5 is then the kernel's, per cell, and the block's pair is a placeholder no kernel reads.
+struct RosCall {
+  int ierr = 1;                   // the decode's: 1, or the refusal -1 .. -5
+  int method = kRos3;             // IPAR(4), 0 resolved to Ros4 (gas.f:1057)
+  int max_steps = 0;
+  bool vector = false;            // IPAR(2) = 0: every entry of a tolerance row is read; else entry 0 alone
+  std::vector<double> block;      // the options block the kernel reads (kernel_args.hpp: RosOptSlot)
+};
+RosCall decode_call(const RosRequest& q) {
   RosCall c;
   RosResolved r;
+  const double *atol = q.atol, *rtol = q.rtol;
   std::vector<double> one_a, one_r;
-  if (ct) {
-    one_a.assign((size_t)kMech[mech].dims.nvar, 1.0);
-    one_r.assign((size_t)kMech[mech].dims.nvar, 1.0e-3);
+  if (q.per_cell) {
+    one_a.assign((size_t)kMech[q.mech].dims.nvar, 1.0);
+    one_r.assign((size_t)kMech[q.mech].dims.nvar, 1.0e-3);
     atol = one_a.data(); rtol = one_r.data();
-    c.cell_atol = ct->atol; c.cell_rtol = ct->rtol; c.ntol = ct->ntol;
-    c.vector = ipar[1] == 0;
+    c.vector = q.ipar[1] == 0;
   }
-  c.ierr = resolve_options(mech, ipar, rpar, atol, rtol, &r);
+  c.ierr = resolve_options(q.mech, q.ipar, q.rpar, atol, rtol, &r);
   if (c.ierr != 1) return c;
-  c.method = ipar[3] == 0 ? (int)kRos4 : (int)ipar[3];
-  c.max_steps = ipar[2] ? ipar[2] : g_max_steps;
-  c.block = options_block(mech, r, atol, rtol);
+  c.method = q.ipar[3] == 0 ? (int)kRos4 : (int)q.ipar[3];
+  c.max_steps = q.ipar[2] ? q.ipar[2] : g_max_steps;
+  c.block = options_block(q.mech, r, atol, rtol);
   return c;
 }
 
-// The kernel of a call: the VARIANT from the arguments (dense output, else a series — with linear rates, with the flux of every leg or plain —, else the flux, else the trace, else a method other than Ros3, else the product unit's
+// The block of a call: its options, then the tail its family reads through the same pointer — the series' times, the dense sample times, or a replay's
+// shared sequence with its count in the first half of one more word.  at = nullptr: nothing is written.  -> the words of the block and where the tail and
+// the count word lie in it: the one convention for both paths
+struct BlockLayout {
+  size_t words = 0, tail = 0, count = 0;
+};
+BlockLayout put_block(double* at, const RosCall& call, const RosRequest& q) {
+  const size_t nb = call.block.size();
+  const double* from = q.series ? q.times : q.dense ? q.ts : q.hsteps;
+  const size_t n = q.series ? (size_t)q.nleg + 1 : q.dense ? (size_t)q.ns : q.replay && !q.own_rows() ? (size_t)q.nsteps[0] : 0;      // (check_replay: 0 .. cap)
+  const bool counted = q.replay && !q.own_rows();
+  if (at) {
+    std::memcpy(at, call.block.data(), nb * sizeof(double));
+    if (n) std::memcpy(at + nb, from, n * sizeof(double));      // read here: the caller's array is free when the call returns
+    if (counted) {
+      at[nb + n] = 0.0;
+      std::memcpy(at + nb + n, q.nsteps, sizeof(int32_t));
+    }
+  }
+  return BlockLayout{nb + n + (counted ? 1 : 0), nb, nb + n};
+}
+
+// The kernel of a call: the VARIANT from the arguments (the replay, else dense output, else a series — with linear rates, with the flux of every leg or plain —, else the flux, else the trace, else a method other than Ros3, else the product unit's
 // kernels), one guard, one slot of the mechanism's table.  A method other than Ros3 never runs as a quiet Ros3: what is not built is refused.
 int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, int method = kRos3) {
   static const struct { const char *user, *refusal; } kText[kVariants] = {
@@ -1201,11 +1243,12 @@ int launch(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream, in
       {"series of Rosenbrock_x calls", "no series kernel for this Rosenbrock method"},
       {"reaction-flux entries", "no flux kernel for this Rosenbrock method"},
       {"dense-output entries", "no dense-output kernel for this Rosenbrock method"},
-      {}, {},      // (8, the operators: launch_ops, not an integration; 9, the replay: launch_replay)
+      {},      // (8, the operators: launch_ops, not an integration)
+      {"replay entries", "no replay kernel for this mechanism"},
       {"series of Rosenbrock_x calls", "no series kernel with rate constants linear in time for this Rosenbrock method"},
       {"reaction-flux entries", "no series kernel with the reaction flux for this Rosenbrock method"}};
   const MechDesc& M = kMech[mech];
-  const int variant = a.dense_nout ? 7 : a.times ? (a.lin_rates ? 10 : a.flux ? 11 : 5) : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
+  const int variant = a.replay_n ? 9 : a.dense_nout ? 7 : a.times ? (a.lin_rates ? 10 : a.flux ? 11 : 5) : a.flux ? 6 : a.ntrace ? 4 : method != kRos3 ? 3 : 0;
   hipError_t e = hipErrorInvalidValue;
   if (variant) {
     if (M.user) return fail_user_slot(mech, kText[variant].user);
@@ -1376,150 +1419,200 @@ int on_cell_blocks(int ncell, F&& block) {
   return 0;
 }
 
-// one device's share of a host-buffer call: upload, integrate, download (synchronous on that device)
-// `env` != nullptr: the caller hands over the rate evaluator's inputs instead of the rate constants (rconst is then ignored): RCONST
-// is made on the device and never crosses PCIe
-int integrate_host_on(DeviceState& D, int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
-                      double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, size_t batch_start = 0,
-                      const double* env = nullptr, const double* hstart = nullptr, const RosCall* call = nullptr) {
-  HIP_TRY(hipSetDevice(D.id));
-  MechState& S = D.mech[mech];
-  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nc = (size_t)ncell;
-  HIP_TRY(S.s_var.reserve(nc * nv));
-  HIP_TRY(S.s_fix.reserve(nc * nf));
-  HIP_TRY(S.s_rct.reserve(nc * nr));
-  HIP_TRY(S.s_ierr.reserve(nc));
-  HIP_TRY(S.s_stats.reserve(nc * 8));
-  HIP_TRY(S.s_sing.reserve(nc * 8));
-  if (t_h) HIP_TRY(S.s_th.reserve(nc * 3));
-  HIP_TRY(hipMemcpy(S.s_var.p, var_in, nc * nv * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(S.s_fix.p, fix, nc * nf * sizeof(double), hipMemcpyHostToDevice));
-  if (env) {      // (the caller has checked that the mechanism has a rate table)
-    const size_t ne = (size_t)S.rates.nenv;
-    HIP_TRY(S.s_env.reserve(nc * ne));
-    HIP_TRY(hipMemcpy(S.s_env.p, env, nc * ne * sizeof(double), hipMemcpyHostToDevice));
-    LAUNCH_TRY(launch_update_rconst(S.rates.dev(), S.s_env.p, S.s_rct.p, ncell, nullptr));
-  } else {
-    HIP_TRY(hipMemcpy(S.s_rct.p, rconst, nc * nr * sizeof(double), hipMemcpyHostToDevice));
+// The one binder: what a request adds to make_args' arguments.  `at` is the request with every array where the kernel reads it — the caller's device
+// arrays (ros_device) or this slot's staging of its `nc` cells (ros_host_on); `block` the device address of the call's block (call = nullptr: the integrate
+// family, which has none and keeps the options in force).  The only place these members are assigned outside make_args.
+void bind_request(KernelArgs* a, const RosRequest& at, const RosCall* call, const double* block, const BlockLayout& L, size_t nc, double* h_last,
+                  int32_t* sing_rows) {
+  const MechDims& dims = kMech[at.mech].dims;
+  const int64_t nv = (int64_t)nc * dims.nvar, nf = (int64_t)nc * dims.nfix, nr = (int64_t)nc * dims.nreact;
+  a->hstart = at.hstart;
+  a->h_last = h_last;
+  a->sing_rows = sing_rows;      // stays on the device: fetched by mistra_chem_singular_rows, i.e. only when a cell reports Nsng > 0
+  if (call) {
+    a->opt = block;
+    a->max_steps = call->max_steps;
   }
-  KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, tin, tout, S.s_var.p, S.s_ierr.p, S.s_stats.p, t_h ? S.s_th.p : nullptr);
-  if (t_h) a.h_last = S.s_th.p + 2 * nc;
-  if (call) {      // the call's own options (mistra_chem_rosenbrock_ex) instead of the ones in force
-    HIP_TRY(S.call_opt.reserve(call->block.size()));
-    HIP_TRY(hipMemcpy(S.call_opt.p, call->block.data(), call->block.size() * sizeof(double), hipMemcpyHostToDevice));
-    a.opt = S.call_opt.p;
-    a.max_steps = call->max_steps;
-    if (int rc = upload_cell_tol(S, *call, batch_start, nc, &a)) return rc;
+  if (at.per_cell) {      // device rows [nc][ntol]
+    a->tol_abs = at.atol; a->tol_rel = at.rtol;
+    a->tol_cell_stride = at.ntol;
+    a->tol_spec_stride = call->vector ? 1 : 0;
   }
-  const int method = call ? call->method : policy_args(S, &a);
-  const bool trace = call && call->trace;
-  const size_t cap = trace ? (size_t)call->cap : 0;
-  if (trace) {      // the caller's log arrays go up first: rows the kernel does not write come back as they were
-    HIP_TRY(S.s_ntr.reserve(nc));
-    a.ntrace = S.s_ntr.p;
-    a.trace_cap = call->cap;
-    if (cap) {
-      HIP_TRY(S.s_trd.reserve(nc * cap * 4));
-      HIP_TRY(S.s_tri.reserve(nc * cap * 2));
-      HIP_TRY(hipMemcpy(S.s_trd.p, call->trace_d + batch_start * cap * 4, nc * cap * 4 * sizeof(double), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(S.s_tri.p, call->trace_i + batch_start * cap * 2, nc * cap * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
-      a.trace_d = S.s_trd.p;
-      a.trace_i = S.s_tri.p;
+  if (at.trace) { a->trace_cap = at.cap; a->trace_d = at.trace_d; a->trace_i = at.trace_i; a->ntrace = at.ntrace; a->ctrl = at.ctrl; }
+  a->flux = at.flux;
+  if (at.dense) { a->times = block + L.tail; a->dense_out = at.ysample; a->dense_nout = at.nout; a->dense_ns = at.ns; a->dense_block = nv; }
+  if (at.series) {
+    a->times = block + L.tail; a->nleg = at.nleg; a->carry_h = at.carry_h ? 1 : 0;
+    a->leg_var = nv; a->leg_ierr = (int64_t)nc; a->leg_stats = (int64_t)nc * 8; a->leg_th = (int64_t)nc * 2; a->leg_h = (int64_t)nc;
+    a->leg_rconst = at.rconst_legs > 1 || at.lin ? nr : 0;      // the stride of the blocks the kernel reads, at the head of every leg
+    a->leg_fix = at.fix_legs > 1 ? nf : 0;
+    a->lin_rates = at.lin ? 1 : 0;      // (... of every evaluation: the node blocks, nleg + 1 of them)
+    if (at.flux) a->leg_flux = nr;      // selects the series kernels with the flux (launch)
+  }
+  if (at.replay) {      // selects the replay kernel (launch); a shared sequence and its count lie in the block
+    const bool own = at.own_rows();
+    a->replay_cap = at.replay_cap;
+    a->replay_h = own ? at.hsteps : block + L.tail;
+    a->replay_n = own ? at.nsteps : reinterpret_cast<const int32_t*>(block + L.count);
+    a->replay_h_stride = own ? (int64_t)at.replay_cap : 0;
+    a->replay_err = at.replay_cap ? at.err : nullptr;
+  }
+}
+
+// ---- staging of a host-buffer call as data: one entry per array that crosses PCIe for this slot's cells [start, start + nc) of the caller's `total`.
+//      The caller's array is [blocks][total][bytes per cell], the slot's [blocks][nc][bytes per cell]; `shared`: one row for the whole batch (the block).
+struct Staged {
+  const void* up;      // the caller's array that goes up before the kernel, or null
+  void* down;          // ... that is fetched behind it, or null
+  void* dev;
+  size_t bytes, blocks;
+  bool shared;
+};
+struct StageList {
+  size_t start, nc, total;
+  std::vector<Staged> v;
+  hipError_t err = hipSuccess;
+  // `want`: the request has this array.  Reserves `room` elements of b (0: what the array needs behind `at`), points `slot` — the array's member of the
+  // request the binder reads — at element `at` of it, and lists the copies.  Not wanted: slot = null, nothing else
+  template <class T, class P>
+  void add(DevBuf<T>& b, P& slot, size_t words, size_t blocks, const std::common_type_t<T>* up, std::common_type_t<T>* down, bool want = true, size_t at = 0, size_t room = 0, bool shared = false) {
+    slot = nullptr;
+    if (!want || err != hipSuccess) return;
+    err = b.reserve(room ? room : at + blocks * (shared ? 1 : nc) * words);
+    slot = b.p + at;
+    if (up || down) v.push_back(Staged{up, down, b.p + at, words * sizeof(T), blocks, shared});
+  }
+  // one block: a plain copy; several blocks of a batch: the slot's cells of each, one strided copy
+  hipError_t copy(const Staged& s, bool to_device) const {
+    const size_t row = (s.shared ? 1 : nc) * s.bytes, off = s.shared ? 0 : start * s.bytes;
+    if (!row) return hipSuccess;
+    if (to_device) {
+      const char* src = static_cast<const char*>(s.up) + off;
+      return s.blocks == 1 ? hipMemcpy(s.dev, src, row, hipMemcpyHostToDevice) : hipMemcpy2D(s.dev, row, src, total * s.bytes, row, s.blocks, hipMemcpyHostToDevice);
     }
-    if (call->ctrl) {
-      HIP_TRY(S.s_ctl.reserve(nc * nv));
-      a.ctrl = S.s_ctl.p;
-      if (call->cell_atol)      // (a cell refused with -5 writes no row: the caller's goes up, as the logs do)
-        HIP_TRY(hipMemcpy(S.s_ctl.p, call->ctrl + batch_start * nv, nc * nv * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    char* dst = static_cast<char*>(s.down) + off;
+    return s.blocks == 1 ? hipMemcpy(dst, s.dev, row, hipMemcpyDeviceToHost) : hipMemcpy2D(dst, total * s.bytes, s.dev, row, row, s.blocks, hipMemcpyDeviceToHost);
   }
-  const bool flux = call && call->flux;
-  if (flux) {      // every row is written by the kernel (a cell refused with -5: zeros): nothing goes up
-    HIP_TRY(S.s_flux.reserve(nc * nr));
-    a.flux = S.s_flux.p;
-  }
-  const bool dense = call && call->dense_nout;
-  if (dense) {      // every row is written by the kernel (the ones not reached: zeros): nothing goes up
-    HIP_TRY(S.s_dn_y.reserve((size_t)call->dense_ns * nc * nv));
-    HIP_TRY(S.s_dn_n.reserve(nc));
-    a.times = S.call_opt.p + call->dense_at;
-    a.dense_out = S.s_dn_y.p; a.dense_nout = S.s_dn_n.p; a.dense_ns = call->dense_ns; a.dense_block = (int64_t)(nc * nv);
-  }
-  if (hstart) {      // OPT-IN: the caller's first step size per cell (mistra_chem_integrate_hstart_ex)
-    HIP_TRY(S.s_hst.reserve(nc));
-    HIP_TRY(hipMemcpy(S.s_hst.p, hstart, nc * sizeof(double), hipMemcpyHostToDevice));
-    a.hstart = S.s_hst.p;
-  }
-  a.sing_rows = S.s_sing.p;      // stays on the device: fetched by mistra_chem_singular_rows, i.e. only when a cell reports Nsng > 0
-  S.sing_start = batch_start; S.sing_count = nc; S.sing_one = false;
-  // diagnostic builds only (-DMISTRA_DIAG_ENV, tools/diag_dense.sh env): MISTRA_CHEM_PROFILE=1 prints where wave 0 of the
-  // workgroups spent its cycles (mean over the cells of the call).  The product library does not read the environment here.
-  DevBuf<unsigned long long> prof;
-#ifdef MISTRA_DIAG_ENV
-  const bool profile = std::getenv("MISTRA_CHEM_PROFILE") != nullptr;
-#else
-  const bool profile = false;
-#endif
-  if (profile) {
-    if (a.opt) return fail("the profiling kernel keeps INTEGRATE_x's values: clear the options (mistra_chem_set_options) first");
-    HIP_TRY(prof.reserve(nc * kProfStride));
-    HIP_TRY(hipMemset(prof.p, 0, nc * kProfStride * sizeof(unsigned long long)));      // (a workgroup of fewer than kProfWaves waves leaves the rest unwritten)
-    a.prof = prof.p;
-  }
+};
+
+// the kernel of a host-buffer call and the wait for it
+int launch_and_wait(DeviceState& D, int mech, const KernelArgs& a, int method) {
   if (int rc = launch(D, mech, a, nullptr, method)) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  if (profile) {
-    std::vector<unsigned long long> h(nc * kProfStride);
-    HIP_TRY(hipMemcpy(h.data(), prof.p, nc * kProfStride * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double sum[kProfStride] = {0};
-    for (size_t c = 0; c < nc; c++)
-      for (int k = 0; k < kProfStride; k++) sum[k] += (double)h[c * kProfStride + k];
-    const char* names[kProfSlots] = {"fun", "jac", "prepare", "lu", "solve(rest)", "norm", "other", "total", "solve_head_fwd", "solve_tail", "solve_head_bwd", "lu_scale", "lu_dense", "jac_products", "jac_sums", "fun_products"};
-    std::fprintf(stderr, "[mistra_chem profile] %s, %zu cells, mean shader-clock ticks per cell:", kMech[mech].name, nc);
-    for (int k = 0; k < kProfSlots; k++) std::fprintf(stderr, " %s=%.0f (%.1f%%)", names[k], sum[k] / nc, 100.0 * sum[k] / sum[7]);
+  return 0;
+}
+#ifdef MISTRA_DIAG_ENV
+// diagnostic builds only (-DMISTRA_DIAG_ENV, tools/diag_dense.sh env): MISTRA_CHEM_PROFILE=1 prints where wave 0 of the
+// workgroups spent its cycles (mean over the cells of the call).  The product library does not read the environment here.
+int launch_profiled(DeviceState& D, int mech, KernelArgs a, int method, size_t nc) {
+  if (a.opt) return fail("the profiling kernel keeps INTEGRATE_x's values: clear the options (mistra_chem_set_options) first");
+  DevBuf<unsigned long long> prof;
+  HIP_TRY(prof.reserve(nc * kProfStride));
+  HIP_TRY(hipMemset(prof.p, 0, nc * kProfStride * sizeof(unsigned long long)));      // (a workgroup of fewer than kProfWaves waves leaves the rest unwritten)
+  a.prof = prof.p;
+  if (int rc = launch_and_wait(D, mech, a, method)) return rc;
+  std::vector<unsigned long long> h(nc * kProfStride);
+  HIP_TRY(hipMemcpy(h.data(), prof.p, nc * kProfStride * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  double sum[kProfStride] = {0};
+  for (size_t c = 0; c < nc; c++)
+    for (int k = 0; k < kProfStride; k++) sum[k] += (double)h[c * kProfStride + k];
+  const char* names[kProfSlots] = {"fun", "jac", "prepare", "lu", "solve(rest)", "norm", "other", "total", "solve_head_fwd", "solve_tail", "solve_head_bwd", "lu_scale", "lu_dense", "jac_products", "jac_sums", "fun_products"};
+  std::fprintf(stderr, "[mistra_chem profile] %s, %zu cells, mean shader-clock ticks per cell:", kMech[mech].name, nc);
+  for (int k = 0; k < kProfSlots; k++) std::fprintf(stderr, " %s=%.0f (%.1f%%)", names[k], sum[k] / nc, 100.0 * sum[k] / sum[7]);
+  std::fprintf(stderr, "\n");
+  // the gather-sum machine per wave (kernel_args.hpp: kProfStride): mean ticks per call since wave 0 entered the evaluator.  The sums'
+  // barrier opens when the last wave reaches the call, so `sums` = left - latest reach is the wave's own fill, rows and drain, and
+  // `waits` = latest left - left is what the wave then idles at the next barrier behind the slowest one.
+  const char* evaluator[2] = {"fun", "fun_jac"};
+  for (int e = 0; e < 2; e++) {
+    const double calls = sum[kProfSlots + 4 * kProfWaves + e];
+    if (calls <= 0) continue;
+    double reach[kProfWaves], left[kProfWaves], opens = 0, last = 0;
+    for (int w = 0; w < kProfWaves; w++) {
+      reach[w] = sum[kProfSlots + 4 * w + 2 * e] / calls;
+      left[w] = sum[kProfSlots + 4 * w + 2 * e + 1] / calls;
+      opens = std::max(opens, reach[w]);
+      last = std::max(last, left[w]);
+    }
+    std::fprintf(stderr, "[mistra_chem profile] %s, sums per wave: %.1f calls per cell, ticks per call, barrier opens at %.0f:", evaluator[e], calls / nc, opens);
+    for (int w = 0; w < kProfWaves; w++)
+      if (left[w] > 0) std::fprintf(stderr, " w%d reach=%.0f left=%.0f sums=%.0f waits=%.0f |", w, reach[w], left[w], left[w] - opens, last - left[w]);
     std::fprintf(stderr, "\n");
-    // the gather-sum machine per wave (kernel_args.hpp: kProfStride): mean ticks per call since wave 0 entered the evaluator.  The sums'
-    // barrier opens when the last wave reaches the call, so `sums` = left - latest reach is the wave's own fill, rows and drain, and
-    // `waits` = latest left - left is what the wave then idles at the next barrier behind the slowest one.
-    const char* evaluator[2] = {"fun", "fun_jac"};
-    for (int e = 0; e < 2; e++) {
-      const double calls = sum[kProfSlots + 4 * kProfWaves + e];
-      if (calls <= 0) continue;
-      double reach[kProfWaves], left[kProfWaves], opens = 0, last = 0;
-      for (int w = 0; w < kProfWaves; w++) {
-        reach[w] = sum[kProfSlots + 4 * w + 2 * e] / calls;
-        left[w] = sum[kProfSlots + 4 * w + 2 * e + 1] / calls;
-        opens = std::max(opens, reach[w]);
-        last = std::max(last, left[w]);
+  }
+  prof.release();
+  return 0;
+}
+#endif
+
+// One device slot's share of a host-buffer call (ros_host): cells [start, start + nc) of the request's batch up, the kernel, the results down,
+// synchronous on that device.  call = nullptr: the integrate family.  Every upload of the slot precedes its downloads and slots own disjoint cells, so
+// var_in may alias var_out (one leg's block of it in a series).
+int ros_host_on(DeviceState& D, const RosRequest& q, const RosCall* call, const std::vector<double>& blk, const BlockLayout& L, size_t start, size_t nc) {
+  HIP_TRY(hipSetDevice(D.id));
+  MechState& S = D.mech[q.mech];
+  const MechDims& dims = kMech[q.mech].dims;
+  const size_t nv = (size_t)dims.nvar, nf = (size_t)dims.nfix, nr = (size_t)dims.nreact, ne = q.env ? (size_t)S.rates.nenv : 0;
+  const size_t nl = q.legs(), cap = (size_t)q.cap, rcap = (size_t)q.replay_cap, ntol = (size_t)q.ntol;
+  const size_t nlr = q.lin ? nl + 1 : (size_t)q.rconst_legs;      // the node blocks: one more than there are legs
+  const bool own = q.own_rows(), keep_err = q.err && rcap;
+  const size_t o_err = own ? nc * rcap : 0, rp_room = o_err + (keep_err ? nc * rcap : 0);      // one arena: the cells' own rows | their Err rows
+  RosRequest at = q;      // every array where this slot keeps its cells of it
+  at.ts = at.times = nullptr;      // (in the block)
+  const double* block = nullptr;
+  int32_t* sing = nullptr;
+  StageList st{start, nc, (size_t)q.ncell, {}};
+  st.v.reserve(24);
+  // Caller output arrays that go up are the ones the kernel writes in part: the trace logs, ctrl under per-cell tolerances (a cell refused with -5 writes
+  // no row) and the replay's err rows come back as they were where it wrote nothing.  The flux and the samples are written whole: nothing goes up.
+  st.add(S.s_var, at.var_in, nv, 1, q.var_in, q.series ? nullptr : q.var_out);      // (the single calls integrate in place)
+  st.add(S.s_fix, at.fix, nf, (size_t)q.fix_legs, q.fix, nullptr);
+  st.add(S.s_env, at.env, ne, 1, q.env, nullptr, q.env != nullptr);                 // (the caller has checked that the mechanism has a rate table)
+  st.add(S.s_rct, at.rconst, nr, nlr, q.env ? nullptr : q.rconst, nullptr);
+  st.add(S.call_opt, block, L.words, 1, blk.data(), nullptr, call != nullptr, 0, 0, true);
+  st.add(S.s_ser_var, at.var_out, nv, nl, nullptr, q.var_out, q.series);
+  if (!q.series) at.var_out = S.s_var.p;
+  st.add(S.s_ierr, at.ierr, 1, nl, nullptr, q.ierr);
+  st.add(S.s_stats, at.stats, 8, nl, nullptr, q.stats);
+  st.add(S.s_sing, sing, 8, 1, nullptr, nullptr, q.record_sing);
+  st.add(S.s_rp, at.hsteps, rcap, 1, q.hsteps, nullptr, own && rcap, 0, rp_room);
+  st.add(S.s_ntr, at.nsteps, 1, 1, q.nsteps, nullptr, own);
+  st.add(S.s_rp, at.err, rcap, 1, q.err, q.err, q.replay && keep_err, o_err, rp_room);
+  st.add(S.s_tol, at.atol, ntol, 1, q.atol, nullptr, q.per_cell, 0, 2 * nc * ntol);
+  st.add(S.s_tol, at.rtol, ntol, 1, q.rtol, nullptr, q.per_cell, nc * ntol, 2 * nc * ntol);
+  st.add(S.s_ntr, at.ntrace, 1, 1, nullptr, q.ntrace, q.trace);
+  st.add(S.s_trd, at.trace_d, cap * 4, 1, q.trace_d, q.trace_d, q.trace && cap);
+  st.add(S.s_tri, at.trace_i, cap * 2, 1, q.trace_i, q.trace_i, q.trace && cap);
+  st.add(S.s_ctl, at.ctrl, nv, 1, q.per_cell ? q.ctrl : nullptr, q.ctrl, q.trace && q.ctrl);
+  st.add(S.s_flux, at.flux, nr, nl, nullptr, q.flux, q.flux != nullptr);
+  st.add(S.s_dn_y, at.ysample, nv, (size_t)q.ns, nullptr, q.ysample, q.dense);
+  st.add(S.s_dn_n, at.nout, 1, 1, nullptr, q.nout, q.dense);
+  st.add(S.s_hst, at.hstart, 1, 1, q.hstart, nullptr, q.hstart != nullptr);
+  st.add(S.s_th, at.th, 3, nl, nullptr, nullptr, q.th || q.replay);      // device: [legs][nc][2] (T, Hexit) then [legs][nc] (H); fetched below
+  HIP_TRY(st.err);
+  for (const Staged& s : st.v)
+    if (s.up) HIP_TRY(st.copy(s, true));
+  if (q.env) LAUNCH_TRY(launch_update_rconst(S.rates.dev(), at.env, S.s_rct.p, (int)nc, nullptr));
+  const double t0 = q.series ? q.times[0] : q.tstart, t1 = q.series ? q.times[q.nleg] : q.tend;
+  KernelArgs a = make_args(S, (int)nc, at.var_in, at.fix, at.rconst, t0, t1, at.var_out, at.ierr, at.stats, at.th);
+  bind_request(&a, at, call, block, L, nc, at.th ? at.th + 2 * nl * nc : nullptr, sing);
+  const int method = call ? call->method : policy_args(S, &a);
+  if (q.record_sing) { S.sing_start = start; S.sing_count = nc; S.sing_one = false; }
+#ifdef MISTRA_DIAG_ENV
+  if (std::getenv("MISTRA_CHEM_PROFILE") && !q.series && !q.replay) {
+    if (int rc = launch_profiled(D, q.mech, a, method, nc)) return rc;
+  } else
+#endif
+  if (int rc = launch_and_wait(D, q.mech, a, method)) return rc;
+  for (const Staged& s : st.v)
+    if (s.down) HIP_TRY(st.copy(s, false));
+  if (q.th) {      // the slot's [legs][nc][2] and [legs][nc]  ->  the caller's [legs][total][3]
+    std::vector<double> h(nl * nc * 3);
+    HIP_TRY(hipMemcpy(h.data(), at.th, nl * nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nl; k++)
+      for (size_t c = 0; c < nc; c++) {
+        double* o = q.th + (k * st.total + start + c) * 3;
+        o[0] = h[(k * nc + c) * 2]; o[1] = h[(k * nc + c) * 2 + 1]; o[2] = h[2 * nl * nc + k * nc + c];
       }
-      std::fprintf(stderr, "[mistra_chem profile] %s, sums per wave: %.1f calls per cell, ticks per call, barrier opens at %.0f:", evaluator[e], calls / nc, opens);
-      for (int w = 0; w < kProfWaves; w++)
-        if (left[w] > 0) std::fprintf(stderr, " w%d reach=%.0f left=%.0f sums=%.0f waits=%.0f |", w, reach[w], left[w], left[w] - opens, last - left[w]);
-      std::fprintf(stderr, "\n");
-    }
-    prof.release();
-  }
-  HIP_TRY(hipMemcpy(var_out, S.s_var.p, nc * nv * sizeof(double), hipMemcpyDeviceToHost));
-  if (ierr) HIP_TRY(hipMemcpy(ierr, S.s_ierr.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (stats) HIP_TRY(hipMemcpy(stats, S.s_stats.p, nc * 8 * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (trace) {
-    HIP_TRY(hipMemcpy(call->ntrace + batch_start, S.s_ntr.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (cap) {
-      HIP_TRY(hipMemcpy(call->trace_d + batch_start * cap * 4, S.s_trd.p, nc * cap * 4 * sizeof(double), hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(call->trace_i + batch_start * cap * 2, S.s_tri.p, nc * cap * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    if (call->ctrl) HIP_TRY(hipMemcpy(call->ctrl + batch_start * nv, S.s_ctl.p, nc * nv * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  if (flux) HIP_TRY(hipMemcpy(call->flux + batch_start * nr, S.s_flux.p, nc * nr * sizeof(double), hipMemcpyDeviceToHost));
-  if (dense) {      // the slot's [ns][nc] blocks into the caller's [ns][total] array
-    HIP_TRY(hipMemcpy2D(call->dense_y + batch_start * nv, call->dense_total * nv * sizeof(double), S.s_dn_y.p, nc * nv * sizeof(double), nc * nv * sizeof(double),
-                        (size_t)call->dense_ns, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(call->dense_nout + batch_start, S.s_dn_n.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
-  if (t_h) {      // device: [ncell][2] (T, Hexit) then [ncell] (H)  ->  caller: [ncell][3]
-    std::vector<double> h(nc * 3);
-    HIP_TRY(hipMemcpy(h.data(), S.s_th.p, nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < nc; c++) { t_h[3 * c] = h[2 * c]; t_h[3 * c + 1] = h[2 * c + 1]; t_h[3 * c + 2] = h[2 * nc + c]; }
   }
   return 0;
 }
@@ -2591,9 +2684,17 @@ static int lazy_init() {
   return mistra_chem_init(dev ? std::atoi(dev) : 0);
 }
 
+// the two paths every Rosenbrock_x request takes (below, behind the families' checks): host buffers, device pointers
+static int ros_host(const RosRequest& q);
+static int ros_device(const RosRequest& q, void* hip_stream);
+
+// the integrate family: the request without options of its own, under the options and the policy in force
 static int integrate_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, const double* env, double tin,
-                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart = nullptr,
-                          const RosCall* call = nullptr);
+                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart = nullptr) {
+  RosRequest q = ros_request(mech, ncell, var_in, fix, rconst, tin, tout, nullptr, nullptr, nullptr, nullptr, var_out, ierr, stats, t_h, hstart);
+  q.options = false; q.env = env; q.record_sing = true;
+  return ros_host(q);
+}
 
 int mistra_chem_integrate_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tin,
                              double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h) {
@@ -2610,26 +2711,6 @@ int mistra_chem_integrate_hstart_ex(int mech, int ncell, const double* var_in, c
                                     double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart) {
   if ((rconst != nullptr) == (env != nullptr)) return fail("mistra_chem_integrate_hstart_ex: exactly one of rconst and env");
   return integrate_host(mech, ncell, var_in, fix, rconst, env, tin, tout, var_out, ierr, stats, t_h, hstart);
-}
-
-static int integrate_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, const double* env, double tin,
-                          double tout, double* var_out, int32_t* ierr, int32_t* stats, double* t_h, const double* hstart, const RosCall* call) {
-  if (env && known_mech(mech) && kMech[mech].user) return fail_user_slot(mech, "rate table");      // (mistra_chem_integrate_hstart_ex with env)
-  if (int rc = lazy_init()) return rc;
-  if (int rc = check_call(mech, ncell, true)) return rc;
-  if (ncell == 0) return 0;
-  if (!var_in || !fix || !var_out || (!rconst && !env)) return fail("null host pointer");
-  std::lock_guard<std::mutex> lock(g_mu);
-  Slot t;
-  if (int rc = on_primary(mech, env ? kNeedRates : 0, true, &t)) return rc;
-  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact;
-  const size_t ne = env ? (size_t)t.S->rates.nenv : 0;
-  for (auto& d : g_devs) d.mech[mech].sing_count = 0;
-  return on_cell_blocks(ncell, [=](DeviceState& D, size_t start, int count) {
-    return integrate_host_on(D, mech, count, var_in + start * nv, fix + start * nf, rconst ? rconst + start * nr : nullptr, tin, tout, var_out + start * nv,
-                             ierr ? ierr + start : nullptr, stats ? stats + start * 8 : nullptr, t_h ? t_h + start * 3 : nullptr, start,
-                             env ? env + start * ne : nullptr, hstart ? hstart + start : nullptr, call);
-  });
 }
 
 int mistra_chem_method_table(int method, int* S, double* A15, double* C15, double* M6, double* E6, double* gamma6, int32_t* newf6, double* elo) {
@@ -2651,179 +2732,75 @@ int mistra_chem_method_table(int method, int* S, double* A15, double* C15, doubl
   return 0;
 }
 
-// mistra_chem_rosenbrock_ex and, with tr set (its trace members filled in), mistra_chem_rosenbrock_trace_ex; flux set: mistra_chem_rosenbrock_flux_ex;
-// dn set (checked by the caller: check_dense): mistra_chem_rosenbrock_dense_ex
-static int rosenbrock_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
-                           const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
-                           int32_t* stats, double* t_h, const RosCall* tr, const CellTol* ct = nullptr, double* flux = nullptr, const DenseOut* dn = nullptr) {
-  if (int rc = user_slot_method(mech, ipar)) return rc;
-  if (int rc = lazy_init()) return rc;
-  if (int rc = check_call(mech, ncell, true)) return rc;
-  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
-  if (ncell == 0) return 0;
-  if (!var_in || !fix || !rconst || !var_out) return fail("null host pointer");
-  RosCall call;
-  {
-    std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps)
-    if (g_devs[0].mech[mech].pend.active) return step_is_open(mech);
-    call = decode_call(mech, ipar, rpar, atol, rtol, ct);
-  }
-  if (tr) { call.trace = true; call.cap = tr->cap; call.trace_d = tr->trace_d; call.trace_i = tr->trace_i; call.ntrace = tr->ntrace; call.ctrl = tr->ctrl; }
-  call.flux = flux;
-  if (dn) {      // the sample times behind the options: one upload, read by the kernel as a series reads its times
-    call.dense_ns = dn->ns; call.dense_at = call.block.size(); call.dense_total = (size_t)ncell; call.dense_y = dn->ysample; call.dense_nout = dn->nout;
-    if (call.ierr == 1) call.block.insert(call.block.end(), dn->ts, dn->ts + dn->ns);
-  }
-  if (call.ierr != 1) {      // Rosenbrock_x returns before it touches Y or the statistics (gas.f:936-1053): a result, nothing is launched
-    const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
-    if (tr) std::fill(tr->ntrace, tr->ntrace + nc, 0);      // no attempt was made: the logs and ctrl stay as they are
-    if (var_out != var_in) std::memmove(var_out, var_in, nc * nv * sizeof(double));
-    if (ierr) std::fill(ierr, ierr + nc, (int32_t)call.ierr);
-    if (stats) std::fill(stats, stats + nc * 8, 0);
-    if (t_h) std::fill(t_h, t_h + nc * 3, 0.0);
-    if (flux) std::fill(flux, flux + nc * (size_t)kMech[mech].dims.nreact, 0.0);
-    if (dn) {      // no step was made: no sample is reached
-      std::fill(dn->ysample, dn->ysample + (size_t)dn->ns * nc * nv, 0.0);
-      std::fill(dn->nout, dn->nout + nc, 0);
-    }
-    return 0;
-  }
-  return integrate_host(mech, ncell, var_in, fix, rconst, nullptr, tstart, tend, var_out, ierr, stats, t_h, nullptr, &call);
+// ---- Rosenbrock_x with the call's own options.  Every entry below, and every family further down, describes its call (ros_request and what the family
+//      adds) and takes one of the two paths: ros_host with host buffers — these record the zero-pivot rows —, ros_device with device pointers.
+static int single_host(RosRequest q) {
+  q.record_sing = true;
+  return ros_host(q);
 }
 
 int mistra_chem_rosenbrock_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                               const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
                               int32_t* stats, double* t_h) {
-  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr);
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h));
 }
 
 int mistra_chem_rosenbrock_trace_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                                     const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
                                     int32_t* stats, double* t_h, int cap, double* trace_d, int32_t* trace_i, int32_t* ntrace, int32_t* ctrl) {
-  if (int rc = builtin_only(mech, "step-control trace")) return rc;
-  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
-  if (int rc = check_trace_args(ipar, cap, trace_d, trace_i, ntrace)) return rc;
-  const RosCall tr = trace_call(cap, trace_d, trace_i, ntrace, ctrl);
-  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, &tr);
-}
-
-// mistra_chem_rosenbrock_device and, with tr set (device arrays), mistra_chem_rosenbrock_trace_device; d_flux set: mistra_chem_rosenbrock_flux_device;
-// dn set (checked by the caller: check_dense; device arrays): mistra_chem_rosenbrock_dense_device
-static int rosenbrock_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
-                                double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
-                                int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream, const RosCall* tr,
-                                const CellTol* ct = nullptr, double* d_flux = nullptr, const DenseOut* dn = nullptr) {
-  if (int rc = user_slot_method(mech, ipar)) return rc;
-  if (ncell == 0) return check_call(mech, 0, true);
-  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
-  if (!d_var_in || !d_fix || !d_rconst || !d_var_out || !d_ierr || !d_stats) return fail("null device pointer");
-  Slot t;
-  if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (ct)
-    if (int rc = check_tol_reachable(*ct, t.D->id)) return rc;
-  std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of options blocks)
-  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
-  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
-  if (call.ierr != 1) {      // the refusal as a result, in stream order; no kernel of the library runs
-    if (d_var_out != d_var_in) HIP_TRY(hipMemcpyAsync(d_var_out, d_var_in, nc * nv * sizeof(double), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_ierr), call.ierr, nc, st));
-    HIP_TRY(hipMemsetAsync(d_stats, 0, nc * 8 * sizeof(int32_t), st));
-    if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nc * 2 * sizeof(double), st));
-    if (tr) HIP_TRY(hipMemsetAsync(tr->ntrace, 0, nc * sizeof(int32_t), st));      // no attempt was made: the logs and ctrl stay as they are
-    if (d_flux) HIP_TRY(hipMemsetAsync(d_flux, 0, nc * (size_t)kMech[mech].dims.nreact * sizeof(double), st));
-    if (dn) {      // no step was made: no sample is reached
-      HIP_TRY(hipMemsetAsync(dn->ysample, 0, (size_t)dn->ns * nc * nv * sizeof(double), st));
-      HIP_TRY(hipMemsetAsync(dn->nout, 0, nc * sizeof(int32_t), st));
-    }
-    return 0;
-  }
-  // a dense-output call keeps its sample times behind its options: a block of the series' ring, which has the room (MISTRA_DENSE_MAX_TIMES fits)
-  static_assert(MISTRA_DENSE_MAX_TIMES <= MISTRA_SERIES_MAX_LEGS + 1, "the sample times travel in a block of the series' ring");
-  const size_t nb = call.block.size(), ns = dn ? (size_t)dn->ns : 0;
-  RosCallRing& R = dn ? t.S->series_ring : t.S->call_ring;
-  int i;
-  double *hb, *db;
-  HIP_TRY(R.acquire(dn ? nb + (size_t)MISTRA_SERIES_MAX_LEGS + 1 : nb, &i, &hb, &db));
-  std::memcpy(hb, call.block.data(), nb * sizeof(double));
-  if (dn) std::memcpy(hb + nb, dn->ts, ns * sizeof(double));      // read here: the caller's array is free when the call returns
-  HIP_TRY(hipMemcpyAsync(db, hb, (nb + ns) * sizeof(double), hipMemcpyHostToDevice, st));
-  KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_var_out, d_ierr, d_stats, d_texit_hexit);
-  a.hstart = d_hstart;
-  a.opt = db;
-  a.max_steps = call.max_steps;
-  if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
-  if (tr) { a.trace_cap = tr->cap; a.trace_d = tr->trace_d; a.trace_i = tr->trace_i; a.ntrace = tr->ntrace; a.ctrl = tr->ctrl; }
-  a.flux = d_flux;
-  if (dn) { a.times = db + nb; a.dense_out = dn->ysample; a.dense_nout = dn->nout; a.dense_ns = dn->ns; a.dense_block = (int64_t)(nc * nv); }
-  const int rc = launch(*t.D, mech, a, st, call.method);
-  R.mark(i, st);
-  return rc;
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h)
+                         .traced(cap, trace_d, trace_i, ntrace, ctrl));
 }
 
 int mistra_chem_rosenbrock_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                   double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* d_var_out,
                                   int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart, void* hip_stream) {
-  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                              d_hstart, hip_stream, nullptr);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit, d_hstart),
+                    hip_stream);
 }
 
 int mistra_chem_rosenbrock_trace_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                         double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                                         double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
                                         void* hip_stream, int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl) {
-  if (int rc = builtin_only(mech, "step-control trace")) return rc;
-  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
-  if (int rc = check_trace_args(ipar, cap, d_trace_d, d_trace_i, d_ntrace)) return rc;
-  const RosCall tr = trace_call(cap, d_trace_d, d_trace_i, d_ntrace, d_ctrl);
-  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                              d_hstart, hip_stream, &tr);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit, d_hstart)
+                        .traced(cap, d_trace_d, d_trace_i, d_ntrace, d_ctrl),
+                    hip_stream);
 }
 
-// ---- tolerances per cell: the same two paths, the rows in place of the pair
+// ---- tolerances per cell: the rows in place of the pair
 int mistra_chem_rosenbrock_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                                     const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar, double* var_out,
                                     int32_t* ierr, int32_t* stats, double* t_h) {
-  if (int rc = user_slot_method(mech, ipar)) return rc;
-  const CellTol ct{atol, rtol, ntol};
-  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
-  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, &ct);
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h).cells(ntol));
 }
 
 int mistra_chem_rosenbrock_trace_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                                           const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar, double* var_out,
                                           int32_t* ierr, int32_t* stats, double* t_h, int cap, double* trace_d, int32_t* trace_i, int32_t* ntrace,
                                           int32_t* ctrl) {
-  if (int rc = builtin_only(mech, "step-control trace")) return rc;
-  const CellTol ct{atol, rtol, ntol};
-  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
-  if (int rc = check_trace_args(ipar, cap, trace_d, trace_i, ntrace)) return rc;
-  const RosCall tr = trace_call(cap, trace_d, trace_i, ntrace, ctrl);
-  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, &tr, &ct);
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h)
+                         .cells(ntol)
+                         .traced(cap, trace_d, trace_i, ntrace, ctrl));
 }
 
 int mistra_chem_rosenbrock_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                         double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar,
                                         double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
                                         void* hip_stream) {
-  if (int rc = user_slot_method(mech, ipar)) return rc;
-  const CellTol ct{d_atol, d_rtol, ntol};
-  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
-  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                              d_hstart, hip_stream, nullptr, &ct);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit, d_hstart)
+                        .cells(ntol),
+                    hip_stream);
 }
 
 int mistra_chem_rosenbrock_trace_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                               double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar,
                                               double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
                                               void* hip_stream, int cap, double* d_trace_d, int32_t* d_trace_i, int32_t* d_ntrace, int32_t* d_ctrl) {
-  if (int rc = builtin_only(mech, "step-control trace")) return rc;
-  const CellTol ct{d_atol, d_rtol, ntol};
-  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
-  if (int rc = check_trace_args(ipar, cap, d_trace_d, d_trace_i, d_ntrace)) return rc;
-  const RosCall tr = trace_call(cap, d_trace_d, d_trace_i, d_ntrace, d_ctrl);
-  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                              d_hstart, hip_stream, &tr, &ct);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit, d_hstart)
+                        .cells(ntol)
+                        .traced(cap, d_trace_d, d_trace_i, d_ntrace, d_ctrl),
+                    hip_stream);
 }
 
 // ---- the operators: Fun_x, Jac_SP_x and solves with shift*I - Jac_SP_x at a state the caller gives (kernel VARIANT 8).  No integration
@@ -2945,235 +2922,60 @@ int mistra_chem_ops_device(int mech, int ncell, const double* d_var, const doubl
 // ---- the replay: Ros3 along a step sequence the caller prescribes, every step accepted, its Err handed back (kernel VARIANT 9).  The
 //      options of the call give AbsTol, RelTol and Autonomous; the options in force, the integrator policy and step reuse are not involved.  Checked before
 //      anything touches a device, each refusal by its text: the mechanism (no user slot), the table and the method.
-struct ReplayTable {      // the step table of a replay entry: hsteps [hrows][cap], nsteps [hrows]; err [ncell][cap] or null
-  int cap, hrows;
-  const double* hsteps;
-  const int32_t* nsteps;
-  double* err;
-};
 // counts_on_host: nsteps is a host array (always but for the device entries' per-cell rows)
-static int check_replay(int mech, int ncell, const double* rpar, const int32_t* ipar, const ReplayTable& rt, bool counts_on_host) {
-  if (int rc = builtin_only(mech, "replay entries")) return rc;
-  if (!rpar || !ipar) return fail("null options pointer");
-  if (rt.cap < 0) return fail("replay: negative step capacity");
-  if (rt.hrows != 1 && rt.hrows != ncell) return fail("replay: hrows = " + std::to_string(rt.hrows) + " is neither 1 (one sequence shared by all cells) nor ncell (one per cell)");
-  if (rt.cap > 0 && !rt.hsteps) return fail("replay: step capacity > 0 with a null hsteps pointer (hsteps: [hrows][cap])");
-  if (!rt.nsteps) return fail("replay: null nsteps pointer (nsteps: [hrows])");
+static int check_replay(const RosRequest& q, bool counts_on_host) {
+  if (int rc = builtin_only(q.mech, "replay entries")) return rc;
+  if (!q.rpar || !q.ipar) return fail("null options pointer");
+  if (q.replay_cap < 0) return fail("replay: negative step capacity");
+  if (q.hrows != 1 && q.hrows != q.ncell) return fail("replay: hrows = " + std::to_string(q.hrows) + " is neither 1 (one sequence shared by all cells) nor ncell (one per cell)");
+  if (q.replay_cap > 0 && !q.hsteps) return fail("replay: step capacity > 0 with a null hsteps pointer (hsteps: [hrows][cap])");
+  if (!q.nsteps) return fail("replay: null nsteps pointer (nsteps: [hrows])");
   if (counts_on_host)
-    for (int r = 0; r < rt.hrows; r++)
-      if (rt.nsteps[r] < 0 || rt.nsteps[r] > rt.cap)
-        return fail("replay: nsteps[" + std::to_string(r) + "] = " + std::to_string(rt.nsteps[r]) + " lies outside 0 .. cap = " + std::to_string(rt.cap));
-  if (ipar[3] != 2) return fail("the replay is built for Ros3 (ipar[3] = 2) only");
+    for (int r = 0; r < q.hrows; r++)
+      if (q.nsteps[r] < 0 || q.nsteps[r] > q.replay_cap)
+        return fail("replay: nsteps[" + std::to_string(r) + "] = " + std::to_string(q.nsteps[r]) + " lies outside 0 .. cap = " + std::to_string(q.replay_cap));
+  if (q.ipar[3] != 2) return fail("the replay is built for Ros3 (ipar[3] = 2) only");
   return 0;
-}
-
-static int launch_replay(DeviceState& D, int mech, const KernelArgs& a, hipStream_t stream) {
-  const LaunchFn fn = kMech[mech].unit.fn[9][kRos3];
-  if (!fn) return fail("no replay kernel for this mechanism");
-  const hipError_t e = fn(a, stream, &D.lds_configured[mech][9][kRos3]);
-  if (e != hipSuccess) return fail(std::string("kernel launch: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// a shared sequence behind a call's options block: the nsteps[0] steps the kernel reads, then the count in the first half of one more cell -> the words written
-static size_t put_shared_steps(double* at, const ReplayTable& rt) {
-  const size_t n = (size_t)rt.nsteps[0];      // (check_replay: 0 .. cap)
-  if (n) std::memcpy(at, rt.hsteps, n * sizeof(double));
-  at[n] = 0.0;
-  std::memcpy(at + n, rt.nsteps, sizeof(int32_t));
-  return n + 1;
-}
-// the device entries' rows per cell: the kernel reads these itself, memory the cells' device cannot reach is refused here, not met there
-static int check_rows_reachable(const ReplayTable& rt, int device) {
-  for (const void* p : {static_cast<const void*>(rt.hsteps), static_cast<const void*>(rt.nsteps)}) {
-    if (!p) continue;      // (hsteps with cap = 0)
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type == hipMemoryTypeUnregistered || (attr.type == hipMemoryTypeDevice && attr.device != device))
-      return fail("replay: hsteps / nsteps with hrows = ncell are not device arrays on the cells' device (a shared sequence, hrows = 1, is a host array)");
-  }
-  return 0;
-}
-
-// one device's share of mistra_chem_rosenbrock_replay_ex: its cells and its rows up, the kernel, the results down (synchronous on that device)
-static int replay_host_on(DeviceState& D, int mech, int ncell, size_t start, const double* var_in, const double* fix, const double* rconst, double tstart,
-                          double tend, const RosCall& call, const ReplayTable& rt, double* var_out, int32_t* ierr, int32_t* stats, double* t_h) {
-  HIP_TRY(hipSetDevice(D.id));
-  MechState& S = D.mech[mech];
-  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nc = (size_t)ncell;
-  const size_t cap = (size_t)rt.cap, nb = call.block.size();
-  const bool own = rt.hrows != 1;
-  HIP_TRY(S.s_var.reserve(nc * nv));
-  HIP_TRY(S.s_fix.reserve(nc * nf));
-  HIP_TRY(S.s_rct.reserve(nc * nr));
-  HIP_TRY(S.s_ierr.reserve(nc));
-  HIP_TRY(S.s_stats.reserve(nc * 8));
-  HIP_TRY(S.s_sing.reserve(nc * 8));
-  HIP_TRY(S.s_th.reserve(nc * 3));
-  // one arena: the cells' own rows | their Err rows | their counts
-  const size_t o_h = 0, o_err = o_h + (own ? nc * cap : 0), o_n = o_err + (rt.err ? nc * cap : 0);
-  HIP_TRY(S.s_rp.reserve(o_n + (own ? nc / 2 + 1 : 0) + 1));
-  double* const B = S.s_rp.p;
-  const size_t nshared = own ? 0 : (size_t)rt.nsteps[0];
-  HIP_TRY(S.call_opt.reserve(nb + nshared + 1));
-  HIP_TRY(hipMemcpy(S.s_var.p, var_in + start * nv, nc * nv * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(S.s_fix.p, fix + start * nf, nc * nf * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(S.s_rct.p, rconst + start * nr, nc * nr * sizeof(double), hipMemcpyHostToDevice));
-  std::vector<double> blk(call.block);
-  blk.resize(nb + nshared + 1, 0.0);
-  if (!own) put_shared_steps(blk.data() + nb, rt);
-  HIP_TRY(hipMemcpy(S.call_opt.p, blk.data(), blk.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (own) {
-    if (cap) HIP_TRY(hipMemcpy(B + o_h, rt.hsteps + start * cap, nc * cap * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(B + o_n, rt.nsteps + start, nc * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  if (rt.err && cap)      // the caller's rows go up first: entries past a cell's count come back as they were
-    HIP_TRY(hipMemcpy(B + o_err, rt.err + start * cap, nc * cap * sizeof(double), hipMemcpyHostToDevice));
-  KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, tstart, tend, S.s_var.p, S.s_ierr.p, S.s_stats.p, S.s_th.p);
-  a.h_last = S.s_th.p + 2 * nc;
-  a.opt = S.call_opt.p;
-  a.max_steps = call.max_steps;
-  if (int rc = upload_cell_tol(S, call, start, nc, &a)) return rc;
-  a.replay_cap = rt.cap;
-  a.replay_h = own ? B + o_h : S.call_opt.p + nb;
-  a.replay_n = reinterpret_cast<const int32_t*>(own ? B + o_n : S.call_opt.p + nb + nshared);
-  a.replay_h_stride = own ? (int64_t)cap : 0;
-  a.replay_err = rt.err && cap ? B + o_err : nullptr;
-  a.sing_rows = S.s_sing.p;
-  S.sing_start = start; S.sing_count = nc; S.sing_one = false;
-  if (int rc = launch_replay(D, mech, a, nullptr)) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(var_out + start * nv, S.s_var.p, nc * nv * sizeof(double), hipMemcpyDeviceToHost));
-  if (ierr) HIP_TRY(hipMemcpy(ierr + start, S.s_ierr.p, nc * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (stats) HIP_TRY(hipMemcpy(stats + start * 8, S.s_stats.p, nc * 8 * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (rt.err && cap) HIP_TRY(hipMemcpy(rt.err + start * cap, B + o_err, nc * cap * sizeof(double), hipMemcpyDeviceToHost));
-  if (t_h) {      // device: [ncell][2] (T, Hexit) then [ncell] (H)  ->  caller: [ncell][3]
-    std::vector<double> h(nc * 3);
-    HIP_TRY(hipMemcpy(h.data(), S.s_th.p, nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < nc; c++) { double* o = t_h + (start + c) * 3; o[0] = h[2 * c]; o[1] = h[2 * c + 1]; o[2] = h[2 * nc + c]; }
-  }
-  return 0;
-}
-
-static int replay_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend, const double* atol,
-                       const double* rtol, const double* rpar, const int32_t* ipar, const ReplayTable& rt, double* var_out, int32_t* ierr, int32_t* stats,
-                       double* t_h, const CellTol* ct) {
-  if (int rc = check_replay(mech, ncell, rpar, ipar, rt, true)) return rc;
-  if (ct)
-    if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
-  if (!atol || !rtol) return fail("null options pointer");
-  if (int rc = lazy_init()) return rc;
-  if (int rc = check_call(mech, ncell)) return rc;
-  if (ncell == 0) return 0;
-  if (!var_in || !fix || !rconst || !var_out) return fail("null host pointer");
-  std::lock_guard<std::mutex> lock(g_mu);
-  if (g_devs[0].mech[mech].pend.active) return step_is_open(mech);
-  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
-  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
-  if (call.ierr != 1) {      // Rosenbrock_x returns before it touches Y or the statistics: a result, nothing is launched, err_log stays as it is
-    if (var_out != var_in) std::memmove(var_out, var_in, nc * nv * sizeof(double));
-    if (ierr) std::fill(ierr, ierr + nc, (int32_t)call.ierr);
-    if (stats) std::fill(stats, stats + nc * 8, 0);
-    if (t_h) std::fill(t_h, t_h + nc * 3, 0.0);
-    return 0;
-  }
-  for (auto& d : g_devs) d.mech[mech].sing_count = 0;
-  return on_cell_blocks(ncell, [=, &call, &rt](DeviceState& D, size_t start, int count) {
-    return replay_host_on(D, mech, count, start, var_in, fix, rconst, tstart, tend, call, rt, var_out, ierr, stats, t_h);
-  });
-}
-
-static int replay_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart, double tend,
-                            const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, const ReplayTable& rt, double* d_var_out,
-                            int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, void* hip_stream, const CellTol* ct) {
-  const bool own = rt.hrows != 1;      // (one cell: the shared form, host arrays)
-  if (int rc = check_replay(mech, ncell, rpar, ipar, rt, !own)) return rc;
-  if (!own && rt.nsteps[0] > MISTRA_REPLAY_MAX_SHARED)
-    return fail("replay: nsteps[0] = " + std::to_string(rt.nsteps[0]) + ": a shared sequence of the device entries holds at most MISTRA_REPLAY_MAX_SHARED = " +
-                std::to_string(MISTRA_REPLAY_MAX_SHARED) + " steps (it travels in the call's block); give every cell its row");
-  if (ct)
-    if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
-  if (!atol || !rtol) return fail("null options pointer");
-  if (ncell == 0) return check_call(mech, 0);
-  if (!d_var_in || !d_fix || !d_rconst || !d_var_out || !d_ierr || !d_stats) return fail("null device pointer");
-  Slot t;
-  if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (ct)
-    if (int rc = check_tol_reachable(*ct, t.D->id)) return rc;
-  if (own)
-    if (int rc = check_rows_reachable(rt, t.D->id)) return rc;
-  std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of series blocks)
-  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
-  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell;
-  if (call.ierr != 1) {      // the refusal as a result, in stream order; no kernel of the library runs
-    if (d_var_out != d_var_in) HIP_TRY(hipMemcpyAsync(d_var_out, d_var_in, nc * nv * sizeof(double), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_ierr), call.ierr, nc, st));
-    HIP_TRY(hipMemsetAsync(d_stats, 0, nc * 8 * sizeof(int32_t), st));
-    if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nc * 2 * sizeof(double), st));
-    return 0;
-  }
-  // the options and, behind them, a shared sequence: a block of the series' ring, which has the room
-  static_assert(MISTRA_REPLAY_MAX_SHARED + 1 <= MISTRA_SERIES_MAX_LEGS + 1, "a shared sequence and its count travel in a block of the series' ring");
-  const size_t nb = call.block.size(), cap = (size_t)rt.cap;
-  RosCallRing& R = t.S->series_ring;
-  int i;
-  double *hb, *db;
-  HIP_TRY(R.acquire(nb + (size_t)MISTRA_SERIES_MAX_LEGS + 1, &i, &hb, &db));
-  std::memcpy(hb, call.block.data(), nb * sizeof(double));
-  const size_t nshared = own ? 0 : put_shared_steps(hb + nb, rt);      // read here: the caller's arrays are free when the call returns
-  HIP_TRY(hipMemcpyAsync(db, hb, (nb + nshared) * sizeof(double), hipMemcpyHostToDevice, st));
-  KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_var_out, d_ierr, d_stats, d_texit_hexit);
-  a.opt = db;
-  a.max_steps = call.max_steps;
-  if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
-  a.replay_cap = rt.cap;
-  a.replay_h = own ? rt.hsteps : db + nb;
-  a.replay_n = own ? rt.nsteps : reinterpret_cast<const int32_t*>(db + nb + nshared - 1);
-  a.replay_h_stride = own ? (int64_t)cap : 0;
-  a.replay_err = cap ? rt.err : nullptr;
-  const int rc = launch_replay(*t.D, mech, a, st);
-  R.mark(i, st);
-  return rc;
 }
 
 int mistra_chem_rosenbrock_replay_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                                      const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int cap, int hrows,
                                      const double* hsteps, const int32_t* nsteps, double* var_out, int32_t* ierr, int32_t* stats, double* t_h,
                                      double* err_log) {
-  const ReplayTable rt{cap, hrows, hsteps, nsteps, err_log};
-  return replay_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, rt, var_out, ierr, stats, t_h, nullptr);
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h)
+                         .replayed(cap, hrows, hsteps, nsteps, err_log));
 }
 
 int mistra_chem_rosenbrock_replay_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                                            const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar, int cap, int hrows,
                                            const double* hsteps, const int32_t* nsteps, double* var_out, int32_t* ierr, int32_t* stats, double* t_h,
                                            double* err_log) {
-  const ReplayTable rt{cap, hrows, hsteps, nsteps, err_log};
-  const CellTol ct{atol, rtol, ntol};
-  return replay_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, rt, var_out, ierr, stats, t_h, &ct);
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h)
+                         .cells(ntol)
+                         .replayed(cap, hrows, hsteps, nsteps, err_log));
 }
 
 int mistra_chem_rosenbrock_replay_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                          double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int cap, int hrows,
                                          const double* hsteps, const int32_t* nsteps, double* d_var_out, int32_t* d_ierr, int32_t* d_stats,
                                          double* d_texit_hexit, double* d_err_log, void* hip_stream) {
-  const ReplayTable rt{cap, hrows, hsteps, nsteps, d_err_log};
-  return replay_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, rt, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                          hip_stream, nullptr);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit)
+                        .replayed(cap, hrows, hsteps, nsteps, d_err_log),
+                    hip_stream);
 }
 
 int mistra_chem_rosenbrock_replay_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                                double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar,
                                                int cap, int hrows, const double* hsteps, const int32_t* nsteps, double* d_var_out, int32_t* d_ierr,
                                                int32_t* d_stats, double* d_texit_hexit, double* d_err_log, void* hip_stream) {
-  const ReplayTable rt{cap, hrows, hsteps, nsteps, d_err_log};
-  const CellTol ct{d_atol, d_rtol, ntol};
-  return replay_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, rt, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                          hip_stream, &ct);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit)
+                        .cells(ntol)
+                        .replayed(cap, hrows, hsteps, nsteps, d_err_log),
+                    hip_stream);
 }
 
-// ---- the reaction flux: Rosenbrock_x as above, plus every reaction's rate integrated over the call (kernel VARIANT 6).  The same two
-//      paths with one more output.  Checked before anything touches a device: the mechanism (no user slot) and the flux pointer.
+// ---- the reaction flux: Rosenbrock_x as above, plus every reaction's rate integrated over the call (kernel VARIANT 6).  One
+//      more output of the request.  Checked before anything touches a device: the mechanism (no user slot) and the flux pointer.
 static int check_flux(int mech, const void* flux) {
   if (int rc = builtin_only(mech, "reaction-flux entries")) return rc;
   if (!flux) return fail("null flux pointer (flux: [ncell][NREACT])");
@@ -3183,41 +2985,36 @@ static int check_flux(int mech, const void* flux) {
 int mistra_chem_rosenbrock_flux_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                                    const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
                                    int32_t* stats, double* t_h, double* flux) {
-  if (int rc = check_flux(mech, flux)) return rc;
-  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, nullptr, flux);
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h).with_flux(flux));
 }
 
 int mistra_chem_rosenbrock_flux_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                        double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                                        double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
                                        void* hip_stream, double* d_flux) {
-  if (int rc = check_flux(mech, d_flux)) return rc;
-  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                              d_hstart, hip_stream, nullptr, nullptr, d_flux);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit, d_hstart)
+                        .with_flux(d_flux),
+                    hip_stream);
 }
 
 int mistra_chem_rosenbrock_flux_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart,
                                          double tend, const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar,
                                          double* var_out, int32_t* ierr, int32_t* stats, double* t_h, double* flux) {
-  if (int rc = check_flux(mech, flux)) return rc;
-  const CellTol ct{atol, rtol, ntol};
-  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
-  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, &ct, flux);
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h).cells(ntol).with_flux(flux));
 }
 
 int mistra_chem_rosenbrock_flux_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                              double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar,
                                              const int32_t* ipar, double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                              const double* d_hstart, void* hip_stream, double* d_flux) {
-  if (int rc = check_flux(mech, d_flux)) return rc;
-  const CellTol ct{d_atol, d_rtol, ntol};
-  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
-  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                              d_hstart, hip_stream, nullptr, &ct, d_flux);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit, d_hstart)
+                        .cells(ntol)
+                        .with_flux(d_flux),
+                    hip_stream);
 }
 
 // ---- dense output: Rosenbrock_x as above, plus the state at ns sample times inside the call, by the cubic Hermite interpolant between the accepted states
-//      (kernel VARIANT 7).  The same two paths with two more outputs.  Checked before anything touches a device, each refusal by its
+//      (kernel VARIANT 7).  Two more outputs of the request.  Checked before anything touches a device, each refusal by its
 //      text: the mechanism (no user slot), the pointers, the count and the times against the call's interval and direction (the kernel's: Tend >= Tstart).
 static int check_dense(int mech, double tstart, double tend, int ns, const double* ts, const void* ysample, const void* nout) {
   if (int rc = builtin_only(mech, "dense-output entries")) return rc;
@@ -3244,42 +3041,36 @@ static int check_dense(int mech, double tstart, double tend, int ns, const doubl
 int mistra_chem_rosenbrock_dense_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart, double tend,
                                     const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, double* var_out, int32_t* ierr,
                                     int32_t* stats, double* t_h, int ns, const double* ts, double* ysample, int32_t* nout) {
-  if (int rc = check_dense(mech, tstart, tend, ns, ts, ysample, nout)) return rc;
-  const DenseOut dn{ns, ts, ysample, nout};
-  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, nullptr, nullptr, &dn);
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h)
+                         .sampled(ns, ts, ysample, nout));
 }
 
 int mistra_chem_rosenbrock_dense_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                         double tend, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                                         double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, const double* d_hstart,
                                         void* hip_stream, int ns, const double* ts, double* d_ysample, int32_t* d_nout) {
-  if (int rc = check_dense(mech, tstart, tend, ns, ts, d_ysample, d_nout)) return rc;
-  const DenseOut dn{ns, ts, d_ysample, d_nout};
-  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                              d_hstart, hip_stream, nullptr, nullptr, nullptr, &dn);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, atol, rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit, d_hstart)
+                        .sampled(ns, ts, d_ysample, d_nout),
+                    hip_stream);
 }
 
 int mistra_chem_rosenbrock_dense_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, double tstart,
                                           double tend, const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar,
                                           double* var_out, int32_t* ierr, int32_t* stats, double* t_h, int ns, const double* ts, double* ysample,
                                           int32_t* nout) {
-  if (int rc = check_dense(mech, tstart, tend, ns, ts, ysample, nout)) return rc;
-  const CellTol ct{atol, rtol, ntol};
-  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
-  const DenseOut dn{ns, ts, ysample, nout};
-  return rosenbrock_host(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h, nullptr, &ct, nullptr, &dn);
+  return single_host(ros_request(mech, ncell, var_in, fix, rconst, tstart, tend, atol, rtol, rpar, ipar, var_out, ierr, stats, t_h)
+                         .cells(ntol)
+                         .sampled(ns, ts, ysample, nout));
 }
 
 int mistra_chem_rosenbrock_dense_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, double tstart,
                                               double tend, const double* d_atol, const double* d_rtol, int ntol, const double* rpar,
                                               const int32_t* ipar, double* d_var_out, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                               const double* d_hstart, void* hip_stream, int ns, const double* ts, double* d_ysample, int32_t* d_nout) {
-  if (int rc = check_dense(mech, tstart, tend, ns, ts, d_ysample, d_nout)) return rc;
-  const CellTol ct{d_atol, d_rtol, ntol};
-  if (int rc = check_cell_tol(mech, ncell, ct, rpar, ipar)) return rc;
-  const DenseOut dn{ns, ts, d_ysample, d_nout};
-  return rosenbrock_on_device(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit,
-                              d_hstart, hip_stream, nullptr, &ct, nullptr, &dn);
+  return ros_device(ros_request(mech, ncell, d_var_in, d_fix, d_rconst, tstart, tend, d_atol, d_rtol, rpar, ipar, d_var_out, d_ierr, d_stats, d_texit_hexit, d_hstart)
+                        .cells(ntol)
+                        .sampled(ns, ts, d_ysample, d_nout),
+                    hip_stream);
 }
 
 // ---- series: nleg calls of Rosenbrock_x over times[0 .. nleg] in one launch, the state on chip from leg to leg (kernel VARIANT 5).  One path for the
@@ -3319,210 +3110,196 @@ static int check_nodes(const double* rconst_nodes) {
   return 0;
 }
 
-// one device slot's share of mistra_chem_rosenbrock_series_ex: cells [start, start + ncell) of the caller's batch of `total` cells
-static int series_host_on(DeviceState& D, int mech, int ncell, size_t start, size_t total, const double* var_in, const double* fix, const double* rconst,
-                          int rconst_legs, int fix_legs, int nleg, const double* times, const RosCall& call, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
-                          int32_t* stats, double* t_h, bool lin, double* flux_series) {
-  HIP_TRY(hipSetDevice(D.id));
-  MechState& S = D.mech[mech];
-  if (lin) rconst_legs = nleg + 1;      // the node blocks: one more than there are legs
-  const size_t nv = (size_t)kMech[mech].dims.nvar, nf = (size_t)kMech[mech].dims.nfix, nr = (size_t)kMech[mech].dims.nreact, nc = (size_t)ncell, nl = (size_t)nleg;
-  const size_t nb = call.block.size();
-  HIP_TRY(S.s_var.reserve(nc * nv));
-  const size_t nlf = (size_t)fix_legs, nlr = (size_t)rconst_legs;
-  HIP_TRY(S.s_fix.reserve(nlf * nc * nf));
-  HIP_TRY(S.s_rct.reserve(nlr * nc * nr));
-  HIP_TRY(S.s_ser_var.reserve(nl * nc * nv));
-  HIP_TRY(S.s_ser_ierr.reserve(nl * nc));
-  HIP_TRY(S.s_ser_stats.reserve(nl * nc * 8));
-  if (t_h) HIP_TRY(S.s_ser_th.reserve(nl * nc * 3));
-  if (flux_series) HIP_TRY(S.s_ser_flux.reserve(nl * nc * nr));
-  HIP_TRY(S.call_opt.reserve(nb + nl + 1));
-  HIP_TRY(hipMemcpy(S.s_var.p, var_in + start * nv, nc * nv * sizeof(double), hipMemcpyHostToDevice));
-  // the slot's cells of every block of fix and rconst, [legs][total][.] of the caller's into [legs][nc][.] here: one 2-D copy each (one block: one row)
-  HIP_TRY(hipMemcpy2D(S.s_fix.p, nc * nf * sizeof(double), fix + start * nf, total * nf * sizeof(double), nc * nf * sizeof(double), nlf, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy2D(S.s_rct.p, nc * nr * sizeof(double), rconst + start * nr, total * nr * sizeof(double), nc * nr * sizeof(double), nlr, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(S.call_opt.p, call.block.data(), nb * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(S.call_opt.p + nb, times, (nl + 1) * sizeof(double), hipMemcpyHostToDevice));
-  KernelArgs a = make_args(S, ncell, S.s_var.p, S.s_fix.p, S.s_rct.p, times[0], times[nleg], S.s_ser_var.p, S.s_ser_ierr.p, S.s_ser_stats.p, t_h ? S.s_ser_th.p : nullptr);
-  if (t_h) a.h_last = S.s_ser_th.p + 2 * nl * nc;      // device: [nleg][ncell][2] (T, Hexit) then [nleg][ncell] (H)
-  a.opt = S.call_opt.p;
-  a.max_steps = call.max_steps;
-  a.times = S.call_opt.p + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
-  a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
-  a.leg_rconst = rconst_legs > 1 ? (int64_t)(nc * nr) : 0; a.leg_fix = fix_legs > 1 ? (int64_t)(nc * nf) : 0;      // the block's stride, not the caller's
-  a.lin_rates = lin ? 1 : 0;
-  if (flux_series) { a.flux = S.s_ser_flux.p; a.leg_flux = (int64_t)(nc * nr); }      // selects the series kernels with the flux (launch)
-  if (int rc = upload_cell_tol(S, call, start, nc, &a)) return rc;
-  if (hstart) {
-    HIP_TRY(S.s_hst.reserve(nc));
-    HIP_TRY(hipMemcpy(S.s_hst.p, hstart + start, nc * sizeof(double), hipMemcpyHostToDevice));
-    a.hstart = S.s_hst.p;
+// ---- the two paths of every request.  What the families check before anything touches a device keeps each family's own order of refusals: the shared
+//      paths run this first and repeat the generic tests behind it.
+static int check_request(const RosRequest& q, bool device) {
+  if (!q.options) return q.env && known_mech(q.mech) && kMech[q.mech].user ? fail_user_slot(q.mech, "rate table") : 0;      // (mistra_chem_integrate_hstart_ex with env)
+  const bool null_options = !q.atol || !q.rtol || !q.rpar || !q.ipar;
+  if (q.series) {
+    if (int rc = check_series(q.mech, q.nleg, q.times, q.var_out, q.rconst_legs, q.fix_legs, q.wants_flux, q.flux)) return rc;
+    if (q.lin)
+      if (int rc = check_nodes(q.rconst)) return rc;
+  } else if (q.replay) {
+    if (int rc = check_replay(q, !device || !q.own_rows())) return rc;
+    if (device && !q.own_rows() && q.nsteps[0] > MISTRA_REPLAY_MAX_SHARED)
+      return fail("replay: nsteps[0] = " + std::to_string(q.nsteps[0]) + ": a shared sequence of the device entries holds at most MISTRA_REPLAY_MAX_SHARED = " +
+                  std::to_string(MISTRA_REPLAY_MAX_SHARED) + " steps (it travels in the call's block); give every cell its row");
+  } else if (q.trace) {
+    if (int rc = builtin_only(q.mech, "step-control trace")) return rc;
+    if (!q.per_cell && null_options) return fail("null options pointer");
+  } else if (q.wants_flux) {
+    if (int rc = check_flux(q.mech, q.flux)) return rc;
+  } else if (q.dense) {
+    if (int rc = check_dense(q.mech, q.tstart, q.tend, q.ns, q.ts, q.ysample, q.nout)) return rc;
+  } else if (int rc = user_slot_method(q.mech, q.ipar)) {
+    return rc;
   }
-  if (int rc = launch(D, mech, a, nullptr, call.method)) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  // the slot's [nleg][nc] blocks into the caller's [nleg][total] arrays
-  HIP_TRY(hipMemcpy2D(var_series + start * nv, total * nv * sizeof(double), S.s_ser_var.p, nc * nv * sizeof(double), nc * nv * sizeof(double), nl, hipMemcpyDeviceToHost));
-  if (ierr) HIP_TRY(hipMemcpy2D(ierr + start, total * sizeof(int32_t), S.s_ser_ierr.p, nc * sizeof(int32_t), nc * sizeof(int32_t), nl, hipMemcpyDeviceToHost));
-  if (stats)
-    HIP_TRY(hipMemcpy2D(stats + start * 8, total * 8 * sizeof(int32_t), S.s_ser_stats.p, nc * 8 * sizeof(int32_t), nc * 8 * sizeof(int32_t), nl, hipMemcpyDeviceToHost));
-  if (flux_series)
-    HIP_TRY(hipMemcpy2D(flux_series + start * nr, total * nr * sizeof(double), S.s_ser_flux.p, nc * nr * sizeof(double), nc * nr * sizeof(double), nl, hipMemcpyDeviceToHost));
-  if (t_h) {
-    std::vector<double> h(nl * nc * 3);
-    HIP_TRY(hipMemcpy(h.data(), S.s_ser_th.p, nl * nc * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < nl; k++)
-      for (size_t c = 0; c < nc; c++) {
-        double* o = t_h + (k * total + start + c) * 3;
-        o[0] = h[(k * nc + c) * 2]; o[1] = h[(k * nc + c) * 2 + 1]; o[2] = h[2 * nl * nc + k * nc + c];
-      }
+  if (q.per_cell)
+    if (int rc = check_cell_tol(q)) return rc;
+  if (q.trace)
+    if (int rc = check_trace_args(q)) return rc;
+  if ((q.series || q.replay) && null_options) return fail("null options pointer");      // (the single calls: behind check_call, in the paths)
+  return user_slot_method(q.mech, q.ipar);
+}
+
+// Rosenbrock_x refused the options: it returns before it touches Y or the statistics (gas.f:936-1053).  A result, nothing is launched: every leg (one
+// for the single calls) gets var = var_in, the code and zeros; no attempt was made and no sample reached, and the trace logs, ctrl and the replay's err
+// stay as they are.  Two writers: the host call's, and the device call's in stream order.
+static int refuse_host(const RosRequest& q, int code) {
+  const size_t nv = (size_t)kMech[q.mech].dims.nvar, nr = (size_t)kMech[q.mech].dims.nreact, nc = (size_t)q.ncell, n = q.legs() * nc;
+  for (size_t k = 0; k < q.legs(); k++)
+    if (q.var_out + k * nc * nv != q.var_in) std::memmove(q.var_out + k * nc * nv, q.var_in, nc * nv * sizeof(double));
+  if (q.ierr) std::fill(q.ierr, q.ierr + n, (int32_t)code);
+  if (q.stats) std::fill(q.stats, q.stats + n * 8, 0);
+  if (q.th) std::fill(q.th, q.th + n * 3, 0.0);
+  if (q.trace) std::fill(q.ntrace, q.ntrace + nc, 0);
+  if (q.flux) std::fill(q.flux, q.flux + n * nr, 0.0);
+  if (q.dense) {
+    std::fill(q.ysample, q.ysample + (size_t)q.ns * nc * nv, 0.0);
+    std::fill(q.nout, q.nout + nc, 0);
+  }
+  return 0;
+}
+static int refuse_stream(const RosRequest& q, int code, hipStream_t st) {
+  const size_t nv = (size_t)kMech[q.mech].dims.nvar, nr = (size_t)kMech[q.mech].dims.nreact, nc = (size_t)q.ncell, n = q.legs() * nc;
+  for (size_t k = 0; k < q.legs(); k++)
+    if (q.var_out + k * nc * nv != q.var_in) HIP_TRY(hipMemcpyAsync(q.var_out + k * nc * nv, q.var_in, nc * nv * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(q.ierr), code, n, st));
+  HIP_TRY(hipMemsetAsync(q.stats, 0, n * 8 * sizeof(int32_t), st));
+  if (q.th) HIP_TRY(hipMemsetAsync(q.th, 0, n * 2 * sizeof(double), st));
+  if (q.trace) HIP_TRY(hipMemsetAsync(q.ntrace, 0, nc * sizeof(int32_t), st));
+  if (q.flux) HIP_TRY(hipMemsetAsync(q.flux, 0, n * nr * sizeof(double), st));
+  if (q.dense) {
+    HIP_TRY(hipMemsetAsync(q.ysample, 0, (size_t)q.ns * nc * nv * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(q.nout, 0, nc * sizeof(int32_t), st));
   }
   return 0;
 }
 
-static int series_host(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs, int fix_legs, int nleg,
-                       const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int carry_h,
-                       const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h, const CellTol* ct, bool lin = false,
-                       bool sflux = false, double* flux_series = nullptr) {
-  if (int rc = check_series(mech, nleg, times, var_series, rconst_legs, fix_legs, sflux, flux_series)) return rc;
-  if (!sflux) flux_series = nullptr;      // (the flux of every leg is the entries' own that ask for it)
-  if (lin)
-    if (int rc = check_nodes(rconst)) return rc;
-  if (ct)
-    if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
-  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
+// Host buffers: the batch is split over the device slots (on_cell_blocks), each slot stages its cells, runs the kernel and fetches (ros_host_on).
+static int ros_host(const RosRequest& q) {
+  if (int rc = check_request(q, false)) return rc;
   if (int rc = lazy_init()) return rc;
-  if (int rc = check_call(mech, ncell)) return rc;
-  if (ncell == 0) return 0;
-  if (!var_in || !fix || !rconst) return fail("null host pointer");
-  std::lock_guard<std::mutex> lock(g_mu);
-  if (g_devs[0].mech[mech].pend.active) return step_is_open(mech);
-  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
-  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell, nl = (size_t)nleg;
-  if (call.ierr != 1) {      // nleg refused calls: var = var_in, the code, zeros; nothing is launched
-    for (size_t k = 0; k < nl; k++)
-      if (var_series + k * nc * nv != var_in) std::memmove(var_series + k * nc * nv, var_in, nc * nv * sizeof(double));
-    if (ierr) std::fill(ierr, ierr + nl * nc, (int32_t)call.ierr);
-    if (stats) std::fill(stats, stats + nl * nc * 8, 0);
-    if (t_h) std::fill(t_h, t_h + nl * nc * 3, 0.0);
-    if (flux_series) std::fill(flux_series, flux_series + nl * nc * (size_t)kMech[mech].dims.nreact, 0.0);
-    return 0;
+  if (int rc = check_call(q.mech, q.ncell, true)) return rc;
+  if (q.options && (!q.atol || !q.rtol || !q.rpar || !q.ipar)) return fail("null options pointer");
+  if (q.ncell == 0) return 0;
+  if (!q.var_in || !q.fix || !q.var_out || (!q.rconst && !q.env)) return fail("null host pointer");
+  std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slots' staging)
+  Slot t;
+  if (int rc = on_primary(q.mech, q.env ? kNeedRates : 0, true, &t)) return rc;
+  RosCall call;
+  std::vector<double> blk;
+  BlockLayout L;
+  if (q.options) {
+    call = decode_call(q);
+    if (call.ierr != 1) return refuse_host(q, call.ierr);
+    blk.resize(put_block(nullptr, call, q).words);
+    L = put_block(blk.data(), call, q);      // one upload per slot, read by the kernel through the options pointer
   }
-  // var_in may alias one leg's block of var_series: every slot has its inputs on the device before any result comes back (below: all uploads of a
-  // slot precede its downloads, and slots own disjoint cells)
-  return on_cell_blocks(ncell, [=, &call](DeviceState& D, size_t start, int count) {
-    return series_host_on(D, mech, count, start, nc, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, call, carry_h, hstart, var_series, ierr, stats, t_h, lin,
-                          flux_series);
+  if (q.record_sing)
+    for (auto& d : g_devs) d.mech[q.mech].sing_count = 0;
+  return on_cell_blocks(q.ncell, [&](DeviceState& D, size_t start, int count) {
+    return ros_host_on(D, q, q.options ? &call : nullptr, blk, L, start, (size_t)count);
   });
 }
 
-static int series_on_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int rconst_legs, int fix_legs,
-                            int nleg, const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
-                            double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart,
-                            void* hip_stream, const CellTol* ct, bool lin = false, bool sflux = false, double* d_flux_series = nullptr) {
-  if (int rc = check_series(mech, nleg, times, d_var_series, rconst_legs, fix_legs, sflux, d_flux_series)) return rc;
-  if (!sflux) d_flux_series = nullptr;
-  if (lin)
-    if (int rc = check_nodes(d_rconst)) return rc;
-  if (ct)
-    if (int rc = check_cell_tol(mech, ncell, *ct, rpar, ipar)) return rc;
-  if (!atol || !rtol || !rpar || !ipar) return fail("null options pointer");
-  if (ncell == 0) return check_call(mech, 0);
-  if (!d_var_in || !d_fix || !d_rconst || !d_ierr || !d_stats) return fail("null device pointer");
+// Device pointers: the buffers decide the device, the call is queued on the caller's stream and returns.  The kernel reads the caller's arrays in
+// stream order, no copy but the call's block: a plain call's in the slot's call_ring, one with a tail in series_ring, whose blocks have the room.
+static int ros_device(const RosRequest& q, void* hip_stream) {
+  if (int rc = check_request(q, true)) return rc;
+  if (q.ncell == 0) return check_call(q.mech, 0, true);
+  if (!q.atol || !q.rtol || !q.rpar || !q.ipar) return fail("null options pointer");
+  if (!q.var_in || !q.fix || !q.rconst || !q.var_out || !q.ierr || !q.stats) return fail("null device pointer");
   Slot t;
-  if (int rc = on_device(mech, ncell, d_var_in, "d_var_in", 0, &t)) return rc;
+  if (int rc = on_device(q.mech, q.ncell, q.var_in, "d_var_in", 0, &t)) return rc;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (ct)
-    if (int rc = check_tol_reachable(*ct, t.D->id)) return rc;
-  std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's ring of series blocks)
-  const RosCall call = decode_call(mech, ipar, rpar, atol, rtol, ct);
-  const size_t nv = (size_t)kMech[mech].dims.nvar, nc = (size_t)ncell, nl = (size_t)nleg;
-  if (call.ierr != 1) {      // nleg refused calls as results, in stream order; no kernel of the library runs
-    for (size_t k = 0; k < nl; k++)
-      if (d_var_series + k * nc * nv != d_var_in) HIP_TRY(hipMemcpyAsync(d_var_series + k * nc * nv, d_var_in, nc * nv * sizeof(double), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_ierr), call.ierr, nl * nc, st));
-    HIP_TRY(hipMemsetAsync(d_stats, 0, nl * nc * 8 * sizeof(int32_t), st));
-    if (d_texit_hexit) HIP_TRY(hipMemsetAsync(d_texit_hexit, 0, nl * nc * 2 * sizeof(double), st));
-    if (d_flux_series) HIP_TRY(hipMemsetAsync(d_flux_series, 0, nl * nc * (size_t)kMech[mech].dims.nreact * sizeof(double), st));
-    return 0;
-  }
-  const size_t nb = call.block.size();
-  RosCallRing& R = t.S->series_ring;
+  if (q.per_cell)
+    if (int rc = check_reachable({q.atol, q.rtol}, t.D->id, "d_atol / d_rtol are not device arrays on the cells' device")) return rc;
+  if (q.own_rows())
+    if (int rc = check_reachable({q.hsteps, q.nsteps}, t.D->id,
+                                 "replay: hsteps / nsteps with hrows = ncell are not device arrays on the cells' device (a shared sequence, hrows = 1, is a host array)"))
+      return rc;
+  std::lock_guard<std::mutex> lock(g_mu);      // (g_max_steps, the slot's rings of blocks)
+  const RosCall call = decode_call(q);
+  if (call.ierr != 1) return refuse_stream(q, call.ierr, st);
+  static_assert(MISTRA_DENSE_MAX_TIMES <= MISTRA_SERIES_MAX_LEGS + 1, "the sample times travel in a block of the series' ring");
+  static_assert(MISTRA_REPLAY_MAX_SHARED + 1 <= MISTRA_SERIES_MAX_LEGS + 1, "a shared sequence and its count travel in a block of the series' ring");
+  const bool tail = q.series || q.dense || q.replay;
+  RosCallRing& R = tail ? t.S->series_ring : t.S->call_ring;
   int i;
   double *hb, *db;
-  HIP_TRY(R.acquire(nb + (size_t)MISTRA_SERIES_MAX_LEGS + 1, &i, &hb, &db));
-  std::memcpy(hb, call.block.data(), nb * sizeof(double));
-  std::memcpy(hb + nb, times, (nl + 1) * sizeof(double));      // read here: the caller's array is free when the call returns
-  HIP_TRY(hipMemcpyAsync(db, hb, (nb + nl + 1) * sizeof(double), hipMemcpyHostToDevice, st));
-  KernelArgs a = make_args(*t.S, ncell, d_var_in, d_fix, d_rconst, times[0], times[nleg], d_var_series, d_ierr, d_stats, d_texit_hexit);
-  a.hstart = d_hstart;
-  a.opt = db;
-  a.max_steps = call.max_steps;
-  a.times = db + nb; a.nleg = nleg; a.carry_h = carry_h ? 1 : 0;
-  a.leg_var = (int64_t)(nc * nv); a.leg_ierr = (int64_t)nc; a.leg_stats = (int64_t)(nc * 8); a.leg_th = (int64_t)(nc * 2); a.leg_h = (int64_t)nc;
-  a.leg_rconst = rconst_legs > 1 || lin ? (int64_t)(nc * (size_t)kMech[mech].dims.nreact) : 0;      // the caller's arrays, read at the head of every leg
-  a.lin_rates = lin ? 1 : 0;      // (... of every evaluation: the node blocks, nleg + 1 of them)
-  a.leg_fix = fix_legs > 1 ? (int64_t)(nc * (size_t)kMech[mech].dims.nfix) : 0;
-  if (d_flux_series) { a.flux = d_flux_series; a.leg_flux = (int64_t)(nc * (size_t)kMech[mech].dims.nreact); }      // selects the series kernels with the flux (launch)
-  if (ct) set_cell_tol(&a, call, ct->atol, ct->rtol);      // the caller's device arrays, read by the kernel in stream order: no copy
-  const int rc = launch(*t.D, mech, a, st, call.method);
+  HIP_TRY(R.acquire(call.block.size() + (tail ? (size_t)MISTRA_SERIES_MAX_LEGS + 1 : 0), &i, &hb, &db));
+  const BlockLayout L = put_block(hb, call, q);
+  HIP_TRY(hipMemcpyAsync(db, hb, L.words * sizeof(double), hipMemcpyHostToDevice, st));
+  const double t0 = q.series ? q.times[0] : q.tstart, t1 = q.series ? q.times[q.nleg] : q.tend;
+  KernelArgs a = make_args(*t.S, q.ncell, q.var_in, q.fix, q.rconst, t0, t1, q.var_out, q.ierr, q.stats, q.th);
+  bind_request(&a, q, &call, db, L, (size_t)q.ncell, nullptr, nullptr);
+  const int rc = launch(*t.D, q.mech, a, st, call.method);
   R.mark(i, st);
   return rc;
+}
+
+static RosRequest series_request(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs, int fix_legs, int nleg,
+                                 const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int carry_h,
+                                 const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* th) {
+  return ros_request(mech, ncell, var_in, fix, rconst, 0.0, 0.0, atol, rtol, rpar, ipar, var_series, ierr, stats, th, hstart).over(nleg, times, carry_h, rconst_legs, fix_legs);
 }
 
 int mistra_chem_rosenbrock_series_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int nleg, const double* times,
                                      const double* atol, const double* rtol, const double* rpar, const int32_t* ipar, int carry_h, const double* hstart,
                                      double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
-  return series_host(mech, ncell, var_in, fix, rconst, 1, 1, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h, nullptr);
+  return ros_host(series_request(mech, ncell, var_in, fix, rconst, 1, 1, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h));
 }
 
 int mistra_chem_rosenbrock_series_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int nleg, const double* times,
                                            const double* atol, const double* rtol, int ntol, const double* rpar, const int32_t* ipar, int carry_h,
                                            const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
-  const CellTol ct{atol, rtol, ntol};
-  return series_host(mech, ncell, var_in, fix, rconst, 1, 1, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h, &ct);
+  return ros_host(series_request(mech, ncell, var_in, fix, rconst, 1, 1, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h).cells(ntol));
 }
 
 int mistra_chem_rosenbrock_series_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int nleg,
                                          const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                                          double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h,
                                          const double* d_hstart, void* hip_stream) {
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, 1, 1, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats, d_texit_hexit, carry_h,
-                          d_hstart, hip_stream, nullptr);
+  return ros_device(series_request(mech, ncell, d_var_in, d_fix, d_rconst, 1, 1, nleg, times, atol, rtol, rpar, ipar, carry_h, d_hstart, d_var_series, d_ierr, d_stats,
+                                   d_texit_hexit),
+                    hip_stream);
 }
 
 int mistra_chem_rosenbrock_series_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int nleg,
                                                const double* times, const double* d_atol, const double* d_rtol, int ntol, const double* rpar,
                                                const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                                int carry_h, const double* d_hstart, void* hip_stream) {
-  const CellTol ct{d_atol, d_rtol, ntol};
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, 1, 1, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr, d_stats, d_texit_hexit,
-                          carry_h, d_hstart, hip_stream, &ct);
+  return ros_device(series_request(mech, ncell, d_var_in, d_fix, d_rconst, 1, 1, nleg, times, d_atol, d_rtol, rpar, ipar, carry_h, d_hstart, d_var_series, d_ierr,
+                                   d_stats, d_texit_hexit)
+                        .cells(ntol),
+                    hip_stream);
 }
 
-// ---- the series with rate constants and FIX of the leg's own: the same path, the two counts the caller's
+// ---- the series with rate constants and FIX of the leg's own: the two counts the caller's
 int mistra_chem_rosenbrock_series_rates_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs, int fix_legs,
                                            int nleg, const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                                            int carry_h, const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
-  return series_host(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
-                     t_h, nullptr);
+  return ros_host(series_request(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
+                                 t_h));
 }
 
 int mistra_chem_rosenbrock_series_rates_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs,
                                                  int fix_legs, int nleg, const double* times, const double* atol, const double* rtol, int ntol,
                                                  const double* rpar, const int32_t* ipar, int carry_h, const double* hstart, double* var_series,
                                                  int32_t* ierr, int32_t* stats, double* t_h) {
-  const CellTol ct{atol, rtol, ntol};
-  return series_host(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
-                     t_h, &ct);
+  return ros_host(series_request(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
+                                 t_h)
+                      .cells(ntol));
 }
 
 int mistra_chem_rosenbrock_series_rates_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int rconst_legs,
                                                int fix_legs, int nleg, const double* times, const double* atol, const double* rtol, const double* rpar,
                                                const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                                int carry_h, const double* d_hstart, void* hip_stream) {
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats,
-                          d_texit_hexit, carry_h, d_hstart, hip_stream, nullptr);
+  return ros_device(series_request(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, d_hstart, d_var_series,
+                                   d_ierr, d_stats, d_texit_hexit),
+                    hip_stream);
 }
 
 int mistra_chem_rosenbrock_series_rates_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
@@ -3530,71 +3307,80 @@ int mistra_chem_rosenbrock_series_rates_cells_device(int mech, int ncell, const 
                                                      const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar, double* d_var_series,
                                                      int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart,
                                                      void* hip_stream) {
-  const CellTol ct{d_atol, d_rtol, ntol};
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr,
-                          d_stats, d_texit_hexit, carry_h, d_hstart, hip_stream, &ct);
+  return ros_device(series_request(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, carry_h, d_hstart,
+                                   d_var_series, d_ierr, d_stats, d_texit_hexit)
+                        .cells(ntol),
+                    hip_stream);
 }
 
-// ---- the series with rate constants linear in time over each leg (kernel VARIANT 10): the same path again, rconst_nodes holding
-//      nleg + 1 blocks, block k the rate constants AT times[k]; FIX stays piecewise constant (fix_legs = 1 or nleg)
+// ---- the series with rate constants linear in time over each leg (kernel VARIANT 10): rconst_nodes holds nleg + 1 blocks, block k
+//      the rate constants AT times[k]; FIX stays piecewise constant (fix_legs = 1 or nleg)
 int mistra_chem_rosenbrock_series_linrates_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst_nodes, int fix_legs, int nleg,
                                               const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                                               int carry_h, const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h) {
-  return series_host(mech, ncell, var_in, fix, rconst_nodes, 1, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h,
-                     nullptr, true);
+  return ros_host(series_request(mech, ncell, var_in, fix, rconst_nodes, 1, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h)
+                      .linear());
 }
 
 int mistra_chem_rosenbrock_series_linrates_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst_nodes, int fix_legs,
                                                     int nleg, const double* times, const double* atol, const double* rtol, int ntol, const double* rpar,
                                                     const int32_t* ipar, int carry_h, const double* hstart, double* var_series, int32_t* ierr,
                                                     int32_t* stats, double* t_h) {
-  const CellTol ct{atol, rtol, ntol};
-  return series_host(mech, ncell, var_in, fix, rconst_nodes, 1, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h,
-                     &ct, true);
+  return ros_host(series_request(mech, ncell, var_in, fix, rconst_nodes, 1, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats, t_h)
+                      .linear()
+                      .cells(ntol));
 }
 
 int mistra_chem_rosenbrock_series_linrates_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst_nodes, int fix_legs,
                                                   int nleg, const double* times, const double* atol, const double* rtol, const double* rpar,
                                                   const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                                   int carry_h, const double* d_hstart, void* hip_stream) {
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst_nodes, 1, fix_legs, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats,
-                          d_texit_hexit, carry_h, d_hstart, hip_stream, nullptr, true);
+  return ros_device(series_request(mech, ncell, d_var_in, d_fix, d_rconst_nodes, 1, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, d_hstart, d_var_series,
+                                   d_ierr, d_stats, d_texit_hexit)
+                        .linear(),
+                    hip_stream);
 }
 
 int mistra_chem_rosenbrock_series_linrates_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst_nodes,
                                                         int fix_legs, int nleg, const double* times, const double* d_atol, const double* d_rtol, int ntol,
                                                         const double* rpar, const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats,
                                                         double* d_texit_hexit, int carry_h, const double* d_hstart, void* hip_stream) {
-  const CellTol ct{d_atol, d_rtol, ntol};
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst_nodes, 1, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr, d_stats,
-                          d_texit_hexit, carry_h, d_hstart, hip_stream, &ct, true);
+  return ros_device(series_request(mech, ncell, d_var_in, d_fix, d_rconst_nodes, 1, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, carry_h, d_hstart, d_var_series,
+                                   d_ierr, d_stats, d_texit_hexit)
+                        .linear()
+                        .cells(ntol),
+                    hip_stream);
 }
 
-// ---- the series with the reaction flux of every leg (kernel VARIANT 11): the series with rates' path and arguments, flux_series
+// ---- the series with the reaction flux of every leg (kernel VARIANT 11): the series with rates' arguments, flux_series
 //      [nleg][ncell][NREACT] behind them, leg k's rows what mistra_chem_rosenbrock_flux_device returns for the call that leg k is
 int mistra_chem_rosenbrock_series_flux_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs, int fix_legs,
                                           int nleg, const double* times, const double* atol, const double* rtol, const double* rpar, const int32_t* ipar,
                                           int carry_h, const double* hstart, double* var_series, int32_t* ierr, int32_t* stats, double* t_h,
                                           double* flux_series) {
-  return series_host(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
-                     t_h, nullptr, false, true, flux_series);
+  return ros_host(series_request(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
+                                 t_h)
+                      .with_flux(flux_series));
 }
 
 int mistra_chem_rosenbrock_series_flux_cells_ex(int mech, int ncell, const double* var_in, const double* fix, const double* rconst, int rconst_legs,
                                                 int fix_legs, int nleg, const double* times, const double* atol, const double* rtol, int ntol,
                                                 const double* rpar, const int32_t* ipar, int carry_h, const double* hstart, double* var_series,
                                                 int32_t* ierr, int32_t* stats, double* t_h, double* flux_series) {
-  const CellTol ct{atol, rtol, ntol};
-  return series_host(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
-                     t_h, &ct, false, true, flux_series);
+  return ros_host(series_request(mech, ncell, var_in, fix, rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, hstart, var_series, ierr, stats,
+                                 t_h)
+                      .cells(ntol)
+                      .with_flux(flux_series));
 }
 
 int mistra_chem_rosenbrock_series_flux_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst, int rconst_legs,
                                               int fix_legs, int nleg, const double* times, const double* atol, const double* rtol, const double* rpar,
                                               const int32_t* ipar, double* d_var_series, int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit,
                                               int carry_h, const double* d_hstart, void* hip_stream, double* d_flux_series) {
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, d_var_series, d_ierr, d_stats,
-                          d_texit_hexit, carry_h, d_hstart, hip_stream, nullptr, false, true, d_flux_series);
+  return ros_device(series_request(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, atol, rtol, rpar, ipar, carry_h, d_hstart, d_var_series,
+                                   d_ierr, d_stats, d_texit_hexit)
+                        .with_flux(d_flux_series),
+                    hip_stream);
 }
 
 int mistra_chem_rosenbrock_series_flux_cells_device(int mech, int ncell, const double* d_var_in, const double* d_fix, const double* d_rconst,
@@ -3602,9 +3388,11 @@ int mistra_chem_rosenbrock_series_flux_cells_device(int mech, int ncell, const d
                                                     const double* d_rtol, int ntol, const double* rpar, const int32_t* ipar, double* d_var_series,
                                                     int32_t* d_ierr, int32_t* d_stats, double* d_texit_hexit, int carry_h, const double* d_hstart,
                                                     void* hip_stream, double* d_flux_series) {
-  const CellTol ct{d_atol, d_rtol, ntol};
-  return series_on_device(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, d_var_series, d_ierr,
-                          d_stats, d_texit_hexit, carry_h, d_hstart, hip_stream, &ct, false, true, d_flux_series);
+  return ros_device(series_request(mech, ncell, d_var_in, d_fix, d_rconst, rconst_legs, fix_legs, nleg, times, d_atol, d_rtol, rpar, ipar, carry_h, d_hstart,
+                                   d_var_series, d_ierr, d_stats, d_texit_hexit)
+                        .cells(ntol)
+                        .with_flux(d_flux_series),
+                    hip_stream);
 }
 
 int mistra_chem_cell_atol_device(int mech, int ncell, const double* d_var, double factor, double floor, double* d_atol, void* hip_stream) {

@@ -164,6 +164,31 @@ def test_l4_every_cell_reads_its_own_nodes(chem, ncell):
     assert np.array_equal(h.var, got_c.var) and np.array_equal(h.ierr, got_c.ierr) and np.array_equal(h.stats, got_c.stats) and np.array_equal(h.t_h[..., :2], got_c.t_h)
 
 
+def test_l4_two_device_slots_ragged_split(chem):
+    """init_devices([0, 0]), five gas cells over two slots (3 + 2), the host entry with two legs: every slot takes its own cells of the three node
+    blocks and of the two blocks of FIX — a strided upload of nleg + 1 and of nleg blocks — and of every leg's results.  Bit for bit one slot's."""
+    V3, LF, NK3 = _nodes("gas")
+    s = LR.series_set("gas", "m2")[0]
+    s = s._replace(times=np.ascontiguousarray(s.times[:3]))
+    idx = np.array([0, 1, 2, 1, 0])
+    V = V3[idx] * (1.0 + np.arange(5) / 1024.0).reshape(5, 1)                             # five different cells
+    F = np.ascontiguousarray(LF[:2, idx])                                                 # FIX per leg: [2, 5, NFIX]
+    NK = np.ascontiguousarray(NK3[:3, idx] * (1.0 + np.arange(5) / 2048.0).reshape(1, 5, 1))      # the nodes: [3, 5, NREACT]
+    one = _lin(chem, "gas", V, F, NK, s, host=True)
+    assert one.var.shape[:2] == (2, 5) and (one.ierr == 1).all()
+    assert len({one.var[-1, c].tobytes() for c in range(5)}) == 5      # (a cell handed to the wrong slot, or its rows from the wrong block, would show)
+    try:
+        chem.finalize()
+        chem.init_devices([0, 0])
+        assert chem.device_count() == 2
+        two = _lin(chem, "gas", V, F, NK, s, host=True)
+    finally:
+        chem.finalize()
+        chem.init(0)
+    for a, b, what in zip(two, one, ("var", "ierr", "stats", "t_h")):
+        assert a.tobytes() == b.tobytes(), what
+
+
 # ---- 5. user slots
 def test_l5_user_slots_fail_with_the_slots_text(chem):
     names = chem.user_mechs()

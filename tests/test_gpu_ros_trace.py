@@ -345,3 +345,51 @@ def test_t7_two_calls_queued_on_one_stream_keep_their_own_traces(chem):
         assert q.result_bytes() == want[name].result_bytes(), name
         for k in ("td", "ti", "nt", "ct"):
             assert getattr(q, k).tobytes() == getattr(want[name], k).tobytes(), (name, k)
+
+
+def test_t8_two_device_slots_ragged_split(chem):
+    """init_devices([0, 0]), five gas cells over two slots (3 + 2), the host entries with the shared pair and with rows per cell: every slot stages its
+    own rows of the caller's logs and of ctrl and hands them back.  cap is smaller than the longest cell's attempt count, the logs come in
+    filled with a sentinel: results, n, ctrl and the logs — the sentinel rows past min(n, cap) too — equal one slot's bit for bit.  Cell 2 of the
+    cells form is refused with -5, in the first slot's block: n = 0, its log rows and its ctrl row are the caller's."""
+    g = load_golden("gas")
+    V, F, K = (np.ascontiguousarray(g[k][:5]) for k in ("var_in", "fix", "rconst"))
+    n = 5
+    attempts = chem.rosenbrock_trace("gas", V, F, K, R.TIN, R.TOUT, cap=0)[2].n      # (n counts every attempt whatever the capacity)
+    lo, hi = int(attempts.min()), int(attempts.max())
+    cap = (lo + hi + 1) // 2 if lo < hi else hi - 1      # smaller than the longest cell's count; where the counts differ, larger than the shortest's
+    assert 0 < cap < hi, attempts.tolist()
+    at = np.array([[1.0e-25], [1.0e-20], [1.0e-22], [1.0e-18], [1.0e-24]])
+    rt = np.array([[1.0e-3], [1.0e-4], [1.0], [1.0e-2], [2.0e-3]])
+
+    def both():
+        got = []
+        for cells in (False, True):
+            td, ti = _poison((n, cap, 4), np.float64, 1000.25), _poison((n, cap, 2), np.int32, 5)
+            if cells:
+                res, th, tr = chem.rosenbrock_trace_cells("gas", V, F, K, R.TIN, R.TOUT, None, None, at, rt, cap=cap, trace_d=td, trace_i=ti)
+            else:
+                res, th, tr = chem.rosenbrock_trace("gas", V, F, K, R.TIN, R.TOUT, cap=cap, trace_d=td, trace_i=ti)
+            got.append({"var": res.var, "ierr": res.ierr, "stats": res.stats, "th": th, "td": td, "ti": ti, "n": tr.n, "ctrl": tr.ctrl})
+        return got
+
+    one = both()
+    sentinel_d, sentinel_i = _poison((n, cap, 4), np.float64, 1000.25), _poison((n, cap, 2), np.int32, 5)
+    plain, cells = one
+    assert (plain["ierr"] == 1).all() and np.array_equal(plain["n"], attempts) and (plain["n"] > cap).any()
+    assert cells["ierr"][2] == -5 and cells["n"][2] == 0 and (np.delete(cells["ierr"], 2) == 1).all() and (np.delete(cells["n"], 2) > 0).all()
+    assert np.array_equal(cells["td"][2], sentinel_d[2]) and np.array_equal(cells["ti"][2], sentinel_i[2]) and not cells["ctrl"][2].any()
+    for c in range(n):      # every kept row is written, every row past min(n, cap) is the sentinel's
+        k = min(int(plain["n"][c]), cap)
+        assert not np.isin(plain["ti"][c, :k], sentinel_i).any() and np.array_equal(plain["td"][c, k:], sentinel_d[c, k:]), c
+    try:
+        chem.finalize()
+        chem.init_devices([0, 0])
+        assert chem.device_count() == 2
+        two = both()
+    finally:
+        chem.finalize()
+        chem.init(0)
+    for a, b, form in zip(two, one, ("shared pair", "cells form")):
+        for k in a:
+            assert a[k].tobytes() == b[k].tobytes(), (form, k)
